@@ -74,6 +74,49 @@ def host_copy(dev_ptr, count, dtype):
     return out
 
 
+DUMP_LIMIT_BYTES = 64_000_000
+DUMP_SEED = 20240917
+DUMP_COUNTS = ("nrows", "products", "nnz_before_prune", "nnz", "nnz_diag", "nnz_upper", "max_numshared")
+DUMP_ENTRY_FIELDS = ("row", "col", "q0", "t0", "q1", "t1", "numshared")
+
+
+def dump_outputs(eng, st, outdir):
+    """--dump-outputs: what the last timed step handed its caller, as OUTDIR/<name>.npy in float64 (every value is an integer below 2^53).
+    counts: the step's statistics (DUMP_COUNTS); b_row_nnz: the number of entries of every row of B; b_<field>: every entry of a fixed
+    seeded sample of B's rows (rows in a seeded random order, as many as fit in DUMP_LIMIT_BYTES, then ascending; all of B when it fits),
+    one array per field of DUMP_ENTRY_FIELDS.  Returns a summary for the result line."""
+    v = eng.device_view()
+    M = int(v["M"])
+    row_nnz = np.diff(host_copy(v["b_rowptr"], M + 1, np.int64))
+    out = {"counts": np.array([st[key] for key in DUMP_COUNTS], dtype=np.float64), "b_row_nnz": row_nnz.astype(np.float64)}
+    header = 128                                                               # bytes of one .npy header
+    room = DUMP_LIMIT_BYTES - sum(a.nbytes + header for a in out.values()) - header * len(DUMP_ENTRY_FIELDS)
+    budget = max(0, room // (8 * len(DUMP_ENTRY_FIELDS)))                     # entries of B that fit
+    order = np.random.default_rng(DUMP_SEED).permutation(M)
+    nrows = int(np.searchsorted(np.cumsum(row_nnz[order]), budget, side="right"))
+    rows = np.sort(order[:nrows])
+    parts = {f: [] for f in DUMP_ENTRY_FIELDS}
+    runs = np.flatnonzero(np.diff(rows, prepend=-2) != 1).tolist() + [nrows]  # runs of consecutive rows: one export each
+    for a, b in zip(runs[:-1], runs[1:]):
+        lo, hi = int(rows[a]), int(rows[b - 1]) + 1
+        B = eng.export_csr(lo, hi)
+        parts["row"].append(np.repeat(np.arange(lo, hi, dtype=np.int64), np.diff(B["rowptr"])))
+        parts["col"].append(B["col"])
+        for f in DUMP_ENTRY_FIELDS[2:]:
+            parts[f].append(B["val"][f])
+    for f in DUMP_ENTRY_FIELDS:
+        out["b_" + f] = np.concatenate(parts[f]).astype(np.float64) if parts[f] else np.zeros(0, dtype=np.float64)
+    os.makedirs(outdir, exist_ok=True)
+    total = 0
+    for name, a in out.items():
+        path = os.path.join(outdir, name + ".npy")
+        np.save(path, a)
+        total += os.path.getsize(path)
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError("--dump-outputs wrote %d bytes, more than %d" % (total, DUMP_LIMIT_BYTES))
+    return {"dir": outdir, "bytes": total, "rows_sampled": nrows, "rows": M, "entries_sampled": int(len(out["b_row"])), "entries": int(v["Y"])}
+
+
 def host_memory_available():
     """bytes this process may still allocate: the smaller of MemAvailable and the cgroup's limit minus its usage"""
     avail = None
@@ -115,7 +158,13 @@ def main():
     ap.add_argument("--aux", action="store_true", help="N = 1: also run the stages on either side of the path once (FASTA ingest, x-drop alignment, string graph); "
                     "minutes on the 200 k-read set")
     ap.add_argument("--weak", action="store_true", help="N > 1: keep the per-GPU read count and grow the genome with N instead of sharding one read set")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="N = 1: after the timed steps, write what the last one computed (B: row sizes and a fixed "
+                    "seeded sample of its rows, and the step's counts) as DIR/<name>.npy, float64, at most 64 MB")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
 
     import torch
     import elba_amd
@@ -149,6 +198,8 @@ def main():
     w = WORKLOADS[args.workload]
     k, lo, up = w["k"], w["lower"], w["upper"]
     single = world == 1 and not force_dist
+    if args.dump_outputs and not single:
+        raise SystemExit("--dump-outputs needs the one-GPU path (--gpus 1)")
 
     def barrier_sync():
         if dist is not None:
@@ -211,6 +262,9 @@ def main():
     barrier_sync()
     dt = time.perf_counter() - t0
     st_cold = st
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(eng, st, args.dump_outputs)
     if dist is not None:
         tt = torch.tensor([dt], dtype=torch.float64, device="cuda")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -565,6 +619,7 @@ def main():
             "hbm_tier_forced": hbm_forced,
             "tiers": {key: int(st_cold[key]) for key in ("rows_lds", "rows_global", "rows_escalated", "nnz_before_prune", "passes") if key in st_cold},
             "aux_stages": aux,
+            "outputs_dumped": dumped,
             "gen_s": round(t_gen, 2),
         }
         try:                                     # RCCL prints its version banner through C stdio: flush it first so the JSON line is last

@@ -208,7 +208,62 @@ def read_kmer_vectors2(k, rng):
         fo.write("\n".join(rows) + "\n")
 
 
+def live_primitive_vectors():
+    """The inputs of tests/test_oracle_golden.py::test_live_against_reference_primitives (seed 99) and what the reference's DnaSeq::compress,
+    Kmer<1>::GetRepKmers and GetHash return for them: one line per read, `k ascii packed_hex kmers_hex hashes_of_the_first_five`."""
+    rng = np.random.default_rng(99)
+    rows = []
+    for k in (17, 31):
+        R = po.ref_lib(k)
+        for _ in range(20):
+            ln = int(rng.integers(k, 400))
+            s = bytes(rng.choice(list(b"ACGTNacgtn"), ln).tolist())
+            m = np.zeros((ln + 3) // 4 + 8, dtype=np.uint8)
+            R.ref_encode(s, ln, m.ctypes.data)
+            o = np.zeros(ln, dtype=np.uint64)
+            n = R.ref_kmers(m.ctypes.data, ln, o.ctypes.data, 1)
+            assert (o[n:] == 0).all()
+            hs = [R.ref_kmer_hash(C.byref(C.c_uint64(w))) for w in o[:5].tolist()]
+            rows.append("%d %s %s %s %s" % (k, s.decode(), m.tobytes().hex(), ",".join("%016x" % w for w in o[:n].tolist()) or "-",
+                                            ",".join("%016x" % h for h in hs) or "-"))
+    head = "# k ascii packed_hex canonical_kmers_hex murmur3_64_of_the_first_five   [reference DnaSeq::compress, Kmer<1>::GetRepKmers / GetHash]\n"
+    with gzip.GzipFile(os.path.join(HERE, "primitives_live.txt.gz"), "wb", compresslevel=9, mtime=0) as g:
+        g.write((head + "\n".join(rows) + "\n").encode())
+
+
+def live_xdrop_vectors():
+    """The inputs of tests/test_oracle_xdrop.py::test_oracle_xdrop_live_against_reference_build (seed 3: seeds of the oracle's B on small_err
+    with random scores, then random seeds that the aligner rejects) and what the reference's xdrop_aligner + classify_alignment return."""
+    import util
+    R = po.ref_lib(17)
+    rng = np.random.default_rng(3)
+    seqs = util.read_fasta(os.path.join(HERE, "small_err.fa"))
+    buf, off, lens = po.pack_reads(seqs)
+    o = po.Oracle(17, 2, 8); o.count_and_build(buf, off, lens); o.spgemm(1)
+    B = o.B()
+    rows = np.repeat(np.arange(B["M"]), np.diff(B["rowptr"]))
+    up = np.nonzero(rows < B["col"])[0]
+    cases = []
+    for e in rng.choice(up, size=min(300, len(up)), replace=False):
+        i, j = int(rows[e]), int(B["col"][e])
+        mat, mis, gap, x = int(rng.integers(1, 3)), -int(rng.integers(1, 4)), -int(rng.integers(1, 4)), int(rng.integers(0, 60))
+        cases.append((i, j, int(B["val"][e]["q0"]), int(B["val"][e]["t0"]), mat, mis, gap, x))
+    for _ in range(500):
+        i, j = (int(v) for v in rng.integers(0, len(seqs), 2))
+        q0, t0 = int(rng.integers(-2, lens[i] + 2)), int(rng.integers(-2, lens[j] + 2))
+        cases.append((i, j, q0, t0, 1, -1, -1, 15))
+    with open(os.path.join(HERE, "xdrop_live_small_err_k17.txt"), "w") as f:
+        f.write("# i j seedQ seedT mat mis gap xdrop -> ret begQ endQ begT endT score rc OverlapClass   (reference: src/XDropAligner.cpp, KMER_SIZE=17)\n")
+        for (i, j, a, b, mat, mis, gap, x) in cases:
+            out = po.ref_xdrop(R, buf[int(off[i]):], int(lens[i]), buf[int(off[j]):], int(lens[j]), a, b, mat, mis, gap, x)
+            f.write("%d %d %d %d %d %d %d %d %s\n" % (i, j, a, b, mat, mis, gap, x, " ".join(str(v) for v in out)))
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "live":           # only the stored answers of the two live cross-checks
+        assert po.ref_lib(17) is not None and po.ref_lib(31) is not None, "run `make -C oracle ref` first"
+        live_primitive_vectors(); live_xdrop_vectors()
+        return
     if len(sys.argv) > 1 and sys.argv[1] == "kmers2":         # only the two-word k-mer vectors
         rng = np.random.default_rng(20261005)
         read_kmer_vectors2(33, rng); read_kmer_vectors2(63, rng); read_kmer_vectors2(65, rng); read_kmer_vectors2(95, rng)

@@ -1,6 +1,7 @@
 """CPU tests: the oracle (oracle/elba_oracle.c) against the committed golden vectors, which were produced by the
 REFERENCE's own compiled code (tests/golden/make_golden.py) or measured from it by the survey."""
 import ctypes as C
+import gzip
 import os
 
 import numpy as np
@@ -246,22 +247,32 @@ def test_column_hand_over_and_B_comparison():
             po.Oracle(m["k"], m["lower"], m["upper"]).set_csc(A["M"], A["N"], A["colptr"].astype(np.uint32), bad, 1)
 
 
-@pytest.mark.skipif(po.ref_lib(17) is None, reason="oracle/_ref not built (reference tree absent)")
 def test_live_against_reference_primitives():
-    """Random cross-check against the reference's compiled Kmer/DnaSeq/HashFuncs (only where oracle/_ref exists)."""
+    """Random cross-check against the reference's compiled Kmer/DnaSeq/HashFuncs: 20 random reads (seed 99) per k, with what the reference
+    returned for them stored in tests/golden/primitives_live.txt.gz (make_golden.py live); where oracle/_ref is built, recomputed live as well."""
     L = po.lib()
-    rng = np.random.default_rng(99)
-    for k in (17, 31):
-        R = po.ref_lib(k)
-        for _ in range(20):
-            ln = int(rng.integers(k, 400))
-            s = bytes(rng.choice(list(b"ACGTNacgtn"), ln).tolist())
-            m1 = np.zeros((ln + 3) // 4 + 8, dtype=np.uint8); m2 = m1.copy()
-            R.ref_encode(s, ln, m1.ctypes.data); L.orc_encode_read(s, ln, m2.ctypes.data)
+    rows = [line.split() for line in gzip.open(os.path.join(G, "primitives_live.txt.gz"), "rt") if line[0] != "#"]
+    assert [int(r[0]) for r in rows] == [17] * 20 + [31] * 20
+    refs = {k: po.ref_lib(k) for k in (17, 31)}
+    for k, s, packed, kmers, hashes in rows:
+        k, s = int(k), s.encode()
+        ln = len(s)
+        want_kmers = [] if kmers == "-" else [int(x, 16) for x in kmers.split(",")]
+        want_hashes = [] if hashes == "-" else [int(x, 16) for x in hashes.split(",")]
+        m2 = np.zeros((ln + 3) // 4 + 8, dtype=np.uint8)
+        L.orc_encode_read(s, ln, m2.ctypes.data)
+        assert m2.tobytes().hex() == packed
+        o2 = np.zeros(ln, dtype=np.uint64)
+        n2 = L.orc_read_kmers(m2.ctypes.data, ln, k, o2.ctypes.data)
+        assert n2 == len(want_kmers) and o2[:n2].tolist() == want_kmers and (o2[n2:] == 0).all()
+        assert [L.orc_kmer_hash(w) for w in o2[:5].tolist()] == want_hashes
+        R = refs[k]
+        if R is not None:
+            m1 = np.zeros_like(m2)
+            R.ref_encode(s, ln, m1.ctypes.data)
             assert (m1 == m2).all()
-            o1 = np.zeros(ln, dtype=np.uint64); o2 = o1.copy()
+            o1 = np.zeros(ln, dtype=np.uint64)
             n1 = R.ref_kmers(m1.ctypes.data, ln, o1.ctypes.data, 1)
-            n2 = L.orc_read_kmers(m2.ctypes.data, ln, k, o2.ctypes.data)
             assert n1 == n2 and (o1 == o2).all()
             for w in o1[:5].tolist():
                 x = C.c_uint64(w)
