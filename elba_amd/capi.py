@@ -77,6 +77,16 @@ class StringStats(C.Structure):
                 ("iterations", C.c_int32), ("reserved", C.c_int32), ("ms_total", C.c_float), ("ms_minplus", C.c_float)]
 
 
+class ContigStats(C.Structure):
+    _fields_ = [("nreads", C.c_int64), ("branches", C.c_int64), ("components", C.c_int64), ("used_components", C.c_int64), ("contigs", C.c_int64),
+                ("cycles", C.c_int64), ("contig_reads", C.c_int64), ("bases", C.c_int64), ("longest", C.c_int64), ("ms_total", C.c_float), ("ms_rank", C.c_float)]
+
+
+class Contigs(C.Structure):
+    _fields_ = [("n", C.c_int64), ("seq_off", C.c_void_p), ("seq", C.c_void_p), ("chain_off", C.c_void_p), ("chain_read", C.c_void_p),
+                ("chain_prefix", C.c_void_p), ("chain_strand", C.c_void_p)]
+
+
 class Overlaps(C.Structure):
     _fields_ = [("n", C.c_int64), ("rows", C.c_void_p), ("cols", C.c_void_p), ("vals", C.c_void_p)]
 
@@ -128,6 +138,7 @@ EXPORTED_SYMBOLS = [
     "elba_kmer_hash_owner", "elba_dist_value_histogram", "elba_dist_set_owner_ranges", "elba_dist_set_kmer_id_base", "elba_dist_count_owners", "elba_dist_fill_send", "elba_dist_packed_format", "elba_dist_fill_send_packed", "elba_dist_unpack_records", "elba_dist_count_records", "elba_dist_get_reliable_kmers", "elba_dist_copy_reliable_kmers",
     "elba_dist_set_global_kmers", "elba_dist_panel_counts", "elba_dist_panel_fill", "elba_dist_panel_counts_win", "elba_dist_panel_fill_win", "elba_dist_set_panel",
     "elba_seed_matrix_begin", "elba_seed_matrix_fill", "elba_seed_matrix_end", "elba_set_stream", "elba_seed_matrix_send", "elba_seed_matrix_recv", "elba_set_kmer_matrix_device", "elba_export_triples_device", "elba_get_stat", "elba_release_workspace",
+    "elba_generate_contigs", "elba_export_contigs", "elba_free_contigs", "elba_export_read_contigs",
 ]
 
 _lib = None
@@ -177,6 +188,10 @@ def load_library():
     L.elba_transitive_reduction.restype = i32; L.elba_transitive_reduction.argtypes = [vp, C.c_double, i32, C.POINTER(StringStats)]
     L.elba_export_string_graph.restype = i32; L.elba_export_string_graph.argtypes = [vp, C.POINTER(Overlaps)]
     L.elba_export_read_flags.restype = i32; L.elba_export_read_flags.argtypes = [vp, vp, i64]
+    L.elba_generate_contigs.restype = i32; L.elba_generate_contigs.argtypes = [vp, C.POINTER(ContigStats)]
+    L.elba_export_contigs.restype = i32; L.elba_export_contigs.argtypes = [vp, C.POINTER(Contigs)]
+    L.elba_free_contigs.restype = None; L.elba_free_contigs.argtypes = [C.POINTER(Contigs)]
+    L.elba_export_read_contigs.restype = i32; L.elba_export_read_contigs.argtypes = [vp, vp, i64]
     L.elba_export_dcsc.restype = i32; L.elba_export_dcsc.argtypes = [vp, i64, i64, i64, i64, C.POINTER(Dcsc)]
     L.elba_free_dcsc.restype = None; L.elba_free_dcsc.argtypes = [C.POINTER(Dcsc)]
     L.elba_export_csr.restype = i32; L.elba_export_csr.argtypes = [vp, i64, i64, C.POINTER(Csr)]
@@ -385,6 +400,35 @@ class Engine:
         f = np.zeros(int(nreads), dtype=np.uint8)
         self._check(self.L.elba_export_read_flags(self.h, f.ctypes.data, int(nreads)))
         return f
+
+    # --- contigs (src/ContigGeneration.cpp:18-51,110,376-457, one rank) ---
+    def generate_contigs(self):
+        """GenerateContigs on the string graph of the last transitive_reduction: branches dropped, paths walked from their smaller end."""
+        st = ContigStats()
+        self._check(self.L.elba_generate_contigs(self.h, C.byref(st)))
+        return _stats(st)
+
+    def export_contigs(self):
+        """{n, seqs (list of str, emission order), seq_off, chain_off, chain_read, chain_prefix, chain_strand}."""
+        o = Contigs()
+        self._check(self.L.elba_export_contigs(self.h, C.byref(o)))
+        try:
+            n = o.n
+            seq_off = _copy(o.seq_off, n + 1, np.int64)
+            chain_off = _copy(o.chain_off, n + 1, np.int64)
+            E = int(chain_off[-1]) if n else 0
+            raw = _copy(o.seq, int(seq_off[-1]) if n else 0, np.uint8).tobytes()
+            seqs = [raw[int(seq_off[i]):int(seq_off[i + 1])].decode("ascii") for i in range(n)]
+            return dict(n=n, seqs=seqs, seq_off=seq_off if n else np.zeros(1, np.int64), chain_off=chain_off if n else np.zeros(1, np.int64),
+                        chain_read=_copy(o.chain_read, E, np.int64), chain_prefix=_copy(o.chain_prefix, E, np.int32), chain_strand=_copy(o.chain_strand, E, np.uint8))
+        finally:
+            self.L.elba_free_contigs(C.byref(o))
+
+    def export_read_contigs(self, nreads):
+        """Contig index of every read of the graph; -1 for branches, isolated reads and reads on cycles."""
+        out = np.zeros(int(nreads), dtype=np.int64)
+        self._check(self.L.elba_export_read_contigs(self.h, out.ctypes.data, int(nreads)))
+        return out
 
     # --- outputs ---
     def export_csr(self, row_lo=0, row_hi=None):

@@ -335,6 +335,7 @@ int elba_set_overlaps(elba_ctx *ctx, int64_t nreads, const int64_t *rows, const 
 int elba_transitive_reduction(elba_ctx *ctx, double bad_read_cutoff, int fuzz, elba_string_stats *stats)
 {
     return guarded(ctx, [&](Ctx &c) {
+        c.have_contigs = false;                                     // a new S invalidates the contigs of the old one, whatever this call ends in
         stage_transitive_reduction(c, bad_read_cutoff, fuzz);
         if (stats) *stats = c.sstats;
     });
@@ -366,6 +367,56 @@ int elba_export_read_flags(elba_ctx *ctx, uint8_t *flags, int64_t nreads)
         ELBA_REQUIRE(nreads == c.tr_M && (flags || nreads == 0), ELBA_ERR_INVALID_ARG, "export_read_flags: need one byte per read of the graph");
         if (nreads) ELBA_HIP(hipMemcpyAsync(flags, c.tr_flags.p, (size_t)nreads, hipMemcpyDeviceToHost, c.stream));
         ELBA_HIP(hipStreamSynchronize(c.stream));
+    });
+}
+
+int elba_generate_contigs(elba_ctx *ctx, elba_contig_stats *stats)
+{
+    return guarded(ctx, [&](Ctx &c) {
+        stage_generate_contigs(c);
+        if (stats) *stats = c.cstats;
+    });
+}
+
+int elba_export_contigs(elba_ctx *ctx, elba_contigs_t *out)
+{
+    return guarded(ctx, [&](Ctx &c) {
+        ELBA_REQUIRE(out, ELBA_ERR_INVALID_ARG, "export_contigs: null output");
+        memset(out, 0, sizeof(*out));
+        ELBA_REQUIRE(c.have_S && c.have_contigs, ELBA_ERR_STATE, "export_contigs: no contigs of the current string graph (call elba_generate_contigs)");
+        const int64_t n = c.cg_n, E = c.cg_E, b = c.cg_bases;
+        elba_contigs_t o{};
+        o.n = n;
+        o.seq_off = host_alloc<int64_t>((size_t)n + 1); o.seq = host_alloc<char>((size_t)b); o.chain_off = host_alloc<int64_t>((size_t)n + 1);
+        o.chain_read = host_alloc<int64_t>((size_t)E); o.chain_prefix = host_alloc<int32_t>((size_t)E); o.chain_strand = host_alloc<uint8_t>((size_t)E);
+        *out = o;                                                   // (allocated before any copy: elba_free_contigs releases them if a copy fails)
+        hipStream_t s = c.stream;
+        ELBA_HIP(hipMemcpyAsync(o.seq_off, c.cg_soff.p, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, s));
+        ELBA_HIP(hipMemcpyAsync(o.chain_off, c.cg_coff.p, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, s));
+        if (b) ELBA_HIP(hipMemcpyAsync(o.seq, c.cg_seq.p, (size_t)b, hipMemcpyDeviceToHost, s));
+        if (E) {
+            ELBA_HIP(hipMemcpyAsync(o.chain_read, c.cg_eread.p, (size_t)E * 8, hipMemcpyDeviceToHost, s));
+            ELBA_HIP(hipMemcpyAsync(o.chain_prefix, c.cg_epre.p, (size_t)E * 4, hipMemcpyDeviceToHost, s));
+            ELBA_HIP(hipMemcpyAsync(o.chain_strand, c.cg_estr.p, (size_t)E, hipMemcpyDeviceToHost, s));
+        }
+        ELBA_HIP(hipStreamSynchronize(s));
+    });
+}
+
+void elba_free_contigs(elba_contigs_t *c)
+{
+    if (!c) return;
+    free(c->seq_off); free(c->seq); free(c->chain_off); free(c->chain_read); free(c->chain_prefix); free(c->chain_strand);
+    memset(c, 0, sizeof(*c));
+}
+
+int elba_export_read_contigs(elba_ctx *ctx, int64_t *contig_of_read, int64_t nreads)
+{
+    return guarded(ctx, [&](Ctx &c) {
+        ELBA_REQUIRE(c.have_S && c.have_contigs, ELBA_ERR_STATE, "export_read_contigs: no contigs of the current string graph (call elba_generate_contigs)");
+        ELBA_REQUIRE(nreads == c.tr_M && (contig_of_read || nreads == 0), ELBA_ERR_INVALID_ARG, "export_read_contigs: need one entry per read of the graph");
+        const std::vector<int32_t> h = download<int32_t>(c, c.cg_cid.p, (size_t)nreads);
+        for (int64_t v = 0; v < nreads; ++v) contig_of_read[v] = h[(size_t)v];
     });
 }
 
@@ -555,6 +606,9 @@ int elba_release_workspace(elba_ctx *ctx)
         ELBA_HIP(hipStreamSynchronize(c.stream));
         c.ws_a.release(); c.ws_b.release(); c.ws_c.release(); c.ws_d.release(); c.ws_e.release(); c.ws_f.release(); c.ws_g.release(); c.ws_h.release(); c.ws_sort.release();
         c.csr_words.release(); c.kid_of_entry.release();
+        c.cg_ptr.release(); c.cg_slot.release(); c.cg_kdeg.release(); c.cg_term.release(); c.cg_vinfo.release(); c.cg_ctr.release();   // contig scratch (the results stay)
+        c.cg_flag.release(); c.cg_cidx.release(); c.cg_nel.release(); c.cg_eoff.release();
+        for (int b = 0; b < 2; ++b) { c.cg_far[b].release(); c.cg_rank[b].release(); c.cg_mn[b].release(); }
         if (c.have_counts) { c.pre_ready = false; c.pre_consumed = true; }    // (the CSR sort keys / column ids of the entries are gone: create_kmer_matrix rebuilds them from the column pointers)
     });
 }
@@ -572,6 +626,12 @@ int elba_get_stat(elba_ctx *ctx, const char *name, int64_t *value)
         else if (!strcmp(name, "triples_path")) *value = c.triples_path;
         else if (!strcmp(name, "padded_columns")) *value = c.have_A && c.use_ell ? 1 : 0;
         else if (!strcmp(name, "gather_slots")) *value = c.have_A && c.use_ell ? c.ell_nslots : 0;
+        else if (!strcmp(name, "contig_count")) *value = c.have_contigs ? c.cstats.contigs : 0;          // the last elba_generate_contigs (0: none valid)
+        else if (!strcmp(name, "contig_cycles")) *value = c.have_contigs ? c.cstats.cycles : 0;
+        else if (!strcmp(name, "contig_reads")) *value = c.have_contigs ? c.cstats.contig_reads : 0;
+        else if (!strcmp(name, "contig_bases")) *value = c.have_contigs ? c.cstats.bases : 0;
+        else if (!strcmp(name, "contig_branches")) *value = c.have_contigs ? c.cstats.branches : 0;
+        else if (!strcmp(name, "contig_rank_us")) *value = c.have_contigs ? (int64_t)(c.cstats.ms_rank * 1000.0f) : -1;
         else if (!strcmp(name, "resident_bytes_A")) {
             int64_t b = 0;
             if (c.have_A) {

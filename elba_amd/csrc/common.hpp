@@ -290,6 +290,14 @@ struct Ctx {
     DevBuf tr_deg, tr_pas, tr_flags, tr_k0, tr_v0, tr_k1, tr_v1, tr_ptr, tr_sym, tr_src, tr_mark, tr_ctr, tr_sel, tr_out_rows, tr_out_cols, tr_out_vals;
     elba_string_stats sstats{};
 
+    // contigs (contig.hip): results (cid, eread, epre, estr, eboff, soff, coff, seq) survive elba_release_workspace, the rest is scratch
+    bool have_contigs = false;
+    int64_t cg_n = 0, cg_E = 0, cg_bases = 0;
+    DevBuf cg_ptr, cg_slot, cg_kdeg, cg_far[2], cg_rank[2], cg_mn[2], cg_term, cg_vinfo, cg_flag, cg_cidx, cg_nel, cg_eoff, cg_ctr;
+    DevBuf cg_cid, cg_eread, cg_epre, cg_estr, cg_eboff, cg_soff, cg_coff, cg_seq;
+    EventTimer cg_t_total, cg_t_rank;
+    elba_contig_stats cstats{};
+
     // workspaces
     DevBuf ws_scan, ws_sort, ws_a, ws_b, ws_c, ws_d, ws_e, ws_f;
     DevBuf ws_cursor;       // the gather-slot cursor of the k-mer stage's emit kernels (kmer_msd.hip)
@@ -348,6 +356,7 @@ void stage_align_seeds(Ctx &c, int mat, int mis, int gap, int dropoff);   // ali
 void stage_dist_set_all_reads(Ctx &c, const void *d_packed, int64_t packed_bytes, const void *d_byte_off, const void *d_len, int64_t nreads_total);   // align.hip
 void stage_set_overlaps(Ctx &c, int64_t nreads, const int64_t *rows, const int64_t *cols, const elba_overlap_t *vals, int64_t n);   // tr.hip
 void stage_transitive_reduction(Ctx &c, double bad_read_cutoff, int fuzz);   // tr.hip
+void stage_generate_contigs(Ctx &c);                                          // contig.hip
 void stage_dist_count_owners(Ctx &c, int nranks, uint64_t *counts_host);                                   // kmer.hip
 void stage_dist_value_histogram(Ctx &c, uint64_t *hist_host, int64_t nbins);
 void stage_ref_hash_owner(Ctx &c, const uint64_t *kmers_host, int64_t n, int nprocs, uint64_t *hash_host, int32_t *owner_host);

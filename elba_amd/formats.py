@@ -98,3 +98,13 @@ def write_paf(path, overlaps, names, lens, dcsc_order=False):
         for a in idx:
             i, j = int(overlaps["rows"][a]), int(overlaps["cols"][a])
             f.write(paf_line(overlaps["vals"][a], names[i], names[j], int(lens[i]), int(lens[j])) + "\n")
+
+
+def write_contigs_fasta(path, seqs, first=0):
+    """<prefix>.contigs.fa as parallel_write_contigs writes it (src/main.cpp:496-499): `>contig<i>` then the sequence, i counted from `first`
+    (the rank's offset from MPI_Exscan; 0 on one rank)."""
+    with open(path, "wb") as f:
+        for i, s in enumerate(seqs):
+            f.write(b">contig%d\n" % (i + first))
+            f.write(s.encode("ascii") if isinstance(s, str) else bytes(s))
+            f.write(b"\n")

@@ -18,6 +18,8 @@
 //   find_bad_reads / find_contained_reads / TransitiveReduction   src/main.cpp:305-312, src/TransitiveReduction.cpp:3-90
 //                                                                             elba::TransitiveReduction(R, cutoff): the prunes and the reduction in one
 //                                                                             call on the GPU -> elba::StringGraph (S + the two read lists)
+//   GenerateContigs / parallel_write_contigs   src/ContigGeneration.cpp:376-457, src/main.cpp:487-512   same names (one rank): the contigs are
+//                                                                             built on the GPU from the S left there
 //
 // Errors: the reference asserts/aborts; here every failing C-ABI status throws elba::Error (status + text).
 // There is no CPU path: constructing an engine without a GPU throws ELBA_ERR_NO_DEVICE.
@@ -371,6 +373,7 @@ public:
     std::vector<Overlap> vals;
     std::vector<int64_t> bad_reads, contained_reads;
     elba_string_stats stats{};
+    std::shared_ptr<detail::Engine> engine;  // S stays on the device for the contig stage
     int64_t getnnz() const { return (int64_t)vals.size(); }
 };
 
@@ -381,6 +384,7 @@ inline std::unique_ptr<StringGraph> TransitiveReduction(const DnaBuffer &myreads
 {
     auto S = std::make_unique<StringGraph>();
     S->numreads = R.numreads;
+    S->engine = R.engine;
     R.engine->check(elba_transitive_reduction(R.engine->ctx, bad_read_cutoff, fuzz, &S->stats));
     elba_overlaps_t o;
     R.engine->check(elba_export_string_graph(R.engine->ctx, &o));
@@ -402,6 +406,37 @@ inline std::unique_ptr<StringGraph> TransitiveReduction(const DnaBuffer &myreads
         if (flags[(size_t)v] & 2) S->contained_reads.push_back(v);
     }
     return S;
+}
+
+// GenerateContigs(S, mydna, dfd) — src/ContigGeneration.cpp:376-457 on one rank: branches (degree > 2) dropped, every path of >= 2 reads
+// walked from its smaller-id end, the contig built from the reads' prefixes; on the GPU, on the S that TransitiveReduction left there.
+// The reads are the ones the context was given (mydna on one rank).  Contigs in the reference's emission order.
+inline std::vector<std::string> GenerateContigs(StringGraph &S, const DnaBuffer &mydna, elba_contig_stats *stats = nullptr)
+{
+    if (!S.engine) throw Error(ELBA_ERR_STATE, "GenerateContigs: the string graph is not on a device");
+    if ((int64_t)mydna.size() != S.numreads) throw Error(ELBA_ERR_INVALID_ARG, "GenerateContigs: mydna does not hold the graph's reads");
+    elba_contig_stats st{};
+    S.engine->check(elba_generate_contigs(S.engine->ctx, &st));
+    if (stats) *stats = st;
+    elba_contigs_t c;
+    S.engine->check(elba_export_contigs(S.engine->ctx, &c));
+    std::vector<std::string> contigs;
+    contigs.reserve((size_t)c.n);
+    for (int64_t i = 0; i < c.n; ++i) contigs.emplace_back(c.seq + c.seq_off[i], (size_t)(c.seq_off[i + 1] - c.seq_off[i]));
+    elba_free_contigs(&c);
+    return contigs;
+}
+
+// parallel_write_contigs (src/main.cpp:487-512) on one rank: the Exscan offset is 0; the reference takes the name from
+// get_contigs_fasta_name() (<prefix>.contigs.fa), here it is an argument.
+inline void parallel_write_contigs(const std::vector<std::string> &contigs, const std::string &contigs_fname)
+{
+    std::stringstream contig_filecontents;
+    for (size_t i = 0; i < contigs.size(); ++i) contig_filecontents << ">contig" << i << "\n" << contigs[i] << "\n";
+    std::ofstream f(contigs_fname, std::ios::binary);
+    const std::string cfs = contig_filecontents.str();
+    f.write(cfs.data(), (std::streamsize)cfs.size());
+    if (!f) throw Error(ELBA_ERR_INVALID_ARG, "parallel_write_contigs: cannot write " + contigs_fname);
 }
 
 // ---- the reference's text outputs -------------------------------------------------------------------------------

@@ -292,6 +292,36 @@ int  elba_transitive_reduction(elba_ctx *ctx, double bad_read_cutoff, int fuzz, 
 int  elba_export_string_graph(elba_ctx *ctx, elba_overlaps_t *out);
 int  elba_export_read_flags(elba_ctx *ctx, uint8_t *flags, int64_t nreads);
 
+/* Contigs: GenerateContigs (src/ContigGeneration.cpp:18-51,110,376-457) on the S of elba_transitive_reduction, one rank.  Reads of degree > 2
+ * in S are branches and are dropped; the rest falls into paths, cycles and isolated reads; every path of >= 2 reads is walked from its
+ * smaller-id end, and its contig is the concatenation over the chain of the first `prefix` bases of each read (reverse-complemented when the
+ * strand bit is set): prefix = suffixT of the walk's S(cur, next), the whole read for the last one.  Contigs come in the reference's emission
+ * order (ascending start read).  Cycles emit nothing.  The reads 0 .. nreads-1 of the graph must be on the context: its own reads
+ * (elba_set_reads*, as many as the graph has) or the replicated set of elba_dist_set_all_reads; otherwise ELBA_ERR_STATE.  A prefix outside
+ * [0, len] (undefined behaviour in the reference) fails with ELBA_ERR_INVALID_ARG and leaves no contigs.  elba_transitive_reduction and
+ * every new read set invalidate the contigs.  The writer (formats.write_contigs_fasta, hostcpp parallel_write_contigs) writes ">contig<i>\n<seq>\n" per contig (src/main.cpp:496-499). */
+typedef struct {
+    int64_t nreads, branches, components;   /* components: CC's count on S without the branches' edges, size-1 components included (:51) */
+    int64_t used_components;                /* components of >= 2 reads (:110): contigs + cycles */
+    int64_t contigs, cycles, contig_reads, bases, longest;   /* contig_reads: chain elements; bases: sum of contig lengths; longest: in bases */
+    float   ms_total, ms_rank;              /* device time of the stage / the pointer-jumping rounds */
+} elba_contig_stats;
+
+typedef struct {
+    int64_t n;                 /* contigs, in the reference's emission order */
+    int64_t *seq_off;          /* [n+1] into seq */
+    char    *seq;              /* ASCII ACGT, not NUL-separated */
+    int64_t *chain_off;        /* [n+1] into the chain arrays */
+    int64_t *chain_read;       /* global read id */
+    int32_t *chain_prefix;     /* bases taken from that read */
+    uint8_t *chain_strand;     /* 1 = reverse complement */
+} elba_contigs_t;
+
+int  elba_generate_contigs(elba_ctx *ctx, elba_contig_stats *stats);
+int  elba_export_contigs(elba_ctx *ctx, elba_contigs_t *out);
+void elba_free_contigs(elba_contigs_t *c);
+int  elba_export_read_contigs(elba_ctx *ctx, int64_t *contig_of_read, int64_t nreads);  /* contig index of every read, -1: branch, singleton or cycle */
+
 int  elba_export_dcsc(elba_ctx *ctx, int64_t row_lo, int64_t row_hi, int64_t col_lo, int64_t col_hi, elba_dcsc_t *out);
 void elba_free_dcsc(elba_dcsc_t *d);
 int  elba_export_csr(elba_ctx *ctx, int64_t row_lo, int64_t row_hi, elba_csr_t *out);
