@@ -621,6 +621,11 @@ int elba_get_stat(elba_ctx *ctx, const char *name, int64_t *value)
         else if (!strcmp(name, "overlap_slab_q16")) *value = (int64_t)c.ov_slab_q16_used;
         else if (!strcmp(name, "kmer_path")) *value = c.kmer_path;
         else if (!strcmp(name, "kmer_passes")) *value = c.kmer_passes;      // value-range passes the last elba_count_kmers took (1: the whole input at once)
+        else if (!strcmp(name, "kmer_crowded_buckets")) *value = c.kmer_crowded;      // buckets the last elba_count_kmers gave up to a crowded path (wide: k31_count's crowded parents; k <= 17: k_msd_bucket's)
+        else if (!strcmp(name, "kmer_crowded_small")) *value = c.kmer_crowded_small;      // wide crowded parents whose folded entry count lies in (0, small_cap]: what the main emit classes would take
+        else if (!strcmp(name, "kmer_largest_pass")) *value = c.kmer_largest_pass;      // instances of the last elba_count_kmers' largest value-range pass (I when unbatched)
+        else if (!strcmp(name, "overlap_passes")) *value = c.ov_passes;      // passes the last create_seed_matrix took (1: no repeat; set also when the call failed)
+        else if (!strcmp(name, "overlap_forwarded")) *value = c.ov_forwarded;      // rows the last create_seed_matrix forwarded to a larger tier on a prediction, all passes
         else if (!strcmp(name, "spgemm_prep_us")) *value = c.prep_us;      // (option "measure_prep"; -1: not measured — the option was off, or the path taken has no emit kernels of its own)
         else if (!strcmp(name, "emit_us")) *value = c.emit_us;
         else if (!strcmp(name, "triples_path")) *value = c.triples_path;

@@ -202,6 +202,7 @@ struct Ctx {
     bool have_counts = false;
     int triples_path = 0; // diagnostic: how the last elba_set_kmer_matrix_device built the matrix — 0 radix sorts of the whole matrix (matrix.hip), 1 the k-mer stage's bucket kernels (kmer_msd.hip)
     int kmer_passes = 1;  // diagnostic: value-range passes of the last elba_count_kmers (kmer_msd.hip)
+    int64_t kmer_crowded = 0, kmer_crowded_small = 0, kmer_largest_pass = 0;      // diagnostic: the last elba_count_kmers' crowded buckets, wide ones of them with a folded entry count in (0, small_cap], instances of its largest pass (kmer_msd.hip)
     int kmer_path = 0;    // diagnostic: how the last elba_count_kmers counted — 0 the sort of kmer.hip, 1 two-level partition + LDS count tables (k <= 17), 2 the same on 16-byte records + LDS sort (19 <= k <= 31)
     int64_t I = 0, ndistinct = 0;
     DevBuf inst_off;      // u64[M+1] instance offset of each read
@@ -319,6 +320,7 @@ struct Ctx {
     bool ov_slab_on = false;        // the running call has slabs (ov_launch_finalize reads them)
     uint32_t ov_slab_q16_used = 0;  // diagnostic: the ratio the last call's slabs were sized by (margin included), 0 = none
     int64_t ov_mir_placed = 0;      // diagnostic: mirrored entries of the last call that did NOT go to a slab (placed by k_mirror)
+    int64_t ov_passes = 0, ov_forwarded = 0;      // diagnostic: passes the last call took (1 = no repeat); rows its numeric kernels forwarded on a prediction (spgemm_direct.hpp)
     // sharded call with mirror exchange (spgemm.hip: stage_seed_matrix_begin / _fill / _end)
     int ov_phase = 0;               // 1: begin has run (numeric done, staged records waiting), end not yet
     int ov_pend_passes = 1; bool ov_pend_timed = false; float ov_pend_ms[3] = {0, 0, 0};

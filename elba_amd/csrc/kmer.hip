@@ -551,6 +551,7 @@ void stage_count_kmers(Ctx &c)
     // (more than 2^32 instances: the two-level partition of kmer_msd.hip counts them in passes over value ranges — k <= 17; every other path holds 32-bit places)
     ELBA_REQUIRE(I < 0xFFFFFFF0ull || (k <= 17 && k >= 9 && !c.opt.kmer_no_msd), ELBA_ERR_UNSUPPORTED, "count_kmers: more than 2^32 k-mer instances on one GPU (k <= 17 only)");
     c.I = (int64_t)I; c.kmer_passes = 1;
+    c.kmer_crowded = 0; c.kmer_crowded_small = 0; c.kmer_largest_pass = (int64_t)I;
     c.inst_off.reserve((size_t)(M + 1) * 8);
     ELBA_HIP(hipMemcpyAsync(c.inst_off.p, off.data(), (size_t)(M + 1) * 8, hipMemcpyHostToDevice, s));
 

@@ -1747,6 +1747,12 @@ __global__ void k31_fold_pseudo(const uint32_t *bN2, const uint32_t *bZ2, const 
     const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j < np) { const uint32_t b = clist[parent_of[j]]; atomicAdd(&bN[b], bN2[j]); atomicAdd(&bZ[b], bZ2[j]); }
 }
+// a crowded parent's entries: folded (what the scan over the buckets took) and as the main emit sees them (zero: k31_count gave the bucket up)
+__global__ void k31_parent_counts(const uint32_t *clist, uint32_t nc, const uint32_t *bZ_folded, const uint32_t *bZ, uint32_t *out)
+{
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p < nc) { const uint32_t b = clist[p]; out[p] = bZ_folded[b]; out[nc + p] = bZ[b]; }
+}
 __global__ void k31_pseudo_bases(const uint32_t *kidbase, const uint32_t *entbase, const uint32_t *clist, const uint32_t *pbase, uint32_t nc, const uint32_t *bN2, const uint32_t *bZ2, uint32_t *kidbase2, uint32_t *entbase2)
 {
     const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1892,10 +1898,11 @@ static bool msd_run(Ctx &c, uint64_t I, elba_kmer_stats *stp, MsdTriples *tri)
     const bool batched = !wide && !tri && I > batch_cap;
     if (!batched && I >= 0xFFFFFFF0ull) return false;      // (the caller refuses: the sort, the wide partition and the triples hold 32-bit places)
     ELBA_REQUIRE((I + tile - 1) / tile < 0xFFFFFFF0ull, ELBA_ERR_UNSUPPORTED, "count_kmers: more than 2^45 k-mer instances");
-    const uint64_t Ibuf = batched ? std::min<uint64_t>(I, batch_cap + (I >> (m.b1 - 1)) + (1u << 20)) : I;      // (a pass: the cap, or one digit beyond it — a digit holds ~2 I / 2^b1 at most on canonical k-mers; checked per pass below)
     const uint32_t ntiles1 = (uint32_t)((I + tile - 1) / tile), ntiles2 = ntiles1 + nb1;
 
-    c.ws_a.reserve((size_t)(Ibuf + 2) * (wide ? 16 : 8)); c.ws_c.reserve((size_t)(Ibuf + 2) * (wide ? 16 : 8));
+    // (value-range batching: a pass takes whole first digits — one digit may hold most of the input: a homopolymer, AT-rich reads —, the two partition
+    //  buffers are sized by the largest pass once the passes are planned, below, and every pass is checked against them)
+    if (!batched) { c.ws_a.reserve((size_t)(I + 2) * (wide ? 16 : 8)); c.ws_c.reserve((size_t)(I + 2) * (wide ? 16 : 8)); }
     c.ws_sort.reserve(((size_t)ntiles2 << (wide ? W2_MAXBITS : MT_MAXBITS)) * 4 + 4096);
     c.ws_e.reserve((size_t)(nbuckets + 2) * 4 * 6 + (size_t)(2 * nb1 + 8) * 4 + 256 + 64 + (size_t)(ntiles2 + 4) * 8);
     uint32_t *hist = c.ws_sort.as<uint32_t>();
@@ -1926,17 +1933,20 @@ static bool msd_run(Ctx &c, uint64_t I, elba_kmer_stats *stp, MsdTriples *tri)
         ELBA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k31_count), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     });
     // pseudo-buckets of the wide partition's crowded buckets (the section above k31_gather_crowded)
-    struct { bool on = false; uint32_t nc = 0, np = 0; const uint64_t *words = nullptr; uint64_t *wrel = nullptr; uint32_t *b2s = nullptr, *bN = nullptr, *bZ = nullptr, *kidbase = nullptr, *entbase = nullptr, *crowded = nullptr;
+    struct { bool on = false; uint32_t nc = 0, np = 0; const uint64_t *words = nullptr; uint64_t *wrel = nullptr; uint32_t *b2s = nullptr, *bN = nullptr, *bZ = nullptr, *kidbase = nullptr, *entbase = nullptr, *crowded = nullptr, *pz = nullptr;
              BucketStats *gstat = nullptr; const uint32_t *clist = nullptr, *pbase = nullptr; const uint64_t *cdist = nullptr; const uint32_t *dist_base = nullptr; BucketStats hs{}; } ps;
     // value-range batching (the section "VALUE-RANGE BATCHING" below): the passes, and what phase A learnt of each
     struct Pass { uint32_t dlo = 0, dhi = 0; uint64_t I = 0, N = 0, Z = 0; BucketStats hs{}; };
     std::vector<Pass> passes;
+    uint64_t largest = I;      // instances of the largest pass
     std::function<void(uint32_t, uint32_t, uint64_t, bool)> partition_count;
-    // k-mers and entries in front of every bucket (+ the totals), the count kernels' statistics: one host round trip
+    // k-mers and entries in front of every bucket (+ the totals), the count kernels' statistics: one host round trip.  The counts scanned are bN / bZ,
+    // or — crowded buckets of the wide partition — copies with the pseudo-buckets' counts folded in (the emit kernels read bZ: a crowded parent stays 0 there)
+    uint32_t *sN = bN, *sZ = bZ;
     auto scan_buckets = [&](BucketStats *hs_out, uint64_t *N_out, uint64_t *Z_out) {
-        ELBA_HIP(hipMemsetAsync(bN + nbuckets, 0, 4, s)); ELBA_HIP(hipMemsetAsync(bZ + nbuckets, 0, 4, s));
-        exclusive_scan_u32(s, bN, kidbase, (int64_t)nbuckets + 1, c.ws_scan);
-        exclusive_scan_u32(s, bZ, entbase, (int64_t)nbuckets + 1, c.ws_scan);      // (a pass holds fewer than 2^32 instances)
+        ELBA_HIP(hipMemsetAsync(sN + nbuckets, 0, 4, s)); ELBA_HIP(hipMemsetAsync(sZ + nbuckets, 0, 4, s));
+        exclusive_scan_u32(s, sN, kidbase, (int64_t)nbuckets + 1, c.ws_scan);
+        exclusive_scan_u32(s, sZ, entbase, (int64_t)nbuckets + 1, c.ws_scan);      // (a pass holds fewer than 2^32 instances)
         if (!hs_out) return;
         uint32_t h2[2] = {0, 0};
         ELBA_HIP(hipMemcpyAsync(&h2[0], kidbase + nbuckets, 4, hipMemcpyDeviceToHost, s));
@@ -1976,6 +1986,7 @@ static bool msd_run(Ctx &c, uint64_t I, elba_kmer_stats *stp, MsdTriples *tri)
     // The reads' instances whose FIRST digit lies in [dlo, dhi) — Iv of them; one pass: every instance —: two-level partition, then one workgroup per bucket
     // counts.  hist1 and the first scatter enumerate ALL reads (tiles of the whole instance range) and keep their pass's instances.
     partition_count = [&, shift2, sgrid](uint32_t dlo, uint32_t dhi, uint64_t Iv, bool timed) {
+        ELBA_REQUIRE(Iv + 2 <= std::min(c.ws_a.cap, c.ws_c.cap) / 8, ELBA_ERR_INTERNAL, "count_kmers: a value-range pass is larger than its partition buffers");
         const uint32_t nt2 = (uint32_t)((Iv + tile - 1) / tile) + nb1;
         if (timed) c.t_a.start(s);
         hipLaunchKernelGGL(k_msd_hist1, dim3(ntiles1), dim3(MT_THREADS), 0, s, e, bi, m, hist, dlo, dhi);
@@ -2036,6 +2047,11 @@ static bool msd_run(Ctx &c, uint64_t I, elba_kmer_stats *stp, MsdTriples *tri)
             if (ps1.I) passes.push_back(ps1);
         }
         if (c.opt.trace) fprintf(stderr, "[elba] count_kmers: %llu instances in %zu value-range passes\n", (unsigned long long)I, passes.size());
+        largest = 0;
+        for (const Pass &ps1 : passes) largest = std::max(largest, ps1.I);
+        c.kmer_largest_pass = (int64_t)largest;
+        c.ws_a.reserve((size_t)(largest + 2) * 8); c.ws_c.reserve((size_t)(largest + 2) * 8);
+        wa = c.ws_a.as<uint64_t>(); wb = c.ws_c.as<uint64_t>();
         for (Pass &ps1 : passes) {
             partition_count(ps1.dlo, ps1.dhi, ps1.I, false);
             scan_buckets(&ps1.hs, &ps1.N, &ps1.Z);
@@ -2110,9 +2126,10 @@ static bool msd_run(Ctx &c, uint64_t I, elba_kmer_stats *stp, MsdTriples *tri)
             for (uint32_t q = 0; q < nc; ++q) { pbase[q] = np; np += (uint32_t)(((uint64_t)(dfirst[q + 1] - dfirst[q]) + (1u << pshift) - 1u) >> pshift); }
             pbase[nc] = np;
             ELBA_HIP(hipMemcpyAsync(pbase_d, pbase.data(), ((size_t)nc + 1) * 4, hipMemcpyHostToDevice, s));
-            c.ws_h.reserve(((size_t)np + 4) * 4 * 9 + sizeof(BucketStats) + 256);
+            c.ws_h.reserve(((size_t)np + 4) * 4 * 9 + ((size_t)nbuckets + 2) * 4 * 2 + ((size_t)nc + 2) * 4 * 2 + sizeof(BucketStats) + 256);
             uint32_t *b2s = c.ws_h.as<uint32_t>() + 64, *parent_of = b2s + (np + 4), *dist_base = parent_of + (np + 4), *bN2 = dist_base + (np + 4), *bZ2 = bN2 + (np + 4),
                      *kidbase2 = bZ2 + (np + 4), *entbase2 = kidbase2 + (np + 4), *crowded2 = entbase2 + (np + 4);
+            uint32_t *bNf = crowded2 + (np + 4), *bZf = bNf + (nbuckets + 2), *pz = bZf + (nbuckets + 2);      // (the counts the scan takes; the parents' counts for the host)
             BucketStats *gstat2 = c.ws_h.as<BucketStats>();
             static_assert(sizeof(BucketStats) <= 256, "the pseudo-buckets' statistics sit in front of their arrays");
             hipLaunchKernelGGL(k31_crowded_words, dim3((unsigned)((Rc + 255) / 256)), dim3(256), 0, s, (const uint64_t *)sk, (const uint64_t *)sv, Rc, (const uint32_t *)head, (const uint32_t *)dpos, (const uint64_t *)coff_d,
@@ -2123,7 +2140,14 @@ static bool msd_run(Ctx &c, uint64_t I, elba_kmer_stats *stp, MsdTriples *tri)
             const unsigned pgrid = (unsigned)std::min<uint32_t>(np, (uint32_t)c.num_cus);
             if (m.rk) hipLaunchKernelGGL(k_msd_count<true>, dim3(pgrid), dim3(BK_THREADS), CT_LDS, s, (const uint64_t *)words2, (const uint32_t *)b2s, np, m, (uint32_t)c.cfg.lower, (uint32_t)c.cfg.upper, small_cap, bN2, bZ2, gstat2, crowded2, wrel2);
             else hipLaunchKernelGGL(k_msd_count<false>, dim3(pgrid), dim3(BK_THREADS), CT_LDS, s, (const uint64_t *)words2, (const uint32_t *)b2s, np, m, (uint32_t)c.cfg.lower, (uint32_t)c.cfg.upper, small_cap, bN2, bZ2, gstat2, crowded2, wrel2);
-            hipLaunchKernelGGL(k31_fold_pseudo, dim3((np + 255) / 256), dim3(256), 0, s, (const uint32_t *)bN2, (const uint32_t *)bZ2, (const uint32_t *)parent_of, (const uint32_t *)clist_d, np, bN, bZ);
+            // the folded counts go to copies that only the scan over the buckets reads: k31_count never wrote a crowded parent's entries to wa, the
+            // main emit kernels must keep finding bZ = 0 there (a parent of 0 < Z <= small_cap was once sorted and emitted from stale records,
+            // across its neighbours' columns)
+            ELBA_HIP(hipMemcpyAsync(bNf, bN, (size_t)nbuckets * 4, hipMemcpyDeviceToDevice, s));
+            ELBA_HIP(hipMemcpyAsync(bZf, bZ, (size_t)nbuckets * 4, hipMemcpyDeviceToDevice, s));
+            hipLaunchKernelGGL(k31_fold_pseudo, dim3((np + 255) / 256), dim3(256), 0, s, (const uint32_t *)bN2, (const uint32_t *)bZ2, (const uint32_t *)parent_of, (const uint32_t *)clist_d, np, bNf, bZf);
+            sN = bNf; sZ = bZf;
+            ps.pz = pz;
             ps.on = true; ps.nc = nc; ps.np = np; ps.words = words2; ps.wrel = wrel2; ps.b2s = b2s; ps.bN = bN2; ps.bZ = bZ2; ps.kidbase = kidbase2; ps.entbase = entbase2; ps.crowded = crowded2;
             ps.gstat = gstat2; ps.clist = clist_d; ps.pbase = pbase_d; ps.cdist = cdist; ps.dist_base = dist_base;
         }
@@ -2131,16 +2155,28 @@ static bool msd_run(Ctx &c, uint64_t I, elba_kmer_stats *stp, MsdTriples *tri)
     BucketStats hs{};
     uint64_t N = 0, Z = 0;
     unsigned long long nbad = 0;
+    int64_t ncrowded = 0, crowded_small = 0;      // (the statistics kmer_crowded_buckets / kmer_crowded_small)
     if (batched) {      // (phase A has scanned every pass: the totals, and what the layout of A depends on)
-        for (const Pass &ps1 : passes) { N += ps1.N; Z += ps1.Z; hs.distinct += ps1.hs.distinct; hs.sumsq += ps1.hs.sumsq; hs.maxcol = std::max(hs.maxcol, ps1.hs.maxcol); }
+        for (const Pass &ps1 : passes) { N += ps1.N; Z += ps1.Z; hs.distinct += ps1.hs.distinct; hs.sumsq += ps1.hs.sumsq; hs.maxcol = std::max(hs.maxcol, ps1.hs.maxcol); ncrowded += ps1.hs.ncrowded; }
     } else {
         if (tri) ELBA_HIP(hipMemcpyAsync(&nbad, one_seg + 4, 8, hipMemcpyDeviceToHost, s));
-        if (ps.on) ELBA_HIP(hipMemcpyAsync(&ps.hs, ps.gstat, sizeof(BucketStats), hipMemcpyDeviceToHost, s));
+        std::vector<uint32_t> pz;
+        if (ps.on) {
+            ELBA_HIP(hipMemcpyAsync(&ps.hs, ps.gstat, sizeof(BucketStats), hipMemcpyDeviceToHost, s));
+            pz.resize((size_t)ps.nc * 2);
+            hipLaunchKernelGGL(k31_parent_counts, dim3((ps.nc + 255) / 256), dim3(256), 0, s, ps.clist, ps.nc, (const uint32_t *)sZ, (const uint32_t *)bZ, ps.pz);
+            ELBA_HIP(hipMemcpyAsync(pz.data(), ps.pz, (size_t)ps.nc * 8, hipMemcpyDeviceToHost, s));
+        }
         scan_buckets(&hs, &N, &Z);
         if (ps.on) {
+            for (uint32_t p = 0; p < ps.nc; ++p) crowded_small += pz[p] > 0u && pz[p] <= small_cap ? 1 : 0;
+            c.kmer_crowded = ps.nc; c.kmer_crowded_small = crowded_small;      // (set before the check below: they describe the input)
+            for (uint32_t p = 0; p < ps.nc; ++p)
+                ELBA_REQUIRE(pz[ps.nc + p] == 0u, ELBA_ERR_INTERNAL, "count_kmers: a crowded bucket of the wide partition is visible to the main emit kernels");
             hipLaunchKernelGGL(k31_pseudo_bases, dim3((ps.nc + 255) / 256), dim3(256), 0, s, (const uint32_t *)kidbase, (const uint32_t *)entbase, ps.clist, ps.pbase, ps.nc, (const uint32_t *)ps.bN, (const uint32_t *)ps.bZ, ps.kidbase, ps.entbase);
             hs.distinct += ps.hs.distinct; hs.sumsq += ps.hs.sumsq; hs.maxcol = std::max(hs.maxcol, ps.hs.maxcol);
         }
+        ncrowded = ps.on ? ps.nc : hs.ncrowded;
         Pass whole{}; whole.dlo = 0; whole.dhi = nb1; whole.I = I; whole.N = N; whole.Z = Z; whole.hs = hs;
         passes.assign(1, whole);
     }
@@ -2323,6 +2359,7 @@ static bool msd_run(Ctx &c, uint64_t I, elba_kmer_stats *stp, MsdTriples *tri)
     c.N = (int64_t)N; c.Z = (int64_t)Z;
     c.kmer_path = wide ? 2 : 1;
     c.kmer_passes = (int)passes.size();
+    c.kmer_crowded = ncrowded; c.kmer_crowded_small = crowded_small; c.kmer_largest_pass = (int64_t)largest;
     return true;
 }
 

@@ -59,6 +59,7 @@ struct OvCounters {              // device-side counters, zeroed per call
     unsigned int fin_count[2];            // rows needing the workgroup bucket sort / the HBM-bitonic sort of their columns
     unsigned int slab_q16;                // mirror slabs: slab entries per row entry of A (x 65536) of this call, 0 = no slabs (k_classify_direct writes it: the sample's rows run before it is known)
     unsigned int ntick;                   // staged entries whose image took a ticket: the list k_mirror walks (OvParams::tick, 16-byte records)
+    unsigned int nforward;                // diagnostic: rows forwarded to a larger tier on a prediction (spgemm_direct.hpp, use_feedback)
     unsigned long long mir_placed;        // diagnostic: mirrored entries k_mirror placed (those that found no room in their row's slab, or had none)
     unsigned long long pad2[13];          // keep the feedback sums on a cache line of their own
     alignas(128) unsigned int sample_next[8][32];          // the same for the sample queue (below)
@@ -1022,6 +1023,7 @@ static void create_seed_matrix_direct(Ctx &c, int phase)
     hc = OvCounters{};
     uint32_t skipped_tiers = 0, skipped_sorts = 0;
     int passes = 0;
+    c.ov_passes = 0; c.ov_forwarded = 0;
     float ms_sym = 0, ms_num = 0, ms_fin = 0, ms_tot = 0;
     bool was_timed = true;
     for (;;) {
@@ -1092,8 +1094,9 @@ static void create_seed_matrix_direct(Ctx &c, int phase)
             // the highest tier ANY row of this matrix can reach: a row's distinct partners <= min(its entries x the longest column, reads), the tier that holds
             // twice that is guaranteed to fit it and k_classify_direct never starts a row above it.  A cold call on a small matrix launched five tiers
             // nobody could queue on (~5 us each, dependent: hifi-half 0.59 -> 0.53 ms with the finalize's counterpart).  (Still under the `missed` check below.)
+            // (a repeated pass launches every tier: whatever the first one missed, it cannot miss it again for want of a launch)
             int tmax = NUM_TIERS;
-            if (c.opt.tune[4] != 2) {
+            if (c.opt.tune[4] != 2 && passes == 1) {
                 const uint64_t ubm = std::min<uint64_t>((uint64_t)std::max<int64_t>(c.max_row_nnz, 1) * (uint64_t)p.max_col, (uint64_t)p.Mcols);
                 const int gmax = ubm <= 1 ? 1 : 64 - __builtin_clzll(2 * ubm - 1);
                 tmax = gmax <= LDS_TBITS0 ? 0 : gmax - LDS_TBITS0;
@@ -1158,6 +1161,7 @@ static void create_seed_matrix_direct(Ctx &c, int phase)
         ELBA_HIP(hipStreamSynchronize(s));
         if (timed) { ms_sym += c.ov_marks.ms(0, 1); ms_num += c.ov_marks.ms(1, 2); ms_fin = c.ov_marks.ms(2, 3); ms_tot += c.ov_marks.ms(0, 3); }
         was_timed = timed;
+        c.ov_passes = passes; c.ov_forwarded += hc.nforward;
         bool missed = false;
         for (int t = 0; t < NUM_TIERS; ++t) missed |= ((skipped_tiers >> t) & 1u) && hc.tier_count[t] > 0;
         missed |= ((skipped_sorts & 1u) && hc.fin_count[0] > 0) || ((skipped_sorts & 2u) && hc.fin_count[1] > 0);

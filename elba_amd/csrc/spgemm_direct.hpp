@@ -205,10 +205,14 @@ __global__ __launch_bounds__(BLOCK, SUFFIX ? ELBA_DENSE_OCC : (DK == 4 ? 1 : 4))
             fb_settled = gu >= p.fb_enough;
             if (gu >= (1ull << 18)) {
                 const double pred = 1.25 * (double)nnz * (double)gc / (double)gu;
-                if (pred > 1.2 * (double)p.tier_limit[tier] && guaranteed_tbits(ub_i, p.Mcols) > lds_tbits) {
+                const uint32_t gbits = guaranteed_tbits(ub_i, p.Mcols);
+                if (pred > 1.2 * (double)p.tier_limit[tier] && gbits > lds_tbits) {
                     int t2 = tier + 1;
                     while (t2 < NUM_LDS_TIERS && pred > (double)p.tier_limit[t2]) ++t2;
+                    // never above the tier guaranteed to fit the row: the host launches no tier beyond the matrix's guaranteed one (spgemm.hip, tmax)
+                    if (t2 > (int)gbits - LDS_TBITS0) t2 = (int)gbits - LDS_TBITS0;
                     if (tid == 0) {
+                        atomicAdd(&p.ctr->nforward, 1u);
                         const uint32_t at = atomicAdd(&p.ctr->tier_count[t2], 1u);
                         p.lists[(size_t)t2 * p.M + at] = i;
                     }

@@ -367,6 +367,11 @@ int  elba_set_option(elba_ctx *ctx, const char *name, int64_t value);
  *                            (elba_release_workspace on other contexts of the device, then build again)
  *   "gather_slots"           columns of the padded column store in use (with inline partners: only the columns some row entry still fetches)
  *   "kmer_passes"            value-range passes the last elba_count_kmers took (1: the whole input at once; option "kmer_batch_instances")
+ *   "kmer_largest_pass"      instances of its largest value-range pass (a pass holds whole first digits: it may exceed the cap; I when unbatched)
+ *   "kmer_crowded_buckets"   buckets it gave up to a crowded path (19 <= k <= 31: the pseudo-bucket path; k <= 17: the windowed bucket kernel)
+ *   "kmer_crowded_small"     19 <= k <= 31: crowded buckets whose kept entries (0 < Z <= the emit kernels' largest class) would fit an ordinary emit
+ *   "overlap_passes"         passes the last elba_create_seed_matrix call took (1: no repeat; also set when the call failed)
+ *   "overlap_forwarded"      rows that call forwarded to a larger table tier on its in-call prediction (cold calls without a sample), all passes
  *   "spgemm_prep_us"         option "measure_prep": device microseconds the emit kernels of the last elba_count_kmers spent on hint bits, inline partners,
  *                            gather slots and padded columns (the kernels as built minus the same kernels without them; -1: not measured)
  *   "emit_us"                ... and the emit kernels as built */

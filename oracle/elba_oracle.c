@@ -454,17 +454,20 @@ int orc_count_and_build_mt(orc_ctx *c, const uint8_t *buf, const uint64_t *byte_
         while (t < T) rbound[++t] = nreads;
     }
 #define ORC_BK(w0) ((int)((w0) >> 56))
+    /* The T read ranges are shared out by `omp for`: the region may deliver fewer threads than asked for (OMP_THREAD_LIMIT, dynamic adjustment, a
+       nested region) and every range must still be walked — by whichever thread; range t's counts and cursors are its own whatever thread runs it. */
     int fail = 0;
 #pragma omp parallel num_threads(T)
     {
-        const int t = omp_get_thread_num();
         uint64_t *scratch = (uint64_t *)malloc((size_t)(maxlen + 1) * sizeof(uint64_t));
         if (!scratch) {
 #pragma omp atomic write
             fail = 1;
         }
 #pragma omp barrier
-        if (!fail) {
+#pragma omp for schedule(static, 1)
+        for (int t = 0; t < T; ++t) {
+            if (fail) continue;
             int64_t *mycnt = cnt + (size_t)t * NBK;
             for (int64_t r = rbound[t]; r < rbound[t + 1]; ++r) {
                 if (k > 32) {
@@ -476,7 +479,6 @@ int orc_count_and_build_mt(orc_ctx *c, const uint8_t *buf, const uint64_t *byte_
                 }
             }
         }
-#pragma omp barrier
 #pragma omp single
         {
             int64_t run = 0;
@@ -486,7 +488,9 @@ int orc_count_and_build_mt(orc_ctx *c, const uint8_t *buf, const uint64_t *byte_
             }
             bstart[NBK] = run;
         }
-        if (!fail) {
+#pragma omp for schedule(static, 1)
+        for (int t = 0; t < T; ++t) {
+            if (fail) continue;
             int64_t *cur = cnt + (size_t)t * NBK;
             for (int64_t r = rbound[t]; r < rbound[t + 1]; ++r) {
                 if (k > 32) {
@@ -511,6 +515,7 @@ int orc_count_and_build_mt(orc_ctx *c, const uint8_t *buf, const uint64_t *byte_
     /* every bucket on its own: sort (the number of passes does not depend on the bucket: all of them end in the same buffer), count */
     int64_t bN[NBK + 1], bZ[NBK + 1], bD[NBK];
     int64_t *hists = (int64_t *)calloc((size_t)NBK * ((size_t)c->upper + 2), sizeof(int64_t));
+    if (!hists) { free(a); free(b); free(rbound); free(cnt); free(bstart); return -1; }
     orc_inst_t *sorted_in = NULL;
 #pragma omp parallel for num_threads(T) schedule(dynamic, 1)
     for (int bk = 0; bk < NBK; ++bk) {
@@ -533,7 +538,7 @@ int orc_count_and_build_mt(orc_ctx *c, const uint8_t *buf, const uint64_t *byte_
     bN[NBK] = N; bZ[NBK] = Z;
     c->N = N; c->Z = Z; c->ndistinct = nd;
     c->hist = (int64_t *)calloc((size_t)c->upper + 2, sizeof(int64_t));
-    for (int bk = 0; bk < NBK; ++bk) for (int64_t q = 0; q < (int64_t)c->upper + 2; ++q) c->hist[q] += hists[(size_t)bk * ((size_t)c->upper + 2) + (size_t)q];
+    if (c->hist) for (int bk = 0; bk < NBK; ++bk) for (int64_t q = 0; q < (int64_t)c->upper + 2; ++q) c->hist[q] += hists[(size_t)bk * ((size_t)c->upper + 2) + (size_t)q];
     free(hists);
     c->kmers = (uint64_t *)malloc((size_t)(N + 1) * sizeof(uint64_t));
     c->kmers_lo = k > 32 ? (uint64_t *)malloc((size_t)(N + 1) * sizeof(uint64_t)) : NULL;
@@ -544,6 +549,9 @@ int orc_count_and_build_mt(orc_ctx *c, const uint8_t *buf, const uint64_t *byte_
     c->rowptr = (int64_t *)calloc((size_t)(nreads + 2), sizeof(int64_t));
     c->csr_kid = (uint32_t *)malloc((size_t)(Z + 1) * sizeof(uint32_t));
     c->csr_pos = (uint32_t *)malloc((size_t)(Z + 1) * sizeof(uint32_t));
+    if (!c->hist || !c->kmers || (k > 32 && !c->kmers_lo) || (k > 64 && !c->kmers_lo2) || !c->colptr || !c->csc_read || !c->csc_pos || !c->rowptr || !c->csr_kid || !c->csr_pos) {
+        free(a); free(b); free(rbound); free(cnt); free(bstart); orc_free_A(c); return -1;
+    }
     const orc_inst_t *sall = sorted_in ? sorted_in : a;
 #pragma omp parallel for num_threads(T) schedule(dynamic, 1)
     for (int bk = 0; bk < NBK; ++bk) {
@@ -569,14 +577,15 @@ int orc_count_and_build_mt(orc_ctx *c, const uint8_t *buf, const uint64_t *byte_
     free(a); free(b); free(rbound); free(cnt); free(bstart);
     /* CSR: stable counting transpose, columns split over the threads (thread t's entries of a row lie behind those of the threads before it) */
     int64_t *rc = (int64_t *)calloc((size_t)T * (size_t)(nreads + 1), sizeof(int64_t));
-    if (!rc) return -1;
+    if (!rc) { orc_free_A(c); return -1; }
 #pragma omp parallel num_threads(T)
     {
-        const int t = omp_get_thread_num();
-        const int64_t k0 = N * t / T, k1 = N * (t + 1) / T;
-        int64_t *mine = rc + (size_t)t * (size_t)(nreads + 1);
-        for (int64_t e = c->colptr[k0]; e < c->colptr[k1]; ++e) mine[c->csc_read[e]]++;
-#pragma omp barrier
+#pragma omp for schedule(static, 1)
+        for (int t = 0; t < T; ++t) {      /* (column range t: its own row counts, whatever thread runs it) */
+            const int64_t k0 = N * t / T, k1 = N * (t + 1) / T;
+            int64_t *mine = rc + (size_t)t * (size_t)(nreads + 1);
+            for (int64_t e = c->colptr[k0]; e < c->colptr[k1]; ++e) mine[c->csc_read[e]]++;
+        }
 #pragma omp for schedule(static)
         for (int64_t r = 0; r < nreads; ++r) { int64_t tot = 0; for (int tt = 0; tt < T; ++tt) tot += rc[(size_t)tt * (size_t)(nreads + 1) + (size_t)r]; c->rowptr[r + 1] = tot; }
 #pragma omp single
@@ -586,11 +595,16 @@ int orc_count_and_build_mt(orc_ctx *c, const uint8_t *buf, const uint64_t *byte_
             int64_t run = c->rowptr[r];
             for (int tt = 0; tt < T; ++tt) { int64_t *x = &rc[(size_t)tt * (size_t)(nreads + 1) + (size_t)r]; const int64_t v = *x; *x = run; run += v; }
         }
-        for (int64_t kk = k0; kk < k1; ++kk)
-            for (int64_t e = c->colptr[kk]; e < c->colptr[kk + 1]; ++e) {
-                const int64_t d = mine[c->csc_read[e]]++;
-                c->csr_kid[d] = (uint32_t)kk; c->csr_pos[d] = c->csc_pos[e];
-            }
+#pragma omp for schedule(static, 1)
+        for (int t = 0; t < T; ++t) {
+            const int64_t k0 = N * t / T, k1 = N * (t + 1) / T;
+            int64_t *mine = rc + (size_t)t * (size_t)(nreads + 1);
+            for (int64_t kk = k0; kk < k1; ++kk)
+                for (int64_t e = c->colptr[kk]; e < c->colptr[kk + 1]; ++e) {
+                    const int64_t d = mine[c->csc_read[e]]++;
+                    c->csr_kid[d] = (uint32_t)kk; c->csr_pos[d] = c->csc_pos[e];
+                }
+        }
     }
     free(rc);
     return 0;
