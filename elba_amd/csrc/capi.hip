@@ -578,7 +578,7 @@ int elba_set_option(elba_ctx *ctx, const char *name, int64_t value)
         ELBA_REQUIRE(name, ELBA_ERR_INVALID_ARG, "set_option: null name");
         struct { const char *n; bool *b; } flags[] = {
             {"overlap_cold_calls", &c.cold_calls}, {"no_symmetry", &c.opt.no_symmetry}, {"no_ell", &c.opt.no_ell}, {"no_pay", &c.opt.no_pay}, {"mir32", &c.opt.mir32},
-            {"no_hints", &c.opt.no_hints}, {"no_sample", &c.opt.no_sample}, {"no_slab", &c.opt.no_slab}, {"no_ell_compact", &c.opt.no_ell_compact}, {"msd_no_emit8", &c.opt.msd_no_emit8}, {"msd_no_rank", &c.opt.msd_no_rank}, {"msd_rank", &c.opt.msd_rank}, {"csr_pairs_late", &c.opt.csr_pairs_late}, {"no_suffix", &c.opt.no_suffix}, {"no_row_order", &c.opt.no_row_order}, {"no_inline", &c.opt.no_inline}, {"panel_inline", &c.opt.panel_inline}, {"kmer_pairs", &c.opt.kmer_pairs},
+            {"no_hints", &c.opt.no_hints}, {"no_sample", &c.opt.no_sample}, {"no_slab", &c.opt.no_slab}, {"no_ell_compact", &c.opt.no_ell_compact}, {"msd_no_emit8", &c.opt.msd_no_emit8}, {"msd_no_rank", &c.opt.msd_no_rank}, {"msd_rank", &c.opt.msd_rank}, {"csr_pairs_late", &c.opt.csr_pairs_late}, {"no_suffix", &c.opt.no_suffix}, {"ov_generic", &c.opt.ov_generic}, {"no_row_order", &c.opt.no_row_order}, {"no_inline", &c.opt.no_inline}, {"panel_inline", &c.opt.panel_inline}, {"kmer_pairs", &c.opt.kmer_pairs},
             {"kmer_unfused", &c.opt.kmer_unfused}, {"kmer_no_msd", &c.opt.kmer_no_msd}, {"kmer_msd", &c.opt.kmer_msd}, {"csr_pairs", &c.opt.csr_pairs}, {"emit_plain", &c.opt.emit_plain}, {"trace", &c.opt.trace}, {"measure_prep", &c.opt.measure_prep}};
         for (auto &f : flags) if (!strcmp(name, f.n)) { *f.b = value != 0; return; }
         if (!strcmp(name, "kmer_drop")) { ELBA_REQUIRE(value >= 0 && value <= 3, ELBA_ERR_INVALID_ARG, "set_option: kmer_drop is 0..3"); c.opt.kmer_drop = (int)value; }
@@ -625,6 +625,7 @@ int elba_get_stat(elba_ctx *ctx, const char *name, int64_t *value)
         else if (!strcmp(name, "kmer_crowded_small")) *value = c.kmer_crowded_small;      // wide crowded parents whose folded entry count lies in (0, small_cap]: what the main emit classes would take
         else if (!strcmp(name, "kmer_largest_pass")) *value = c.kmer_largest_pass;      // instances of the last elba_count_kmers' largest value-range pass (I when unbatched)
         else if (!strcmp(name, "overlap_passes")) *value = c.ov_passes;      // passes the last create_seed_matrix took (1: no repeat; set also when the call failed)
+        else if (!strcmp(name, "overlap_spec")) *value = c.ov_spec;      // 1: the last create_seed_matrix ran the reads-path instantiation of the numeric kernel (spgemm.hip: ov_spec_ok), 0: the general one
         else if (!strcmp(name, "overlap_forwarded")) *value = c.ov_forwarded;      // rows the last create_seed_matrix forwarded to a larger tier on a prediction, all passes
         else if (!strcmp(name, "spgemm_prep_us")) *value = c.prep_us;      // (option "measure_prep"; -1: not measured — the option was off, or the path taken has no emit kernels of its own)
         else if (!strcmp(name, "emit_us")) *value = c.emit_us;

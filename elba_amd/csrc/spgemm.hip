@@ -117,6 +117,32 @@ struct OvParams {
     unsigned long long *slab_pos;      // [M] per row: slab end << 32 | next free slab entry (k_classify_direct sets it to end << 32 | start)
 };
 
+// The reads path's parameter block (k_spgemm_direct<..., SPEC = true>): a matrix built from reads, multiplied whole in one call with one triangle +
+// mirror, sets every switch of OvParams the same way on every call — padded columns with inline partners and ownership hints, 32-bit accumulators
+// that carry posT, 16-byte staging words, no dense path, single queue places.  Those switches are compile-time constants here (the kernel's dead
+// branches go, and so do the scalars it used to hold for them: the general kernel spills ~120 SGPRs to VGPR lanes); what still varies between
+// such calls — slabs or none, feedback, the tier, fbits, stride, lanes per entry — stays a field.  ov_spec_ok (spgemm.hip) is the predicate.
+struct OvSpecParams {
+    static constexpr uint32_t half = 1, inl = 1, pay16 = 1, rec16 = 1, suffix = 0, qblk_log2 = 0, j_shift = 0;
+    static constexpr uint32_t hint_mask = 1u << 31, pos_mask = 0x3FFFFFFFu;
+    static constexpr uint32_t row_lo = 0, row_hi = 0xFFFFFFFFu;      // the whole matrix: every partner id (< M) lies inside the window
+    static constexpr const uint32_t *a_colptr = nullptr, *a_ellj = nullptr, *row_order = nullptr, *row_label = nullptr;
+    static constexpr const uint64_t *a_csc = nullptr;
+    static constexpr StageRec *tmp = nullptr;
+    static constexpr uint32_t *gtable = nullptr;
+    static constexpr unsigned long long gstride = 0;
+    const uint32_t *a_rowptr; const uint64_t *a_csr; const uint64_t *a_ell;
+    uint32_t *tick_rows;
+    uint32_t s_stride, lpc_log2, max_col, fbits, M, Mcols, use_feedback;
+    uint32_t tier_limit[NUM_LDS_TIERS];
+    unsigned long long fb_enough, tmp_cap;
+    uint32_t *row_cnt, *low_cnt; unsigned long long *row_off;
+    uint32_t *lists, *sample_list;
+    OvCounters *ctr;
+    uint4 *rec; uint32_t *tick;
+    uint4 *slab; unsigned long long *slab_pos;
+};
+
 // several small buffers zeroed by one launch (the counters of a call)
 struct ZeroList { uint32_t *p[6]; size_t words[6]; int n; };
 __global__ __launch_bounds__(256) void k_zero_regions(ZeroList z)
@@ -906,6 +932,29 @@ static void ov_finish_stats(Ctx &c, OvCounters &hc, elba_overlap_stats &st, int 
     c.have_B = true;
 }
 
+// The reads-path instantiation of the numeric kernel (OvSpecParams) runs a call whose every switch has the value that instantiation fixes: padded columns
+// with inline partners and ownership hints, one triangle + mirror over the whole matrix in one call, 32-bit accumulators carrying posT, 16-byte records,
+// the gather depth of inline rows.  Anything else — both triangles, CSC columns, 64-bit accumulators, 32-byte records, the dense path, windows and
+// shards, a forced gather depth or tier (option "dk", "tune3" .. "tune5", "tune7"), option "ov_generic" (A/B) — takes the general kernel.
+static bool ov_spec_ok(const Ctx &c, const OvParams &p, bool pay, int dk)
+{
+    return !c.opt.ov_generic && c.opt.dk < 0 && dk == 0 && !pay && p.pay16 == OvSpecParams::pay16 && p.a_ell != nullptr && p.half == OvSpecParams::half &&
+           p.hint_mask == OvSpecParams::hint_mask && p.pos_mask == OvSpecParams::pos_mask && p.inl == OvSpecParams::inl && p.rec16 == OvSpecParams::rec16 &&
+           p.suffix == OvSpecParams::suffix && p.row_order == nullptr && p.qblk_log2 == OvSpecParams::qblk_log2 && p.row_lo == 0u && p.row_hi == p.M && p.Mcols == p.M &&
+           c.opt.tune[3] == 0 && c.opt.tune[4] == 0 && c.opt.tune[5] == 0 && c.opt.tune[7] == 0;
+}
+static OvSpecParams ov_spec_params(const OvParams &p)
+{
+    OvSpecParams q{};
+    q.a_rowptr = p.a_rowptr; q.a_csr = p.a_csr; q.a_ell = p.a_ell; q.tick_rows = p.tick_rows;
+    q.s_stride = p.s_stride; q.lpc_log2 = p.lpc_log2; q.max_col = p.max_col; q.fbits = p.fbits; q.M = p.M; q.Mcols = p.Mcols; q.use_feedback = p.use_feedback;
+    for (int t = 0; t < NUM_LDS_TIERS; ++t) q.tier_limit[t] = p.tier_limit[t];
+    q.fb_enough = p.fb_enough; q.tmp_cap = p.tmp_cap;
+    q.row_cnt = p.row_cnt; q.low_cnt = p.low_cnt; q.row_off = p.row_off; q.lists = p.lists; q.sample_list = p.sample_list; q.ctr = p.ctr;
+    q.rec = p.rec; q.tick = p.tick; q.slab = p.slab; q.slab_pos = p.slab_pos;
+    return q;
+}
+
 // phase 0: the whole call.  phase 1: the first half of a sharded call with mirror exchange (stage_seed_matrix_begin): classify + numeric with
 // GLOBAL pair ownership, stops before the finalize pass.  phase 2: the same, only QUEUED — every tier is launched, nothing is read back and the
 // host does not wait (stage_seed_matrix_send; what phase 1 checks after its synchronisation, stage_seed_matrix_recv checks at the end of the step).
@@ -1016,6 +1065,9 @@ static void create_seed_matrix_direct(Ctx &c, int phase)
         ELBA_ATTR(256, false, 1); ELBA_ATTR(256, false, 2); ELBA_ATTR(256, false, 4);
         ELBA_ATTR(512, false, 1); ELBA_ATTR(512, false, 2); ELBA_ATTR(512, false, 4); ELBA_ATTR(1024, false, 1); ELBA_ATTR(1024, false, 2); ELBA_ATTR(1024, false, 4);
 #undef ELBA_ATTR
+#define ELBA_ATTR(B) ELBA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_spgemm_direct<B, false, false, 0, false, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds))
+        ELBA_ATTR(128); ELBA_ATTR(256); ELBA_ATTR(512); ELBA_ATTR(1024);
+#undef ELBA_ATTR
     });
 
     c.ov_host.reserve(sizeof(OvCounters));
@@ -1023,7 +1075,7 @@ static void create_seed_matrix_direct(Ctx &c, int phase)
     hc = OvCounters{};
     uint32_t skipped_tiers = 0, skipped_sorts = 0;
     int passes = 0;
-    c.ov_passes = 0; c.ov_forwarded = 0;
+    c.ov_passes = 0; c.ov_forwarded = 0; c.ov_spec = 0;
     float ms_sym = 0, ms_num = 0, ms_fin = 0, ms_tot = 0;
     bool was_timed = true;
     for (;;) {
@@ -1106,7 +1158,9 @@ static void create_seed_matrix_direct(Ctx &c, int phase)
 #define ELBA_DTIER(t, stmt) do { if ((all_tiers || c.ov_tier_used[t]) && (t) <= tmax) { stmt; } else skipped_tiers |= 1u << (t); } while (0)
 #define ELBA_LAUNCH_D(B, G, P, grid, lds, tier, tb, smp)                                                                                  \
     do {                                                                                                                                  \
-        if (dk == 0) hipLaunchKernelGGL((k_spgemm_direct<B, G, P, 0>), dim3(grid), dim3(B), (lds), s, p, (tier), (tb), (smp));            \
+        if (spec && !(G) && !(P))                                                                                                         \
+            hipLaunchKernelGGL((k_spgemm_direct<B, false, false, 0, false, 0, true>), dim3(grid), dim3(B), (lds), s, ov_spec_params(p), (tier), (tb), (smp)); \
+        else if (dk == 0) hipLaunchKernelGGL((k_spgemm_direct<B, G, P, 0>), dim3(grid), dim3(B), (lds), s, p, (tier), (tb), (smp));            \
         else if (dk == 1) hipLaunchKernelGGL((k_spgemm_direct<B, G, P, 1>), dim3(grid), dim3(B), (lds), s, p, (tier), (tb), (smp));       \
         else if (dk == 4) hipLaunchKernelGGL((k_spgemm_direct<B, G, P, 4>), dim3(grid), dim3(B), (lds), s, p, (tier), (tb), (smp));       \
         else hipLaunchKernelGGL((k_spgemm_direct<B, G, P, 2>), dim3(grid), dim3(B), (lds), s, p, (tier), (tb), (smp));                    \
@@ -1115,6 +1169,8 @@ static void create_seed_matrix_direct(Ctx &c, int phase)
             // reads, 15 %-error reads: 6.49 -> 6.27 ms on config 3 —, 2 (DK = 1) otherwise (columns of ~7 reads at 5 % error lose 4 % with one trip);
             // the option "dk" (0, 1, 2, 4) overrides
             const int dk = c.opt.dk >= 0 ? c.opt.dk : ((c.csr_inline && c.N > 0 && c.Z < 3 * c.N) ? 0 : 1);
+            const bool spec = ov_spec_ok(c, p, pay, dk);      // (the reads path: its switches compiled into the kernel)
+            c.ov_spec = spec ? 1 : 0;
 // (dense path: 32-bit accumulators + seed look-ups for the few survivors; the first tier's grid is a tuning knob: the path waits for memory)
 #define ELBA_LAUNCH_S(B, TBC, grid, lds, tier, tb, smp) hipLaunchKernelGGL((k_spgemm_direct<B, false, false, 2, true, TBC>), dim3((tier) == 0 ? cus * c.opt.dense_wgs : (grid)), dim3(B), (size_t)18 * (1u << (tb)) + 256 + (size_t)((B) / 64) * 2368, s, p, (tier), (tb), (smp))
             if (sampling) {

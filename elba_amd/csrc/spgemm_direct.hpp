@@ -77,13 +77,15 @@ __device__ __forceinline__ bool owns_pair(uint32_t i, uint32_t j, uint32_t row_l
 // SUFFIX: the dense path (OvParams::suffix) instead of the general one — an instantiation of its own, so that the general kernel does not carry its registers
 // (second launch bound = wavefronts per SIMD the register allocation must leave room for: 4 keeps two 512-thread workgroups on a CU — at 132
 //  VGPRs instead of 128 the kernel loses one of them and runs twice as long (measured) —, 8 is what the dense path's 8 workgroups of 4 wavefronts per CU need)
-template <int BLOCK, bool GLOBAL, bool PAY, int DK = 2, bool SUFFIX = false, int TB = 0>
+// SPEC: the reads path (OvSpecParams: its switches are constants) on the LDS tiers with 32-bit accumulators
+template <int BLOCK, bool GLOBAL, bool PAY, int DK = 2, bool SUFFIX = false, int TB = 0, bool SPEC = false>
 #ifndef ELBA_DENSE_OCC
 #define ELBA_DENSE_OCC 8
 #endif
-__global__ __launch_bounds__(BLOCK, SUFFIX ? ELBA_DENSE_OCC : (DK == 4 ? 1 : 4)) void k_spgemm_direct(OvParams p, int tier, uint32_t lds_tbits, uint32_t sample)
+__global__ __launch_bounds__(BLOCK, SUFFIX ? ELBA_DENSE_OCC : (DK == 4 ? 1 : 4)) void k_spgemm_direct(std::conditional_t<SPEC, OvSpecParams, OvParams> p, int tier, uint32_t lds_tbits, uint32_t sample)
 {
     static_assert(!PAY || !GLOBAL, "payload accumulators: LDS tiers only");
+    static_assert(!SPEC || (!GLOBAL && !PAY && !SUFFIX), "the reads path: LDS tiers, 32-bit accumulators carrying posT");
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     uint32_t *misc = GLOBAL ? smem : smem + (size_t)(PAY ? 6 : 4) * (1u << lds_tbits) + ((size_t)1 << lds_tbits) / 2;
     const uint32_t tid = threadIdx.x, lane = tid & 63;
@@ -92,7 +94,7 @@ __global__ __launch_bounds__(BLOCK, SUFFIX ? ELBA_DENSE_OCC : (DK == 4 ? 1 : 4))
     if (nrows == 0) return;      // (a tier nobody queued on — most tiers of a small matrix: its workgroups leave before they initialise a table; rows only ever move to HIGHER tiers, which start later)
     const uint32_t lb = p.lpc_log2, sub = tid & ((1u << lb) - 1u), grp = tid >> lb, EPT = (uint32_t)BLOCK >> lb;
     const uint32_t fbits = p.fbits, fmask = (1u << fbits) - 1u, stride = p.s_stride;
-    const bool ell = p.a_ell != nullptr;
+    const bool ell = SPEC || p.a_ell != nullptr;
     const uint32_t hmask = p.hint_mask, pmask = p.pos_mask;      // ownership hints in the row entries (Ctx::csr_hints): skip bit of this call's mode, position bits
     const uint2 *csr2 = reinterpret_cast<const uint2 *>(p.a_csr);      // .x = position in the read, .y = k-mer id
     // mirror slabs (spgemm.hip): the ratio k_classify_direct settled for this call (0: none — the sample's rows run before it is known) and the
