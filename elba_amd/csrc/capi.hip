@@ -624,6 +624,7 @@ int elba_get_stat(elba_ctx *ctx, const char *name, int64_t *value)
         else if (!strcmp(name, "kmer_crowded_buckets")) *value = c.kmer_crowded;      // buckets the last elba_count_kmers gave up to a crowded path (wide: k31_count's crowded parents; k <= 17: k_msd_bucket's)
         else if (!strcmp(name, "kmer_crowded_small")) *value = c.kmer_crowded_small;      // wide crowded parents whose folded entry count lies in (0, small_cap]: what the main emit classes would take
         else if (!strcmp(name, "kmer_largest_pass")) *value = c.kmer_largest_pass;      // instances of the last elba_count_kmers' largest value-range pass (I when unbatched)
+        else if (!strcmp(name, "kmer_peak_bytes")) *value = c.kmer_peak_bytes;      // device bytes the last elba_count_kmers' value-range passes of k > 31 held at their high point (0: not batched)
         else if (!strcmp(name, "kmer_buckets")) *value = c.kmer_buckets;      // buckets of the last elba_count_kmers' value partition, all passes (0: the sort)
         else if (!strcmp(name, "overlap_passes")) *value = c.ov_passes;      // passes the last create_seed_matrix took (1: no repeat; set also when the call failed)
         else if (!strcmp(name, "overlap_spec")) *value = c.ov_spec;      // 1: the last create_seed_matrix ran the reads-path instantiation of the numeric kernel (spgemm.hip: ov_spec_ok), 0: the general one

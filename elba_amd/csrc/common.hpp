@@ -70,6 +70,14 @@ struct DevBuf {
         if (e != hipSuccess) { p = nullptr; throw Error{ELBA_ERR_OUT_OF_MEMORY, "hipMalloc of " + std::to_string(bytes) + " bytes failed"}; }
         cap = want;
     }
+    void reserve_exact(size_t bytes)      // (no slack: buffers that are filled once, at a size known in advance)
+    {
+        if (bytes <= cap) return;
+        release();
+        const hipError_t e = hipMalloc(&p, bytes);
+        if (e != hipSuccess) { p = nullptr; throw Error{ELBA_ERR_OUT_OF_MEMORY, "hipMalloc of " + std::to_string(bytes) + " bytes failed"}; }
+        cap = bytes;
+    }
     template <class T> T *as() const { return reinterpret_cast<T *>(p); }
     void swap(DevBuf &o) { void *tp = p; p = o.p; o.p = tp; size_t tc = cap; cap = o.cap; o.cap = tc; }
 };
@@ -169,7 +177,7 @@ struct Options {
                                 // inline partners, gather slots + padded columns), both runs bracketed by events: elba_get_stat("spgemm_prep_us") = the difference (kmer_msd.hip)
     int64_t tune[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // A/B switches of the round in progress ("tune0" .. "tune7"): what each means is said where it is read
     int msd_wide_bits = 0;      // tests: value bits the partition of the 19 <= k <= 31 path takes (0: chosen from the number of instances; batched: each pass's, at least 11 + its first level's extra bits)
-    int64_t kmer_batch_instances = 0;      // k-mer stage (k <= 31, reads): more instances than this are counted in passes over value ranges (0: 0xE0000000 — what a 32-bit place holds); tests force passes on small sets
+    int64_t kmer_batch_instances = 0;      // k-mer stage (reads, k >= 9): more instances than this are counted in passes over value ranges (0: 0xE0000000 — what a 32-bit place holds; k > 31: also no more than the device memory holds); tests force passes on small sets
     int msd_small_cap = 0;      // tests: buckets with more entries than this go to the crowded-bucket kernel (0 = its real capacity)
     int kmer_drop = 0;          // test hook: force that many dropped index bits on a small input (1..3)
     int dense_up = 1;           // SpGEMM, dense path: the tier its rows start on at least (1: eight wavefronts share a 1024-slot table — 32 per CU as with four on 512 slots, half the load)
@@ -204,6 +212,7 @@ struct Ctx {
     int triples_path = 0; // diagnostic: how the last elba_set_kmer_matrix_device built the matrix — 0 radix sorts of the whole matrix (matrix.hip), 1 the k-mer stage's bucket kernels (kmer_msd.hip)
     int kmer_passes = 1;  // diagnostic: value-range passes of the last elba_count_kmers (kmer_msd.hip)
     int64_t kmer_crowded = 0, kmer_crowded_small = 0, kmer_largest_pass = 0;      // diagnostic: the last elba_count_kmers' crowded buckets, wide ones of them with a folded entry count in (0, small_cap], instances of its largest pass (kmer_msd.hip)
+    int64_t kmer_peak_bytes = 0;   // diagnostic: device bytes the last elba_count_kmers held at its high point, measured (value-range passes of k > 31; 0 otherwise)
     int64_t kmer_buckets = 0;      // diagnostic: buckets of the last elba_count_kmers' value partition, summed over its passes (kmer_msd.hip; 0: the sort)
     int kmer_path = 0;    // diagnostic: how the last elba_count_kmers counted — 0 the sort of kmer.hip, 1 two-level partition + LDS count tables (k <= 17), 2 the same on 16-byte records + LDS sort (19 <= k <= 31)
     int64_t I = 0, ndistinct = 0;

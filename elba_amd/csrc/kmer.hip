@@ -17,6 +17,7 @@
 //
 // Packed k-mer layout (src/Kmer.cpp:67-87): base i at bits 2*(31-i), low 64-2k bits zero; canonical = min(kmer, twin)
 // (src/Kmer.cpp:200-205); position = forward start index (include/KmerOps.hpp:91-103).
+#include <memory>
 #include "common.hpp"
 #include "matrix.hpp"
 
@@ -152,7 +153,7 @@ __device__ __forceinline__ bool same_kmer(const RunParams &p, uint64_t a, uint64
 template <bool EMIT>
 __global__ __launch_bounds__(RUN_THREADS) void k_runs(RunParams p, uint32_t *blk_rel, uint32_t *blk_ent, uint32_t *blk_heads, const uint32_t *off_rel, const uint32_t *off_ent,
                                                       uint64_t *rel_kmers, uint64_t *rel_kmers_lo, uint64_t *rel_kmers_lo2, uint32_t *rel_counts, uint32_t *colptr,
-                                                      uint64_t *payload, uint64_t *kid_of_entry)
+                                                      uint64_t *payload, uint64_t *kid_of_entry, uint64_t kid_base, uint32_t ent_base)
 {
     // Item q of the tile (q = i * 256 + tid: consecutive lanes, consecutive items — coalesced) is compared with its left neighbour once;
     // the answers live in LDS as one bit per item (+ 64 items of halo behind the tile), and a head reads its run length off the bits:
@@ -239,8 +240,8 @@ __global__ __launch_bounds__(RUN_THREADS) void k_runs(RunParams p, uint32_t *blk
             rel_kmers[kid] = p.ib ? (p.keys[g] >> p.ib) << (64 - p.k2) : p.keys[g];
             if (p.lo) rel_kmers_lo[kid] = p.lo[g];
             if (p.lo2) rel_kmers_lo2[kid] = p.lo2[g];
-            rel_counts[kid] = l; colptr[kid] = at;
-            for (uint32_t t = 0; t < l; ++t) { payload[at + t] = p.ib ? (p.keys[g + t] & pmask) : p.vals[g + t]; kid_of_entry[at + t] = kid; }
+            rel_counts[kid] = l; colptr[kid] = ent_base + at;
+            for (uint32_t t = 0; t < l; ++t) { payload[at + t] = p.ib ? (p.keys[g + t] & pmask) : p.vals[g + t]; kid_of_entry[at + t] = kid_base + kid; }
         }
     }
 }
@@ -438,8 +439,12 @@ EnumParams make_enum(Ctx &c)
 // Sorted words / (k-mer, value) pairs -> runs -> reliable columns: rel_kmers / rel_counts / a_colptr / a_csc / kid_of_entry of the context
 // (see the comment above k_runs).  ib: payload bits below the value in `skeys` (0: the payload is svals); drop: low bits of the instance
 // index that were cut off the payload.  scratch: at least (Z + 8) u64 (entry payloads), allocated by the caller's pool.
+// base: one value-range pass of the sort of k > 31 (count_long_kmers_in_passes): the column pointers it writes count from the entries of the passes
+// before it, its entries' column ids from their k-mers, and the arrays are allocated at exactly their size (they are staged, then concatenated).
+// The per-head path only (ib == 0).
+struct ColumnBase { uint64_t kid = 0; uint32_t ent = 0; bool exact = false; };
 static void runs_to_columns(Ctx &c, const uint64_t *skeys, const uint64_t *svals, uint64_t I, uint64_t &nruns_out, uint64_t &N_out, uint64_t &Z_out,
-                            const uint64_t *skeys_lo = nullptr, const uint64_t *skeys_lo2 = nullptr, int ib = 0, int drop = 0)
+                            const uint64_t *skeys_lo = nullptr, const uint64_t *skeys_lo2 = nullptr, int ib = 0, int drop = 0, ColumnBase base = {})
 {
     hipStream_t s = c.stream;
     const uint32_t nblocks = (uint32_t)((I + RUN_TILE - 1) / RUN_TILE);
@@ -452,7 +457,7 @@ static void runs_to_columns(Ctx &c, const uint64_t *skeys, const uint64_t *svals
     if (I > 0) {
         ELBA_HIP(hipMemsetAsync(blk_rel, 0, (size_t)(nblocks + 2) * 4 * 3, s));
         hipLaunchKernelGGL((k_runs<false>), dim3(nblocks), dim3(RUN_THREADS), 0, s, p, blk_rel, blk_ent, blk_heads, (const uint32_t *)nullptr, (const uint32_t *)nullptr,
-                           (uint64_t *)nullptr, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, (uint64_t *)nullptr, (uint64_t *)nullptr);
+                           (uint64_t *)nullptr, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, (uint64_t *)nullptr, (uint64_t *)nullptr, 0ull, 0u);
         exclusive_scan_u32(s, blk_rel, off_rel, (int64_t)nblocks + 1, c.ws_scan);
         exclusive_scan_u32(s, blk_ent, off_ent, (int64_t)nblocks + 1, c.ws_scan);      // Z <= I < 2^32: the 32-bit scan cannot wrap
         exclusive_scan_u32(s, blk_heads, blk_heads, (int64_t)nblocks + 1, c.ws_scan);
@@ -463,14 +468,15 @@ static void runs_to_columns(Ctx &c, const uint64_t *skeys, const uint64_t *svals
         ELBA_HIP(hipStreamSynchronize(s));
         N = h3[0]; Z = h3[1]; nruns = h3[2];
     }
-    ELBA_REQUIRE(Z < 0xFFFFFFF0ull, ELBA_ERR_UNSUPPORTED, "count_kmers: nnz(A) beyond 32-bit device offsets");
-    c.rel_kmers.reserve((size_t)(N + 1) * 8);
-    if (skeys_lo) c.rel_kmers_lo.reserve((size_t)(N + 1) * 8);
-    if (skeys_lo2) c.rel_kmers_lo2.reserve((size_t)(N + 1) * 8);
-    c.rel_counts.reserve((size_t)(N + 2) * 4);
-    c.a_colptr.reserve((size_t)(N + 2) * 4);
-    c.a_csc.reserve((size_t)(Z + 8) * 8);   // + guard entries (matrix.hip)
-    c.kid_of_entry.reserve((size_t)(Z + 8) * 8);
+    ELBA_REQUIRE(base.ent + Z < 0xFFFFFFF0ull, ELBA_ERR_UNSUPPORTED, "count_kmers: nnz(A) beyond 32-bit device offsets");
+    auto res = [&](DevBuf &b, size_t bytes) { if (base.exact) b.reserve_exact(bytes); else b.reserve(bytes); };
+    res(c.rel_kmers, (size_t)(N + 1) * 8);
+    if (skeys_lo) res(c.rel_kmers_lo, (size_t)(N + 1) * 8);
+    if (skeys_lo2) res(c.rel_kmers_lo2, (size_t)(N + 1) * 8);
+    res(c.rel_counts, (size_t)(N + 2) * 4);
+    res(c.a_colptr, (size_t)(N + 2) * 4);
+    res(c.a_csc, (size_t)(Z + 8) * 8);   // + guard entries (matrix.hip)
+    res(c.kid_of_entry, (size_t)(Z + 8) * 8);
     // Packed words with UPPER <= 62: one fused pass writes the columns, the entries' (read, pos) and — when read, k-mer id and position fit
     // one word — the sort keys of the CSR build (k_runs_emit).  Otherwise: heads write payloads and column ids, a second kernel converts.
     c.pre_ready = false; c.pre_consumed = false; c.pre_hints_done = false; c.pre_ell_done = false; c.pre_inline_pending = false; c.pre_pairs = false;
@@ -514,7 +520,7 @@ static void runs_to_columns(Ctx &c, const uint64_t *skeys, const uint64_t *svals
     if (I > 0)
         hipLaunchKernelGGL((k_runs<true>), dim3(nblocks), dim3(RUN_THREADS), 0, s, p, (uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, off_rel, off_ent,
                            c.rel_kmers.as<uint64_t>(), skeys_lo ? c.rel_kmers_lo.as<uint64_t>() : (uint64_t *)nullptr, skeys_lo2 ? c.rel_kmers_lo2.as<uint64_t>() : (uint64_t *)nullptr,
-                           c.rel_counts.as<uint32_t>(), c.a_colptr.as<uint32_t>(), pay, c.kid_of_entry.as<uint64_t>());
+                           c.rel_counts.as<uint32_t>(), c.a_colptr.as<uint32_t>(), pay, c.kid_of_entry.as<uint64_t>(), base.kid, base.ent);
     if (ib && Z > 0) {
         EnumParams e = make_enum(c);
         const uint64_t nib = (I >> IB_SHIFT) + 1;
@@ -524,11 +530,43 @@ static void runs_to_columns(Ctx &c, const uint64_t *skeys, const uint64_t *svals
                            c.ws_b.as<BlockInfo>());
     }
     }
-    const uint32_t Zz = (uint32_t)Z;
+    const uint32_t Zz = base.ent + (uint32_t)Z;
     ELBA_HIP(hipMemcpyAsync(c.a_colptr.as<uint32_t>() + N, &Zz, 4, hipMemcpyHostToDevice, s));
     ELBA_HIP(hipStreamSynchronize(s));
     nruns_out = nruns; N_out = N; Z_out = Z;
 }
+
+// Stable LSD sort of n multi-word keys (src[0] most significant) through an index permutation, last word first; `perm` receives the
+// order (perm[j] = index of the j-th smallest key).  Scratch: four n-word buffers.
+static const uint64_t *sort_words_permutation(Ctx &c, int words, const uint64_t *const src[3], uint64_t n, int k, uint64_t *ia, uint64_t *ib, uint64_t *ka, uint64_t *kb)
+{
+    hipStream_t s = c.stream;
+    const unsigned nb = (unsigned)((n + 255) / 256);
+    for (int wd = words - 1; wd >= 0; --wd) {
+        if (wd == words - 1) ELBA_HIP(hipMemcpyAsync(ka, src[wd], (size_t)n * 8, hipMemcpyDeviceToDevice, s));     // ia is the identity here
+        else hipLaunchKernelGGL(k_gather_u64, dim3(nb), dim3(256), 0, s, ia, src[wd], n, ka);
+        const int lo_bit = wd == words - 1 ? 64 - 2 * (k - 32 * (words - 1)) : 0;
+        const int w = radix_sort_pairs(s, ka, ia, kb, ib, (int64_t)n, lo_bit, 64, c.ws_sort);
+        if (w) { uint64_t *t; t = ia; ia = ib; ib = t; t = ka; ka = kb; kb = t; }
+    }
+    return ia;
+}
+
+// The sort of two- and three-word k-mers (stage_count_kmers, and every value-range pass of count_long_kmers_in_passes): the identity permutation i0
+// sorted by the words, then the k-mers' words and values gathered in sorted order into shi / slo / slo2 / sval.  n > 0; i1, t0, t1: n words each.
+static void sort_long_kmers(Ctx &c, int words, uint64_t n, const uint64_t *const wordsrc[3], const uint64_t *val, uint64_t *i0, uint64_t *i1, uint64_t *t0, uint64_t *t1,
+                            uint64_t *shi, uint64_t *slo, uint64_t *slo2, uint64_t *sval)
+{
+    hipStream_t s = c.stream;
+    const unsigned nbI = (unsigned)((n + 255) / 256);
+    const uint64_t *fin = sort_words_permutation(c, words, wordsrc, n, c.cfg.k, i0, i1, t0, t1);
+    hipLaunchKernelGGL(k_gather_u64, dim3(nbI), dim3(256), 0, s, fin, wordsrc[0], n, shi);
+    hipLaunchKernelGGL(k_gather_u64, dim3(nbI), dim3(256), 0, s, fin, wordsrc[1], n, slo);
+    if (words == 3) hipLaunchKernelGGL(k_gather_u64, dim3(nbI), dim3(256), 0, s, fin, wordsrc[2], n, slo2);
+    hipLaunchKernelGGL(k_gather_u64, dim3(nbI), dim3(256), 0, s, fin, val, n, sval);
+}
+
+static bool count_long_kmers_in_passes(Ctx &c, uint64_t I, int words, size_t free0, elba_kmer_stats &st);      // (below, beside the enumeration kernels it shares with the distributed path)
 
 void stage_count_kmers(Ctx &c)
 {
@@ -549,13 +587,16 @@ void stage_count_kmers(Ctx &c)
     off[(size_t)M] = I;
     c.max_read_len = maxlen;      // (the one host walk over the read lengths of this stage: kmer_msd.hip sizes its position field by it)
     // (more than 2^32 instances: the two-level partition of kmer_msd.hip counts them in passes over value ranges — 9 <= k <= 31, on 16-byte records from
-    //  k = 18 on; the sort of k > 31 holds 32-bit places, and so does the wide partition's LDS sort of a bucket's entries beyond UPPER = 255)
-    if (I >= 0xFFFFFFF0ull) {
-        ELBA_REQUIRE(k <= 31 && k >= 9, ELBA_ERR_UNSUPPORTED, "count_kmers: more than 2^32 k-mer instances on one GPU need 9 <= k <= 31 (the sort of longer k-mers holds 32-bit places)");
+    //  k = 18 on —, and so does the sort of k > 31 (count_long_kmers_in_passes); the wide partition's LDS sort of a bucket's entries beyond UPPER = 255
+    //  holds 32-bit places)
+    size_t free0 = 0;
+    if (k > 31) { size_t total = 0; ELBA_HIP(hipMemGetInfo(&free0, &total)); }      // (what bounds the passes of the sort: count_long_kmers_in_passes)
+    if (I >= 0xFFFFFFF0ull && k <= 31) {
+        ELBA_REQUIRE(k >= 9, ELBA_ERR_UNSUPPORTED, "count_kmers: more than 2^32 k-mer instances on one GPU need k >= 9 (the sort of short k-mers holds 32-bit places)");
         ELBA_REQUIRE(!c.opt.kmer_no_msd, ELBA_ERR_UNSUPPORTED, "count_kmers: more than 2^32 k-mer instances on one GPU need the value partition (option kmer_no_msd is set)");
         ELBA_REQUIRE(k <= 17 || c.cfg.upper <= 255, ELBA_ERR_UNSUPPORTED, "count_kmers: more than 2^32 k-mer instances on one GPU need UPPER <= 255 for k > 17 (the sort holds 32-bit places)");
     }
-    c.I = (int64_t)I; c.kmer_passes = 1;
+    c.I = (int64_t)I; c.kmer_passes = 1; c.kmer_peak_bytes = 0;
     c.kmer_crowded = 0; c.kmer_crowded_small = 0; c.kmer_largest_pass = (int64_t)I; c.kmer_buckets = 0;
     c.inst_off.reserve((size_t)(M + 1) * 8);
     ELBA_HIP(hipMemcpyAsync(c.inst_off.p, off.data(), (size_t)(M + 1) * 8, hipMemcpyHostToDevice, s));
@@ -563,6 +604,7 @@ void stage_count_kmers(Ctx &c)
     if (k > 31) {
         // ---- two- and three-word k-mers: sort an index permutation, last word first (stable LSD over all words), then gather ----
         const int words = k > 64 ? 3 : 2;
+        if (count_long_kmers_in_passes(c, I, words, free0, st)) return;
         DevBuf khi, klo, klo2, val, i0, i1, t0, t1, s2buf;
         for (DevBuf *b : {&khi, &klo, &val, &i0, &i1, &t0, &t1}) b->reserve((size_t)(I + 2) * 8);
         if (words == 3) { klo2.reserve((size_t)(I + 2) * 8); s2buf.reserve((size_t)(I + 2) * 8); }
@@ -572,26 +614,12 @@ void stage_count_kmers(Ctx &c)
         c.t_a.start(s);
         EnumParams e = make_enum(c);
         const uint64_t nblocks = (I + EN_PER_BLOCK - 1) / EN_PER_BLOCK;
-        const unsigned nbI = (unsigned)((I + 255) / 256);
         uint64_t *shi = c.ws_a.as<uint64_t>(), *slo = c.ws_b.as<uint64_t>(), *sval = c.ws_c.as<uint64_t>(), *slo2 = words == 3 ? s2buf.as<uint64_t>() : nullptr;
         if (I > 0) {
             if (words == 3) hipLaunchKernelGGL(k_kmer_emit3, dim3((unsigned)nblocks), dim3(EN_THREADS), 0, s, e, khi.as<uint64_t>(), klo.as<uint64_t>(), klo2.as<uint64_t>(), val.as<uint64_t>(), i0.as<uint64_t>());
             else hipLaunchKernelGGL(k_kmer_emit2, dim3((unsigned)nblocks), dim3(EN_THREADS), 0, s, e, khi.as<uint64_t>(), klo.as<uint64_t>(), val.as<uint64_t>(), i0.as<uint64_t>());
-            uint64_t *ia = i0.as<uint64_t>(), *ib = i1.as<uint64_t>(), *ka = t0.as<uint64_t>(), *kb = t1.as<uint64_t>();
             const uint64_t *wordsrc[3] = {khi.as<uint64_t>(), klo.as<uint64_t>(), words == 3 ? klo2.as<uint64_t>() : nullptr};
-            for (int wd = words - 1; wd >= 0; --wd) {
-                // keys of this pass = word wd in the current order
-                if (wd == words - 1) ELBA_HIP(hipMemcpyAsync(ka, wordsrc[wd], (size_t)I * 8, hipMemcpyDeviceToDevice, s));
-                else hipLaunchKernelGGL(k_gather_u64, dim3(nbI), dim3(256), 0, s, ia, wordsrc[wd], I, ka);
-                const int lo_bit = wd == words - 1 ? 64 - 2 * (k - 32 * (words - 1)) : 0;
-                const int w = radix_sort_pairs(s, ka, ia, kb, ib, (int64_t)I, lo_bit, 64, c.ws_sort);
-                if (w) { uint64_t *t; t = ia; ia = ib; ib = t; t = ka; ka = kb; kb = t; }
-            }
-            const uint64_t *fin = ia;
-            hipLaunchKernelGGL(k_gather_u64, dim3(nbI), dim3(256), 0, s, fin, khi.as<uint64_t>(), I, shi);
-            hipLaunchKernelGGL(k_gather_u64, dim3(nbI), dim3(256), 0, s, fin, klo.as<uint64_t>(), I, slo);
-            if (words == 3) hipLaunchKernelGGL(k_gather_u64, dim3(nbI), dim3(256), 0, s, fin, klo2.as<uint64_t>(), I, slo2);
-            hipLaunchKernelGGL(k_gather_u64, dim3(nbI), dim3(256), 0, s, fin, val.as<uint64_t>(), I, sval);
+            sort_long_kmers(c, words, I, wordsrc, val.as<uint64_t>(), i0.as<uint64_t>(), i1.as<uint64_t>(), t0.as<uint64_t>(), t1.as<uint64_t>(), shi, slo, slo2, sval);
         }
         c.t_a.stop(s);
         c.t_b.start(s);
@@ -756,6 +784,57 @@ __global__ __launch_bounds__(EN_THREADS) void k_dist_value_hist(EnumParams e, un
     for_each_kmer_words<W>(e, [&](uint64_t, uint32_t, uint32_t, uint64_t a, uint64_t, uint64_t) { atomicAdd(&h[(uint32_t)(a >> (64 - OWNER_BITS))], 1u); });
     __syncthreads();
     for (uint32_t b = threadIdx.x; b < (1u << OWNER_BITS); b += EN_THREADS) if (h[b]) atomicAdd(&hist[b], (unsigned long long)h[b]);
+}
+
+// ---- value-range passes of the sort of k > 31 (count_long_kmers_in_passes) ----
+// A pass is a range [lo, hi) of the leading 24 bits of the canonical first word.  Planned from k_dist_value_hist<W> (the leading 12 bits) and, for the
+// 12-bit bins that hold more than the cap, one refining histogram over the next 12 bits of all of them at once: slot_of_bin[bin] = the bin's row of
+// hist2, or -1.
+constexpr int LONG_PREFIX_BITS = 24;
+__device__ __forceinline__ bool in_long_pass(uint64_t a, uint32_t lo, uint32_t hi) { const uint32_t d = (uint32_t)(a >> (64 - LONG_PREFIX_BITS)); return d >= lo && d < hi; }
+
+template <int W>
+__global__ __launch_bounds__(EN_THREADS) void k_long_refine_hist(EnumParams e, const int32_t *slot_of_bin, unsigned long long *hist2)
+{
+    for_each_kmer_words<W>(e, [&](uint64_t, uint32_t, uint32_t, uint64_t a, uint64_t, uint64_t) {
+        const int32_t sl = slot_of_bin[a >> (64 - OWNER_BITS)];
+        if (sl >= 0) atomicAdd(&hist2[((uint64_t)sl << OWNER_BITS) | ((a >> (64 - LONG_PREFIX_BITS)) & ((1u << OWNER_BITS) - 1u))], 1ull);
+    });
+}
+
+// instances of the pass per wavefront (a wavefront enumerates EN_PER_WAVE consecutive instances): what the exclusive scan turns into the place of
+// every wavefront's first instance of the pass
+template <int W>
+__global__ __launch_bounds__(EN_THREADS) void k_long_pass_count(EnumParams e, uint32_t lo, uint32_t hi, uint32_t *wave_cnt)
+{
+    uint32_t n = 0;
+    for_each_kmer_words<W>(e, [&](uint64_t, uint32_t, uint32_t, uint64_t a, uint64_t, uint64_t) { n += in_long_pass(a, lo, hi) ? 1u : 0u; });
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) n += __shfl_xor(n, d, 64);
+    if ((threadIdx.x & 63) == 0) wave_cnt[((uint64_t)blockIdx.x * EN_THREADS + threadIdx.x) >> 6] = n;
+}
+
+// k_kmer_emit2 / k_kmer_emit3 of the instances of one pass only, in instance order (the wavefront's place from the scan, then its lanes' ranks by
+// ballot, step by step): the stable sort then leaves every column's entries in (read, pos) order, as one pass does.  idx = the pass-local slot;
+// slots at or beyond nmax (the pass's planned size) are not written.
+template <int W>
+__global__ __launch_bounds__(EN_THREADS) void k_kmer_emit_range(EnumParams e, uint32_t lo, uint32_t hi, const uint32_t *wave_off, uint64_t nmax,
+                                                               uint64_t *k0, uint64_t *k1, uint64_t *k2, uint64_t *vals, uint64_t *idx)
+{
+    const uint64_t wave = ((uint64_t)blockIdx.x * EN_THREADS + threadIdx.x) >> 6;
+    const uint64_t lt = (1ull << (threadIdx.x & 63)) - 1;
+    uint64_t at = wave_off[wave];
+    for_each_kmer_words<W>(e, [&](uint64_t, uint32_t r, uint32_t p, uint64_t a, uint64_t b, uint64_t c2) {
+        const bool in = in_long_pass(a, lo, hi);
+        const uint64_t bal = __ballot(in);
+        const uint64_t slot = at + (uint64_t)__popcll(bal & lt);
+        if (in && slot < nmax) {
+            k0[slot] = a; k1[slot] = b;
+            if constexpr (W == 3) k2[slot] = c2;
+            vals[slot] = ((uint64_t)r << 32) | p; idx[slot] = slot;
+        }
+        at += (uint64_t)__popcll(bal);
+    });
 }
 
 template <int W>
@@ -955,20 +1034,189 @@ __global__ void k_deinterleave(const uint64_t *rec, uint64_t n, uint64_t *k0, ui
 
 static int kmer_words(int k) { return k > 64 ? 3 : (k > 32 ? 2 : 1); }      // (k is odd: 31 is the last one-word k, 63 the last two-word k)
 
-// Stable LSD sort of n multi-word keys (src[0] most significant) through an index permutation, last word first; `perm` receives the
-// order (perm[j] = index of the j-th smallest key).  Scratch: four n-word buffers.
-static const uint64_t *sort_words_permutation(Ctx &c, int words, const uint64_t *const src[3], uint64_t n, int k, uint64_t *ia, uint64_t *ib, uint64_t *ka, uint64_t *kb)
+// ---- two- and three-word k-mers in value-range passes ----
+// The sort of k > 31 (stage_count_kmers) holds 32-bit places and reserves its workspace for the whole input at once.  Inputs that do not fit one pass
+// — 2^32 instances and more, more than the cap (option kmer_batch_instances, else 0xE0000000), or more than the device memory holds — are counted in
+// passes over ranges [lo, hi) of the leading 24 bits of the canonical first word, in ascending order: each pass emits its instances in instance order
+// (k_long_pass_count, a scan, k_kmer_emit_range), sorts and gathers them as one pass would, and cuts its runs into columns whose k-mer ids and entries
+// follow those of the passes before it.  Every pass stages its columns in buffers of exactly their size; once the passes are done and their workspace
+// is released, the context's arrays are allocated and the staged pieces concatenated into them, one kind of array at a time (peak: the staged
+// columns plus one array of the final size).  Passes change no result.  false: one pass takes the input (the caller runs the launches it always has).
+static bool count_long_kmers_in_passes(Ctx &c, uint64_t I, int words, size_t free0, elba_kmer_stats &st)
 {
     hipStream_t s = c.stream;
-    const unsigned nb = (unsigned)((n + 255) / 256);
-    for (int wd = words - 1; wd >= 0; --wd) {
-        if (wd == words - 1) ELBA_HIP(hipMemcpyAsync(ka, src[wd], (size_t)n * 8, hipMemcpyDeviceToDevice, s));     // ia is the identity here
-        else hipLaunchKernelGGL(k_gather_u64, dim3(nb), dim3(256), 0, s, ia, src[wd], n, ka);
-        const int lo_bit = wd == words - 1 ? 64 - 2 * (k - 32 * (words - 1)) : 0;
-        const int w = radix_sort_pairs(s, ka, ia, kb, ib, (int64_t)n, lo_bit, 64, c.ws_sort);
-        if (w) { uint64_t *t; t = ia; ia = ib; ib = t; t = ka; ka = kb; kb = t; }
+    // device bytes per instance, DevBuf's 1/8 slack included.  One pass (stage_count_kmers' reservations): khi klo val i0 i1 t0 t1, ws_a ws_b ws_c
+    // (8 each), ws_e (4), ws_f (8); three words: klo2 and s2buf (8 each).  A value-range pass: the same without ws_e / ws_f, which the sort path does
+    // not use at the instance count, plus the sort's histograms and the wavefront counts (under 1).  The columns: at most I entries (a_csc and
+    // kid_of_entry, 8 each) and I / LOWER k-mers (the words, count and pointer).
+    const double one_pass_b = (words == 2 ? 92.0 : 108.0) * 1.125, pass_b = (words == 2 ? 80.0 : 96.0) * 1.125 + 1.0;
+    const double out_b = (16.0 + (8.0 * words + 8.0) / (double)std::max(c.cfg.lower, 1)) * 1.125;
+    // what the call may use: the memory free when it started, the context's buffers that it overwrites, less 2 GiB for the runtime and small buffers
+    size_t held = 0;
+    for (DevBuf *b : {&c.ws_a, &c.ws_b, &c.ws_c, &c.ws_e, &c.ws_f, &c.rel_kmers, &c.rel_kmers_lo, &c.rel_kmers_lo2, &c.rel_counts, &c.a_colptr, &c.a_csc, &c.kid_of_entry}) held += b->cap;
+    const double avail = (double)free0 + (double)held - 2.0 * (double)(1ull << 30);
+    const uint64_t opt_cap = c.opt.kmer_batch_instances > 0 ? (uint64_t)c.opt.kmer_batch_instances : 0xE0000000ull;
+    if (I < 0xFFFFFFF0ull && I <= opt_cap && (double)I * (one_pass_b + out_b) <= avail) return false;
+    const double room = avail - out_b * (double)I;                      // for the workspace of the largest pass
+    const uint64_t mem_cap = room > 0 ? (uint64_t)(room / pass_b) : 0;
+    char why[256];
+    snprintf(why, sizeof why, "count_kmers: %llu k-mer instances at k = %d leave room for passes of %llu instances only (the columns may need %.1f GB)",
+             (unsigned long long)I, c.cfg.k, (unsigned long long)mem_cap, out_b * (double)I / 1e9);
+    ELBA_REQUIRE(mem_cap >= std::min<uint64_t>(I, 1ull << 24), ELBA_ERR_OUT_OF_MEMORY, why);
+    const uint64_t cap = std::max<uint64_t>(std::min<uint64_t>(std::min(opt_cap, mem_cap), 0xE0000000ull), 1);
+
+    c.t_total.start(s);
+    EnumParams e = make_enum(c);
+    const uint64_t nblocks = (I + EN_PER_BLOCK - 1) / EN_PER_BLOCK, nwaves = nblocks * (EN_THREADS / 64);
+    constexpr uint32_t NB = 1u << OWNER_BITS;
+    // ---- plan: instances per 12-bit bin of the first word; the bins above the cap per 24-bit prefix ----
+    std::vector<unsigned long long> h1(NB);
+    std::vector<unsigned long long> h2;
+    std::vector<uint32_t> heavy;
+    {
+        DevBuf plan;
+        plan.reserve((size_t)NB * 12);
+        unsigned long long *dh = plan.as<unsigned long long>();
+        ELBA_HIP(hipMemsetAsync(dh, 0, (size_t)NB * 8, s));
+        if (words == 3) hipLaunchKernelGGL(k_dist_value_hist<3>, dim3((unsigned)nblocks), dim3(EN_THREADS), 0, s, e, dh);
+        else hipLaunchKernelGGL(k_dist_value_hist<2>, dim3((unsigned)nblocks), dim3(EN_THREADS), 0, s, e, dh);
+        ELBA_HIP(hipMemcpyAsync(h1.data(), dh, (size_t)NB * 8, hipMemcpyDeviceToHost, s));
+        ELBA_HIP(hipStreamSynchronize(s));
+        std::vector<int32_t> slot(NB, -1);
+        for (uint32_t b = 0; b < NB; ++b) if (h1[b] > cap) { slot[b] = (int32_t)heavy.size(); heavy.push_back(b); }
+        if (!heavy.empty()) {
+            DevBuf hist2;
+            hist2.reserve(heavy.size() * NB * 8);
+            int32_t *dslot = reinterpret_cast<int32_t *>(dh + NB);
+            ELBA_HIP(hipMemcpyAsync(dslot, slot.data(), (size_t)NB * 4, hipMemcpyHostToDevice, s));
+            ELBA_HIP(hipMemsetAsync(hist2.p, 0, heavy.size() * NB * 8, s));
+            if (words == 3) hipLaunchKernelGGL(k_long_refine_hist<3>, dim3((unsigned)nblocks), dim3(EN_THREADS), 0, s, e, (const int32_t *)dslot, hist2.as<unsigned long long>());
+            else hipLaunchKernelGGL(k_long_refine_hist<2>, dim3((unsigned)nblocks), dim3(EN_THREADS), 0, s, e, (const int32_t *)dslot, hist2.as<unsigned long long>());
+            h2.resize(heavy.size() * NB);
+            ELBA_HIP(hipMemcpyAsync(h2.data(), hist2.p, heavy.size() * NB * 8, hipMemcpyDeviceToHost, s));
+            ELBA_HIP(hipStreamSynchronize(s));
+        }
     }
-    return ia;
+    // units in ascending order (a 12-bit bin, or one 24-bit prefix of a heavy bin); passes of whole units, balanced as the wide partition's: as many
+    // as the cap needs, each near I / passes.  A unit above the cap is a pass of its own.
+    struct LongPass { uint32_t lo, hi; uint64_t n; };
+    std::vector<LongPass> passes;
+    {
+        const uint64_t npass = (I + cap - 1) / cap, target = (I + npass - 1) / npass;
+        uint32_t lo = 0;
+        uint64_t cnt = 0;
+        size_t hv = 0;
+        auto unit = [&](uint32_t start, uint64_t x) {
+            if (cnt > 0 && (cnt + x > cap || cnt + x / 2 > target)) { passes.push_back(LongPass{lo, start, cnt}); lo = start; cnt = 0; }
+            cnt += x;
+        };
+        for (uint32_t b = 0; b < NB; ++b) {
+            if (hv < heavy.size() && heavy[hv] == b) { for (uint32_t d = 0; d < NB; ++d) unit((b << OWNER_BITS) | d, h2[hv * NB + d]); ++hv; }
+            else unit(b << OWNER_BITS, h1[b]);
+        }
+        passes.push_back(LongPass{lo, 1u << LONG_PREFIX_BITS, cnt});
+    }
+    uint64_t largest = 0;
+    for (const LongPass &p : passes) {
+        if (p.n > largest) largest = p.n;
+        snprintf(why, sizeof why, "count_kmers: the k-mers whose first word begins with the 24-bit prefix 0x%06x%s number %llu instances, more than one pass of the sort "
+                 "holds (2^32)", p.lo, p.hi - p.lo > 1 ? " (and the prefixes up to it)" : "", (unsigned long long)p.n);
+        ELBA_REQUIRE(p.n < 0xFFFFFFF0ull, ELBA_ERR_UNSUPPORTED, why);
+        snprintf(why, sizeof why, "count_kmers: the k-mers whose first word begins with the 24-bit prefix 0x%06x%s number %llu instances: the workspace of their pass "
+                 "(%.1f GB) does not fit beside the columns", p.lo, p.hi - p.lo > 1 ? " (and the prefixes up to it)" : "", (unsigned long long)p.n, pass_b * (double)p.n / 1e9);
+        ELBA_REQUIRE(pass_b * (double)p.n <= room, ELBA_ERR_OUT_OF_MEMORY, why);
+    }
+    if (c.opt.trace) fprintf(stderr, "[elba] count_kmers: %llu instances of %d-word k-mers in %zu value-range passes (cap %llu, largest %llu)\n", (unsigned long long)I, words,
+                             passes.size(), (unsigned long long)cap, (unsigned long long)largest);
+    c.kmer_passes = (int)passes.size(); c.kmer_largest_pass = (int64_t)largest;
+
+    // ---- the passes ----
+    // (the columns of an earlier call and the workspace sized for another input go first: what is freed is what the passes were planned with)
+    for (DevBuf *b : {&c.ws_a, &c.ws_b, &c.ws_c, &c.ws_e, &c.ws_f, &c.rel_kmers, &c.rel_kmers_lo, &c.rel_kmers_lo2, &c.rel_counts, &c.a_colptr, &c.a_csc, &c.kid_of_entry}) b->release();
+    size_t free_base = 0, free_now = 0, total = 0;
+    ELBA_HIP(hipMemGetInfo(&free_base, &total));
+    uint64_t peak = 0;
+    auto checkpoint = [&]() { ELBA_HIP(hipMemGetInfo(&free_now, &total)); if (free_now < free_base && free_base - free_now > peak) peak = free_base - free_now; };
+    struct Staged { DevBuf kmers, lo, lo2, counts, colptr, csc, kid; uint64_t N = 0, Z = 0; };
+    std::unique_ptr<Staged[]> staged(new Staged[passes.size()]);
+    uint64_t kid_base = 0, ent_base = 0, distinct = 0;
+    double ms_count = 0, ms_sort = 0;
+    {
+        DevBuf khi, klo, klo2, val, i0, i1, t0, t1, s2buf, wcnt;
+        for (DevBuf *b : {&khi, &klo, &val, &i0, &i1, &t0, &t1, &c.ws_a, &c.ws_b, &c.ws_c}) b->reserve((size_t)(largest + 2) * 8);
+        if (words == 3) { klo2.reserve((size_t)(largest + 2) * 8); s2buf.reserve((size_t)(largest + 2) * 8); }
+        wcnt.reserve((size_t)(nwaves + 1) * 4);
+        uint32_t *wc = wcnt.as<uint32_t>();
+        uint64_t *shi = c.ws_a.as<uint64_t>(), *slo = c.ws_b.as<uint64_t>(), *sval = c.ws_c.as<uint64_t>(), *slo2 = words == 3 ? s2buf.as<uint64_t>() : nullptr;
+        const uint64_t *wordsrc[3] = {khi.as<uint64_t>(), klo.as<uint64_t>(), words == 3 ? klo2.as<uint64_t>() : nullptr};
+        for (size_t q = 0; q < passes.size(); ++q) {
+            const LongPass &p = passes[q];
+            c.t_a.start(s);
+            ELBA_HIP(hipMemsetAsync(wc + nwaves, 0, 4, s));
+            if (words == 3) hipLaunchKernelGGL(k_long_pass_count<3>, dim3((unsigned)nblocks), dim3(EN_THREADS), 0, s, e, p.lo, p.hi, wc);
+            else hipLaunchKernelGGL(k_long_pass_count<2>, dim3((unsigned)nblocks), dim3(EN_THREADS), 0, s, e, p.lo, p.hi, wc);
+            exclusive_scan_u32(s, wc, wc, (int64_t)nwaves + 1, c.ws_scan);      // (p.n < 2^32: the 32-bit scan cannot wrap)
+            if (words == 3)
+                hipLaunchKernelGGL(k_kmer_emit_range<3>, dim3((unsigned)nblocks), dim3(EN_THREADS), 0, s, e, p.lo, p.hi, (const uint32_t *)wc, p.n, khi.as<uint64_t>(), klo.as<uint64_t>(),
+                                   klo2.as<uint64_t>(), val.as<uint64_t>(), i0.as<uint64_t>());
+            else
+                hipLaunchKernelGGL(k_kmer_emit_range<2>, dim3((unsigned)nblocks), dim3(EN_THREADS), 0, s, e, p.lo, p.hi, (const uint32_t *)wc, p.n, khi.as<uint64_t>(), klo.as<uint64_t>(),
+                                   (uint64_t *)nullptr, val.as<uint64_t>(), i0.as<uint64_t>());
+            uint32_t got = 0;
+            ELBA_HIP(hipMemcpyAsync(&got, wc + nwaves, 4, hipMemcpyDeviceToHost, s));
+            ELBA_HIP(hipStreamSynchronize(s));
+            ELBA_REQUIRE(got == p.n, ELBA_ERR_INTERNAL, "count_kmers: a value-range pass emitted another number of instances than its plan counted");
+            if (p.n > 0) sort_long_kmers(c, words, p.n, wordsrc, val.as<uint64_t>(), i0.as<uint64_t>(), i1.as<uint64_t>(), t0.as<uint64_t>(), t1.as<uint64_t>(), shi, slo, slo2, sval);
+            c.t_a.stop(s);
+            c.t_b.start(s);
+            uint64_t nruns = 0, N = 0, Z = 0;
+            ColumnBase base;
+            base.kid = kid_base; base.ent = (uint32_t)ent_base; base.exact = true;
+            runs_to_columns(c, shi, sval, p.n, nruns, N, Z, slo, slo2, 0, 0, base);
+            c.t_b.stop(s);
+            ms_count += c.t_a.ms(); ms_sort += c.t_b.ms();
+            Staged &g = staged[q];
+            g.kmers.swap(c.rel_kmers); g.lo.swap(c.rel_kmers_lo); g.lo2.swap(c.rel_kmers_lo2); g.counts.swap(c.rel_counts); g.colptr.swap(c.a_colptr);
+            g.csc.swap(c.a_csc); g.kid.swap(c.kid_of_entry);
+            g.N = N; g.Z = Z;
+            kid_base += N; ent_base += Z; distinct += nruns;
+            checkpoint();
+        }
+    }
+    c.ws_a.release(); c.ws_b.release(); c.ws_c.release();
+    // ---- the context's arrays: the staged pieces, concatenated (a pass's pieces of one kind are freed once its copy is done) ----
+    const uint64_t N = kid_base, Z = ent_base;
+    auto concat = [&](DevBuf &dst, size_t bytes, DevBuf Staged::*m, size_t elem, bool per_entry) {
+        dst.reserve(bytes);
+        checkpoint();
+        uint64_t at = 0;
+        for (size_t q = 0; q < passes.size(); ++q) {
+            const uint64_t n = per_entry ? staged[q].Z : staged[q].N;
+            if (n) ELBA_HIP(hipMemcpyAsync(dst.as<char>() + at * elem, (staged[q].*m).p, (size_t)n * elem, hipMemcpyDeviceToDevice, s));
+            at += n;
+        }
+        ELBA_HIP(hipStreamSynchronize(s));
+        for (size_t q = 0; q < passes.size(); ++q) (staged[q].*m).release();
+    };
+    concat(c.a_csc, (size_t)(Z + 8) * 8, &Staged::csc, 8, true);      // (+ guard entries, matrix.hip)
+    concat(c.kid_of_entry, (size_t)(Z + 8) * 8, &Staged::kid, 8, true);
+    concat(c.rel_kmers, (size_t)(N + 1) * 8, &Staged::kmers, 8, false);
+    concat(c.rel_kmers_lo, (size_t)(N + 1) * 8, &Staged::lo, 8, false);
+    if (words == 3) concat(c.rel_kmers_lo2, (size_t)(N + 1) * 8, &Staged::lo2, 8, false);
+    concat(c.rel_counts, (size_t)(N + 2) * 4, &Staged::counts, 4, false);
+    concat(c.a_colptr, (size_t)(N + 2) * 4, &Staged::colptr, 4, false);
+    const uint32_t Zz = (uint32_t)Z;
+    ELBA_HIP(hipMemcpyAsync(c.a_colptr.as<uint32_t>() + N, &Zz, 4, hipMemcpyHostToDevice, s));
+    c.t_total.stop(s);
+    ELBA_HIP(hipStreamSynchronize(s));
+    c.kmer_peak_bytes = (int64_t)peak;
+    st.instances = (int64_t)I; st.distinct = (int64_t)distinct; st.reliable = (int64_t)N; st.entries = (int64_t)Z;
+    st.ms_total = c.t_total.ms(); st.ms_count = ms_count; st.ms_sort = ms_sort; st.ms_lookup = 0;
+    c.ndistinct = (int64_t)distinct;
+    c.N = (int64_t)N; c.Z = (int64_t)Z;
+    c.kstats = st;
+    c.have_counts = true;
+    return true;
 }
 
 // the owners' boundaries set by elba_dist_set_owner_ranges (one rank: everything is rank 0's; otherwise they must have been set for this world size)

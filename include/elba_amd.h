@@ -343,15 +343,19 @@ int  elba_get_device_view(elba_ctx *ctx, elba_device_view *view);
  *       multiplies every matrix once pays — the reference's create_seed_matrix is called once per A (src/main.cpp:281).  Buffers stay
  *       allocated.  Default 0.
  *   "kmer_batch_instances" (>= 0): LIMITS.  The reference batches its k-mer exchange so that the input's size is no limit
- *       (include/KmerOps.hpp:10-12,33-56).  Here a context counts any number of k-mer instances for 9 <= k <= 31 — more than this option allows at
+ *       (include/KmerOps.hpp:10-12,33-56).  Here a context counts any number of k-mer instances for 9 <= k <= 95 — more than this option allows at
  *       once (0, the default: 0xE0000000, what a 32-bit place holds) are counted in PASSES over ranges of the k-mer value (consecutive first
  *       digits of the value partition — 19 <= k <= 31: of its coarse digit, the leading 10 bits of the flattened value, each pass partitioned
- *       finer inside its own range —: the passes yield consecutive k-mer ids and consecutive stretches of the columns; every pass enumerates the
- *       reads again and the whole input is counted twice — once for the sizes A's layout depends on, once to write it) — bounded by device memory
- *       (16 bytes per instance of the largest pass for k <= 17, 32 for 19 <= k <= 31) and by nnz(A) < 2^32 per context (32-bit row / column
- *       pointers).  Tests set a small value to force passes; the result does not depend on it.  What still holds 32-bit places and refuses more
- *       than 2^32 instances with ELBA_ERR_UNSUPPORTED: k > 31 (the sort), 19 <= k <= 31 with UPPER > 255, option "kmer_no_msd", and
- *       elba_set_kmer_matrix_device (triples).
+ *       finer inside its own range; k > 31: ranges of the leading 24 bits of the first word —: the passes yield consecutive k-mer ids and
+ *       consecutive stretches of the columns; every pass enumerates the reads again — k <= 31: the whole input is counted twice, once for the
+ *       sizes A's layout depends on, once to write it; k > 31: each pass's columns are staged and concatenated at the end) — bounded by device
+ *       memory (16 bytes per instance of the largest pass for k <= 17, 32 for 19 <= k <= 31, 80 / 96 for two- / three-word k-mers, whose
+ *       columns are also staged) and by nnz(A) < 2^32 per context (32-bit row / column pointers).  For k > 31 the sort also takes passes, whatever
+ *       this option says, when one pass would not fit the device memory free as elba_count_kmers starts (its workspace, 92 / 108 bytes per
+ *       instance, and the columns at their largest), or at 2^32 instances; a single 24-bit prefix that holds 2^32 instances or whose pass does
+ *       not fit fails with ELBA_ERR_UNSUPPORTED / ELBA_ERR_OUT_OF_MEMORY, naming it.  Tests set a small value to force passes; the result does not
+ *       depend on it.  What still holds 32-bit places and refuses more than 2^32 instances with ELBA_ERR_UNSUPPORTED: 19 <= k <= 31 with
+ *       UPPER > 255, option "kmer_no_msd", and elba_set_kmer_matrix_device (triples).
  *   "measure_prep" (0 | 1): diagnostic — elba_count_kmers runs its emit kernels a second time without what they write for the SpGEMM's sake alone and
  *       brackets both runs with events (elba_get_stat "spgemm_prep_us").
  *   "tune0" .. "tune7": A/B switches of the round in progress (what each means is said where the library reads it); never a result-changing switch. */
@@ -371,6 +375,8 @@ int  elba_set_option(elba_ctx *ctx, const char *name, int64_t value);
  *   "gather_slots"           columns of the padded column store in use (with inline partners: only the columns some row entry still fetches)
  *   "kmer_passes"            value-range passes the last elba_count_kmers took, either partition path (1: the whole input at once; option "kmer_batch_instances")
  *   "kmer_largest_pass"      instances of its largest value-range pass (a pass holds whole first digits: it may exceed the cap; I when unbatched)
+ *   "kmer_peak_bytes"        k > 31 in value-range passes: device bytes the call's passes and column assembly held at their high point, measured
+ *                            (hipMemGetInfo); 0 when the call took one pass
  *   "kmer_crowded_buckets"   buckets it gave up to a crowded path (19 <= k <= 31: the pseudo-bucket path; k <= 17: the windowed bucket kernel)
  *   "kmer_crowded_small"     19 <= k <= 31: crowded buckets whose kept entries (0 < Z <= the emit kernels' largest class) would fit an ordinary emit
  *   "kmer_buckets"           buckets of the value partition, summed over the passes (0: the sort) — with kmer_crowded_buckets (summed too), the share
