@@ -13,7 +13,12 @@ hint bits per entry — "under the parity rule that assigns every pair of rows t
 column": such an entry (40 % of them on this workload) does not fetch its column.  Every timed step runs COLD
 (elba_set_option "overlap_cold_calls"): it forgets what earlier calls on the same matrix learned (the distinct-partner ratio that picks
 the starting table tiers, which tiers and column sorts received rows), so that each step is what a caller that multiplies a matrix once
-pays, as ELBA does.  Buffers stay allocated.  The steady state (hints kept between calls) is reported as a secondary key.
+pays, as ELBA does.  Buffers stay allocated.
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line: the headline and what the timed steps and the
+build of A already measured (roofline of the step, k-mer stage, counts against the one-GPU build).  Everything that takes runs of its own
+is behind `--full`: the steady state (hints kept between calls), the HBM-table tier forced, the SpGEMM-only preparation of A, A handed over
+as device triples, and the CPU baselines with the oracle's parity on a sample and on the whole matrix.  Their keys are null without it.
 
 Workload at N = 1: BASELINE.json configs[2] restated per SURVEY.md §8d-3 ("200k-long-reads": 200 100 reads of ~10 kb, 66.7 Mb genome,
 30x, 15 % sub/ins/del error, k=17, L=2, U=8, seed 2) — the configuration the metric's scaling is quoted on, and it fits one GPU.
@@ -148,11 +153,13 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="200k-long-reads", choices=sorted(WORKLOADS))
-    ap.add_argument("--steady-steps", type=int, default=10, help="untimed-by-the-contract steps with the hints of earlier calls kept (secondary figure)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-accounting", action="store_true", help="skip spgemm_prep / from_triples (two more contexts)")
-    ap.add_argument("--cpu-sample-div", type=int, default=0, help="CPU baseline, one-core leg: the same generator with the genome divided by this (0: chosen for ~10-30 s of CPU work)")
-    ap.add_argument("--no-cpu-full", action="store_true", help="skip the all-cores CPU baseline on the WHOLE workload matrix (and the entry-by-entry comparison of B with it)")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beyond the headline: steady state, HBM-table tier, "
+                    "spgemm_prep / from_triples, CPU baselines and the oracle's parity (about 45 s more on the default workload)")
+    ap.add_argument("--steady-steps", type=int, default=10, help="--full: untimed-by-the-contract steps with the hints of earlier calls kept (secondary figure)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines and the oracle's parity")
+    ap.add_argument("--no-accounting", action="store_true", help="--full: skip the forced HBM-table tier and spgemm_prep / from_triples (two more contexts)")
+    ap.add_argument("--cpu-sample-div", type=int, default=0, help="--full, CPU baseline, one-core leg: the same generator with the genome divided by this (0: chosen for ~10-30 s of CPU work)")
+    ap.add_argument("--no-cpu-full", action="store_true", help="--full: skip the all-cores CPU baseline on the WHOLE workload matrix (and the entry-by-entry comparison of B with it)")
     ap.add_argument("--timing-stride", type=int, default=4, help="the library records its phase events (kernel_ms of the roofline) on every N-th step only: "
                     "an event record costs ~5 us of stream time; kernel_ms is the mean over the steps that were measured")
     ap.add_argument("--aux", action="store_true", help="N = 1: also run the stages on either side of the path once (FASTA ingest, x-drop alignment, string graph); "
@@ -301,7 +308,7 @@ def main():
     # ---- secondary: the steady state (the hints of earlier calls kept: starting tiers from the measured ratio, unused tiers not launched)
     eng.set_option("overlap_cold_calls", 0)
     steady = None
-    if args.steady_steps > 0:
+    if args.full and args.steady_steps > 0:
         for _ in range(2):
             step()
         barrier_sync()
@@ -393,8 +400,9 @@ def main():
     #     elba_set_kmer_matrix_device rebuilds CSR + columns + hints, then ONE cold call.
     # what the HBM-table tier costs when every row is FORCED onto it: two cold calls with "tune7" = 6 (k_classify_direct queues every row on the
     # spill tier: tables in HBM instead of LDS), the second one timed; same B by count
+    accounting = args.full and single and rank == 0 and not args.no_accounting
     hbm_forced = None
-    if single and rank == 0 and not args.no_accounting:
+    if accounting:
         eng.set_option("tune7", 6); eng.set_option("overlap_cold_calls", 1)
         try:
             eng.create_seed_matrix(); torch.cuda.synchronize()
@@ -408,9 +416,9 @@ def main():
         eng.create_seed_matrix(); torch.cuda.synchronize()      # (the context holds the LDS-tier result again: exports and the CPU comparison below read it)
     prep = None
     from_triples = None
-    if single and rank == 0 and not args.no_accounting and args.workload.startswith("dense-repeats-8"):
+    if accounting and args.workload.startswith("dense-repeats-8"):
         prep = {"skipped": "two more contexts of this size do not fit beside the timed one"}
-    elif single and rank == 0 and not args.no_accounting:
+    elif accounting:
         # (round 5) measured by EVENTS inside the k-mer stage: with the option "measure_prep" elba_count_kmers runs its emit kernels a second time without the
         # hint bits, inline partners, gather slots and padded columns (they are the only kernels that write them), both runs bracketed by events on the
         # library's stream: elba_get_stat("spgemm_prep_us") = the difference of two ~11 ms device times (round 4 subtracted two ~50 ms host-clock runs of
@@ -472,7 +480,7 @@ def main():
     # ---- CPU baseline + parity on a bounded sample of the same workload (rank 0, N = 1) ------------------------------------------------
     cpu = None
     parity = None
-    if rank == 0 and single and not args.no_cpu_baseline:
+    if args.full and rank == 0 and single and not args.no_cpu_baseline:
         from oracle import pyoracle as po   # checker + CPU baseline only
         # the sample: the same generator (lengths, depth, error, k, L, U), genome divided so that the oracle's SpGEMM is ~10-30 s of CPU work
         div = args.cpu_sample_div or max(1, int(round(P / 1.5e8)))
@@ -591,7 +599,7 @@ def main():
         out = {
             "metric": "overlap nnz/sec (A·Aᵀ SpGEMM, SharedSeeds semiring, after Prune(numshared<=1))",
             "value": round(Y / (dt / steps), 1), "unit": "overlap nnz/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(ms_step, 4), "higher_is_better": True, "scaling": "weak" if (args.weak and world > 1) else "strong", "vs_baseline": None, "dtype": "u32",
+            "ms_per_step": round(ms_step, 4), "higher_is_better": True, "full": bool(args.full), "scaling": "weak" if (args.weak and world > 1) else "strong", "vs_baseline": None, "dtype": "u32",
             "data": "synthetic",
             "transport": None if dist is None else {
                 "backend": "RCCL (torch.distributed backend nccl)" if backend == "nccl" else "REHEARSAL: %s over host copies, %d processes on %d device(s) — not a scaling measurement" % (backend, world, torch.cuda.device_count()),
