@@ -87,6 +87,20 @@ class Contigs(C.Structure):
                 ("chain_prefix", C.c_void_p), ("chain_strand", C.c_void_p)]
 
 
+class PileupCfg(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("margin", C.c_int32), ("min_depth", C.c_int32), ("min_run", C.c_int32), ("trim_len", C.c_int32), ("reserved", C.c_int32)]
+
+
+class PileupStats(C.Structure):
+    _fields_ = [("nreads", C.c_int64), ("pairs", C.c_int64), ("intervals", C.c_int64), ("segments", C.c_int64), ("max_depth", C.c_int64),
+                ("unsupported", C.c_int64), ("split", C.c_int64), ("trimmed", C.c_int64), ("trimmed_bases", C.c_int64), ("ms_total", C.c_float), ("reserved", C.c_float)]
+
+
+class Pileup(C.Structure):
+    _fields_ = [("n", C.c_int64), ("nseg", C.c_int64), ("seg_off", C.c_void_p), ("seg_start", C.c_void_p), ("seg_depth", C.c_void_p),
+                ("trim_beg", C.c_void_p), ("trim_end", C.c_void_p), ("flags", C.c_void_p)]
+
+
 class Overlaps(C.Structure):
     _fields_ = [("n", C.c_int64), ("rows", C.c_void_p), ("cols", C.c_void_p), ("vals", C.c_void_p)]
 
@@ -139,6 +153,7 @@ EXPORTED_SYMBOLS = [
     "elba_dist_set_global_kmers", "elba_dist_panel_counts", "elba_dist_panel_fill", "elba_dist_panel_counts_win", "elba_dist_panel_fill_win", "elba_dist_set_panel",
     "elba_seed_matrix_begin", "elba_seed_matrix_fill", "elba_seed_matrix_end", "elba_set_stream", "elba_seed_matrix_send", "elba_seed_matrix_recv", "elba_set_kmer_matrix_device", "elba_export_triples_device", "elba_get_stat", "elba_release_workspace",
     "elba_generate_contigs", "elba_export_contigs", "elba_free_contigs", "elba_export_read_contigs",
+    "elba_read_pileup", "elba_export_pileup", "elba_free_pileup", "elba_prune_reads",
 ]
 
 _lib = None
@@ -192,6 +207,10 @@ def load_library():
     L.elba_export_contigs.restype = i32; L.elba_export_contigs.argtypes = [vp, C.POINTER(Contigs)]
     L.elba_free_contigs.restype = None; L.elba_free_contigs.argtypes = [C.POINTER(Contigs)]
     L.elba_export_read_contigs.restype = i32; L.elba_export_read_contigs.argtypes = [vp, vp, i64]
+    L.elba_read_pileup.restype = i32; L.elba_read_pileup.argtypes = [vp, C.POINTER(PileupCfg), C.POINTER(PileupStats)]
+    L.elba_export_pileup.restype = i32; L.elba_export_pileup.argtypes = [vp, C.POINTER(Pileup)]
+    L.elba_free_pileup.restype = None; L.elba_free_pileup.argtypes = [C.POINTER(Pileup)]
+    L.elba_prune_reads.restype = i32; L.elba_prune_reads.argtypes = [vp, i32, C.POINTER(C.c_int64)]
     L.elba_export_dcsc.restype = i32; L.elba_export_dcsc.argtypes = [vp, i64, i64, i64, i64, C.POINTER(Dcsc)]
     L.elba_free_dcsc.restype = None; L.elba_free_dcsc.argtypes = [C.POINTER(Dcsc)]
     L.elba_export_csr.restype = i32; L.elba_export_csr.argtypes = [vp, i64, i64, C.POINTER(Csr)]
@@ -429,6 +448,34 @@ class Engine:
         out = np.zeros(int(nreads), dtype=np.int64)
         self._check(self.L.elba_export_read_contigs(self.h, out.ctypes.data, int(nreads)))
         return out
+
+    # --- read pileups and chimera flags (src/PruneChimeras.cpp; after align_seeds, before transitive_reduction) ---
+    def read_pileup(self, mode=0, margin=0, min_depth=1, min_run=1, trim_len=2500):
+        """Per-read coverage from the pairs transitive_reduction would read (both reads of a pair credited), the trimmed interval by
+        GetTrimmedInterval's rule (best run returned) and the flags (bit 0 unsupported, bit 1 split).  Returns the stats."""
+        cfg = PileupCfg(int(mode), int(margin), int(min_depth), int(min_run), int(trim_len), 0)
+        st = PileupStats()
+        self._check(self.L.elba_read_pileup(self.h, C.byref(cfg), C.byref(st)))
+        d = _stats(st)
+        d.pop("reserved", None)
+        return d
+
+    def export_pileup(self):
+        """{n, seg_off (i64[n+1]), seg_start, seg_depth (i32), trim_beg, trim_end (i32[n]), flags (u8[n])}."""
+        o = Pileup()
+        self._check(self.L.elba_export_pileup(self.h, C.byref(o)))
+        try:
+            n, S = o.n, o.nseg
+            return dict(n=n, seg_off=_copy(o.seg_off, n + 1, np.int64), seg_start=_copy(o.seg_start, S, np.int32), seg_depth=_copy(o.seg_depth, S, np.int32),
+                        trim_beg=_copy(o.trim_beg, n, np.int32), trim_end=_copy(o.trim_end, n, np.int32), flags=_copy(o.flags, n, np.uint8))
+        finally:
+            self.L.elba_free_pileup(C.byref(o))
+
+    def prune_reads(self, mask):
+        """PruneFull of the reads with flags & mask: the kept pairs become the edge list transitive_reduction reads next.  Returns their count."""
+        kept = C.c_int64(0)
+        self._check(self.L.elba_prune_reads(self.h, int(mask), C.byref(kept)))
+        return int(kept.value)
 
     # --- outputs ---
     def export_csr(self, row_lo=0, row_hi=None):

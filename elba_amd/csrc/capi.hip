@@ -139,7 +139,7 @@ int elba_set_reads(elba_ctx *ctx, const uint8_t *packed, const uint64_t *byte_of
         c.h_byte_off.assign(byte_off, byte_off + nreads);
         c.nreads = nreads; c.first_global_id = first_global_id; c.packed_bytes = pb;
         // a new read set invalidates everything derived from the old one (as stage_set_reads_fasta does)
-        c.have_reads = true; c.have_counts = false; c.have_aln = false; c.have_edges = false; c.have_S = false;
+        c.have_reads = true; c.have_counts = false; c.have_aln = false; c.have_edges = false; c.have_S = false; c.have_pileup = false;
         if (c.A_has_kmers) { c.have_A = false; c.have_B = false; }      // (an A handed over as triples / a panel does not come from these reads)
     });
 }
@@ -147,7 +147,10 @@ int elba_set_reads(elba_ctx *ctx, const uint8_t *packed, const uint64_t *byte_of
 int elba_set_reads_fasta(elba_ctx *ctx, const char *chunk, int64_t chunk_bytes, uint64_t chunk_file_offset, const elba_fasta_record_t *recs, int64_t nreads,
                          int64_t first_global_id, elba_ingest_stats *stats)
 {
-    return guarded(ctx, [&](Ctx &c) { stage_set_reads_fasta(c, chunk, chunk_bytes, chunk_file_offset, recs, nreads, first_global_id, stats); });
+    return guarded(ctx, [&](Ctx &c) {
+        c.have_pileup = false;
+        stage_set_reads_fasta(c, chunk, chunk_bytes, chunk_file_offset, recs, nreads, first_global_id, stats);
+    });
 }
 
 int elba_export_reads(elba_ctx *ctx, uint8_t *packed, int64_t packed_capacity, uint64_t *byte_off, uint32_t *len, int64_t nreads_capacity)
@@ -183,7 +186,7 @@ int elba_set_reads_device(elba_ctx *ctx, const void *d_packed, int64_t packed_by
             ELBA_REQUIRE((int64_t)c.h_byte_off[r] + ((int64_t)c.h_len[r] + 3) / 4 <= packed_bytes, ELBA_ERR_INVALID_ARG, "set_reads_device: read exceeds the packed buffer");
         c.nreads = nreads; c.first_global_id = first_global_id; c.packed_bytes = packed_bytes;
         // a new read set invalidates everything derived from the old one (as stage_set_reads_fasta does)
-        c.have_reads = true; c.have_counts = false; c.have_aln = false; c.have_edges = false; c.have_S = false;
+        c.have_reads = true; c.have_counts = false; c.have_aln = false; c.have_edges = false; c.have_S = false; c.have_pileup = false;
         if (c.A_has_kmers) { c.have_A = false; c.have_B = false; }      // (an A handed over as triples / a panel does not come from these reads)
     });
 }
@@ -291,6 +294,7 @@ int elba_seed_matrix_end(elba_ctx *ctx, const void *d_recv, int64_t nrecords, el
 int elba_align_seeds(elba_ctx *ctx, int mat, int mis, int gap, int dropoff, elba_align_stats *stats)
 {
     return guarded(ctx, [&](Ctx &c) {
+        c.have_pileup = false;                                      // new alignments invalidate the pileup of the old ones, whatever this call ends in
         stage_align_seeds(c, mat, mis, gap, dropoff);
         if (stats) *stats = c.astats;
     });
@@ -298,7 +302,10 @@ int elba_align_seeds(elba_ctx *ctx, int mat, int mis, int gap, int dropoff, elba
 
 int elba_dist_set_all_reads(elba_ctx *ctx, const void *d_packed, int64_t packed_bytes, const void *d_byte_off, const void *d_len, int64_t nreads_total)
 {
-    return guarded(ctx, [&](Ctx &c) { stage_dist_set_all_reads(c, d_packed, packed_bytes, d_byte_off, d_len, nreads_total); });
+    return guarded(ctx, [&](Ctx &c) {
+        c.have_pileup = false;
+        stage_dist_set_all_reads(c, d_packed, packed_bytes, d_byte_off, d_len, nreads_total);
+    });
 }
 
 int elba_export_overlaps(elba_ctx *ctx, elba_overlaps_t *out)
@@ -329,7 +336,10 @@ void elba_free_overlaps(elba_overlaps_t *o)
 
 int elba_set_overlaps(elba_ctx *ctx, int64_t nreads, const int64_t *rows, const int64_t *cols, const elba_overlap_t *vals, int64_t n)
 {
-    return guarded(ctx, [&](Ctx &c) { stage_set_overlaps(c, nreads, rows, cols, vals, n); });
+    return guarded(ctx, [&](Ctx &c) {
+        c.have_pileup = false;
+        stage_set_overlaps(c, nreads, rows, cols, vals, n);
+    });
 }
 
 int elba_transitive_reduction(elba_ctx *ctx, double bad_read_cutoff, int fuzz, elba_string_stats *stats)
@@ -418,6 +428,56 @@ int elba_export_read_contigs(elba_ctx *ctx, int64_t *contig_of_read, int64_t nre
         const std::vector<int32_t> h = download<int32_t>(c, c.cg_cid.p, (size_t)nreads);
         for (int64_t v = 0; v < nreads; ++v) contig_of_read[v] = h[(size_t)v];
     });
+}
+
+int elba_read_pileup(elba_ctx *ctx, const elba_pileup_cfg *cfg, elba_pileup_stats *stats)
+{
+    return guarded(ctx, [&](Ctx &c) {
+        c.have_pileup = false;
+        ELBA_REQUIRE(cfg, ELBA_ERR_INVALID_ARG, "read_pileup: null cfg");
+        stage_read_pileup(c, *cfg);
+        if (stats) *stats = c.pustats;
+    });
+}
+
+int elba_export_pileup(elba_ctx *ctx, elba_pileup_t *out)
+{
+    return guarded(ctx, [&](Ctx &c) {
+        ELBA_REQUIRE(out, ELBA_ERR_INVALID_ARG, "export_pileup: null output");
+        memset(out, 0, sizeof(*out));
+        ELBA_REQUIRE(c.have_pileup, ELBA_ERR_STATE, "export_pileup: no pileup of the current overlaps (call elba_read_pileup)");
+        const int64_t n = c.pu_M, S = c.pu_nseg;
+        elba_pileup_t o{};
+        o.n = n; o.nseg = S;
+        o.seg_off = host_alloc<int64_t>((size_t)n + 1); o.seg_start = host_alloc<int32_t>((size_t)S); o.seg_depth = host_alloc<int32_t>((size_t)S);
+        o.trim_beg = host_alloc<int32_t>((size_t)n); o.trim_end = host_alloc<int32_t>((size_t)n); o.flags = host_alloc<uint8_t>((size_t)n);
+        *out = o;                                                   // (allocated before any copy: elba_free_pileup releases them if a copy fails)
+        hipStream_t s = c.stream;
+        ELBA_HIP(hipMemcpyAsync(o.seg_off, c.pu_seg_off.p, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, s));
+        if (S) {
+            ELBA_HIP(hipMemcpyAsync(o.seg_start, c.pu_seg_start.p, (size_t)S * 4, hipMemcpyDeviceToHost, s));
+            ELBA_HIP(hipMemcpyAsync(o.seg_depth, c.pu_seg_depth.p, (size_t)S * 4, hipMemcpyDeviceToHost, s));
+        }
+        std::vector<int32_t> trim((size_t)(2 * n));
+        if (n) {
+            ELBA_HIP(hipMemcpyAsync(trim.data(), c.pu_trim.p, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+            ELBA_HIP(hipMemcpyAsync(o.flags, c.pu_flags.p, (size_t)n, hipMemcpyDeviceToHost, s));
+        }
+        ELBA_HIP(hipStreamSynchronize(s));
+        for (int64_t v = 0; v < n; ++v) { o.trim_beg[v] = trim[(size_t)(2 * v)]; o.trim_end[v] = trim[(size_t)(2 * v + 1)]; }
+    });
+}
+
+void elba_free_pileup(elba_pileup_t *p)
+{
+    if (!p) return;
+    free(p->seg_off); free(p->seg_start); free(p->seg_depth); free(p->trim_beg); free(p->trim_end); free(p->flags);
+    memset(p, 0, sizeof(*p));
+}
+
+int elba_prune_reads(elba_ctx *ctx, int mask, int64_t *kept)
+{
+    return guarded(ctx, [&](Ctx &c) { stage_prune_reads(c, mask, kept); });
 }
 
 int elba_export_csr(elba_ctx *ctx, int64_t row_lo, int64_t row_hi, elba_csr_t *out)
@@ -609,6 +669,8 @@ int elba_release_workspace(elba_ctx *ctx)
         c.cg_ptr.release(); c.cg_slot.release(); c.cg_kdeg.release(); c.cg_term.release(); c.cg_vinfo.release(); c.cg_ctr.release();   // contig scratch (the results stay)
         c.cg_flag.release(); c.cg_cidx.release(); c.cg_nel.release(); c.cg_eoff.release();
         for (int b = 0; b < 2; ++b) { c.cg_far[b].release(); c.cg_rank[b].release(); c.cg_mn[b].release(); }
+        c.pu_k0.release(); c.pu_k1.release(); c.pu_eptr.release(); c.pu_head.release(); c.pu_hidx.release(); c.pu_delta.release();   // pileup scratch (the results stay)
+        c.pu_dsum.release(); c.pu_gstart.release(); c.pu_tok.release(); c.pu_tpos.release(); c.pu_sel.release(); c.pu_rows.release(); c.pu_cols.release(); c.pu_vals.release();
         if (c.have_counts) { c.pre_ready = false; c.pre_consumed = true; }    // (the CSR sort keys / column ids of the entries are gone: create_kmer_matrix rebuilds them from the column pointers)
     });
 }

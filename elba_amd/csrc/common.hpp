@@ -310,6 +310,14 @@ struct Ctx {
     EventTimer cg_t_total, cg_t_rank;
     elba_contig_stats cstats{};
 
+    // read pileups (pileup.hip): results (seg_off, seg_start, seg_depth, trim, flags) survive elba_release_workspace, the rest is scratch
+    bool have_pileup = false;
+    int64_t pu_M = 0, pu_n = 0, pu_nseg = 0;
+    DevBuf pu_k0, pu_k1, pu_eptr, pu_head, pu_hidx, pu_delta, pu_dsum, pu_gstart, pu_tok, pu_tpos, pu_ctr, pu_sel, pu_rows, pu_cols, pu_vals;
+    DevBuf pu_seg_off, pu_seg_start, pu_seg_depth, pu_trim, pu_flags;
+    EventTimer pu_t_total;
+    elba_pileup_stats pustats{};
+
     // workspaces
     DevBuf ws_scan, ws_sort, ws_a, ws_b, ws_c, ws_d, ws_e, ws_f;
     DevBuf ws_cursor;       // the gather-slot cursor of the k-mer stage's emit kernels (kmer_msd.hip)
@@ -371,6 +379,8 @@ void stage_dist_set_all_reads(Ctx &c, const void *d_packed, int64_t packed_bytes
 void stage_set_overlaps(Ctx &c, int64_t nreads, const int64_t *rows, const int64_t *cols, const elba_overlap_t *vals, int64_t n);   // tr.hip
 void stage_transitive_reduction(Ctx &c, double bad_read_cutoff, int fuzz);   // tr.hip
 void stage_generate_contigs(Ctx &c);                                          // contig.hip
+void stage_read_pileup(Ctx &c, const elba_pileup_cfg &cfg);                   // pileup.hip
+void stage_prune_reads(Ctx &c, int mask, int64_t *kept);
 void stage_dist_count_owners(Ctx &c, int nranks, uint64_t *counts_host);                                   // kmer.hip
 void stage_dist_value_histogram(Ctx &c, uint64_t *hist_host, int64_t nbins);
 void stage_ref_hash_owner(Ctx &c, const uint64_t *kmers_host, int64_t n, int nprocs, uint64_t *hash_host, int32_t *owner_host);

@@ -129,6 +129,15 @@ class HipBackend:
     def export_read_flags(self, nreads):
         return self.e.export_read_flags(nreads)
 
+    def read_pileup(self, mode, margin, min_depth, min_run, trim_len):
+        return self.e.read_pileup(mode, margin, min_depth, min_run, trim_len)
+
+    def export_pileup(self):
+        return self.e.export_pileup()
+
+    def prune_reads(self, mask):
+        return self.e.prune_reads(mask)
+
     def value_histogram(self):
         out = np.zeros(OWNER_BINS, dtype=np.uint64)
         self.e._check(self.L.elba_dist_value_histogram(self.h, out.ctypes.data, OWNER_BINS))
@@ -316,6 +325,7 @@ class DistributedOverlap:
         self.exchange_chunks = 0          # rounds of the packed exchange #1 (0: four once a peer's message reaches 4 M records, else one; 1: never chunked; n > 1: n rounds)
         self.exchange_rounds = 1          # (what the last build used)
         self.exchange_format = None
+        self._pruned = False              # prune_reads left the gathered, pruned list loaded: the next transitive_reduction reduces it as it is
 
     # ---- inputs -----------------------------------------------------------------------------------------------------
     def set_reads(self, packed, off, lens, first_global_id, bounds):
@@ -697,7 +707,15 @@ class DistributedOverlap:
         """src/main.cpp:305-312 across ranks.  The aligned pairs are small next to everything before them (52 bytes per pair): every
         rank gathers the others' shares with ONE all-gather, merges them into (row, col) order and runs the whole reduction itself —
         replicas, no further exchange (the reference runs a distributed SpGEMM and several distributed element-wise passes here).
-        Every rank ends up holding all of S; export_string_graph(local=True) cuts out the rows of this rank's reads."""
+        Every rank ends up holding all of S; export_string_graph(local=True) cuts out the rows of this rank's reads.  After prune_reads the
+        pruned list already loaded is reduced as it is."""
+        if not self._pruned:
+            self._load_gathered_overlaps()
+        self._pruned = False
+        return self.be.transitive_reduction(bad_read_cutoff, fuzz)
+
+    def _load_gathered_overlaps(self):
+        """Every rank's aligned pairs, gathered with ONE all-gather and merged into (row, col) order, loaded as this rank's edge list."""
         torch = self.be.torch
         g = self.be.export_overlaps()
         n = int(g["n"])
@@ -714,7 +732,24 @@ class DistributedOverlap:
         order = np.lexsort((cols, rows))
         m_total = int(self.bounds[-1])
         self.be.set_overlaps(m_total, rows[order], cols[order], vals[order])
-        return self.be.transitive_reduction(bad_read_cutoff, fuzz)
+
+    # ---- between the two: read pileups and chimera flags (src/PruneChimeras.cpp) ---------------------------------------------
+    def read_pileup(self, mode=0, margin=0, min_depth=1, min_run=1, trim_len=2500):
+        """elba_read_pileup across ranks: the same gathered list transitive_reduction loads (one all-gather, merged), so every rank holds
+        every read's profile, trimmed interval and flags (the replicated reads of align_seeds give the lengths)."""
+        self._load_gathered_overlaps()
+        self._pruned = False
+        return self.be.read_pileup(mode, margin, min_depth, min_run, trim_len)
+
+    def export_pileup(self):
+        return self.be.export_pileup()
+
+    def prune_reads(self, mask):
+        """PruneFull of the flagged reads on the gathered list, on every rank alike; the next transitive_reduction reduces what is left
+        instead of gathering again."""
+        kept = self.be.prune_reads(mask)
+        self._pruned = True
+        return kept
 
     def export_string_graph(self, local=False):
         S = self.be.export_string_graph()

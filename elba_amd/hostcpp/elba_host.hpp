@@ -408,6 +408,96 @@ inline std::unique_ptr<StringGraph> TransitiveReduction(const DnaBuffer &myreads
     return S;
 }
 
+// PileupVector (include/PruneChimeras.hpp:11-26): here a read's coverage is held as the (start, depth) segments elba_export_pileup returns;
+// the per-base vector of the reference is built from them on request.
+class PileupVector {
+public:
+    int length = 0;
+    std::vector<int> seg_start, seg_depth;      // maximal runs of equal depth, starts ascending from 0, the last ends at length
+    std::tuple<int, int> trimmed{-1, -1};       // what elba_read_pileup computed: [beststart, bestend + 1) or (-1, -1)
+    uint8_t flags = 0;                          // bit 0 unsupported, bit 1 split
+    int Length() const { return length; }
+    std::vector<int> pileup() const
+    {
+        std::vector<int> v((size_t)length, 0);
+        for (size_t j = 0; j < seg_start.size(); ++j) {
+            const int e = j + 1 < seg_start.size() ? seg_start[j + 1] : length;
+            for (int i = seg_start[j]; i < e; ++i) v[(size_t)i] = seg_depth[j];
+        }
+        return v;
+    }
+    // GetTrimmedInterval (src/PruneChimeras.cpp:30-69) on the per-base vector, with the best run returned (the reference returns the run still
+    // open at the last base) half-open; maxlen = the reference's starting 2500.  The host restatement the device's `trimmed` is held against.
+    std::tuple<int, int> GetTrimmedInterval(int threshold, int maxlen = 2500) const
+    {
+        const std::vector<int> p = pileup();
+        int beststart = -1, bestend = -1, start = -1, end = -1;
+        double bestavg = 0;
+        long long curbases = 0;
+        for (int i = 0; i < length; ++i) {
+            if (p[(size_t)i] >= threshold) {
+                if (start == -1) { curbases = 0; start = i; }
+                end = i;
+                curbases += p[(size_t)i];
+                const int span = end - start + 1;
+                const double curavg = static_cast<double>(curbases) / static_cast<double>(span);
+                if (span > maxlen && curavg > bestavg) { beststart = start; bestend = end; maxlen = span; bestavg = curavg; }
+            } else {
+                start = -1; end = -1;
+            }
+        }
+        return beststart < 0 ? std::make_tuple(-1, -1) : std::make_tuple(beststart, bestend + 1);
+    }
+};
+
+// GetReadPileup(dfd, Rmat) — src/PruneChimeras.cpp:108-158, on the symmetrised R (both reads of a pair credited; the reference credits only
+// the column read of the upper triangle) and on the device: elba_read_pileup on the pairs the next TransitiveReduction reads.
+inline std::vector<PileupVector> GetReadPileup(const DnaBuffer &myreads, OverlapMatrix &R, const elba_pileup_cfg &cfg, elba_pileup_stats *stats = nullptr)
+{
+    if ((int64_t)myreads.size() != R.numreads) throw Error(ELBA_ERR_INVALID_ARG, "GetReadPileup: myreads does not hold the overlaps' reads");
+    if (!R.engine) throw Error(ELBA_ERR_STATE, "GetReadPileup: the overlaps are not on a device");
+    elba_pileup_stats st{};
+    R.engine->check(elba_read_pileup(R.engine->ctx, &cfg, &st));
+    if (stats) *stats = st;
+    elba_pileup_t o;
+    R.engine->check(elba_export_pileup(R.engine->ctx, &o));
+    std::vector<PileupVector> out((size_t)o.n);
+    for (int64_t v = 0; v < o.n; ++v) {
+        PileupVector &p = out[(size_t)v];
+        p.length = (int)myreads.lengths()[v];
+        p.seg_start.assign(o.seg_start + o.seg_off[v], o.seg_start + o.seg_off[v + 1]);
+        p.seg_depth.assign(o.seg_depth + o.seg_off[v], o.seg_depth + o.seg_off[v + 1]);
+        p.trimmed = std::make_tuple(o.trim_beg[v], o.trim_end[v]);
+        p.flags = o.flags[v];
+    }
+    elba_free_pileup(&o);
+    return out;
+}
+
+// R->PruneFull(x, x) for x = the reads with flags & mask (CombBLAS SpParMat::PruneFull): the kept pairs become the edge list the next
+// TransitiveReduction reads; the host copy of R is pruned alike.  Returns the pairs kept.
+inline int64_t PruneFull(OverlapMatrix &R, int mask)
+{
+    if (!R.engine) throw Error(ELBA_ERR_STATE, "PruneFull: the overlaps are not on a device");
+    std::vector<uint8_t> flags;
+    {
+        elba_pileup_t o;
+        R.engine->check(elba_export_pileup(R.engine->ctx, &o));
+        flags.assign(o.flags, o.flags + o.n);
+        elba_free_pileup(&o);
+    }
+    int64_t kept = 0;
+    R.engine->check(elba_prune_reads(R.engine->ctx, mask, &kept));
+    size_t w = 0;
+    for (size_t a = 0; a < R.vals.size(); ++a) {
+        if ((flags[(size_t)R.rows[a]] | flags[(size_t)R.cols[a]]) & mask) continue;
+        R.rows[w] = R.rows[a]; R.cols[w] = R.cols[a]; R.vals[w] = R.vals[a]; ++w;
+    }
+    R.rows.resize(w); R.cols.resize(w); R.vals.resize(w);
+    if ((int64_t)w != kept) throw Error(ELBA_ERR_INTERNAL, "PruneFull: the device kept " + std::to_string(kept) + " pairs, the host " + std::to_string(w));
+    return kept;
+}
+
 // GenerateContigs(S, mydna, dfd) — src/ContigGeneration.cpp:376-457 on one rank: branches (degree > 2) dropped, every path of >= 2 reads
 // walked from its smaller-id end, the contig built from the reads' prefixes; on the GPU, on the S that TransitiveReduction left there.
 // The reads are the ones the context was given (mydna on one rank).  Contigs in the reference's emission order.

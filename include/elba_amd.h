@@ -322,6 +322,57 @@ int  elba_export_contigs(elba_ctx *ctx, elba_contigs_t *out);
 void elba_free_contigs(elba_contigs_t *c);
 int  elba_export_read_contigs(elba_ctx *ctx, int64_t *contig_of_read, int64_t nreads);  /* contig index of every read, -1: branch, singleton or cycle */
 
+/* Read pileups and chimera flags: PileupVector / GetReadPileup / GetTrimmedInterval (src/PruneChimeras.cpp:14-69,108-158,
+ * include/PruneChimeras.hpp), which src/main.cpp never calls, and R->PruneFull(x, x) of the reads it flags.  Runs after elba_align_seeds,
+ * before elba_transitive_reduction, on the pairs that call would read: the list of elba_set_overlaps if one is loaded, else this context's
+ * alignments (a row shard's fail with ELBA_ERR_STATE).  The lengths of reads 0 .. nreads-1 must be on the context (its own reads or the
+ * replicated set of elba_dist_set_all_reads), otherwise ELBA_ERR_STATE.
+ *   pileup     every accepted pair (mode 0: passed; mode 1: score > 0) adds 1 on [begQ + margin, endQ - margin) of read Q and on
+ *              [begT + margin, endT - margin) of read T; an interval left empty is dropped.  begT / endT are on T's forward strand also when
+ *              rc is set (xdrop_aligner maps them back, src/XDropAligner.cpp:275-276; align.hip does the same, and on rc pairs of the tests the
+ *              T interval's reverse complement aligns to the Q interval).  An interval outside [0, len] or with beg > end in a credited pair
+ *              fails with ELBA_ERR_INVALID_ARG (the reference asserts, :26).
+ *   profile    per read, maximal runs of equal depth as (start, depth) segments: starts strictly increasing from 0, neighbours of different
+ *              depth, the last one ends at len; a read without intervals is (0, 0), a read of length 0 has none.
+ *   trimmed    GetTrimmedInterval's rule with threshold min_depth and the starting maxlen trim_len (2500 in the reference, :36): the run of
+ *              depth >= min_depth replaces the best at a base when span > maxlen && curavg > bestavg (curavg in double, as written);
+ *              returned half-open [beststart, bestend + 1), or (-1, -1).
+ *   flags      bit 0: no run of depth >= min_depth at least min_run long (unsupported); bit 1: two or more (split: chimera candidate).
+ * Two deliberate deviations from the reference: both reads of a pair are credited (GetReadPileup credits only the column read of the
+ * upper-triangular R, :137-146), and the trimmed interval is the best run (the reference returns the run still open at the last base, :68).
+ * elba_prune_reads removes every pair with either end in {v : flags[v] & mask} and loads the kept pairs, in (row, col) order, as the edge
+ * list elba_transitive_reduction reads next (elba_export_overlaps still returns the alignments).  A new read set, new alignments,
+ * elba_set_overlaps and elba_prune_reads invalidate the pileup (ELBA_ERR_STATE on export). */
+typedef struct {
+    int32_t mode;               /* 0: pairs with passed; 1: every pair with score > 0 */
+    int32_t margin;             /* >= 0: bases dropped at each end of every interval */
+    int32_t min_depth;          /* >= 1: the threshold */
+    int32_t min_run;            /* >= 1: the length of a long run (flags) */
+    int32_t trim_len;           /* >= 0: GetTrimmedInterval's starting maxlen */
+    int32_t reserved;           /* 0 */
+} elba_pileup_cfg;
+
+typedef struct {
+    int64_t nreads, pairs, intervals, segments, max_depth;   /* pairs: accepted by the mode; intervals: credited (non-empty after the margin) */
+    int64_t unsupported, split, trimmed;                      /* reads with flag bit 0 / bit 1 / a trimmed interval other than [0, len) */
+    int64_t trimmed_bases;                                    /* bases inside trimmed intervals */
+    float   ms_total;                                         /* device time of the stage */
+    float   reserved;
+} elba_pileup_stats;
+
+typedef struct {
+    int64_t n, nseg;           /* reads, segments */
+    int64_t *seg_off;          /* [n+1] into the segment arrays */
+    int32_t *seg_start, *seg_depth;
+    int32_t *trim_beg, *trim_end;   /* [n] half-open trimmed interval, -1 / -1: none */
+    uint8_t *flags;            /* [n] bit 0 unsupported, bit 1 split */
+} elba_pileup_t;
+
+int  elba_read_pileup(elba_ctx *ctx, const elba_pileup_cfg *cfg, elba_pileup_stats *stats);
+int  elba_export_pileup(elba_ctx *ctx, elba_pileup_t *out);
+void elba_free_pileup(elba_pileup_t *p);
+int  elba_prune_reads(elba_ctx *ctx, int mask, int64_t *kept);
+
 int  elba_export_dcsc(elba_ctx *ctx, int64_t row_lo, int64_t row_hi, int64_t col_lo, int64_t col_hi, elba_dcsc_t *out);
 void elba_free_dcsc(elba_dcsc_t *d);
 int  elba_export_csr(elba_ctx *ctx, int64_t row_lo, int64_t row_hi, elba_csr_t *out);
