@@ -259,10 +259,41 @@ def live_xdrop_vectors():
             f.write("%d %d %d %d %d %d %d %d %s\n" % (i, j, a, b, mat, mis, gap, x, " ".join(str(v) for v in out)))
 
 
+PLANTED_KS = (17, 31, 33, 63, 95)          # the k of tests/xdrop_util.py's families that oracle/Makefile's `ref` builds
+
+
+def planted_xdrop_vectors():
+    """The planted-seed families of tests/xdrop_util.py through the reference's own xdrop_aligner + classify_alignment, one file per k.
+    The generators are deterministic, so a line names its case (family, name, seed, scores) instead of spelling the reads out; the CRC-32
+    of `query|target` tells a reader whose generator drifted that the line no longer speaks of the same pair."""
+    import xdrop_util as xu
+    lines = {k: [] for k in PLANTED_KS}
+    for fam in xu.FAMILY_NAMES:
+        k, groups = xu.family(fam)
+        if k not in lines:
+            continue
+        R = po.ref_lib(k)
+        assert R is not None, "run `make -C oracle ref` first"
+        for params, cases in groups:
+            packed, off, lens = ref_pack(R, [s for cs in cases for s in (cs.q, cs.t)])
+            for c, cs in enumerate(cases):
+                out = po.ref_xdrop(R, packed[int(off[2 * c]):], int(lens[2 * c]), packed[int(off[2 * c + 1]):], int(lens[2 * c + 1]), cs.q0, cs.t0, *params)
+                lines[k].append("%s %s %d %d %d %d %d %d %08x %s" % ((fam, cs.name, cs.q0, cs.t0) + tuple(params) + (xu.case_crc(cs), " ".join(str(v) for v in out))))
+    for k, rows in lines.items():
+        with open(os.path.join(HERE, "xdrop_planted_k%d.txt" % k), "w") as f:
+            f.write("# family case seedQ seedT mat mis gap xdrop crc32(query|target) -> ret begQ endQ begT endT score rc OverlapClass   "
+                    "(cases: tests/xdrop_util.py; reference: src/XDropAligner.cpp, KMER_SIZE=%d)\n" % k)
+            f.write("\n".join(rows) + "\n")
+        print(k, len(rows))
+
+
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == "live":           # only the stored answers of the two live cross-checks
         assert po.ref_lib(17) is not None and po.ref_lib(31) is not None, "run `make -C oracle ref` first"
         live_primitive_vectors(); live_xdrop_vectors()
+        return
+    if len(sys.argv) > 1 and sys.argv[1] == "planted":        # only the planted-seed x-drop vectors
+        planted_xdrop_vectors()
         return
     if len(sys.argv) > 1 and sys.argv[1] == "kmers2":         # only the two-word k-mer vectors
         rng = np.random.default_rng(20261005)
