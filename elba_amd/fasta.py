@@ -40,6 +40,8 @@ def write_fai(fasta_path, fai_path=None):
                 bases, width = le - j, le - j + 1
             length += le - j
             j = le + 1
+        if bases == 0:      # an empty record (a header, then an empty line or nothing): no line to measure; any width > 0 places its zero bases
+            bases, width = 1, 2
         out.append("%s\t%d\t%d\t%d\t%d" % (name, length, pos, bases, width))
         i = j
     with open(fai_path, "w") as f:
