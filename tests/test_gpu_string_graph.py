@@ -11,22 +11,8 @@ from oracle import pyoracle as po
 
 pytestmark = pytest.mark.gpu
 
-COUNTS = ("bad_reads", "edges_passed", "contained_reads", "edges_kept", "products", "marked", "removed", "nnz", "iterations")
-
-
-def _same(e, nreads, rows, cols, vals, cutoff=0.65, fuzz=1000):
-    st = e.transitive_reduction(cutoff, fuzz)
-    g = e.export_string_graph()
-    S, flags, ost = po.string_graph(nreads, rows, cols, vals, cutoff=cutoff, fuzz=fuzz)
-    for key in COUNTS:
-        assert st[key] == ost[key], (key, st, ost)
-    assert st["nreads"] == nreads and st["nedges"] == len(rows)
-    assert g["n"] == S["n"] and (g["rows"] == S["rows"]).all() and (g["cols"] == S["cols"]).all()
-    for f in po.OVERLAP_DTYPE.names:
-        if f != "pad":
-            assert (g["vals"][f] == S["vals"][f]).all(), f
-    assert (e.export_read_flags(nreads) == flags).all()
-    return st
+COUNTS = sg.COUNTS
+_same = sg.assert_same_as_oracle            # shared with tests/test_gpu_string_graph_scale.py
 
 
 @pytest.mark.parametrize("seed", range(8))
