@@ -28,6 +28,9 @@ def numeric_source_fingerprint():
     return h.hexdigest()[:16]
 
 
+ELBA_ERR_HIP = 3
+
+
 class ElbaError(RuntimeError):
     def __init__(self, status, text):
         super().__init__("elba status %d: %s" % (status, text))
@@ -101,6 +104,19 @@ class Pileup(C.Structure):
                 ("trim_beg", C.c_void_p), ("trim_end", C.c_void_p), ("flags", C.c_void_p)]
 
 
+class TrimCfg(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("min_len", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class TrimStats(C.Structure):
+    _fields_ = [("nreads_in", C.c_int64), ("pieces", C.c_int64), ("reads_dropped", C.c_int64), ("reads_split", C.c_int64), ("reads_unchanged", C.c_int64),
+                ("bases_in", C.c_int64), ("bases_out", C.c_int64), ("packed_bytes", C.c_int64), ("longest", C.c_int64), ("ms_total", C.c_float), ("ms_repack", C.c_float)]
+
+
+class TrimMap(C.Structure):
+    _fields_ = [("n", C.c_int64), ("src_read", C.c_void_p), ("src_beg", C.c_void_p), ("src_end", C.c_void_p)]
+
+
 class Overlaps(C.Structure):
     _fields_ = [("n", C.c_int64), ("rows", C.c_void_p), ("cols", C.c_void_p), ("vals", C.c_void_p)]
 
@@ -154,6 +170,7 @@ EXPORTED_SYMBOLS = [
     "elba_seed_matrix_begin", "elba_seed_matrix_fill", "elba_seed_matrix_end", "elba_set_stream", "elba_seed_matrix_send", "elba_seed_matrix_recv", "elba_set_kmer_matrix_device", "elba_export_triples_device", "elba_get_stat", "elba_release_workspace",
     "elba_generate_contigs", "elba_export_contigs", "elba_free_contigs", "elba_export_read_contigs",
     "elba_read_pileup", "elba_export_pileup", "elba_free_pileup", "elba_prune_reads",
+    "elba_trim_reads", "elba_export_trim_map", "elba_free_trim_map", "elba_get_trimmed_reads_device", "elba_adopt_trimmed_reads",
 ]
 
 _lib = None
@@ -211,6 +228,11 @@ def load_library():
     L.elba_export_pileup.restype = i32; L.elba_export_pileup.argtypes = [vp, C.POINTER(Pileup)]
     L.elba_free_pileup.restype = None; L.elba_free_pileup.argtypes = [C.POINTER(Pileup)]
     L.elba_prune_reads.restype = i32; L.elba_prune_reads.argtypes = [vp, i32, C.POINTER(C.c_int64)]
+    L.elba_trim_reads.restype = i32; L.elba_trim_reads.argtypes = [vp, C.POINTER(TrimCfg), C.POINTER(TrimStats)]
+    L.elba_export_trim_map.restype = i32; L.elba_export_trim_map.argtypes = [vp, C.POINTER(TrimMap)]
+    L.elba_free_trim_map.restype = None; L.elba_free_trim_map.argtypes = [C.POINTER(TrimMap)]
+    L.elba_get_trimmed_reads_device.restype = i32; L.elba_get_trimmed_reads_device.argtypes = [vp, C.POINTER(vp), C.POINTER(i64), C.POINTER(vp), C.POINTER(vp), C.POINTER(i64)]
+    L.elba_adopt_trimmed_reads.restype = i32; L.elba_adopt_trimmed_reads.argtypes = [vp]
     L.elba_export_dcsc.restype = i32; L.elba_export_dcsc.argtypes = [vp, i64, i64, i64, i64, C.POINTER(Dcsc)]
     L.elba_free_dcsc.restype = None; L.elba_free_dcsc.argtypes = [C.POINTER(Dcsc)]
     L.elba_export_csr.restype = i32; L.elba_export_csr.argtypes = [vp, i64, i64, C.POINTER(Csr)]
@@ -236,6 +258,19 @@ def _copy(ptr, n, dtype):
         return np.zeros(0, dtype=dt)
     buf = (C.c_char * (n * dt.itemsize)).from_address(ptr)
     return np.frombuffer(buf, dtype=dt, count=n).copy()
+
+
+def _copy_from_device(dev_ptr, n, dtype):
+    """n items of dtype from a device address of the library into a fresh numpy array: hipMemcpy of the HIP runtime the library itself
+    is linked to (looked up through the library's handle, so no second runtime enters the process)."""
+    out = np.empty(int(n), dtype=dtype)
+    if n:
+        f = load_library().hipMemcpy
+        f.restype = C.c_int; f.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        rc = f(out.ctypes.data, int(dev_ptr), out.nbytes, 2)      # hipMemcpyDeviceToHost
+        if rc:
+            raise ElbaError(ELBA_ERR_HIP, "hipMemcpy device to host failed: %d" % rc)
+    return out
 
 
 def _stats(s):
@@ -476,6 +511,43 @@ class Engine:
         kept = C.c_int64(0)
         self._check(self.L.elba_prune_reads(self.h, int(mask), C.byref(kept)))
         return int(kept.value)
+
+    # --- reads cut to their supported intervals (after read_pileup; adopt_trimmed_reads starts the pipeline again on the pieces) ---
+    def trim_reads(self, mode=0, min_len=1, reserved=(0, 0)):
+        """mode 0: one piece per read, its trimmed interval; mode 1: one piece per long run of the last read_pileup (a chimera is split).
+        Pieces shorter than min_len are dropped.  The new read set stays on the device.  Returns the stats."""
+        cfg = TrimCfg(int(mode), int(min_len), (C.c_int32 * 2)(int(reserved[0]), int(reserved[1])))
+        st = TrimStats()
+        self._check(self.L.elba_trim_reads(self.h, C.byref(cfg), C.byref(st)))
+        return _stats(st)
+
+    def export_trim_map(self):
+        """{n, src_read (i64[n]), src_beg, src_end (i32[n])}: piece p is bases [src_beg, src_end) of read src_read; (src_read, src_beg) ascending."""
+        o = TrimMap()
+        self._check(self.L.elba_export_trim_map(self.h, C.byref(o)))
+        try:
+            n = o.n
+            return dict(n=n, src_read=_copy(o.src_read, n, np.int64), src_beg=_copy(o.src_beg, n, np.int32), src_end=_copy(o.src_end, n, np.int32))
+        finally:
+            self.L.elba_free_trim_map(C.byref(o))
+
+    def trimmed_reads_device(self):
+        """{d_packed, packed_bytes, d_byte_off (u64[n]), d_len (u32[n]), n}: device addresses of the trimmed read set (DnaBuffer layout, 16
+        zeroed guard bytes behind packed_bytes), valid until the next trim_reads, adopt_trimmed_reads or close."""
+        dp, do, dl = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        pb, n = C.c_int64(0), C.c_int64(0)
+        self._check(self.L.elba_get_trimmed_reads_device(self.h, C.byref(dp), C.byref(pb), C.byref(do), C.byref(dl), C.byref(n)))
+        return dict(d_packed=dp.value, packed_bytes=int(pb.value), d_byte_off=do.value, d_len=dl.value, n=int(n.value))
+
+    def export_trimmed_reads(self):
+        """Host copies (packed with its 16 guard bytes, byte_off u64, len u32) of the trimmed read set; the snapshot stays on the device."""
+        v = self.trimmed_reads_device()
+        return (_copy_from_device(v["d_packed"], v["packed_bytes"] + 16, np.uint8), _copy_from_device(v["d_byte_off"], v["n"], np.uint64),
+                _copy_from_device(v["d_len"], v["n"], np.uint32))
+
+    def adopt_trimmed_reads(self):
+        """The pieces become this context's reads, exactly as after set_reads (everything derived from the old reads is invalidated)."""
+        self._check(self.L.elba_adopt_trimmed_reads(self.h))
 
     # --- outputs ---
     def export_csr(self, row_lo=0, row_hi=None):

@@ -138,9 +138,7 @@ int elba_set_reads(elba_ctx *ctx, const uint8_t *packed, const uint64_t *byte_of
         c.h_len.assign(len, len + nreads);
         c.h_byte_off.assign(byte_off, byte_off + nreads);
         c.nreads = nreads; c.first_global_id = first_global_id; c.packed_bytes = pb;
-        // a new read set invalidates everything derived from the old one (as stage_set_reads_fasta does)
-        c.have_reads = true; c.have_counts = false; c.have_aln = false; c.have_edges = false; c.have_S = false; c.have_pileup = false;
-        if (c.A_has_kmers) { c.have_A = false; c.have_B = false; }      // (an A handed over as triples / a panel does not come from these reads)
+        reads_replaced(c);
     });
 }
 
@@ -148,7 +146,7 @@ int elba_set_reads_fasta(elba_ctx *ctx, const char *chunk, int64_t chunk_bytes, 
                          int64_t first_global_id, elba_ingest_stats *stats)
 {
     return guarded(ctx, [&](Ctx &c) {
-        c.have_pileup = false;
+        c.have_pileup = false; c.have_trim = false;
         stage_set_reads_fasta(c, chunk, chunk_bytes, chunk_file_offset, recs, nreads, first_global_id, stats);
     });
 }
@@ -185,9 +183,7 @@ int elba_set_reads_device(elba_ctx *ctx, const void *d_packed, int64_t packed_by
         for (int64_t r = 0; r < nreads; ++r)
             ELBA_REQUIRE((int64_t)c.h_byte_off[r] + ((int64_t)c.h_len[r] + 3) / 4 <= packed_bytes, ELBA_ERR_INVALID_ARG, "set_reads_device: read exceeds the packed buffer");
         c.nreads = nreads; c.first_global_id = first_global_id; c.packed_bytes = packed_bytes;
-        // a new read set invalidates everything derived from the old one (as stage_set_reads_fasta does)
-        c.have_reads = true; c.have_counts = false; c.have_aln = false; c.have_edges = false; c.have_S = false; c.have_pileup = false;
-        if (c.A_has_kmers) { c.have_A = false; c.have_B = false; }      // (an A handed over as triples / a panel does not come from these reads)
+        reads_replaced(c);
     });
 }
 
@@ -303,7 +299,7 @@ int elba_align_seeds(elba_ctx *ctx, int mat, int mis, int gap, int dropoff, elba
 int elba_dist_set_all_reads(elba_ctx *ctx, const void *d_packed, int64_t packed_bytes, const void *d_byte_off, const void *d_len, int64_t nreads_total)
 {
     return guarded(ctx, [&](Ctx &c) {
-        c.have_pileup = false;
+        c.have_pileup = false; c.have_trim = false;
         stage_dist_set_all_reads(c, d_packed, packed_bytes, d_byte_off, d_len, nreads_total);
     });
 }
@@ -433,7 +429,7 @@ int elba_export_read_contigs(elba_ctx *ctx, int64_t *contig_of_read, int64_t nre
 int elba_read_pileup(elba_ctx *ctx, const elba_pileup_cfg *cfg, elba_pileup_stats *stats)
 {
     return guarded(ctx, [&](Ctx &c) {
-        c.have_pileup = false;
+        c.have_pileup = false; c.have_trim = false;                 // (the trimmed reads are cut from the pileup they were asked of)
         ELBA_REQUIRE(cfg, ELBA_ERR_INVALID_ARG, "read_pileup: null cfg");
         stage_read_pileup(c, *cfg);
         if (stats) *stats = c.pustats;
@@ -478,6 +474,58 @@ void elba_free_pileup(elba_pileup_t *p)
 int elba_prune_reads(elba_ctx *ctx, int mask, int64_t *kept)
 {
     return guarded(ctx, [&](Ctx &c) { stage_prune_reads(c, mask, kept); });
+}
+
+int elba_trim_reads(elba_ctx *ctx, const elba_trim_cfg *cfg, elba_trim_stats *stats)
+{
+    return guarded(ctx, [&](Ctx &c) {
+        c.have_trim = false;
+        ELBA_REQUIRE(cfg, ELBA_ERR_INVALID_ARG, "trim_reads: null cfg");
+        stage_trim_reads(c, *cfg);
+        if (stats) *stats = c.tmstats;
+    });
+}
+
+int elba_export_trim_map(elba_ctx *ctx, elba_trim_map_t *out)
+{
+    return guarded(ctx, [&](Ctx &c) {
+        ELBA_REQUIRE(out, ELBA_ERR_INVALID_ARG, "export_trim_map: null output");
+        memset(out, 0, sizeof(*out));
+        ELBA_REQUIRE(c.have_trim, ELBA_ERR_STATE, "export_trim_map: no trimmed reads (call elba_trim_reads)");
+        const int64_t n = c.tm_n;
+        elba_trim_map_t o{};
+        o.n = n;
+        o.src_read = host_alloc<int64_t>((size_t)n); o.src_beg = host_alloc<int32_t>((size_t)n); o.src_end = host_alloc<int32_t>((size_t)n);
+        *out = o;                                                   // (allocated before any copy: elba_free_trim_map releases them if a copy fails)
+        hipStream_t s = c.stream;
+        if (n) {
+            ELBA_HIP(hipMemcpyAsync(o.src_read, c.tm_src.p, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+            ELBA_HIP(hipMemcpyAsync(o.src_beg, c.tm_beg.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+            ELBA_HIP(hipMemcpyAsync(o.src_end, c.tm_end.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+        }
+        ELBA_HIP(hipStreamSynchronize(s));
+    });
+}
+
+void elba_free_trim_map(elba_trim_map_t *m)
+{
+    if (!m) return;
+    free(m->src_read); free(m->src_beg); free(m->src_end);
+    memset(m, 0, sizeof(*m));
+}
+
+int elba_get_trimmed_reads_device(elba_ctx *ctx, const void **d_packed, int64_t *packed_bytes, const void **d_byte_off, const void **d_len, int64_t *n)
+{
+    return guarded(ctx, [&](Ctx &c) {
+        ELBA_REQUIRE(d_packed && packed_bytes && d_byte_off && d_len && n, ELBA_ERR_INVALID_ARG, "get_trimmed_reads_device: null output");
+        ELBA_REQUIRE(c.have_trim, ELBA_ERR_STATE, "get_trimmed_reads_device: no trimmed reads (call elba_trim_reads)");
+        *d_packed = c.tm_packed.p; *packed_bytes = c.tm_packed_bytes; *d_byte_off = c.tm_off.p; *d_len = c.tm_len.p; *n = c.tm_n;
+    });
+}
+
+int elba_adopt_trimmed_reads(elba_ctx *ctx)
+{
+    return guarded(ctx, [&](Ctx &c) { stage_adopt_trimmed_reads(c); });
 }
 
 int elba_export_csr(elba_ctx *ctx, int64_t row_lo, int64_t row_hi, elba_csr_t *out)
@@ -671,6 +719,7 @@ int elba_release_workspace(elba_ctx *ctx)
         for (int b = 0; b < 2; ++b) { c.cg_far[b].release(); c.cg_rank[b].release(); c.cg_mn[b].release(); }
         c.pu_k0.release(); c.pu_k1.release(); c.pu_eptr.release(); c.pu_head.release(); c.pu_hidx.release(); c.pu_delta.release();   // pileup scratch (the results stay)
         c.pu_dsum.release(); c.pu_gstart.release(); c.pu_tok.release(); c.pu_tpos.release(); c.pu_sel.release(); c.pu_rows.release(); c.pu_cols.release(); c.pu_vals.release();
+        c.tm_cnt.release(); c.tm_bytes.release(); c.tm_first.release(); c.tm_boff.release(); c.tm_srcb.release();   // trim scratch (the trimmed reads and their map stay)
         if (c.have_counts) { c.pre_ready = false; c.pre_consumed = true; }    // (the CSR sort keys / column ids of the entries are gone: create_kmer_matrix rebuilds them from the column pointers)
     });
 }

@@ -317,6 +317,16 @@ struct Ctx {
     DevBuf pu_seg_off, pu_seg_start, pu_seg_depth, pu_trim, pu_flags;
     EventTimer pu_t_total;
     elba_pileup_stats pustats{};
+    elba_pileup_cfg pu_cfg{};                  // the cfg of the pileup that is valid now (trim.hip's long runs are its min_depth / min_run)
+
+    // trimmed reads (trim.hip): a snapshot in buffers of its own — packed / off / len in DnaBuffer layout, the map (src, beg, end); it survives
+    // elba_prune_reads and elba_release_workspace, a new read set or a new pileup invalidates it, elba_adopt_trimmed_reads consumes it
+    bool have_trim = false;
+    int64_t tm_n = 0, tm_packed_bytes = 0;
+    DevBuf tm_packed, tm_off, tm_len, tm_src, tm_beg, tm_end;
+    DevBuf tm_cnt, tm_bytes, tm_first, tm_boff, tm_srcb, tm_ctr;      // scratch
+    EventTimer tm_t_total, tm_t_repack;
+    elba_trim_stats tmstats{};
 
     // workspaces
     DevBuf ws_scan, ws_sort, ws_a, ws_b, ws_c, ws_d, ws_e, ws_f;
@@ -357,6 +367,13 @@ struct Ctx {
     PhaseMarks<5> ov_marks;        // overlap SpGEMM: 0 call start, 1 numeric start, 2 numeric end, 3 call end, 4 finalize start when the host synchronised before it
 };
 
+// a new read set invalidates everything derived from the old one (elba_set_reads, elba_set_reads_device, elba_adopt_trimmed_reads; stage_set_reads_fasta does the same)
+inline void reads_replaced(Ctx &c)
+{
+    c.have_reads = true; c.have_counts = false; c.have_aln = false; c.have_edges = false; c.have_S = false; c.have_pileup = false; c.have_trim = false;
+    if (c.A_has_kmers) { c.have_A = false; c.have_B = false; }      // (an A handed over as triples / a panel does not come from these reads)
+}
+
 // ---- stages -----------------------------------------------------------------------------------------------------
 void stage_set_reads_fasta(Ctx &c, const char *chunk, int64_t chunk_bytes, uint64_t chunk_file_offset, const elba_fasta_record_t *recs, int64_t nreads,
                            int64_t first_global_id, elba_ingest_stats *stats);      // ingest.hip
@@ -381,6 +398,8 @@ void stage_transitive_reduction(Ctx &c, double bad_read_cutoff, int fuzz);   // 
 void stage_generate_contigs(Ctx &c);                                          // contig.hip
 void stage_read_pileup(Ctx &c, const elba_pileup_cfg &cfg);                   // pileup.hip
 void stage_prune_reads(Ctx &c, int mask, int64_t *kept);
+void stage_trim_reads(Ctx &c, const elba_trim_cfg &cfg);                      // trim.hip
+void stage_adopt_trimmed_reads(Ctx &c);
 void stage_dist_count_owners(Ctx &c, int nranks, uint64_t *counts_host);                                   // kmer.hip
 void stage_dist_value_histogram(Ctx &c, uint64_t *hist_host, int64_t nbins);
 void stage_ref_hash_owner(Ctx &c, const uint64_t *kmers_host, int64_t n, int nprocs, uint64_t *hash_host, int32_t *owner_host);

@@ -350,7 +350,7 @@ void stage_read_pileup(Ctx &c, const elba_pileup_cfg &cfg)
     st.nreads = M; st.pairs = (int64_t)h[0]; st.intervals = (int64_t)h[1]; st.segments = (int64_t)h[3]; st.max_depth = (int64_t)h[4];
     st.unsupported = (int64_t)h[5]; st.split = (int64_t)h[6]; st.trimmed = (int64_t)h[7]; st.trimmed_bases = (int64_t)h[8];
     st.ms_total = c.pu_t_total.ms();
-    c.pu_M = M; c.pu_nseg = st.segments; c.pu_n = n; c.pustats = st; c.have_pileup = true;
+    c.pu_M = M; c.pu_nseg = st.segments; c.pu_n = n; c.pustats = st; c.pu_cfg = cfg; c.have_pileup = true;
 }
 
 void stage_prune_reads(Ctx &c, int mask, int64_t *kept)

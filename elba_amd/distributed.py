@@ -138,6 +138,11 @@ class HipBackend:
     def prune_reads(self, mask):
         return self.e.prune_reads(mask)
 
+    def trim_reads(self, mode, min_len):
+        st = self.e.trim_reads(mode, min_len)
+        packed, off, ln = self.e.export_trimmed_reads()
+        return dict(self.e.export_trim_map(), stats=st, packed=packed, byte_off=off, len=ln)
+
     def value_histogram(self):
         out = np.zeros(OWNER_BINS, dtype=np.uint64)
         self.e._check(self.L.elba_dist_value_histogram(self.h, out.ctypes.data, OWNER_BINS))
@@ -750,6 +755,12 @@ class DistributedOverlap:
         kept = self.be.prune_reads(mask)
         self._pruned = True
         return kept
+
+    def trim_reads(self, mode=0, min_len=1):
+        """elba_trim_reads across ranks, after read_pileup: every rank holds every read's pileup and the replicated reads of align_seeds, so
+        each cuts all of them and returns the same pieces: {n, src_read, src_beg, src_end, stats, packed (with its 16 guard bytes), byte_off,
+        len} on the host.  No exchange.  The caller partitions the pieces and hands each rank its share with set_reads, as for any read set."""
+        return self.be.trim_reads(mode, min_len)
 
     def export_string_graph(self, local=False):
         S = self.be.export_string_graph()

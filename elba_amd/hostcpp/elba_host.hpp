@@ -79,6 +79,13 @@ public:
     const uint64_t *offsets() const { return off_.data(); }
     const uint32_t *lengths() const { return len_.data(); }
     int base(size_t read, size_t i) const { return (buf_[off_[read] + i / 4] >> (6 - 2 * (i % 4))) & 3; }   // DnaSeq::operator[]
+    // a buffer that exists in this layout already (elba_export_reads): packed bytes, byte offsets, lengths
+    static DnaBuffer from_packed(std::vector<uint8_t> buf, std::vector<uint64_t> off, std::vector<uint32_t> len)
+    {
+        DnaBuffer d;
+        d.buf_ = std::move(buf); d.off_ = std::move(off); d.len_ = std::move(len);
+        return d;
+    }
 
 private:
     static uint8_t code(char c)                                                        // include/DnaSeq.hpp:136-154
@@ -496,6 +503,58 @@ inline int64_t PruneFull(OverlapMatrix &R, int mask)
     R.rows.resize(w); R.cols.resize(w); R.vals.resize(w);
     if ((int64_t)w != kept) throw Error(ELBA_ERR_INTERNAL, "PruneFull: the device kept " + std::to_string(kept) + " pairs, the host " + std::to_string(w));
     return kept;
+}
+
+// The reads cut to their supported intervals (elba_trim_reads): what GetTrimmedInterval's interval is computed for; the reference stops
+// before this step.  TrimReads cuts the reads of the last GetReadPileup on the device — mode 0: every read to its trimmed interval, mode 1:
+// one piece per long run, so that a chimera is split — and leaves the pieces there; ExportTrimMap says where each piece came from,
+// TrimmedReadsDevice hands out their device addresses, AdoptTrimmedReads makes them the engine's reads (as after elba_set_reads) and returns
+// them as the DnaBuffer the next get_kmer_count_map_keys(..., engine) round reads its lengths from.
+struct TrimMap {
+    std::vector<int64_t> src_read;              // piece p = bases [src_beg, src_end) of read src_read; (src_read, src_beg) ascending
+    std::vector<int32_t> src_beg, src_end;
+    size_t size() const { return src_read.size(); }
+};
+
+struct TrimmedReadsView { const void *d_packed = nullptr, *d_byte_off = nullptr, *d_len = nullptr; int64_t packed_bytes = 0, n = 0; };
+
+inline elba_trim_stats TrimReads(OverlapMatrix &R, const elba_trim_cfg &cfg)
+{
+    if (!R.engine) throw Error(ELBA_ERR_STATE, "TrimReads: the overlaps are not on a device");
+    elba_trim_stats st{};
+    R.engine->check(elba_trim_reads(R.engine->ctx, &cfg, &st));
+    return st;
+}
+
+inline TrimMap ExportTrimMap(OverlapMatrix &R)
+{
+    if (!R.engine) throw Error(ELBA_ERR_STATE, "ExportTrimMap: the overlaps are not on a device");
+    elba_trim_map_t m;
+    R.engine->check(elba_export_trim_map(R.engine->ctx, &m));
+    TrimMap out;
+    out.src_read.assign(m.src_read, m.src_read + m.n); out.src_beg.assign(m.src_beg, m.src_beg + m.n); out.src_end.assign(m.src_end, m.src_end + m.n);
+    elba_free_trim_map(&m);
+    return out;
+}
+
+inline TrimmedReadsView TrimmedReadsDevice(OverlapMatrix &R)
+{
+    if (!R.engine) throw Error(ELBA_ERR_STATE, "TrimmedReadsDevice: the overlaps are not on a device");
+    TrimmedReadsView v;
+    R.engine->check(elba_get_trimmed_reads_device(R.engine->ctx, &v.d_packed, &v.packed_bytes, &v.d_byte_off, &v.d_len, &v.n));
+    return v;
+}
+
+// R's engine holds the pieces afterwards and nothing derived from the old reads: R itself (the host triples) describes the old reads.
+inline DnaBuffer AdoptTrimmedReads(OverlapMatrix &R)
+{
+    const TrimmedReadsView v = TrimmedReadsDevice(R);
+    R.engine->check(elba_adopt_trimmed_reads(R.engine->ctx));
+    std::vector<uint8_t> buf((size_t)v.packed_bytes);
+    std::vector<uint64_t> off((size_t)v.n);
+    std::vector<uint32_t> len((size_t)v.n);
+    R.engine->check(elba_export_reads(R.engine->ctx, buf.data(), v.packed_bytes, off.data(), len.data(), v.n));
+    return DnaBuffer::from_packed(std::move(buf), std::move(off), std::move(len));
 }
 
 // GenerateContigs(S, mydna, dfd) — src/ContigGeneration.cpp:376-457 on one rank: branches (degree > 2) dropped, every path of >= 2 reads

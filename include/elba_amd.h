@@ -373,6 +373,44 @@ int  elba_export_pileup(elba_ctx *ctx, elba_pileup_t *out);
 void elba_free_pileup(elba_pileup_t *p);
 int  elba_prune_reads(elba_ctx *ctx, int mask, int64_t *kept);
 
+/* Reads cut to their supported intervals, chimeras split: what GetTrimmedInterval's [beststart, bestend] is computed for (the reference
+ * never cuts: src/main.cpp does not call src/PruneChimeras.cpp).  elba_trim_reads turns the intervals of the LAST elba_read_pileup into a
+ * new read set on the device, which elba_adopt_trimmed_reads makes the context's own: reads -> pileup -> pieces -> k-mers -> ... -> contigs.
+ *   mode 0     one piece per read: its trimmed interval [trim_beg, trim_end); a read with (-1, -1) gives none.
+ *   mode 1     one piece per LONG RUN of the read: a maximal run of depth >= min_depth at least min_run bases long, with the min_depth /
+ *              min_run of the elba_read_pileup call that made the pileup (the runs the flags count): flag bit 0 <=> no piece, flag bit 1
+ *              <=> two or more (while min_len <= min_run).
+ * In both modes a piece shorter than min_len (>= 1) is dropped.  Pieces are numbered by (src_read, src_beg) ascending; piece p is bases
+ * [src_beg, src_end) of read src_read.  The new set is in DnaBuffer layout, as elba_set_reads_fasta leaves it: byte_off[p] (u64) is the
+ * running sum of (len + 3) / 4, len is u32, 16 zeroed guard bytes follow the last piece, and the unused low bits of a piece's last byte
+ * are zero whatever follows in the source (DnaSeq::compress, src/DnaSeq.cpp:17).
+ * Needs a valid pileup and the bases of its reads on the context (its own reads, as many as the pileup has, or the replicated set of
+ * elba_dist_set_all_reads: the choice elba_read_pileup makes for the lengths), otherwise ELBA_ERR_STATE.  A mode other than 0 / 1,
+ * min_len < 1 or a non-zero reserved word: ELBA_ERR_INVALID_ARG.
+ * The result is a snapshot in buffers of its own: it survives elba_prune_reads and elba_release_workspace; a new read set
+ * (elba_set_reads*, elba_dist_set_all_reads), a new elba_read_pileup or a new elba_trim_reads invalidates it (export, get and adopt then
+ * return ELBA_ERR_STATE).  Every read dropped is no error: n = 0, packed_bytes = 0, and adopting leaves a context with 0 reads.
+ * elba_adopt_trimmed_reads consumes the snapshot: the pieces become the context's reads exactly as after elba_set_reads (first_global_id
+ * 0; k-mers, A, B, alignments, edge list, string graph, pileup of the old reads invalidated; elba_export_reads returns the pieces); a
+ * second adopt without a new trim is ELBA_ERR_STATE.  The pointers of elba_get_trimmed_reads_device stay valid until the next
+ * elba_trim_reads, adopt or destroy. */
+typedef struct { int32_t mode; int32_t min_len; int32_t reserved[2]; } elba_trim_cfg;
+
+typedef struct {
+    int64_t nreads_in, pieces;                            /* reads of the pileup; pieces written */
+    int64_t reads_dropped, reads_split, reads_unchanged;  /* reads with no piece (reads of length 0 included) / two or more / one piece that is [0, len) */
+    int64_t bases_in, bases_out, packed_bytes, longest;   /* bases of the reads / of the pieces; bytes of the new packed buffer; longest piece in bases */
+    float   ms_total, ms_repack;                          /* device time of the stage / of the repack kernel */
+} elba_trim_stats;
+
+typedef struct { int64_t n; int64_t *src_read; int32_t *src_beg, *src_end; } elba_trim_map_t;   /* piece p = bases [src_beg, src_end) of read src_read */
+
+int  elba_trim_reads(elba_ctx *ctx, const elba_trim_cfg *cfg, elba_trim_stats *stats);
+int  elba_export_trim_map(elba_ctx *ctx, elba_trim_map_t *out);
+void elba_free_trim_map(elba_trim_map_t *m);
+int  elba_get_trimmed_reads_device(elba_ctx *ctx, const void **d_packed, int64_t *packed_bytes, const void **d_byte_off, const void **d_len, int64_t *n);
+int  elba_adopt_trimmed_reads(elba_ctx *ctx);
+
 int  elba_export_dcsc(elba_ctx *ctx, int64_t row_lo, int64_t row_hi, int64_t col_lo, int64_t col_hi, elba_dcsc_t *out);
 void elba_free_dcsc(elba_dcsc_t *d);
 int  elba_export_csr(elba_ctx *ctx, int64_t row_lo, int64_t row_hi, elba_csr_t *out);
