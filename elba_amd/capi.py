@@ -85,6 +85,14 @@ class ContigStats(C.Structure):
                 ("cycles", C.c_int64), ("contig_reads", C.c_int64), ("bases", C.c_int64), ("longest", C.c_int64), ("ms_total", C.c_float), ("ms_rank", C.c_float)]
 
 
+class ContigCfg(C.Structure):
+    _fields_ = [("flags", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+CONTIG_CIRCULAR, CONTIG_SINGLETONS = 1, 2          # elba_contig_cfg.flags
+CONTIG_KIND_PATH, CONTIG_KIND_CIRCULAR, CONTIG_KIND_SINGLE = 0, 1, 2
+
+
 class Contigs(C.Structure):
     _fields_ = [("n", C.c_int64), ("seq_off", C.c_void_p), ("seq", C.c_void_p), ("chain_off", C.c_void_p), ("chain_read", C.c_void_p),
                 ("chain_prefix", C.c_void_p), ("chain_strand", C.c_void_p)]
@@ -168,7 +176,7 @@ EXPORTED_SYMBOLS = [
     "elba_kmer_hash_owner", "elba_dist_value_histogram", "elba_dist_set_owner_ranges", "elba_dist_set_kmer_id_base", "elba_dist_count_owners", "elba_dist_fill_send", "elba_dist_packed_format", "elba_dist_fill_send_packed", "elba_dist_unpack_records", "elba_dist_count_records", "elba_dist_get_reliable_kmers", "elba_dist_copy_reliable_kmers",
     "elba_dist_set_global_kmers", "elba_dist_panel_counts", "elba_dist_panel_fill", "elba_dist_panel_counts_win", "elba_dist_panel_fill_win", "elba_dist_set_panel",
     "elba_seed_matrix_begin", "elba_seed_matrix_fill", "elba_seed_matrix_end", "elba_set_stream", "elba_seed_matrix_send", "elba_seed_matrix_recv", "elba_set_kmer_matrix_device", "elba_export_triples_device", "elba_get_stat", "elba_release_workspace",
-    "elba_generate_contigs", "elba_export_contigs", "elba_free_contigs", "elba_export_read_contigs",
+    "elba_generate_contigs", "elba_export_contigs", "elba_free_contigs", "elba_export_read_contigs", "elba_generate_contigs_ex", "elba_export_contig_kinds",
     "elba_read_pileup", "elba_export_pileup", "elba_free_pileup", "elba_prune_reads",
     "elba_trim_reads", "elba_export_trim_map", "elba_free_trim_map", "elba_get_trimmed_reads_device", "elba_adopt_trimmed_reads",
 ]
@@ -221,6 +229,8 @@ def load_library():
     L.elba_export_string_graph.restype = i32; L.elba_export_string_graph.argtypes = [vp, C.POINTER(Overlaps)]
     L.elba_export_read_flags.restype = i32; L.elba_export_read_flags.argtypes = [vp, vp, i64]
     L.elba_generate_contigs.restype = i32; L.elba_generate_contigs.argtypes = [vp, C.POINTER(ContigStats)]
+    L.elba_generate_contigs_ex.restype = i32; L.elba_generate_contigs_ex.argtypes = [vp, C.POINTER(ContigCfg), C.POINTER(ContigStats)]
+    L.elba_export_contig_kinds.restype = i32; L.elba_export_contig_kinds.argtypes = [vp, vp, i64]
     L.elba_export_contigs.restype = i32; L.elba_export_contigs.argtypes = [vp, C.POINTER(Contigs)]
     L.elba_free_contigs.restype = None; L.elba_free_contigs.argtypes = [C.POINTER(Contigs)]
     L.elba_export_read_contigs.restype = i32; L.elba_export_read_contigs.argtypes = [vp, vp, i64]
@@ -456,14 +466,24 @@ class Engine:
         return f
 
     # --- contigs (src/ContigGeneration.cpp:18-51,110,376-457, one rank) ---
-    def generate_contigs(self):
-        """GenerateContigs on the string graph of the last transitive_reduction: branches dropped, paths walked from their smaller end."""
+    def generate_contigs(self, circular=False, singletons=False):
+        """GenerateContigs on the string graph of the last transitive_reduction: branches dropped, paths walked from their smaller end.
+        circular: every cycle is also walked once round from its smallest read (towards its smaller neighbour).  singletons: every read in
+        no path and no cycle that is neither bad nor contained, and not empty, is also emitted, as it is.  All kinds by ascending start read."""
         st = ContigStats()
-        self._check(self.L.elba_generate_contigs(self.h, C.byref(st)))
+        cfg = ContigCfg((CONTIG_CIRCULAR if circular else 0) | (CONTIG_SINGLETONS if singletons else 0))
+        self._check(self.L.elba_generate_contigs_ex(self.h, C.byref(cfg), C.byref(st)))
         return _stats(st)
 
+    def export_contig_kinds(self, ncontigs):
+        """One byte per contig: 0 path, 1 circular, 2 single read."""
+        k = np.zeros(int(ncontigs), dtype=np.uint8)
+        self._check(self.L.elba_export_contig_kinds(self.h, k.ctypes.data, int(ncontigs)))
+        return k
+
     def export_contigs(self):
-        """{n, seqs (list of str, emission order), seq_off, chain_off, chain_read, chain_prefix, chain_strand}."""
+        """{n, seqs (list of str, emission order), seq_off, chain_off, chain_read, chain_prefix, chain_strand, kinds (0 path, 1 circular,
+        2 single read)}."""
         o = Contigs()
         self._check(self.L.elba_export_contigs(self.h, C.byref(o)))
         try:
@@ -474,12 +494,13 @@ class Engine:
             raw = _copy(o.seq, int(seq_off[-1]) if n else 0, np.uint8).tobytes()
             seqs = [raw[int(seq_off[i]):int(seq_off[i + 1])].decode("ascii") for i in range(n)]
             return dict(n=n, seqs=seqs, seq_off=seq_off if n else np.zeros(1, np.int64), chain_off=chain_off if n else np.zeros(1, np.int64),
-                        chain_read=_copy(o.chain_read, E, np.int64), chain_prefix=_copy(o.chain_prefix, E, np.int32), chain_strand=_copy(o.chain_strand, E, np.uint8))
+                        chain_read=_copy(o.chain_read, E, np.int64), chain_prefix=_copy(o.chain_prefix, E, np.int32), chain_strand=_copy(o.chain_strand, E, np.uint8),
+                        kinds=self.export_contig_kinds(n))
         finally:
             self.L.elba_free_contigs(C.byref(o))
 
     def export_read_contigs(self, nreads):
-        """Contig index of every read of the graph; -1 for branches, isolated reads and reads on cycles."""
+        """Contig index of every read of the graph; -1 for the reads in none (by default: branches, isolated reads and reads on cycles)."""
         out = np.zeros(int(nreads), dtype=np.int64)
         self._check(self.L.elba_export_read_contigs(self.h, out.ctypes.data, int(nreads)))
         return out

@@ -379,7 +379,19 @@ int elba_export_read_flags(elba_ctx *ctx, uint8_t *flags, int64_t nreads)
 int elba_generate_contigs(elba_ctx *ctx, elba_contig_stats *stats)
 {
     return guarded(ctx, [&](Ctx &c) {
-        stage_generate_contigs(c);
+        stage_generate_contigs(c, 0);
+        if (stats) *stats = c.cstats;
+    });
+}
+
+int elba_generate_contigs_ex(elba_ctx *ctx, const elba_contig_cfg *cfg, elba_contig_stats *stats)
+{
+    return guarded(ctx, [&](Ctx &c) {
+        c.have_contigs = false;                                     // a rejected call leaves no contigs either
+        ELBA_REQUIRE(cfg, ELBA_ERR_INVALID_ARG, "generate_contigs_ex: null cfg");
+        ELBA_REQUIRE(!cfg->reserved[0] && !cfg->reserved[1] && !cfg->reserved[2], ELBA_ERR_INVALID_ARG, "generate_contigs_ex: reserved words must be 0");
+        ELBA_REQUIRE((cfg->flags & ~(ELBA_CONTIG_CIRCULAR | ELBA_CONTIG_SINGLETONS)) == 0, ELBA_ERR_INVALID_ARG, "generate_contigs_ex: unknown flag bits");
+        stage_generate_contigs(c, cfg->flags);
         if (stats) *stats = c.cstats;
     });
 }
@@ -423,6 +435,16 @@ int elba_export_read_contigs(elba_ctx *ctx, int64_t *contig_of_read, int64_t nre
         ELBA_REQUIRE(nreads == c.tr_M && (contig_of_read || nreads == 0), ELBA_ERR_INVALID_ARG, "export_read_contigs: need one entry per read of the graph");
         const std::vector<int32_t> h = download<int32_t>(c, c.cg_cid.p, (size_t)nreads);
         for (int64_t v = 0; v < nreads; ++v) contig_of_read[v] = h[(size_t)v];
+    });
+}
+
+int elba_export_contig_kinds(elba_ctx *ctx, uint8_t *kind, int64_t ncontigs)
+{
+    return guarded(ctx, [&](Ctx &c) {
+        ELBA_REQUIRE(c.have_S && c.have_contigs, ELBA_ERR_STATE, "export_contig_kinds: no contigs of the current string graph (call elba_generate_contigs)");
+        ELBA_REQUIRE(ncontigs == c.cg_n && (kind || ncontigs == 0), ELBA_ERR_INVALID_ARG, "export_contig_kinds: need one byte per contig");
+        if (ncontigs) ELBA_HIP(hipMemcpyAsync(kind, c.cg_kind.p, (size_t)ncontigs, hipMemcpyDeviceToHost, c.stream));
+        ELBA_HIP(hipStreamSynchronize(c.stream));
     });
 }
 
@@ -716,7 +738,7 @@ int elba_release_workspace(elba_ctx *ctx)
         c.csr_words.release(); c.kid_of_entry.release();
         c.cg_ptr.release(); c.cg_slot.release(); c.cg_kdeg.release(); c.cg_term.release(); c.cg_vinfo.release(); c.cg_ctr.release();   // contig scratch (the results stay)
         c.cg_flag.release(); c.cg_cidx.release(); c.cg_nel.release(); c.cg_eoff.release();
-        for (int b = 0; b < 2; ++b) { c.cg_far[b].release(); c.cg_rank[b].release(); c.cg_mn[b].release(); }
+        for (int b = 0; b < 2; ++b) { c.cg_far[b].release(); c.cg_rank[b].release(); c.cg_mn[b].release(); c.cg_cfar[b].release(); c.cg_crank[b].release(); }
         c.pu_k0.release(); c.pu_k1.release(); c.pu_eptr.release(); c.pu_head.release(); c.pu_hidx.release(); c.pu_delta.release();   // pileup scratch (the results stay)
         c.pu_dsum.release(); c.pu_gstart.release(); c.pu_tok.release(); c.pu_tpos.release(); c.pu_sel.release(); c.pu_rows.release(); c.pu_cols.release(); c.pu_vals.release();
         c.tm_cnt.release(); c.tm_bytes.release(); c.tm_first.release(); c.tm_boff.release(); c.tm_srcb.release();   // trim scratch (the trimmed reads and their map stay)
@@ -747,6 +769,8 @@ int elba_get_stat(elba_ctx *ctx, const char *name, int64_t *value)
         else if (!strcmp(name, "gather_slots")) *value = c.have_A && c.use_ell ? c.ell_nslots : 0;
         else if (!strcmp(name, "contig_count")) *value = c.have_contigs ? c.cstats.contigs : 0;          // the last elba_generate_contigs (0: none valid)
         else if (!strcmp(name, "contig_cycles")) *value = c.have_contigs ? c.cstats.cycles : 0;
+        else if (!strcmp(name, "contig_circular")) *value = c.have_contigs ? c.cg_circular : 0;
+        else if (!strcmp(name, "contig_singletons")) *value = c.have_contigs ? c.cg_singletons : 0;
         else if (!strcmp(name, "contig_reads")) *value = c.have_contigs ? c.cstats.contig_reads : 0;
         else if (!strcmp(name, "contig_bases")) *value = c.have_contigs ? c.cstats.bases : 0;
         else if (!strcmp(name, "contig_branches")) *value = c.have_contigs ? c.cstats.branches : 0;

@@ -302,11 +302,12 @@ struct Ctx {
     DevBuf tr_deg, tr_pas, tr_flags, tr_k0, tr_v0, tr_k1, tr_v1, tr_ptr, tr_sym, tr_src, tr_mark, tr_ctr, tr_sel, tr_out_rows, tr_out_cols, tr_out_vals;
     elba_string_stats sstats{};
 
-    // contigs (contig.hip): results (cid, eread, epre, estr, eboff, soff, coff, seq) survive elba_release_workspace, the rest is scratch
+    // contigs (contig.hip): results (cid, eread, epre, estr, eboff, soff, coff, seq, kind) survive elba_release_workspace, the rest is scratch
     bool have_contigs = false;
-    int64_t cg_n = 0, cg_E = 0, cg_bases = 0;
+    int64_t cg_n = 0, cg_E = 0, cg_bases = 0, cg_circular = 0, cg_singletons = 0;
     DevBuf cg_ptr, cg_slot, cg_kdeg, cg_far[2], cg_rank[2], cg_mn[2], cg_term, cg_vinfo, cg_flag, cg_cidx, cg_nel, cg_eoff, cg_ctr;
-    DevBuf cg_cid, cg_eread, cg_epre, cg_estr, cg_eboff, cg_soff, cg_coff, cg_seq;
+    DevBuf cg_cid, cg_eread, cg_epre, cg_estr, cg_eboff, cg_soff, cg_coff, cg_seq, cg_kind;
+    DevBuf cg_cfar[2], cg_crank[2];          // scratch of the second ranking pass (ELBA_CONTIG_CIRCULAR)
     EventTimer cg_t_total, cg_t_rank;
     elba_contig_stats cstats{};
 
@@ -395,7 +396,7 @@ void stage_align_seeds(Ctx &c, int mat, int mis, int gap, int dropoff);   // ali
 void stage_dist_set_all_reads(Ctx &c, const void *d_packed, int64_t packed_bytes, const void *d_byte_off, const void *d_len, int64_t nreads_total);   // align.hip
 void stage_set_overlaps(Ctx &c, int64_t nreads, const int64_t *rows, const int64_t *cols, const elba_overlap_t *vals, int64_t n);   // tr.hip
 void stage_transitive_reduction(Ctx &c, double bad_read_cutoff, int fuzz);   // tr.hip
-void stage_generate_contigs(Ctx &c);                                          // contig.hip
+void stage_generate_contigs(Ctx &c, int flags);                                          // contig.hip
 void stage_read_pileup(Ctx &c, const elba_pileup_cfg &cfg);                   // pileup.hip
 void stage_prune_reads(Ctx &c, int mask, int64_t *kept);
 void stage_trim_reads(Ctx &c, const elba_trim_cfg &cfg);                      // trim.hip

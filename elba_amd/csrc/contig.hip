@@ -23,6 +23,24 @@
 //   k_cg_write        one wavefront per element: 2-bit packed bases -> ASCII, reverse complement on the strand bit; lanes own 8-byte
 //                     aligned words of the output, whole words go out as one 8-byte store, the two boundary words bytewise
 //
+// Two opt-in extensions (elba_generate_contigs_ex; with flags 0 nothing below is launched and the sequence above is unchanged):
+//
+//   ELBA_CONTIG_CIRCULAR    pointer jumping cannot rank a cycle, so it is cut: after the R rounds k_cg_cut rebuilds the initial arcs with
+//                           every arc whose head is its cycle's smallest read s (mn of the first pass, which stays untouched) terminal,
+//                           and k_cg_jump2 x R ranks the cut cycles (far, rank; arcs off every cycle and the cut arcs are fixed points
+//                           written to both buffers once and skipped; every round returns at once when k_cg_cut counted no cut arc on
+//                           the device, the host does not wait for that count).  Both arcs leaving a cycle read now reach a terminal arc into s; the one
+//                           that points along the walk (s -> its smaller neighbour -> ...) ends in the arc whose tail is s's larger
+//                           neighbour.  Cycle length = rank of s's chosen arc + 1, place in the chain = length - 1 - rank, outgoing slot =
+//                           the chosen arc's, for the last read too (its next is s): every element follows the interior rule, the
+//                           contig closes on itself.  No strand-consistency check (the reference makes none on paths either).
+//   ELBA_CONTIG_SINGLETONS  a read with no kept neighbour (isolated, or a branch) whose read flags are 0 and whose length is not 0 is a
+//                           chain of its own: (v, len, strand 0).
+//
+// The starts of all three kinds set `flag`, so the scans merge them by ascending start read; k_cg_contigs writes each contig's kind.
+// The second ranking pass moves 2 x 4 bytes x 2 x 2M per round when cycles exist (it carries no mn), against the first pass's
+// 3 x 4 bytes x 2 x 2M; 4 bytes x 2M per round for a graph whose arcs are all off cycles would be read if the count did not end the round first.
+//
 // Bounds: every index into S is below tr_nnz, every vertex index below M, arc ids below 2M, chain elements below M (a read is in at most
 // one chain), base offsets below the total the scan returns, which sizes the output.  Bytes moved (algorithmic): S once (8 + 36 bytes per
 // entry, the rows / values of the at most two entries of a non-branch column), 3 x 4 bytes x 2 x 2M per jump round, O(M) for the scans,
@@ -99,9 +117,45 @@ __global__ void k_cg_jump(uint32_t n, const uint32_t *far0, const uint32_t *rank
     mn1[a] = m0 < m1 ? m0 : m1;
 }
 
+// CIRCULAR: the initial arcs again, cut at every cycle's smallest read.  far / mn: the first pass's result (read only).  A cycle arc whose
+// head is mn becomes terminal; arcs that need no ranking (off every cycle, cut, absent) are fixed points in both buffers.  ctr[8]: cut arcs.
+__global__ void k_cg_cut(const CgSlot *slot, const uint8_t *kdeg, const uint32_t *far, const uint32_t *mn, const uint8_t *term, uint32_t M,
+                         uint32_t *cfar0, uint32_t *crank0, uint32_t *cfar1, uint32_t *crank1, unsigned long long *ctr)
+{
+    const uint32_t a = blockIdx.x * blockDim.x + threadIdx.x;
+    bool cut = false;
+    if (a < 2 * M) {
+        const uint32_t v = a >> 1, k = a & 1u;
+        uint32_t succ = CG_NONE;
+        if (k < kdeg[v] && !term[far[a]]) {                     // a cycle arc: both ends have two kept neighbours
+            const uint32_t w = slot[a].nb;
+            cut = w == mn[a];
+            if (!cut) succ = slot[2 * w].nb == v ? 2 * w + 1 : 2 * w;
+        }
+        if (succ == CG_NONE) { cfar0[a] = a; crank0[a] = 0; cfar1[a] = a; crank1[a] = 0; }
+        else { cfar0[a] = succ; crank0[a] = 1; }
+    }
+    const unsigned long long b = __ballot(cut);
+    if (b && (threadIdx.x & 63) == (unsigned)__builtin_ctzll(b)) atomicAdd(&ctr[8], (unsigned long long)__builtin_popcountll(b));
+}
+
+__global__ void k_cg_jump2(uint32_t n, const uint32_t *far0, const uint32_t *rank0, uint32_t *far1, uint32_t *rank1, const unsigned long long *ctr)
+{
+    if (ctr[8] == 0) return;                                    // no cycle: every arc is a fixed point in both buffers
+    const uint32_t a = blockIdx.x * blockDim.x + threadIdx.x;
+    if (a >= n) return;
+    const uint32_t f = far0[a];
+    if (f == a) return;
+    far1[a] = far0[f];
+    rank1[a] = rank0[a] + rank0[f];
+}
+
 // vinfo[v] = {start, place in the chain, slot of the outgoing edge (CG_NONE: last element)}; flag / nel at the starts
+// vinfo.w = the kind of v's contig (0 path, 1 circular, 2 single read).  cfar / crank: the ranks of the cut cycles (CIRCULAR only);
+// rflags / len: the read flags of the transitive reduction and the read lengths (SINGLETONS only)
 __global__ void k_cg_vertices(const CgSlot *slot, const uint8_t *kdeg, const uint32_t *far, const uint32_t *rank, const uint32_t *mn, const uint8_t *term,
-                              uint32_t M, uint4 *vinfo, uint32_t *flag, uint32_t *nel, unsigned long long *ctr)
+                              uint32_t M, uint4 *vinfo, uint32_t *flag, uint32_t *nel, unsigned long long *ctr, int cflags, const uint32_t *cfar,
+                              const uint32_t *crank, const uint8_t *rflags, const uint32_t *len)
 {
     const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
     bool cycle_head = false;
@@ -112,7 +166,16 @@ __global__ void k_cg_vertices(const CgSlot *slot, const uint8_t *kdeg, const uin
         if (kd > 0) {
             const uint32_t f0 = far[2 * v];
             if (!term[f0]) {                                        // on a cycle: no degree-1 read, the walk never starts there
-                cycle_head = kd == 2 && mn[2 * v] == v;
+                const uint32_t s = mn[2 * v];
+                cycle_head = kd == 2 && s == v;
+                if (cflags & ELBA_CONTIG_CIRCULAR) {                // the walk leaves s towards its smaller neighbour and comes back by the larger
+                    const uint32_t n0 = slot[2 * s].nb, n1 = slot[2 * s + 1].nb;
+                    const uint32_t hi = n0 < n1 ? n1 : n0, sarc = 2 * s + (n0 < n1 ? 0u : 1u);
+                    const uint32_t out = (cfar[2 * v] >> 1) == hi ? 0u : 1u;        // the arc whose terminal arc leaves s's larger neighbour
+                    const uint32_t L = crank[sarc] + 1;
+                    info = make_uint4(s, L - 1 - crank[2 * v + out], out, 1);
+                    if (v == s) { f = 1; n = L; }
+                }
             } else {
                 const uint32_t e0 = slot[f0].nb;
                 const uint32_t e1 = kd == 2 ? slot[far[2 * v + 1]].nb : v;      // the two ends of the path (v itself when it is one)
@@ -124,6 +187,8 @@ __global__ void k_cg_vertices(const CgSlot *slot, const uint8_t *kdeg, const uin
                 else { pos = rank[2 * v + 1] + 1; out = 0; }
                 info = make_uint4(s, pos, out, 0);
             }
+        } else if ((cflags & ELBA_CONTIG_SINGLETONS) && rflags[v] == 0 && len[v] != 0) {     // no kept neighbour (isolated or a branch), neither bad nor contained
+            info = make_uint4(v, 0, CG_NONE, 2); f = 1; n = 1;
         }
         vinfo[v] = info; flag[v] = f; nel[v] = n;
     } else if (v == M) { flag[v] = 0; nel[v] = 0; }
@@ -148,26 +213,33 @@ __global__ void k_cg_elements(const CgSlot *slot, const uint4 *vinfo, const uint
         prefix = o.sfx; strand = (o.dwalk >> 1) & 1;                   // (o.direction >> 1) & 1, :437
         if (prefix < 0 || prefix > L) { atomicMin(&ctr[3], ((unsigned long long)v << 32) | o.nb); prefix = 0; }
     } else {
-        prefix = L; strand = 1 - (slot[2 * v].din & 1);                // 1 - (lastdir & 1), :450
+        prefix = L; strand = info.w == 2 ? 0 : 1 - (slot[2 * v].din & 1);      // 1 - (lastdir & 1), :450; a single read as it is
     }
     epre[el] = prefix; estr[el] = (uint8_t)strand;
 }
 
-__global__ void k_cg_contigs(const uint32_t *flag, const uint32_t *cidx, const uint32_t *eoff, const uint32_t *nel, const int64_t *eboff, uint32_t M,
-                             int64_t *soff, int64_t *coff, unsigned long long *ctr)
+// ctr[9] circular contigs, ctr[10] single-read contigs
+__global__ void k_cg_contigs(const uint32_t *flag, const uint32_t *cidx, const uint32_t *eoff, const uint32_t *nel, const int64_t *eboff, const uint4 *vinfo, uint32_t M,
+                             int64_t *soff, int64_t *coff, uint8_t *kind, unsigned long long *ctr)
 {
     const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t kd = 0;
     if (v == M) {
         const uint32_t nc = cidx[M], E = eoff[M];
         soff[nc] = eboff[E]; coff[nc] = E;
         ctr[4] = nc; ctr[5] = E; ctr[6] = (unsigned long long)eboff[E];
-        return;
+    } else if (v < M && flag[v]) {
+        const uint32_t k = cidx[v], e = eoff[v];
+        const int64_t b0 = eboff[e], b1 = eboff[e + nel[v]];
+        soff[k] = b0; coff[k] = e;
+        kd = vinfo[v].w;
+        kind[k] = (uint8_t)kd;
+        atomicMax(&ctr[7], (unsigned long long)(b1 - b0));
     }
-    if (v > M || !flag[v]) return;
-    const uint32_t k = cidx[v], e = eoff[v];
-    const int64_t b0 = eboff[e], b1 = eboff[e + nel[v]];
-    soff[k] = b0; coff[k] = e;
-    atomicMax(&ctr[7], (unsigned long long)(b1 - b0));
+    const unsigned long long bc = __ballot(kd == 1), bs = __ballot(kd == 2);
+    const unsigned lane = threadIdx.x & 63;
+    if (bc && lane == (unsigned)__builtin_ctzll(bc)) atomicAdd(&ctr[9], (unsigned long long)__builtin_popcountll(bc));
+    if (bs && lane == (unsigned)__builtin_ctzll(bs)) atomicAdd(&ctr[10], (unsigned long long)__builtin_popcountll(bs));
 }
 
 __device__ __forceinline__ uint32_t cg_base(const uint8_t *mem, uint32_t i) { return (mem[i >> 2] >> (6 - 2 * (i & 3))) & 3u; }   // src/DnaSeq.cpp:48-54
@@ -213,9 +285,10 @@ __global__ __launch_bounds__(CG_WRITE_THREADS) void k_cg_write(const int64_t *er
 
 }  // namespace
 
-void stage_generate_contigs(Ctx &c)
+void stage_generate_contigs(Ctx &c, int flags)
 {
     c.have_contigs = false;
+    ELBA_REQUIRE((flags & ~(ELBA_CONTIG_CIRCULAR | ELBA_CONTIG_SINGLETONS)) == 0, ELBA_ERR_INVALID_ARG, "generate_contigs: unknown flag bits");
     ELBA_REQUIRE(c.have_S, ELBA_ERR_STATE, "generate_contigs: no string graph (call elba_transitive_reduction)");
     const int64_t M = c.tr_M, nnz = c.tr_nnz;
     const uint8_t *packed; const uint64_t *byte_off; const uint32_t *len;
@@ -234,11 +307,15 @@ void stage_generate_contigs(Ctx &c)
     c.cg_term.reserve((size_t)2 * M + 4); c.cg_vinfo.reserve((size_t)(M + 1) * sizeof(uint4));
     c.cg_flag.reserve((size_t)(M + 2) * 4); c.cg_cidx.reserve((size_t)(M + 2) * 4); c.cg_nel.reserve((size_t)(M + 2) * 4); c.cg_eoff.reserve((size_t)(M + 2) * 4);
     c.cg_cid.reserve((size_t)(M + 1) * 4); c.cg_eread.reserve((size_t)(M + 1) * 8); c.cg_epre.reserve((size_t)(M + 2) * 4); c.cg_estr.reserve((size_t)M + 4);
-    c.cg_eboff.reserve((size_t)(M + 2) * 8); c.cg_soff.reserve((size_t)(M + 2) * 8); c.cg_coff.reserve((size_t)(M + 2) * 8); c.cg_ctr.reserve(64);
+    c.cg_eboff.reserve((size_t)(M + 2) * 8); c.cg_soff.reserve((size_t)(M + 2) * 8); c.cg_coff.reserve((size_t)(M + 2) * 8); c.cg_ctr.reserve(128);
+    c.cg_kind.reserve((size_t)M + 4);
+    const bool circular = (flags & ELBA_CONTIG_CIRCULAR) != 0;
+    if (circular)                                               // the second ranking pass reads the first one's far / mn / term, which stay as they are
+        for (int b = 0; b < 2; ++b) { c.cg_cfar[b].reserve((size_t)(2 * M + 2) * 4); c.cg_crank[b].reserve((size_t)(2 * M + 2) * 4); }
     uint32_t *ptr = c.cg_ptr.as<uint32_t>(); CgSlot *slot = c.cg_slot.as<CgSlot>(); uint8_t *kdeg = c.cg_kdeg.as<uint8_t>(), *term = c.cg_term.as<uint8_t>();
     unsigned long long *ctr = c.cg_ctr.as<unsigned long long>();
     c.cg_t_total.start(s);
-    ELBA_HIP(hipMemsetAsync(ctr, 0, 64, s));
+    ELBA_HIP(hipMemsetAsync(ctr, 0, 128, s));
     ELBA_HIP(hipMemsetAsync(ctr + 3, 0xff, 8, s));
     ELBA_HIP(hipMemsetAsync(c.cg_epre.p, 0, (size_t)(M + 2) * 4, s));
     const unsigned nbM = (unsigned)((M + 1 + 255) / 256), nbA = (unsigned)((2 * M + 255) / 256);
@@ -255,21 +332,30 @@ void stage_generate_contigs(Ctx &c)
             hipLaunchKernelGGL(k_cg_jump, dim3(nbA), dim3(256), 0, s, (uint32_t)(2 * M), c.cg_far[which].as<uint32_t>(), c.cg_rank[which].as<uint32_t>(), c.cg_mn[which].as<uint32_t>(),
                                c.cg_far[which ^ 1].as<uint32_t>(), c.cg_rank[which ^ 1].as<uint32_t>(), c.cg_mn[which ^ 1].as<uint32_t>());
     }
+    int cwhich = 0;
+    if (circular && M > 0) {
+        hipLaunchKernelGGL(k_cg_cut, dim3(nbA), dim3(256), 0, s, slot, kdeg, c.cg_far[which].as<uint32_t>(), c.cg_mn[which].as<uint32_t>(), term, (uint32_t)M,
+                           c.cg_cfar[0].as<uint32_t>(), c.cg_crank[0].as<uint32_t>(), c.cg_cfar[1].as<uint32_t>(), c.cg_crank[1].as<uint32_t>(), ctr);
+        for (int r = 0; r < R; ++r, cwhich ^= 1)
+            hipLaunchKernelGGL(k_cg_jump2, dim3(nbA), dim3(256), 0, s, (uint32_t)(2 * M), c.cg_cfar[cwhich].as<uint32_t>(), c.cg_crank[cwhich].as<uint32_t>(),
+                               c.cg_cfar[cwhich ^ 1].as<uint32_t>(), c.cg_crank[cwhich ^ 1].as<uint32_t>(), ctr);
+    }
     c.cg_t_rank.stop(s);
     uint32_t *flag = c.cg_flag.as<uint32_t>(), *cidx = c.cg_cidx.as<uint32_t>(), *nel = c.cg_nel.as<uint32_t>(), *eoff = c.cg_eoff.as<uint32_t>();
     hipLaunchKernelGGL(k_cg_vertices, dim3(nbM), dim3(256), 0, s, slot, kdeg, c.cg_far[which].as<uint32_t>(), c.cg_rank[which].as<uint32_t>(), c.cg_mn[which].as<uint32_t>(), term,
-                       (uint32_t)M, c.cg_vinfo.as<uint4>(), flag, nel, ctr);
+                       (uint32_t)M, c.cg_vinfo.as<uint4>(), flag, nel, ctr, flags, circular ? c.cg_cfar[cwhich].as<uint32_t>() : nullptr,
+                       circular ? c.cg_crank[cwhich].as<uint32_t>() : nullptr, c.tr_flags.as<uint8_t>(), len);
     exclusive_scan_u32(s, flag, cidx, M + 1, c.ws_scan);
     exclusive_scan_u32(s, nel, eoff, M + 1, c.ws_scan);
     if (M > 0)
         hipLaunchKernelGGL(k_cg_elements, dim3(nbM), dim3(256), 0, s, slot, c.cg_vinfo.as<uint4>(), cidx, eoff, len, (uint32_t)M, base, c.cg_cid.as<int32_t>(),
                            c.cg_eread.as<int64_t>(), c.cg_epre.as<int32_t>(), c.cg_estr.as<uint8_t>(), ctr);
     exclusive_scan_u32_to_i64(s, c.cg_epre.as<uint32_t>(), c.cg_eboff.as<int64_t>(), M + 1, c.ws_scan);     // prefixes are >= 0 here (bad ones were zeroed)
-    hipLaunchKernelGGL(k_cg_contigs, dim3(nbM), dim3(256), 0, s, flag, cidx, eoff, nel, c.cg_eboff.as<int64_t>(), (uint32_t)M, c.cg_soff.as<int64_t>(),
-                       c.cg_coff.as<int64_t>(), ctr);
+    hipLaunchKernelGGL(k_cg_contigs, dim3(nbM), dim3(256), 0, s, flag, cidx, eoff, nel, c.cg_eboff.as<int64_t>(), c.cg_vinfo.as<uint4>(), (uint32_t)M,
+                       c.cg_soff.as<int64_t>(), c.cg_coff.as<int64_t>(), c.cg_kind.as<uint8_t>(), ctr);
     ELBA_HIP(hipGetLastError());
-    unsigned long long h[8] = {0};
-    ELBA_HIP(hipMemcpyAsync(h, ctr, 64, hipMemcpyDeviceToHost, s));
+    unsigned long long h[16] = {0};
+    ELBA_HIP(hipMemcpyAsync(h, ctr, 128, hipMemcpyDeviceToHost, s));
     ELBA_HIP(hipStreamSynchronize(s));
     if (h[3] != ~0ull) {
         const uint32_t v = (uint32_t)(h[3] >> 32), r = (uint32_t)h[3];
@@ -293,12 +379,13 @@ void stage_generate_contigs(Ctx &c)
     }
     c.cg_t_total.stop(s);
     ELBA_HIP(hipStreamSynchronize(s));
+    const int64_t ncirc = (int64_t)h[9], nsingle = (int64_t)h[10];
     st.branches = (int64_t)h[0]; st.cycles = (int64_t)h[2]; st.contigs = nc;
-    st.used_components = nc + st.cycles;
+    st.used_components = nc - ncirc - nsingle + st.cycles;                  // paths + cycles, whether the cycles were emitted or not
     st.components = st.branches + (int64_t)h[1] + st.used_components;     // CC on S without the branches' rows and columns: a branch read is a component of its own
     st.contig_reads = E; st.bases = bases; st.longest = (int64_t)h[7];
     st.ms_total = c.cg_t_total.ms(); st.ms_rank = c.cg_t_rank.ms();
-    c.cg_n = nc; c.cg_E = E; c.cg_bases = bases; c.cstats = st; c.have_contigs = true;
+    c.cg_n = nc; c.cg_E = E; c.cg_bases = bases; c.cg_circular = ncirc; c.cg_singletons = nsingle; c.cstats = st; c.have_contigs = true;
 }
 
 }  // namespace elba

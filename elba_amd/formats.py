@@ -100,11 +100,14 @@ def write_paf(path, overlaps, names, lens, dcsc_order=False):
             f.write(paf_line(overlaps["vals"][a], names[i], names[j], int(lens[i]), int(lens[j])) + "\n")
 
 
-def write_contigs_fasta(path, seqs, first=0):
+def write_contigs_fasta(path, seqs, first=0, kinds=None):
     """<prefix>.contigs.fa as parallel_write_contigs writes it (src/main.cpp:496-499): `>contig<i>` then the sequence, i counted from `first`
-    (the rank's offset from MPI_Exscan; 0 on one rank)."""
+    (the rank's offset from MPI_Exscan; 0 on one rank).  With `kinds` (one per contig, Engine.export_contigs()["kinds"]) the header of a
+    circular contig (kind 1) is `>contig<i> circular`; every other line is the same."""
+    if kinds is not None and len(kinds) != len(seqs):
+        raise ValueError("write_contigs_fasta: one kind per contig")
     with open(path, "wb") as f:
         for i, s in enumerate(seqs):
-            f.write(b">contig%d\n" % (i + first))
+            f.write(b">contig%d%s\n" % (i + first, b" circular" if kinds is not None and int(kinds[i]) == 1 else b""))
             f.write(s.encode("ascii") if isinstance(s, str) else bytes(s))
             f.write(b"\n")

@@ -560,12 +560,18 @@ inline DnaBuffer AdoptTrimmedReads(OverlapMatrix &R)
 // GenerateContigs(S, mydna, dfd) — src/ContigGeneration.cpp:376-457 on one rank: branches (degree > 2) dropped, every path of >= 2 reads
 // walked from its smaller-id end, the contig built from the reads' prefixes; on the GPU, on the S that TransitiveReduction left there.
 // The reads are the ones the context was given (mydna on one rank).  Contigs in the reference's emission order.
-inline std::vector<std::string> GenerateContigs(StringGraph &S, const DnaBuffer &mydna, elba_contig_stats *stats = nullptr)
+// flags (not in the reference): ELBA_CONTIG_CIRCULAR also walks every cycle once round from its smallest read, ELBA_CONTIG_SINGLETONS also
+// emits every unflagged read outside all paths and cycles as a contig of its own; contigs of all kinds by ascending start read.  kinds, if
+// given, receives one byte per contig: 0 path, 1 circular, 2 single read.
+inline std::vector<std::string> GenerateContigs(StringGraph &S, const DnaBuffer &mydna, elba_contig_stats *stats = nullptr, int flags = 0,
+                                                std::vector<uint8_t> *kinds = nullptr)
 {
     if (!S.engine) throw Error(ELBA_ERR_STATE, "GenerateContigs: the string graph is not on a device");
     if ((int64_t)mydna.size() != S.numreads) throw Error(ELBA_ERR_INVALID_ARG, "GenerateContigs: mydna does not hold the graph's reads");
     elba_contig_stats st{};
-    S.engine->check(elba_generate_contigs(S.engine->ctx, &st));
+    elba_contig_cfg cfg{};
+    cfg.flags = flags;
+    S.engine->check(elba_generate_contigs_ex(S.engine->ctx, &cfg, &st));
     if (stats) *stats = st;
     elba_contigs_t c;
     S.engine->check(elba_export_contigs(S.engine->ctx, &c));
@@ -573,15 +579,22 @@ inline std::vector<std::string> GenerateContigs(StringGraph &S, const DnaBuffer 
     contigs.reserve((size_t)c.n);
     for (int64_t i = 0; i < c.n; ++i) contigs.emplace_back(c.seq + c.seq_off[i], (size_t)(c.seq_off[i + 1] - c.seq_off[i]));
     elba_free_contigs(&c);
+    if (kinds) {
+        kinds->assign(contigs.size(), 0);
+        S.engine->check(elba_export_contig_kinds(S.engine->ctx, kinds->data(), (int64_t)contigs.size()));
+    }
     return contigs;
 }
 
 // parallel_write_contigs (src/main.cpp:487-512) on one rank: the Exscan offset is 0; the reference takes the name from
 // get_contigs_fasta_name() (<prefix>.contigs.fa), here it is an argument.
-inline void parallel_write_contigs(const std::vector<std::string> &contigs, const std::string &contigs_fname)
+// With kinds (GenerateContigs' own, one per contig) the header of a circular contig is `>contig<i> circular`; nothing else changes.
+inline void parallel_write_contigs(const std::vector<std::string> &contigs, const std::string &contigs_fname, const std::vector<uint8_t> *kinds = nullptr)
 {
+    if (kinds && kinds->size() != contigs.size()) throw Error(ELBA_ERR_INVALID_ARG, "parallel_write_contigs: one kind per contig");
     std::stringstream contig_filecontents;
-    for (size_t i = 0; i < contigs.size(); ++i) contig_filecontents << ">contig" << i << "\n" << contigs[i] << "\n";
+    for (size_t i = 0; i < contigs.size(); ++i)
+        contig_filecontents << ">contig" << i << (kinds && (*kinds)[i] == 1 ? " circular" : "") << "\n" << contigs[i] << "\n";
     std::ofstream f(contigs_fname, std::ios::binary);
     const std::string cfs = contig_filecontents.str();
     f.write(cfs.data(), (std::streamsize)cfs.size());

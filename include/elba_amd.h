@@ -318,9 +318,30 @@ typedef struct {
 } elba_contigs_t;
 
 int  elba_generate_contigs(elba_ctx *ctx, elba_contig_stats *stats);
+
+/* Two opt-in extensions of elba_generate_contigs; elba_generate_contigs(ctx, st) is elba_generate_contigs_ex with flags 0.  Every contig
+ * has a start read, and contigs of all kinds come merged by ascending start read (a path's start is its smaller end).
+ *   ELBA_CONTIG_CIRCULAR    a cycle (a component of the branch-free graph whose reads all have two kept neighbours; >= 3 reads) is walked
+ *                           from its smallest read s towards the smaller of s's two neighbours, once round.  Every element, the last one
+ *                           included, takes prefix = suffixT of S(cur, next) and strand = (direction of S(cur, next) >> 1) & 1; for the last
+ *                           one next = s, so the sequence closes on itself and the bases s shares with its predecessor are not written
+ *                           twice.  A prefix outside [0, len] fails as on a path, the closing element's included.  Strand consistency
+ *                           round the cycle is not checked (the reference checks none on paths either).
+ *   ELBA_CONTIG_SINGLETONS  every read in no path and no cycle (no kept neighbour, or a branch) whose flags of elba_export_read_flags are 0
+ *                           and whose length is not 0 is a contig of one element (read, len, strand 0).  Reads of a cycle are never
+ *                           singletons; without ELBA_CONTIG_CIRCULAR they emit nothing.
+ * In the stats contigs, contig_reads, bases and longest cover everything emitted; branches, components, used_components and cycles keep
+ * their meaning (cycles: found, emitted or not).  elba_get_stat "contig_circular" / "contig_singletons": the counts of the last call.
+ * A null cfg, unknown flag bits or a non-zero reserved word: ELBA_ERR_INVALID_ARG, no contigs left valid.
+ * elba_export_contig_kinds: one byte per contig of the last call, 0 path, 1 circular, 2 single read; ELBA_ERR_STATE without valid contigs,
+ * ELBA_ERR_INVALID_ARG unless ncontigs is their count. */
+enum { ELBA_CONTIG_CIRCULAR = 1, ELBA_CONTIG_SINGLETONS = 2 };
+typedef struct { int32_t flags; int32_t reserved[3]; } elba_contig_cfg;
+int  elba_generate_contigs_ex(elba_ctx *ctx, const elba_contig_cfg *cfg, elba_contig_stats *stats);
+int  elba_export_contig_kinds(elba_ctx *ctx, uint8_t *kind, int64_t ncontigs);
 int  elba_export_contigs(elba_ctx *ctx, elba_contigs_t *out);
 void elba_free_contigs(elba_contigs_t *c);
-int  elba_export_read_contigs(elba_ctx *ctx, int64_t *contig_of_read, int64_t nreads);  /* contig index of every read, -1: branch, singleton or cycle */
+int  elba_export_read_contigs(elba_ctx *ctx, int64_t *contig_of_read, int64_t nreads);  /* contig index of every read, -1: in none (without the _ex flags: branch, singleton or cycle) */
 
 /* Read pileups and chimera flags: PileupVector / GetReadPileup / GetTrimmedInterval (src/PruneChimeras.cpp:14-69,108-158,
  * include/PruneChimeras.hpp), which src/main.cpp never calls, and R->PruneFull(x, x) of the reads it flags.  Runs after elba_align_seeds,
