@@ -125,6 +125,16 @@ class TrimMap(C.Structure):
     _fields_ = [("n", C.c_int64), ("src_read", C.c_void_p), ("src_beg", C.c_void_p), ("src_end", C.c_void_p)]
 
 
+class TipCfg(C.Structure):
+    _fields_ = [("max_tip_reads", C.c_int32), ("rounds", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class TipStats(C.Structure):
+    _fields_ = [("nreads", C.c_int64), ("nnz_before", C.c_int64), ("nnz_after", C.c_int64), ("dead_ends", C.c_int64), ("tips", C.c_int64),
+                ("reads_removed", C.c_int64), ("entries_removed", C.c_int64), ("spared_anchors", C.c_int64), ("rounds_run", C.c_int32), ("reserved", C.c_int32),
+                ("ms_total", C.c_float), ("ms_compact", C.c_float)]
+
+
 class Overlaps(C.Structure):
     _fields_ = [("n", C.c_int64), ("rows", C.c_void_p), ("cols", C.c_void_p), ("vals", C.c_void_p)]
 
@@ -179,6 +189,7 @@ EXPORTED_SYMBOLS = [
     "elba_generate_contigs", "elba_export_contigs", "elba_free_contigs", "elba_export_read_contigs", "elba_generate_contigs_ex", "elba_export_contig_kinds",
     "elba_read_pileup", "elba_export_pileup", "elba_free_pileup", "elba_prune_reads",
     "elba_trim_reads", "elba_export_trim_map", "elba_free_trim_map", "elba_get_trimmed_reads_device", "elba_adopt_trimmed_reads",
+    "elba_clip_tips",
 ]
 
 _lib = None
@@ -228,6 +239,7 @@ def load_library():
     L.elba_transitive_reduction.restype = i32; L.elba_transitive_reduction.argtypes = [vp, C.c_double, i32, C.POINTER(StringStats)]
     L.elba_export_string_graph.restype = i32; L.elba_export_string_graph.argtypes = [vp, C.POINTER(Overlaps)]
     L.elba_export_read_flags.restype = i32; L.elba_export_read_flags.argtypes = [vp, vp, i64]
+    L.elba_clip_tips.restype = i32; L.elba_clip_tips.argtypes = [vp, C.POINTER(TipCfg), C.POINTER(TipStats)]
     L.elba_generate_contigs.restype = i32; L.elba_generate_contigs.argtypes = [vp, C.POINTER(ContigStats)]
     L.elba_generate_contigs_ex.restype = i32; L.elba_generate_contigs_ex.argtypes = [vp, C.POINTER(ContigCfg), C.POINTER(ContigStats)]
     L.elba_export_contig_kinds.restype = i32; L.elba_export_contig_kinds.argtypes = [vp, vp, i64]
@@ -460,10 +472,21 @@ class Engine:
             self.L.elba_free_overlaps(C.byref(o))
 
     def export_read_flags(self, nreads):
-        """One byte per read: bit 0 = bad read, bit 1 = contained read."""
+        """One byte per read: bit 0 = bad read, bit 1 = contained read, bit 2 = removed by clip_tips."""
         f = np.zeros(int(nreads), dtype=np.uint8)
         self._check(self.L.elba_export_read_flags(self.h, f.ctypes.data, int(nreads)))
         return f
+
+    # --- tip clipping (between transitive_reduction and generate_contigs; not in the reference) ---
+    def clip_tips(self, max_tip_reads, rounds=1):
+        """Removes dead-end chains of at most max_tip_reads reads that hang off a read of degree >= 3 from the string graph, in up to
+        `rounds` rounds (a star of nothing but short chains is spared).  Removed reads get flag 4.  Returns the stats."""
+        cfg = TipCfg(int(max_tip_reads), int(rounds), (C.c_int32 * 2)(0, 0))
+        st = TipStats()
+        self._check(self.L.elba_clip_tips(self.h, C.byref(cfg), C.byref(st)))
+        d = _stats(st)
+        d.pop("reserved", None)
+        return d
 
     # --- contigs (src/ContigGeneration.cpp:18-51,110,376-457, one rank) ---
     def generate_contigs(self, circular=False, singletons=False):

@@ -376,6 +376,16 @@ int elba_export_read_flags(elba_ctx *ctx, uint8_t *flags, int64_t nreads)
     });
 }
 
+int elba_clip_tips(elba_ctx *ctx, const elba_tip_cfg *cfg, elba_tip_stats *stats)
+{
+    return guarded(ctx, [&](Ctx &c) {
+        ELBA_REQUIRE(c.have_S, ELBA_ERR_STATE, "clip_tips: no string graph (call elba_transitive_reduction)");
+        ELBA_REQUIRE(cfg, ELBA_ERR_INVALID_ARG, "clip_tips: null cfg");
+        stage_clip_tips(c, *cfg);                                   // (a rejected cfg leaves S and the contigs as they are)
+        if (stats) *stats = c.tpstats;
+    });
+}
+
 int elba_generate_contigs(elba_ctx *ctx, elba_contig_stats *stats)
 {
     return guarded(ctx, [&](Ctx &c) {
@@ -742,6 +752,8 @@ int elba_release_workspace(elba_ctx *ctx)
         c.pu_k0.release(); c.pu_k1.release(); c.pu_eptr.release(); c.pu_head.release(); c.pu_hidx.release(); c.pu_delta.release();   // pileup scratch (the results stay)
         c.pu_dsum.release(); c.pu_gstart.release(); c.pu_tok.release(); c.pu_tpos.release(); c.pu_sel.release(); c.pu_rows.release(); c.pu_cols.release(); c.pu_vals.release();
         c.tm_cnt.release(); c.tm_bytes.release(); c.tm_first.release(); c.tm_boff.release(); c.tm_srcb.release();   // trim scratch (the trimmed reads and their map stay)
+        c.tp_ptr.release(); c.tp_ntips.release(); c.tp_anchor.release(); c.tp_removed.release(); c.tp_keep.release(); c.tp_pos.release(); c.tp_st.release();   // tip scratch and the
+        c.tp_rows.release(); c.tp_cols.release(); c.tp_vals.release();                                                                    // spare buffer of S (S itself stays)
         if (c.have_counts) { c.pre_ready = false; c.pre_consumed = true; }    // (the CSR sort keys / column ids of the entries are gone: create_kmer_matrix rebuilds them from the column pointers)
     });
 }

@@ -20,6 +20,7 @@
 //                                                                             call on the GPU -> elba::StringGraph (S + the two read lists)
 //   GenerateContigs / parallel_write_contigs   src/ContigGeneration.cpp:376-457, src/main.cpp:487-512   same names (one rank): the contigs are
 //                                                                             built on the GPU from the S left there
+//   (none: the reference drops every branch read)                             elba::ClipTips(S, reads, max_tip_reads, rounds): dead-end tips leave S
 //
 // Errors: the reference asserts/aborts; here every failing C-ABI status throws elba::Error (status + text).
 // There is no CPU path: constructing an engine without a GPU throws ELBA_ERR_NO_DEVICE.
@@ -413,6 +414,39 @@ inline std::unique_ptr<StringGraph> TransitiveReduction(const DnaBuffer &myreads
         if (flags[(size_t)v] & 2) S->contained_reads.push_back(v);
     }
     return S;
+}
+
+// ClipTips(S, myreads, max_tip_reads, rounds) — not in the reference: elba_clip_tips on the S that TransitiveReduction left on the device, between
+// that call and GenerateContigs.  Dead-end chains of at most max_tip_reads reads that hang off a read of degree >= 3 leave S (a star of nothing
+// but such chains is spared), in up to `rounds` rounds; the host copy of S is replaced by the clipped graph, and clipped_reads, if given,
+// receives the reads removed so far (flag bit 2 of elba_export_read_flags), ascending.
+inline elba_tip_stats ClipTips(StringGraph &S, const DnaBuffer &myreads, int max_tip_reads, int rounds = 1, std::vector<int64_t> *clipped_reads = nullptr)
+{
+    if (!S.engine) throw Error(ELBA_ERR_STATE, "ClipTips: the string graph is not on a device");
+    elba_tip_cfg cfg{};
+    cfg.max_tip_reads = max_tip_reads; cfg.rounds = rounds;
+    elba_tip_stats st{};
+    S.engine->check(elba_clip_tips(S.engine->ctx, &cfg, &st));
+    elba_overlaps_t o;
+    S.engine->check(elba_export_string_graph(S.engine->ctx, &o));
+    S.rows.assign(o.rows, o.rows + o.n); S.cols.assign(o.cols, o.cols + o.n);
+    S.vals.assign((size_t)o.n, Overlap());
+    for (int64_t a = 0; a < o.n; ++a) {
+        const elba_overlap_t &v = o.vals[a];
+        Overlap &w = S.vals[(size_t)a];
+        w.beg = std::make_tuple((PosInRead)v.begQ, (PosInRead)v.begT); w.end = std::make_tuple((PosInRead)v.endQ, (PosInRead)v.endT);
+        w.len = std::make_tuple((PosInRead)myreads.lengths()[o.rows[a]], (PosInRead)myreads.lengths()[o.cols[a]]);
+        w.score = v.score; w.suffix = v.suffix; w.suffixT = v.suffixT; w.direction = v.direction; w.directionT = v.directionT;
+        w.rc = v.rc; w.passed = v.passed; w.containedQ = v.containedQ; w.containedT = v.containedT;
+    }
+    elba_free_overlaps(&o);
+    if (clipped_reads) {
+        std::vector<uint8_t> flags((size_t)S.numreads);
+        S.engine->check(elba_export_read_flags(S.engine->ctx, flags.data(), S.numreads));
+        clipped_reads->clear();
+        for (int64_t v = 0; v < S.numreads; ++v) if (flags[(size_t)v] & 4) clipped_reads->push_back(v);
+    }
+    return st;
 }
 
 // PileupVector (include/PruneChimeras.hpp:11-26): here a read's coverage is held as the (start, depth) segments elba_export_pileup returns;

@@ -286,7 +286,8 @@ void elba_free_overlaps(elba_overlaps_t *o);
  * a multi-GPU driver concatenates its ranks' shares (merged into that order) and hands them to every rank or to one.
  * elba_export_string_graph returns the entries of S, both triangles, in the order parallel_write_paf walks the reference's S
  * (src/main.cpp:527-541: columns ascending, rows ascending within a column); an entry below the diagonal carries Overlap::Transpose
- * (include/Overlap.hpp:43-69) of its mirror image.  elba_export_read_flags: flags[v] bit 0 = bad read, bit 1 = contained read. */
+ * (include/Overlap.hpp:43-69) of its mirror image.  elba_export_read_flags: flags[v] bit 0 = bad read, bit 1 = contained read,
+ * bit 2 = removed by elba_clip_tips since. */
 int  elba_set_overlaps(elba_ctx *ctx, int64_t nreads, const int64_t *rows, const int64_t *cols, const elba_overlap_t *vals, int64_t n);
 int  elba_transitive_reduction(elba_ctx *ctx, double bad_read_cutoff, int fuzz, elba_string_stats *stats);
 int  elba_export_string_graph(elba_ctx *ctx, elba_overlaps_t *out);
@@ -342,6 +343,44 @@ int  elba_export_contig_kinds(elba_ctx *ctx, uint8_t *kind, int64_t ncontigs);
 int  elba_export_contigs(elba_ctx *ctx, elba_contigs_t *out);
 void elba_free_contigs(elba_contigs_t *c);
 int  elba_export_read_contigs(elba_ctx *ctx, int64_t *contig_of_read, int64_t nreads);  /* contig index of every read, -1: in none (without the _ex flags: branch, singleton or cycle) */
+
+/* Tip clipping (not in the reference, whose GenerateContigs drops every read of degree > 2 with its edges: one stray read hanging off a good
+ * path cuts it into three contigs and loses the branch read).  elba_clip_tips works on the S of elba_transitive_reduction, in place, between
+ * that call and elba_generate_contigs*.  The rule is on degrees alone — no sequence, no suffix, no length in bases — and is stated on the
+ * columns of S: deg(v) = entries of column v, the neighbours of v = their rows (S holds both triangles; where the reduction kept only one
+ * image of a pair, the direction -1 case, the same statements hold on the columns as they are).  One ROUND, on the degrees as it finds them:
+ *   dead end   a read of degree 1.
+ *   tip        from a dead end v1 walk v1, v2, ...: v2 is v1's neighbour, and from a read vi (i > 1) of degree 2 the walk goes on to the
+ *              neighbour that is not v(i-1) (the smaller one, should neither be).  The first read b of degree >= 3 ends it: v1 .. vt, t <=
+ *              max_tip_reads, is a tip of t reads anchored at b.  A read of degree 1 (or 0) ends it too: a plain path, no tip.  A chain that
+ *              would take more than max_tip_reads reads is no tip.
+ *   sparing    T(b) = tips anchored at b.  T(b) < deg(b): every tip at b is removed.  T(b) >= deg(b) (a star of short chains): none is, and
+ *              b counts once as a spared anchor — clipping never erases a whole component.
+ *   removal    every entry of S whose row or column is a read of a removed tip goes, in both triangles; the other entries keep their values
+ *              and their order (columns ascending, rows ascending within a column).
+ * Up to `rounds` rounds run, each on the S the one before left (an anchor that fell to degree 2 joins two chains, one that fell to degree 1
+ * is a new dead end); the call stops after a round that removed nothing (rounds_run counts that round).  The result does not depend on the
+ * order in which reads are looked at.  A removed read gets bit 2 (value 4) in the flags of elba_export_read_flags until the next
+ * elba_transitive_reduction rebuilds them; since ELBA_CONTIG_SINGLETONS emits only reads whose flags are 0, a clipped read does not come
+ * back as a contig of its own.
+ * After ELBA_OK the context's S is the clipped one (elba_export_string_graph returns it, elba_generate_contigs* walks it), contigs made
+ * before are invalid as after elba_transitive_reduction, and a second call clips further from there.  An S without entries or reads: ELBA_OK,
+ * nothing removed, rounds_run 1.  ELBA_ERR_STATE without a valid S; ELBA_ERR_INVALID_ARG for a null cfg, a value out of range or a non-zero
+ * reserved word: S, the flags and the contigs stay as they were.
+ * Stats: tips counts the tips found, removed or spared; tips, reads_removed, entries_removed (both triangles) and spared_anchors are summed
+ * over the rounds; ms_compact is the compaction of the first round (keep flags, scan, scatter), the one that moves the whole of S.
+ * Cost of `rounds`: rounds are queued four at a time and the host looks at the device counters once per four; a call that is finished within
+ * four rounds (or asks for at most four) synchronises once, and whatever `rounds` is, at most three rounds that have nothing to do are queued
+ * (each returns at once but for a scan of 4 bytes per entry).  rounds = 64 is a fair way to say "to the end". */
+typedef struct { int32_t max_tip_reads;   /* 1 .. 65535 */
+                 int32_t rounds;          /* 1 .. 64: at most this many */
+                 int32_t reserved[2]; } elba_tip_cfg;
+typedef struct { int64_t nreads, nnz_before, nnz_after;
+                 int64_t dead_ends;       /* degree-1 reads when round 1 starts */
+                 int64_t tips, reads_removed, entries_removed, spared_anchors;  /* summed over the rounds */
+                 int32_t rounds_run, reserved;
+                 float   ms_total, ms_compact; } elba_tip_stats;
+int  elba_clip_tips(elba_ctx *ctx, const elba_tip_cfg *cfg, elba_tip_stats *stats);
 
 /* Read pileups and chimera flags: PileupVector / GetReadPileup / GetTrimmedInterval (src/PruneChimeras.cpp:14-69,108-158,
  * include/PruneChimeras.hpp), which src/main.cpp never calls, and R->PruneFull(x, x) of the reads it flags.  Runs after elba_align_seeds,

@@ -2,7 +2,9 @@
 The stage is timed by its own device events (ms_total, ms_rank) on calls after a warm-up call; the string graph's stage time is recorded beside
 it.  --flags F runs elba_generate_contigs_ex with F (1 circular contigs, 2 single-read contigs, 3 both) in place of the plain call;
 --rings N adds a synthetic graph of N reads in cycles of 8 (loaded as an edge list), --chain N one of N reads in a single path (no cycle).
-Usage: python profiles/contig_profile.py OUT.json [--reps N] [--flags F] [--rings N] [--chain N]"""
+--clip-tips T clips tips of at most T reads (elba_clip_tips, 4 rounds) before the contigs and records the call's own times; the string graph
+is rebuilt before every timed clip, since the call changes it.
+Usage: python profiles/contig_profile.py OUT.json [--reps N] [--flags F] [--rings N] [--chain N] [--clip-tips T]"""
 import argparse
 import json
 import os
@@ -45,7 +47,7 @@ def _synthetic(n, ring):
     return rng.integers(0, 256, 8 * n + 16).astype(np.uint8), (np.arange(n, dtype=np.uint64) * 8), lens, r[o], c[o], v
 
 
-def run(name, w, reps, flags=None):
+def run(name, w, reps, flags=None, clip=0):
     t0 = time.time()
     if "synthetic" in w:
         packed, off, lens, rows, cols, vals = _synthetic(w["synthetic"], w["ring"])
@@ -61,6 +63,17 @@ def run(name, w, reps, flags=None):
         e.count_kmers(); e.create_kmer_matrix(); e.create_seed_matrix()
         al = e.align_seeds()
         sg = e.transitive_reduction(0.65, 1000)
+    tips = None
+    if clip:
+        cutoff, fuzz = (0.0, 0) if "synthetic" in w else (0.65, 1000)
+        clips = []
+        for _ in range(reps + 1):                            # the first one is the warm-up
+            clips.append(e.clip_tips(clip, 4))
+            if len(clips) <= reps:
+                e.transitive_reduction(cutoff, fuzz)
+        mt = sorted(c["ms_total"] for c in clips[1:]); mc = sorted(c["ms_compact"] for c in clips[1:])
+        tips = {"max_tip_reads": clip, "rounds": 4, "ms_total_median": round(mt[len(mt) // 2], 4), "ms_compact_median": round(mc[len(mc) // 2], 4),
+                "counts": {k: int(clips[-1][k]) for k in ("nnz_before", "nnz_after", "dead_ends", "tips", "reads_removed", "spared_anchors", "rounds_run")}}
     _generate(e, flags)                                      # warm-up: buffers allocated
     runs = [_generate(e, flags) for _ in range(reps)]
     st = runs[-1]
@@ -69,7 +82,7 @@ def run(name, w, reps, flags=None):
     e.close()
     ms = sorted(r["ms_total"] for r in runs)
     mr = sorted(r["ms_rank"] for r in runs)
-    return {"workload": name, "flags": flags, "params": w, "reads": int(len(lens)), "aligned_pairs": int(al["nalignments"]), "string_graph": {"nnz": int(sg["nnz"]), "ms_total": round(sg["ms_total"], 4)},
+    return {"workload": name, "flags": flags, "tip_stage": tips, "params": w, "reads": int(len(lens)), "aligned_pairs": int(al["nalignments"]), "string_graph": {"nnz": int(sg["nnz"]), "ms_total": round(sg["ms_total"], 4)},
             "contig_stage": {"ms_total_median": round(ms[len(ms) // 2], 4), "ms_total_min": round(ms[0], 4), "ms_total_max": round(ms[-1], 4), "ms_rank_median": round(mr[len(mr) // 2], 4),
                              "ms_rank_min": round(mr[0], 4), "ms_rank_max": round(mr[-1], 4), "reps": reps},
             "counts": {k: int(st[k]) for k in ("nreads", "branches", "components", "used_components", "contigs", "cycles", "contig_reads", "bases", "longest")},
@@ -84,12 +97,13 @@ def main():
     ap.add_argument("--flags", type=int, choices=[0, 1, 2, 3])
     ap.add_argument("--rings", type=int, default=0)
     ap.add_argument("--chain", type=int, default=0)
+    ap.add_argument("--clip-tips", type=int, default=0)
     a = ap.parse_args()
-    res = [] if (a.rings or a.chain) and not a.workload else [run(n, WORKLOADS[n], a.reps, a.flags) for n in (a.workload or sorted(WORKLOADS))]
+    res = [] if (a.rings or a.chain) and not a.workload else [run(n, WORKLOADS[n], a.reps, a.flags, a.clip_tips) for n in (a.workload or sorted(WORKLOADS))]
     if a.rings:
-        res.append(run("rings-of-8", {"synthetic": a.rings, "ring": 8}, a.reps, a.flags))
+        res.append(run("rings-of-8", {"synthetic": a.rings, "ring": 8}, a.reps, a.flags, a.clip_tips))
     if a.chain:
-        res.append(run("one-path", {"synthetic": a.chain, "ring": 0}, a.reps, a.flags))
+        res.append(run("one-path", {"synthetic": a.chain, "ring": 0}, a.reps, a.flags, a.clip_tips))
     with open(a.out, "w") as f:
         json.dump(res, f, indent=1)
     print(json.dumps(res))
