@@ -468,15 +468,15 @@ __global__ void k_aln_combine(AlnParams p)
 
 void stage_align_seeds(Ctx &c, int mat, int mis, int gap, int dropoff)
 {
-    ELBA_REQUIRE(c.have_B, ELBA_ERR_STATE, "align_seeds: needs the seed matrix on this context");
+    enter(c.v, EV_ALIGN_SEEDS);                    // (new alignments invalidate the pileup of the old ones, whatever this call ends in)
+    ELBA_REQUIRE(has(c.v, P_B), ELBA_ERR_STATE, "align_seeds: needs the seed matrix on this context");
     const bool shard = c.row_hi >= 0 && !(c.row_lo == 0 && c.row_hi == c.M);        // rows of a row-sharded B (multi-GPU)
     if (shard) ELBA_REQUIRE(c.aln_all_n == c.M, ELBA_ERR_STATE, "align_seeds: a row shard of B needs every read resident (elba_dist_set_all_reads)");
-    else ELBA_REQUIRE(c.have_reads && c.nreads == c.M, ELBA_ERR_UNSUPPORTED, "align_seeds: every read of B must be resident on this context");
+    else ELBA_REQUIRE(has(c.v, P_READS) && c.nreads == c.M, ELBA_ERR_UNSUPPORTED, "align_seeds: every read of B must be resident on this context");
     ELBA_REQUIRE(dropoff >= 0, ELBA_ERR_INVALID_ARG, "align_seeds: negative x-drop");
     hipStream_t s = c.stream;
     const int64_t M = c.M;
-    c.have_aln = false;
-    c.have_edges = false; c.have_S = false;        // fresh alignments replace a loaded edge list as the string graph's input (tr.hip)
+    accepted(c.v, EV_ALIGN_SEEDS);
     AlnParams p{};
     if (shard) { p.packed = c.aln_all_packed.as<uint8_t>(); p.byte_off = c.aln_all_off.as<uint64_t>(); p.len = c.aln_all_len.as<uint32_t>(); }
     else { p.packed = c.d_packed; p.byte_off = c.d_byte_off; p.len = c.d_len; }
@@ -573,7 +573,7 @@ void stage_align_seeds(Ctx &c, int mat, int mis, int gap, int dropoff)
         for (const auto &o : h) { st.seeds_rejected += o.score == -1 && o.endQ == 0 && o.endT == 0; st.passed += o.passed; st.contained += (o.containedQ | o.containedT); }
     }
     c.astats = st;
-    c.have_aln = true;
+    done(c.v, EV_ALIGN_SEEDS);
 }
 
 // Multi-GPU alignment: the reads are small next to HBM (2 bits per base), so every rank keeps ALL of them (one all-gather by the
@@ -581,6 +581,7 @@ void stage_align_seeds(Ctx &c, int mat, int mis, int gap, int dropoff)
 // row and column read blocks of a 2D grid instead (src/DistributedFastaData.cpp).
 void stage_dist_set_all_reads(Ctx &c, const void *d_packed, int64_t packed_bytes, const void *d_byte_off, const void *d_len, int64_t nreads_total)
 {
+    enter(c.v, EV_DIST_SET_ALL_READS);
     ELBA_REQUIRE(nreads_total >= 0 && packed_bytes >= 0 && (nreads_total == 0 || (d_packed && d_byte_off && d_len)), ELBA_ERR_INVALID_ARG, "dist_set_all_reads: null array");
     hipStream_t s = c.stream;
     c.aln_all_packed.reserve((size_t)packed_bytes + 16); c.aln_all_off.reserve((size_t)(nreads_total + 1) * 8); c.aln_all_len.reserve((size_t)(nreads_total + 1) * 4);
@@ -600,7 +601,7 @@ void stage_dist_set_all_reads(Ctx &c, const void *d_packed, int64_t packed_bytes
     for (int64_t r = 0; r < nreads_total; ++r)          // the x-drop kernels trust these offsets (as elba_set_reads_device checks its own)
         ELBA_REQUIRE((int64_t)ho[(size_t)r] + ((int64_t)hl[(size_t)r] + 3) / 4 <= packed_bytes, ELBA_ERR_INVALID_ARG, "dist_set_all_reads: read exceeds the packed buffer");
     c.aln_all_maxlen = mx; c.aln_all_n = nreads_total;
-    c.have_aln = false;
+    done(c.v, EV_DIST_SET_ALL_READS);
 }
 
 }  // namespace elba

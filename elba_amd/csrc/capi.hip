@@ -120,8 +120,10 @@ static void check_reads_host(const uint64_t *byte_off, const uint32_t *len, int6
 int elba_set_reads(elba_ctx *ctx, const uint8_t *packed, const uint64_t *byte_off, const uint32_t *len, int64_t nreads, int64_t first_global_id)
 {
     return guarded(ctx, [&](Ctx &c) {
+        enter(c.v, EV_SET_READS);
         ELBA_REQUIRE(nreads >= 0 && (nreads == 0 || (packed && byte_off && len)), ELBA_ERR_INVALID_ARG, "set_reads: null array");
         ELBA_REQUIRE(nreads < 0xFFFFFFFFll, ELBA_ERR_UNSUPPORTED, "set_reads: more than 2^32-1 reads on one GPU");
+        accepted(c.v, EV_SET_READS);
         int64_t pb = 0;
         check_reads_host(byte_off, len, nreads, &pb);
         c.own_packed.reserve((size_t)pb + 16);       // +16: the enumerate kernel reads whole 8-byte windows
@@ -138,23 +140,20 @@ int elba_set_reads(elba_ctx *ctx, const uint8_t *packed, const uint64_t *byte_of
         c.h_len.assign(len, len + nreads);
         c.h_byte_off.assign(byte_off, byte_off + nreads);
         c.nreads = nreads; c.first_global_id = first_global_id; c.packed_bytes = pb;
-        reads_replaced(c);
+        reads_replaced(c, EV_SET_READS);
     });
 }
 
 int elba_set_reads_fasta(elba_ctx *ctx, const char *chunk, int64_t chunk_bytes, uint64_t chunk_file_offset, const elba_fasta_record_t *recs, int64_t nreads,
                          int64_t first_global_id, elba_ingest_stats *stats)
 {
-    return guarded(ctx, [&](Ctx &c) {
-        c.have_pileup = false; c.have_trim = false;
-        stage_set_reads_fasta(c, chunk, chunk_bytes, chunk_file_offset, recs, nreads, first_global_id, stats);
-    });
+    return guarded(ctx, [&](Ctx &c) { stage_set_reads_fasta(c, chunk, chunk_bytes, chunk_file_offset, recs, nreads, first_global_id, stats); });
 }
 
 int elba_export_reads(elba_ctx *ctx, uint8_t *packed, int64_t packed_capacity, uint64_t *byte_off, uint32_t *len, int64_t nreads_capacity)
 {
     return guarded(ctx, [&](Ctx &c) {
-        ELBA_REQUIRE(c.have_reads, ELBA_ERR_STATE, "export_reads: no reads");
+        ELBA_REQUIRE(has(c.v, P_READS), ELBA_ERR_STATE, "export_reads: no reads");
         if (packed) {
             ELBA_REQUIRE(packed_capacity >= c.packed_bytes, ELBA_ERR_INVALID_ARG, "export_reads: packed buffer too small");
             if (c.packed_bytes) ELBA_HIP(hipMemcpyAsync(packed, c.d_packed, (size_t)c.packed_bytes, hipMemcpyDeviceToHost, c.stream));
@@ -169,8 +168,10 @@ int elba_export_reads(elba_ctx *ctx, uint8_t *packed, int64_t packed_capacity, u
 int elba_set_reads_device(elba_ctx *ctx, const void *d_packed, int64_t packed_bytes, const void *d_byte_off, const void *d_len, int64_t nreads, int64_t first_global_id)
 {
     return guarded(ctx, [&](Ctx &c) {
+        enter(c.v, EV_SET_READS_DEVICE);
         ELBA_REQUIRE(nreads >= 0 && packed_bytes >= 0 && (nreads == 0 || (d_packed && d_byte_off && d_len)), ELBA_ERR_INVALID_ARG, "set_reads_device: null array");
         ELBA_REQUIRE(nreads < 0xFFFFFFFFll, ELBA_ERR_UNSUPPORTED, "set_reads_device: more than 2^32-1 reads on one GPU");
+        accepted(c.v, EV_SET_READS_DEVICE);
         // the packed buffer is copied once device-to-device so that the 16 guard bytes behind it exist; offsets/lengths are borrowed
         c.own_packed.reserve((size_t)packed_bytes + 16);
         ELBA_HIP(hipMemsetAsync(c.own_packed.p, 0, (size_t)packed_bytes + 16, c.stream));
@@ -183,7 +184,7 @@ int elba_set_reads_device(elba_ctx *ctx, const void *d_packed, int64_t packed_by
         for (int64_t r = 0; r < nreads; ++r)
             ELBA_REQUIRE((int64_t)c.h_byte_off[r] + ((int64_t)c.h_len[r] + 3) / 4 <= packed_bytes, ELBA_ERR_INVALID_ARG, "set_reads_device: read exceeds the packed buffer");
         c.nreads = nreads; c.first_global_id = first_global_id; c.packed_bytes = packed_bytes;
-        reads_replaced(c);
+        reads_replaced(c, EV_SET_READS_DEVICE);
     });
 }
 
@@ -290,7 +291,6 @@ int elba_seed_matrix_end(elba_ctx *ctx, const void *d_recv, int64_t nrecords, el
 int elba_align_seeds(elba_ctx *ctx, int mat, int mis, int gap, int dropoff, elba_align_stats *stats)
 {
     return guarded(ctx, [&](Ctx &c) {
-        c.have_pileup = false;                                      // new alignments invalidate the pileup of the old ones, whatever this call ends in
         stage_align_seeds(c, mat, mis, gap, dropoff);
         if (stats) *stats = c.astats;
     });
@@ -298,10 +298,7 @@ int elba_align_seeds(elba_ctx *ctx, int mat, int mis, int gap, int dropoff, elba
 
 int elba_dist_set_all_reads(elba_ctx *ctx, const void *d_packed, int64_t packed_bytes, const void *d_byte_off, const void *d_len, int64_t nreads_total)
 {
-    return guarded(ctx, [&](Ctx &c) {
-        c.have_pileup = false; c.have_trim = false;
-        stage_dist_set_all_reads(c, d_packed, packed_bytes, d_byte_off, d_len, nreads_total);
-    });
+    return guarded(ctx, [&](Ctx &c) { stage_dist_set_all_reads(c, d_packed, packed_bytes, d_byte_off, d_len, nreads_total); });
 }
 
 int elba_export_overlaps(elba_ctx *ctx, elba_overlaps_t *out)
@@ -309,7 +306,7 @@ int elba_export_overlaps(elba_ctx *ctx, elba_overlaps_t *out)
     return guarded(ctx, [&](Ctx &c) {
         ELBA_REQUIRE(out, ELBA_ERR_INVALID_ARG, "export_overlaps: null output");
         memset(out, 0, sizeof(*out));
-        ELBA_REQUIRE(c.have_aln, ELBA_ERR_STATE, "export_overlaps: no alignments (call elba_align_seeds)");
+        ELBA_REQUIRE(has(c.v, P_ALN), ELBA_ERR_STATE, "export_overlaps: no alignments (call elba_align_seeds)");
         const int64_t n = c.naln;
         out->n = n;
         out->rows = host_alloc<int64_t>((size_t)n); out->cols = host_alloc<int64_t>((size_t)n); out->vals = host_alloc<elba_overlap_t>((size_t)n);
@@ -332,16 +329,12 @@ void elba_free_overlaps(elba_overlaps_t *o)
 
 int elba_set_overlaps(elba_ctx *ctx, int64_t nreads, const int64_t *rows, const int64_t *cols, const elba_overlap_t *vals, int64_t n)
 {
-    return guarded(ctx, [&](Ctx &c) {
-        c.have_pileup = false;
-        stage_set_overlaps(c, nreads, rows, cols, vals, n);
-    });
+    return guarded(ctx, [&](Ctx &c) { stage_set_overlaps(c, nreads, rows, cols, vals, n); });
 }
 
 int elba_transitive_reduction(elba_ctx *ctx, double bad_read_cutoff, int fuzz, elba_string_stats *stats)
 {
     return guarded(ctx, [&](Ctx &c) {
-        c.have_contigs = false;                                     // a new S invalidates the contigs of the old one, whatever this call ends in
         stage_transitive_reduction(c, bad_read_cutoff, fuzz);
         if (stats) *stats = c.sstats;
     });
@@ -352,7 +345,7 @@ int elba_export_string_graph(elba_ctx *ctx, elba_overlaps_t *out)
     return guarded(ctx, [&](Ctx &c) {
         ELBA_REQUIRE(out, ELBA_ERR_INVALID_ARG, "export_string_graph: null output");
         memset(out, 0, sizeof(*out));
-        ELBA_REQUIRE(c.have_S, ELBA_ERR_STATE, "export_string_graph: no string graph (call elba_transitive_reduction)");
+        ELBA_REQUIRE(has(c.v, P_S), ELBA_ERR_STATE, "export_string_graph: no string graph (call elba_transitive_reduction)");
         const int64_t n = c.tr_nnz;
         out->n = n;
         out->rows = host_alloc<int64_t>((size_t)n); out->cols = host_alloc<int64_t>((size_t)n); out->vals = host_alloc<elba_overlap_t>((size_t)n);
@@ -369,7 +362,7 @@ int elba_export_string_graph(elba_ctx *ctx, elba_overlaps_t *out)
 int elba_export_read_flags(elba_ctx *ctx, uint8_t *flags, int64_t nreads)
 {
     return guarded(ctx, [&](Ctx &c) {
-        ELBA_REQUIRE(c.have_S, ELBA_ERR_STATE, "export_read_flags: no string graph (call elba_transitive_reduction)");
+        ELBA_REQUIRE(has(c.v, P_S), ELBA_ERR_STATE, "export_read_flags: no string graph (call elba_transitive_reduction)");
         ELBA_REQUIRE(nreads == c.tr_M && (flags || nreads == 0), ELBA_ERR_INVALID_ARG, "export_read_flags: need one byte per read of the graph");
         if (nreads) ELBA_HIP(hipMemcpyAsync(flags, c.tr_flags.p, (size_t)nreads, hipMemcpyDeviceToHost, c.stream));
         ELBA_HIP(hipStreamSynchronize(c.stream));
@@ -379,9 +372,7 @@ int elba_export_read_flags(elba_ctx *ctx, uint8_t *flags, int64_t nreads)
 int elba_clip_tips(elba_ctx *ctx, const elba_tip_cfg *cfg, elba_tip_stats *stats)
 {
     return guarded(ctx, [&](Ctx &c) {
-        ELBA_REQUIRE(c.have_S, ELBA_ERR_STATE, "clip_tips: no string graph (call elba_transitive_reduction)");
-        ELBA_REQUIRE(cfg, ELBA_ERR_INVALID_ARG, "clip_tips: null cfg");
-        stage_clip_tips(c, *cfg);                                   // (a rejected cfg leaves S and the contigs as they are)
+        stage_clip_tips(c, cfg);
         if (stats) *stats = c.tpstats;
     });
 }
@@ -397,11 +388,7 @@ int elba_generate_contigs(elba_ctx *ctx, elba_contig_stats *stats)
 int elba_generate_contigs_ex(elba_ctx *ctx, const elba_contig_cfg *cfg, elba_contig_stats *stats)
 {
     return guarded(ctx, [&](Ctx &c) {
-        c.have_contigs = false;                                     // a rejected call leaves no contigs either
-        ELBA_REQUIRE(cfg, ELBA_ERR_INVALID_ARG, "generate_contigs_ex: null cfg");
-        ELBA_REQUIRE(!cfg->reserved[0] && !cfg->reserved[1] && !cfg->reserved[2], ELBA_ERR_INVALID_ARG, "generate_contigs_ex: reserved words must be 0");
-        ELBA_REQUIRE((cfg->flags & ~(ELBA_CONTIG_CIRCULAR | ELBA_CONTIG_SINGLETONS)) == 0, ELBA_ERR_INVALID_ARG, "generate_contigs_ex: unknown flag bits");
-        stage_generate_contigs(c, cfg->flags);
+        stage_generate_contigs_ex(c, cfg);
         if (stats) *stats = c.cstats;
     });
 }
@@ -411,7 +398,7 @@ int elba_export_contigs(elba_ctx *ctx, elba_contigs_t *out)
     return guarded(ctx, [&](Ctx &c) {
         ELBA_REQUIRE(out, ELBA_ERR_INVALID_ARG, "export_contigs: null output");
         memset(out, 0, sizeof(*out));
-        ELBA_REQUIRE(c.have_S && c.have_contigs, ELBA_ERR_STATE, "export_contigs: no contigs of the current string graph (call elba_generate_contigs)");
+        ELBA_REQUIRE(has(c.v, P_S, P_CONTIGS), ELBA_ERR_STATE, "export_contigs: no contigs of the current string graph (call elba_generate_contigs)");
         const int64_t n = c.cg_n, E = c.cg_E, b = c.cg_bases;
         elba_contigs_t o{};
         o.n = n;
@@ -441,7 +428,7 @@ void elba_free_contigs(elba_contigs_t *c)
 int elba_export_read_contigs(elba_ctx *ctx, int64_t *contig_of_read, int64_t nreads)
 {
     return guarded(ctx, [&](Ctx &c) {
-        ELBA_REQUIRE(c.have_S && c.have_contigs, ELBA_ERR_STATE, "export_read_contigs: no contigs of the current string graph (call elba_generate_contigs)");
+        ELBA_REQUIRE(has(c.v, P_S, P_CONTIGS), ELBA_ERR_STATE, "export_read_contigs: no contigs of the current string graph (call elba_generate_contigs)");
         ELBA_REQUIRE(nreads == c.tr_M && (contig_of_read || nreads == 0), ELBA_ERR_INVALID_ARG, "export_read_contigs: need one entry per read of the graph");
         const std::vector<int32_t> h = download<int32_t>(c, c.cg_cid.p, (size_t)nreads);
         for (int64_t v = 0; v < nreads; ++v) contig_of_read[v] = h[(size_t)v];
@@ -451,7 +438,7 @@ int elba_export_read_contigs(elba_ctx *ctx, int64_t *contig_of_read, int64_t nre
 int elba_export_contig_kinds(elba_ctx *ctx, uint8_t *kind, int64_t ncontigs)
 {
     return guarded(ctx, [&](Ctx &c) {
-        ELBA_REQUIRE(c.have_S && c.have_contigs, ELBA_ERR_STATE, "export_contig_kinds: no contigs of the current string graph (call elba_generate_contigs)");
+        ELBA_REQUIRE(has(c.v, P_S, P_CONTIGS), ELBA_ERR_STATE, "export_contig_kinds: no contigs of the current string graph (call elba_generate_contigs)");
         ELBA_REQUIRE(ncontigs == c.cg_n && (kind || ncontigs == 0), ELBA_ERR_INVALID_ARG, "export_contig_kinds: need one byte per contig");
         if (ncontigs) ELBA_HIP(hipMemcpyAsync(kind, c.cg_kind.p, (size_t)ncontigs, hipMemcpyDeviceToHost, c.stream));
         ELBA_HIP(hipStreamSynchronize(c.stream));
@@ -461,9 +448,7 @@ int elba_export_contig_kinds(elba_ctx *ctx, uint8_t *kind, int64_t ncontigs)
 int elba_read_pileup(elba_ctx *ctx, const elba_pileup_cfg *cfg, elba_pileup_stats *stats)
 {
     return guarded(ctx, [&](Ctx &c) {
-        c.have_pileup = false; c.have_trim = false;                 // (the trimmed reads are cut from the pileup they were asked of)
-        ELBA_REQUIRE(cfg, ELBA_ERR_INVALID_ARG, "read_pileup: null cfg");
-        stage_read_pileup(c, *cfg);
+        stage_read_pileup(c, cfg);
         if (stats) *stats = c.pustats;
     });
 }
@@ -473,7 +458,7 @@ int elba_export_pileup(elba_ctx *ctx, elba_pileup_t *out)
     return guarded(ctx, [&](Ctx &c) {
         ELBA_REQUIRE(out, ELBA_ERR_INVALID_ARG, "export_pileup: null output");
         memset(out, 0, sizeof(*out));
-        ELBA_REQUIRE(c.have_pileup, ELBA_ERR_STATE, "export_pileup: no pileup of the current overlaps (call elba_read_pileup)");
+        ELBA_REQUIRE(has(c.v, P_PILEUP), ELBA_ERR_STATE, "export_pileup: no pileup of the current overlaps (call elba_read_pileup)");
         const int64_t n = c.pu_M, S = c.pu_nseg;
         elba_pileup_t o{};
         o.n = n; o.nseg = S;
@@ -511,9 +496,7 @@ int elba_prune_reads(elba_ctx *ctx, int mask, int64_t *kept)
 int elba_trim_reads(elba_ctx *ctx, const elba_trim_cfg *cfg, elba_trim_stats *stats)
 {
     return guarded(ctx, [&](Ctx &c) {
-        c.have_trim = false;
-        ELBA_REQUIRE(cfg, ELBA_ERR_INVALID_ARG, "trim_reads: null cfg");
-        stage_trim_reads(c, *cfg);
+        stage_trim_reads(c, cfg);
         if (stats) *stats = c.tmstats;
     });
 }
@@ -523,7 +506,7 @@ int elba_export_trim_map(elba_ctx *ctx, elba_trim_map_t *out)
     return guarded(ctx, [&](Ctx &c) {
         ELBA_REQUIRE(out, ELBA_ERR_INVALID_ARG, "export_trim_map: null output");
         memset(out, 0, sizeof(*out));
-        ELBA_REQUIRE(c.have_trim, ELBA_ERR_STATE, "export_trim_map: no trimmed reads (call elba_trim_reads)");
+        ELBA_REQUIRE(has(c.v, P_TRIM), ELBA_ERR_STATE, "export_trim_map: no trimmed reads (call elba_trim_reads)");
         const int64_t n = c.tm_n;
         elba_trim_map_t o{};
         o.n = n;
@@ -550,7 +533,7 @@ int elba_get_trimmed_reads_device(elba_ctx *ctx, const void **d_packed, int64_t 
 {
     return guarded(ctx, [&](Ctx &c) {
         ELBA_REQUIRE(d_packed && packed_bytes && d_byte_off && d_len && n, ELBA_ERR_INVALID_ARG, "get_trimmed_reads_device: null output");
-        ELBA_REQUIRE(c.have_trim, ELBA_ERR_STATE, "get_trimmed_reads_device: no trimmed reads (call elba_trim_reads)");
+        ELBA_REQUIRE(has(c.v, P_TRIM), ELBA_ERR_STATE, "get_trimmed_reads_device: no trimmed reads (call elba_trim_reads)");
         *d_packed = c.tm_packed.p; *packed_bytes = c.tm_packed_bytes; *d_byte_off = c.tm_off.p; *d_len = c.tm_len.p; *n = c.tm_n;
     });
 }
@@ -565,7 +548,7 @@ int elba_export_csr(elba_ctx *ctx, int64_t row_lo, int64_t row_hi, elba_csr_t *o
     return guarded(ctx, [&](Ctx &c) {
         ELBA_REQUIRE(out, ELBA_ERR_INVALID_ARG, "export_csr: null output");
         memset(out, 0, sizeof(*out));
-        ELBA_REQUIRE(c.have_B, ELBA_ERR_STATE, "export_csr: no seed matrix");
+        ELBA_REQUIRE(has(c.v, P_B), ELBA_ERR_STATE, "export_csr: no seed matrix");
         ELBA_REQUIRE(row_lo >= 0 && row_lo <= row_hi && row_hi <= c.M, ELBA_ERR_INVALID_ARG, "export_csr: bad row range");
         auto rp = download<int64_t>(c, c.b_rowptr.as<int64_t>() + row_lo, (size_t)(row_hi - row_lo + 1));
         const int64_t e0 = rp.front(), e1 = rp.back(), n = e1 - e0;
@@ -593,7 +576,7 @@ int elba_export_dcsc(elba_ctx *ctx, int64_t row_lo, int64_t row_hi, int64_t col_
     return guarded(ctx, [&](Ctx &c) {
         ELBA_REQUIRE(out, ELBA_ERR_INVALID_ARG, "export_dcsc: null output");
         memset(out, 0, sizeof(*out));
-        ELBA_REQUIRE(c.have_B, ELBA_ERR_STATE, "export_dcsc: no seed matrix");
+        ELBA_REQUIRE(has(c.v, P_B), ELBA_ERR_STATE, "export_dcsc: no seed matrix");
         ELBA_REQUIRE(row_lo >= 0 && row_lo <= row_hi && row_hi <= c.M && col_lo >= 0 && col_lo <= col_hi && col_hi <= c.M, ELBA_ERR_INVALID_ARG, "export_dcsc: bad block");
         // rows [row_lo,row_hi) of the device CSR -> host; column-major regrouping is index bookkeeping on the exported copy
         auto rp = download<int64_t>(c, c.b_rowptr.as<int64_t>() + row_lo, (size_t)(row_hi - row_lo + 1));
@@ -639,7 +622,7 @@ int elba_export_kmer_matrix(elba_ctx *ctx, elba_kmer_matrix_t *out)
     return guarded(ctx, [&](Ctx &c) {
         ELBA_REQUIRE(out, ELBA_ERR_INVALID_ARG, "export_kmer_matrix: null output");
         memset(out, 0, sizeof(*out));
-        ELBA_REQUIRE(c.have_A, ELBA_ERR_STATE, "export_kmer_matrix: no k-mer matrix");
+        ELBA_REQUIRE(has(c.v, P_A), ELBA_ERR_STATE, "export_kmer_matrix: no k-mer matrix");
         const size_t M = (size_t)c.M, N = (size_t)c.N, Z = (size_t)c.Z;
         auto rp = download<uint32_t>(c, c.a_rowptr.p, M + 1);
         auto cp = download<uint32_t>(c, c.a_colptr.p, N + 1);
@@ -689,7 +672,7 @@ int elba_kmer_histogram(elba_ctx *ctx, int64_t *hist, int64_t len)
 {
     return guarded(ctx, [&](Ctx &c) {
         ELBA_REQUIRE(hist && len > 0, ELBA_ERR_INVALID_ARG, "kmer_histogram: null output");
-        ELBA_REQUIRE(c.have_A, ELBA_ERR_STATE, "kmer_histogram: no k-mer matrix");
+        ELBA_REQUIRE(has(c.v, P_A), ELBA_ERR_STATE, "kmer_histogram: no k-mer matrix");
         auto cp = download<uint32_t>(c, c.a_colptr.p, (size_t)c.N + 1);
         for (int64_t i = 0; i < len; ++i) hist[i] = 0;
         for (int64_t k = 0; k < c.N; ++k) { int64_t n = (int64_t)cp[(size_t)k + 1] - cp[(size_t)k]; if (n < len) hist[n]++; }
@@ -702,13 +685,13 @@ int elba_get_device_view(elba_ctx *ctx, elba_device_view *v)
         ELBA_REQUIRE(v, ELBA_ERR_INVALID_ARG, "get_device_view: null output");
         memset(v, 0, sizeof(*v));
         v->stream = (void *)c.stream;
-        if (c.have_A) { v->M = c.M; v->N = c.N; v->Z = c.Z; v->a_rowptr = c.a_rowptr.p; v->a_csr = c.a_csr.p; v->a_colptr = c.a_colptr.p; v->a_csc = c.a_csc.p;
+        if (has(c.v, P_A)) { v->M = c.M; v->N = c.N; v->Z = c.Z; v->a_rowptr = c.a_rowptr.p; v->a_csr = c.a_csr.p; v->a_colptr = c.a_colptr.p; v->a_csc = c.a_csc.p;
                         v->a_csr_format = c.csr_inline ? ELBA_CSR_INLINE : (c.csr_suffix ? ELBA_CSR_DENSE : (c.csr_hints ? ELBA_CSR_HINTS : ELBA_CSR_PLAIN));
                         v->a_csr_pos_mask = c.csr_suffix ? 0xFFFFu : (c.csr_hints ? 0x3FFFFFFFu : 0xFFFFFFFFu);
                         v->a_kmers = c.A_has_kmers ? c.rel_kmers.p : nullptr;
                         v->a_gather_slots = c.use_ell && c.ell_compact ? c.ell_nslots : 0;
                         v->a_slot_kid = c.use_ell && c.ell_compact ? c.ell_slot_kid.p : nullptr; }
-        if (c.have_B) { v->Y = c.Y; v->b_rowptr = c.b_rowptr.p; v->b_col = c.b_col.p; v->b_val = c.b_val.p; }
+        if (has(c.v, P_B)) { v->Y = c.Y; v->b_rowptr = c.b_rowptr.p; v->b_col = c.b_col.p; v->b_val = c.b_val.p; }
     });
 }
 
@@ -754,7 +737,7 @@ int elba_release_workspace(elba_ctx *ctx)
         c.tm_cnt.release(); c.tm_bytes.release(); c.tm_first.release(); c.tm_boff.release(); c.tm_srcb.release();   // trim scratch (the trimmed reads and their map stay)
         c.tp_ptr.release(); c.tp_ntips.release(); c.tp_anchor.release(); c.tp_removed.release(); c.tp_keep.release(); c.tp_pos.release(); c.tp_st.release();   // tip scratch and the
         c.tp_rows.release(); c.tp_cols.release(); c.tp_vals.release();                                                                    // spare buffer of S (S itself stays)
-        if (c.have_counts) { c.pre_ready = false; c.pre_consumed = true; }    // (the CSR sort keys / column ids of the entries are gone: create_kmer_matrix rebuilds them from the column pointers)
+        if (has(c.v, P_COUNTS)) { c.pre_ready = false; c.pre_consumed = true; }    // (the CSR sort keys / column ids of the entries are gone: create_kmer_matrix rebuilds them from the column pointers)
     });
 }
 
@@ -777,19 +760,19 @@ int elba_get_stat(elba_ctx *ctx, const char *name, int64_t *value)
         else if (!strcmp(name, "spgemm_prep_us")) *value = c.prep_us;      // (option "measure_prep"; -1: not measured — the option was off, or the path taken has no emit kernels of its own)
         else if (!strcmp(name, "emit_us")) *value = c.emit_us;
         else if (!strcmp(name, "triples_path")) *value = c.triples_path;
-        else if (!strcmp(name, "padded_columns")) *value = c.have_A && c.use_ell ? 1 : 0;
-        else if (!strcmp(name, "gather_slots")) *value = c.have_A && c.use_ell ? c.ell_nslots : 0;
-        else if (!strcmp(name, "contig_count")) *value = c.have_contigs ? c.cstats.contigs : 0;          // the last elba_generate_contigs (0: none valid)
-        else if (!strcmp(name, "contig_cycles")) *value = c.have_contigs ? c.cstats.cycles : 0;
-        else if (!strcmp(name, "contig_circular")) *value = c.have_contigs ? c.cg_circular : 0;
-        else if (!strcmp(name, "contig_singletons")) *value = c.have_contigs ? c.cg_singletons : 0;
-        else if (!strcmp(name, "contig_reads")) *value = c.have_contigs ? c.cstats.contig_reads : 0;
-        else if (!strcmp(name, "contig_bases")) *value = c.have_contigs ? c.cstats.bases : 0;
-        else if (!strcmp(name, "contig_branches")) *value = c.have_contigs ? c.cstats.branches : 0;
-        else if (!strcmp(name, "contig_rank_us")) *value = c.have_contigs ? (int64_t)(c.cstats.ms_rank * 1000.0f) : -1;
+        else if (!strcmp(name, "padded_columns")) *value = has(c.v, P_A) && c.use_ell ? 1 : 0;
+        else if (!strcmp(name, "gather_slots")) *value = has(c.v, P_A) && c.use_ell ? c.ell_nslots : 0;
+        else if (!strcmp(name, "contig_count")) *value = has(c.v, P_S, P_CONTIGS) ? c.cstats.contigs : 0;          // the last elba_generate_contigs (0: none valid — the condition of the contig exports)
+        else if (!strcmp(name, "contig_cycles")) *value = has(c.v, P_S, P_CONTIGS) ? c.cstats.cycles : 0;
+        else if (!strcmp(name, "contig_circular")) *value = has(c.v, P_S, P_CONTIGS) ? c.cg_circular : 0;
+        else if (!strcmp(name, "contig_singletons")) *value = has(c.v, P_S, P_CONTIGS) ? c.cg_singletons : 0;
+        else if (!strcmp(name, "contig_reads")) *value = has(c.v, P_S, P_CONTIGS) ? c.cstats.contig_reads : 0;
+        else if (!strcmp(name, "contig_bases")) *value = has(c.v, P_S, P_CONTIGS) ? c.cstats.bases : 0;
+        else if (!strcmp(name, "contig_branches")) *value = has(c.v, P_S, P_CONTIGS) ? c.cstats.branches : 0;
+        else if (!strcmp(name, "contig_rank_us")) *value = has(c.v, P_S, P_CONTIGS) ? (int64_t)(c.cstats.ms_rank * 1000.0f) : -1;
         else if (!strcmp(name, "resident_bytes_A")) {
             int64_t b = 0;
-            if (c.have_A) {
+            if (has(c.v, P_A)) {
                 b = (int64_t)(c.M + 1) * 4 + (int64_t)(c.N + 1) * 4 + 16 * c.Z;
                 if (c.use_ell) b += 8 * c.ell_nslots * (int64_t)c.s_stride + (c.ell_compact ? 4 * c.ell_nslots : 0);
                 if (c.csr_suffix) b += (4ll * c.N) << c.j_shift;
@@ -872,7 +855,7 @@ int elba_dist_get_reliable_kmers(elba_ctx *ctx, const void **d_kmers, int64_t *n
 {
     return guarded(ctx, [&](Ctx &c) {
         ELBA_REQUIRE(d_kmers && n, ELBA_ERR_INVALID_ARG, "dist_get_reliable_kmers: null output");
-        ELBA_REQUIRE(c.have_counts && c.dist_owner, ELBA_ERR_STATE, "dist_get_reliable_kmers: call dist_count_records first");
+        ELBA_REQUIRE(has(c.v, P_COUNTS) && c.dist_owner, ELBA_ERR_STATE, "dist_get_reliable_kmers: call dist_count_records first");
         ELBA_REQUIRE(c.cfg.k <= 31, ELBA_ERR_UNSUPPORTED, "dist_get_reliable_kmers: multi-word k-mers are handed out interleaved by elba_dist_copy_reliable_kmers");
         *d_kmers = c.rel_kmers.p; *n = c.own_N;
     });
@@ -881,7 +864,7 @@ int elba_dist_get_reliable_kmers(elba_ctx *ctx, const void **d_kmers, int64_t *n
 int elba_dist_copy_reliable_kmers(elba_ctx *ctx, void *d_dst, int64_t capacity)
 {
     return guarded(ctx, [&](Ctx &c) {
-        ELBA_REQUIRE(c.have_counts && c.dist_owner, ELBA_ERR_STATE, "dist_copy_reliable_kmers: call dist_count_records first");
+        ELBA_REQUIRE(has(c.v, P_COUNTS) && c.dist_owner, ELBA_ERR_STATE, "dist_copy_reliable_kmers: call dist_count_records first");
         ELBA_REQUIRE(capacity >= c.own_N && (d_dst || c.own_N == 0), ELBA_ERR_INVALID_ARG, "dist_copy_reliable_kmers: buffer too small");
         stage_dist_copy_reliable_kmers(c, d_dst);
     });

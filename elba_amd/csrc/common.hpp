@@ -9,6 +9,7 @@
 #include <string>
 #include <vector>
 #include "../../include/elba_amd.h"
+#include "state.hpp"
 
 namespace elba {
 
@@ -195,6 +196,7 @@ struct Ctx {
     hipStream_t stream = nullptr;
     std::string last_error;
     int num_cus = 256;
+    Validity v;                            // which of the products below are valid: state.hpp decides, the stages name their event
 
     // reads (DnaBuffer layout)
     int64_t nreads = 0, first_global_id = 0, packed_bytes = 0;
@@ -202,13 +204,11 @@ struct Ctx {
     const uint64_t *d_byte_off = nullptr;
     const uint32_t *d_len = nullptr;
     DevBuf own_packed, own_byte_off, own_len;
-    bool have_reads = false;
     uint32_t max_read_len = 0;             // longest read (set by stage_count_kmers)
     std::vector<uint32_t> h_len;           // host copy of lengths (instance offsets are a host-side prefix sum)
     std::vector<uint64_t> h_byte_off;
 
     // k-mer stage results (device)
-    bool have_counts = false;
     int triples_path = 0; // diagnostic: how the last elba_set_kmer_matrix_device built the matrix — 0 radix sorts of the whole matrix (matrix.hip), 1 the k-mer stage's bucket kernels (kmer_msd.hip)
     int kmer_passes = 1;  // diagnostic: value-range passes of the last elba_count_kmers (kmer_msd.hip)
     int64_t kmer_crowded = 0, kmer_crowded_small = 0, kmer_largest_pass = 0;      // diagnostic: the last elba_count_kmers' crowded buckets, wide ones of them with a folded entry count in (0, small_cap], instances of its largest pass (kmer_msd.hip)
@@ -244,7 +244,6 @@ struct Ctx {
     elba_kmer_stats kstats{};
 
     // A (device)
-    bool have_A = false;
     bool A_has_kmers = false;
     int64_t M = 0, N = 0, Z = 0, max_row_nnz = 0, max_col_nnz = 0;
     DevBuf a_rowptr, a_csr, a_colptr, a_csc;   // u32[M+1], u64[Z], u32[N+1], u64[Z]
@@ -280,13 +279,11 @@ struct Ctx {
     int64_t own_N = 0, own_Z = 0; // a rank serves one panel per row block of every rank (elba_dist_panel_*_win)
 
     // B (device)
-    bool have_B = false;
     int64_t Y = 0;
     DevBuf b_rowptr, b_col, b_val;             // i64[M+1], u32[Y], elba_seed_t[Y]
     elba_overlap_stats ostats{};
 
     // alignments (align.hip)
-    bool have_aln = false;
     int64_t naln = 0;
     DevBuf aln_tasks, aln_ext, aln_cnt, aln_ptr, aln_ctr, aln_ofl, aln_scratch, aln_rows, aln_cols, aln_out;
     elba_align_stats astats{};
@@ -294,16 +291,13 @@ struct Ctx {
     int64_t aln_all_n = -1; uint32_t aln_all_maxlen = 0;
 
     // string graph (tr.hip)
-    bool have_edges = false;                   // an edge list loaded with elba_set_overlaps (otherwise this context's alignments are the input)
     int64_t tr_in_M = 0, tr_in_n = 0;
     DevBuf tr_in_rows, tr_in_cols, tr_in_vals;
-    bool have_S = false;
     int64_t tr_M = 0, tr_nnz = 0, tr_id_base = 0;
     DevBuf tr_deg, tr_pas, tr_flags, tr_k0, tr_v0, tr_k1, tr_v1, tr_ptr, tr_sym, tr_src, tr_mark, tr_ctr, tr_sel, tr_out_rows, tr_out_cols, tr_out_vals;
     elba_string_stats sstats{};
 
     // contigs (contig.hip): results (cid, eread, epre, estr, eboff, soff, coff, seq, kind) survive elba_release_workspace, the rest is scratch
-    bool have_contigs = false;
     int64_t cg_n = 0, cg_E = 0, cg_bases = 0, cg_circular = 0, cg_singletons = 0;
     DevBuf cg_ptr, cg_slot, cg_kdeg, cg_far[2], cg_rank[2], cg_mn[2], cg_term, cg_vinfo, cg_flag, cg_cidx, cg_nel, cg_eoff, cg_ctr;
     DevBuf cg_cid, cg_eread, cg_epre, cg_estr, cg_eboff, cg_soff, cg_coff, cg_seq, cg_kind;
@@ -312,7 +306,6 @@ struct Ctx {
     elba_contig_stats cstats{};
 
     // read pileups (pileup.hip): results (seg_off, seg_start, seg_depth, trim, flags) survive elba_release_workspace, the rest is scratch
-    bool have_pileup = false;
     int64_t pu_M = 0, pu_n = 0, pu_nseg = 0;
     DevBuf pu_k0, pu_k1, pu_eptr, pu_head, pu_hidx, pu_delta, pu_dsum, pu_gstart, pu_tok, pu_tpos, pu_ctr, pu_sel, pu_rows, pu_cols, pu_vals;
     DevBuf pu_seg_off, pu_seg_start, pu_seg_depth, pu_trim, pu_flags;
@@ -322,7 +315,6 @@ struct Ctx {
 
     // trimmed reads (trim.hip): a snapshot in buffers of its own — packed / off / len in DnaBuffer layout, the map (src, beg, end); it survives
     // elba_prune_reads and elba_release_workspace, a new read set or a new pileup invalidates it, elba_adopt_trimmed_reads consumes it
-    bool have_trim = false;
     int64_t tm_n = 0, tm_packed_bytes = 0;
     DevBuf tm_packed, tm_off, tm_len, tm_src, tm_beg, tm_end;
     DevBuf tm_cnt, tm_bytes, tm_first, tm_boff, tm_srcb, tm_ctr;      // scratch
@@ -373,11 +365,35 @@ struct Ctx {
     PhaseMarks<5> ov_marks;        // overlap SpGEMM: 0 call start, 1 numeric start, 2 numeric end, 3 call end, 4 finalize start when the host synchronised before it
 };
 
-// a new read set invalidates everything derived from the old one (elba_set_reads, elba_set_reads_device, elba_adopt_trimmed_reads; stage_set_reads_fasta does the same)
-inline void reads_replaced(Ctx &c)
+// a new read set is in place (elba_set_reads*, elba_adopt_trimmed_reads): ev's row, and an A built from the old reads goes with them
+inline void reads_replaced(Ctx &c, Event ev)
 {
-    c.have_reads = true; c.have_counts = false; c.have_aln = false; c.have_edges = false; c.have_S = false; c.have_pileup = false; c.have_trim = false;
-    if (c.A_has_kmers) { c.have_A = false; c.have_B = false; }      // (an A handed over as triples / a panel does not come from these reads)
+    done(c.v, ev);
+    if (c.A_has_kmers) done(c.v, EV_MATRIX_OF_OLD_READS);
+}
+
+// The pairs the string graph is built from — what elba_transitive_reduction, elba_read_pileup and elba_prune_reads read: a loaded edge
+// list while one is valid, else this context's own alignments of a whole B.  id_base: what the exported graph adds to its read ids.
+struct GraphInput { int64_t M, n, id_base; const int64_t *rows, *cols; const elba_overlap_t *vals; };
+inline GraphInput graph_input(Ctx &c, const char *who)
+{
+    if (has(c.v, P_EDGES)) return {c.tr_in_M, c.tr_in_n, 0, c.tr_in_rows.as<int64_t>(), c.tr_in_cols.as<int64_t>(), c.tr_in_vals.as<elba_overlap_t>()};
+    ELBA_REQUIRE(has(c.v, P_ALN), ELBA_ERR_STATE, std::string(who) + ": no overlaps (call elba_align_seeds or elba_set_overlaps)");
+    ELBA_REQUIRE(c.row_hi < 0 || (c.row_lo == 0 && c.row_hi == c.M), ELBA_ERR_STATE,
+                 std::string(who) + ": this context aligned a row shard; gather the ranks' overlaps and load them with elba_set_overlaps");
+    return {c.M, c.naln, c.first_global_id_rows(), c.aln_rows.as<int64_t>(), c.aln_cols.as<int64_t>(), c.aln_out.as<elba_overlap_t>()};
+}
+
+// Where reads 0 .. M-1 are: the replicated set (elba_dist_set_all_reads) when it holds M reads and the caller takes it, else the context's
+// own.  what: the reads as the error names them, '#' standing for M.
+struct ReadSource { const uint8_t *packed; const uint64_t *byte_off; const uint32_t *len; bool replicated; };
+inline ReadSource read_source(Ctx &c, int64_t M, const char *who, const char *what, bool take_replicated = true)
+{
+    if (take_replicated && c.aln_all_n == M && c.aln_all_n >= 0) return {c.aln_all_packed.as<uint8_t>(), c.aln_all_off.as<uint64_t>(), c.aln_all_len.as<uint32_t>(), true};
+    if (has(c.v, P_READS) && c.nreads == M) return {c.d_packed, c.d_byte_off, c.d_len, false};
+    std::string w(what);
+    w.replace(w.find('#'), 1, std::to_string(M));
+    throw Error{ELBA_ERR_STATE, std::string(who) + ": the " + w + " are not on this context (elba_set_reads or elba_dist_set_all_reads)"};
 }
 
 // ---- stages -----------------------------------------------------------------------------------------------------
@@ -402,11 +418,12 @@ void stage_dist_set_all_reads(Ctx &c, const void *d_packed, int64_t packed_bytes
 void stage_set_overlaps(Ctx &c, int64_t nreads, const int64_t *rows, const int64_t *cols, const elba_overlap_t *vals, int64_t n);   // tr.hip
 void stage_transitive_reduction(Ctx &c, double bad_read_cutoff, int fuzz);   // tr.hip
 void stage_generate_contigs(Ctx &c, int flags);                                          // contig.hip
-void stage_read_pileup(Ctx &c, const elba_pileup_cfg &cfg);                   // pileup.hip
+void stage_generate_contigs_ex(Ctx &c, const elba_contig_cfg *cfg);                      // contig.hip
+void stage_read_pileup(Ctx &c, const elba_pileup_cfg *cfg);                   // pileup.hip
 void stage_prune_reads(Ctx &c, int mask, int64_t *kept);
-void stage_trim_reads(Ctx &c, const elba_trim_cfg &cfg);                      // trim.hip
+void stage_trim_reads(Ctx &c, const elba_trim_cfg *cfg);                      // trim.hip
 void stage_adopt_trimmed_reads(Ctx &c);
-void stage_clip_tips(Ctx &c, const elba_tip_cfg &cfg);                        // tips.hip
+void stage_clip_tips(Ctx &c, const elba_tip_cfg *cfg);                        // tips.hip
 void stage_dist_count_owners(Ctx &c, int nranks, uint64_t *counts_host);                                   // kmer.hip
 void stage_dist_value_histogram(Ctx &c, uint64_t *hist_host, int64_t nbins);
 void stage_ref_hash_owner(Ctx &c, const uint64_t *kmers_host, int64_t n, int nprocs, uint64_t *hash_host, int32_t *owner_host);

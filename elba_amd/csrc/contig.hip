@@ -287,14 +287,14 @@ __global__ __launch_bounds__(CG_WRITE_THREADS) void k_cg_write(const int64_t *er
 
 void stage_generate_contigs(Ctx &c, int flags)
 {
-    c.have_contigs = false;
+    enter(c.v, EV_GENERATE_CONTIGS);
     ELBA_REQUIRE((flags & ~(ELBA_CONTIG_CIRCULAR | ELBA_CONTIG_SINGLETONS)) == 0, ELBA_ERR_INVALID_ARG, "generate_contigs: unknown flag bits");
-    ELBA_REQUIRE(c.have_S, ELBA_ERR_STATE, "generate_contigs: no string graph (call elba_transitive_reduction)");
+    ELBA_REQUIRE(has(c.v, P_S), ELBA_ERR_STATE, "generate_contigs: no string graph (call elba_transitive_reduction)");
     const int64_t M = c.tr_M, nnz = c.tr_nnz;
-    const uint8_t *packed; const uint64_t *byte_off; const uint32_t *len;
-    if (c.tr_id_base == 0 && c.aln_all_n == M) { packed = c.aln_all_packed.as<uint8_t>(); byte_off = c.aln_all_off.as<uint64_t>(); len = c.aln_all_len.as<uint32_t>(); }
-    else if (c.have_reads && c.nreads == M) { packed = c.d_packed; byte_off = c.d_byte_off; len = c.d_len; }
-    else throw Error{ELBA_ERR_STATE, "generate_contigs: the sequences of the graph's " + std::to_string(M) + " reads are not on this context (elba_set_reads or elba_dist_set_all_reads)"};
+    // (the replicated set is indexed by global read id, the graph by row: the same reads only when the graph's ids have no base)
+    const ReadSource src = read_source(c, M, "generate_contigs", "sequences of the graph's # reads", c.tr_id_base == 0);
+    const uint8_t *packed = src.packed; const uint64_t *byte_off = src.byte_off; const uint32_t *len = src.len;
+    accepted(c.v, EV_GENERATE_CONTIGS);
     hipStream_t s = c.stream;
     const int64_t base = c.tr_id_base;
     elba_contig_stats st{};
@@ -385,7 +385,16 @@ void stage_generate_contigs(Ctx &c, int flags)
     st.components = st.branches + (int64_t)h[1] + st.used_components;     // CC on S without the branches' rows and columns: a branch read is a component of its own
     st.contig_reads = E; st.bases = bases; st.longest = (int64_t)h[7];
     st.ms_total = c.cg_t_total.ms(); st.ms_rank = c.cg_t_rank.ms();
-    c.cg_n = nc; c.cg_E = E; c.cg_bases = bases; c.cg_circular = ncirc; c.cg_singletons = nsingle; c.cstats = st; c.have_contigs = true;
+    c.cg_n = nc; c.cg_E = E; c.cg_bases = bases; c.cg_circular = ncirc; c.cg_singletons = nsingle; c.cstats = st; done(c.v, EV_GENERATE_CONTIGS);
+}
+
+void stage_generate_contigs_ex(Ctx &c, const elba_contig_cfg *cfg)
+{
+    enter(c.v, EV_GENERATE_CONTIGS);                            // (before the checks: a rejected call leaves no contigs either; entered again below, which changes nothing)
+    ELBA_REQUIRE(cfg, ELBA_ERR_INVALID_ARG, "generate_contigs_ex: null cfg");
+    ELBA_REQUIRE(!cfg->reserved[0] && !cfg->reserved[1] && !cfg->reserved[2], ELBA_ERR_INVALID_ARG, "generate_contigs_ex: reserved words must be 0");
+    ELBA_REQUIRE((cfg->flags & ~(ELBA_CONTIG_CIRCULAR | ELBA_CONTIG_SINGLETONS)) == 0, ELBA_ERR_INVALID_ARG, "generate_contigs_ex: unknown flag bits");
+    stage_generate_contigs(c, cfg->flags);
 }
 
 }  // namespace elba

@@ -93,6 +93,7 @@ __global__ __launch_bounds__(ENC_THREADS) void k_fasta_encode(const uint8_t *chu
 void stage_set_reads_fasta(Ctx &c, const char *chunk, int64_t chunk_bytes, uint64_t chunk_file_offset, const elba_fasta_record_t *recs, int64_t nreads,
                            int64_t first_global_id, elba_ingest_stats *stats)
 {
+    enter(c.v, EV_SET_READS_FASTA);
     ELBA_REQUIRE(nreads >= 0 && chunk_bytes >= 0 && (nreads == 0 || (chunk && recs)), ELBA_ERR_INVALID_ARG, "set_reads_fasta: null array");
     ELBA_REQUIRE(nreads < 0xFFFFFFFFll, ELBA_ERR_UNSUPPORTED, "set_reads_fasta: more than 2^32-1 reads on one GPU");
     hipStream_t s = c.stream;
@@ -134,8 +135,7 @@ void stage_set_reads_fasta(Ctx &c, const char *chunk, int64_t chunk_bytes, uint6
     c.d_packed = c.own_packed.as<uint8_t>(); c.d_byte_off = c.own_byte_off.as<uint64_t>(); c.d_len = c.own_len.as<uint32_t>();
     c.h_len = len; off.pop_back(); c.h_byte_off = off;
     c.nreads = nreads; c.first_global_id = first_global_id; c.packed_bytes = (int64_t)pb;
-    c.have_reads = true; c.have_counts = false; c.have_aln = false; c.have_edges = false; c.have_S = false;
-    if (c.A_has_kmers) { c.have_A = false; c.have_B = false; }
+    reads_replaced(c, EV_SET_READS_FASTA);
     if (stats) {
         stats->nreads = nreads; stats->bases = (int64_t)totbases; stats->packed_bytes = (int64_t)pb; stats->chunk_bytes = chunk_bytes;
         stats->ms_total = c.t_total.ms(); stats->ms_encode = nreads ? c.t_a.ms() : 0.f;

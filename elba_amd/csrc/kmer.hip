@@ -570,11 +570,13 @@ static bool count_long_kmers_in_passes(Ctx &c, uint64_t I, int words, size_t fre
 
 void stage_count_kmers(Ctx &c)
 {
-    ELBA_REQUIRE(c.have_reads, ELBA_ERR_STATE, "count_kmers: no reads (call elba_set_reads)");
+    enter(c.v, EV_COUNT_KMERS);
+    ELBA_REQUIRE(has(c.v, P_READS), ELBA_ERR_STATE, "count_kmers: no reads (call elba_set_reads)");
     hipStream_t s = c.stream;
     const int k = c.cfg.k;
     const int64_t M = c.nreads;
-    c.have_counts = false; c.have_A = false; c.have_B = false; c.dist_owner = false;
+    accepted(c.v, EV_COUNT_KMERS);
+    c.dist_owner = false;
     c.kmer_path = 0;
     elba_kmer_stats st{};
     st.nreads = M;
@@ -604,7 +606,7 @@ void stage_count_kmers(Ctx &c)
     if (k > 31) {
         // ---- two- and three-word k-mers: sort an index permutation, last word first (stable LSD over all words), then gather ----
         const int words = k > 64 ? 3 : 2;
-        if (count_long_kmers_in_passes(c, I, words, free0, st)) return;
+        if (count_long_kmers_in_passes(c, I, words, free0, st)) { done(c.v, EV_COUNT_KMERS); return; }
         DevBuf khi, klo, klo2, val, i0, i1, t0, t1, s2buf;
         for (DevBuf *b : {&khi, &klo, &val, &i0, &i1, &t0, &t1}) b->reserve((size_t)(I + 2) * 8);
         if (words == 3) { klo2.reserve((size_t)(I + 2) * 8); s2buf.reserve((size_t)(I + 2) * 8); }
@@ -633,12 +635,12 @@ void stage_count_kmers(Ctx &c)
         c.ndistinct = (int64_t)nruns;
         c.N = (int64_t)N; c.Z = (int64_t)Z;
         c.kstats = st;
-        c.have_counts = true;
+        done(c.v, EV_COUNT_KMERS);
         return;
     }
     if (msd_count_kmers(c, I, st)) {      // k <= 17 on inputs of some size: two-level value partition + LDS count tables (kmer_msd.hip)
         c.kstats = st;
-        c.have_counts = true;
+        done(c.v, EV_COUNT_KMERS);
         return;
     }
     ELBA_REQUIRE(I < 0xFFFFFFF0ull, ELBA_ERR_UNSUPPORTED, "count_kmers: more than 2^32 k-mer instances on one GPU and the two-level partition does not take this input");
@@ -692,7 +694,7 @@ void stage_count_kmers(Ctx &c)
         c.ndistinct = (int64_t)nruns;
         c.N = (int64_t)N; c.Z = (int64_t)Z;
         c.kstats = st;
-        c.have_counts = true;
+        done(c.v, EV_COUNT_KMERS);
         return;
     }
 
@@ -708,11 +710,12 @@ __global__ void k_expand_colptr(const uint32_t *colptr, uint64_t N, uint64_t *ki
 
 void stage_create_kmer_matrix(Ctx &c)
 {
-    ELBA_REQUIRE(c.have_counts, ELBA_ERR_STATE, "create_kmer_matrix: no k-mer counts (call elba_count_kmers)");
+    enter(c.v, EV_CREATE_KMER_MATRIX);
+    ELBA_REQUIRE(has(c.v, P_COUNTS), ELBA_ERR_STATE, "create_kmer_matrix: no k-mer counts (call elba_count_kmers)");
     ELBA_REQUIRE(!c.dist_owner, ELBA_ERR_STATE, "create_kmer_matrix: this context counted exchanged records (elba_dist_count_records); its matrix is a panel (elba_dist_set_panel)");
     hipStream_t s = c.stream;
     const int64_t M = c.nreads, N = c.N, Z = c.Z;
-    c.have_A = false; c.have_B = false;
+    accepted(c.v, EV_CREATE_KMER_MATRIX);
     // CSC(A) came out of the counting sort already; the CSR build needs the column id of every entry.  The fused column pass (k_runs_emit) left
     // them as ready-made sort keys (csr_words), which the build CONSUMES (hint bits are ORed in, the sort ping-pongs over them): a second call
     // after one elba_count_kmers rebuilds the column ids from the column pointers instead.
@@ -727,6 +730,7 @@ void stage_create_kmer_matrix(Ctx &c)
     finish_matrix_from_sorted_csc(c, M, N, Z, c.kid_of_entry.as<uint64_t>(), 0, c.a_csc.as<uint64_t>(), 0, -1, pre);      // (column ids — or the CSR sort keys — were written with the columns: k_runs / k_runs_emit)
     if (pre) { c.pre_ready = false; c.pre_consumed = true; }
     c.kstats.ms_lookup = c.t_c.ms();
+    done(c.v, EV_CREATE_KMER_MATRIX);
 }
 
 }  // namespace elba
@@ -1215,7 +1219,6 @@ static bool count_long_kmers_in_passes(Ctx &c, uint64_t I, int words, size_t fre
     c.ndistinct = (int64_t)distinct;
     c.N = (int64_t)N; c.Z = (int64_t)Z;
     c.kstats = st;
-    c.have_counts = true;
     return true;
 }
 
@@ -1248,7 +1251,7 @@ static uint64_t upload_instance_offsets(Ctx &c)
 
 void stage_dist_value_histogram(Ctx &c, uint64_t *hist_host, int64_t nbins)
 {
-    ELBA_REQUIRE(c.have_reads, ELBA_ERR_STATE, "dist_value_histogram: no reads");
+    ELBA_REQUIRE(has(c.v, P_READS), ELBA_ERR_STATE, "dist_value_histogram: no reads");
     ELBA_REQUIRE(nbins == (1 << OWNER_BITS) && hist_host, ELBA_ERR_INVALID_ARG, "dist_value_histogram: the histogram has 4096 bins");
     hipStream_t s = c.stream;
     const uint64_t I = upload_instance_offsets(c);
@@ -1278,7 +1281,7 @@ void stage_dist_set_owner_ranges(Ctx &c, int nranks, const uint32_t *upper_bins)
 // global k-mer ids of this owner's columns: base + local index (the owners hold ascending value ranges)
 void stage_dist_set_kmer_id_base(Ctx &c, int64_t base, int64_t nall)
 {
-    ELBA_REQUIRE(c.have_counts && c.dist_owner, ELBA_ERR_STATE, "dist_set_kmer_id_base: call dist_count_records first");
+    ELBA_REQUIRE(has(c.v, P_COUNTS) && c.dist_owner, ELBA_ERR_STATE, "dist_set_kmer_id_base: call dist_count_records first");
     ELBA_REQUIRE(base >= 0 && base + c.own_N <= nall && nall < 0xFFFFFFF0ll, ELBA_ERR_INVALID_ARG, "dist_set_kmer_id_base: bad id range");
     c.dist_gid.reserve((size_t)(c.own_N + 1) * 4);
     if (c.own_N > 0) hipLaunchKernelGGL(k_iota_u32, dim3((unsigned)((c.own_N + 255) / 256)), dim3(256), 0, c.stream, c.dist_gid.as<uint32_t>(), (uint64_t)c.own_N, (uint32_t)base);
@@ -1338,7 +1341,7 @@ void stage_ref_hash_owner(Ctx &c, const uint64_t *kmers_host, int64_t n, int npr
 
 void stage_dist_count_owners(Ctx &c, int nranks, uint64_t *counts_host)
 {
-    ELBA_REQUIRE(c.have_reads, ELBA_ERR_STATE, "dist_count_owners: no reads");
+    ELBA_REQUIRE(has(c.v, P_READS), ELBA_ERR_STATE, "dist_count_owners: no reads");
     ELBA_REQUIRE(nranks >= 1 && nranks <= MAX_RANKS, ELBA_ERR_INVALID_ARG, "dist_count_owners: 1..64 ranks");
     hipStream_t s = c.stream;
     const int k = c.cfg.k;
@@ -1360,7 +1363,7 @@ void stage_dist_count_owners(Ctx &c, int nranks, uint64_t *counts_host)
 
 void stage_dist_fill_send(Ctx &c, int nranks, void *d_send, const uint64_t *offsets_host)
 {
-    ELBA_REQUIRE(c.have_reads && c.inst_off.p, ELBA_ERR_STATE, "dist_fill_send: call dist_count_owners first");
+    ELBA_REQUIRE(has(c.v, P_READS) && c.inst_off.p, ELBA_ERR_STATE, "dist_fill_send: call dist_count_owners first");
     ELBA_REQUIRE(nranks >= 1 && nranks <= MAX_RANKS, ELBA_ERR_INVALID_ARG, "dist_fill_send: 1..64 ranks");
     hipStream_t s = c.stream;
     c.ws_scan.reserve(MAX_RANKS * 8);
@@ -1424,7 +1427,7 @@ bool stage_dist_packed_format(Ctx &c, int nranks, const int64_t *bounds, const u
 
 void stage_dist_fill_send_packed(Ctx &c, int nranks, void *d_send, const uint64_t *offsets_host)
 {
-    ELBA_REQUIRE(c.have_reads && c.inst_off.p, ELBA_ERR_STATE, "dist_fill_send_packed: call dist_count_owners first");
+    ELBA_REQUIRE(has(c.v, P_READS) && c.inst_off.p, ELBA_ERR_STATE, "dist_fill_send_packed: call dist_count_owners first");
     ELBA_REQUIRE(c.dist_pack_ib > 0 && (int)c.dist_bounds.size() == nranks + 1, ELBA_ERR_STATE, "dist_fill_send_packed: call dist_packed_format first (it must have returned 1)");
     hipStream_t s = c.stream;
     c.ws_scan.reserve(MAX_RANKS * 8);
@@ -1460,11 +1463,12 @@ void stage_dist_unpack_records(Ctx &c, int nranks, int rank, const void *d_packe
 // Owner side of exchange #1: count the received records exactly, keep LOWER <= count <= UPPER, sort the kept k-mers.
 void stage_dist_count_records(Ctx &c, const void *d_rec, int64_t nrec)
 {
+    enter(c.v, EV_DIST_COUNT_RECORDS);
     ELBA_REQUIRE(nrec >= 0 && (nrec == 0 || d_rec), ELBA_ERR_INVALID_ARG, "dist_count_records: null records");
     ELBA_REQUIRE(nrec < 0xFFFFFFF0ll, ELBA_ERR_UNSUPPORTED, "more than 2^32 records on one GPU");
     hipStream_t s = c.stream;
     const int k = c.cfg.k;
-    c.have_counts = false; c.have_A = false; c.have_B = false;
+    accepted(c.v, EV_DIST_COUNT_RECORDS);
     c.d_records = static_cast<const uint64_t *>(d_rec); c.nrecords = nrec;
     const uint64_t I = (uint64_t)nrec;
     // The owner counts exactly like the single-GPU path, by sorting (file header): records -> (k-mer, read << 32 | pos) pairs -> stable radix
@@ -1507,12 +1511,11 @@ void stage_dist_count_records(Ctx &c, const void *d_rec, int64_t nrec)
     c.I = nrec; c.ndistinct = (int64_t)hc.distinct; c.N = (int64_t)N; c.Z = (int64_t)Z;
     c.kstats = elba_kmer_stats{};
     c.kstats.instances = nrec; c.kstats.distinct = (int64_t)hc.distinct; c.kstats.reliable = (int64_t)N; c.kstats.entries = (int64_t)Z;
-    c.have_counts = true;
     c.dist_owner = true;
     // the owner's columns leave the context's A (which every panel this rank RECEIVES overwrites) for buffers of their own
     c.a_colptr.swap(c.own_colptr); c.a_csc.swap(c.own_csc);
     c.own_N = (int64_t)N; c.own_Z = (int64_t)Z;
-    c.have_A = false;
+    done(c.v, EV_DIST_COUNT_RECORDS);
 }
 
 void stage_dist_copy_reliable_kmers(Ctx &c, void *d_dst)
@@ -1530,7 +1533,7 @@ void stage_dist_copy_reliable_kmers(Ctx &c, void *d_dst)
 // After the all-gather of every owner's sorted reliable k-mers: global k-mer ids of the local columns.
 void stage_dist_set_global_kmers(Ctx &c, const void *d_all, int64_t nall)
 {
-    ELBA_REQUIRE(c.have_counts && c.dist_owner, ELBA_ERR_STATE, "dist_set_global_kmers: call dist_count_records first");
+    ELBA_REQUIRE(has(c.v, P_COUNTS) && c.dist_owner, ELBA_ERR_STATE, "dist_set_global_kmers: call dist_count_records first");
     ELBA_REQUIRE(nall >= c.own_N && nall < 0xFFFFFFF0ll, ELBA_ERR_INVALID_ARG, "dist_set_global_kmers: bad global k-mer count");
     hipStream_t s = c.stream;
     const int W = kmer_words(c.cfg.k);
@@ -1602,9 +1605,11 @@ void stage_dist_panel(Ctx &c, int nranks, const uint64_t *bounds_host, const uin
 // rows [row_lo, row_hi) only — the rows this rank owns, whose columns are complete by construction.
 void stage_dist_set_panel(Ctx &c, const void *d_rec, int64_t nrec, int64_t M_total, int64_t N_total, int64_t row_lo, int64_t row_hi)
 {
+    enter(c.v, EV_DIST_SET_PANEL);
     ELBA_REQUIRE(nrec >= 0 && (nrec == 0 || d_rec), ELBA_ERR_INVALID_ARG, "dist_set_panel: null records");
     ELBA_REQUIRE(M_total >= 0 && N_total >= 0 && M_total < 0xFFFFFFFFll && N_total < 0xFFFFFFFFll && nrec < 0xFFFFFFF0ll, ELBA_ERR_UNSUPPORTED, "dist_set_panel: dimension beyond 32 bits");
     ELBA_REQUIRE(row_lo >= 0 && row_lo <= row_hi && row_hi <= M_total, ELBA_ERR_INVALID_ARG, "dist_set_panel: bad row window");
+    accepted(c.v, EV_DIST_SET_PANEL);
     hipStream_t s = c.stream;
     c.ws_a.reserve((size_t)(nrec + 1) * 8); c.ws_b.reserve((size_t)(nrec + 1) * 8); c.ws_c.reserve((size_t)(nrec + 1) * 8); c.ws_d.reserve((size_t)(nrec + 1) * 8);
     c.ws_e.reserve((size_t)(nrec + 1) * 8); c.ws_f.reserve((size_t)(nrec + 1) * 8);
@@ -1634,6 +1639,7 @@ void stage_dist_set_panel(Ctx &c, const void *d_rec, int64_t nrec, int64_t M_tot
     c.A_has_kmers = false;
     finish_matrix_from_sorted_csc(c, M_total, N_local, nrec, c.ws_e.as<uint64_t>(), 0, c.ws_f.as<uint64_t>(), row_lo, row_hi);
     c.N_global = N_total;
+    done(c.v, EV_DIST_SET_PANEL);
 }
 
 }  // namespace elba

@@ -459,8 +459,6 @@ void finish_matrix_from_sorted_csc(Ctx &c, int64_t M, int64_t N, int64_t Z, cons
         hipLaunchKernelGGL(k_ell_partners, dim3((unsigned)std::min<uint64_t>((nslots / 4 + 255) / 256, 1ull << 20)), dim3(256), 0, s, windowed ? (const uint64_t *)c.a_ell.as<uint64_t>() : (const uint64_t *)nullptr, (const uint64_t *)c.a_csc.as<uint64_t>(), (const uint32_t *)c.a_colptr.as<uint32_t>(), (uint64_t)N, c.s_stride,
                            c.j_shift, c.a_ellj.as<uint32_t>(), c.have_row_order ? (const uint32_t *)c.row_label.as<uint32_t>() : (const uint32_t *)nullptr);
     }
-    c.have_A = true;
-    c.have_B = false;
 }
 
 namespace {
@@ -551,9 +549,11 @@ static void set_kmer_matrix_from_pairs(Ctx &c, int64_t M, int64_t N, int64_t Z, 
 
 void stage_set_kmer_matrix_device(Ctx &c, int64_t M, int64_t N, int64_t Z, const int64_t *d_rows, const int64_t *d_cols, const uint32_t *d_vals)
 {
+    enter(c.v, EV_SET_KMER_MATRIX_DEVICE);
     ELBA_REQUIRE(M >= 0 && N >= 0 && Z >= 0, ELBA_ERR_INVALID_ARG, "negative matrix dimension");
     ELBA_REQUIRE(M < 0xFFFFFFFFll && N < 0xFFFFFFFFll && Z < 0xFFFFFFFFll, ELBA_ERR_UNSUPPORTED, "matrix dimension beyond 32-bit device indices");
     ELBA_REQUIRE(Z == 0 || (d_rows && d_cols && d_vals), ELBA_ERR_INVALID_ARG, "null triple array");
+    accepted(c.v, EV_SET_KMER_MATRIX_DEVICE);       // (before the device checks the indices: the bucket kernels write into A's buffers as they check)
     hipStream_t s = c.stream;
     c.ws_scan.reserve(64);
     const unsigned nbz = (unsigned)((Z + 255) / 256);
@@ -567,6 +567,7 @@ void stage_set_kmer_matrix_device(Ctx &c, int64_t M, int64_t N, int64_t Z, const
         c.A_has_kmers = false;
         finish_matrix_from_sorted_csc(c, M, N, Z, nullptr, 0, c.a_csc.as<uint64_t>(), 0, -1, true);
         c.pre_ready = false; c.pre_consumed = true;
+        done(c.v, EV_SET_KMER_MATRIX_DEVICE);
         return;
     }
     ELBA_HIP(hipMemsetAsync(c.ws_scan.p, 0, 16, s));
@@ -588,17 +589,19 @@ void stage_set_kmer_matrix_device(Ctx &c, int64_t M, int64_t N, int64_t Z, const
         hipLaunchKernelGGL(k_unpack_triple_words, dim3(nbz), dim3(256), 0, s, (const uint64_t *)(where ? w1 : w0), Z, mb, pb, c.ws_e.as<uint64_t>(), c.ws_f.as<uint64_t>());
         c.A_has_kmers = false;
         finish_matrix_from_sorted_csc(c, M, N, Z, c.ws_e.as<uint64_t>(), 32, c.ws_f.as<uint64_t>());
+        done(c.v, EV_SET_KMER_MATRIX_DEVICE);
         return;
     }
     if (Z > 0)
         hipLaunchKernelGGL(k_pack_triples, dim3(nbz), dim3(256), 0, s, d_rows, d_cols, d_vals, Z, M, N, c.ws_a.as<uint64_t>(), c.ws_b.as<uint64_t>(), c.ws_scan.as<unsigned long long>());
     ELBA_HIP(hipStreamSynchronize(s));
     set_kmer_matrix_from_pairs(c, M, N, Z, chk[1]);
+    done(c.v, EV_SET_KMER_MATRIX_DEVICE);
 }
 
 void stage_export_triples_device(Ctx &c, int64_t *d_rows, int64_t *d_cols, uint32_t *d_vals)
 {
-    ELBA_REQUIRE(c.have_A, ELBA_ERR_STATE, "export_triples_device: no k-mer matrix");
+    ELBA_REQUIRE(has(c.v, P_A), ELBA_ERR_STATE, "export_triples_device: no k-mer matrix");
     ELBA_REQUIRE(c.Z == 0 || (d_rows && d_cols && d_vals), ELBA_ERR_INVALID_ARG, "null triple array");
     if (c.csr_inline && c.N > 0 && c.Z > 0) {      // (rows with inline partners do not name every entry's k-mer: the triples come from the columns)
         hipLaunchKernelGGL(k_export_triples_csc, dim3((unsigned)((c.N + 255) / 256)), dim3(256), 0, c.stream, (const uint32_t *)c.a_colptr.as<uint32_t>(), (const uint64_t *)c.a_csc.as<uint64_t>(), (uint64_t)c.N, d_rows, d_cols, d_vals);
@@ -612,6 +615,7 @@ void stage_export_triples_device(Ctx &c, int64_t *d_rows, int64_t *d_cols, uint3
 
 void stage_set_kmer_matrix(Ctx &c, int64_t M, int64_t N, int64_t Z, const int64_t *rows, const int64_t *cols, const uint32_t *vals)
 {
+    enter(c.v, EV_SET_KMER_MATRIX);
     ELBA_REQUIRE(M >= 0 && N >= 0 && Z >= 0, ELBA_ERR_INVALID_ARG, "negative matrix dimension");
     ELBA_REQUIRE(M < 0xFFFFFFFFll && N < 0xFFFFFFFFll && Z < 0xFFFFFFFFll, ELBA_ERR_UNSUPPORTED, "matrix dimension beyond 32-bit device indices");
     ELBA_REQUIRE(Z == 0 || (rows && cols && vals), ELBA_ERR_INVALID_ARG, "null triple array");
@@ -624,6 +628,7 @@ void stage_set_kmer_matrix(Ctx &c, int64_t M, int64_t N, int64_t Z, const int64_
         hv[(size_t)z] = ((uint64_t)cols[z] << 32) | (uint64_t)rows[z];
         if (vals[z] > maxpos) maxpos = vals[z];
     }
+    accepted(c.v, EV_SET_KMER_MATRIX);
     c.ws_a.reserve((size_t)(Z + 1) * 8); c.ws_b.reserve((size_t)(Z + 1) * 8);
     c.ws_c.reserve((size_t)(Z + 1) * 8); c.ws_d.reserve((size_t)(Z + 1) * 8);
     c.ws_e.reserve((size_t)(Z + 1) * 8); c.ws_f.reserve((size_t)(Z + 1) * 8);
@@ -633,6 +638,7 @@ void stage_set_kmer_matrix(Ctx &c, int64_t M, int64_t N, int64_t Z, const int64_
         ELBA_HIP(hipStreamSynchronize(s));      // (the host vectors go out of scope below)
     }
     set_kmer_matrix_from_pairs(c, M, N, Z, maxpos);
+    done(c.v, EV_SET_KMER_MATRIX);
 }
 
 }  // namespace elba

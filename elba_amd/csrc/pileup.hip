@@ -247,41 +247,33 @@ __global__ void k_pu_prune_scatter(const int64_t *rows, const int64_t *cols, con
     orow[at] = rows[a]; ocol[at] = cols[a]; oval[at] = vals[a];
 }
 
-struct PuInput { int64_t M, n; const int64_t *rows, *cols; const elba_overlap_t *vals; const uint32_t *len; uint32_t maxlen; };
+struct PuInput : GraphInput { const uint32_t *len; uint32_t maxlen; };
 
-// the pairs elba_transitive_reduction would read next and the lengths of reads 0 .. M-1 (the same preconditions as TR and contigs)
+// the pairs elba_transitive_reduction would read next and the lengths of reads 0 .. M-1
 PuInput pileup_input(Ctx &c, const char *who)
 {
-    PuInput in{};
-    if (c.have_edges) {
-        in.M = c.tr_in_M; in.n = c.tr_in_n;
-        in.rows = c.tr_in_rows.as<int64_t>(); in.cols = c.tr_in_cols.as<int64_t>(); in.vals = c.tr_in_vals.as<elba_overlap_t>();
-    } else {
-        ELBA_REQUIRE(c.have_aln, ELBA_ERR_STATE, std::string(who) + ": no overlaps (call elba_align_seeds or elba_set_overlaps)");
-        ELBA_REQUIRE(c.row_hi < 0 || (c.row_lo == 0 && c.row_hi == c.M), ELBA_ERR_STATE,
-                     std::string(who) + ": this context aligned a row shard; gather the ranks' overlaps and load them with elba_set_overlaps");
-        in.M = c.M; in.n = c.naln;
-        in.rows = c.aln_rows.as<int64_t>(); in.cols = c.aln_cols.as<int64_t>(); in.vals = c.aln_out.as<elba_overlap_t>();
-    }
-    if (c.aln_all_n == in.M && c.aln_all_n >= 0) { in.len = c.aln_all_len.as<uint32_t>(); in.maxlen = c.aln_all_maxlen; }
-    else if (c.have_reads && c.nreads == in.M) {
-        in.len = c.d_len;
-        for (uint32_t l : c.h_len) in.maxlen = l > in.maxlen ? l : in.maxlen;
-    } else throw Error{ELBA_ERR_STATE, std::string(who) + ": the lengths of the " + std::to_string(in.M) + " reads of the overlaps are not on this context (elba_set_reads or elba_dist_set_all_reads)"};
+    PuInput in{graph_input(c, who), nullptr, 0};
+    const ReadSource src = read_source(c, in.M, who, "lengths of the # reads of the overlaps");
+    in.len = src.len;
+    if (src.replicated) in.maxlen = c.aln_all_maxlen;
+    else for (uint32_t l : c.h_len) in.maxlen = l > in.maxlen ? l : in.maxlen;
     return in;
 }
 
 }  // namespace
 
-void stage_read_pileup(Ctx &c, const elba_pileup_cfg &cfg)
+void stage_read_pileup(Ctx &c, const elba_pileup_cfg *cfgp)
 {
-    c.have_pileup = false;
+    enter(c.v, EV_READ_PILEUP);
+    ELBA_REQUIRE(cfgp, ELBA_ERR_INVALID_ARG, "read_pileup: null cfg");
+    const elba_pileup_cfg &cfg = *cfgp;
     ELBA_REQUIRE(cfg.mode == 0 || cfg.mode == 1, ELBA_ERR_INVALID_ARG, "read_pileup: mode must be 0 (passed pairs) or 1 (score > 0)");
     ELBA_REQUIRE(cfg.margin >= 0 && cfg.min_depth >= 1 && cfg.min_run >= 1 && cfg.trim_len >= 0, ELBA_ERR_INVALID_ARG,
                  "read_pileup: need margin >= 0, min_depth >= 1, min_run >= 1, trim_len >= 0");
     const PuInput in = pileup_input(c, "read_pileup");
     const int64_t M = in.M, n = in.n, n4 = 4 * n;
     ELBA_REQUIRE(M < 0x7fffffff && n4 + M < 0xfffffff0ll, ELBA_ERR_UNSUPPORTED, "read_pileup: more than 2^31 reads or 2^30 pairs");
+    accepted(c.v, EV_READ_PILEUP);
     hipStream_t s = c.stream;
     int mb = 1, pb = 1;
     while ((1ll << mb) < M + 1) ++mb;
@@ -350,15 +342,17 @@ void stage_read_pileup(Ctx &c, const elba_pileup_cfg &cfg)
     st.nreads = M; st.pairs = (int64_t)h[0]; st.intervals = (int64_t)h[1]; st.segments = (int64_t)h[3]; st.max_depth = (int64_t)h[4];
     st.unsupported = (int64_t)h[5]; st.split = (int64_t)h[6]; st.trimmed = (int64_t)h[7]; st.trimmed_bases = (int64_t)h[8];
     st.ms_total = c.pu_t_total.ms();
-    c.pu_M = M; c.pu_nseg = st.segments; c.pu_n = n; c.pustats = st; c.pu_cfg = cfg; c.have_pileup = true;
+    c.pu_M = M; c.pu_nseg = st.segments; c.pu_n = n; c.pustats = st; c.pu_cfg = cfg; done(c.v, EV_READ_PILEUP);
 }
 
 void stage_prune_reads(Ctx &c, int mask, int64_t *kept)
 {
+    enter(c.v, EV_PRUNE_READS);
     ELBA_REQUIRE(mask >= 0 && mask <= 255, ELBA_ERR_INVALID_ARG, "prune_reads: mask must fit in one byte");
-    ELBA_REQUIRE(c.have_pileup, ELBA_ERR_STATE, "prune_reads: no pileup of the current overlaps (call elba_read_pileup)");
+    ELBA_REQUIRE(has(c.v, P_PILEUP), ELBA_ERR_STATE, "prune_reads: no pileup of the current overlaps (call elba_read_pileup)");
     const PuInput in = pileup_input(c, "prune_reads");
     ELBA_REQUIRE(in.M == c.pu_M && in.n == c.pu_n, ELBA_ERR_STATE, "prune_reads: the pileup was computed on other overlaps");
+    accepted(c.v, EV_PRUNE_READS);
     hipStream_t s = c.stream;
     const int64_t n = in.n;
     c.pu_sel.reserve((size_t)(2 * n + 4) * 4);
@@ -375,8 +369,8 @@ void stage_prune_reads(Ctx &c, int mask, int64_t *kept)
     ELBA_HIP(hipStreamSynchronize(s));
     // the kept pairs become the loaded edge list (elba_set_overlaps' buffers); the context's own alignments stay as they are
     c.tr_in_rows.swap(c.pu_rows); c.tr_in_cols.swap(c.pu_cols); c.tr_in_vals.swap(c.pu_vals);
-    c.tr_in_M = in.M; c.tr_in_n = total; c.have_edges = true;
-    c.have_S = false; c.have_contigs = false; c.have_pileup = false;
+    c.tr_in_M = in.M; c.tr_in_n = total;
+    done(c.v, EV_PRUNE_READS);
     if (kept) *kept = total;
 }
 

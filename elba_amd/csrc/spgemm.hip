@@ -929,7 +929,6 @@ static void ov_finish_stats(Ctx &c, OvCounters &hc, elba_overlap_stats &st, int 
     st.ms_total = ms_tot; st.ms_symbolic = ms_sym; st.ms_numeric = ms_num; st.ms_finalize = ms_fin;
     c.Y = Y;
     c.ostats = st;
-    c.have_B = true;
 }
 
 // The reads-path instantiation of the numeric kernel (OvSpecParams) runs a call whose every switch has the value that instantiation fixes: padded columns
@@ -965,7 +964,7 @@ static void create_seed_matrix_direct(Ctx &c, int phase)
     const int64_t row_lo = c.row_lo, row_hi = c.row_hi < 0 ? M : c.row_hi;
     elba_overlap_stats st{};
     st.nrows = row_hi - row_lo;
-    c.have_B = false;
+    accepted(c.v, phase == 0 ? EV_CREATE_SEED_MATRIX : phase == 1 ? EV_SEED_MATRIX_BEGIN : EV_SEED_MATRIX_SEND);
     c.ov_phase = 0;      // (a begun sharded call that was never ended is abandoned here: its staged records are about to be overwritten)
     ELBA_REQUIRE(M < 0xFFFFFF00ll, ELBA_ERR_UNSUPPORTED, "read ids beyond 2^32 - 256 (the top of the id range marks empty slots and idle lanes)");
     if (c.cold_calls) { c.ov_prior_q16 = 0; c.ov_slab_q16 = 0; c.ov_tiers_known = false; c.ov_sort_used[0] = c.ov_sort_used[1] = true; }
@@ -1234,6 +1233,7 @@ static void create_seed_matrix_direct(Ctx &c, int phase)
     if (phase == 1) { c.ov_pend_passes = passes; c.ov_pend_timed = was_timed; c.ov_pend_ms[0] = ms_tot; c.ov_pend_ms[1] = ms_sym; c.ov_pend_ms[2] = ms_num; c.ov_phase = 1; return; }
 
     ov_finish_stats(c, hc, st, passes, was_timed, ms_tot, ms_sym, ms_num, ms_fin, 0, 0);
+    done(c.v, EV_CREATE_SEED_MATRIX);
 }
 
 
@@ -1250,7 +1250,8 @@ static RemoteParams remote_params(Ctx &c)
 
 void stage_seed_matrix_begin(Ctx &c, int nranks, const uint64_t *bounds_host, uint64_t *send_counts_host)
 {
-    ELBA_REQUIRE(c.have_A, ELBA_ERR_STATE, "seed_matrix_begin: no k-mer matrix");
+    enter(c.v, EV_SEED_MATRIX_BEGIN);
+    ELBA_REQUIRE(has(c.v, P_A), ELBA_ERR_STATE, "seed_matrix_begin: no k-mer matrix");
     ELBA_REQUIRE(nranks >= 1 && nranks <= REMOTE_MAX_RANKS && bounds_host && send_counts_host, ELBA_ERR_INVALID_ARG, "seed_matrix_begin: 1..64 ranks, read bounds and a count array");
     const int64_t row_lo = c.row_lo, row_hi = c.row_hi < 0 ? c.M : c.row_hi;
     bool found = false;
@@ -1283,8 +1284,10 @@ void stage_seed_matrix_fill(Ctx &c, void *d_send, const uint64_t *offsets_host)
 
 void stage_seed_matrix_end(Ctx &c, const void *d_recv, int64_t nrecv)
 {
+    enter(c.v, EV_SEED_MATRIX_END);
     ELBA_REQUIRE(c.ov_phase == 1, ELBA_ERR_STATE, "seed_matrix_end: call seed_matrix_begin first");
     ELBA_REQUIRE(nrecv >= 0 && (nrecv == 0 || d_recv), ELBA_ERR_INVALID_ARG, "seed_matrix_end: null records");
+    accepted(c.v, EV_SEED_MATRIX_END);
     hipStream_t s = c.stream;
     const int64_t row_lo = c.row_lo, row_hi = c.row_hi < 0 ? c.M : c.row_hi;
     OvCounters &hc = *static_cast<OvCounters *>(c.ov_host.p);          // the numeric phase's counters (read back by begin)
@@ -1319,6 +1322,7 @@ void stage_seed_matrix_end(Ctx &c, const void *d_recv, int64_t nrecv)
     st.nrows = row_hi - row_lo;
     const float ms_fin = c.ov_marks.ms(2, 3);
     ov_finish_stats(c, hc, st, c.ov_pend_passes, c.ov_pend_timed, c.ov_pend_ms[0] + ms_fin, c.ov_pend_ms[1], c.ov_pend_ms[2], ms_fin, nrecv, (int64_t)chk[1]);
+    done(c.v, EV_SEED_MATRIX_END);
 }
 
 // ---- the same step with ONE host synchronisation: fixed-size slots, nothing about the exchange is known on the host ------------------------
@@ -1408,7 +1412,8 @@ __global__ void k_ingest_remote_slots(StageRec *rem, unsigned long long slot, ui
 
 void stage_seed_matrix_send(Ctx &c, int nranks, const uint64_t *bounds_host, void *d_send, int64_t slot)
 {
-    ELBA_REQUIRE(c.have_A, ELBA_ERR_STATE, "seed_matrix_send: no k-mer matrix");
+    enter(c.v, EV_SEED_MATRIX_SEND);
+    ELBA_REQUIRE(has(c.v, P_A), ELBA_ERR_STATE, "seed_matrix_send: no k-mer matrix");
     ELBA_REQUIRE(nranks >= 1 && nranks <= REMOTE_MAX_RANKS && bounds_host && d_send && slot >= 2, ELBA_ERR_INVALID_ARG, "seed_matrix_send: 1..64 ranks, read bounds, a send buffer of nranks slots of >= 2 records");
     const int64_t row_lo = c.row_lo, row_hi = c.row_hi < 0 ? c.M : c.row_hi;
     bool found = false;
@@ -1432,9 +1437,11 @@ void stage_seed_matrix_send(Ctx &c, int nranks, const uint64_t *bounds_host, voi
 // returns false when the step has to be repeated (this rank or any sender ran out of room; *slot_needed = the slot size that would have done)
 bool stage_seed_matrix_recv(Ctx &c, void *d_recv, int64_t slot, int64_t *slot_needed)
 {
+    enter(c.v, EV_SEED_MATRIX_RECV);
     ELBA_REQUIRE(c.ov_phase == 2, ELBA_ERR_STATE, "seed_matrix_recv: call seed_matrix_send first");
     ELBA_REQUIRE(d_recv && slot >= 2, ELBA_ERR_INVALID_ARG, "seed_matrix_recv: null records");
     ELBA_REQUIRE(slot == c.ov_send_slot, ELBA_ERR_INVALID_ARG, "seed_matrix_recv: slot_records differs from the value given to seed_matrix_send");
+    accepted(c.v, EV_SEED_MATRIX_RECV);
     hipStream_t s = c.stream;
     const int64_t row_lo = c.row_lo, row_hi = c.row_hi < 0 ? c.M : c.row_hi;
     const int nranks = (int)c.ov_remote_bounds.size() - 1;
@@ -1475,12 +1482,14 @@ bool stage_seed_matrix_recv(Ctx &c, void *d_recv, int64_t slot, int64_t *slot_ne
     st.nrows = row_hi - row_lo;
     const float ms_sym = c.ov_pend_timed ? c.ov_marks.ms(0, 1) : 0.f, ms_num = c.ov_pend_timed ? c.ov_marks.ms(1, 2) : 0.f, ms_fin = c.ov_marks.ms(4, 3);
     ov_finish_stats(c, hc, st, 1, c.ov_pend_timed, c.ov_pend_timed ? c.ov_marks.ms(0, 3) : ms_fin, ms_sym, ms_num, ms_fin, (int64_t)hchk[4], (int64_t)hchk[1]);
+    done(c.v, EV_SEED_MATRIX_RECV);
     return true;
 }
 
 void stage_create_seed_matrix(Ctx &c)
 {
-    ELBA_REQUIRE(c.have_A, ELBA_ERR_STATE, "create_seed_matrix: no k-mer matrix (call elba_create_kmer_matrix or elba_set_kmer_matrix)");
+    enter(c.v, EV_CREATE_SEED_MATRIX);
+    ELBA_REQUIRE(has(c.v, P_A), ELBA_ERR_STATE, "create_seed_matrix: no k-mer matrix (call elba_create_kmer_matrix or elba_set_kmer_matrix)");
     create_seed_matrix_direct(c, 0);
 }
 

@@ -170,18 +170,20 @@ __global__ __launch_bounds__(TP_THREADS) void k_tip_scatter(const int64_t *rows,
 
 }  // namespace
 
-void stage_clip_tips(Ctx &c, const elba_tip_cfg &cfg)
+void stage_clip_tips(Ctx &c, const elba_tip_cfg *cfgp)
 {
-    ELBA_REQUIRE(c.have_S, ELBA_ERR_STATE, "clip_tips: no string graph (call elba_transitive_reduction)");
+    enter(c.v, EV_CLIP_TIPS);
+    ELBA_REQUIRE(has(c.v, P_S), ELBA_ERR_STATE, "clip_tips: no string graph (call elba_transitive_reduction)");
+    ELBA_REQUIRE(cfgp, ELBA_ERR_INVALID_ARG, "clip_tips: null cfg");
+    const elba_tip_cfg &cfg = *cfgp;
     ELBA_REQUIRE(cfg.max_tip_reads >= 1 && cfg.max_tip_reads <= 65535, ELBA_ERR_INVALID_ARG, "clip_tips: max_tip_reads outside 1 .. 65535");
     ELBA_REQUIRE(cfg.rounds >= 1 && cfg.rounds <= TP_MAX_ROUNDS, ELBA_ERR_INVALID_ARG, "clip_tips: rounds outside 1 .. 64");
     ELBA_REQUIRE(!cfg.reserved[0] && !cfg.reserved[1], ELBA_ERR_INVALID_ARG, "clip_tips: reserved words must be 0");
     const int64_t M = c.tr_M, n0 = c.tr_nnz;
     ELBA_REQUIRE(M < 0xffffffffll && n0 < 0xfffffffell, ELBA_ERR_UNSUPPORTED, "clip_tips: index ranges beyond 32 bit");
-    c.have_contigs = false;                                     // S changes under the contigs of the old one
     elba_tip_stats st{};
     st.nreads = M; st.nnz_before = n0; st.nnz_after = n0; st.rounds_run = 1;
-    if (M == 0 || n0 == 0) { c.tpstats = st; return; }          // no entry: no dead end, the one round removes nothing
+    if (M == 0 || n0 == 0) { accepted(c.v, EV_CLIP_TIPS); done(c.v, EV_CLIP_TIPS); c.tpstats = st; return; }      // no entry: no dead end, the one round removes nothing
     hipStream_t s = c.stream;
     // every buffer of the launch sequence before the first launch
     c.tp_ptr.reserve((size_t)(M + 2) * 4); c.tp_ntips.reserve((size_t)(M + 1) * 4); c.tp_anchor.reserve((size_t)(M + 1) * 4); c.tp_removed.reserve((size_t)(M + 1) * 4);
@@ -196,7 +198,8 @@ void stage_clip_tips(Ctx &c, const elba_tip_cfg &cfg)
     const int64_t lanes = M > n0 + 1 ? M : n0 + 1;
     const unsigned nbB = (unsigned)((lanes + TP_THREADS - 1) / TP_THREADS), nbM = (unsigned)((M + TP_THREADS - 1) / TP_THREADS);
     const unsigned nbK = (unsigned)((n0 + 1 + TP_THREADS - 1) / TP_THREADS), nbS = (unsigned)((n0 + TP_TILE - 1) / TP_TILE);
-    c.have_S = false;                                           // until the counters are back: a call that fails below leaves no S rather than one in the wrong buffer
+    accepted(c.v, EV_CLIP_TIPS);                                // S changes under the contigs of the old one, and is itself invalid until the counters are back:
+                                                                // a call that fails below leaves no S rather than one in the wrong buffer
     c.tp_t_total.start(s);
     ELBA_HIP(hipMemsetAsync(dst, 0, TP_ST * 8, s));
     ELBA_HIP(hipMemsetAsync(removed, 0, (size_t)(M + 1) * 4, s));
@@ -227,7 +230,7 @@ void stage_clip_tips(Ctx &c, const elba_tip_cfg &cfg)
     }
     if (moves & 1) { c.tr_out_rows.swap(c.tp_rows); c.tr_out_cols.swap(c.tp_cols); c.tr_out_vals.swap(c.tp_vals); }
     c.tr_nnz = (int64_t)h[TP_NNZ + moves];
-    c.have_S = true;
+    done(c.v, EV_CLIP_TIPS);
     st.nnz_after = c.tr_nnz; st.entries_removed = n0 - c.tr_nnz;
     st.dead_ends = (int64_t)h[TP_DEAD]; st.tips = (int64_t)h[TP_TIPS]; st.reads_removed = (int64_t)h[TP_READS]; st.spared_anchors = (int64_t)h[TP_SPARED];
     st.rounds_run = moves < cfg.rounds ? moves + 1 : cfg.rounds;

@@ -227,6 +227,7 @@ __global__ void k_tr_scatter(const uint64_t *keys, const uint64_t *kv, const uin
 
 void stage_set_overlaps(Ctx &c, int64_t nreads, const int64_t *rows, const int64_t *cols, const elba_overlap_t *vals, int64_t n)
 {
+    enter(c.v, EV_SET_OVERLAPS);
     ELBA_REQUIRE(nreads >= 0 && n >= 0 && (n == 0 || (rows && cols && vals)), ELBA_ERR_INVALID_ARG, "set_overlaps: null array");
     ELBA_REQUIRE(nreads < 0x7fffffff && n < 0x7fffffff, ELBA_ERR_UNSUPPORTED, "set_overlaps: more than 2^31 reads or pairs");
     for (int64_t a = 0; a < n; ++a) {
@@ -234,7 +235,7 @@ void stage_set_overlaps(Ctx &c, int64_t nreads, const int64_t *rows, const int64
         if (a) ELBA_REQUIRE(rows[a - 1] < rows[a] || (rows[a - 1] == rows[a] && cols[a - 1] < cols[a]), ELBA_ERR_INVALID_ARG, "set_overlaps: pairs must be strictly ascending in (row, col)");
     }
     hipStream_t s = c.stream;
-    c.have_edges = false; c.have_S = false;
+    accepted(c.v, EV_SET_OVERLAPS);
     c.tr_in_rows.reserve((size_t)(n + 1) * 8); c.tr_in_cols.reserve((size_t)(n + 1) * 8); c.tr_in_vals.reserve((size_t)(n + 1) * sizeof(elba_overlap_t));
     if (n) {
         ELBA_HIP(hipMemcpyAsync(c.tr_in_rows.p, rows, (size_t)n * 8, hipMemcpyHostToDevice, s));
@@ -242,27 +243,22 @@ void stage_set_overlaps(Ctx &c, int64_t nreads, const int64_t *rows, const int64
         ELBA_HIP(hipMemcpyAsync(c.tr_in_vals.p, vals, (size_t)n * sizeof(elba_overlap_t), hipMemcpyHostToDevice, s));
     }
     ELBA_HIP(hipStreamSynchronize(s));
-    c.tr_in_M = nreads; c.tr_in_n = n; c.have_edges = true;
+    c.tr_in_M = nreads; c.tr_in_n = n;
+    done(c.v, EV_SET_OVERLAPS);
 }
 
 void stage_transitive_reduction(Ctx &c, double bad_read_cutoff, int fuzz)
 {
+    enter(c.v, EV_TRANSITIVE_REDUCTION);                        // (a new S invalidates the contigs of the old one, whatever this call ends in)
+    const GraphInput in = graph_input(c, "transitive_reduction");
+    const int64_t M = in.M, n = in.n;
+    c.tr_id_base = in.id_base;
     TrParams p{};
-    int64_t M, n;
-    if (c.have_edges) {
-        M = c.tr_in_M; n = c.tr_in_n; c.tr_id_base = 0;
-        p.rows = c.tr_in_rows.as<int64_t>(); p.cols = c.tr_in_cols.as<int64_t>(); p.vals = c.tr_in_vals.as<elba_overlap_t>();
-    } else {
-        ELBA_REQUIRE(c.have_aln, ELBA_ERR_STATE, "transitive_reduction: no overlaps (call elba_align_seeds or elba_set_overlaps)");
-        ELBA_REQUIRE(c.row_hi < 0 || (c.row_lo == 0 && c.row_hi == c.M), ELBA_ERR_STATE,
-                     "transitive_reduction: this context aligned a row shard; gather the ranks' overlaps and load them with elba_set_overlaps");
-        M = c.M; n = c.naln; c.tr_id_base = c.first_global_id_rows();
-        p.rows = c.aln_rows.as<int64_t>(); p.cols = c.aln_cols.as<int64_t>(); p.vals = c.aln_out.as<elba_overlap_t>();
-    }
+    p.rows = in.rows; p.cols = in.cols; p.vals = in.vals;
     ELBA_REQUIRE(fuzz >= 0, ELBA_ERR_INVALID_ARG, "transitive_reduction: negative fuzz");
     ELBA_REQUIRE(M < 0x7fffffff && n < 0x7fffffff, ELBA_ERR_UNSUPPORTED, "transitive_reduction: more than 2^31 reads or pairs");
     hipStream_t s = c.stream;
-    c.have_S = false;
+    accepted(c.v, EV_TRANSITIVE_REDUCTION);
     elba_string_stats st{};
     st.nreads = M; st.nedges = n;
     int mb = 1;
@@ -329,7 +325,7 @@ void stage_transitive_reduction(Ctx &c, double bad_read_cutoff, int fuzz)
     st.products = (int64_t)h[4]; st.marked = (int64_t)h[5]; st.removed = (int64_t)h[6]; st.nnz = nnz;
     st.iterations = st.removed > 0 ? 2 : 1;
     st.ms_total = c.t_total.ms(); st.ms_minplus = ms_mark;
-    c.tr_M = M; c.tr_nnz = nnz; c.sstats = st; c.have_S = true;
+    c.tr_M = M; c.tr_nnz = nnz; c.sstats = st; done(c.v, EV_TRANSITIVE_REDUCTION);
 }
 
 }  // namespace elba

@@ -170,26 +170,20 @@ __global__ __launch_bounds__(TRIM_THREADS) void k_trim_repack(const uint8_t *__r
     out[w] = __builtin_bswap64(W);
 }
 
-// the packed bases of reads 0 .. M-1: the replicated set when it holds M reads, else the context's own (the choice pileup_input makes for the lengths)
-struct TrimSource { const uint8_t *packed; const uint64_t *byte_off; const uint32_t *len; };
-TrimSource trim_source(Ctx &c, int64_t M)
-{
-    if (c.aln_all_n == M && c.aln_all_n >= 0) return {c.aln_all_packed.as<uint8_t>(), c.aln_all_off.as<uint64_t>(), c.aln_all_len.as<uint32_t>()};
-    if (c.have_reads && c.nreads == M) return {c.d_packed, c.d_byte_off, c.d_len};
-    throw Error{ELBA_ERR_STATE, "trim_reads: the bases of the pileup's " + std::to_string(M) + " reads are not on this context (elba_set_reads or elba_dist_set_all_reads)"};
-}
-
 }  // namespace
 
-void stage_trim_reads(Ctx &c, const elba_trim_cfg &cfg)
+void stage_trim_reads(Ctx &c, const elba_trim_cfg *cfgp)
 {
-    c.have_trim = false;
+    enter(c.v, EV_TRIM_READS);
+    ELBA_REQUIRE(cfgp, ELBA_ERR_INVALID_ARG, "trim_reads: null cfg");
+    const elba_trim_cfg &cfg = *cfgp;
     ELBA_REQUIRE(cfg.mode == 0 || cfg.mode == 1, ELBA_ERR_INVALID_ARG, "trim_reads: mode must be 0 (trimmed intervals) or 1 (long runs)");
     ELBA_REQUIRE(cfg.min_len >= 1, ELBA_ERR_INVALID_ARG, "trim_reads: need min_len >= 1");
     ELBA_REQUIRE(cfg.reserved[0] == 0 && cfg.reserved[1] == 0, ELBA_ERR_INVALID_ARG, "trim_reads: reserved words must be 0");
-    ELBA_REQUIRE(c.have_pileup, ELBA_ERR_STATE, "trim_reads: no pileup of the current overlaps (call elba_read_pileup)");
+    ELBA_REQUIRE(has(c.v, P_PILEUP), ELBA_ERR_STATE, "trim_reads: no pileup of the current overlaps (call elba_read_pileup)");
     const int64_t M = c.pu_M;
-    const TrimSource in = trim_source(c, M);
+    const ReadSource in = read_source(c, M, "trim_reads", "bases of the pileup's # reads");
+    accepted(c.v, EV_TRIM_READS);
     hipStream_t s = c.stream;
     TrimParams p{};
     p.seg_off = c.pu_seg_off.as<int64_t>(); p.seg_start = c.pu_seg_start.as<int32_t>(); p.seg_depth = c.pu_seg_depth.as<int32_t>(); p.trim = c.pu_trim.as<int2>();
@@ -233,13 +227,13 @@ void stage_trim_reads(Ctx &c, const elba_trim_cfg &cfg)
     st.nreads_in = M; st.pieces = n; st.reads_dropped = (int64_t)h[1]; st.reads_split = (int64_t)h[2]; st.reads_unchanged = (int64_t)h[3];
     st.bases_in = (int64_t)h[4]; st.bases_out = (int64_t)h[5]; st.packed_bytes = pb; st.longest = (int64_t)h[7];
     st.ms_total = c.tm_t_total.ms(); st.ms_repack = c.tm_t_repack.ms();
-    c.tm_n = n; c.tm_packed_bytes = pb; c.tmstats = st; c.have_trim = true;
+    c.tm_n = n; c.tm_packed_bytes = pb; c.tmstats = st; done(c.v, EV_TRIM_READS);
 }
 
 // the pieces become the context's own reads, exactly as after elba_set_reads
 void stage_adopt_trimmed_reads(Ctx &c)
 {
-    ELBA_REQUIRE(c.have_trim, ELBA_ERR_STATE, "adopt_trimmed_reads: no trimmed reads (call elba_trim_reads)");
+    ELBA_REQUIRE(has(c.v, P_TRIM), ELBA_ERR_STATE, "adopt_trimmed_reads: no trimmed reads (call elba_trim_reads)");
     hipStream_t s = c.stream;
     const int64_t n = c.tm_n;
     std::vector<uint32_t> hl((size_t)n);
@@ -249,12 +243,11 @@ void stage_adopt_trimmed_reads(Ctx &c)
         ELBA_HIP(hipMemcpyAsync(ho.data(), c.tm_off.p, (size_t)n * 8, hipMemcpyDeviceToHost, s));
     }
     ELBA_HIP(hipStreamSynchronize(s));
-    c.have_trim = false;
     c.own_packed.swap(c.tm_packed); c.own_byte_off.swap(c.tm_off); c.own_len.swap(c.tm_len);
     c.d_packed = c.own_packed.as<uint8_t>(); c.d_byte_off = c.own_byte_off.as<uint64_t>(); c.d_len = c.own_len.as<uint32_t>();
     c.h_len.swap(hl); c.h_byte_off.swap(ho);
     c.nreads = n; c.first_global_id = 0; c.packed_bytes = c.tm_packed_bytes;
-    reads_replaced(c);
+    reads_replaced(c, EV_ADOPT_TRIMMED_READS);
 }
 
 }  // namespace elba

@@ -1,0 +1,35 @@
+// test_state_table — walks csrc/state.hpp's table without the library: every argument is an event name, optionally suffixed
+// ":reject" or ":state" (the call is refused for its arguments / for what the context holds: only `enter` applies) or ":fail" (it
+// fails after its checks have passed: `enter` and `accepted`).
+// Prints one line per event: the event as given, the mask in hex, the valid products by name (tests/test_state_cpu.py reads them).
+#include "../csrc/state.hpp"
+#include <cstdio>
+#include <cstring>
+#include <string>
+
+using namespace elba;
+
+static const char *const PRODUCT_NAMES[P_COUNT] = {"reads", "counts", "A", "B", "aln", "edges", "S", "contigs", "pileup", "trim"};
+
+int main(int argc, char **argv)
+{
+    if (argc == 2 && !strcmp(argv[1], "--events")) {
+        for (const Row &r : TABLE) printf("%s\n", r.name);
+        return 0;
+    }
+    Validity v;
+    for (int a = 1; a < argc; ++a) {
+        const std::string arg = argv[a], name = arg.substr(0, arg.find(':')), how = arg.size() > name.size() ? arg.substr(name.size() + 1) : "";
+        const Row *row = nullptr;
+        for (const Row &r : TABLE) if (name == r.name) row = &r;
+        const bool refused = how == "reject" || how == "state";
+        if (!row || (how != "" && !refused && how != "fail")) { fprintf(stderr, "test_state_table: unknown event or ending '%s'\n", argv[a]); return 2; }
+        enter(v, row->ev);
+        if (!refused) accepted(v, row->ev);
+        if (how == "") done(v, row->ev);
+        printf("%s 0x%03x", argv[a], (unsigned)v.bits);
+        for (unsigned p = 0; p < P_COUNT; ++p) if (has(v, (Product)p)) printf(" %s", PRODUCT_NAMES[p]);
+        printf("\n");
+    }
+    return 0;
+}

@@ -248,6 +248,13 @@ int  elba_set_reads_fasta(elba_ctx *ctx, const char *chunk, int64_t chunk_bytes,
 /* The resident reads back on the host in DnaBuffer layout: packed[packed_bytes], byte_off[nreads], len[nreads] (caller-allocated;
  * any pointer may be NULL to skip it).  Sizes: elba_ingest_stats, or nreads and sum((len+3)/4). */
 int  elba_export_reads(elba_ctx *ctx, uint8_t *packed, int64_t packed_capacity, uint64_t *byte_off, uint32_t *len, int64_t nreads_capacity);
+/* What a call invalidates is decided in one table, elba_amd/csrc/state.hpp.  The rule of the matrices: a call that replaces A or B —
+ * elba_count_kmers, elba_create_kmer_matrix, elba_set_kmer_matrix[_device], elba_create_seed_matrix, elba_seed_matrix_begin / _send,
+ * elba_dist_count_records, elba_dist_set_panel — invalidates B, the alignments of the old B and the pileup, and with them the string graph
+ * and its contigs unless the graph was built from an edge list loaded with elba_set_overlaps (or left by elba_prune_reads), which stays
+ * loaded.  All but the seed-matrix calls also invalidate A as soon as their arguments are accepted, so one that fails later
+ * leaves no A; elba_count_kmers, elba_dist_count_records and elba_set_kmer_matrix[_device] invalidate the k-mer counts as well (the
+ * triples land where the counted columns live).  Calls that need what is gone return ELBA_ERR_STATE. */
 int  elba_count_kmers(elba_ctx *ctx, elba_kmer_stats *stats);
 int  elba_create_kmer_matrix(elba_ctx *ctx, elba_matrix_stats *stats);
 
@@ -299,8 +306,9 @@ int  elba_export_read_flags(elba_ctx *ctx, uint8_t *flags, int64_t nreads);
  * strand bit is set): prefix = suffixT of the walk's S(cur, next), the whole read for the last one.  Contigs come in the reference's emission
  * order (ascending start read).  Cycles emit nothing.  The reads 0 .. nreads-1 of the graph must be on the context: its own reads
  * (elba_set_reads*, as many as the graph has) or the replicated set of elba_dist_set_all_reads; otherwise ELBA_ERR_STATE.  A prefix outside
- * [0, len] (undefined behaviour in the reference) fails with ELBA_ERR_INVALID_ARG and leaves no contigs.  elba_transitive_reduction and
- * every new read set invalidate the contigs.  The writer (formats.write_contigs_fasta, hostcpp parallel_write_contigs) writes ">contig<i>\n<seq>\n" per contig (src/main.cpp:496-499). */
+ * [0, len] (undefined behaviour in the reference) fails with ELBA_ERR_INVALID_ARG and leaves no contigs.  elba_transitive_reduction, every
+ * new read set and a replaced A or B under a graph of this context's own alignments invalidate the contigs: the exports and the contig_*
+ * counters of elba_get_stat answer only while both the graph and its contigs are valid.  The writer (formats.write_contigs_fasta, hostcpp parallel_write_contigs) writes ">contig<i>\n<seq>\n" per contig (src/main.cpp:496-499). */
 typedef struct {
     int64_t nreads, branches, components;   /* components: CC's count on S without the branches' edges, size-1 components included (:51) */
     int64_t used_components;                /* components of >= 2 reads (:110): contigs + cycles */
@@ -401,7 +409,7 @@ int  elba_clip_tips(elba_ctx *ctx, const elba_tip_cfg *cfg, elba_tip_stats *stat
  * Two deliberate deviations from the reference: both reads of a pair are credited (GetReadPileup credits only the column read of the
  * upper-triangular R, :137-146), and the trimmed interval is the best run (the reference returns the run still open at the last base, :68).
  * elba_prune_reads removes every pair with either end in {v : flags[v] & mask} and loads the kept pairs, in (row, col) order, as the edge
- * list elba_transitive_reduction reads next (elba_export_overlaps still returns the alignments).  A new read set, new alignments,
+ * list elba_transitive_reduction reads next (elba_export_overlaps still returns the alignments).  A new read set, a replaced A or B, new alignments,
  * elba_set_overlaps and elba_prune_reads invalidate the pileup (ELBA_ERR_STATE on export). */
 typedef struct {
     int32_t mode;               /* 0: pairs with passed; 1: every pair with score > 0 */
@@ -534,7 +542,10 @@ int  elba_set_option(elba_ctx *ctx, const char *name, int64_t value);
  *   "overlap_forwarded"      rows that call forwarded to a larger table tier on its in-call prediction (cold calls without a sample), all passes
  *   "spgemm_prep_us"         option "measure_prep": device microseconds the emit kernels of the last elba_count_kmers spent on hint bits, inline partners,
  *                            gather slots and padded columns (the kernels as built minus the same kernels without them; -1: not measured)
- *   "emit_us"                ... and the emit kernels as built */
+ *   "emit_us"                ... and the emit kernels as built
+ *   "contig_count", "contig_cycles", "contig_circular", "contig_singletons", "contig_reads", "contig_bases", "contig_branches"
+ *                            the last elba_generate_contigs[_ex], under the condition of the contig exports: 0 when the string graph or its
+ *                            contigs are not valid ("contig_rank_us": -1) */
 int  elba_get_stat(elba_ctx *ctx, const char *name, int64_t *value);
 
 /* Gives the stage calls' scratch memory back to the device (the sort / partition buffers of elba_count_kmers, elba_create_kmer_matrix and
