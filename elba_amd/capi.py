@@ -135,6 +135,16 @@ class TipStats(C.Structure):
                 ("ms_total", C.c_float), ("ms_compact", C.c_float)]
 
 
+class BubbleCfg(C.Structure):
+    _fields_ = [("max_arm_reads", C.c_int32), ("rounds", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class BubbleStats(C.Structure):
+    _fields_ = [("nreads", C.c_int64), ("nnz_before", C.c_int64), ("nnz_after", C.c_int64), ("anchors", C.c_int64), ("arms", C.c_int64), ("bubbles", C.c_int64),
+                ("arms_removed", C.c_int64), ("reads_removed", C.c_int64), ("entries_removed", C.c_int64), ("rounds_run", C.c_int32), ("reserved", C.c_int32),
+                ("ms_total", C.c_float), ("ms_compact", C.c_float)]
+
+
 class Overlaps(C.Structure):
     _fields_ = [("n", C.c_int64), ("rows", C.c_void_p), ("cols", C.c_void_p), ("vals", C.c_void_p)]
 
@@ -189,7 +199,7 @@ EXPORTED_SYMBOLS = [
     "elba_generate_contigs", "elba_export_contigs", "elba_free_contigs", "elba_export_read_contigs", "elba_generate_contigs_ex", "elba_export_contig_kinds",
     "elba_read_pileup", "elba_export_pileup", "elba_free_pileup", "elba_prune_reads",
     "elba_trim_reads", "elba_export_trim_map", "elba_free_trim_map", "elba_get_trimmed_reads_device", "elba_adopt_trimmed_reads",
-    "elba_clip_tips",
+    "elba_clip_tips", "elba_pop_bubbles",
 ]
 
 _lib = None
@@ -240,6 +250,7 @@ def load_library():
     L.elba_export_string_graph.restype = i32; L.elba_export_string_graph.argtypes = [vp, C.POINTER(Overlaps)]
     L.elba_export_read_flags.restype = i32; L.elba_export_read_flags.argtypes = [vp, vp, i64]
     L.elba_clip_tips.restype = i32; L.elba_clip_tips.argtypes = [vp, C.POINTER(TipCfg), C.POINTER(TipStats)]
+    L.elba_pop_bubbles.restype = i32; L.elba_pop_bubbles.argtypes = [vp, C.POINTER(BubbleCfg), C.POINTER(BubbleStats)]
     L.elba_generate_contigs.restype = i32; L.elba_generate_contigs.argtypes = [vp, C.POINTER(ContigStats)]
     L.elba_generate_contigs_ex.restype = i32; L.elba_generate_contigs_ex.argtypes = [vp, C.POINTER(ContigCfg), C.POINTER(ContigStats)]
     L.elba_export_contig_kinds.restype = i32; L.elba_export_contig_kinds.argtypes = [vp, vp, i64]
@@ -472,7 +483,7 @@ class Engine:
             self.L.elba_free_overlaps(C.byref(o))
 
     def export_read_flags(self, nreads):
-        """One byte per read: bit 0 = bad read, bit 1 = contained read, bit 2 = removed by clip_tips."""
+        """One byte per read: bit 0 = bad read, bit 1 = contained read, bit 2 = removed by clip_tips, bit 3 = removed by pop_bubbles."""
         f = np.zeros(int(nreads), dtype=np.uint8)
         self._check(self.L.elba_export_read_flags(self.h, f.ctypes.data, int(nreads)))
         return f
@@ -487,6 +498,30 @@ class Engine:
         d = _stats(st)
         d.pop("reserved", None)
         return d
+
+    # --- bubble popping (between transitive_reduction and generate_contigs, before or after clip_tips; not in the reference) ---
+    def pop_bubbles(self, max_arm_reads, rounds=1):
+        """Where two or more chains of at most max_arm_reads reads of degree 2 join the same two reads of degree >= 3, keeps the one with the
+        most reads (on a tie the one whose first read is smallest) and removes the others from the string graph, in up to `rounds` rounds.
+        Removed reads get flag 8.  Returns the stats."""
+        cfg = BubbleCfg(int(max_arm_reads), int(rounds), (C.c_int32 * 2)(0, 0))
+        st = BubbleStats()
+        self._check(self.L.elba_pop_bubbles(self.h, C.byref(cfg), C.byref(st)))
+        d = _stats(st)
+        d.pop("reserved", None)
+        return d
+
+    def simplify_graph(self, max_tip_reads, max_arm_reads, passes=16):
+        """clip_tips(max_tip_reads, 64) then pop_bubbles(max_arm_reads, 64), again and again until a pass of both removes nothing or `passes`
+        passes have run.  pop_bubbles alone does not reach that fixed point: a tip on an arm gives the arm a read of degree 3, so there is
+        no arm until the tip is clipped.  (A pop makes no new tip on a symmetric graph — it lowers anchors to degree 2, which only lengthens
+        dead-end chains — so the second pass is the one that finds nothing.)  Returns [(tip stats, bubble stats)], one pair per pass."""
+        out = []
+        for _ in range(int(passes)):
+            out.append((self.clip_tips(max_tip_reads, 64), self.pop_bubbles(max_arm_reads, 64)))
+            if out[-1][0]["reads_removed"] == 0 and out[-1][1]["reads_removed"] == 0:
+                break
+        return out
 
     # --- contigs (src/ContigGeneration.cpp:18-51,110,376-457, one rank) ---
     def generate_contigs(self, circular=False, singletons=False):

@@ -1,0 +1,186 @@
+// bubbles.hip — popping simple bubbles in the string graph (elba_pop_bubbles): not in the reference, whose GenerateContigs drops every read
+// of degree > 2 with its edges, so that two short chains between the same two reads cut a path into four contigs and lose both end reads.
+//
+// Input and output: the S that tr.hip leaves on the context (tr_out_*), column-major, both triangles, as for tips.hip.  The rule is stated on
+// columns alone: deg(v) = length of column v, the neighbours of v = the rows of column v (ascending).  One ROUND, on the degrees as it finds them:
+//   anchor     a read of degree >= 3
+//   arm        for an entry z of a column a that is an anchor, whose row v1 has degree 2: the walk of tips.hip from v1, "came from" = a; from
+//              vi of degree 2 it goes on to the smaller row of column vi that is not v(i-1).  The first read b of degree >= 3 ends it: v1 ..
+//              vt, 1 <= t <= max_arm_reads, is an arm of t reads from a to b — if b > a (the arm is recorded at its smaller anchor; b == a, a
+//              chain back to a, is no arm).  A read of degree 0 or 1 ends it too (no arm), and so does read max_arm_reads + 1 (too long)
+//   bubble     the arms with the same (a, b), when there are two or more
+//   kept arm   the one with the most reads; among those the one with the smallest entry z (= the smallest first read: rows ascend in a column)
+//   removal    the reads of every other arm of a bubble go: every entry whose row or column is one of them leaves S, the others keep their
+//              values and their order.  An entry a - b itself is no arm and stays
+// Everything a round decides is read from tables frozen when it starts (ptr, then arm_end / arm_len, which k_bub_pick only reads) and what it
+// writes are sets (removed) and sums: the order in which the lanes run does not show in the result.
+//
+//   k_bub_begin     column pointers of the round's S from its column ids (nnz read on the device: sg_col_ptrs), arm_end = none, arm_len = 0
+//   k_bub_walk      one lane per entry z; if deg(col) >= 3 and deg(row) == 2 the lane walks at most max_arm_reads steps; at an anchor b > col
+//                   it writes arm_end[z] = b, arm_len[z] = t and counts an arm.  The first entry of every column of length >= 3 counts an
+//                   anchor (first round only)
+//   k_bub_pick      one lane per entry that holds an arm: it looks through column a's entries for arms with the same arm_end; it is the kept
+//                   arm if none has a larger (arm_len, -z); the kept lane of a group of >= 2 counts a bubble; every other lane walks its arm
+//                   again, arm_len reads: removed[vi] = 1 (atomicExch: the winner counts the read and sets flag bit 3), and counts a removed arm
+//   keep flags, scan, scatter: the compaction of sg_rounds.hpp (k_sg_keep, k_sg_scatter), shared with tips.hip
+//
+// The pick is quadratic per anchor: an arm costs deg(a) reads of arm_end (4 bytes, the same addresses for the lanes of a column, which are
+// neighbours: cached) and one of arm_len per arm of its group, so a pair of hubs joined by d arms costs d^2 of each.  The alternative, sorting
+// arm records by (a, b, len, z) with prims.hip's radix sort, costs four passes over 16-byte records and two more buffers for every round of
+// every call; after the reduction degrees are small (the layout graph of DESIGN 4.12: 3 or 4 at an anchor), so the scan of a column is a
+// handful of reads, and the sort would be the larger part of a round.  DESIGN 4.14 has what a hub of 3000 arms costs.
+//
+// Rounds without host synchronisation, in batches of four with one synchronisation per batch: the protocol of sg_rounds.hpp.  The rule's
+// part of it: every kernel here returns at once when the round before removed nothing, and k_bub_pick adds the reads it removed to
+// st[SG_LIVE + r + 1].
+//
+// Bounds: a lane works on an entry z < n, the round's nnz; ptr is built from n, so every column range lies in [0, n) and arm_end / arm_len
+// (n0 + 1 elements, n <= n0) are read and written below n; every read index is tested below M before ptr is read at it (rows and cols of S
+// are; the walks test cur < M again); a walk reads rows only from a column of length 2, at its two entries; k_bub_pick repeats a walk that
+// k_bub_walk finished on the same tables, for exactly arm_len steps; removed and flags are written at reads below M; the compaction's bounds
+// are in sg_rounds.hpp.
+// Bytes (algorithmic) per round: k_bub_begin 8 per entry read (column ids), 8 written (arm_end, arm_len), 4 x M of pointers written;
+// k_bub_walk 16 per entry read (row, column id) and the two pointers of its column; k_bub_pick 4 per entry read (arm_end): 36 x nnz + 4 x M,
+// the walks and the anchors' columns apart (they touch the arms only).  If the round removes something, the compaction's as well
+// (sg_rounds.hpp: 52 bytes per entry read, 52 per kept entry written, + 28).
+#include "sg_rounds.hpp"
+
+namespace elba {
+
+namespace {
+
+constexpr uint32_t BB_NONE = 0xffffffffu;
+constexpr int BB_THREADS = SG_THREADS;          // threads of every kernel here
+// st[]: 0 anchors (first round), 1 arms, 2 bubbles, 3 arms removed, 4 reads removed; the protocol's slots: sg_rounds.hpp
+enum { BB_ANCHORS = 0, BB_ARMS = 1, BB_BUBBLES = 2, BB_GONE = 3, BB_READS = 4 };
+static_assert(BB_READS < SG_LIVE, "the rule's counters lie in front of the protocol's");
+
+// one atomicAdd per wavefront for a count of lanes
+__device__ __forceinline__ void bb_count(u64 *slot, bool mine)
+{
+    const u64 b = __ballot(mine);
+    if (b && (threadIdx.x & 63) == (unsigned)__builtin_ctzll(b)) atomicAdd(slot, (u64)__builtin_popcountll(b));
+}
+
+__global__ void k_bub_begin(const int64_t *cols, const u64 *st, int r, uint32_t M, uint32_t *ptr, uint32_t *arm_end, uint32_t *arm_len)
+{
+    if (st[SG_LIVE + r] == 0) return;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t n = (int64_t)st[SG_NNZ + r];
+    if (i < n) { arm_end[i] = BB_NONE; arm_len[i] = 0; }
+    sg_col_ptrs(cols, n, M, i, ptr);
+}
+
+__global__ void k_bub_walk(const uint32_t *ptr, const int64_t *rows, const int64_t *cols, u64 *st, int r, uint32_t maxt, uint32_t M,
+                           uint32_t *arm_end, uint32_t *arm_len)
+{
+    if (st[SG_LIVE + r] == 0) return;
+    const int64_t z = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t n = (int64_t)st[SG_NNZ + r];
+    bool anchor = false, arm = false;
+    if (z < n) {
+        const uint32_t a = (uint32_t)cols[z], v1 = (uint32_t)rows[z];
+        if (a < M && v1 < M) {
+            const uint32_t as = ptr[a];
+            if (ptr[a + 1] - as >= 3) {
+                anchor = r == 0 && (int64_t)as == z;                    // once per anchor: at the first entry of its column
+                uint32_t prev = a, cur = v1, t = 0;                     // t reads in the chain so far
+                while (cur < M) {
+                    const uint32_t cs = ptr[cur], d = ptr[cur + 1] - cs;
+                    if (d >= 3) {                                       // b: an arm if it has a read, and is recorded here if a is the smaller anchor
+                        if (t >= 1 && cur > a) { arm_end[z] = cur; arm_len[z] = t; arm = true; }
+                        break;
+                    }
+                    if (d != 2 || t == maxt) break;                     // a dead end, or a chain longer than max_arm_reads
+                    const uint32_t x = (uint32_t)rows[cs];
+                    const uint32_t nx = x != prev ? x : (uint32_t)rows[cs + 1];
+                    prev = cur; cur = nx; ++t;
+                }
+            }
+        }
+    }
+    bb_count(&st[BB_ANCHORS], anchor);
+    bb_count(&st[BB_ARMS], arm);
+}
+
+__global__ void k_bub_pick(const uint32_t *ptr, const int64_t *rows, const int64_t *cols, u64 *st, int r, uint32_t M, const uint32_t *arm_end,
+                           const uint32_t *arm_len, uint32_t *removed, uint8_t *flags)
+{
+    if (st[SG_LIVE + r] == 0) return;
+    const int64_t z = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t n = (int64_t)st[SG_NNZ + r];
+    bool bubble = false, gone = false;
+    if (z < n) {
+        const uint32_t b = arm_end[z];
+        if (b != BB_NONE) {                                             // k_bub_walk found a = cols[z] < M, an anchor, and an arm of len reads to b
+            const uint32_t a = (uint32_t)cols[z], len = arm_len[z];
+            const uint32_t ys = ptr[a], ye = ptr[a + 1];
+            uint32_t group = 0;
+            bool kept = true;
+            for (uint32_t y = ys; y < ye; ++y) {
+                if (arm_end[y] != b) continue;
+                ++group;
+                const uint32_t ly = arm_len[y];
+                if (ly > len || (ly == len && y < (uint32_t)z)) kept = false;
+            }
+            bubble = kept && group >= 2;
+            gone = !kept;
+            if (gone) {                                                 // the walk of k_bub_walk again: it passed len reads of degree 2
+                uint32_t prev = a, cur = (uint32_t)rows[z], cnt = 0;
+                for (uint32_t i = 0; i < len && cur < M; ++i) {
+                    if (atomicExch(&removed[cur], 1u) == 0) { ++cnt; flags[cur] = (uint8_t)(flags[cur] | 8u); }
+                    const uint32_t cs = ptr[cur];
+                    if (ptr[cur + 1] - cs != 2) break;                  // (never: k_bub_walk went through here on the same tables)
+                    const uint32_t x = (uint32_t)rows[cs];
+                    const uint32_t nx = x != prev ? x : (uint32_t)rows[cs + 1];
+                    prev = cur; cur = nx;
+                }
+                if (cnt) { atomicAdd(&st[BB_READS], (u64)cnt); atomicAdd(&st[SG_LIVE + r + 1], (u64)cnt); }
+            }
+        }
+    }
+    bb_count(&st[BB_BUBBLES], bubble);
+    bb_count(&st[BB_GONE], gone);
+}
+
+}  // namespace
+
+void stage_pop_bubbles(Ctx &c, const elba_bubble_cfg *cfgp)
+{
+    enter(c.v, EV_POP_BUBBLES);
+    ELBA_REQUIRE(has(c.v, P_S), ELBA_ERR_STATE, "pop_bubbles: no string graph (call elba_transitive_reduction)");
+    ELBA_REQUIRE(cfgp, ELBA_ERR_INVALID_ARG, "pop_bubbles: null cfg");
+    const elba_bubble_cfg &cfg = *cfgp;
+    ELBA_REQUIRE(cfg.max_arm_reads >= 1 && cfg.max_arm_reads <= 65535, ELBA_ERR_INVALID_ARG, "pop_bubbles: max_arm_reads outside 1 .. 65535");
+    ELBA_REQUIRE(cfg.rounds >= 1 && cfg.rounds <= SG_MAX_ROUNDS, ELBA_ERR_INVALID_ARG, "pop_bubbles: rounds outside 1 .. 64");
+    ELBA_REQUIRE(!cfg.reserved[0] && !cfg.reserved[1], ELBA_ERR_INVALID_ARG, "pop_bubbles: reserved words must be 0");
+    const int64_t M = c.tr_M, n0 = c.tr_nnz;
+    ELBA_REQUIRE(M < 0xffffffffll && n0 < 0xfffffffell, ELBA_ERR_UNSUPPORTED, "pop_bubbles: index ranges beyond 32 bit");
+    elba_bubble_stats st{};
+    st.nreads = M; st.nnz_before = n0; st.nnz_after = n0; st.rounds_run = 1;
+    if (M == 0 || n0 == 0) { accepted(c.v, EV_POP_BUBBLES); done(c.v, EV_POP_BUBBLES); c.bbstats = st; return; }      // no entry: no anchor, the one round removes nothing
+    hipStream_t s = c.stream;
+    // every buffer of the launch sequence before the first launch
+    sg_reserve(c, M, n0);
+    c.bb_end.reserve((size_t)(n0 + 1) * 4); c.bb_len.reserve((size_t)(n0 + 1) * 4);
+    uint32_t *ptr = c.tp_ptr.as<uint32_t>(), *arm_end = c.bb_end.as<uint32_t>(), *arm_len = c.bb_len.as<uint32_t>(), *removed = c.tp_removed.as<uint32_t>();
+    u64 *dst = c.tp_st.as<u64>();
+    const int64_t lanes = M > n0 + 1 ? M : n0 + 1;
+    const unsigned nbB = (unsigned)((lanes + BB_THREADS - 1) / BB_THREADS), nbZ = (unsigned)((n0 + BB_THREADS - 1) / BB_THREADS);
+    accepted(c.v, EV_POP_BUBBLES);                              // as in stage_clip_tips: the contigs go, and S is invalid until the counters are back
+    u64 h[SG_ST];
+    const int moves = sg_run_rounds(c, cfg.rounds, c.bb_t_total, c.bb_t_compact, h, [&](int r, const int64_t *rows, const int64_t *cols) {
+        hipLaunchKernelGGL(k_bub_begin, dim3(nbB), dim3(BB_THREADS), 0, s, cols, dst, r, (uint32_t)M, ptr, arm_end, arm_len);
+        hipLaunchKernelGGL(k_bub_walk, dim3(nbZ), dim3(BB_THREADS), 0, s, ptr, rows, cols, dst, r, (uint32_t)cfg.max_arm_reads, (uint32_t)M, arm_end, arm_len);
+        hipLaunchKernelGGL(k_bub_pick, dim3(nbZ), dim3(BB_THREADS), 0, s, ptr, rows, cols, dst, r, (uint32_t)M, arm_end, arm_len, removed, c.tr_flags.as<uint8_t>());
+    });
+    done(c.v, EV_POP_BUBBLES);
+    st.nnz_after = c.tr_nnz; st.entries_removed = n0 - c.tr_nnz;
+    st.anchors = (int64_t)h[BB_ANCHORS]; st.arms = (int64_t)h[BB_ARMS]; st.bubbles = (int64_t)h[BB_BUBBLES]; st.arms_removed = (int64_t)h[BB_GONE];
+    st.reads_removed = (int64_t)h[BB_READS];
+    st.rounds_run = moves < cfg.rounds ? moves + 1 : cfg.rounds;
+    st.ms_total = c.bb_t_total.ms(); st.ms_compact = c.bb_t_compact.ms();
+    c.bbstats = st;
+}
+
+}  // namespace elba

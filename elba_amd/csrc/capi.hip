@@ -377,6 +377,14 @@ int elba_clip_tips(elba_ctx *ctx, const elba_tip_cfg *cfg, elba_tip_stats *stats
     });
 }
 
+int elba_pop_bubbles(elba_ctx *ctx, const elba_bubble_cfg *cfg, elba_bubble_stats *stats)
+{
+    return guarded(ctx, [&](Ctx &c) {
+        stage_pop_bubbles(c, cfg);
+        if (stats) *stats = c.bbstats;
+    });
+}
+
 int elba_generate_contigs(elba_ctx *ctx, elba_contig_stats *stats)
 {
     return guarded(ctx, [&](Ctx &c) {
@@ -737,6 +745,7 @@ int elba_release_workspace(elba_ctx *ctx)
         c.tm_cnt.release(); c.tm_bytes.release(); c.tm_first.release(); c.tm_boff.release(); c.tm_srcb.release();   // trim scratch (the trimmed reads and their map stay)
         c.tp_ptr.release(); c.tp_ntips.release(); c.tp_anchor.release(); c.tp_removed.release(); c.tp_keep.release(); c.tp_pos.release(); c.tp_st.release();   // tip scratch and the
         c.tp_rows.release(); c.tp_cols.release(); c.tp_vals.release();                                                                    // spare buffer of S (S itself stays)
+        c.bb_end.release(); c.bb_len.release();                                                                                            // bubble scratch
         if (has(c.v, P_COUNTS)) { c.pre_ready = false; c.pre_consumed = true; }    // (the CSR sort keys / column ids of the entries are gone: create_kmer_matrix rebuilds them from the column pointers)
     });
 }

@@ -321,10 +321,16 @@ struct Ctx {
     EventTimer tm_t_total, tm_t_repack;
     elba_trim_stats tmstats{};
 
-    // tip clipping (tips.hip): all scratch; tp_rows / tp_cols / tp_vals are the second buffer of S (swapped with tr_out_* after an odd number of moves)
+    // tip clipping (tips.hip): all scratch; tp_rows / tp_cols / tp_vals are the second buffer of S (swapped with tr_out_* after an odd number of moves).
+    // tp_ptr, tp_removed, tp_keep, tp_pos, tp_st and that second buffer belong to the rounds of sg_rounds.hpp, which bubbles.hip runs too
     DevBuf tp_ptr, tp_ntips, tp_anchor, tp_removed, tp_keep, tp_pos, tp_st, tp_rows, tp_cols, tp_vals;
     EventTimer tp_t_total, tp_t_compact;
     elba_tip_stats tpstats{};
+
+    // bubble popping (bubbles.hip): scratch of its own, one word per entry of S each
+    DevBuf bb_end, bb_len;
+    EventTimer bb_t_total, bb_t_compact;
+    elba_bubble_stats bbstats{};
 
     // workspaces
     DevBuf ws_scan, ws_sort, ws_a, ws_b, ws_c, ws_d, ws_e, ws_f;
@@ -424,6 +430,7 @@ void stage_prune_reads(Ctx &c, int mask, int64_t *kept);
 void stage_trim_reads(Ctx &c, const elba_trim_cfg *cfg);                      // trim.hip
 void stage_adopt_trimmed_reads(Ctx &c);
 void stage_clip_tips(Ctx &c, const elba_tip_cfg *cfg);                        // tips.hip
+void stage_pop_bubbles(Ctx &c, const elba_bubble_cfg *cfg);                   // bubbles.hip
 void stage_dist_count_owners(Ctx &c, int nranks, uint64_t *counts_host);                                   // kmer.hip
 void stage_dist_value_histogram(Ctx &c, uint64_t *hist_host, int64_t nbins);
 void stage_ref_hash_owner(Ctx &c, const uint64_t *kmers_host, int64_t n, int nprocs, uint64_t *hash_host, int32_t *owner_host);

@@ -21,6 +21,7 @@
 //   GenerateContigs / parallel_write_contigs   src/ContigGeneration.cpp:376-457, src/main.cpp:487-512   same names (one rank): the contigs are
 //                                                                             built on the GPU from the S left there
 //   (none: the reference drops every branch read)                             elba::ClipTips(S, reads, max_tip_reads, rounds): dead-end tips leave S
+//   (none)                                                                    elba::PopBubbles(S, reads, max_arm_reads, rounds): all but one arm of a bubble leave S
 //
 // Errors: the reference asserts/aborts; here every failing C-ABI status throws elba::Error (status + text).
 // There is no CPU path: constructing an engine without a GPU throws ELBA_ERR_NO_DEVICE.
@@ -416,17 +417,10 @@ inline std::unique_ptr<StringGraph> TransitiveReduction(const DnaBuffer &myreads
     return S;
 }
 
-// ClipTips(S, myreads, max_tip_reads, rounds) — not in the reference: elba_clip_tips on the S that TransitiveReduction left on the device, between
-// that call and GenerateContigs.  Dead-end chains of at most max_tip_reads reads that hang off a read of degree >= 3 leave S (a star of nothing
-// but such chains is spared), in up to `rounds` rounds; the host copy of S is replaced by the clipped graph, and clipped_reads, if given,
-// receives the reads removed so far (flag bit 2 of elba_export_read_flags), ascending.
-inline elba_tip_stats ClipTips(StringGraph &S, const DnaBuffer &myreads, int max_tip_reads, int rounds = 1, std::vector<int64_t> *clipped_reads = nullptr)
+// The host copy of S after a call that changed it on the device (ClipTips, PopBubbles): the entries of elba_export_string_graph; removed_reads,
+// if given, receives the reads that carry `flag` in elba_export_read_flags, ascending.
+inline void reload_string_graph(StringGraph &S, const DnaBuffer &myreads, uint8_t flag, std::vector<int64_t> *removed_reads)
 {
-    if (!S.engine) throw Error(ELBA_ERR_STATE, "ClipTips: the string graph is not on a device");
-    elba_tip_cfg cfg{};
-    cfg.max_tip_reads = max_tip_reads; cfg.rounds = rounds;
-    elba_tip_stats st{};
-    S.engine->check(elba_clip_tips(S.engine->ctx, &cfg, &st));
     elba_overlaps_t o;
     S.engine->check(elba_export_string_graph(S.engine->ctx, &o));
     S.rows.assign(o.rows, o.rows + o.n); S.cols.assign(o.cols, o.cols + o.n);
@@ -440,12 +434,42 @@ inline elba_tip_stats ClipTips(StringGraph &S, const DnaBuffer &myreads, int max
         w.rc = v.rc; w.passed = v.passed; w.containedQ = v.containedQ; w.containedT = v.containedT;
     }
     elba_free_overlaps(&o);
-    if (clipped_reads) {
+    if (removed_reads) {
         std::vector<uint8_t> flags((size_t)S.numreads);
         S.engine->check(elba_export_read_flags(S.engine->ctx, flags.data(), S.numreads));
-        clipped_reads->clear();
-        for (int64_t v = 0; v < S.numreads; ++v) if (flags[(size_t)v] & 4) clipped_reads->push_back(v);
+        removed_reads->clear();
+        for (int64_t v = 0; v < S.numreads; ++v) if (flags[(size_t)v] & flag) removed_reads->push_back(v);
     }
+}
+
+// ClipTips(S, myreads, max_tip_reads, rounds) — not in the reference: elba_clip_tips on the S that TransitiveReduction left on the device, between
+// that call and GenerateContigs.  Dead-end chains of at most max_tip_reads reads that hang off a read of degree >= 3 leave S (a star of nothing
+// but such chains is spared), in up to `rounds` rounds; the host copy of S is replaced by the clipped graph, and clipped_reads, if given,
+// receives the reads removed so far (flag bit 2 of elba_export_read_flags), ascending.
+inline elba_tip_stats ClipTips(StringGraph &S, const DnaBuffer &myreads, int max_tip_reads, int rounds = 1, std::vector<int64_t> *clipped_reads = nullptr)
+{
+    if (!S.engine) throw Error(ELBA_ERR_STATE, "ClipTips: the string graph is not on a device");
+    elba_tip_cfg cfg{};
+    cfg.max_tip_reads = max_tip_reads; cfg.rounds = rounds;
+    elba_tip_stats st{};
+    S.engine->check(elba_clip_tips(S.engine->ctx, &cfg, &st));
+    reload_string_graph(S, myreads, 4, clipped_reads);
+    return st;
+}
+
+// PopBubbles(S, myreads, max_arm_reads, rounds) — not in the reference: elba_pop_bubbles on the S that TransitiveReduction (or ClipTips) left on the
+// device, before GenerateContigs.  Where two or more chains of at most max_arm_reads reads of degree 2 join the same two reads of degree >= 3,
+// the one with the most reads stays (on a tie the one whose first read is smallest) and the others leave S, in up to `rounds` rounds; the host
+// copy of S is replaced by the popped graph, and popped_reads, if given, receives the reads removed so far (flag bit 3 of
+// elba_export_read_flags), ascending.
+inline elba_bubble_stats PopBubbles(StringGraph &S, const DnaBuffer &myreads, int max_arm_reads, int rounds = 1, std::vector<int64_t> *popped_reads = nullptr)
+{
+    if (!S.engine) throw Error(ELBA_ERR_STATE, "PopBubbles: the string graph is not on a device");
+    elba_bubble_cfg cfg{};
+    cfg.max_arm_reads = max_arm_reads; cfg.rounds = rounds;
+    elba_bubble_stats st{};
+    S.engine->check(elba_pop_bubbles(S.engine->ctx, &cfg, &st));
+    reload_string_graph(S, myreads, 8, popped_reads);
     return st;
 }
 

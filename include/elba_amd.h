@@ -294,7 +294,7 @@ void elba_free_overlaps(elba_overlaps_t *o);
  * elba_export_string_graph returns the entries of S, both triangles, in the order parallel_write_paf walks the reference's S
  * (src/main.cpp:527-541: columns ascending, rows ascending within a column); an entry below the diagonal carries Overlap::Transpose
  * (include/Overlap.hpp:43-69) of its mirror image.  elba_export_read_flags: flags[v] bit 0 = bad read, bit 1 = contained read,
- * bit 2 = removed by elba_clip_tips since. */
+ * bit 2 = removed by elba_clip_tips since, bit 3 = removed by elba_pop_bubbles since. */
 int  elba_set_overlaps(elba_ctx *ctx, int64_t nreads, const int64_t *rows, const int64_t *cols, const elba_overlap_t *vals, int64_t n);
 int  elba_transitive_reduction(elba_ctx *ctx, double bad_read_cutoff, int fuzz, elba_string_stats *stats);
 int  elba_export_string_graph(elba_ctx *ctx, elba_overlaps_t *out);
@@ -389,6 +389,54 @@ typedef struct { int64_t nreads, nnz_before, nnz_after;
                  int32_t rounds_run, reserved;
                  float   ms_total, ms_compact; } elba_tip_stats;
 int  elba_clip_tips(elba_ctx *ctx, const elba_tip_cfg *cfg, elba_tip_stats *stats);
+
+/* Bubble popping (not in the reference either).  A bubble is two or more short chains of degree-2 reads between the same two branch reads: a
+ * heterozygous site, a run of reads with one systematic error, an overlap the reduction could not prove redundant.  Both end reads have
+ * degree 3 and are dropped by elba_generate_contigs*, so one bubble breaks a path into four contigs (before, arm, arm, after), and a cycle
+ * into three linear ones.  elba_pop_bubbles works on the S of elba_transitive_reduction, in place, between that call and
+ * elba_generate_contigs*, before or after elba_clip_tips.  The rule is stated on the columns of S alone, as the tips rule is: deg(v) = entries of
+ * column v, the neighbours of v = their rows; no sequence, no suffix, no direction, no length in bases.  One ROUND, on the degrees as it finds
+ * them:
+ *   anchor     a read of degree >= 3.
+ *   arm        for an anchor a and an entry of column a whose row v1 has degree 2, the tips walk: from a read vi of degree 2 it goes on to the
+ *              row of column vi that is not the read it came from (the smaller one, should neither be); for v1, "came from" is a.  The first
+ *              read b of degree >= 3 ends it: v1 .. vt, 1 <= t <= max_arm_reads, is an arm of t reads from a to b.  There is no arm if the
+ *              walk ends at a read of degree 0 or 1, if it returns to a (b == a), or if it would need more than max_arm_reads reads.  A direct
+ *              entry between two anchors is no arm (t >= 1).  Every arm is recorded once, at its smaller anchor (a < b); its first read is the
+ *              one in a's column.
+ *   bubble     the set of all arms with the same (a, b), when there are two or more.
+ *   kept arm   the arm with the most reads; on a tie the one whose first read is smallest (the earliest entry of column a).  Every other arm
+ *              of the bubble is removed.  A direct entry a - b stays.  (After the reduction an arm is a minimal chain over its span, so more
+ *              reads mean more coverage; overlap scores, lengths in bases and strands are not looked at.)
+ *   removal    every entry of S whose row or column is a read of a removed arm goes, in both triangles; the other entries keep their values
+ *              and their order (columns ascending, rows ascending within a column).
+ * On a symmetric S the arms are disjoint (their reads have degree 2), each belongs to one (a, b), and a bubble keeps one arm: no anchor loses
+ * its last edge and no component is erased.  Everything a round decides is read from tables frozen at its start, and what it writes are sets
+ * and sums: the result does not depend on the order in which entries are looked at.  Where the reduction kept only one image of a pair (the
+ * direction -1 case) the contract is what the statements above produce on the columns as they are; the guarantees are not claimed there.
+ * Up to `rounds` rounds run, each on the S the one before left (an anchor that fell to degree 2 joins two chains, so the outer bubble of a
+ * nested pair shows one round later); the call stops after a round that removed nothing (rounds_run counts that round).  A removed read gets
+ * bit 3 (value 8) in the flags of elba_export_read_flags until the next elba_transitive_reduction rebuilds them, so ELBA_CONTIG_SINGLETONS
+ * does not bring it back.
+ * Errors and state are those of elba_clip_tips: after ELBA_OK the context's S is the popped one, contigs made before are invalid, and a second
+ * call — or elba_clip_tips — goes on from there.  An S without entries or reads: ELBA_OK, nothing removed, rounds_run 1.  ELBA_ERR_STATE
+ * without a valid S; ELBA_ERR_INVALID_ARG for a null cfg, a value out of range or a non-zero reserved word: S, the flags and the contigs stay
+ * as they were.
+ * This call alone does not reach the fixed point of both: a tip on an arm gives the arm a read of degree 3, so there is no arm until the tip
+ * is clipped.  Clip first, then pop, and alternate until both remove nothing (Engine.simplify_graph in the Python binding does).  On a
+ * symmetric S a pop makes no new tip — it lowers anchors to degree 2, which only lengthens dead-end chains — so the second pass finds nothing.
+ * Stats: arms counts the arms found, in a bubble or not; arms, bubbles, arms_removed, reads_removed and entries_removed (both triangles) are
+ * summed over the rounds; ms_compact is the compaction of the first round, as for tips, and `rounds` costs what it costs there: four rounds
+ * are queued per look at the device counters.  Picking the kept arm costs, per arm, one pass over its anchor's column. */
+typedef struct { int32_t max_arm_reads;   /* 1 .. 65535 */
+                 int32_t rounds;          /* 1 .. 64: at most this many */
+                 int32_t reserved[2]; } elba_bubble_cfg;
+typedef struct { int64_t nreads, nnz_before, nnz_after;
+                 int64_t anchors;         /* reads of degree >= 3 when round 1 starts */
+                 int64_t arms, bubbles, arms_removed, reads_removed, entries_removed;  /* summed over the rounds */
+                 int32_t rounds_run, reserved;
+                 float   ms_total, ms_compact; } elba_bubble_stats;
+int  elba_pop_bubbles(elba_ctx *ctx, const elba_bubble_cfg *cfg, elba_bubble_stats *stats);
 
 /* Read pileups and chimera flags: PileupVector / GetReadPileup / GetTrimmedInterval (src/PruneChimeras.cpp:14-69,108-158,
  * include/PruneChimeras.hpp), which src/main.cpp never calls, and R->PruneFull(x, x) of the reads it flags.  Runs after elba_align_seeds,
