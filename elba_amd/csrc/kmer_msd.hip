@@ -27,8 +27,8 @@
 // hash table per bucket for the counts; from the compacted entries on, the k <= 17 kernels.
 #include "common.hpp"
 #include "matrix.hpp"
+#include "msd_plan.hpp"
 #include <algorithm>
-#include <functional>
 
 namespace elba {
 
@@ -36,17 +36,8 @@ namespace {
 
 #include "kmer_enum.hpp"
 
-// (16384-key tiles, 139 KB of LDS, one workgroup per CU: on 1024 lanes x 16 keys — sixteen wavefronts to hide the barriers — the partition of
-//  config 3 takes 26.4 ms, on 512 x 32 27.6 ms)
-#ifndef ELBA_MT_THREADS
-#define ELBA_MT_THREADS 1024
-#endif
-#ifndef ELBA_MT_ITEMS
-#define ELBA_MT_ITEMS 16
-#endif
-constexpr int MT_THREADS = ELBA_MT_THREADS, MT_ITEMS = ELBA_MT_ITEMS, MT_TILE = MT_THREADS * MT_ITEMS;      // instances per tile; a wavefront's share is at most one block of the instance -> read table
-constexpr int MT_MAXBITS = 9, MT_MAXBINS = 1 << MT_MAXBITS;
-constexpr int VBITS = 16;                     // value bits left to the bucket kernel (two halves of 2^15 values)
+// (the tile sizes, digit widths and VBITS: msd_plan.hpp, with the ELBA_MT_* / ELBA_W2_* defaults)
+constexpr int MT_THREADS = ELBA_MT_THREADS, MT_ITEMS = ELBA_MT_ITEMS, MT_MAXBINS = 1 << MT_MAXBITS;
 constexpr int BK_THREADS = 1024;
 constexpr uint32_t EW = 2048;                 // entries of a bucket half staged at a time (a window of its columns)
 constexpr uint32_t KW = EW / 2 + 1;           // columns such a window can hold (a reliable column has >= 2 entries)
@@ -194,13 +185,14 @@ __global__ void k_add_u32(uint32_t *a, uint32_t n, uint32_t v)
 }
 
 // ---- tiles of the second pass: none of them straddles two first-digit buckets ------------------------------------------------------------
-// b1start[d] = place of bucket d (row 0 of the scanned first histogram), tile0[d] = first tile of bucket d; one workgroup of 512 threads
-__global__ __launch_bounds__(MT_MAXBINS) void k_msd_tiles(const uint32_t *hist1_row0, uint32_t nb1, uint64_t I, uint32_t *b1start, uint32_t *tile0)
+// b1start[d] = place of bucket d (row 0 of the scanned first histogram), tile0[d] = first tile of bucket d; one workgroup of MAXBINS threads (k <= 17: 512 first digits, tiles of MT_TILE words; the wide partition: up to 1024, tiles of W2_TILE records)
+template <int TILE, int MAXBINS>
+__global__ __launch_bounds__(MAXBINS) void k_tiles(const uint32_t *hist1_row0, uint32_t nb1, uint64_t I, uint32_t *b1start, uint32_t *tile0)
 {
-    __shared__ uint32_t wsum[MT_MAXBINS / 64];
+    __shared__ uint32_t wsum[MAXBINS / 64];
     const uint32_t d = threadIdx.x, lane = d & 63, w = d >> 6;
     const uint32_t st = d < nb1 ? hist1_row0[d] : (uint32_t)I, en = d + 1 < nb1 ? hist1_row0[d + 1] : (uint32_t)I;
-    const uint32_t nt = d < nb1 ? (en - st + MT_TILE - 1) / MT_TILE : 0u;
+    const uint32_t nt = d < nb1 ? (en - st + TILE - 1) / TILE : 0u;
     uint32_t inc = nt;
 #pragma unroll
     for (int s2 = 1; s2 < 64; s2 <<= 1) { const uint32_t o = __shfl_up(inc, s2, 64); if (lane >= (uint32_t)s2) inc += o; }
@@ -214,15 +206,17 @@ __global__ __launch_bounds__(MT_MAXBINS) void k_msd_tiles(const uint32_t *hist1_
 
 struct SegTiles { const uint32_t *b1start, *tile0; uint32_t nb1; const uint2 *tinfo; };      // tinfo (or null): every tile's (first key, keys), written once by k_msd_tile_info
 // tile t of the second pass: its bucket (last b with tile0[b] <= t: empty buckets share their successor's first tile), first key, keys
+// (TINFO: the kernel looks at sg.tinfo — the k <= 17 kernels; the wide partition's never do, and keep no branch for it)
+template <int TILE = MT_TILE, bool TINFO = true>
 __device__ __forceinline__ void seg_tile(const SegTiles &sg, uint32_t t, uint32_t &bucket, uint32_t &start, uint32_t &count)
 {
-    if (sg.tinfo) { const uint2 ti = sg.tinfo[t]; bucket = 0; start = ti.x; count = ti.y; return; }      // (ONE load: the search below is nine dependent ones, in front of every tile of a persistent workgroup)
+    if (TINFO && sg.tinfo) { const uint2 ti = sg.tinfo[t]; bucket = 0; start = ti.x; count = ti.y; return; }      // (ONE load: the search below is nine dependent ones, in front of every tile of a persistent workgroup)
     uint32_t lo = 0, hi = sg.nb1;
     while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (sg.tile0[mid] <= t) lo = mid; else hi = mid; }
     bucket = lo;
-    start = sg.b1start[lo] + (t - sg.tile0[lo]) * (uint32_t)MT_TILE;
+    start = sg.b1start[lo] + (t - sg.tile0[lo]) * (uint32_t)TILE;
     const uint32_t end = sg.b1start[lo + 1];
-    count = end - start < (uint32_t)MT_TILE ? end - start : (uint32_t)MT_TILE;
+    count = end - start < (uint32_t)TILE ? end - start : (uint32_t)TILE;
 }
 
 __global__ __launch_bounds__(256) void k_msd_tile_info(SegTiles sg, uint2 *tinfo)
@@ -559,7 +553,6 @@ __global__ __launch_bounds__(MT_THREADS) void k_msd_scatter(EnumParams e, const 
 __device__ __forceinline__ void lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 struct BucketStats { unsigned long long distinct, sumsq; unsigned int maxcol, ncrowded, nmid, nbig; };      // nmid / nbig: buckets of 4097..8192 / 8193..ES_CAP_MAX entries
-constexpr uint32_t ES_CAP_MAX = 12288;      // entries of a bucket the widest emit kernel sorts in LDS
 struct BucketOut {
     uint64_t *rel_kmers; uint32_t *rel_counts, *colptr;
     uint64_t *csc, *csr_words, *kid_of_entry, *ell;
@@ -1235,14 +1228,7 @@ __global__ __launch_bounds__(BK_THREADS) void k_msd_bucket(const uint64_t *words
 // of the flattened value —, each pass partitioned on e more bits of its coarse digits ((dhi - dlo) << e <= 2^10 first digits, k31_hist1<true> /
 // k31_scatter<true, true>) and a second digit of up to 10 bits, so that its buckets are as fine as those of an input of its size (msd_run).
 // HBM traffic per instance: 16 B written + 16 read (hist2) + 16 read + 16 written + 16 read = 80 B, against 7 passes x 32 B + 3 x 16 B on the sort path.
-#ifndef ELBA_W2_THREADS
-#define ELBA_W2_THREADS 512
-#endif
-#ifndef ELBA_W2_ITEMS
-#define ELBA_W2_ITEMS 16
-#endif
-constexpr int W2_THREADS = ELBA_W2_THREADS, W2_ITEMS = ELBA_W2_ITEMS, W2_TILE = W2_THREADS * W2_ITEMS;      // 8192 records of 16 bytes: 128 KB of LDS (runs of 8 records per digit and tile; 4096-record tiles: partition 78 -> 58 ms on 2.0 G instances)
-constexpr int W2_MAXBITS = 10, W2_MAXBINS = 1 << W2_MAXBITS;
+constexpr int W2_THREADS = ELBA_W2_THREADS, W2_ITEMS = ELBA_W2_ITEMS, W2_MAXBINS = 1 << W2_MAXBITS;      // (W2_TILE, W2_MAXBITS: msd_plan.hpp)
 constexpr uint32_t W2_CAP = 4096;                // records of a bucket k31_count takes (eight per lane, in registers)
 constexpr int W2C_THREADS = 512, W2C_KPT = (int)(W2_CAP / W2C_THREADS);
 static_assert(W2_ITEMS * 64 <= (1 << IB_SHIFT), "a wavefront's share of a tile lies inside one block of the instance -> read table");
@@ -1278,32 +1264,7 @@ __global__ __launch_bounds__(W2_THREADS) void k31_hist1(EnumParams e, const Bloc
     for (uint32_t i = threadIdx.x; i < nbins; i += W2_THREADS) hist[(size_t)blockIdx.x * nbins + i] = h[i];
 }
 
-// tiles of the second pass (none straddles two first-digit buckets): as k_msd_tiles, up to 1024 first digits, tiles of W2_TILE records
-__global__ __launch_bounds__(W2_MAXBINS) void k31_tiles(const uint32_t *hist1_row0, uint32_t nb1, uint64_t I, uint32_t *b1start, uint32_t *tile0)
-{
-    __shared__ uint32_t wsum[W2_MAXBINS / 64];
-    const uint32_t d = threadIdx.x, lane = d & 63, w = d >> 6;
-    const uint32_t st = d < nb1 ? hist1_row0[d] : (uint32_t)I, en = d + 1 < nb1 ? hist1_row0[d + 1] : (uint32_t)I;
-    const uint32_t nt = d < nb1 ? (en - st + W2_TILE - 1) / W2_TILE : 0u;
-    uint32_t inc = nt;
-#pragma unroll
-    for (int s2 = 1; s2 < 64; s2 <<= 1) { const uint32_t o = __shfl_up(inc, s2, 64); if (lane >= (uint32_t)s2) inc += o; }
-    if (lane == 63) wsum[w] = inc;
-    __syncthreads();
-    uint32_t run = inc - nt;
-    for (uint32_t ww = 0; ww < w; ++ww) run += wsum[ww];
-    if (d < nb1) { b1start[d] = st; tile0[d] = run; }
-    if (d == nb1 - 1) { b1start[nb1] = (uint32_t)I; tile0[nb1] = run + nt; }
-}
-__device__ __forceinline__ void seg_tile2(const SegTiles &sg, uint32_t t, uint32_t &bucket, uint32_t &start, uint32_t &count)
-{
-    uint32_t lo = 0, hi = sg.nb1;
-    while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (sg.tile0[mid] <= t) lo = mid; else hi = mid; }
-    bucket = lo;
-    start = sg.b1start[lo] + (t - sg.tile0[lo]) * (uint32_t)W2_TILE;
-    const uint32_t end = sg.b1start[lo + 1];
-    count = end - start < (uint32_t)W2_TILE ? end - start : (uint32_t)W2_TILE;
-}
+// (the tiles of the second pass: k_tiles<W2_TILE, W2_MAXBINS>; a tile's bucket and keys: seg_tile<W2_TILE, false>)
 
 // (shift / bits of the digit refer to the flattened leading 32 bits, w2_flat; k2 - 32 = the value bits below them)
 __global__ __launch_bounds__(W2_THREADS) void k31_hist2(const Rec2 *recs, SegTiles sg, int k2, int shift, int bits, uint32_t *hist)
@@ -1314,7 +1275,7 @@ __global__ __launch_bounds__(W2_THREADS) void k31_hist2(const Rec2 *recs, SegTil
     for (uint32_t i = threadIdx.x; i < nbins; i += W2_THREADS) h[i] = 0;
     __syncthreads();
     uint32_t bucket, start, count;
-    seg_tile2(sg, blockIdx.x, bucket, start, count);
+    seg_tile<W2_TILE, false>(sg, blockIdx.x, bucket, start, count);
     uint64_t k[W2_ITEMS];
 #pragma unroll
     for (int r = 0; r < W2_ITEMS; ++r) { const uint32_t q = (uint32_t)r * W2_THREADS + threadIdx.x; k[r] = q < count ? recs[start + q].hi : 0; }
@@ -1383,7 +1344,7 @@ __global__ __launch_bounds__(W2_THREADS) void k31_scatter(EnumParams e, const Bl
         enum_consecutive<W2_ITEMS>(e, block_read, base, [&](int it, uint64_t km, uint32_t r, uint32_t p) { khi[it] = km >> (64 - k2); klo[it] = ((uint64_t)r << pbits) | p; });
     } else {
         uint32_t bucket, start;
-        seg_tile2(sg, blockIdx.x, bucket, start, count);
+        seg_tile<W2_TILE, false>(sg, blockIdx.x, bucket, start, count);
 #pragma unroll
         for (int it = 0; it < W2_ITEMS; ++it) {
             const uint32_t q = (uint32_t)it * W2_THREADS + threadIdx.x;
@@ -1799,13 +1760,6 @@ __global__ void k31_pseudo_bases(const uint32_t *kidbase, const uint32_t *entbas
     for (uint32_t j = pbase[p]; j < pbase[p + 1]; ++j) { kidbase2[j] = kn; entbase2[j] = en; kn += bN2[j]; en += bZ2[j]; }
 }
 
-int bits_needed_u(uint64_t maxval)
-{
-    int b = 1;
-    while (b < 64 && (maxval >> b)) ++b;
-    return b;
-}
-
 }  // namespace
 
 // largest position among the triples (what the layout of a partition word depends on)
@@ -1873,200 +1827,212 @@ __global__ __launch_bounds__(256) void k_tri_stats(const uint64_t *words, const 
     if (lane == 0) { if (st_distinct) atomicAdd(&gstat->distinct, st_distinct); if (st_sumsq) atomicAdd(&gstat->sumsq, st_sumsq); if (st_maxcol) atomicMax(&gstat->maxcol, st_maxcol); }
 }
 
+// ---- the host driver: msd_run (below) reads top to bottom — plan (msd_plan.hpp), phase A over the passes, totals, layout of A, phase B or emit, finish.
+// Its state is one MsdRun; every step is a member whose comment says what it reads and what it leaves behind (the k-mer stage's map).
+// a planned pass (msd_plan.hpp) and its count kernels' statistics
+struct CountedPass : Pass { BucketStats hs{}; };
+
+// sub-arrays of one workspace, front to back: take<T>(n) is the next n elements of T, at `align` bytes (a kernel that relies on two arrays being
+// neighbours — bN + nbuckets and its like — gets them by two takes in a row)
+struct Carver {
+    char *base; size_t off = 0;
+    explicit Carver(DevBuf &b) : base(b.as<char>()) {}
+    template <class T> T *take(size_t n, size_t align = alignof(T))
+    {
+        T *p = reinterpret_cast<T *>(base + (off = (off + align - 1) & ~(align - 1)));
+        off += n * sizeof(T);
+        return p;
+    }
+    void fits(size_t reserved) const { ELBA_REQUIRE(off <= reserved, ELBA_ERR_INTERNAL, "count_kmers: a workspace is carved past its reserved size"); }
+};
+
+// One table of buckets as the emit kernels see it: a pass's own buckets, or the pseudo-buckets of its crowded ones.
+// words: the partitioned words — what the crowded-bucket kernel (k_msd_bucket) reads; NULL: this table never runs it (the wide partition's own buckets:
+// its crowded ones become pseudo-buckets instead).  wrel: the kept entries, bucket by bucket — what the k_msd_emit_small kernels read.
+struct BucketTable {
+    const uint64_t *words = nullptr, *wrel = nullptr;
+    uint32_t *b2start = nullptr, *bN = nullptr, *bZ = nullptr, *kidbase = nullptr, *entbase = nullptr, *crowded = nullptr, nbuckets = 0;
+    BucketStats *gstat = nullptr;
+};
+
+struct EmitGrids { uint32_t g8, g16, g32; };      // workgroups of the 256- / 512- / 1024-lane emit kernels
+static EmitGrids emit_grids(const Ctx &c, uint32_t n) { const uint32_t cu = (uint32_t)c.num_cus; return {std::min(n, cu * 24u), std::min(n, cu * 12u), std::min(n, cu * 4u)}; }
+
+// The emit kernels over one bucket table.  hs: the statistics of the count over THIS table — which classes hold buckets.
+// entries per bucket: up to 2048 / 4096 / 8192 -> k_msd_emit_small on 256 / 512 / 1024 lanes, beyond -> k_msd_bucket (option "msd_small_cap": tests lower the last bound)
+static void launch_emit(Ctx &c, const MsdParams &m, uint32_t small_cap, const BucketTable &t, const BucketStats &hs, const BucketOut &o, const EmitGrids &g)
+{
+    hipStream_t s = c.stream;
+    const uint32_t cap16 = std::min<uint32_t>(small_cap, 4096u), cap8 = std::min<uint32_t>(cap16, c.opt.msd_no_emit8 ? 0u : 2048u), nbuckets = t.nbuckets;
+    const uint32_t *b2start = t.b2start, *bZ = t.bZ, *kidbase = t.kidbase, *entbase = t.entbase;
+    // (buckets of up to 2048 entries — more than half of them on BASELINE config 3, where a bucket holds 2040 on average — through an instantiation
+    //  with 8 entries per lane: half the predicated-off work of the 16-entry one, 26 KB of LDS instead of 49: six workgroups per CU)
+    // (512 lanes x 4 for them was measured too: 17.6 against 17.5 ms on config 3, 48.4 against 47.6 ms on the k = 31 workload)
+    // (pseudo-buckets look their k-mers up — kmer_dist, ncols —: never the specialised instantiation)
+    const bool spec = m.rk == 0 && m.dup == 0u && o.compact && o.hints && o.csr_words && !o.pair_val && !o.kmer_src && !o.kmer_dist && !o.ncols && o.rel_kmers && c.opt.tune[6] != 3;      // ("tune6" = 3: the general instantiation — A/B)
+    if (cap8 && spec) hipLaunchKernelGGL((k_msd_emit_small<8, 256, true>), dim3(g.g8), dim3(256), 0, s, t.wrel, b2start, bZ, nbuckets, m, 0u, cap8, kidbase, entbase, o);
+    else if (cap8) hipLaunchKernelGGL((k_msd_emit_small<8>), dim3(g.g8), dim3(256), 0, s, t.wrel, b2start, bZ, nbuckets, m, 0u, cap8, kidbase, entbase, o);
+    // 2049..4096 entries: 512 lanes x 8 (three workgroups of eight wavefronts per CU, not of four: 19.0 -> 17.5 ms for the bucket kernels on config 3)
+    if (cap16 > cap8 && spec) hipLaunchKernelGGL((k_msd_emit_small<8, 512, true>), dim3(g.g16), dim3(512), 0, s, t.wrel, b2start, bZ, nbuckets, m, cap8, cap16, kidbase, entbase, o);
+    else if (cap16 > cap8) hipLaunchKernelGGL((k_msd_emit_small<8, 512>), dim3(g.g16), dim3(512), 0, s, t.wrel, b2start, bZ, nbuckets, m, cap8, cap16, kidbase, entbase, o);
+    if (small_cap > 4096u && hs.nmid)
+        // (8192 entries on 1024 lanes x 8: the 99 KB of LDS allow ONE workgroup per CU — sixteen wavefronts hide the barriers better than eight:
+        //  39.7 against 46.8 ms for the bucket kernels on BASELINE config 5 at one GPU's share)
+        hipLaunchKernelGGL((k_msd_emit_small<8, 1024>), dim3(g.g32), dim3(1024), 0, s, t.wrel, b2start, bZ, nbuckets, m, 4096u, std::min(small_cap, 8192u), kidbase, entbase, o);
+    // 8193..12288 entries (the lowest values of a deep read set: the canonical k-mer is the smaller of two, the first buckets hold twice the average):
+    // twelve entries per lane, 144 KB of LDS — one kernel launch over a few percent of the buckets instead of the windowed kernel's ~45 us per bucket
+    if (small_cap > 8192u && hs.nbig)
+        hipLaunchKernelGGL((k_msd_emit_small<12, 1024>), dim3(g.g32), dim3(1024), 0, s, t.wrel, b2start, bZ, nbuckets, m, 8192u, small_cap, kidbase, entbase, o);
+    if (hs.ncrowded && t.words)
+        hipLaunchKernelGGL((k_msd_bucket<true>), dim3((unsigned)std::min<uint32_t>(hs.ncrowded, (uint32_t)c.num_cus)), dim3(BK_THREADS), BK_LDS_EMIT, s, t.words, b2start, nbuckets, m,
+                           (uint32_t)c.cfg.lower, (uint32_t)c.cfg.upper, (const uint32_t *)t.crowded, (const BucketStats *)t.gstat, kidbase, entbase, o);
+}
+
 // A matrix handed over as device triples (elba_set_kmer_matrix_device, INTEGRATION.md option B) through the same bucket kernels: the "value" is the
 // column id, a bucket 2^vb consecutive columns.  Every column counts as reliable; a matrix with an EMPTY column (the bucket kernels number the
 // columns they find), or with a bucket beyond what the LDS sort takes, keeps the sort of matrix.hip.
 struct MsdTriples { int64_t M, N; uint64_t maxpos; const int64_t *rows, *cols; const uint32_t *vals; unsigned long long bad; };
 
-// The k-mer stage of one GPU for 9 <= k <= 17 (see the file header).  Leaves behind exactly what runs_to_columns (kmer.hip) leaves: rel_kmers,
-// rel_counts, a_colptr, a_csc, the CSR sort keys (csr_words, hint bits included) or kid_of_entry — plus the padded column store.
-static bool msd_run(Ctx &c, uint64_t I, elba_kmer_stats *stp, MsdTriples *tri)
-{
-    const int k = tri ? 17 : c.cfg.k, k2 = 2 * k;
-    if (c.opt.kmer_no_msd || c.opt.kmer_pairs || c.opt.kmer_unfused || c.opt.emit_plain || c.opt.kmer_drop) return false;
-    if (k > 31 || (!tri && c.cfg.upper > 255) || I == 0) return false;
-    // k <= 17: the partition takes all but 16 value bits.  19 <= k <= 31 ("wide", 16-byte records): as many bits as make a bucket of ~1500 instances
-    const bool wide = !tri && k2 - VBITS > 2 * MT_MAXBITS;
-    int T = k2 - VBITS, vb = VBITS;      // partitioned bits; value bits below them
-    if (wide) {
-        T = 12;
-        while (T < 2 * W2_MAXBITS && (I >> T) > 512) ++T;      // (a bucket may hold W2_CAP: six times this average — k-mers are not spread evenly over real genomes)
-        if (c.opt.msd_wide_bits > 0) T = std::min(std::max(c.opt.msd_wide_bits, 2), 2 * W2_MAXBITS);      // (tests: other splits)
-        if (T > k2 - 2) return false;
-    }
-    if (tri) {
-        // buckets of ~2048 entries: 2^vb columns of Z / N entries each; at most 2 x 9 partitioned bits
-        if (tri->N < 8 || c.opt.csr_pairs) return false;
-        const int nbc = bits_needed_u((uint64_t)tri->N - 1);
-        const uint64_t avg = (I + (uint64_t)tri->N - 1) / (uint64_t)tri->N;
-        vb = 1;
-        while (vb < 13 && (avg << (vb + 1)) <= 2048) ++vb;
-        if (nbc - vb > 2 * MT_MAXBITS) vb = nbc - 2 * MT_MAXBITS;
-        // (a bucket holds at most 1024 columns: the emit kernels keep a column table of half their capacity + 1 — enough for k-mers, which come with LOWER >= 2
-        //  entries each, and for 1024 one-entry columns in the smallest class; a bucket beyond the largest class sends the whole matrix to the sort: the
-        //  average must stay clear of it)
-        if (vb > 10 || (avg << vb) > 6144) return false;
-        T = nbc - vb;
-    }
-    if (T < 2) return false;
-    // worth it from ~512 instances per bucket on (the bucket kernels pay a few us per bucket whatever it holds: BASELINE config 2 — 530 per bucket — 6.9 ms
-    // here, 7.1 ms through the sort); smaller inputs keep the sort
-    if (!c.opt.kmer_msd && (wide ? I < (1ull << 22) : I < ((uint64_t)512 << T))) return false;
-    const uint32_t maxlen = c.max_read_len;      // (stage_count_kmers' walk over the read lengths)
-    const uint64_t maxpos = tri ? tri->maxpos : maxlen >= (uint32_t)k ? maxlen - (uint32_t)k : 0;
-    const int64_t nrows = tri ? tri->M : c.nreads;
-    const uint32_t lower = tri ? 1u : (uint32_t)c.cfg.lower, upper = tri ? 0xFFFFu : (uint32_t)c.cfg.upper;
+struct MsdRun {
+    Ctx &c;
+    const MsdPlan pl;
+    const MsdTriples *tri;
+    hipStream_t s;
     MsdParams m{};
-    m.k2 = k2; m.b1 = (T + 1) / 2; m.b2 = T - m.b1; m.I = I;
-    m.pbits = bits_needed_u(maxpos);
-    const int mb = bits_needed_u((uint64_t)(nrows > 0 ? nrows - 1 : 0));
-    m.PB = mb + m.pbits;
-    if ((wide ? VBITS : tri ? T + vb : m.b2 + VBITS) + m.PB > 62) return false;      // (the two top bits of a staged entry carry its hint)
-    // an entry's column rank inside its bucket (< 8192: the emit kernels take no more entries) above the 16 value bits, where there is room for it
-    // ... and where columns grow long enough for one value to fill a sort range of the emit kernels (UPPER beyond HINT_MAX_COL; the wide path ranks its columns anyway)
-    m.rk = (m.PB + VBITS + 13 <= 64 && !c.opt.msd_no_rank && (wide || tri || upper > HINT_MAX_COL || c.opt.msd_rank)) ? m.PB + VBITS : 0;
-    m.rkmask = 0xFFFFFFFFu;
-    if (tri) { m.rk = m.PB; m.rkmask = (1u << vb) - 1u; m.dup = 1u; }      // (the rank of a column inside its bucket = the low bits of its id: every column holds entries, or the matrix is refused below)
-    hipStream_t s = c.stream;
-    uint32_t nb1 = 1u << m.b1, nb2 = 1u << m.b2, nbuckets = nb1 * nb2;      // (the wide partition under value-range batching: the current pass's)
-    const uint32_t tile = wide ? (uint32_t)W2_TILE : (uint32_t)MT_TILE;
-    // more instances than a 32-bit place holds (or than "kmer_batch_instances": tests): passes over value ranges (reads)
-    const uint64_t batch_cap = c.opt.kmer_batch_instances > 0 ? (uint64_t)c.opt.kmer_batch_instances : 0xE0000000ull;
-    const bool batched = !tri && I > batch_cap;
-    if (!batched && I >= 0xFFFFFFF0ull) return false;      // (the caller refuses: the sort and the triples hold 32-bit places)
-    ELBA_REQUIRE((I + tile - 1) / tile < 0xFFFFFFF0ull, ELBA_ERR_UNSUPPORTED, "count_kmers: more than 2^45 k-mer instances");
-    // the bucket arrays hold the most first digits / buckets of any pass: the wide partition's passes choose their own (up to 2^10 x 2^10)
-    const uint32_t nb1_cap = wide && batched ? (uint32_t)W2_MAXBINS : nb1, nbk_cap = wide && batched ? (uint32_t)W2_MAXBINS << W2_MAXBITS : nbuckets;
-    const uint32_t ntiles1 = (uint32_t)((I + tile - 1) / tile), ntiles2 = ntiles1 + nb1_cap;
-
-    // (value-range batching: a pass takes whole first digits — one digit may hold most of the input: a homopolymer, AT-rich reads —, the two partition
-    //  buffers are sized by the largest pass once the passes are planned, below, and every pass is checked against them)
-    if (!batched) { c.ws_a.reserve((size_t)(I + 2) * (wide ? 16 : 8)); c.ws_c.reserve((size_t)(I + 2) * (wide ? 16 : 8)); }
-    c.ws_sort.reserve(((size_t)ntiles2 << (wide ? W2_MAXBITS : MT_MAXBITS)) * 4 + 4096);
-    c.ws_e.reserve((size_t)(nbk_cap + 2) * 4 * 6 + (size_t)(2 * nb1_cap + 8) * 4 + 256 + 64 + (size_t)(ntiles2 + 4) * 8);
-    uint32_t *hist = c.ws_sort.as<uint32_t>();
-    BucketStats *gstat = c.ws_e.as<BucketStats>();
-    uint32_t *b2start = c.ws_e.as<uint32_t>() + 16, *bN = b2start + (nbk_cap + 2), *bZ = bN + (nbk_cap + 2), *kidbase = bZ + (nbk_cap + 2), *entbase = kidbase + (nbk_cap + 2);
-    uint32_t *crowded = entbase + (nbk_cap + 2), *b1start = crowded + (nbk_cap + 2), *tile0 = b1start + (nb1_cap + 2);
-    uint32_t *one_seg = tile0 + (nb1_cap + 2);      // (triples: the whole input as ONE segment of tiles, for the first digit's pass)
-    uint2 *tinfo = reinterpret_cast<uint2 *>(c.ws_e.as<char>() + (((size_t)((char *)(one_seg + 16) - c.ws_e.as<char>()) + 15) & ~(size_t)15));      // (k <= 17: the second pass's tiles)
-    uint64_t *wa = c.ws_a.as<uint64_t>(), *wb = c.ws_c.as<uint64_t>();
-
-    c.t_total.start(s);
-    c.t_a.start(s);
     EnumParams e{};
-    e.packed = c.d_packed; e.byte_off = c.d_byte_off; e.len = c.d_len; e.inst_off = c.inst_off.as<uint64_t>();
-    e.nreads = (uint32_t)c.nreads; e.I = I; e.k = k;
-    const uint64_t nib = (I >> IB_SHIFT) + 1;
-    if (!tri) c.ws_b.reserve((size_t)(nib + 1) * sizeof(BlockInfo));
-    const BlockInfo *bi = c.ws_b.as<BlockInfo>();
-    if (!tri) hipLaunchKernelGGL(k_block_reads, dim3((unsigned)((nib + 255) / 256)), dim3(256), 0, s, e.inst_off, e.byte_off, e.nreads, nib, c.ws_b.as<BlockInfo>());
-    SegTiles sg{b1start, tile0, nb1};
+    const BlockInfo *bi = nullptr;
+    // the current pass's buckets (arrays in ws_e, sized for the largest pass), the first level's segments, the triples' one segment, the second pass's tiles (k <= 17)
+    BucketTable bt;
+    uint32_t *b1start = nullptr, *tile0 = nullptr, *one_seg = nullptr;
+    uint2 *tinfo = nullptr;
+    // what the scan over the current pass's buckets takes: bt.bN / bt.bZ, or — after cut_crowded found crowded buckets — copies with the pseudo-buckets'
+    // counts folded in (the emit kernels read bt.bZ: a crowded parent stays 0 there).  Set by every partition_* step and by cut_crowded.
+    uint32_t *sN = nullptr, *sZ = nullptr;
+    // pseudo-buckets of the current pass's crowded buckets (the section above k31_gather_crowded); on: the pass has some.  Set by partition_wide (off) and cut_crowded.
+    struct { bool on = false; uint32_t nc = 0; BucketTable t; uint32_t *pz = nullptr; const uint32_t *clist = nullptr, *pbase = nullptr; const uint64_t *cdist = nullptr; const uint32_t *dist_base = nullptr; BucketStats hs{}; } ps;
     BucketOut o{};
-    const uint32_t small_cap = c.opt.msd_small_cap > 0 && (uint32_t)c.opt.msd_small_cap < ES_CAP_MAX ? (uint32_t)c.opt.msd_small_cap : ES_CAP_MAX;
-    static DeviceOnce attr_once;
-    attr_once.run(c.device, [&] {
-        ELBA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_msd_count<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        ELBA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_msd_count<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        ELBA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_msd_bucket<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        ELBA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k31_count), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    });
-    // pseudo-buckets of the wide partition's crowded buckets (the section above k31_gather_crowded)
-    struct { bool on = false; uint32_t nc = 0, np = 0; const uint64_t *words = nullptr; uint64_t *wrel = nullptr; uint32_t *b2s = nullptr, *bN = nullptr, *bZ = nullptr, *kidbase = nullptr, *entbase = nullptr, *crowded = nullptr, *pz = nullptr;
-             BucketStats *gstat = nullptr; const uint32_t *clist = nullptr, *pbase = nullptr; const uint64_t *cdist = nullptr; const uint32_t *dist_base = nullptr; BucketStats hs{}; } ps;
-    // value-range batching (the section "VALUE-RANGE BATCHING" below): the passes, and what phase A learnt of each
-    // (nb1, nb2, T, e: the pass's partition — fixed for k <= 17; the wide partition's passes cut their range finer, below; ncrowded, crowded_small, np: its crowded buckets,
-    //  those with a small folded entry count, its pseudo-buckets)
-    struct Pass { uint32_t dlo = 0, dhi = 0; uint64_t I = 0, N = 0, Z = 0; BucketStats hs{}; uint32_t nb1 = 0, nb2 = 0; int T = 0, e = 0; int64_t ncrowded = 0, crowded_small = 0; uint32_t np = 0; };
-    std::vector<Pass> passes;
-    uint64_t largest = I;      // instances of the largest pass
-    std::function<void(uint32_t, uint32_t, uint64_t, bool)> partition_count;
-    std::function<void(const Pass &, bool)> wide_count;
-    // k-mers and entries in front of every bucket (+ the totals), the count kernels' statistics: one host round trip.  The counts scanned are bN / bZ,
-    // or — crowded buckets of the wide partition — copies with the pseudo-buckets' counts folded in (the emit kernels read bZ: a crowded parent stays 0 there)
-    uint32_t *sN = bN, *sZ = bZ;
-    auto scan_buckets = [&](BucketStats *hs_out, uint64_t *N_out, uint64_t *Z_out) {
-        ELBA_HIP(hipMemsetAsync(sN + nbuckets, 0, 4, s)); ELBA_HIP(hipMemsetAsync(sZ + nbuckets, 0, 4, s));
-        exclusive_scan_u32(s, sN, kidbase, (int64_t)nbuckets + 1, c.ws_scan);
-        exclusive_scan_u32(s, sZ, entbase, (int64_t)nbuckets + 1, c.ws_scan);      // (a pass holds fewer than 2^32 instances)
-        if (!hs_out) return;
-        uint32_t h2[2] = {0, 0};
-        ELBA_HIP(hipMemcpyAsync(&h2[0], kidbase + nbuckets, 4, hipMemcpyDeviceToHost, s));
-        ELBA_HIP(hipMemcpyAsync(&h2[1], entbase + nbuckets, 4, hipMemcpyDeviceToHost, s));
-        ELBA_HIP(hipMemcpyAsync(hs_out, gstat, sizeof(BucketStats), hipMemcpyDeviceToHost, s));
-        ELBA_HIP(hipStreamSynchronize(s));
-        *N_out = h2[0]; *Z_out = h2[1];
-    };
-    // the scan over the buckets of a pass (or of the whole input) — k-mer ids and entries of the passes before it added (Nprev, Zprev) —, the checks of the wide
-    // partition's crowded parents and its pseudo-buckets' bases; the pass's counts and statistics into pp; tally: the crowded buckets count towards the stage's statistics
-    auto scan_pass = [&](Pass &pp, uint64_t Nprev, uint64_t Zprev, bool tally) {
-        std::vector<uint32_t> pz;
-        if (ps.on) {
-            ELBA_HIP(hipMemcpyAsync(&ps.hs, ps.gstat, sizeof(BucketStats), hipMemcpyDeviceToHost, s));
-            pz.resize((size_t)ps.nc * 2);
-            hipLaunchKernelGGL(k31_parent_counts, dim3((ps.nc + 255) / 256), dim3(256), 0, s, ps.clist, ps.nc, (const uint32_t *)sZ, (const uint32_t *)bZ, ps.pz);
-            ELBA_HIP(hipMemcpyAsync(pz.data(), ps.pz, (size_t)ps.nc * 8, hipMemcpyDeviceToHost, s));
-        }
-        scan_buckets(&pp.hs, &pp.N, &pp.Z);
-        if (Nprev) hipLaunchKernelGGL(k_add_u32, dim3((nbuckets + 1 + 255) / 256), dim3(256), 0, s, kidbase, nbuckets + 1, (uint32_t)Nprev);
-        if (Zprev) hipLaunchKernelGGL(k_add_u32, dim3((nbuckets + 1 + 255) / 256), dim3(256), 0, s, entbase, nbuckets + 1, (uint32_t)Zprev);
-        pp.crowded_small = 0;
-        if (ps.on) {
-            for (uint32_t p = 0; p < ps.nc; ++p) pp.crowded_small += pz[p] > 0u && pz[p] <= small_cap ? 1 : 0;
-            if (tally) { c.kmer_crowded += ps.nc; c.kmer_crowded_small += pp.crowded_small; }      // (set before the check below: they describe the input)
-            for (uint32_t p = 0; p < ps.nc; ++p)
-                ELBA_REQUIRE(pz[ps.nc + p] == 0u, ELBA_ERR_INTERNAL, "count_kmers: a crowded bucket of the wide partition is visible to the main emit kernels");
-            hipLaunchKernelGGL(k31_pseudo_bases, dim3((ps.nc + 255) / 256), dim3(256), 0, s, (const uint32_t *)kidbase, (const uint32_t *)entbase, ps.clist, ps.pbase, ps.nc, (const uint32_t *)ps.bN, (const uint32_t *)ps.bZ, ps.kidbase, ps.entbase);
-            pp.hs.distinct += ps.hs.distinct; pp.hs.sumsq += ps.hs.sumsq; pp.hs.maxcol = std::max(pp.hs.maxcol, ps.hs.maxcol);
-        }
-        pp.ncrowded = ps.on ? ps.nc : pp.hs.ncrowded;
-        pp.np = ps.on ? ps.np : 0u;
-    };
-    if (!wide) {
-    const int shift2 = m.PB + vb;
+    std::vector<CountedPass> passes;
+    uint64_t largest = 0;      // instances of the largest pass
+    // the totals over the passes (total_passes): ncrowded / crowded_small: the statistics kmer_crowded_buckets / kmer_crowded_small; np_max: pseudo-buckets of the pass that has the most
+    BucketStats hs{};
+    uint64_t N = 0, Z = 0;
+    int64_t ncrowded = 0, crowded_small = 0;
+    uint32_t np_max = 0;
+    // the layout of A (layout_output)
+    int nb = 0, pb = 0, rs = 0, pbi = 0;
+    bool words = false, hints = false, inl = false, pairs = false, compact = false, mprep = false;
+    EmitGrids grids{};
+    MsdRun(Ctx &c_, const MsdPlan &pl_, const MsdTriples *tri_) : c(c_), pl(pl_), tri(tri_), s(c_.stream) {}
+
+    // the partition's buffers and histogram, wherever their workspaces lie NOW (a reserve() moves them: ws_sort under the sort of crowded buckets,
+    // ws_a / ws_c once the passes are planned)
+    uint32_t *hist() const { return c.ws_sort.as<uint32_t>(); }
+    uint64_t *wa() const { return c.ws_a.as<uint64_t>(); }
+    uint64_t *wb() const { return c.ws_c.as<uint64_t>(); }
+    // k <= 17: the first level's segments, the scatter kernels' grid, the second digit's shift
+    SegTiles seg() const { return SegTiles{b1start, tile0, pl.nb1, nullptr}; }
+    int shift2() const { return m.PB + pl.vb; }
 #ifndef ELBA_SCATTER_ONE_TILE
-    const uint32_t sgrid = c.opt.tune[0] == 1 ? 0xFFFFFFFFu : (uint32_t)c.num_cus * (MT_TILE <= 8192 ? 2u : 1u);      // (tune0 = 1: a workgroup per tile — A/B)
+    uint32_t sgrid() const { return c.opt.tune[0] == 1 ? 0xFFFFFFFFu : (uint32_t)c.num_cus * (MT_TILE <= 8192 ? 2u : 1u); }      // (tune0 = 1: a workgroup per tile — A/B)
 #else
-    const uint32_t sgrid = 0xFFFFFFFFu;      // a workgroup per tile
+    uint32_t sgrid() const { return 0xFFFFFFFFu; }      // a workgroup per tile
 #endif
-    if (tri) {
+
+    // Workspaces, timers, the reads' block table.  Leaves: bt and the segment arrays carved from ws_e, m, e, bi; t_total and t_a running.
+    void begin()
+    {
+        const bool wide = pl.wide;
+        const uint64_t I = pl.I;
+        m.k2 = pl.k2; m.b1 = pl.b1; m.b2 = pl.b2; m.I = I; m.pbits = pl.pbits; m.PB = pl.PB; m.rk = pl.rk; m.rkmask = pl.rkmask; m.dup = pl.dup;
+        const uint32_t nbk_cap = pl.nbk_cap, nb1_cap = pl.nb1_cap, ntiles2 = pl.ntiles2;
+        // (value-range batching: a pass takes whole first digits — one digit may hold most of the input: a homopolymer, AT-rich reads —, the two partition
+        //  buffers are sized by the largest pass once the passes are planned, and every pass is checked against them)
+        if (!pl.batched) { c.ws_a.reserve((size_t)(I + 2) * (wide ? 16 : 8)); c.ws_c.reserve((size_t)(I + 2) * (wide ? 16 : 8)); }
+        c.ws_sort.reserve(((size_t)ntiles2 << (wide ? W2_MAXBITS : MT_MAXBITS)) * 4 + 4096);
+        const size_t e_bytes = (size_t)(nbk_cap + 2) * 4 * 6 + (size_t)(2 * nb1_cap + 8) * 4 + 256 + 64 + (size_t)(ntiles2 + 4) * 8;
+        c.ws_e.reserve(e_bytes);
+        Carver ce(c.ws_e);
+        static_assert(sizeof(BucketStats) <= 64, "the statistics sit in front of the bucket arrays");
+        bt.gstat = ce.take<BucketStats>(1);
+        bt.b2start = ce.take<uint32_t>(nbk_cap + 2, 64); bt.bN = ce.take<uint32_t>(nbk_cap + 2); bt.bZ = ce.take<uint32_t>(nbk_cap + 2); bt.kidbase = ce.take<uint32_t>(nbk_cap + 2); bt.entbase = ce.take<uint32_t>(nbk_cap + 2); bt.crowded = ce.take<uint32_t>(nbk_cap + 2);
+        b1start = ce.take<uint32_t>(nb1_cap + 2); tile0 = ce.take<uint32_t>(nb1_cap + 2);
+        one_seg = ce.take<uint32_t>(16);      // (triples: the whole input as ONE segment of tiles, for the first digit's pass; one_seg + 4: the counter of bad indices)
+        tinfo = ce.take<uint2>(ntiles2 + 4, 16);      // (k <= 17: the second pass's tiles)
+        ce.fits(e_bytes);
+        bt.nbuckets = pl.nbuckets;
+        sN = bt.bN; sZ = bt.bZ;
+        c.t_total.start(s);
+        c.t_a.start(s);
+        e.packed = c.d_packed; e.byte_off = c.d_byte_off; e.len = c.d_len; e.inst_off = c.inst_off.as<uint64_t>();
+        e.nreads = (uint32_t)c.nreads; e.I = I; e.k = pl.k;
+        const uint64_t nib = (I >> IB_SHIFT) + 1;
+        if (!tri) c.ws_b.reserve((size_t)(nib + 1) * sizeof(BlockInfo));
+        bi = c.ws_b.as<BlockInfo>();
+        if (!tri) hipLaunchKernelGGL(k_block_reads, dim3((unsigned)((nib + 255) / 256)), dim3(256), 0, s, e.inst_off, e.byte_off, e.nreads, nib, c.ws_b.as<BlockInfo>());
+        static DeviceOnce attr_once;
+        attr_once.run(c.device, [&] {
+            ELBA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_msd_count<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            ELBA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_msd_count<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            ELBA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_msd_bucket<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            ELBA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k31_count), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        });
+        passes.assign(1, CountedPass{whole_pass(pl)});
+        largest = I;
+    }
+
+    // Triples: packed, partitioned on both digits, every bucket's columns and entries counted (k_tri_stats).  Leaves: the partitioned words in wb (they ARE
+    // the entries), bt.b2start / bN / bZ / gstat, the bad-index counter at one_seg + 4; the scan takes the plain counts; t_a stopped, t_b running.
+    void partition_triples()
+    {
+        const uint64_t I = pl.I;
+        const uint32_t nb1 = pl.nb1, nb2 = pl.nb2, ntiles1 = pl.ntiles1, ntiles2 = pl.ntiles2;
+        const SegTiles sg = seg();
         // first digit, from the packed triples: one segment of ntiles1 tiles
-        const uint32_t seg[4] = {0u, (uint32_t)I, 0u, ntiles1};
-        ELBA_HIP(hipMemcpyAsync(one_seg, seg, sizeof(seg), hipMemcpyHostToDevice, s));
+        const uint32_t seg1[4] = {0u, (uint32_t)I, 0u, ntiles1};
+        ELBA_HIP(hipMemcpyAsync(one_seg, seg1, sizeof(seg1), hipMemcpyHostToDevice, s));
         SegTiles sg1{one_seg, one_seg + 2, 1u};
         unsigned long long *badctr = reinterpret_cast<unsigned long long *>(one_seg + 4);
         ELBA_HIP(hipMemsetAsync(badctr, 0, 8, s));
-        hipLaunchKernelGGL(k_pack_triple_msd, dim3((unsigned)((I + 255) / 256)), dim3(256), 0, s, tri->rows, tri->cols, tri->vals, I, tri->M, tri->N, m.pbits, m.PB, wb, badctr);
-        hipLaunchKernelGGL(k_msd_hist2, dim3(ntiles1), dim3(MT_THREADS), 0, s, (const uint64_t *)wb, sg1, shift2 + m.b2, m.b1, hist);
-        radix_column_scan(s, hist, (int64_t)ntiles1, nb1, c.ws_scan);
-        hipLaunchKernelGGL(k_msd_tiles, dim3(1), dim3(MT_MAXBINS), 0, s, (const uint32_t *)hist, nb1, I, b1start, tile0);
-        hipLaunchKernelGGL((k_msd_scatter<false>), dim3(std::min<uint32_t>(ntiles1, sgrid)), dim3(MT_THREADS), 0, s, e, bi, m, (const uint64_t *)wb, sg1, shift2 + m.b2, m.b1, (const uint32_t *)hist, wa, ntiles1, 0u, nb1);
-    // second digit, inside every first-digit bucket
-    hipLaunchKernelGGL(k_msd_hist2, dim3(ntiles2), dim3(MT_THREADS), 0, s, (const uint64_t *)wa, sg, shift2, m.b2, hist);
-    hipLaunchKernelGGL(k_msd_segscan, dim3(nb1), dim3(MT_MAXBINS), 0, s, hist, sg, nb2, b2start, I);
-    hipLaunchKernelGGL((k_msd_scatter<false>), dim3(std::min<uint32_t>(ntiles2, sgrid)), dim3(MT_THREADS), 0, s, e, bi, m, (const uint64_t *)wa, sg, shift2, m.b2, (const uint32_t *)hist, wb, ntiles2, 0u, nb1);
-    c.t_a.stop(s);
-    c.t_b.start(s);
-    ELBA_HIP(hipMemsetAsync(gstat, 0, sizeof(BucketStats), s));
-    hipLaunchKernelGGL(k_tri_stats, dim3((unsigned)std::min<uint32_t>(nbuckets, (uint32_t)c.num_cus * 8u)), dim3(256), 0, s, (const uint64_t *)wb, (const uint32_t *)b2start, nbuckets, m.PB, m.rkmask, small_cap, bN, bZ, gstat);
-    } else {
-    // The reads' instances whose FIRST digit lies in [dlo, dhi) — Iv of them; one pass: every instance —: two-level partition, then one workgroup per bucket
-    // counts.  hist1 and the first scatter enumerate ALL reads (tiles of the whole instance range) and keep their pass's instances.
-    partition_count = [&, shift2, sgrid](uint32_t dlo, uint32_t dhi, uint64_t Iv, bool timed) {
+        hipLaunchKernelGGL(k_pack_triple_msd, dim3((unsigned)((I + 255) / 256)), dim3(256), 0, s, tri->rows, tri->cols, tri->vals, I, tri->M, tri->N, m.pbits, m.PB, wb(), badctr);
+        hipLaunchKernelGGL(k_msd_hist2, dim3(ntiles1), dim3(MT_THREADS), 0, s, (const uint64_t *)wb(), sg1, shift2() + m.b2, m.b1, hist());
+        radix_column_scan(s, hist(), (int64_t)ntiles1, nb1, c.ws_scan);
+        hipLaunchKernelGGL((k_tiles<MT_TILE, MT_MAXBINS>), dim3(1), dim3(MT_MAXBINS), 0, s, (const uint32_t *)hist(), nb1, I, b1start, tile0);
+        hipLaunchKernelGGL((k_msd_scatter<false>), dim3(std::min<uint32_t>(ntiles1, sgrid())), dim3(MT_THREADS), 0, s, e, bi, m, (const uint64_t *)wb(), sg1, shift2() + m.b2, m.b1, (const uint32_t *)hist(), wa(), ntiles1, 0u, nb1);
+        // second digit, inside every first-digit bucket
+        hipLaunchKernelGGL(k_msd_hist2, dim3(ntiles2), dim3(MT_THREADS), 0, s, (const uint64_t *)wa(), sg, shift2(), m.b2, hist());
+        hipLaunchKernelGGL(k_msd_segscan, dim3(nb1), dim3(MT_MAXBINS), 0, s, hist(), sg, nb2, bt.b2start, I);
+        hipLaunchKernelGGL((k_msd_scatter<false>), dim3(std::min<uint32_t>(ntiles2, sgrid())), dim3(MT_THREADS), 0, s, e, bi, m, (const uint64_t *)wa(), sg, shift2(), m.b2, (const uint32_t *)hist(), wb(), ntiles2, 0u, nb1);
+        c.t_a.stop(s);
+        c.t_b.start(s);
+        ELBA_HIP(hipMemsetAsync(bt.gstat, 0, sizeof(BucketStats), s));
+        hipLaunchKernelGGL(k_tri_stats, dim3((unsigned)std::min<uint32_t>(bt.nbuckets, (uint32_t)c.num_cus * 8u)), dim3(256), 0, s, (const uint64_t *)wb(), (const uint32_t *)bt.b2start, bt.nbuckets, m.PB, m.rkmask, pl.small_cap, bt.bN, bt.bZ, bt.gstat);
+        bt.words = wb(); bt.wrel = wb();      // (triples: the partitioned words are the entries)
+        ps.on = false; sN = bt.bN; sZ = bt.bZ;
+    }
+
+    // k <= 17.  The reads' instances whose FIRST digit lies in [dlo, dhi) — pp.I of them; one pass: every instance —: two-level partition, then one
+    // workgroup per bucket counts.  hist1 and the first scatter enumerate ALL reads (tiles of the whole instance range) and keep their pass's instances.
+    // Leaves: the partitioned words in wb (bt.words), the kept entries in wa (bt.wrel), bt.b2start / bN / bZ / crowded / gstat; the scan takes the plain
+    // counts.  timed (one pass): t_a | t_b switch between the partition and the count.
+    void partition_narrow(const Pass &pp, bool timed)
+    {
+        const uint32_t dlo = pp.dlo, dhi = pp.dhi, nb1 = pl.nb1, nb2 = pl.nb2, ntiles1 = pl.ntiles1, nbuckets = bt.nbuckets;
+        const uint64_t Iv = pp.I;
         ELBA_REQUIRE(Iv + 2 <= std::min(c.ws_a.cap, c.ws_c.cap) / 8, ELBA_ERR_INTERNAL, "count_kmers: a value-range pass is larger than its partition buffers");
-        const uint32_t nt2 = (uint32_t)((Iv + tile - 1) / tile) + nb1;
+        const uint32_t nt2 = (uint32_t)((Iv + pl.tile - 1) / pl.tile) + nb1;
+        const SegTiles sg = seg();
         if (timed) c.t_a.start(s);
-        hipLaunchKernelGGL(k_msd_hist1, dim3(ntiles1), dim3(MT_THREADS), 0, s, e, bi, m, hist, dlo, dhi);
-        radix_column_scan(s, hist, (int64_t)ntiles1, nb1, c.ws_scan);
-        hipLaunchKernelGGL(k_msd_tiles, dim3(1), dim3(MT_MAXBINS), 0, s, (const uint32_t *)hist, nb1, Iv, b1start, tile0);
-        if (batched) hipLaunchKernelGGL((k_msd_scatter<true, true>), dim3(std::min<uint32_t>(ntiles1, sgrid)), dim3(MT_THREADS), 0, s, e, bi, m, (const uint64_t *)nullptr, sg, 0, m.b1, (const uint32_t *)hist, wa, ntiles1, dlo, dhi);
-        else hipLaunchKernelGGL((k_msd_scatter<true, false>), dim3(std::min<uint32_t>(ntiles1, sgrid)), dim3(MT_THREADS), 0, s, e, bi, m, (const uint64_t *)nullptr, sg, 0, m.b1, (const uint32_t *)hist, wa, ntiles1, dlo, dhi);
+        hipLaunchKernelGGL(k_msd_hist1, dim3(ntiles1), dim3(MT_THREADS), 0, s, e, bi, m, hist(), dlo, dhi);
+        radix_column_scan(s, hist(), (int64_t)ntiles1, nb1, c.ws_scan);
+        hipLaunchKernelGGL((k_tiles<MT_TILE, MT_MAXBINS>), dim3(1), dim3(MT_MAXBINS), 0, s, (const uint32_t *)hist(), nb1, Iv, b1start, tile0);
+        if (pl.batched) hipLaunchKernelGGL((k_msd_scatter<true, true>), dim3(std::min<uint32_t>(ntiles1, sgrid())), dim3(MT_THREADS), 0, s, e, bi, m, (const uint64_t *)nullptr, sg, 0, m.b1, (const uint32_t *)hist(), wa(), ntiles1, dlo, dhi);
+        else hipLaunchKernelGGL((k_msd_scatter<true, false>), dim3(std::min<uint32_t>(ntiles1, sgrid())), dim3(MT_THREADS), 0, s, e, bi, m, (const uint64_t *)nullptr, sg, 0, m.b1, (const uint32_t *)hist(), wa(), ntiles1, dlo, dhi);
         // second digit, inside every first-digit bucket
         SegTiles sgi = sg; sgi.tinfo = tinfo;
         hipLaunchKernelGGL(k_msd_tile_info, dim3((nt2 + 255u) / 256u), dim3(256), 0, s, sg, tinfo);
-        hipLaunchKernelGGL(k_msd_hist2, dim3(nt2), dim3(MT_THREADS), 0, s, (const uint64_t *)wa, sgi, shift2, m.b2, hist);
-        hipLaunchKernelGGL(k_msd_segscan, dim3(nb1), dim3(MT_MAXBINS), 0, s, hist, sg, nb2, b2start, Iv);
-        hipLaunchKernelGGL((k_msd_scatter<false>), dim3(std::min<uint32_t>(nt2, sgrid)), dim3(MT_THREADS), 0, s, e, bi, m, (const uint64_t *)wa, sgi, shift2, m.b2, (const uint32_t *)hist, wb, nt2, 0u, nb1);
+        hipLaunchKernelGGL(k_msd_hist2, dim3(nt2), dim3(MT_THREADS), 0, s, (const uint64_t *)wa(), sgi, shift2(), m.b2, hist());
+        hipLaunchKernelGGL(k_msd_segscan, dim3(nb1), dim3(MT_MAXBINS), 0, s, hist(), sg, nb2, bt.b2start, Iv);
+        hipLaunchKernelGGL((k_msd_scatter<false>), dim3(std::min<uint32_t>(nt2, sgrid())), dim3(MT_THREADS), 0, s, e, bi, m, (const uint64_t *)wa(), sgi, shift2(), m.b2, (const uint32_t *)hist(), wb(), nt2, 0u, nb1);
 #ifdef ELBA_SCATTER_CLOCK
         {
             ELBA_HIP(hipStreamSynchronize(s));
@@ -2085,414 +2051,446 @@ static bool msd_run(Ctx &c, uint64_t I, elba_kmer_stats *stp, MsdTriples *tri)
 #endif
         if (timed) { c.t_a.stop(s); c.t_b.start(s); }
         // buckets: count
-        ELBA_HIP(hipMemsetAsync(gstat, 0, sizeof(BucketStats), s));
+        ELBA_HIP(hipMemsetAsync(bt.gstat, 0, sizeof(BucketStats), s));
         const unsigned bgrid = (unsigned)std::min<uint32_t>(nbuckets, (uint32_t)c.num_cus);
         // (columns of up to HINT_MAX_COL entries: the value bits spread a bucket's entries evenly over the emit kernels' sort ranges already)
-        // entries per bucket: up to 2048 / 4096 / 8192 -> k_msd_emit_small on 256 / 512 / 1024 lanes, beyond -> k_msd_bucket (option "msd_small_cap": tests lower the last bound)
         // (the first pass's words are dead: their buffer takes the entries — the instances of reliable k-mers —, bucket by bucket)
-        if (m.rk != 0) hipLaunchKernelGGL(k_msd_count<true>, dim3(bgrid), dim3(BK_THREADS), CT_LDS, s, (const uint64_t *)wb, (const uint32_t *)b2start, nbuckets, m, lower, upper, small_cap, bN, bZ, gstat, crowded, wa);
-        else hipLaunchKernelGGL(k_msd_count<false>, dim3(bgrid), dim3(BK_THREADS), CT_LDS, s, (const uint64_t *)wb, (const uint32_t *)b2start, nbuckets, m, lower, upper, small_cap, bN, bZ, gstat, crowded, wa);
-    };
-    if (batched) {
-        // VALUE-RANGE BATCHING (round 5; include/elba_amd.h, "limits"): more instances than a 32-bit place holds (or than the option "kmer_batch_instances"
-        // allows) are counted in passes over RANGES OF FIRST DIGITS — the reference batches its exchange so that size is no limit (include/KmerOps.hpp:33-56)
-        // —: the buckets are value ranges, so pass after pass yields consecutive k-mer ids and consecutive stretches of the columns.  Planning: the
-        // per-digit totals of one unfiltered histogram; phase A (here): partition + count of every pass for N, Z and the longest column — what the layout
-        // of A depends on —; phase B (below): partition + count again, then the emit with the pass's id / entry bases.
-        hipLaunchKernelGGL(k_msd_hist1, dim3(ntiles1), dim3(MT_THREADS), 0, s, e, bi, m, hist, 0u, nb1);
-        c.ws_scan.reserve((size_t)nb1 * 8 + 64);
-        ELBA_HIP(hipMemsetAsync(c.ws_scan.p, 0, (size_t)nb1 * 8, s));
-        hipLaunchKernelGGL(k_msd_digit_totals, dim3((unsigned)((ntiles1 + 255) / 256)), dim3(nb1), 0, s, (const uint32_t *)hist, (uint64_t)ntiles1, nb1, c.ws_scan.as<unsigned long long>());
-        std::vector<unsigned long long> dt(nb1);
-        ELBA_HIP(hipMemcpyAsync(dt.data(), c.ws_scan.p, (size_t)nb1 * 8, hipMemcpyDeviceToHost, s));
-        ELBA_HIP(hipStreamSynchronize(s));
-        for (uint32_t d = 0; d < nb1;) {
-            Pass ps1{}; ps1.dlo = d;
-            do { ps1.I += dt[d]; ++d; } while (d < nb1 && ps1.I + dt[d] <= batch_cap);
-            ps1.dhi = d; ps1.nb1 = nb1; ps1.nb2 = nb2; ps1.T = T;
-            ELBA_REQUIRE(ps1.I < 0xFFFFFFF0ull, ELBA_ERR_UNSUPPORTED, "count_kmers: one first-digit bucket alone holds more than 2^32 k-mer instances");
-            if (ps1.I) passes.push_back(ps1);
-        }
-        if (c.opt.trace) fprintf(stderr, "[elba] count_kmers: %llu instances in %zu value-range passes\n", (unsigned long long)I, passes.size());
-        largest = 0;
-        for (const Pass &ps1 : passes) largest = std::max(largest, ps1.I);
-        c.kmer_largest_pass = (int64_t)largest;
-        c.ws_a.reserve((size_t)(largest + 2) * 8); c.ws_c.reserve((size_t)(largest + 2) * 8);
-        wa = c.ws_a.as<uint64_t>(); wb = c.ws_c.as<uint64_t>();
-        for (Pass &ps1 : passes) {
-            partition_count(ps1.dlo, ps1.dhi, ps1.I, false);
-            scan_buckets(&ps1.hs, &ps1.N, &ps1.Z);
-            ps1.ncrowded = ps1.hs.ncrowded;
-        }
-        c.t_a.stop(s); c.t_b.start(s);      // (the stage's two labels: phase A | phase B)
-    } else partition_count(0u, nb1, I, true);
+        if (m.rk != 0) hipLaunchKernelGGL(k_msd_count<true>, dim3(bgrid), dim3(BK_THREADS), CT_LDS, s, (const uint64_t *)wb(), (const uint32_t *)bt.b2start, nbuckets, m, pl.lower, pl.upper, pl.small_cap, bt.bN, bt.bZ, bt.gstat, bt.crowded, wa());
+        else hipLaunchKernelGGL(k_msd_count<false>, dim3(bgrid), dim3(BK_THREADS), CT_LDS, s, (const uint64_t *)wb(), (const uint32_t *)bt.b2start, nbuckets, m, pl.lower, pl.upper, pl.small_cap, bt.bN, bt.bZ, bt.gstat, bt.crowded, wa());
+        bt.words = wb(); bt.wrel = wa();
+        ps.on = false; sN = bt.bN; sZ = bt.bZ;
     }
-    } else {
-        // 19 <= k <= 31: 16-byte records (the section above k31_hist1).  A pass — the whole input, or under value-range batching the instances of the
-        // coarse digits [dlo, dhi) (the leading W2_MAXBITS bits of the flattened value) — is partitioned on its own T leading bits, its buckets counted,
-        // its crowded buckets cut into pseudo-buckets and counted.
-        wide_count = [&](const Pass &pp, bool timed) {
-            nb1 = pp.nb1; nb2 = pp.nb2; nbuckets = nb1 * nb2;
-            const int Tp = pp.T, b2 = bits_needed_u(nb2) - 1;
-            const uint64_t Iv = pp.I;
-            ELBA_REQUIRE(Iv + 2 <= std::min(c.ws_a.cap, c.ws_c.cap) / 16, ELBA_ERR_INTERNAL, "count_kmers: a value-range pass is larger than its partition buffers");
-            hist = c.ws_sort.as<uint32_t>();      // (the sort of an earlier pass's crowded buckets may have grown its workspace)
-            wa = c.ws_a.as<uint64_t>();
-            Rec2 *ra = c.ws_a.as<Rec2>(), *rb = c.ws_c.as<Rec2>();
-            const SegTiles sgw{b1start, tile0, nb1};
-            const uint32_t nt2 = batched ? (uint32_t)((Iv + tile - 1) / tile) + nb1 : ntiles2;
-            if (batched) {
-                // first level: the pass's coarse digits, each cut into 2^e: (flattened value >> (32 - W2_MAXBITS - e)) - (dlo << e); every read is enumerated again
-                const int sh1 = 32 - W2_MAXBITS - pp.e;
-                const uint32_t xlo = pp.dlo << pp.e;
-                hipLaunchKernelGGL((k31_hist1<true>), dim3(ntiles1), dim3(W2_THREADS), 0, s, e, bi, 0, hist, sh1, xlo, nb1);
-                radix_column_scan(s, hist, (int64_t)ntiles1, nb1, c.ws_scan);
-                hipLaunchKernelGGL(k31_tiles, dim3(1), dim3(W2_MAXBINS), 0, s, (const uint32_t *)hist, nb1, Iv, b1start, tile0);
-                hipLaunchKernelGGL((k31_scatter<true, true>), dim3(ntiles1), dim3(W2_THREADS), 0, s, e, bi, k2, m.pbits, (const Rec2 *)nullptr, sgw, sh1, 0, (const uint32_t *)hist, ra, xlo, nb1);
-            } else {
-                hipLaunchKernelGGL((k31_hist1<false>), dim3(ntiles1), dim3(W2_THREADS), 0, s, e, bi, m.b1, hist, 0, 0u, 0u);
-                radix_column_scan(s, hist, (int64_t)ntiles1, nb1, c.ws_scan);
-                hipLaunchKernelGGL(k31_tiles, dim3(1), dim3(W2_MAXBINS), 0, s, (const uint32_t *)hist, nb1, I, b1start, tile0);
-                hipLaunchKernelGGL((k31_scatter<true>), dim3(ntiles1), dim3(W2_THREADS), 0, s, e, bi, k2, m.pbits, (const Rec2 *)nullptr, sgw, 32 - m.b1, m.b1, (const uint32_t *)hist, ra, 0u, 0u);
-            }
-            hipLaunchKernelGGL(k31_hist2, dim3(nt2), dim3(W2_THREADS), 0, s, (const Rec2 *)ra, sgw, k2, 32 - Tp, b2, hist);
-            hipLaunchKernelGGL(k31_segscan, dim3(nb1), dim3(W2_MAXBINS), 0, s, hist, sgw, nb2, b2start, Iv);
-            hipLaunchKernelGGL((k31_scatter<false>), dim3(nt2), dim3(W2_THREADS), 0, s, e, bi, k2, m.pbits, (const Rec2 *)ra, sgw, 32 - Tp, b2, (const uint32_t *)hist, rb, 0u, 0u);
-            if (timed) { c.t_a.stop(s); c.t_b.start(s); }
-            ELBA_HIP(hipMemsetAsync(gstat, 0, sizeof(BucketStats), s));
-            // (the first pass's records are dead: the front half of their buffer takes the kept entries, one word each, the back half — behind the
-            //  largest pass's entries — the buckets' reliable k-mers)
-            hipLaunchKernelGGL(k31_count, dim3((unsigned)std::min<uint32_t>(nbuckets, (uint32_t)c.num_cus * (c.opt.tune[6] == 1 ? 1u : 2u))), dim3(W2C_THREADS), W2C_LDS, s, (const Rec2 *)rb, (const uint32_t *)b2start, nbuckets, k2, Tp, m.PB, m.rk,
-                               (uint32_t)c.cfg.lower, (uint32_t)c.cfg.upper, bN, bZ, gstat, wa, wa + (largest + 2), crowded);
-            o.kmer_src = wa + (largest + 2);
-            ps.on = false; sN = bN; sZ = bZ;
-            // buckets k31_count gave up (the section above k31_gather_crowded): taken out, sorted by k-mer, cut into pseudo-buckets of 2^16 distinct k-mers and
-            // counted by the k <= 17 kernel — their counts join their bucket's before the scan over the buckets
-            BucketStats hs0{};
-            ELBA_HIP(hipMemcpyAsync(&hs0, gstat, sizeof(hs0), hipMemcpyDeviceToHost, s));
-            ELBA_HIP(hipStreamSynchronize(s));
-            if (hs0.ncrowded) {
-                const uint32_t nc = hs0.ncrowded;
-                std::vector<uint32_t> clist(nc), hb2((size_t)nbuckets + 1);
-                ELBA_HIP(hipMemcpyAsync(clist.data(), crowded, (size_t)nc * 4, hipMemcpyDeviceToHost, s));
-                ELBA_HIP(hipMemcpyAsync(hb2.data(), b2start, ((size_t)nbuckets + 1) * 4, hipMemcpyDeviceToHost, s));
-                ELBA_HIP(hipStreamSynchronize(s));
-                std::sort(clist.begin(), clist.end());      // (bucket order = value order: what the sorted records follow)
-                std::vector<uint64_t> coff((size_t)nc + 1);
-                uint64_t Rc = 0;
-                for (uint32_t q = 0; q < nc; ++q) { coff[q] = Rc; Rc += hb2[clist[q] + 1] - hb2[clist[q]]; }
-                coff[nc] = Rc;
-                if (c.opt.trace) fprintf(stderr, "[elba] count_kmers: %u crowded buckets of the wide partition (%llu records) take the pseudo-bucket path\n", nc, (unsigned long long)Rc);
-                // workspace: two (key, value) buffer pairs for the sort, head flags + their scan, the distinct k-mers, the small per-bucket arrays
-                const size_t R8 = ((size_t)Rc + 8) * 8;
-                c.ws_g.reserve(4 * R8 + 2 * (((size_t)Rc + 8) * 4) + R8 + ((size_t)nc + 2) * 24 + 4096);
-                char *g0 = c.ws_g.as<char>();
-                uint64_t *ck0 = reinterpret_cast<uint64_t *>(g0), *cv0 = reinterpret_cast<uint64_t *>(g0 + R8), *ck1 = reinterpret_cast<uint64_t *>(g0 + 2 * R8), *cv1 = reinterpret_cast<uint64_t *>(g0 + 3 * R8);
-                uint32_t *head = reinterpret_cast<uint32_t *>(g0 + 4 * R8), *dpos = head + (Rc + 8);
-                uint64_t *cdist = reinterpret_cast<uint64_t *>(g0 + 4 * R8 + 2 * (((size_t)Rc + 8) * 4));
-                uint64_t *coff_d = reinterpret_cast<uint64_t *>(reinterpret_cast<char *>(cdist) + R8);
-                uint32_t *clist_d = reinterpret_cast<uint32_t *>(coff_d + (nc + 2)), *pbase_d = clist_d + (nc + 2), *dfirst_d = pbase_d + (nc + 2);
-                ELBA_HIP(hipMemcpyAsync(coff_d, coff.data(), ((size_t)nc + 1) * 8, hipMemcpyHostToDevice, s));
-                ELBA_HIP(hipMemcpyAsync(clist_d, clist.data(), (size_t)nc * 4, hipMemcpyHostToDevice, s));
-                hipLaunchKernelGGL(k31_gather_crowded, dim3(64, (unsigned)std::min<uint32_t>(nc, 1024u)), dim3(256), 0, s, (const Rec2 *)rb, (const uint32_t *)b2start, (const uint32_t *)clist_d, (const uint64_t *)coff_d, nc, ck0, cv0);
-                const int where = radix_sort_pairs(s, ck0, cv0, ck1, cv1, (int64_t)Rc, 0, k2, c.ws_sort);      // (stable; the order inside a k-mer is the emit kernels' business)
-                uint64_t *sk = where ? ck1 : ck0, *sv = where ? cv1 : cv0, *words2 = where ? ck0 : ck1, *wrel2 = where ? cv0 : cv1;
-                hipLaunchKernelGGL(k31_crowded_heads, dim3((unsigned)((Rc + 255) / 256)), dim3(256), 0, s, (const uint64_t *)sk, Rc, head);
-                exclusive_scan_u32(s, head, dpos, (int64_t)Rc, c.ws_scan);
-                hipLaunchKernelGGL(k_gather_u32_at, dim3((nc + 255) / 256), dim3(256), 0, s, (const uint32_t *)dpos, (const uint64_t *)coff_d, nc, dfirst_d);
-                std::vector<uint32_t> dfirst((size_t)nc + 1);
-                uint32_t lasth = 0, lastd = 0;
-                ELBA_HIP(hipMemcpyAsync(dfirst.data(), dfirst_d, (size_t)nc * 4, hipMemcpyDeviceToHost, s));
-                ELBA_HIP(hipMemcpyAsync(&lasth, head + (Rc - 1), 4, hipMemcpyDeviceToHost, s));
-                ELBA_HIP(hipMemcpyAsync(&lastd, dpos + (Rc - 1), 4, hipMemcpyDeviceToHost, s));
-                ELBA_HIP(hipStreamSynchronize(s));
-                dfirst[nc] = lastd + lasth;      // distinct k-mers of all crowded buckets
-                // a pseudo-bucket holds 2^pshift distinct k-mers: as many as make ~4096 records at the crowded buckets' average multiplicity (a satellite at 3-6
-                // copies: 1024 k-mers; HiFi coverage, every genomic k-mer ~34 times: 64) — one workgroup counts a pseudo-bucket, the emit kernels sort <= 12288 entries in LDS
-                uint32_t pshift = 16;
-                { const uint64_t D = std::max<uint32_t>(dfirst[nc], 1u); while (pshift > 4 && ((Rc << pshift) / D) > 4096) --pshift; }
-                std::vector<uint32_t> pbase((size_t)nc + 1);
-                uint32_t np = 0;
-                for (uint32_t q = 0; q < nc; ++q) { pbase[q] = np; np += (uint32_t)(((uint64_t)(dfirst[q + 1] - dfirst[q]) + (1u << pshift) - 1u) >> pshift); }
-                pbase[nc] = np;
-                ELBA_HIP(hipMemcpyAsync(pbase_d, pbase.data(), ((size_t)nc + 1) * 4, hipMemcpyHostToDevice, s));
-                c.ws_h.reserve(((size_t)np + 4) * 4 * 9 + ((size_t)nbuckets + 2) * 4 * 2 + ((size_t)nc + 2) * 4 * 2 + sizeof(BucketStats) + 256);
-                uint32_t *b2s = c.ws_h.as<uint32_t>() + 64, *parent_of = b2s + (np + 4), *dist_base = parent_of + (np + 4), *bN2 = dist_base + (np + 4), *bZ2 = bN2 + (np + 4),
-                         *kidbase2 = bZ2 + (np + 4), *entbase2 = kidbase2 + (np + 4), *crowded2 = entbase2 + (np + 4);
-                uint32_t *bNf = crowded2 + (np + 4), *bZf = bNf + (nbuckets + 2), *pz = bZf + (nbuckets + 2);      // (the counts the scan takes; the parents' counts for the host)
-                BucketStats *gstat2 = c.ws_h.as<BucketStats>();
-                static_assert(sizeof(BucketStats) <= 256, "the pseudo-buckets' statistics sit in front of their arrays");
-                hipLaunchKernelGGL(k31_crowded_words, dim3((unsigned)((Rc + 255) / 256)), dim3(256), 0, s, (const uint64_t *)sk, (const uint64_t *)sv, Rc, (const uint32_t *)head, (const uint32_t *)dpos, (const uint64_t *)coff_d,
-                                   (const uint32_t *)pbase_d, nc, k2, m.PB, pshift, words2, cdist, b2s, parent_of, dist_base);
-                const uint32_t rc32 = (uint32_t)Rc;
-                ELBA_HIP(hipMemcpyAsync(b2s + np, &rc32, 4, hipMemcpyHostToDevice, s));
-                ELBA_HIP(hipMemsetAsync(gstat2, 0, sizeof(BucketStats), s));
-                const unsigned pgrid = (unsigned)std::min<uint32_t>(np, (uint32_t)c.num_cus);
-                if (m.rk) hipLaunchKernelGGL(k_msd_count<true>, dim3(pgrid), dim3(BK_THREADS), CT_LDS, s, (const uint64_t *)words2, (const uint32_t *)b2s, np, m, (uint32_t)c.cfg.lower, (uint32_t)c.cfg.upper, small_cap, bN2, bZ2, gstat2, crowded2, wrel2);
-                else hipLaunchKernelGGL(k_msd_count<false>, dim3(pgrid), dim3(BK_THREADS), CT_LDS, s, (const uint64_t *)words2, (const uint32_t *)b2s, np, m, (uint32_t)c.cfg.lower, (uint32_t)c.cfg.upper, small_cap, bN2, bZ2, gstat2, crowded2, wrel2);
-                // the folded counts go to copies that only the scan over the buckets reads: k31_count never wrote a crowded parent's entries to wa, the
-                // main emit kernels must keep finding bZ = 0 there (a parent of 0 < Z <= small_cap was once sorted and emitted from stale records,
-                // across its neighbours' columns)
-                ELBA_HIP(hipMemcpyAsync(bNf, bN, (size_t)nbuckets * 4, hipMemcpyDeviceToDevice, s));
-                ELBA_HIP(hipMemcpyAsync(bZf, bZ, (size_t)nbuckets * 4, hipMemcpyDeviceToDevice, s));
-                hipLaunchKernelGGL(k31_fold_pseudo, dim3((np + 255) / 256), dim3(256), 0, s, (const uint32_t *)bN2, (const uint32_t *)bZ2, (const uint32_t *)parent_of, (const uint32_t *)clist_d, np, bNf, bZf);
-                sN = bNf; sZ = bZf;
-                ps.pz = pz;
-                ps.on = true; ps.nc = nc; ps.np = np; ps.words = words2; ps.wrel = wrel2; ps.b2s = b2s; ps.bN = bN2; ps.bZ = bZ2; ps.kidbase = kidbase2; ps.entbase = entbase2; ps.crowded = crowded2;
-                ps.gstat = gstat2; ps.clist = clist_d; ps.pbase = pbase_d; ps.cdist = cdist; ps.dist_base = dist_base;
-            }
-        };
-        Pass whole{}; whole.dlo = 0; whole.dhi = nb1; whole.I = I; whole.nb1 = nb1; whole.nb2 = nb2; whole.T = T;
-        if (batched) {
-            // VALUE-RANGE BATCHING of the wide partition, as for k <= 17 above: planned on the coarse digit (the leading W2_MAXBITS bits of the flattened
-            // value) of one unfiltered histogram; passes of whole coarse digits, balanced (as many as the cap demands, each near I / passes: the partition
-            // buffers are sized by the largest).  A pass partitions its own range: its first level takes e more bits of each of its coarse digits ((dhi - dlo) << e
-            // <= 2^10 digits), its second level b2 <= 10 bits, chosen as T is for one pass — a pass's buckets are as fine as those of an input of its size
-            // ("msd_wide_bits": the pass's T = 10 + e + b2 instead, b2 >= 1).  Phase A (here): partition + count + crowded buckets of every pass for N, Z
-            // and the longest column; phase B (emit_passes): all of it again, then the emit with the pass's id / entry bases.
-            hipLaunchKernelGGL((k31_hist1<false>), dim3(ntiles1), dim3(W2_THREADS), 0, s, e, bi, W2_MAXBITS, hist, 0, 0u, 0u);
-            c.ws_scan.reserve((size_t)W2_MAXBINS * 8 + 64);
-            ELBA_HIP(hipMemsetAsync(c.ws_scan.p, 0, (size_t)W2_MAXBINS * 8, s));
-            hipLaunchKernelGGL(k_msd_digit_totals, dim3((unsigned)((ntiles1 + 255) / 256)), dim3(W2_MAXBINS), 0, s, (const uint32_t *)hist, (uint64_t)ntiles1, (uint32_t)W2_MAXBINS, c.ws_scan.as<unsigned long long>());
-            std::vector<unsigned long long> dt(W2_MAXBINS);
-            ELBA_HIP(hipMemcpyAsync(dt.data(), c.ws_scan.p, (size_t)W2_MAXBINS * 8, hipMemcpyDeviceToHost, s));
-            ELBA_HIP(hipStreamSynchronize(s));
-            const uint64_t npass = (I + batch_cap - 1) / batch_cap, target = (I + npass - 1) / npass;
-            for (uint32_t d = 0; d < (uint32_t)W2_MAXBINS;) {
-                Pass p1{}; p1.dlo = d;
-                do { p1.I += dt[d]; ++d; } while (d < (uint32_t)W2_MAXBINS && p1.I + dt[d] <= batch_cap && p1.I + dt[d] / 2 <= target);
-                p1.dhi = d;
-                ELBA_REQUIRE(p1.I < 0xFFFFFFF0ull, ELBA_ERR_UNSUPPORTED, "count_kmers: one coarse digit of the wide partition alone holds more than 2^32 k-mer instances");
-                if (!p1.I) continue;
-                int e1 = 0;
-                while (e1 < W2_MAXBITS && ((p1.dhi - p1.dlo) << (e1 + 1)) <= (uint32_t)W2_MAXBINS) ++e1;
-                p1.e = e1; p1.nb1 = (p1.dhi - p1.dlo) << e1;
-                int b2 = 1;
-                while (b2 < W2_MAXBITS && ((p1.I >> b2) / p1.nb1) > 512) ++b2;
-                if (c.opt.msd_wide_bits > 0) b2 = std::min(std::max(c.opt.msd_wide_bits - W2_MAXBITS - e1, 1), W2_MAXBITS);
-                p1.nb2 = 1u << b2; p1.T = W2_MAXBITS + e1 + b2;
-                passes.push_back(p1);
-            }
-            if (c.opt.trace) fprintf(stderr, "[elba] count_kmers: %llu instances in %zu value-range passes of the wide partition\n", (unsigned long long)I, passes.size());
-            largest = 0;
-            for (const Pass &p1 : passes) largest = std::max(largest, p1.I);
-            c.kmer_largest_pass = (int64_t)largest;
-            c.ws_a.reserve((size_t)(largest + 2) * 16); c.ws_c.reserve((size_t)(largest + 2) * 16);
-            for (Pass &p1 : passes) {
-                wide_count(p1, false);
-                scan_pass(p1, 0, 0, true);
-            }
-            c.t_a.stop(s); c.t_b.start(s);      // (the stage's two labels: phase A | phase B)
+
+    // 19 <= k <= 31: 16-byte records (the section above k31_hist1).  A pass — the whole input, or under value-range batching the instances of the
+    // coarse digits [dlo, dhi) (the leading W2_MAXBITS bits of the flattened value) — is partitioned on its own T leading bits and its buckets counted.
+    // Leaves: bt (nbuckets = the pass's; words = NULL: no crowded-bucket kernel), the kept entries in the front half of wa, o.kmer_src = the buckets'
+    // reliable k-mers behind them; the scan takes the plain counts, no pseudo-buckets — cut_crowded comes next.
+    void partition_wide(const Pass &pp, bool timed)
+    {
+        const uint32_t nb1 = pp.nb1, nb2 = pp.nb2, nbuckets = nb1 * nb2, ntiles1 = pl.ntiles1;
+        const int Tp = pp.T, b2 = bits_needed_u(nb2) - 1, k2 = pl.k2;
+        const uint64_t Iv = pp.I;
+        ELBA_REQUIRE(Iv + 2 <= std::min(c.ws_a.cap, c.ws_c.cap) / 16, ELBA_ERR_INTERNAL, "count_kmers: a value-range pass is larger than its partition buffers");
+        uint32_t *hist = this->hist();      // (the sort of an earlier pass's crowded buckets may have grown its workspace)
+        Rec2 *ra = c.ws_a.as<Rec2>(), *rb = c.ws_c.as<Rec2>();
+        const SegTiles sgw{b1start, tile0, nb1};
+        const uint32_t nt2 = pl.batched ? (uint32_t)((Iv + pl.tile - 1) / pl.tile) + nb1 : pl.ntiles2;
+        if (pl.batched) {
+            // first level: the pass's coarse digits, each cut into 2^e: (flattened value >> (32 - W2_MAXBITS - e)) - (dlo << e); every read is enumerated again
+            const int sh1 = 32 - W2_MAXBITS - pp.e;
+            const uint32_t xlo = pp.dlo << pp.e;
+            hipLaunchKernelGGL((k31_hist1<true>), dim3(ntiles1), dim3(W2_THREADS), 0, s, e, bi, 0, hist, sh1, xlo, nb1);
+            radix_column_scan(s, hist, (int64_t)ntiles1, nb1, c.ws_scan);
+            hipLaunchKernelGGL((k_tiles<W2_TILE, W2_MAXBINS>), dim3(1), dim3(W2_MAXBINS), 0, s, (const uint32_t *)hist, nb1, Iv, b1start, tile0);
+            hipLaunchKernelGGL((k31_scatter<true, true>), dim3(ntiles1), dim3(W2_THREADS), 0, s, e, bi, k2, m.pbits, (const Rec2 *)nullptr, sgw, sh1, 0, (const uint32_t *)hist, ra, xlo, nb1);
         } else {
-            passes.assign(1, whole);
-            wide_count(whole, true);
+            hipLaunchKernelGGL((k31_hist1<false>), dim3(ntiles1), dim3(W2_THREADS), 0, s, e, bi, m.b1, hist, 0, 0u, 0u);
+            radix_column_scan(s, hist, (int64_t)ntiles1, nb1, c.ws_scan);
+            hipLaunchKernelGGL((k_tiles<W2_TILE, W2_MAXBINS>), dim3(1), dim3(W2_MAXBINS), 0, s, (const uint32_t *)hist, nb1, pl.I, b1start, tile0);
+            hipLaunchKernelGGL((k31_scatter<true>), dim3(ntiles1), dim3(W2_THREADS), 0, s, e, bi, k2, m.pbits, (const Rec2 *)nullptr, sgw, 32 - m.b1, m.b1, (const uint32_t *)hist, ra, 0u, 0u);
         }
+        hipLaunchKernelGGL(k31_hist2, dim3(nt2), dim3(W2_THREADS), 0, s, (const Rec2 *)ra, sgw, k2, 32 - Tp, b2, hist);
+        hipLaunchKernelGGL(k31_segscan, dim3(nb1), dim3(W2_MAXBINS), 0, s, hist, sgw, nb2, bt.b2start, Iv);
+        hipLaunchKernelGGL((k31_scatter<false>), dim3(nt2), dim3(W2_THREADS), 0, s, e, bi, k2, m.pbits, (const Rec2 *)ra, sgw, 32 - Tp, b2, (const uint32_t *)hist, rb, 0u, 0u);
+        if (timed) { c.t_a.stop(s); c.t_b.start(s); }
+        ELBA_HIP(hipMemsetAsync(bt.gstat, 0, sizeof(BucketStats), s));
+        // (the first pass's records are dead: the front half of their buffer takes the kept entries, one word each, the back half — behind the
+        //  largest pass's entries — the buckets' reliable k-mers)
+        hipLaunchKernelGGL(k31_count, dim3((unsigned)std::min<uint32_t>(nbuckets, (uint32_t)c.num_cus * (c.opt.tune[6] == 1 ? 1u : 2u))), dim3(W2C_THREADS), W2C_LDS, s, (const Rec2 *)rb, (const uint32_t *)bt.b2start, nbuckets, k2, Tp, m.PB, m.rk,
+                           (uint32_t)c.cfg.lower, (uint32_t)c.cfg.upper, bt.bN, bt.bZ, bt.gstat, wa(), wa() + (largest + 2), bt.crowded);
+        o.kmer_src = wa() + (largest + 2);
+        bt.nbuckets = nbuckets; bt.words = nullptr; bt.wrel = wa();
+        ps.on = false; sN = bt.bN; sZ = bt.bZ;
     }
-    BucketStats hs{};
-    uint64_t N = 0, Z = 0;
-    unsigned long long nbad = 0;
-    int64_t ncrowded = 0, crowded_small = 0;      // (the statistics kmer_crowded_buckets / kmer_crowded_small)
-    uint32_t np_max = 0;                          // (pseudo-buckets of the pass that has the most)
-    if (batched) {      // (phase A has scanned every pass: the totals, and what the layout of A depends on)
-        for (const Pass &ps1 : passes) {
-            N += ps1.N; Z += ps1.Z; hs.distinct += ps1.hs.distinct; hs.sumsq += ps1.hs.sumsq; hs.maxcol = std::max(hs.maxcol, ps1.hs.maxcol);
-            ncrowded += ps1.ncrowded; crowded_small += ps1.crowded_small; np_max = std::max(np_max, ps1.np);
-        }
-    } else {
-        if (tri) ELBA_HIP(hipMemcpyAsync(&nbad, one_seg + 4, 8, hipMemcpyDeviceToHost, s));
-        if (passes.empty()) { Pass whole{}; whole.dlo = 0; whole.dhi = nb1; whole.I = I; whole.nb1 = nb1; whole.nb2 = nb2; whole.T = T; passes.assign(1, whole); }
-        Pass &whole = passes[0];
-        scan_pass(whole, 0, 0, true);
-        hs = whole.hs; N = whole.N; Z = whole.Z; ncrowded = whole.ncrowded; crowded_small = whole.crowded_small; np_max = whole.np;
+
+    // The buckets k31_count gave up (the section above k31_gather_crowded): taken out, sorted by k-mer, cut into pseudo-buckets of 2^16 distinct k-mers and
+    // counted by the k <= 17 kernel — their counts join their bucket's before the scan over the buckets.  Reads the partitioned records in ws_c and bt
+    // as partition_wide left them.  Leaves, if the pass has crowded buckets: ps (on, the pseudo-buckets' table in ws_g / ws_h), sN / sZ = the folded counts.
+    void cut_crowded(const Pass &)
+    {
+        const Rec2 *rb = c.ws_c.as<Rec2>();
+        const uint32_t nbuckets = bt.nbuckets;
+        const int k2 = pl.k2;
+        BucketStats hs0{};
+        ELBA_HIP(hipMemcpyAsync(&hs0, bt.gstat, sizeof(hs0), hipMemcpyDeviceToHost, s));
+        ELBA_HIP(hipStreamSynchronize(s));
+        if (!hs0.ncrowded) return;
+        const uint32_t nc = hs0.ncrowded;
+        std::vector<uint32_t> clist(nc), hb2((size_t)nbuckets + 1);
+        ELBA_HIP(hipMemcpyAsync(clist.data(), bt.crowded, (size_t)nc * 4, hipMemcpyDeviceToHost, s));
+        ELBA_HIP(hipMemcpyAsync(hb2.data(), bt.b2start, ((size_t)nbuckets + 1) * 4, hipMemcpyDeviceToHost, s));
+        ELBA_HIP(hipStreamSynchronize(s));
+        std::sort(clist.begin(), clist.end());      // (bucket order = value order: what the sorted records follow)
+        std::vector<uint64_t> coff((size_t)nc + 1);
+        uint64_t Rc = 0;
+        for (uint32_t q = 0; q < nc; ++q) { coff[q] = Rc; Rc += hb2[clist[q] + 1] - hb2[clist[q]]; }
+        coff[nc] = Rc;
+        if (c.opt.trace) fprintf(stderr, "[elba] count_kmers: %u crowded buckets of the wide partition (%llu records) take the pseudo-bucket path\n", nc, (unsigned long long)Rc);
+        // workspace: two (key, value) buffer pairs for the sort, head flags + their scan, the distinct k-mers, the small per-bucket arrays
+        const size_t R = (size_t)Rc + 8, R8 = R * 8;
+        const size_t g_bytes = 4 * R8 + 2 * (R * 4) + R8 + ((size_t)nc + 2) * 24 + 4096;
+        c.ws_g.reserve(g_bytes);
+        Carver cg(c.ws_g);
+        uint64_t *ck0 = cg.take<uint64_t>(R), *cv0 = cg.take<uint64_t>(R), *ck1 = cg.take<uint64_t>(R), *cv1 = cg.take<uint64_t>(R);
+        uint32_t *head = cg.take<uint32_t>(R), *dpos = cg.take<uint32_t>(R);
+        uint64_t *cdist = cg.take<uint64_t>(R), *coff_d = cg.take<uint64_t>(nc + 2);
+        uint32_t *clist_d = cg.take<uint32_t>(nc + 2), *pbase_d = cg.take<uint32_t>(nc + 2), *dfirst_d = cg.take<uint32_t>(nc + 2);
+        cg.fits(g_bytes);
+        ELBA_HIP(hipMemcpyAsync(coff_d, coff.data(), ((size_t)nc + 1) * 8, hipMemcpyHostToDevice, s));
+        ELBA_HIP(hipMemcpyAsync(clist_d, clist.data(), (size_t)nc * 4, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k31_gather_crowded, dim3(64, (unsigned)std::min<uint32_t>(nc, 1024u)), dim3(256), 0, s, rb, (const uint32_t *)bt.b2start, (const uint32_t *)clist_d, (const uint64_t *)coff_d, nc, ck0, cv0);
+        const int where = radix_sort_pairs(s, ck0, cv0, ck1, cv1, (int64_t)Rc, 0, k2, c.ws_sort);      // (stable; the order inside a k-mer is the emit kernels' business)
+        uint64_t *sk = where ? ck1 : ck0, *sv = where ? cv1 : cv0, *words2 = where ? ck0 : ck1, *wrel2 = where ? cv0 : cv1;
+        hipLaunchKernelGGL(k31_crowded_heads, dim3((unsigned)((Rc + 255) / 256)), dim3(256), 0, s, (const uint64_t *)sk, Rc, head);
+        exclusive_scan_u32(s, head, dpos, (int64_t)Rc, c.ws_scan);
+        hipLaunchKernelGGL(k_gather_u32_at, dim3((nc + 255) / 256), dim3(256), 0, s, (const uint32_t *)dpos, (const uint64_t *)coff_d, nc, dfirst_d);
+        std::vector<uint32_t> dfirst((size_t)nc + 1);
+        uint32_t lasth = 0, lastd = 0;
+        ELBA_HIP(hipMemcpyAsync(dfirst.data(), dfirst_d, (size_t)nc * 4, hipMemcpyDeviceToHost, s));
+        ELBA_HIP(hipMemcpyAsync(&lasth, head + (Rc - 1), 4, hipMemcpyDeviceToHost, s));
+        ELBA_HIP(hipMemcpyAsync(&lastd, dpos + (Rc - 1), 4, hipMemcpyDeviceToHost, s));
+        ELBA_HIP(hipStreamSynchronize(s));
+        dfirst[nc] = lastd + lasth;      // distinct k-mers of all crowded buckets
+        // a pseudo-bucket holds 2^pshift distinct k-mers: as many as make ~4096 records at the crowded buckets' average multiplicity (a satellite at 3-6
+        // copies: 1024 k-mers; HiFi coverage, every genomic k-mer ~34 times: 64) — one workgroup counts a pseudo-bucket, the emit kernels sort <= 12288 entries in LDS
+        uint32_t pshift = 16;
+        { const uint64_t D = std::max<uint32_t>(dfirst[nc], 1u); while (pshift > 4 && ((Rc << pshift) / D) > 4096) --pshift; }
+        std::vector<uint32_t> pbase((size_t)nc + 1);
+        uint32_t np = 0;
+        for (uint32_t q = 0; q < nc; ++q) { pbase[q] = np; np += (uint32_t)(((uint64_t)(dfirst[q + 1] - dfirst[q]) + (1u << pshift) - 1u) >> pshift); }
+        pbase[nc] = np;
+        ELBA_HIP(hipMemcpyAsync(pbase_d, pbase.data(), ((size_t)nc + 1) * 4, hipMemcpyHostToDevice, s));
+        const size_t h_bytes = ((size_t)np + 4) * 4 * 9 + ((size_t)nbuckets + 2) * 4 * 2 + ((size_t)nc + 2) * 4 * 2 + sizeof(BucketStats) + 256;
+        c.ws_h.reserve(h_bytes);
+        Carver ch(c.ws_h);
+        static_assert(sizeof(BucketStats) <= 256, "the pseudo-buckets' statistics sit in front of their arrays");
+        BucketTable pt;
+        pt.gstat = ch.take<BucketStats>(1);
+        pt.b2start = ch.take<uint32_t>(np + 4, 256);
+        uint32_t *parent_of = ch.take<uint32_t>(np + 4), *dist_base = ch.take<uint32_t>(np + 4);
+        pt.bN = ch.take<uint32_t>(np + 4); pt.bZ = ch.take<uint32_t>(np + 4); pt.kidbase = ch.take<uint32_t>(np + 4); pt.entbase = ch.take<uint32_t>(np + 4); pt.crowded = ch.take<uint32_t>(np + 4);
+        uint32_t *bNf = ch.take<uint32_t>(nbuckets + 2), *bZf = ch.take<uint32_t>(nbuckets + 2), *pz = ch.take<uint32_t>(((size_t)nc + 2) * 2);      // (the counts the scan takes; the parents' counts for the host)
+        ch.fits(h_bytes);
+        pt.words = words2; pt.wrel = wrel2; pt.nbuckets = np;
+        hipLaunchKernelGGL(k31_crowded_words, dim3((unsigned)((Rc + 255) / 256)), dim3(256), 0, s, (const uint64_t *)sk, (const uint64_t *)sv, Rc, (const uint32_t *)head, (const uint32_t *)dpos, (const uint64_t *)coff_d,
+                           (const uint32_t *)pbase_d, nc, k2, m.PB, pshift, words2, cdist, pt.b2start, parent_of, dist_base);
+        const uint32_t rc32 = (uint32_t)Rc;
+        ELBA_HIP(hipMemcpyAsync(pt.b2start + np, &rc32, 4, hipMemcpyHostToDevice, s));
+        ELBA_HIP(hipMemsetAsync(pt.gstat, 0, sizeof(BucketStats), s));
+        const unsigned pgrid = (unsigned)std::min<uint32_t>(np, (uint32_t)c.num_cus);
+        if (m.rk) hipLaunchKernelGGL(k_msd_count<true>, dim3(pgrid), dim3(BK_THREADS), CT_LDS, s, (const uint64_t *)words2, (const uint32_t *)pt.b2start, np, m, (uint32_t)c.cfg.lower, (uint32_t)c.cfg.upper, pl.small_cap, pt.bN, pt.bZ, pt.gstat, pt.crowded, wrel2);
+        else hipLaunchKernelGGL(k_msd_count<false>, dim3(pgrid), dim3(BK_THREADS), CT_LDS, s, (const uint64_t *)words2, (const uint32_t *)pt.b2start, np, m, (uint32_t)c.cfg.lower, (uint32_t)c.cfg.upper, pl.small_cap, pt.bN, pt.bZ, pt.gstat, pt.crowded, wrel2);
+        // the folded counts go to copies that only the scan over the buckets reads: k31_count never wrote a crowded parent's entries to wa, the
+        // main emit kernels must keep finding bZ = 0 there (a parent of 0 < Z <= small_cap was once sorted and emitted from stale records,
+        // across its neighbours' columns)
+        ELBA_HIP(hipMemcpyAsync(bNf, bt.bN, (size_t)nbuckets * 4, hipMemcpyDeviceToDevice, s));
+        ELBA_HIP(hipMemcpyAsync(bZf, bt.bZ, (size_t)nbuckets * 4, hipMemcpyDeviceToDevice, s));
+        hipLaunchKernelGGL(k31_fold_pseudo, dim3((np + 255) / 256), dim3(256), 0, s, (const uint32_t *)pt.bN, (const uint32_t *)pt.bZ, (const uint32_t *)parent_of, (const uint32_t *)clist_d, np, bNf, bZf);
+        sN = bNf; sZ = bZf;
+        ps.on = true; ps.nc = nc; ps.t = pt; ps.pz = pz; ps.clist = clist_d; ps.pbase = pbase_d; ps.cdist = cdist; ps.dist_base = dist_base;
     }
-    ELBA_REQUIRE(nbad == 0, ELBA_ERR_INVALID_ARG, "triple index out of range");
-    if (tri && (hs.ncrowded || (int64_t)N != tri->N || Z != I)) {      // an empty column (the buckets number the columns they find), a bucket beyond the LDS sort: matrix.hip sorts
-        if (c.opt.trace) fprintf(stderr, "[elba] set_kmer_matrix_device: %llu of %lld columns hold entries, %u crowded buckets: sorting instead\n", (unsigned long long)N, (long long)tri->N, hs.ncrowded);
-        c.t_b.stop(s); c.t_total.stop(s);
-        return false;
+
+    // k-mers and entries in front of every bucket of the current pass (+ the totals): the scan of sN / sZ into bt.kidbase / bt.entbase, on the device only
+    void scan_on_device()
+    {
+        const uint32_t nbuckets = bt.nbuckets;
+        ELBA_HIP(hipMemsetAsync(sN + nbuckets, 0, 4, s)); ELBA_HIP(hipMemsetAsync(sZ + nbuckets, 0, 4, s));
+        exclusive_scan_u32(s, sN, bt.kidbase, (int64_t)nbuckets + 1, c.ws_scan);
+        exclusive_scan_u32(s, sZ, bt.entbase, (int64_t)nbuckets + 1, c.ws_scan);      // (a pass holds fewer than 2^32 instances)
     }
-    ELBA_REQUIRE(Z < 0xFFFFFFF0ull, ELBA_ERR_UNSUPPORTED, "count_kmers: nnz(A) beyond 32-bit device offsets");
-    // buckets: emit
-    if (!tri) c.rel_kmers.reserve((size_t)(N + 1) * 8);
-    c.rel_counts.reserve((size_t)(N + 2) * 4);
-    c.a_colptr.reserve((size_t)(N + 2) * 4);
-    c.a_csc.reserve((size_t)(Z + 8) * 8);
-    const int nb = bits_needed_u((uint64_t)(N > 0 ? N - 1 : 0)), pb = m.pbits;
-    const bool words = mb + nb + pb + 2 <= 64 && !c.opt.csr_pairs;
-    const bool hints = pb <= 30 && !c.opt.no_hints;
-    o.rel_kmers = tri ? nullptr : c.rel_kmers.as<uint64_t>(); o.rel_counts = c.rel_counts.as<uint32_t>(); o.colptr = c.a_colptr.as<uint32_t>();
-    c.max_col_nnz = (int64_t)hs.maxcol;
-    choose_column_store(c, (int64_t)N, c.max_col_nnz);
-    // inline partners (Ctx::csr_inline): whole matrix, general (not dense) SpGEMM path with position-carrying accumulators, and a sort word wide
-    // enough for flag | read | partner >> 1 | posQ | posT
-    const bool dense = c.use_ell && maxpos < 65536 && c.max_col_nnz > 16 && !c.opt.no_pay && !c.opt.no_suffix;
-    // The inline key is flag | read << rs | (partner >> 1) << 2 pbi | posQ << pbi | posT with the read as high as it goes (rs = 63 - mb): pbi position
-    // bits are what is left, and an entry is written inline only if both positions fit them (200 100 reads of up to 16.6 kb: 14 bits, all but
-    // the last bases of a handful of reads)
-    int rs = nb + pb + 2, pbi = 0;
-    bool inl = words && hints && c.use_ell && !dense && maxpos < 65536 && !c.opt.no_pay && !c.opt.no_inline && !c.opt.no_symmetry && N < (1ull << 31) && mb >= 2;
-    if (inl) {
-        const int rs2 = 63 - mb;
-        pbi = std::min(pb, (rs2 - (mb - 1)) / 2);
-        if (rs2 >= rs && pbi >= 10) rs = rs2; else inl = false;
+    void add_bases(uint64_t Nprev, uint64_t Zprev)      // ... the k-mer ids and entries of the passes before it added
+    {
+        const uint32_t nbuckets = bt.nbuckets;
+        if (Nprev) hipLaunchKernelGGL(k_add_u32, dim3((nbuckets + 1 + 255) / 256), dim3(256), 0, s, bt.kidbase, nbuckets + 1, (uint32_t)Nprev);
+        if (Zprev) hipLaunchKernelGGL(k_add_u32, dim3((nbuckets + 1 + 255) / 256), dim3(256), 0, s, bt.entbase, nbuckets + 1, (uint32_t)Zprev);
     }
-    o.csc = c.a_csc.as<uint64_t>(); o.nb = nb; o.pb = pb; o.rs = rs; o.mb = mb; o.inl = inl ? (uint32_t)pbi : 0u; o.hints = hints && words && !dense ? 1u : 0u;
-    // a dense matrix's CSR build sorts (read, entry) pairs (matrix.hip, csr_suffix: the entry carries its column's length and its place in it — known
-    // here, where the column lies sorted in LDS): they are written instead of sort words, the values where a sort that ends in a_csr starts
-    // (not under value-range batching: phase B enumerates the reads again through the block table in ws_b, which the pairs would take — the sort words instead, as "csr_pairs_late")
-    const bool pairs = dense && N < (1ull << 32) && c.max_col_nnz < 128 && !c.opt.csr_pairs_late && !batched;
-    c.pre_pairs = pairs;
-    if (pairs) {
-        c.ws_b.reserve((size_t)(Z + 1) * 8); c.ws_d.reserve((size_t)(Z + 1) * 8); c.a_csr.reserve((size_t)(Z + 1) * 8);      // (ws_b: the enumeration's block table is dead)
-        o.pair_key = c.ws_b.as<uint32_t>();
-        o.pair_val = radix_sort_where((int64_t)Z, 0, mb) == 0 ? c.a_csr.as<uint64_t>() : c.ws_d.as<uint64_t>();
-    }
-    else if (words) { c.csr_words.reserve((size_t)(Z + 8) * 8); o.csr_words = c.csr_words.as<uint64_t>(); }
-    else { c.kid_of_entry.reserve((size_t)(Z + 8) * 8); o.kid_of_entry = c.kid_of_entry.as<uint64_t>(); }
-    o.ell = c.use_ell ? c.a_ell.as<uint64_t>() : nullptr; o.ell_stride = c.use_ell ? c.s_stride : 0u;
-    // gather slots: with inline partners the padded store holds the columns that are still fetched, not all of them (BucketOut)
-    const bool compact = inl && words && c.use_ell && !c.opt.no_ell_compact;
-    c.ell_compact = compact; c.ell_nslots = compact ? 0 : (int64_t)N;
-    const uint32_t grid16 = std::min<uint32_t>(nbk_cap, (uint32_t)c.num_cus * 12u), grid32 = std::min<uint32_t>(nbk_cap, (uint32_t)c.num_cus * 4u), grid8 = std::min<uint32_t>(nbk_cap, (uint32_t)c.num_cus * 24u);
-    if (compact) {
-        // Slots are drawn a chunk at a time per workgroup and a chunk's tail may stay unused (a bucket that needs more than what is left takes a new
-        // chunk, or exactly what it needs when that is more than a chunk): the store is sized for every column + one chunk per workgroup + the
-        // largest single draw a workgroup can leave behind — the slots can never run past it.
-        const uint64_t nwg = (uint64_t)grid8 + grid16 + grid32 + (np_max ? 3ull * std::min<uint32_t>(np_max, (uint32_t)c.num_cus * 24u) : 0ull);
-        const uint32_t chunk = (uint32_t)std::max<uint64_t>(64, std::min<uint64_t>(4096, N / (4 * nwg)));
-        // (a chunk's tail stays unused when the next bucket needs more than what is left: a quarter more than the columns covers every read set seen —
-        //  ~4 % are wasted on BASELINE config 3 —; a draw past the store is refused on the device and the emit repeated without slots)
-        uint64_t cap_cols = N + N / 4 + nwg * chunk + 4096;
-        c.a_ell.reserve((size_t)cap_cols * c.s_stride * 8 + 64);
-        if (c.opt.ell_slot_cap > 0 && (uint64_t)c.opt.ell_slot_cap < cap_cols) cap_cols = (uint64_t)c.opt.ell_slot_cap;      // (test hook: a store too small for the slots)
-        const int idbits = std::min(32, rs - pb - 2);      // the id field of a sort key: from the hint bits up to the read
-        if (idbits < 32 && cap_cols > (1ull << idbits)) cap_cols = 1ull << idbits;      // (slots beyond it are refused like slots beyond the store)
-        ELBA_HIP(hipMemsetAsync(c.a_ell.as<char>() + (size_t)cap_cols * c.s_stride * 8, 0xFF, 64, s));
-        c.ell_cap_cols = (int64_t)cap_cols;
-        o.ell = c.a_ell.as<uint64_t>(); o.slot_chunk = chunk; o.slot_cap = cap_cols;
-        c.ell_slot_kid.reserve((size_t)(cap_cols + 1) * 4);
-        c.ws_cursor.reserve(64);      // (a buffer of its own: the scans of the later value-range passes use ws_scan)
-        ELBA_HIP(hipMemsetAsync(c.ws_cursor.p, 0, 16, s));
-        o.slot_cursor = c.ws_cursor.as<unsigned long long>(); o.slot_kid = c.ell_slot_kid.as<uint32_t>(); o.compact = 1u;
-    }
-    const uint64_t *wrel = tri ? wb : wa;      // (triples: the partitioned words are the entries)
-    auto launch_emit = [&](const BucketStats &hs) {      // (hs: the statistics of the pass whose buckets are emitted — which classes hold buckets)
-        if (Z == 0) return;
-        const uint32_t cap16 = std::min<uint32_t>(small_cap, 4096u), cap8 = std::min<uint32_t>(cap16, c.opt.msd_no_emit8 ? 0u : 2048u);
-        // (buckets of up to 2048 entries — more than half of them on BASELINE config 3, where a bucket holds 2040 on average — through an instantiation
-        //  with 8 entries per lane: half the predicated-off work of the 16-entry one, 26 KB of LDS instead of 49: six workgroups per CU)
-        // (512 lanes x 4 for them was measured too: 17.6 against 17.5 ms on config 3, 48.4 against 47.6 ms on the k = 31 workload)
-        const bool spec = m.rk == 0 && m.dup == 0u && o.compact && o.hints && o.csr_words && !o.pair_val && !o.kmer_src && !o.kmer_dist && !o.ncols && o.rel_kmers && c.opt.tune[6] != 3;      // ("tune6" = 3: the general instantiation — A/B)
-        if (cap8 && spec) hipLaunchKernelGGL((k_msd_emit_small<8, 256, true>), dim3(grid8), dim3(256), 0, s, wrel, (const uint32_t *)b2start, (const uint32_t *)bZ, nbuckets, m, 0u, cap8,
-                                     (const uint32_t *)kidbase, (const uint32_t *)entbase, o);
-        else
-        if (cap8) hipLaunchKernelGGL((k_msd_emit_small<8>), dim3(grid8), dim3(256), 0, s, wrel, (const uint32_t *)b2start, (const uint32_t *)bZ, nbuckets, m, 0u, cap8,
-                                     (const uint32_t *)kidbase, (const uint32_t *)entbase, o);
-        // 2049..4096 entries: 512 lanes x 8 (three workgroups of eight wavefronts per CU, not of four: 19.0 -> 17.5 ms for the bucket kernels on config 3)
-        if (cap16 > cap8 && spec) hipLaunchKernelGGL((k_msd_emit_small<8, 512, true>), dim3(grid16), dim3(512), 0, s, wrel, (const uint32_t *)b2start, (const uint32_t *)bZ, nbuckets, m, cap8, cap16,
-                           (const uint32_t *)kidbase, (const uint32_t *)entbase, o);
-        else
-        if (cap16 > cap8) hipLaunchKernelGGL((k_msd_emit_small<8, 512>), dim3(grid16), dim3(512), 0, s, wrel, (const uint32_t *)b2start, (const uint32_t *)bZ, nbuckets, m, cap8, cap16,
-                           (const uint32_t *)kidbase, (const uint32_t *)entbase, o);
-        if (small_cap > 4096u && hs.nmid)
-            // (8192 entries on 1024 lanes x 8: the 99 KB of LDS allow ONE workgroup per CU — sixteen wavefronts hide the barriers better than eight:
-            //  39.7 against 46.8 ms for the bucket kernels on BASELINE config 5 at one GPU's share)
-            hipLaunchKernelGGL((k_msd_emit_small<8, 1024>), dim3(grid32), dim3(1024), 0, s, wrel, (const uint32_t *)b2start, (const uint32_t *)bZ, nbuckets, m, 4096u, std::min(small_cap, 8192u),
-                               (const uint32_t *)kidbase, (const uint32_t *)entbase, o);
-        // 8193..12288 entries (the lowest values of a deep read set: the canonical k-mer is the smaller of two, the first buckets hold twice the average):
-        // twelve entries per lane, 144 KB of LDS — one kernel launch over a few percent of the buckets instead of the windowed kernel's ~45 us per bucket
-        if (small_cap > 8192u && hs.nbig)
-            hipLaunchKernelGGL((k_msd_emit_small<12, 1024>), dim3(grid32), dim3(1024), 0, s, wrel, (const uint32_t *)b2start, (const uint32_t *)bZ, nbuckets, m, 8192u, small_cap,
-                               (const uint32_t *)kidbase, (const uint32_t *)entbase, o);
-        if (hs.ncrowded && !wide)
-            hipLaunchKernelGGL((k_msd_bucket<true>), dim3((unsigned)std::min<uint32_t>(hs.ncrowded, (uint32_t)c.num_cus)), dim3(BK_THREADS), BK_LDS_EMIT, s, (const uint64_t *)wb, (const uint32_t *)b2start, nbuckets, m,
-                               (uint32_t)c.cfg.lower, (uint32_t)c.cfg.upper, (const uint32_t *)crowded, (const BucketStats *)gstat, (const uint32_t *)kidbase, (const uint32_t *)entbase, o);
+
+    // The scan over the buckets of the current pass (or of the whole input) — k-mer ids and entries of the passes before it added (Nprev, Zprev) —, the count
+    // kernels' statistics, the checks of the wide partition's crowded parents and its pseudo-buckets' bases: ONE host round trip.  Leaves: bt.kidbase /
+    // bt.entbase (ps.t's too), the pass's counts and statistics in pp; tally: the crowded buckets count towards the stage's statistics.
+    void scan_pass(CountedPass &pp, uint64_t Nprev, uint64_t Zprev, bool tally)
+    {
+        const uint32_t nbuckets = bt.nbuckets;
+        std::vector<uint32_t> pz;
         if (ps.on) {
-            // the pseudo-buckets of the wide partition's crowded buckets: the same kernels on their own bucket table; the k-mer of a column is looked up by its rank among the distinct ones
-            BucketOut o2 = o;
-            o2.kmer_src = nullptr; o2.kmer_dist = ps.cdist; o2.dist_base = ps.dist_base; o2.ncols = ps.bN;
-            const uint32_t np = ps.np, g8 = std::min<uint32_t>(np, (uint32_t)c.num_cus * 24u), g16 = std::min<uint32_t>(np, (uint32_t)c.num_cus * 12u), g32 = std::min<uint32_t>(np, (uint32_t)c.num_cus * 4u);
-            if (cap8) hipLaunchKernelGGL((k_msd_emit_small<8>), dim3(g8), dim3(256), 0, s, (const uint64_t *)ps.wrel, (const uint32_t *)ps.b2s, (const uint32_t *)ps.bZ, np, m, 0u, cap8, (const uint32_t *)ps.kidbase, (const uint32_t *)ps.entbase, o2);
-            if (cap16 > cap8) hipLaunchKernelGGL((k_msd_emit_small<8, 512>), dim3(g16), dim3(512), 0, s, (const uint64_t *)ps.wrel, (const uint32_t *)ps.b2s, (const uint32_t *)ps.bZ, np, m, cap8, cap16, (const uint32_t *)ps.kidbase, (const uint32_t *)ps.entbase, o2);
-            if (small_cap > 4096u && ps.hs.nmid)
-                hipLaunchKernelGGL((k_msd_emit_small<8, 1024>), dim3(g32), dim3(1024), 0, s, (const uint64_t *)ps.wrel, (const uint32_t *)ps.b2s, (const uint32_t *)ps.bZ, np, m, 4096u, std::min(small_cap, 8192u), (const uint32_t *)ps.kidbase, (const uint32_t *)ps.entbase, o2);
-            if (small_cap > 8192u && ps.hs.nbig)
-                hipLaunchKernelGGL((k_msd_emit_small<12, 1024>), dim3(g32), dim3(1024), 0, s, (const uint64_t *)ps.wrel, (const uint32_t *)ps.b2s, (const uint32_t *)ps.bZ, np, m, 8192u, small_cap, (const uint32_t *)ps.kidbase, (const uint32_t *)ps.entbase, o2);
-            if (ps.hs.ncrowded)
-                hipLaunchKernelGGL((k_msd_bucket<true>), dim3((unsigned)std::min<uint32_t>(ps.hs.ncrowded, (uint32_t)c.num_cus)), dim3(BK_THREADS), BK_LDS_EMIT, s, ps.words, (const uint32_t *)ps.b2s, np, m,
-                                   (uint32_t)c.cfg.lower, (uint32_t)c.cfg.upper, (const uint32_t *)ps.crowded, (const BucketStats *)ps.gstat, (const uint32_t *)ps.kidbase, (const uint32_t *)ps.entbase, o2);
+            ELBA_HIP(hipMemcpyAsync(&ps.hs, ps.t.gstat, sizeof(BucketStats), hipMemcpyDeviceToHost, s));
+            pz.resize((size_t)ps.nc * 2);
+            hipLaunchKernelGGL(k31_parent_counts, dim3((ps.nc + 255) / 256), dim3(256), 0, s, ps.clist, ps.nc, (const uint32_t *)sZ, (const uint32_t *)bt.bZ, ps.pz);
+            ELBA_HIP(hipMemcpyAsync(pz.data(), ps.pz, (size_t)ps.nc * 8, hipMemcpyDeviceToHost, s));
         }
-    };
-    const bool mprep = c.opt.measure_prep && !pairs && words && !batched && !(hs.ncrowded && !wide);      // (the crowded-bucket kernel still reads the partition's buffer)
-    c.prep_us = -1; c.emit_us = -1;
-    if (mprep) c.t_emit.start(s);
-    auto emit_passes = [&]() {
-        // one pass: the buckets are counted, emit them.  Value-range batching, phase B: every pass is partitioned and counted again (phase A kept its
-        // figures only), its k-mer ids and entries start behind those of the passes before it
+        scan_on_device();
+        uint32_t h2[2] = {0, 0};
+        ELBA_HIP(hipMemcpyAsync(&h2[0], bt.kidbase + nbuckets, 4, hipMemcpyDeviceToHost, s));
+        ELBA_HIP(hipMemcpyAsync(&h2[1], bt.entbase + nbuckets, 4, hipMemcpyDeviceToHost, s));
+        ELBA_HIP(hipMemcpyAsync(&pp.hs, bt.gstat, sizeof(BucketStats), hipMemcpyDeviceToHost, s));
+        ELBA_HIP(hipStreamSynchronize(s));
+        pp.N = h2[0]; pp.Z = h2[1];
+        add_bases(Nprev, Zprev);
+        pp.crowded_small = 0;
+        if (ps.on) {
+            for (uint32_t p = 0; p < ps.nc; ++p) pp.crowded_small += pz[p] > 0u && pz[p] <= pl.small_cap ? 1 : 0;
+            if (tally) { c.kmer_crowded += ps.nc; c.kmer_crowded_small += pp.crowded_small; }      // (set before the check below: they describe the input)
+            for (uint32_t p = 0; p < ps.nc; ++p)
+                ELBA_REQUIRE(pz[ps.nc + p] == 0u, ELBA_ERR_INTERNAL, "count_kmers: a crowded bucket of the wide partition is visible to the main emit kernels");
+            hipLaunchKernelGGL(k31_pseudo_bases, dim3((ps.nc + 255) / 256), dim3(256), 0, s, (const uint32_t *)bt.kidbase, (const uint32_t *)bt.entbase, ps.clist, ps.pbase, ps.nc, (const uint32_t *)ps.t.bN, (const uint32_t *)ps.t.bZ, ps.t.kidbase, ps.t.entbase);
+            pp.hs.distinct += ps.hs.distinct; pp.hs.sumsq += ps.hs.sumsq; pp.hs.maxcol = std::max(pp.hs.maxcol, ps.hs.maxcol);
+        }
+        pp.ncrowded = ps.on ? ps.nc : pp.hs.ncrowded;
+        pp.np = ps.on ? ps.t.nbuckets : 0u;
+    }
+
+    // VALUE-RANGE BATCHING (round 5; include/elba_amd.h, "limits"): more instances than a 32-bit place holds (or than the option "kmer_batch_instances"
+    // allows) are counted in passes over RANGES OF FIRST DIGITS — the reference batches its exchange so that size is no limit (include/KmerOps.hpp:33-56)
+    // —: the buckets are value ranges, so pass after pass yields consecutive k-mer ids and consecutive stretches of the columns.  Planning (here): the
+    // per-digit totals of one unfiltered histogram (k <= 17: of the first digit; the wide partition: of the coarse digit), cut into passes by
+    // msd_plan.hpp; phase A: partition + count (+ crowded buckets) of every pass for N, Z and the longest column — what the layout of A depends on —;
+    // phase B: all of it again, then the emit with the pass's id / entry bases.
+    // Leaves: passes, largest, the two partition buffers sized by the largest pass.
+    void plan_batches()
+    {
+        const uint32_t ntiles1 = pl.ntiles1, nd = pl.wide ? (uint32_t)W2_MAXBINS : pl.nb1;
+        if (pl.wide) hipLaunchKernelGGL((k31_hist1<false>), dim3(ntiles1), dim3(W2_THREADS), 0, s, e, bi, W2_MAXBITS, hist(), 0, 0u, 0u);
+        else hipLaunchKernelGGL(k_msd_hist1, dim3(ntiles1), dim3(MT_THREADS), 0, s, e, bi, m, hist(), 0u, pl.nb1);
+        c.ws_scan.reserve((size_t)nd * 8 + 64);
+        ELBA_HIP(hipMemsetAsync(c.ws_scan.p, 0, (size_t)nd * 8, s));
+        hipLaunchKernelGGL(k_msd_digit_totals, dim3((unsigned)((ntiles1 + 255) / 256)), dim3(nd), 0, s, (const uint32_t *)hist(), (uint64_t)ntiles1, nd, c.ws_scan.as<unsigned long long>());
+        std::vector<unsigned long long> dt(nd);
+        ELBA_HIP(hipMemcpyAsync(dt.data(), c.ws_scan.p, (size_t)nd * 8, hipMemcpyDeviceToHost, s));
+        ELBA_HIP(hipStreamSynchronize(s));
+        int64_t oversized = -1;
+        const std::vector<Pass> planned = pl.wide ? plan_wide_passes(dt, pl.I, pl.batch_cap, c.opt.msd_wide_bits, &oversized) : plan_narrow_passes(dt, pl.batch_cap, pl.nb2, pl.T, &oversized);
+        if (pl.wide) ELBA_REQUIRE(oversized < 0, ELBA_ERR_UNSUPPORTED, "count_kmers: one coarse digit of the wide partition alone holds more than 2^32 k-mer instances");
+        else ELBA_REQUIRE(oversized < 0, ELBA_ERR_UNSUPPORTED, "count_kmers: one first-digit bucket alone holds more than 2^32 k-mer instances");
+        passes.clear();
+        for (const Pass &p1 : planned) passes.push_back(CountedPass{p1});
+        if (c.opt.trace) fprintf(stderr, "[elba] count_kmers: %llu instances in %zu value-range passes%s\n", (unsigned long long)pl.I, passes.size(), pl.wide ? " of the wide partition" : "");
+        largest = 0;
+        for (const Pass &p1 : passes) largest = std::max(largest, p1.I);
+        c.kmer_largest_pass = (int64_t)largest;
+        const size_t rec = pl.wide ? 16 : 8;
+        c.ws_a.reserve((size_t)(largest + 2) * rec); c.ws_c.reserve((size_t)(largest + 2) * rec);
+    }
+
+    // The totals over the scanned passes: N, Z, the statistics — what the layout of A depends on.
+    void total_passes()
+    {
+        for (const CountedPass &p1 : passes) {
+            N += p1.N; Z += p1.Z; hs.distinct += p1.hs.distinct; hs.sumsq += p1.hs.sumsq; hs.maxcol = std::max(hs.maxcol, p1.hs.maxcol);
+            ncrowded += p1.ncrowded; crowded_small += p1.crowded_small; np_max = std::max(np_max, p1.np);
+        }
+        if (!pl.batched) hs = passes[0].hs;      // (one pass: its statistics whole — the triples' refusal reads ncrowded)
+    }
+
+    // The output buffers and the BucketOut the emit kernels write through, decided from N, Z and the longest column.  Leaves: o (but kmer_src: partition_wide's),
+    // nb, pb, rs, pbi, words, hints, inl, pairs, compact, grids, the context's column store chosen (and sized for gather slots).
+    void layout_output()
+    {
+        const uint64_t maxpos = pl.maxpos;
+        const int mb = pl.mb;
+        if (!tri) c.rel_kmers.reserve((size_t)(N + 1) * 8);
+        c.rel_counts.reserve((size_t)(N + 2) * 4);
+        c.a_colptr.reserve((size_t)(N + 2) * 4);
+        c.a_csc.reserve((size_t)(Z + 8) * 8);
+        nb = bits_needed_u((uint64_t)(N > 0 ? N - 1 : 0)); pb = m.pbits;
+        words = mb + nb + pb + 2 <= 64 && !c.opt.csr_pairs;
+        hints = pb <= 30 && !c.opt.no_hints;
+        o.rel_kmers = tri ? nullptr : c.rel_kmers.as<uint64_t>(); o.rel_counts = c.rel_counts.as<uint32_t>(); o.colptr = c.a_colptr.as<uint32_t>();
+        c.max_col_nnz = (int64_t)hs.maxcol;
+        choose_column_store(c, (int64_t)N, c.max_col_nnz);
+        // inline partners (Ctx::csr_inline): whole matrix, general (not dense) SpGEMM path with position-carrying accumulators, and a sort word wide
+        // enough for flag | read | partner >> 1 | posQ | posT
+        const bool dense = c.use_ell && maxpos < 65536 && c.max_col_nnz > 16 && !c.opt.no_pay && !c.opt.no_suffix;
+        // The inline key is flag | read << rs | (partner >> 1) << 2 pbi | posQ << pbi | posT with the read as high as it goes (rs = 63 - mb): pbi position
+        // bits are what is left, and an entry is written inline only if both positions fit them (200 100 reads of up to 16.6 kb: 14 bits, all but
+        // the last bases of a handful of reads)
+        rs = nb + pb + 2; pbi = 0;
+        inl = words && hints && c.use_ell && !dense && maxpos < 65536 && !c.opt.no_pay && !c.opt.no_inline && !c.opt.no_symmetry && N < (1ull << 31) && mb >= 2;
+        if (inl) {
+            const int rs2 = 63 - mb;
+            pbi = std::min(pb, (rs2 - (mb - 1)) / 2);
+            if (rs2 >= rs && pbi >= 10) rs = rs2; else inl = false;
+        }
+        o.csc = c.a_csc.as<uint64_t>(); o.nb = nb; o.pb = pb; o.rs = rs; o.mb = mb; o.inl = inl ? (uint32_t)pbi : 0u; o.hints = hints && words && !dense ? 1u : 0u;
+        // a dense matrix's CSR build sorts (read, entry) pairs (matrix.hip, csr_suffix: the entry carries its column's length and its place in it — known
+        // here, where the column lies sorted in LDS): they are written instead of sort words, the values where a sort that ends in a_csr starts
+        // (not under value-range batching: phase B enumerates the reads again through the block table in ws_b, which the pairs would take — the sort words instead, as "csr_pairs_late")
+        pairs = dense && N < (1ull << 32) && c.max_col_nnz < 128 && !c.opt.csr_pairs_late && !pl.batched;
+        c.pre_pairs = pairs;
+        if (pairs) {
+            c.ws_b.reserve((size_t)(Z + 1) * 8); c.ws_d.reserve((size_t)(Z + 1) * 8); c.a_csr.reserve((size_t)(Z + 1) * 8);      // (ws_b: the enumeration's block table is dead)
+            o.pair_key = c.ws_b.as<uint32_t>();
+            o.pair_val = radix_sort_where((int64_t)Z, 0, mb) == 0 ? c.a_csr.as<uint64_t>() : c.ws_d.as<uint64_t>();
+        }
+        else if (words) { c.csr_words.reserve((size_t)(Z + 8) * 8); o.csr_words = c.csr_words.as<uint64_t>(); }
+        else { c.kid_of_entry.reserve((size_t)(Z + 8) * 8); o.kid_of_entry = c.kid_of_entry.as<uint64_t>(); }
+        o.ell = c.use_ell ? c.a_ell.as<uint64_t>() : nullptr; o.ell_stride = c.use_ell ? c.s_stride : 0u;
+        // gather slots: with inline partners the padded store holds the columns that are still fetched, not all of them (BucketOut)
+        compact = inl && words && c.use_ell && !c.opt.no_ell_compact;
+        c.ell_compact = compact; c.ell_nslots = compact ? 0 : (int64_t)N;
+        grids = emit_grids(c, pl.nbk_cap);
+        if (compact) {
+            // Slots are drawn a chunk at a time per workgroup and a chunk's tail may stay unused (a bucket that needs more than what is left takes a new
+            // chunk, or exactly what it needs when that is more than a chunk): the store is sized for every column + one chunk per workgroup + the
+            // largest single draw a workgroup can leave behind — the slots can never run past it.
+            const uint64_t nwg = (uint64_t)grids.g8 + grids.g16 + grids.g32 + (np_max ? 3ull * std::min<uint32_t>(np_max, (uint32_t)c.num_cus * 24u) : 0ull);
+            const uint32_t chunk = (uint32_t)std::max<uint64_t>(64, std::min<uint64_t>(4096, N / (4 * nwg)));
+            // (a chunk's tail stays unused when the next bucket needs more than what is left: a quarter more than the columns covers every read set seen —
+            //  ~4 % are wasted on BASELINE config 3 —; a draw past the store is refused on the device and the emit repeated without slots)
+            uint64_t cap_cols = N + N / 4 + nwg * chunk + 4096;
+            c.a_ell.reserve((size_t)cap_cols * c.s_stride * 8 + 64);
+            if (c.opt.ell_slot_cap > 0 && (uint64_t)c.opt.ell_slot_cap < cap_cols) cap_cols = (uint64_t)c.opt.ell_slot_cap;      // (test hook: a store too small for the slots)
+            const int idbits = std::min(32, rs - pb - 2);      // the id field of a sort key: from the hint bits up to the read
+            if (idbits < 32 && cap_cols > (1ull << idbits)) cap_cols = 1ull << idbits;      // (slots beyond it are refused like slots beyond the store)
+            ELBA_HIP(hipMemsetAsync(c.a_ell.as<char>() + (size_t)cap_cols * c.s_stride * 8, 0xFF, 64, s));
+            c.ell_cap_cols = (int64_t)cap_cols;
+            o.ell = c.a_ell.as<uint64_t>(); o.slot_chunk = chunk; o.slot_cap = cap_cols;
+            c.ell_slot_kid.reserve((size_t)(cap_cols + 1) * 4);
+            c.ws_cursor.reserve(64);      // (a buffer of its own: the scans of the later value-range passes use ws_scan)
+            ELBA_HIP(hipMemsetAsync(c.ws_cursor.p, 0, 16, s));
+            o.slot_cursor = c.ws_cursor.as<unsigned long long>(); o.slot_kid = c.ell_slot_kid.as<uint32_t>(); o.compact = 1u;
+        }
+        mprep = c.opt.measure_prep && !pairs && words && !pl.batched && !(hs.ncrowded && !pl.wide);      // (the crowded-bucket kernel still reads the partition's buffer)
+    }
+
+    // The emit kernels over the current pass's buckets, counted and scanned (pp_hs: the pass's statistics), and over its pseudo-buckets: the same kernels on
+    // their own bucket table; the k-mer of a column is looked up by its rank among the distinct ones
+    void emit(const BucketStats &pp_hs)
+    {
+        if (Z == 0) return;
+        launch_emit(c, m, pl.small_cap, bt, pp_hs, o, grids);
+        if (!ps.on) return;
+        BucketOut o2 = o;
+        o2.kmer_src = nullptr; o2.kmer_dist = ps.cdist; o2.dist_base = ps.dist_base; o2.ncols = ps.t.bN;
+        launch_emit(c, m, pl.small_cap, ps.t, ps.hs, o2, emit_grids(c, ps.t.nbuckets));
+    }
+
+    // one pass: the buckets are counted, emit them.  Value-range batching, phase B: every pass is partitioned and counted again (phase A kept its
+    // figures only), its k-mer ids and entries start behind those of the passes before it
+    void emit_passes()
+    {
         uint64_t Nprev = 0, Zprev = 0;
-        for (const Pass &pp : passes) {
-            if (batched && wide) {
-                wide_count(pp, false);
-                Pass again = pp;
+        for (const CountedPass &pp : passes) {
+            if (pl.batched && pl.wide) {
+                partition_wide(pp, false);
+                cut_crowded(pp);
+                CountedPass again = pp;
                 scan_pass(again, Nprev, Zprev, false);
                 ELBA_REQUIRE(again.N == pp.N && again.Z == pp.Z, ELBA_ERR_INTERNAL, "count_kmers: a value-range pass of the wide partition counted differently the second time");
-            } else if (batched) {
-                partition_count(pp.dlo, pp.dhi, pp.I, false);
-                scan_buckets(nullptr, nullptr, nullptr);
-                if (Nprev) hipLaunchKernelGGL(k_add_u32, dim3((nbuckets + 1 + 255) / 256), dim3(256), 0, s, kidbase, nbuckets + 1, (uint32_t)Nprev);
-                if (Zprev) hipLaunchKernelGGL(k_add_u32, dim3((nbuckets + 1 + 255) / 256), dim3(256), 0, s, entbase, nbuckets + 1, (uint32_t)Zprev);
+            } else if (pl.batched) {
+                partition_narrow(pp, false);
+                scan_on_device();      // (no host round trip: phase A knows the pass's counts)
+                add_bases(Nprev, Zprev);
             }
-            launch_emit(pp.hs);
+            emit(pp.hs);
             Nprev += pp.N; Zprev += pp.Z;
         }
-    };
-    emit_passes();
-    if (mprep) {
-        // (diagnostic) the same kernels once more, without what they write for the SpGEMM's sake alone: no hint bits, no inline partners, no padded column
-        // store / gather slots — the columns, k-mers and counts are rewritten with what they hold, the sort keys go to the partition's dead buffer
+    }
+
+    // (diagnostic, "measure_prep") the same kernels once more, without what they write for the SpGEMM's sake alone: no hint bits, no inline partners, no padded column
+    // store / gather slots — the columns, k-mers and counts are rewritten with what they hold, the sort keys go to the partition's dead buffer
+    void emit_plain_again()
+    {
         c.t_emit.stop(s);
         const BucketOut keep = o;
-        o.hints = 0; o.inl = 0; o.ell = nullptr; o.ell_stride = 0; o.compact = 0; o.csr_words = tri ? wa : wb;
+        o.hints = 0; o.inl = 0; o.ell = nullptr; o.ell_stride = 0; o.compact = 0; o.csr_words = tri ? wa() : wb();
         c.t_emit_plain.start(s);
-        launch_emit(passes[0].hs);
+        emit(passes[0].hs);
         c.t_emit_plain.stop(s);
         o = keep;
     }
-    const uint32_t Zz = (uint32_t)Z;
-    ELBA_HIP(hipMemcpyAsync(c.a_colptr.as<uint32_t>() + N, &Zz, 4, hipMemcpyHostToDevice, s));
-    c.prod_ctr.reserve(64 * 128);
-    ELBA_HIP(hipMemsetAsync(c.prod_ctr.p, 0, 64 * 128, s));
-    const unsigned long long sq = hs.sumsq;
-    ELBA_HIP(hipMemcpyAsync(c.prod_ctr.p, &sq, 8, hipMemcpyHostToDevice, s));
-    unsigned long long slots[2] = {0, 0};
-    if (compact) ELBA_HIP(hipMemcpyAsync(slots, c.ws_cursor.p, 16, hipMemcpyDeviceToHost, s));
-    c.t_b.stop(s);
-    c.t_total.stop(s);
-    ELBA_HIP(hipStreamSynchronize(s));
-    if (mprep) { const float a = c.t_emit.ms(), b = c.t_emit_plain.ms(); c.emit_us = (int64_t)(a * 1000.0f); c.prep_us = (int64_t)((a - b) * 1000.0f); }
-    if (compact && slots[1] != 0) {
-        // more chunk tails were left unused than the store has room for (never seen; a draw past it writes nothing): every column gets the place
-        // of its k-mer id after all — the emit once more, without slots
-        if (c.opt.trace) fprintf(stderr, "[elba] gather slots ran past the padded column store (%llu of %llu): emitting again without them\n", slots[0], (unsigned long long)c.ell_cap_cols);
-        o.compact = 0; c.ell_compact = false; c.ell_nslots = (int64_t)N; c.ell_cap_cols = (int64_t)N;
-        // (the guard words behind column N: choose_column_store's were lost when the store was sized for the slots, and the re-emit writes right up to them)
-        ELBA_HIP(hipMemsetAsync(c.a_ell.as<char>() + (size_t)N * c.s_stride * 8, 0xFF, 64, s));
-        emit_passes();
+
+    // The last column pointer, the SpGEMM's product counter, the slots in use; ONE synchronisation; the emit once more if the gather slots ran out; what the
+    // context and the caller's statistics say of the stage.
+    void finish(elba_kmer_stats *stp)
+    {
+        const uint32_t Zz = (uint32_t)Z;
+        ELBA_HIP(hipMemcpyAsync(c.a_colptr.as<uint32_t>() + N, &Zz, 4, hipMemcpyHostToDevice, s));
+        c.prod_ctr.reserve(64 * 128);
+        ELBA_HIP(hipMemsetAsync(c.prod_ctr.p, 0, 64 * 128, s));
+        const unsigned long long sq = hs.sumsq;
+        ELBA_HIP(hipMemcpyAsync(c.prod_ctr.p, &sq, 8, hipMemcpyHostToDevice, s));
+        unsigned long long slots[2] = {0, 0};
+        if (compact) ELBA_HIP(hipMemcpyAsync(slots, c.ws_cursor.p, 16, hipMemcpyDeviceToHost, s));
+        c.t_b.stop(s);
+        c.t_total.stop(s);
         ELBA_HIP(hipStreamSynchronize(s));
-    } else if (compact) c.ell_nslots = (int64_t)slots[0];      // (an upper bound of the slots in use: chunks are drawn whole)
-    c.pre_ready = true; c.pre_consumed = false; c.pre_words = words; c.pre_hints = hints; c.pre_hints_done = hints && words; c.pre_ell_done = true; c.pre_inline_pending = false;
-    c.pre_nb = nb; c.pre_pb = pb; c.pre_maxpos = maxpos; c.pre_rs = rs; c.pre_inline = inl; c.pre_pbi = pbi;
-    if (tri) return true;
-    elba_kmer_stats &st = *stp;
-    st.instances = (int64_t)I; st.distinct = (int64_t)hs.distinct; st.reliable = (int64_t)N; st.entries = (int64_t)Z;
-    st.ms_total = c.t_total.ms(); st.ms_count = c.t_a.ms(); st.ms_sort = c.t_b.ms(); st.ms_lookup = 0;
-    c.ndistinct = (int64_t)hs.distinct;
-    c.N = (int64_t)N; c.Z = (int64_t)Z;
-    c.kmer_path = wide ? 2 : 1;
-    c.kmer_passes = (int)passes.size();
-    c.kmer_crowded = ncrowded; c.kmer_crowded_small = crowded_small; c.kmer_largest_pass = (int64_t)largest;
-    c.kmer_buckets = 0;
-    for (const Pass &pp : passes) c.kmer_buckets += (int64_t)pp.nb1 * pp.nb2;
+        if (mprep) { const float a = c.t_emit.ms(), b = c.t_emit_plain.ms(); c.emit_us = (int64_t)(a * 1000.0f); c.prep_us = (int64_t)((a - b) * 1000.0f); }
+        if (compact && slots[1] != 0) {
+            // more chunk tails were left unused than the store has room for (never seen; a draw past it writes nothing): every column gets the place
+            // of its k-mer id after all — the emit once more, without slots
+            if (c.opt.trace) fprintf(stderr, "[elba] gather slots ran past the padded column store (%llu of %llu): emitting again without them\n", slots[0], (unsigned long long)c.ell_cap_cols);
+            o.compact = 0; c.ell_compact = false; c.ell_nslots = (int64_t)N; c.ell_cap_cols = (int64_t)N;
+            // (the guard words behind column N: choose_column_store's were lost when the store was sized for the slots, and the re-emit writes right up to them)
+            ELBA_HIP(hipMemsetAsync(c.a_ell.as<char>() + (size_t)N * c.s_stride * 8, 0xFF, 64, s));
+            emit_passes();
+            ELBA_HIP(hipStreamSynchronize(s));
+        } else if (compact) c.ell_nslots = (int64_t)slots[0];      // (an upper bound of the slots in use: chunks are drawn whole)
+        c.pre_ready = true; c.pre_consumed = false; c.pre_words = words; c.pre_hints = hints; c.pre_hints_done = hints && words; c.pre_ell_done = true; c.pre_inline_pending = false;
+        c.pre_nb = nb; c.pre_pb = pb; c.pre_maxpos = pl.maxpos; c.pre_rs = rs; c.pre_inline = inl; c.pre_pbi = pbi;
+        if (tri) return;
+        elba_kmer_stats &st = *stp;
+        st.instances = (int64_t)pl.I; st.distinct = (int64_t)hs.distinct; st.reliable = (int64_t)N; st.entries = (int64_t)Z;
+        st.ms_total = c.t_total.ms(); st.ms_count = c.t_a.ms(); st.ms_sort = c.t_b.ms(); st.ms_lookup = 0;
+        c.ndistinct = (int64_t)hs.distinct;
+        c.N = (int64_t)N; c.Z = (int64_t)Z;
+        c.kmer_path = pl.wide ? 2 : 1;
+        c.kmer_passes = (int)passes.size();
+        c.kmer_crowded = ncrowded; c.kmer_crowded_small = crowded_small; c.kmer_largest_pass = (int64_t)largest;
+        c.kmer_buckets = 0;
+        for (const Pass &pp : passes) c.kmer_buckets += (int64_t)pp.nb1 * pp.nb2;
+    }
+};
+
+// The k-mer stage of one GPU for 9 <= k <= 31, and a matrix handed over as device triples (see the file header).  Leaves behind exactly what
+// runs_to_columns (kmer.hip) leaves: rel_kmers, rel_counts, a_colptr, a_csc, the CSR sort keys (csr_words, hint bits included) or kid_of_entry — plus
+// the padded column store.  false: the input keeps the sort path.
+static bool msd_run(Ctx &c, uint64_t I, elba_kmer_stats *stp, MsdTriples *tri)
+{
+    if (c.opt.kmer_no_msd || c.opt.kmer_pairs || c.opt.kmer_unfused || c.opt.emit_plain || c.opt.kmer_drop) return false;
+    if (tri && c.opt.csr_pairs) return false;
+    MsdInput in{}; in.k = c.cfg.k; in.I = I; in.lower = (uint32_t)c.cfg.lower; in.upper = (uint32_t)c.cfg.upper;
+    in.maxpos = tri ? tri->maxpos : reads_maxpos(c.max_read_len, c.cfg.k);      // (max_read_len: stage_count_kmers' walk over the read lengths)
+    in.nrows = tri ? tri->M : c.nreads; in.triN = tri ? tri->N : -1;
+    MsdOptions op{}; op.kmer_msd = c.opt.kmer_msd; op.msd_wide_bits = c.opt.msd_wide_bits; op.msd_rank = c.opt.msd_rank; op.msd_no_rank = c.opt.msd_no_rank; op.msd_small_cap = c.opt.msd_small_cap; op.kmer_batch_instances = c.opt.kmer_batch_instances;
+    const MsdPlan pl = plan_msd(in, op);
+    if (!pl.ok) return false;
+    ELBA_REQUIRE(!pl.too_many_tiles, ELBA_ERR_UNSUPPORTED, "count_kmers: more than 2^45 k-mer instances");
+    MsdRun r(c, pl, tri);
+    hipStream_t s = c.stream;
+    r.begin();
+    // phase A (or the one pass): partition and count, then the scan with the stage's one host round trip per pass
+    if (tri) r.partition_triples();
+    else if (!pl.batched && !pl.wide) r.partition_narrow(r.passes[0], true);
+    else if (!pl.batched) { r.partition_wide(r.passes[0], true); r.cut_crowded(r.passes[0]); }
+    else {
+        r.plan_batches();
+        for (CountedPass &pp : r.passes) {
+            if (pl.wide) { r.partition_wide(pp, false); r.cut_crowded(pp); }
+            else r.partition_narrow(pp, false);
+            r.scan_pass(pp, 0, 0, true);
+        }
+        c.t_a.stop(s); c.t_b.start(s);      // (the stage's two labels: phase A | phase B)
+    }
+    unsigned long long nbad = 0;
+    if (!pl.batched) {
+        if (tri) ELBA_HIP(hipMemcpyAsync(&nbad, r.one_seg + 4, 8, hipMemcpyDeviceToHost, s));
+        r.scan_pass(r.passes[0], 0, 0, true);
+    }
+    r.total_passes();
+    ELBA_REQUIRE(nbad == 0, ELBA_ERR_INVALID_ARG, "triple index out of range");
+    if (tri && (r.hs.ncrowded || (int64_t)r.N != tri->N || r.Z != I)) {      // an empty column (the buckets number the columns they find), a bucket beyond the LDS sort: matrix.hip sorts
+        if (c.opt.trace) fprintf(stderr, "[elba] set_kmer_matrix_device: %llu of %lld columns hold entries, %u crowded buckets: sorting instead\n", (unsigned long long)r.N, (long long)tri->N, r.hs.ncrowded);
+        c.t_b.stop(s); c.t_total.stop(s);
+        return false;
+    }
+    ELBA_REQUIRE(r.Z < 0xFFFFFFF0ull, ELBA_ERR_UNSUPPORTED, "count_kmers: nnz(A) beyond 32-bit device offsets");
+    // buckets: emit
+    r.layout_output();
+    c.prep_us = -1; c.emit_us = -1;
+    if (r.mprep) c.t_emit.start(s);
+    r.emit_passes();
+    if (r.mprep) r.emit_plain_again();
+    r.finish(stp);
     return true;
 }
 
