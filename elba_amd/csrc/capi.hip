@@ -764,7 +764,7 @@ int elba_get_stat(elba_ctx *ctx, const char *name, int64_t *value)
         else if (!strcmp(name, "kmer_peak_bytes")) *value = c.kmer_peak_bytes;      // device bytes the last elba_count_kmers' value-range passes of k > 31 held at their high point (0: not batched)
         else if (!strcmp(name, "kmer_buckets")) *value = c.kmer_buckets;      // buckets of the last elba_count_kmers' value partition, all passes (0: the sort)
         else if (!strcmp(name, "overlap_passes")) *value = c.ov_passes;      // passes the last create_seed_matrix took (1: no repeat; set also when the call failed)
-        else if (!strcmp(name, "overlap_spec")) *value = c.ov_spec;      // 1: the last create_seed_matrix ran the reads-path instantiation of the numeric kernel (spgemm.hip: ov_spec_ok), 0: the general one
+        else if (!strcmp(name, "overlap_spec")) *value = c.ov_spec;      // 1: the last create_seed_matrix ran the reads-path instantiation of the numeric kernel (ov_plan.hpp: ov_spec_ok), 0: the general one
         else if (!strcmp(name, "overlap_forwarded")) *value = c.ov_forwarded;      // rows the last create_seed_matrix forwarded to a larger tier on a prediction, all passes
         else if (!strcmp(name, "spgemm_prep_us")) *value = c.prep_us;      // (option "measure_prep"; -1: not measured — the option was off, or the path taken has no emit kernels of its own)
         else if (!strcmp(name, "emit_us")) *value = c.emit_us;

@@ -190,6 +190,9 @@ struct Options {
 };
 
 // ---- context ----------------------------------------------------------------------------------------------------
+// the rows [lo, hi) of B a context computes (Ctx::window)
+struct RowWindow { int64_t lo, hi; int64_t rows() const { return hi - lo; } };
+
 struct Ctx {
     elba_cfg cfg{};
     Options opt;
@@ -265,6 +268,7 @@ struct Ctx {
     bool pos16 = false;                        // every position among the entries is < 65536 (mirrored entries of B travel as 16-byte records then)
     uint32_t fbits = 1;                        // bits of the column-position field of a product sequence number
     int64_t row_lo = 0, row_hi = -1;           // rows of B computed by this context (-1: all)
+    RowWindow window() const { return {row_lo, row_hi < 0 ? M : row_hi}; }      // ... resolved
     // rows of an A built from reads are local read indices; exported triples carry global ids (src/KmerOps.cpp:215-219)
     int64_t first_global_id_rows() const { return A_has_kmers ? first_global_id : 0; }
 
@@ -339,7 +343,7 @@ struct Ctx {
     DevBuf ws_g, ws_h;      // crowded buckets of the wide k-mer partition (kmer_msd.hip: k31_gather_crowded ...): their records / the pseudo-buckets' arrays
     DevBuf ov_totcnt, ov_mir, ov_tmp, ov_sum_tmp;  // u32[M+1] mirrored entries per row (ticket counters); mirrored entries laid out like B (32-byte records); staging area (32-byte records)
     bool ov_low_clean = false;                 // the ticket counters are all zero (handed back clean by the previous call)
-    DevBuf ov_rowub, ov_rowcnt, ov_rowoff, ov_lists, ov_counters, ov_gtable, ov_sortkeys;
+    DevBuf ov_rowcnt, ov_rowoff, ov_lists, ov_counters, ov_gtable, ov_sortkeys;
     int64_t ov_tmp_cap = 0;
     bool ov_sort_used[2] = {false, false};      // wide-row sorts used by the previous call
     bool ov_tiers_known = false, ov_tier_used[8] = {false, false, false, false, false, false, false, false};   // tiers that got rows in the previous call

@@ -20,20 +20,19 @@
 //
 // No MFMA anywhere: the contraction is index matching plus integer min/max/add.
 #include "common.hpp"
+#include "ov_plan.hpp"
 #include <algorithm>
+#include <string>
 #include <type_traits>
+#include <utility>
 
 namespace elba {
 
 namespace {
 
 constexpr uint32_t EMPTY = 0xFFFFFFFFu;
-constexpr int NUM_LDS_TIERS = 5;                // 512, 1024, 2048, 4096, 8192 slots (18 B per slot incl. the 16-bit survivor list)
-constexpr int NUM_TIERS = NUM_LDS_TIERS + 1;    // + HBM spill
-constexpr int LDS_TBITS0 = 9;
-constexpr uint32_t STAGE_CHUNK = 1024;          // staging entries a workgroup draws from the global cursor at a time
+// (NUM_LDS_TIERS, NUM_TIERS, LDS_TBITS0, STAGE_CHUNK, FIN_WAVE2_MAX, SLAB_PAD, RP_TILE: ov_plan.hpp — the host's decisions read them too)
 constexpr uint32_t FIN_WAVE_MAX = 256;          // widest row the one-wave rank sort takes
-constexpr uint32_t FIN_WAVE2_MAX = 1024;        // widest row the one-wave bucket sort takes (wider rows: one workgroup each)
 constexpr uint32_t FIN_LDS_MAX = 4096;          // widest row the LDS bitonic sort takes
 
 // End-of-kernel statistics are flushed into one of 64 shards (each on its own 128-B line): thousands of workgroups adding to a
@@ -121,10 +120,10 @@ struct OvParams {
 // mirror, sets every switch of OvParams the same way on every call — padded columns with inline partners and ownership hints, 32-bit accumulators
 // that carry posT, 16-byte staging words, no dense path, single queue places.  Those switches are compile-time constants here (the kernel's dead
 // branches go, and so do the scalars it used to hold for them: the general kernel spills ~120 SGPRs to VGPR lanes); what still varies between
-// such calls — slabs or none, feedback, the tier, fbits, stride, lanes per entry — stays a field.  ov_spec_ok (spgemm.hip) is the predicate.
+// such calls — slabs or none, feedback, the tier, fbits, stride, lanes per entry — stays a field.  ov_spec_ok (ov_plan.hpp) is the predicate.
 struct OvSpecParams {
-    static constexpr uint32_t half = 1, inl = 1, pay16 = 1, rec16 = 1, suffix = 0, qblk_log2 = 0, j_shift = 0;
-    static constexpr uint32_t hint_mask = 1u << 31, pos_mask = 0x3FFFFFFFu;
+    static constexpr uint32_t half = ov_spec::half, inl = ov_spec::inl, pay16 = ov_spec::pay16, rec16 = ov_spec::rec16, suffix = ov_spec::suffix, qblk_log2 = ov_spec::qblk_log2, j_shift = ov_spec::j_shift;
+    static constexpr uint32_t hint_mask = ov_spec::hint_mask, pos_mask = ov_spec::pos_mask;
     static constexpr uint32_t row_lo = 0, row_hi = 0xFFFFFFFFu;      // the whole matrix: every partner id (< M) lies inside the window
     static constexpr const uint32_t *a_colptr = nullptr, *a_ellj = nullptr, *row_order = nullptr, *row_label = nullptr;
     static constexpr const uint64_t *a_csc = nullptr;
@@ -164,7 +163,6 @@ __global__ __launch_bounds__(256) void k_zero_regions(ZeroList z)
 // the sample's own rows, small matrices) draws a ticket from low_cnt[j] and takes the old way (k_mirror, the mirror area); the finalize reads a
 // row's mirrored entries from the slab first (slab_n[j] of them: k_slab_fold), then from the mirror area.  Capacity is a performance matter only,
 // never a correctness limit.
-constexpr uint32_t SLAB_PAD = 16;
 struct __attribute__((packed, aligned(4))) RowPair { uint32_t a, b; };      // a_rowptr[j], a_rowptr[j + 1]
 __device__ __forceinline__ uint32_t slab_base(uint32_t rp, uint32_t rp0, uint32_t row_rel, uint32_t q16)
 {
@@ -266,7 +264,6 @@ __device__ __forceinline__ elba_seed_t rec_seed(const uint4 a, const uint4 b)
 // Row pointers of B = exclusive scan of (staged + mirrored) counts, M+1 outputs, in ONE launch for up to 2^17 rows: every
 // workgroup sums the counts before its tile itself (L2-resident, a few hundred loads per lane at most) instead of waiting for
 // a second and third launch.
-constexpr int RP_TILE = 1024;
 __global__ __launch_bounds__(256) void k_row_pointers(FinParams p)
 {
     __shared__ unsigned long long wsum[4], bsum;
@@ -713,24 +710,8 @@ __global__ __launch_bounds__(256) void k_finalize_huge(FinParams p)
     }
 }
 
-int bits_for_u(uint64_t v)
-{
-    int b = 1;
-    while (b < 64 && (v >> b)) ++b;
-    return b;
-}
-
 }  // namespace
 
-// ---- the plan-free call: CSR + columns of A -> pruned CSR B, everything in between computed here ---------------------------------
-// Launch sequence (one stream, ONE host synchronisation at the end when nothing overflows):
-//   counters = 0, row_cnt = 0 | k_classify_direct | k_spgemm_direct on every table tier, ascending (+ the HBM-table tier) |
-//   k_row_pointers (scan of the rows' counts) | k_mirror (only queues the wide rows: nothing is mirrored, both triangles were computed) |
-//   k_finalize_wave / _bucket / _huge (per-row column sort + move to b_col / b_val) | counter read-back.
-// What a call may remember from earlier calls on the same matrix is a HINT only — the distinct-partner / row-entry ratio that picks the
-// starting tiers, which tiers and sorts got rows — and `cold_calls` (elba_set_option) or a new matrix forgets it: then the ratio starts at
-// 1/4 and the kernel corrects itself from the rows already done, every tier is launched.  Capacities (staging, output) start from nnz(A)
-// and only ever grow; a call that overflows them is repeated with what it measured.
 // ---- mirror exchange between ranks (sharded call with global pair ownership) ---------------------------------------------------------
 // A pair {i, j} whose rows live on two ranks is accumulated by ONE of them (owns_pair's parity rule, whatever the window); the other rank
 // receives the mirrored entry.  k_remote_mirror walks the staged records of this rank's rows, picks those whose partner row is another
@@ -824,92 +805,349 @@ __global__ void k_place_remote(FinParams p, const StageRec *rem, unsigned long l
     }
 }
 
-// row pointers, mirror pass (local pairs, and the mirrored entries other ranks sent: `remote`), per-row column sort + move to b_col / b_val
-static void ov_launch_finalize(Ctx &c, uint32_t half, bool all_sorts, uint32_t &skipped_sorts, const StageRec *remote, int64_t nremote, int64_t slot = 0)
+// ---- the plan-free call: CSR + columns of A -> pruned CSR B, everything in between computed here ---------------------------------------------
+// the driver: decisions from ov_plan.hpp, one OvRun state, steps named for what they leave behind
+
+// mirrored entries travel as 16-byte words (positions fit 16 bits), not as 32-byte records
+static bool ov_mir16(const Ctx &c) { return c.pos16 && !c.opt.mir32; }
+
+// what the plan reads of a context.  pass 1 of a context that has no staging capacity yet (and no workspace hint) asks the device for its free memory
+static OvInput ov_input(Ctx &c, int phase, int pass)
+{
+    OvInput in;
+    const RowWindow w = c.window();
+    in.M = c.M; in.N = c.N; in.Z = c.Z; in.row_lo = w.lo; in.row_hi = w.hi; in.max_row_nnz = c.max_row_nnz; in.max_col_nnz = c.max_col_nnz;
+    in.fbits = c.fbits; in.pos16 = c.pos16; in.use_ell = c.use_ell; in.csr_hints = c.csr_hints; in.csr_inline = c.csr_inline; in.csr_suffix = c.csr_suffix;
+    in.have_row_order = c.have_row_order; in.num_cus = c.num_cus;
+    const Options &o = c.opt;
+    in.opt.no_symmetry = o.no_symmetry; in.opt.no_pay = o.no_pay; in.opt.mir32 = o.mir32; in.opt.no_slab = o.no_slab; in.opt.no_sample = o.no_sample; in.opt.ov_generic = o.ov_generic;
+    in.opt.dk = o.dk; in.opt.dense_up = o.dense_up; in.opt.dense_wgs = o.dense_wgs; in.opt.slab_q16 = o.slab_q16; in.opt.slab_pct = o.slab_pct;
+    in.opt.tune3 = o.tune[3]; in.opt.tune4 = o.tune[4]; in.opt.tune5 = o.tune[5]; in.opt.tune7 = o.tune[7];
+    in.hints.prior_q16 = c.ov_prior_q16; in.hints.slab_q16 = c.ov_slab_q16; in.hints.tiers_known = c.ov_tiers_known;
+    for (int t = 0; t < NUM_TIERS; ++t) in.hints.tier_used[t] = c.ov_tier_used[t];
+    in.hints.sort_used[0] = c.ov_sort_used[0]; in.hints.sort_used[1] = c.ov_sort_used[1];
+    in.phase = phase; in.pass = pass;
+    in.tmp_cap = c.ov_tmp_cap; in.workspace_hint_bytes = c.cfg.workspace_hint_bytes;
+    if (in.tmp_cap == 0 && in.workspace_hint_bytes <= 0) {
+        size_t free_b = 0, total_b = 0;
+        ELBA_HIP(hipMemGetInfo(&free_b, &total_b));
+        in.free_bytes = (int64_t)free_b;
+    }
+    return in;
+}
+
+// ---- the tier table's rows -> instantiations of k_spgemm_direct ------------------------------------------------------------------------------
+// A dense row has one instantiation (gather depth 2, its table bits compiled in where the row names them); every other row one per gather depth, and
+// a row the reads path can run (no HBM table, no payload) that path's instantiation too.  ov_row_kernels is THE enumeration: the launch picks from
+// it, and ov_set_attributes raises the dynamic-LDS limit of everything in it — a launched instantiation cannot be missing there.
+template <int R, int DK, bool SPEC> static constexpr auto ov_row_kernel()
+{
+    constexpr OvTierRow r = OV_ROWS[R];
+    if constexpr (r.dense) return &k_spgemm_direct<r.block, false, false, 2, true, r.tbc>;
+    else if constexpr (SPEC) return &k_spgemm_direct<r.block, false, false, 0, false, 0, true>;
+    else return &k_spgemm_direct<r.block, r.global, r.payload, DK>;
+}
+template <int R> static constexpr bool ov_row_has_spec() { return !OV_ROWS[R].dense && !OV_ROWS[R].global && !OV_ROWS[R].payload; }
+template <int R, typename F> static void ov_row_kernels(F &&f)
+{
+    f(ov_row_kernel<R, 0, false>());
+    if constexpr (!OV_ROWS[R].dense) { f(ov_row_kernel<R, 1, false>()); f(ov_row_kernel<R, 2, false>()); f(ov_row_kernel<R, 4, false>()); }
+    if constexpr (ov_row_has_spec<R>()) f(ov_row_kernel<R, 0, true>());
+}
+template <int... R> static void ov_set_attributes(std::integer_sequence<int, R...>)
+{
+    (ov_row_kernels<R>([](auto k) { ELBA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)OV_LDS_MAX)); }), ...);
+}
+
+static OvSpecParams ov_spec_params(const OvParams &p)
+{
+    OvSpecParams q{};
+    q.a_rowptr = p.a_rowptr; q.a_csr = p.a_csr; q.a_ell = p.a_ell; q.tick_rows = p.tick_rows;
+    q.s_stride = p.s_stride; q.lpc_log2 = p.lpc_log2; q.max_col = p.max_col; q.fbits = p.fbits; q.M = p.M; q.Mcols = p.Mcols; q.use_feedback = p.use_feedback;
+    for (int t = 0; t < NUM_LDS_TIERS; ++t) q.tier_limit[t] = p.tier_limit[t];
+    q.fb_enough = p.fb_enough; q.tmp_cap = p.tmp_cap;
+    q.row_cnt = p.row_cnt; q.low_cnt = p.low_cnt; q.row_off = p.row_off; q.lists = p.lists; q.sample_list = p.sample_list; q.ctr = p.ctr;
+    q.rec = p.rec; q.tick = p.tick; q.slab = p.slab; q.slab_pos = p.slab_pos;
+    return q;
+}
+
+// one row -> its hipLaunchKernelGGL (sample: the launch computes the sample's rows, not the tier's queue)
+template <int R> static void ov_launch_row(const OvLaunch &l, const OvPlan &plan, const OvParams &p, hipStream_t s, uint32_t sample)
+{
+    constexpr OvTierRow r = OV_ROWS[R];
+    const dim3 grid((unsigned)l.grid), block((unsigned)r.block);
+    const uint32_t tb = (uint32_t)r.tbits;
+    if constexpr (ov_row_has_spec<R>()) {
+        if (plan.spec) { hipLaunchKernelGGL((ov_row_kernel<R, 0, true>()), grid, block, l.lds, s, ov_spec_params(p), r.tier, tb, sample); return; }
+    }
+    if (r.dense || plan.dk == 0) hipLaunchKernelGGL((ov_row_kernel<R, 0, false>()), grid, block, l.lds, s, p, r.tier, tb, sample);
+    else if (plan.dk == 1) hipLaunchKernelGGL((ov_row_kernel<R, 1, false>()), grid, block, l.lds, s, p, r.tier, tb, sample);
+    else if (plan.dk == 4) hipLaunchKernelGGL((ov_row_kernel<R, 4, false>()), grid, block, l.lds, s, p, r.tier, tb, sample);
+    else hipLaunchKernelGGL((ov_row_kernel<R, 2, false>()), grid, block, l.lds, s, p, r.tier, tb, sample);
+}
+template <int... R> static void ov_launch(std::integer_sequence<int, R...>, const OvLaunch &l, const OvPlan &plan, const OvParams &p, hipStream_t s, uint32_t sample)
+{
+    ((l.row == R ? ov_launch_row<R>(l, plan, p, s, sample) : (void)0), ...);
+}
+using OvRowSeq = std::make_integer_sequence<int, OV_NROWS>;
+
+// ---- the state of one call --------------------------------------------------------------------------------------------------------------------
+// phase (OvInput): 0 the whole call, 1 seed_matrix_begin, 2 seed_matrix_send
+struct OvRun {
+    Ctx &c;
+    OvInput in; OvPlan plan;
+    OvParams p{};            // rebuilt from the plan and the buffers by every ov_bind: no pointer into a DevBuf outlives a reserve()
+    OvCounters *hc = nullptr;      // the pinned landing area of the counter read-back
+    int passes = 0;
+    bool timed = false, was_timed = true;
+    float ms_sym = 0, ms_num = 0, ms_fin = 0, ms_tot = 0;
+};
+
+// every buffer of a pass at the size its plan asks for, THEN OvParams from the plan and the buffers' addresses (a grown staging area moves: nothing
+// read before this point is used after it); the pass is counted and its timing decided
+static void ov_bind(OvRun &r)
+{
+    Ctx &c = r.c;
+    const OvPlan &pl = r.plan;
+    const int64_t M = c.M;
+    ++r.passes;
+    const int stride = c.cfg.timing_stride > 1 ? c.cfg.timing_stride : 1;
+    r.timed = r.passes > 1 || (c.ov_calls++ % (uint64_t)stride) == 0;
+    c.ov_tmp_cap = pl.tmp_cap;
+    c.ov_tmp.reserve((size_t)pl.tmp_cap * sizeof(StageRec));
+    c.ov_rec16 = pl.mir16;
+    c.b_cap_entries = pl.b_cap;
+    c.b_col.reserve((size_t)(pl.b_cap + 1) * 4);
+    c.b_val.reserve((size_t)(pl.b_cap + 1) * sizeof(elba_seed_t));
+    if (pl.half) c.ov_mir.reserve((size_t)(pl.b_cap + 1) * (pl.mir16 ? 16 : sizeof(StageRec)));
+    c.ov_slab_on = pl.slab_on;
+    if (pl.slab_on) { c.ov_slab_cap = pl.slab_cap; c.ov_slab.reserve((size_t)pl.slab_cap * 16); c.ov_slabpos.reserve((size_t)(M + 4) * 8); c.ov_slabn.reserve((size_t)(M + 8) * 4); }
+    c.ov_sample.reserve(OV_SAMPLE_ROWS * 4);
+
+    OvParams &p = r.p;
+    p = OvParams{};
+    const RowWindow w = c.window();
+    p.a_rowptr = c.a_rowptr.as<uint32_t>(); p.a_csr = c.a_csr.as<uint64_t>();
+    p.a_ell = c.use_ell ? c.a_ell.as<uint64_t>() : nullptr; p.a_ellj = c.csr_suffix ? c.a_ellj.as<uint32_t>() : nullptr; p.j_shift = c.j_shift; p.dense_up = (uint32_t)c.opt.dense_up; p.a_colptr = c.a_colptr.as<uint32_t>(); p.a_csc = c.a_csc.as<uint64_t>();
+    p.s_stride = c.s_stride; p.lpc_log2 = c.lpc_log2; p.max_col = pl.max_col;
+    p.M = (uint32_t)M; p.Mcols = (uint32_t)M; p.row_lo = (uint32_t)w.lo; p.row_hi = (uint32_t)w.hi; p.fbits = c.fbits;
+    p.half = pl.half; p.pos_mask = pl.pos_mask; p.hint_mask = pl.hint_mask; p.suffix = pl.suffix; p.inl = pl.inl;
+    p.row_order = pl.row_order ? c.row_order.as<uint32_t>() : nullptr; p.row_label = pl.row_order ? c.row_label.as<uint32_t>() : nullptr;
+    p.prior_q16 = pl.prior_q16; p.use_feedback = pl.use_feedback; p.fb_enough = pl.fb_enough;
+    p.pay16 = pl.pay16 ? 1u : 0u; p.qblk_log2 = pl.qblk_log2; p.min_tier = pl.min_tier;
+    for (int t = 0; t < NUM_LDS_TIERS; ++t) p.tier_limit[t] = pl.tier_limit[t];
+    p.tick_rows = c.ov_tickrows.as<uint32_t>();
+    p.row_cnt = c.ov_rowcnt.as<uint32_t>(); p.low_cnt = c.ov_totcnt.as<uint32_t>();
+    p.row_off = c.ov_rowoff.as<unsigned long long>(); p.lists = c.ov_lists.as<uint32_t>();
+    p.fin_lists = c.ov_lists.as<uint32_t>() + (size_t)NUM_TIERS * (size_t)(M + 1);
+    p.ctr = c.ov_counters.as<OvCounters>();
+    p.gtable = c.ov_gtable.as<uint32_t>(); p.gstride = pl.gstride;
+    p.tmp = c.ov_tmp.as<StageRec>(); p.tmp_cap = (unsigned long long)pl.tmp_cap;
+    p.rec16 = pl.mir16 ? 1u : 0u; p.rec = c.ov_tmp.as<uint4>(); p.tick = reinterpret_cast<uint32_t *>(c.ov_tmp.as<char>() + (size_t)pl.tmp_cap * 16);
+    p.slab_prior_q16 = pl.slab_prior_q16; p.slab_pct = (uint32_t)c.opt.slab_pct;
+    if (pl.slab_on) { p.slab = c.ov_slab.as<uint4>(); p.slab_cap = (unsigned long long)pl.slab_cap; p.slab_pos = c.ov_slabpos.as<unsigned long long>(); }
+    p.nsample = pl.nsample; p.sstep = pl.sstep; p.sample_list = c.ov_sample.as<uint32_t>();
+}
+
+// begin: the call is accepted, a cold call has forgotten the hints, the buffers whose size the matrix alone decides are there, the first pass is bound
+// What a call may remember from earlier calls on the same matrix is a HINT only — the distinct-partner / row-entry ratio that picks the starting
+// tiers, which tiers and sorts got rows — and `cold_calls` (elba_set_option) or a new matrix forgets it: then the ratio starts at 1/4 and the kernel
+// corrects itself from the rows already done, every tier is launched.  Capacities (staging, output) start from nnz(A) and only ever grow; a call
+// that overflows them is repeated with what it measured.
+static OvRun ov_begin(Ctx &c, int phase)
+{
+    const int64_t M = c.M;
+    accepted(c.v, phase == 0 ? EV_CREATE_SEED_MATRIX : phase == 1 ? EV_SEED_MATRIX_BEGIN : EV_SEED_MATRIX_SEND);
+    c.ov_phase = 0;      // (a begun sharded call that was never ended is abandoned here: its staged records are about to be overwritten)
+    ELBA_REQUIRE(M < 0xFFFFFF00ll, ELBA_ERR_UNSUPPORTED, "read ids beyond 2^32 - 256 (the top of the id range marks empty slots and idle lanes)");
+    if (c.cold_calls) { c.ov_prior_q16 = 0; c.ov_slab_q16 = 0; c.ov_tiers_known = false; c.ov_sort_used[0] = c.ov_sort_used[1] = true; }
+
+    c.ov_rowcnt.reserve((size_t)(M + 2) * 4);
+    c.ov_rowoff.reserve((size_t)(M + 1) * 8);
+    c.ov_lists.reserve((size_t)(NUM_TIERS + 2) * (size_t)(M + 1) * 4);
+    c.ov_counters.reserve(sizeof(OvCounters));
+    c.b_rowptr.reserve((size_t)(M + 2) * 8);
+    if (c.ov_totcnt.cap < (size_t)(M + 2) * 4) c.ov_low_clean = false;
+    c.ov_totcnt.reserve((size_t)(M + 2) * 4);
+    c.ov_tickrows.reserve((size_t)(M / 32 + 2) * 4);
+
+    const OvSpill sp = ov_spill_tables(M, c.num_cus);
+    c.ov_gtable.reserve((size_t)sp.blocks * 5 * sp.gstride * 4);      // (before ov_input asks for the free memory that bounds the staging area)
+    OvRun r{c};
+    r.in = ov_input(c, phase, 1);
+    r.plan = plan_ov(r.in);
+    // (inline partners follow the parity rule over ALL rows: a whole matrix in one call, or a shard's rows with the mirror exchange; a windowed matrix
+    //  multiplied alone keeps every partner outside its window — another rule)
+    ELBA_REQUIRE(!c.csr_inline || (c.use_ell && (phase >= 1 || r.plan.whole)), ELBA_ERR_STATE,
+                 "this windowed matrix carries inline partners (option panel_inline): multiply it through elba_seed_matrix_send / _begin, or rebuild it without the option");
+    c.ov_hints_used = r.plan.hints_used;
+    static DeviceOnce attr_once;
+    attr_once.run(c.device, [] { ov_set_attributes(OvRowSeq{}); });
+    c.ov_host.reserve(sizeof(OvCounters));
+    r.hc = static_cast<OvCounters *>(c.ov_host.p);
+    *r.hc = OvCounters{};
+    c.ov_passes = 0; c.ov_forwarded = 0; c.ov_spec = 0;
+    ov_bind(r);
+    return r;
+}
+
+// zero_counters: mark 0 is set, the call's counters are zero — in ONE launch (five memsets were five ~8 us gaps in front of a 6 ms call).  The ticket
+// counters come back clean from a call that ran to its end (k_finalize_wave); otherwise they are zeroed here too
+static void ov_zero_counters(OvRun &r)
+{
+    Ctx &c = r.c;
+    const int64_t M = c.M;
+    if (r.timed) c.ov_marks.mark(0, c.stream);
+    ZeroList z{};
+    auto add = [&](void *ptr, size_t bytes) { z.p[z.n] = static_cast<uint32_t *>(ptr); z.words[z.n] = (bytes + 3) / 4; ++z.n; };
+    if (!c.ov_low_clean) add(c.ov_totcnt.p, (size_t)(M + 2) * 4);
+    add(c.ov_counters.p, sizeof(OvCounters));
+    add(c.ov_rowcnt.p, (size_t)(M + 2) * 4);
+    add(c.ov_tickrows.p, (size_t)(M / 32 + 2) * 4);
+    if (r.plan.slab_on) add(c.ov_slabn.p, (size_t)(M + 8) * 4);      // (rows outside the window hold no slab entries)
+    size_t most = 0;
+    for (int q = 0; q < z.n; ++q) most = std::max(most, z.words[q]);
+    hipLaunchKernelGGL(k_zero_regions, dim3((unsigned)std::min<size_t>((most + 255) / 256, (size_t)r.plan.zero_blocks_max)), dim3(256), 0, c.stream, z);
+    c.ov_low_clean = false;
+}
+
+// sample: a cold call on a matrix of some size has queued its sample rows and computed them on the sample's tier (mark 1 between the two: the numeric
+// phase starts there); the ratio is measured then — nothing is forwarded on a prediction any more, nobody touches the hot sums
+static void ov_sample(OvRun &r)
+{
+    Ctx &c = r.c;
+    const bool sampling = r.plan.sample.row >= 0;
+    if (sampling) hipLaunchKernelGGL(k_classify_direct, dim3(1), dim3(256), 0, c.stream, r.p, 1);
+    if (r.timed) c.ov_marks.mark(1, c.stream);
+    if (!sampling) return;
+    ov_launch(OvRowSeq{}, r.plan.sample, r.plan, r.p, c.stream, 1u);
+    r.p.use_feedback = 0;
+}
+
+// classify: every (other) row of the window is queued on its starting tier
+static void ov_classify(OvRun &r)
+{
+    if (r.plan.classify_blocks > 0) hipLaunchKernelGGL(k_classify_direct, dim3((unsigned)r.plan.classify_blocks), dim3(256), 0, r.c.stream, r.p, 0);
+}
+
+// numeric: the tiers the plan launches have run, ascending (+ the HBM-table tier); mark 2 is set
+static void ov_numeric(OvRun &r)
+{
+    Ctx &c = r.c;
+    c.ov_spec = r.plan.nrows > 0 && r.plan.spec ? 1 : 0;
+    for (int t = 0; t < NUM_TIERS; ++t)
+        if ((r.plan.launched >> t) & 1u) ov_launch(OvRowSeq{}, r.plan.tier[t], r.plan, r.p, c.stream, 0u);
+    if (r.plan.nrows > 0) ELBA_HIP(hipGetLastError());
+    if (r.timed) c.ov_marks.mark(2, c.stream);
+}
+
+// finalize: row pointers, mirror pass (local pairs, and the mirrored entries other ranks sent: `remote`), per-row column sort + move to b_col / b_val
+static void ov_finalize(Ctx &c, const OvFinPlan &fp, uint32_t half, const StageRec *remote, int64_t nremote, int64_t slot = 0)
 {
     hipStream_t s = c.stream;
     const int64_t M = c.M;
-    const int64_t row_lo = c.row_lo, row_hi = c.row_hi < 0 ? M : c.row_hi, nrows = row_hi - row_lo;
+    const RowWindow w = c.window();
     const int cus = c.num_cus;
-    const bool mir16 = c.pos16 && !c.opt.mir32;
+    const bool mir16 = ov_mir16(c);
+    c.ov_sortkeys.reserve((size_t)fp.huge_blocks * fp.sort_stride * 8);
+    if (fp.scan_rowptr) c.ov_sum_tmp.reserve((size_t)(M + 2) * 4);
     FinParams f{};
     f.row_cnt = c.ov_rowcnt.as<uint32_t>(); f.low_cnt = c.ov_totcnt.as<uint32_t>(); f.tmp = c.ov_tmp.as<StageRec>(); f.mir = half ? c.ov_mir.as<StageRec>() : nullptr; f.half = half; f.row_off = c.ov_rowoff.as<unsigned long long>(); f.b_rowptr = c.b_rowptr.as<int64_t>();
     f.b_col = c.b_col.as<uint32_t>(); f.b_val = c.b_val.as<elba_seed_t>();
-    f.M = (uint32_t)M; f.row_lo = (uint32_t)row_lo; f.row_hi = (uint32_t)row_hi; f.fin_lists = c.ov_lists.as<uint32_t>() + (size_t)NUM_TIERS * (size_t)(M + 1); f.ctr = c.ov_counters.as<OvCounters>();
+    f.M = (uint32_t)M; f.row_lo = (uint32_t)w.lo; f.row_hi = (uint32_t)w.hi; f.fin_lists = c.ov_lists.as<uint32_t>() + (size_t)NUM_TIERS * (size_t)(M + 1); f.ctr = c.ov_counters.as<OvCounters>();
     f.b_cap = c.b_cap_entries;
     f.mir16 = mir16 ? 1u : 0u;
     f.tick_rows = c.ov_tickrows.as<uint32_t>();
     f.rec16 = c.ov_rec16 ? 1u : 0u; f.rec = c.ov_tmp.as<uint4>(); f.tick = reinterpret_cast<const uint32_t *>(c.ov_tmp.as<char>() + (size_t)c.ov_tmp_cap * 16);
-    f.a_rowptr = c.a_rowptr.as<uint32_t>(); f.slab = (half == 1u && mir16 && c.ov_slab_on) ? c.ov_slab.as<uint4>() : nullptr;
+    f.a_rowptr = c.a_rowptr.as<uint32_t>(); f.slab = fp.slabs ? c.ov_slab.as<uint4>() : nullptr;
     f.slab_pos = f.slab ? c.ov_slabpos.as<unsigned long long>() : nullptr; f.slab_n = f.slab ? c.ov_slabn.as<uint32_t>() : nullptr;
-    if (f.slab && nrows > 0) hipLaunchKernelGGL(k_slab_fold, dim3((unsigned)((nrows + 255) / 256)), dim3(256), 0, s, f);
-    const int gblocks = 32;
-    uint64_t sstride = 2;
-    while (sstride < (uint64_t)M) sstride <<= 1;
-    c.ov_sortkeys.reserve((size_t)gblocks * sstride * 8);
-    f.sortkeys = c.ov_sortkeys.as<uint64_t>(); f.sort_stride = sstride;
-    if (M + 1 <= (1 << 17)) {
-        hipLaunchKernelGGL(k_row_pointers, dim3((unsigned)((M + 1 + RP_TILE - 1) / RP_TILE)), dim3(256), 0, s, f);
-    } else {
-        c.ov_sum_tmp.reserve((size_t)(M + 2) * 4);
+    f.sortkeys = c.ov_sortkeys.as<uint64_t>(); f.sort_stride = fp.sort_stride;
+    if (fp.slab_fold_blocks > 0) hipLaunchKernelGGL(k_slab_fold, dim3((unsigned)fp.slab_fold_blocks), dim3(256), 0, s, f);
+    if (!fp.scan_rowptr) hipLaunchKernelGGL(k_row_pointers, dim3((unsigned)fp.rowptr_blocks), dim3(256), 0, s, f);
+    else {
         f.sum_tmp = c.ov_sum_tmp.as<uint32_t>();
-        hipLaunchKernelGGL(k_sum_counts, dim3((unsigned)((M + 1 + 255) / 256)), dim3(256), 0, s, f);
+        hipLaunchKernelGGL(k_sum_counts, dim3((unsigned)fp.rowptr_blocks), dim3(256), 0, s, f);
         exclusive_scan_u32_to_i64(s, f.sum_tmp, c.b_rowptr.as<int64_t>(), M + 1, c.ws_scan);
     }
-    if (nrows > 0) {
-        int nb = (int)((nrows + 3) / 4);
-        if (nb > cus * 32) nb = cus * 32;
-        hipLaunchKernelGGL(k_mirror, dim3(nb), dim3(256), 0, s, f);
-        if (nremote > 0 && slot == 0) hipLaunchKernelGGL(k_place_remote, dim3((unsigned)std::min<int64_t>((nremote + 255) / 256, (int64_t)cus * 32)), dim3(256), 0, s, f, remote, (unsigned long long)nremote, 0ull);
-        if (nremote > 0 && slot != 0) hipLaunchKernelGGL(k_place_remote, dim3((unsigned)std::min<int64_t>((slot + 255) / 256, (int64_t)cus * 4), (unsigned)(nremote / slot)), dim3(256), 0, s, f, remote, (unsigned long long)nremote, (unsigned long long)slot);
-        hipLaunchKernelGGL(k_finalize_wave, dim3(nb), dim3(256), 0, s, f);
-        if (f.rec16 && f.mir16) hipLaunchKernelGGL(k_finalize_mid16, dim3(nb), dim3(256), 0, s, f);
-        else hipLaunchKernelGGL(k_finalize_mid, dim3(nb), dim3(256), 0, s, f);
-        skipped_sorts = 0;
-        bool narrow = false;
-        // (a row of B holds at most min(longest row of A x longest column, reads) entries: the sorts for wider rows are not launched for a matrix that cannot have them)
-        if (c.opt.tune[4] != 2 && std::min<uint64_t>((uint64_t)std::max<int64_t>(c.max_row_nnz, 1) * (uint64_t)std::max<int64_t>(c.max_col_nnz, 1), (uint64_t)M) <= (uint64_t)FIN_WAVE2_MAX && nremote == 0) narrow = true;
-        if (!narrow && (all_sorts || c.ov_sort_used[0])) hipLaunchKernelGGL(k_finalize_bucket, dim3((unsigned)(nrows < (int64_t)cus * 4 ? nrows : (int64_t)cus * 4)), dim3(256), 0, s, f);
-        else skipped_sorts |= 1u;
-        if (!narrow && (all_sorts || c.ov_sort_used[1])) hipLaunchKernelGGL(k_finalize_huge, dim3(gblocks), dim3(256), 0, s, f);
-        else skipped_sorts |= 2u;
-    }
+    if (fp.nrows <= 0) return;
+    const dim3 rows((unsigned)fp.row_blocks);
+    hipLaunchKernelGGL(k_mirror, rows, dim3(256), 0, s, f);
+    if (nremote > 0 && slot == 0) hipLaunchKernelGGL(k_place_remote, dim3((unsigned)std::min<int64_t>((nremote + 255) / 256, (int64_t)cus * 32)), dim3(256), 0, s, f, remote, (unsigned long long)nremote, 0ull);
+    if (nremote > 0 && slot != 0) hipLaunchKernelGGL(k_place_remote, dim3((unsigned)std::min<int64_t>((slot + 255) / 256, (int64_t)cus * 4), (unsigned)(nremote / slot)), dim3(256), 0, s, f, remote, (unsigned long long)nremote, (unsigned long long)slot);
+    hipLaunchKernelGGL(k_finalize_wave, rows, dim3(256), 0, s, f);
+    if (f.rec16 && f.mir16) hipLaunchKernelGGL(k_finalize_mid16, rows, dim3(256), 0, s, f);
+    else hipLaunchKernelGGL(k_finalize_mid, rows, dim3(256), 0, s, f);
+    if (fp.sorts & 1u) hipLaunchKernelGGL(k_finalize_bucket, dim3((unsigned)fp.bucket_blocks), dim3(256), 0, s, f);
+    if (fp.sorts & 2u) hipLaunchKernelGGL(k_finalize_huge, dim3((unsigned)fp.huge_blocks), dim3(256), 0, s, f);
 }
 
-// fold the counter read-back into elba_overlap_stats and remember the hints for the next call; `extra_*`: entries / strict-upper entries that
-// arrived from other ranks (mirror exchange)
-static void ov_finish_stats(Ctx &c, OvCounters &hc, elba_overlap_stats &st, int passes, bool was_timed, float ms_tot, float ms_sym, float ms_num, float ms_fin, int64_t extra_nnz, int64_t extra_upper)
+// read_back: mark 3 is set, the counters are on the host and the stream has drained (the call's ONE synchronisation when nothing overflows); the
+// pass's times are added up
+static void ov_read_back(OvRun &r)
+{
+    Ctx &c = r.c;
+    if (r.timed) c.ov_marks.mark(3, c.stream);
+    ELBA_HIP(hipMemcpyAsync(r.hc, c.ov_counters.p, sizeof(OvCounters), hipMemcpyDeviceToHost, c.stream));
+    ELBA_HIP(hipStreamSynchronize(c.stream));
+    if (r.timed) { r.ms_sym += c.ov_marks.ms(0, 1); r.ms_num += c.ov_marks.ms(1, 2); r.ms_fin = c.ov_marks.ms(2, 3); r.ms_tot += c.ov_marks.ms(0, 3); }
+    r.was_timed = r.timed;
+    c.ov_passes = r.passes; c.ov_forwarded += r.hc->nforward;
+}
+
+// settle: true — the pass stands.  false — the staging area was too small, or a row reached a tier / sort that was not launched: a new plan from
+// what is known now (ov_next_pass: staging as large as the cursor, every tier and sort) is bound for another pass
+static bool ov_settle(OvRun &r)
+{
+    Ctx &c = r.c;
+    const OvCounters &hc = *r.hc;
+    const uint32_t sorts = r.in.phase == 0 ? r.plan.fin.sorts : 3u;      // (no finalize in this call: no sort to miss)
+    bool missed = false;
+    for (int t = 0; t < NUM_TIERS; ++t) missed |= !((r.plan.launched >> t) & 1u) && hc.tier_count[t] > 0;
+    missed |= (!(sorts & 1u) && hc.fin_count[0] > 0) || (!(sorts & 2u) && hc.fin_count[1] > 0);
+    if (!hc.overflow && !missed) { c.ov_low_clean = r.in.phase == 0; return true; }
+    if (c.opt.trace) fprintf(stderr, "[elba] overlap call repeated: overflow=%u missed=%d cursor=%llu tmp_cap=%lld\n", hc.overflow, (int)missed, hc.cursor, (long long)c.ov_tmp_cap);
+    ELBA_REQUIRE(r.passes < 4, ELBA_ERR_INTERNAL, "overlap output did not settle");
+    c.ov_tiers_known = false;
+    r.in = ov_next_pass(r.in, r.plan, hc.overflow != 0, hc.cursor);
+    r.plan = plan_ov(r.in);
+    ov_bind(r);
+    return false;
+}
+
+// finish: fold the counter read-back into elba_overlap_stats and remember the hints for the next call (ov_next_hints); `extra_*`: entries /
+// strict-upper entries that arrived from other ranks (mirror exchange)
+static void ov_finish(Ctx &c, OvCounters &hc, int passes, bool was_timed, float ms_tot, float ms_sym, float ms_num, float ms_fin, int64_t extra_nnz, int64_t extra_upper)
 {
     const int64_t M = c.M, N = c.N, Z = c.Z;
+    const RowWindow w = c.window();
+    elba_overlap_stats st{};
+    st.nrows = w.rows();
 #ifdef ELBA_PHASE_CLOCK
     fprintf(stderr, "[elba phase] wave-0 cycles summed over %llu workgroups: header=%llu init=%llu accumulate=%llu handoff=%llu sweep=%llu reserve=%llu store=%llu | rows %u,%u,%u,%u,%u,%u\n",
             hc.phase[10], hc.phase[0], hc.phase[1], hc.phase[2], hc.phase[3], hc.phase[4], hc.phase[5], hc.phase[6],
             hc.tier_count[0], hc.tier_count[1], hc.tier_count[2], hc.tier_count[3], hc.tier_count[4], hc.tier_count[5]);
 #endif
+    OvMeasured m;
     for (int sh = 0; sh < NUM_SHARDS; ++sh) {       // fold the statistics shards
         const OvShard &x = hc.shard[sh];
         hc.yraw += x.yraw; hc.nnz += x.nnz; hc.ndiag += x.ndiag; hc.nupper += x.nupper; hc.products += x.products;
         if (x.maxshared > hc.maxshared) hc.maxshared = x.maxshared;
         for (int t = 0; t < NUM_TIERS; ++t) hc.tier_done[t] += x.tier_done[t];
+        m.fb_claims += x.fb_claims; m.fb_ub += x.fb_ub;
     }
-    unsigned long long fbc = 0, fbu = 0;
-    for (int sh = 0; sh < NUM_SHARDS; ++sh) { fbc += hc.shard[sh].fb_claims; fbu += hc.shard[sh].fb_ub; }
     const int64_t Y = (int64_t)hc.nnz + extra_nnz;
-    for (int t = 0; t < NUM_TIERS; ++t) c.ov_tier_used[t] = hc.tier_count[t] > 0;
-    c.ov_tiers_known = true;
-    c.ov_sort_used[0] = hc.fin_count[0] > 0; c.ov_sort_used[1] = hc.fin_count[1] > 0;
+    m.Z = Z; m.nnz = (int64_t)hc.nnz; m.ndiag = (int64_t)hc.ndiag; m.extra_nnz = extra_nnz; m.whole = w.lo == 0 && w.hi == M;
+    for (int t = 0; t < NUM_TIERS; ++t) m.tier_count[t] = hc.tier_count[t];
+    m.fin_count[0] = hc.fin_count[0]; m.fin_count[1] = hc.fin_count[1];
+    OvHints old;
+    old.prior_q16 = c.ov_prior_q16; old.slab_q16 = c.ov_slab_q16;
+    const OvHints h = ov_next_hints(old, m);
+    for (int t = 0; t < NUM_TIERS; ++t) c.ov_tier_used[t] = h.tier_used[t];
+    c.ov_tiers_known = h.tiers_known;
+    c.ov_sort_used[0] = h.sort_used[0]; c.ov_sort_used[1] = h.sort_used[1];
+    c.ov_slab_q16 = h.slab_q16; c.ov_prior_q16 = h.prior_q16;
     c.ov_mir_placed = (int64_t)hc.mir_placed;
     c.ov_slab_q16_used = hc.slab_q16;
-    if (c.row_lo == 0 && (c.row_hi < 0 || c.row_hi == M) && Z > 0 && extra_nnz == 0) {      // mirrored entries per row entry of A, for the next call's slabs (a hint, like the ratio below)
-        const double r = 0.5 * (double)((int64_t)hc.nnz - (int64_t)hc.ndiag) / (double)Z * 65536.0;
-        c.ov_slab_q16 = r < 1.0 ? 1u : (r > 4.0e9 ? 4000000000u : (uint32_t)r);
-    }
-    if (fbu > 0) {   // the measured distinct-partner / row-entry ratio (+25 %) picks the next call's starting tiers
-        double r = 1.25 * (double)fbc / (double)fbu * 65536.0;
-        const uint32_t q = r < 64.0 ? 64u : (r > 4.0e9 ? 4000000000u : (uint32_t)r);
-        const uint32_t old = c.ov_prior_q16;
-        if (old == 0 || q > old + old / 10 || q + old / 10 < old) c.ov_prior_q16 = q;
-    }
     st.products = c.ov_hints_used ? c.A_products : (int64_t)hc.products;      // (entries that skip their column do not see its length: counted when A was built)
     st.nnz_before_prune = (int64_t)hc.yraw;
     st.nnz = Y;
@@ -931,340 +1169,107 @@ static void ov_finish_stats(Ctx &c, OvCounters &hc, elba_overlap_stats &st, int 
     c.ostats = st;
 }
 
-// The reads-path instantiation of the numeric kernel (OvSpecParams) runs a call whose every switch has the value that instantiation fixes: padded columns
-// with inline partners and ownership hints, one triangle + mirror over the whole matrix in one call, 32-bit accumulators carrying posT, 16-byte records,
-// the gather depth of inline rows.  Anything else — both triangles, CSC columns, 64-bit accumulators, 32-byte records, the dense path, windows and
-// shards, a forced gather depth or tier (option "dk", "tune3" .. "tune5", "tune7"), option "ov_generic" (A/B) — takes the general kernel.
-static bool ov_spec_ok(const Ctx &c, const OvParams &p, bool pay, int dk)
+// a pass up to the end of its numeric phase — what the three entry points share
+static void ov_numeric_pass(OvRun &r)
 {
-    return !c.opt.ov_generic && c.opt.dk < 0 && dk == 0 && !pay && p.pay16 == OvSpecParams::pay16 && p.a_ell != nullptr && p.half == OvSpecParams::half &&
-           p.hint_mask == OvSpecParams::hint_mask && p.pos_mask == OvSpecParams::pos_mask && p.inl == OvSpecParams::inl && p.rec16 == OvSpecParams::rec16 &&
-           p.suffix == OvSpecParams::suffix && p.row_order == nullptr && p.qblk_log2 == OvSpecParams::qblk_log2 && p.row_lo == 0u && p.row_hi == p.M && p.Mcols == p.M &&
-           c.opt.tune[3] == 0 && c.opt.tune[4] == 0 && c.opt.tune[5] == 0 && c.opt.tune[7] == 0;
-}
-static OvSpecParams ov_spec_params(const OvParams &p)
-{
-    OvSpecParams q{};
-    q.a_rowptr = p.a_rowptr; q.a_csr = p.a_csr; q.a_ell = p.a_ell; q.tick_rows = p.tick_rows;
-    q.s_stride = p.s_stride; q.lpc_log2 = p.lpc_log2; q.max_col = p.max_col; q.fbits = p.fbits; q.M = p.M; q.Mcols = p.Mcols; q.use_feedback = p.use_feedback;
-    for (int t = 0; t < NUM_LDS_TIERS; ++t) q.tier_limit[t] = p.tier_limit[t];
-    q.fb_enough = p.fb_enough; q.tmp_cap = p.tmp_cap;
-    q.row_cnt = p.row_cnt; q.low_cnt = p.low_cnt; q.row_off = p.row_off; q.lists = p.lists; q.sample_list = p.sample_list; q.ctr = p.ctr;
-    q.rec = p.rec; q.tick = p.tick; q.slab = p.slab; q.slab_pos = p.slab_pos;
-    return q;
+    ov_zero_counters(r);
+    ov_sample(r);
+    ov_classify(r);
+    ov_numeric(r);
 }
 
-// phase 0: the whole call.  phase 1: the first half of a sharded call with mirror exchange (stage_seed_matrix_begin): classify + numeric with
-// GLOBAL pair ownership, stops before the finalize pass.  phase 2: the same, only QUEUED — every tier is launched, nothing is read back and the
-// host does not wait (stage_seed_matrix_send; what phase 1 checks after its synchronisation, stage_seed_matrix_recv checks at the end of the step).
-static void create_seed_matrix_direct(Ctx &c, int phase)
+// The whole call.  Launch sequence (one stream, ONE host synchronisation at the end when nothing overflows):
+//   counters = 0, row_cnt = 0 | [sample] | k_classify_direct | k_spgemm_direct on the plan's tiers, ascending (+ the HBM-table tier) |
+//   k_row_pointers (scan of the rows' counts) | k_mirror | k_finalize_wave / _mid / _bucket / _huge (per-row column sort + move to b_col / b_val) |
+//   counter read-back.
+void stage_create_seed_matrix(Ctx &c)
 {
-    hipStream_t s = c.stream;
-    const int64_t M = c.M, Z = c.Z;
-    const int64_t row_lo = c.row_lo, row_hi = c.row_hi < 0 ? M : c.row_hi;
-    elba_overlap_stats st{};
-    st.nrows = row_hi - row_lo;
-    accepted(c.v, phase == 0 ? EV_CREATE_SEED_MATRIX : phase == 1 ? EV_SEED_MATRIX_BEGIN : EV_SEED_MATRIX_SEND);
-    c.ov_phase = 0;      // (a begun sharded call that was never ended is abandoned here: its staged records are about to be overwritten)
-    ELBA_REQUIRE(M < 0xFFFFFF00ll, ELBA_ERR_UNSUPPORTED, "read ids beyond 2^32 - 256 (the top of the id range marks empty slots and idle lanes)");
-    if (c.cold_calls) { c.ov_prior_q16 = 0; c.ov_slab_q16 = 0; c.ov_tiers_known = false; c.ov_sort_used[0] = c.ov_sort_used[1] = true; }
-
-    c.ov_rowcnt.reserve((size_t)(M + 2) * 4);
-    c.ov_rowoff.reserve((size_t)(M + 1) * 8);
-    c.ov_lists.reserve((size_t)(NUM_TIERS + 2) * (size_t)(M + 1) * 4);
-    c.ov_counters.reserve(sizeof(OvCounters));
-    c.b_rowptr.reserve((size_t)(M + 2) * 8);
-    if (c.ov_totcnt.cap < (size_t)(M + 2) * 4) c.ov_low_clean = false;
-    c.ov_totcnt.reserve((size_t)(M + 2) * 4);
-
-    uint64_t gstride = 2;
-    while (gstride < 2ull * (uint64_t)(M > 1 ? M : 1)) gstride <<= 1;
-    int spill_blocks = (int)((4ull << 30) / (20ull * gstride));
-    spill_blocks = spill_blocks < 64 ? 64 : (spill_blocks > c.num_cus * 2 ? c.num_cus * 2 : spill_blocks);
-    c.ov_gtable.reserve((size_t)spill_blocks * 5 * gstride * 4);
-
-    const int cus = c.num_cus;
-    const int64_t nrows = row_hi - row_lo;
-    // B is symmetric up to exchanging the two positions of every seed (exactly: the canonical seeds are min / max over a cross product of
-    // positions per shared k-mer): a pair of rows of this context's window is accumulated on its smaller row only and the surviving
-    // entries are mirrored into the partner's row afterwards (k_mirror) — half the accumulator updates, tables half as full.
-    const bool half = phase >= 1 || !c.opt.no_symmetry || c.csr_inline;      // (rows with inline partners hold one triangle's pairs only: "no_symmetry" counts when A is built)
-    const int64_t slack = (int64_t)cus * 32 * STAGE_CHUNK + 64;      // one open chunk per resident workgroup
-    if (c.ov_tmp_cap == 0) {
-        if (c.cfg.workspace_hint_bytes > 0) c.ov_tmp_cap = c.cfg.workspace_hint_bytes / (int64_t)sizeof(StageRec);
-        else {
-            // nnz(B) <= products / 2 and, on every read set seen so far, < nnz(A) / 4: start from nnz(A) (bounded by half the free memory)
-            size_t free_b = 0, total_b = 0;
-            ELBA_HIP(hipMemGetInfo(&free_b, &total_b));
-            const int64_t budget = (int64_t)(free_b / 2 / (sizeof(StageRec) + (half ? 2 * (24 + 32) : 24)));
-            c.ov_tmp_cap = std::min<int64_t>(std::max<int64_t>(half ? Z / 2 : Z, 1 << 16) + slack, std::max<int64_t>(budget, 1024));
-        }
-        if (c.ov_tmp_cap < 1024) c.ov_tmp_cap = 1024;
-    }
-
-    OvParams p{};
-    p.a_rowptr = c.a_rowptr.as<uint32_t>(); p.a_csr = c.a_csr.as<uint64_t>();
-    p.a_ell = c.use_ell ? c.a_ell.as<uint64_t>() : nullptr; p.a_ellj = c.csr_suffix ? c.a_ellj.as<uint32_t>() : nullptr; p.j_shift = c.j_shift; p.dense_up = (uint32_t)c.opt.dense_up; p.a_colptr = c.a_colptr.as<uint32_t>(); p.a_csc = c.a_csc.as<uint64_t>();
-    p.s_stride = c.s_stride; p.lpc_log2 = c.lpc_log2; p.max_col = (uint32_t)(c.max_col_nnz > 0 ? c.max_col_nnz : 1);
-    p.M = (uint32_t)M; p.Mcols = (uint32_t)M; p.row_lo = (uint32_t)row_lo; p.row_hi = (uint32_t)row_hi; p.fbits = c.fbits;
-    p.half = phase >= 1 ? 2u : (half ? 1u : 0u);      // 2: a pair is accumulated on ONE of its two rows wherever the other row lives (its rank gets the mirrored entry by exchange)
-    p.pos_mask = c.csr_suffix ? 0xFFFFu : (c.csr_hints ? 0x3FFFFFFFu : 0xFFFFFFFFu);
-    p.hint_mask = !c.csr_hints ? 0u : (p.half == 2u ? 1u << 30 : (p.half == 1u ? 1u << 31 : 0u));
-    // (the dense path: one triangle per window, partners outside the window kept — its candidate hand-out knows no other rule.  Both triangles
-    //  ("no_symmetry") and the mirror exchange between ranks (half == 2: the parity rule over all ranks) take the general path, which reads the
-    //  same entries through pos_mask)
-    p.suffix = c.csr_suffix && p.half == 1u ? 1u : 0u;
-    p.inl = c.csr_inline ? 1u : 0u;
-    p.row_order = p.suffix && c.have_row_order ? c.row_order.as<uint32_t>() : nullptr; p.row_label = p.row_order ? c.row_label.as<uint32_t>() : nullptr;
-    c.ov_hints_used = c.ov_hints_used || c.csr_inline;
-    // (inline partners follow the parity rule over ALL rows: a whole matrix in one call, or a shard's rows with the mirror exchange; a windowed matrix
-    //  multiplied alone keeps every partner outside its window — another rule)
-    ELBA_REQUIRE(!c.csr_inline || (c.use_ell && (phase >= 1 || (row_lo == 0 && row_hi == M))), ELBA_ERR_STATE,
-                 "this windowed matrix carries inline partners (option panel_inline): multiply it through elba_seed_matrix_send / _begin, or rebuild it without the option");
-    c.ov_hints_used = p.hint_mask != 0u || p.suffix != 0u || c.csr_inline;      // (entries that fetch no column do not see its length: the product count comes from the build of A)
-    p.prior_q16 = c.ov_prior_q16 ? c.ov_prior_q16 : 16384u;      // distinct partners per row entry: 1/4 until measured
-    p.use_feedback = c.ov_prior_q16 ? 0u : 1u;
-    p.fb_enough = (unsigned long long)std::min<int64_t>(std::max<int64_t>(Z / 32, 1 << 16), 1 << 23);
-    bool pay = c.pos16 && !c.opt.no_pay;
-    // Round 5: where the positions AND every row's product sequence numbers (rank in the row << fbits | place in the column) fit 16 bits — every read set of
-    // ~10 kb reads — the extremes live in 32-bit words that carry posT (posQ is looked up in the row entry the sequence number names): the 2048-slot tier
-    // then needs 37 KB of table + 16 KB of rings per 512-lane workgroup instead of 53 + 24.5: THREE rows per CU in flight instead of two (the kernel waits for
-    // memory 69 % of its time: profiles/r04_summary.json), at the same 72-78 VGPRs.  Option "tune3" = 1 keeps the 64-bit accumulators (A/B).
-    const bool pay16 = pay && c.use_ell && !c.csr_suffix && c.opt.tune[3] != 1 && ((uint64_t)c.max_row_nnz << c.fbits) <= 65536ull;
-    p.pay16 = pay16 ? 1u : 0u;
-    if (pay16) pay = false;
-    // workgroup sizes grow with the table so that the largest tiers still bring enough waves to a CU (one or two workgroups fit its LDS)
-    const uint32_t blk[NUM_LDS_TIERS] = {p.suffix ? 256u : 128u, p.suffix && p.dense_up >= 1u ? 512u : 256u, p.suffix && p.dense_up >= 2u ? 1024u : 512u, 1024u, 512u};      // (dense path: four wavefronts share a 512-slot table — 32 per CU)
-    for (int t = 0; t < NUM_LDS_TIERS; ++t) {
-        const uint32_t T = 1u << (LDS_TBITS0 + t);
-        p.tier_limit[t] = std::min((T >> 2) * 3, T - blk[t]) - 1;      // a lane overshoots by at most one claim (Table::insert_lds)
-    }
-    c.ov_tickrows.reserve((size_t)(M / 32 + 2) * 4);
-    p.tick_rows = c.ov_tickrows.as<uint32_t>();
-    // a large matrix's rows start on the 2048-slot tier at least (three rows per CU with pay16): the two smaller tiers would receive a percent of the rows and cost a
-    // ~60 us launch each — 6.48 -> 6.3x ms on config 3; small matrices keep them (their rows ARE small); option "tune4" = 1: every tier (A/B)
-    p.qblk_log2 = c.opt.tune[5] > 0 ? (uint32_t)std::min<int64_t>(c.opt.tune[5] - 1, 12) : 0u;      // ("tune5" = log2 + 1.  Measured on config 5 at 1/25 — label-ordered queue, blocks of 32 / 128 / 512 places per XCD: 8.66-8.74 against 8.74-8.77 ms: nothing; single places stay)
-    p.min_tier = (pay16 && nrows >= 65536 && Z / nrows >= 1024 && c.opt.tune[4] != 1) ? 2u : 0u;      // (long rows only: a 512-lane workgroup on a row of 75 entries would idle)
-    if (c.opt.tune[7] >= 1 && c.opt.tune[7] <= NUM_TIERS) p.min_tier = (uint32_t)(c.opt.tune[7] - 1);      // ("tune7" = tier + 1: every row starts there at least; 6 = the HBM-table tier for all of them — what the spill tier costs when forced, bench.py)
-    p.row_cnt = c.ov_rowcnt.as<uint32_t>(); p.low_cnt = c.ov_totcnt.as<uint32_t>();
-    p.row_off = c.ov_rowoff.as<unsigned long long>(); p.lists = c.ov_lists.as<uint32_t>();
-    p.fin_lists = c.ov_lists.as<uint32_t>() + (size_t)NUM_TIERS * (size_t)(M + 1);
-    p.ctr = c.ov_counters.as<OvCounters>();
-    p.gtable = c.ov_gtable.as<uint32_t>(); p.gstride = gstride;
-
-    static DeviceOnce attr_once;
-    attr_once.run(c.device, [&] {
-        const int lds = 160 * 1024;
-#define ELBA_ATTR(B, P, D) ELBA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_spgemm_direct<B, false, P, D>), hipFuncAttributeMaxDynamicSharedMemorySize, lds))
-        ELBA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_spgemm_direct<512, false, false, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        ELBA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_spgemm_direct<1024, false, false, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        ELBA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_spgemm_direct<1024, false, false, 2, true, 11>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        ELBA_ATTR(512, true, 0); ELBA_ATTR(1024, true, 0); ELBA_ATTR(256, false, 0); ELBA_ATTR(512, false, 0); ELBA_ATTR(1024, false, 0);
-        ELBA_ATTR(512, true, 1); ELBA_ATTR(512, true, 2); ELBA_ATTR(512, true, 4); ELBA_ATTR(1024, true, 1); ELBA_ATTR(1024, true, 2); ELBA_ATTR(1024, true, 4);
-        ELBA_ATTR(256, false, 1); ELBA_ATTR(256, false, 2); ELBA_ATTR(256, false, 4);
-        ELBA_ATTR(512, false, 1); ELBA_ATTR(512, false, 2); ELBA_ATTR(512, false, 4); ELBA_ATTR(1024, false, 1); ELBA_ATTR(1024, false, 2); ELBA_ATTR(1024, false, 4);
-#undef ELBA_ATTR
-#define ELBA_ATTR(B) ELBA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_spgemm_direct<B, false, false, 0, false, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds))
-        ELBA_ATTR(128); ELBA_ATTR(256); ELBA_ATTR(512); ELBA_ATTR(1024);
-#undef ELBA_ATTR
-    });
-
-    c.ov_host.reserve(sizeof(OvCounters));
-    OvCounters &hc = *static_cast<OvCounters *>(c.ov_host.p);
-    hc = OvCounters{};
-    uint32_t skipped_tiers = 0, skipped_sorts = 0;
-    int passes = 0;
-    c.ov_passes = 0; c.ov_forwarded = 0; c.ov_spec = 0;
-    float ms_sym = 0, ms_num = 0, ms_fin = 0, ms_tot = 0;
-    bool was_timed = true;
-    for (;;) {
-        ++passes;
-        const int stride = c.cfg.timing_stride > 1 ? c.cfg.timing_stride : 1;
-        const bool timed = passes > 1 || (c.ov_calls++ % (uint64_t)stride) == 0;
-        c.ov_tmp.reserve((size_t)c.ov_tmp_cap * sizeof(StageRec));
-        p.tmp = c.ov_tmp.as<StageRec>(); p.tmp_cap = (unsigned long long)c.ov_tmp_cap;
-        const bool mir16 = c.pos16 && !c.opt.mir32;
-        c.ov_rec16 = mir16;
-        p.rec16 = mir16 ? 1u : 0u; p.rec = c.ov_tmp.as<uint4>(); p.tick = reinterpret_cast<uint32_t *>(c.ov_tmp.as<char>() + (size_t)c.ov_tmp_cap * 16);
-        c.b_cap_entries = half ? 2 * c.ov_tmp_cap : c.ov_tmp_cap;      // the output cannot be larger than what was staged (and mirrored)
-        c.b_col.reserve((size_t)(c.b_cap_entries + 1) * 4);
-        c.b_val.reserve((size_t)(c.b_cap_entries + 1) * sizeof(elba_seed_t));
-        if (half) c.ov_mir.reserve((size_t)(c.b_cap_entries + 1) * (mir16 ? 16 : sizeof(StageRec)));
-        // mirror slabs (above): one call on the window, 16-byte records, a ratio to size them by — a sample of this call's rows, an earlier call's
-        // measurement, or the test hook
-        p.use_feedback = c.ov_prior_q16 ? 0u : 1u;      // (a repeated pass starts like the first)
-        const bool sampling = p.use_feedback && nrows >= 8192 && !c.opt.no_sample;
-        p.slab_prior_q16 = c.opt.slab_q16 > 0 ? (uint32_t)c.opt.slab_q16 : c.ov_slab_q16;
-        p.slab_pct = (uint32_t)c.opt.slab_pct;
-        bool zero_slabn = false;
-        c.ov_slab_on = phase == 0 && half && mir16 && !c.opt.no_slab && nrows > 0 && (sampling || p.slab_prior_q16 != 0u);
-        p.slab = nullptr; p.slab_cap = 0;
-        if (c.ov_slab_on) {
-            c.ov_slab_cap = std::min<int64_t>(c.ov_tmp_cap + (int64_t)SLAB_PAD * nrows, 0xFFFF0000ll);
-            // (the fill word of a row is slab end << 32 | next free entry, bumped once per image — also by those that find the slab full: a row receives
-            //  at most M images, so the low half cannot carry into the end as long as the slab area + M stays below 2^32)
-            if (c.ov_slab_cap + M >= 0xFFFFFFFFll) c.ov_slab_cap = std::max<int64_t>(0xFFFFFFFFll - M - 1, 0);
-            if (c.ov_slab_cap <= (int64_t)SLAB_PAD * nrows + 1) c.ov_slab_on = false;      // (no room left for slabs under that bound: tickets + k_mirror)
-        }
-        if (c.ov_slab_on) {
-            c.ov_slab.reserve((size_t)c.ov_slab_cap * 16);
-            p.slab = c.ov_slab.as<uint4>(); p.slab_cap = (unsigned long long)c.ov_slab_cap;
-            c.ov_slabpos.reserve((size_t)(M + 4) * 8); c.ov_slabn.reserve((size_t)(M + 8) * 4);
-            p.slab_pos = c.ov_slabpos.as<unsigned long long>();
-            zero_slabn = true;      // (rows outside the window hold no slab entries; zeroed with the call's other counters, below)
-        }
-
-        if (timed) c.ov_marks.mark(0, s);
-        // the ticket counters come back clean from a call that ran to its end (k_finalize_wave); otherwise zero them here
-        {   // the call's counters, in ONE launch (five memsets were five ~8 us gaps in front of a 6 ms call)
-            ZeroList z{};
-            auto add = [&](void *ptr, size_t bytes) { z.p[z.n] = static_cast<uint32_t *>(ptr); z.words[z.n] = (bytes + 3) / 4; ++z.n; };
-            if (!c.ov_low_clean) add(c.ov_totcnt.p, (size_t)(M + 2) * 4);
-            add(c.ov_counters.p, sizeof(OvCounters));
-            add(c.ov_rowcnt.p, (size_t)(M + 2) * 4);
-            add(c.ov_tickrows.p, (size_t)(M / 32 + 2) * 4);
-            if (zero_slabn) add(c.ov_slabn.p, (size_t)(M + 8) * 4);
-            size_t most = 0;
-            for (int q = 0; q < z.n; ++q) most = std::max(most, z.words[q]);
-            hipLaunchKernelGGL(k_zero_regions, dim3((unsigned)std::min<size_t>((most + 255) / 256, (size_t)cus * 8)), dim3(256), 0, s, z);
-        }
-        c.ov_low_clean = false;
-        // A cold call on a matrix of some size computes a SAMPLE of its rows first (every sstep-th row, on the 4096-slot tier): what they find
-        // — distinct partners per row entry — picks the starting tier of all the others, instead of a guess that sends most rows of a
-        // 15 %-error read set to a tier too small (an abandoned attempt or a forwarding each: 0.9 ms of a 14.7 ms call on the 200 k-read set).
-        p.nsample = sampling ? 256u : 0u; p.sstep = sampling ? (uint32_t)(nrows / 256) : 1u;
-        c.ov_sample.reserve(256 * 4);
-        p.sample_list = c.ov_sample.as<uint32_t>();
-        if (sampling) hipLaunchKernelGGL(k_classify_direct, dim3(1), dim3(256), 0, s, p, 1);
-        if (timed) c.ov_marks.mark(1, s);
-        if (nrows > 0) {
-            // bytes behind the table: misc words + per wavefront one product ring (128 entries of 12 / 8 bytes) and one row-entry FIFO (128 x 12 bytes)
-            auto X = [&](int B, bool P) { return (size_t)256 + (size_t)(B / 64) * (P ? 3072 : (pay16 ? 2048 : 2560)); };
-            const bool all_tiers = !c.ov_tiers_known || phase == 2;
-            skipped_tiers = 0;
-            // the highest tier ANY row of this matrix can reach: a row's distinct partners <= min(its entries x the longest column, reads), the tier that holds
-            // twice that is guaranteed to fit it and k_classify_direct never starts a row above it.  A cold call on a small matrix launched five tiers
-            // nobody could queue on (~5 us each, dependent: hifi-half 0.59 -> 0.53 ms with the finalize's counterpart).  (Still under the `missed` check below.)
-            // (a repeated pass launches every tier: whatever the first one missed, it cannot miss it again for want of a launch)
-            int tmax = NUM_TIERS;
-            if (c.opt.tune[4] != 2 && passes == 1) {
-                const uint64_t ubm = std::min<uint64_t>((uint64_t)std::max<int64_t>(c.max_row_nnz, 1) * (uint64_t)p.max_col, (uint64_t)p.Mcols);
-                const int gmax = ubm <= 1 ? 1 : 64 - __builtin_clzll(2 * ubm - 1);
-                tmax = gmax <= LDS_TBITS0 ? 0 : gmax - LDS_TBITS0;
-                tmax = std::max(tmax, (int)p.min_tier);
-                if (p.suffix) tmax = std::max(tmax, (int)p.dense_up);
-            }
-#define ELBA_DTIER(t, stmt) do { if ((all_tiers || c.ov_tier_used[t]) && (t) <= tmax) { stmt; } else skipped_tiers |= 1u << (t); } while (0)
-#define ELBA_LAUNCH_D(B, G, P, grid, lds, tier, tb, smp)                                                                                  \
-    do {                                                                                                                                  \
-        if (spec && !(G) && !(P))                                                                                                         \
-            hipLaunchKernelGGL((k_spgemm_direct<B, false, false, 0, false, 0, true>), dim3(grid), dim3(B), (lds), s, ov_spec_params(p), (tier), (tb), (smp)); \
-        else if (dk == 0) hipLaunchKernelGGL((k_spgemm_direct<B, G, P, 0>), dim3(grid), dim3(B), (lds), s, p, (tier), (tb), (smp));            \
-        else if (dk == 1) hipLaunchKernelGGL((k_spgemm_direct<B, G, P, 1>), dim3(grid), dim3(B), (lds), s, p, (tier), (tb), (smp));       \
-        else if (dk == 4) hipLaunchKernelGGL((k_spgemm_direct<B, G, P, 4>), dim3(grid), dim3(B), (lds), s, p, (tier), (tb), (smp));       \
-        else hipLaunchKernelGGL((k_spgemm_direct<B, G, P, 2>), dim3(grid), dim3(B), (lds), s, p, (tier), (tb), (smp));                    \
-    } while (0)
-            // gather trips per iteration of the padded-column loop: 1 (DK = 0) where the rows mostly carry their products inline — columns of 2-3
-            // reads, 15 %-error reads: 6.49 -> 6.27 ms on config 3 —, 2 (DK = 1) otherwise (columns of ~7 reads at 5 % error lose 4 % with one trip);
-            // the option "dk" (0, 1, 2, 4) overrides
-            const int dk = c.opt.dk >= 0 ? c.opt.dk : ((c.csr_inline && c.N > 0 && c.Z < 3 * c.N) ? 0 : 1);
-            const bool spec = ov_spec_ok(c, p, pay, dk);      // (the reads path: its switches compiled into the kernel)
-            c.ov_spec = spec ? 1 : 0;
-// (dense path: 32-bit accumulators + seed look-ups for the few survivors; the first tier's grid is a tuning knob: the path waits for memory)
-#define ELBA_LAUNCH_S(B, TBC, grid, lds, tier, tb, smp) hipLaunchKernelGGL((k_spgemm_direct<B, false, false, 2, true, TBC>), dim3((tier) == 0 ? cus * c.opt.dense_wgs : (grid)), dim3(B), (size_t)18 * (1u << (tb)) + 256 + (size_t)((B) / 64) * 2368, s, p, (tier), (tb), (smp))
-            if (sampling) {
-                if (p.suffix) ELBA_LAUNCH_S(1024, 0, cus, (size_t)26 * 4096 + X(1024, true), 3, 12u, 1u);
-                else if (pay) ELBA_LAUNCH_D(1024, false, true, cus, (size_t)26 * 4096 + X(1024, true), 3, 12u, 1u);
-                else ELBA_LAUNCH_D(1024, false, false, cus, (size_t)18 * 4096 + X(1024, false), 3, 12u, 1u);
-                p.use_feedback = 0;      // the ratio is measured: nothing is forwarded on a prediction any more, nobody touches the hot sums
-            }
-            {
-                int nb = (int)((nrows + 255) / 256);
-                if (nb > cus * 4) nb = cus * 4;
-                hipLaunchKernelGGL(k_classify_direct, dim3(nb), dim3(256), 0, s, p, 0);
-            }
-            if (p.suffix) {      // (dense matrices: the LDS tiers with 64-bit accumulators run the dense path; p.suffix implies pay)
-                ELBA_DTIER(0, ELBA_LAUNCH_S(256, 9, cus * 9, (size_t)26 * 512 + X(128, true), 0, 9u, 0u));
-                if (p.dense_up >= 1u) ELBA_DTIER(1, ELBA_LAUNCH_S(512, 10, cus * 4, (size_t)26 * 1024 + X(256, true), 1, 10u, 0u));      // (eight wavefronts share a 1024-slot table: 32 per CU again, half the load)
-                else ELBA_DTIER(1, ELBA_LAUNCH_S(256, 0, cus * 4, (size_t)26 * 1024 + X(256, true), 1, 10u, 0u));
-                if (p.dense_up >= 2u) ELBA_DTIER(2, ELBA_LAUNCH_S(1024, 11, cus * 2, (size_t)26 * 2048 + X(512, true), 2, 11u, 0u));
-                else ELBA_DTIER(2, ELBA_LAUNCH_S(512, 0, cus * 2, (size_t)26 * 2048 + X(512, true), 2, 11u, 0u));
-                ELBA_DTIER(3, ELBA_LAUNCH_S(1024, 0, cus, (size_t)26 * 4096 + X(1024, true), 3, 12u, 0u));
-            } else if (pay) {
-                ELBA_DTIER(0, ELBA_LAUNCH_D(128, false, true, cus * 9, (size_t)26 * 512 + X(128, true), 0, 9u, 0u));
-                ELBA_DTIER(1, ELBA_LAUNCH_D(256, false, true, cus * 4, (size_t)26 * 1024 + X(256, true), 1, 10u, 0u));
-                ELBA_DTIER(2, ELBA_LAUNCH_D(512, false, true, cus * 2, (size_t)26 * 2048 + X(512, true), 2, 11u, 0u));
-                ELBA_DTIER(3, ELBA_LAUNCH_D(1024, false, true, cus, (size_t)26 * 4096 + X(1024, true), 3, 12u, 0u));
-            } else {
-                ELBA_DTIER(0, ELBA_LAUNCH_D(128, false, false, cus * 12, (size_t)18 * 512 + X(128, false), 0, 9u, 0u));
-                ELBA_DTIER(1, ELBA_LAUNCH_D(256, false, false, cus * 7, (size_t)18 * 1024 + X(256, false), 1, 10u, 0u));
-                ELBA_DTIER(2, ELBA_LAUNCH_D(512, false, false, cus * 3, (size_t)18 * 2048 + X(512, false), 2, 11u, 0u));
-                ELBA_DTIER(3, ELBA_LAUNCH_D(1024, false, false, cus, (size_t)18 * 4096 + X(1024, false), 3, 12u, 0u));
-            }
-            ELBA_DTIER(4, ELBA_LAUNCH_D(256, false, false, cus, (size_t)18 * 8192 + X(256, false), 4, 13u, 0u));      // (4 wavefronts: 8192 slots + their rings fill the 160 KB)
-            ELBA_DTIER(5, ELBA_LAUNCH_D(256, true, false, spill_blocks, (size_t)256 + 4 * 2560, NUM_LDS_TIERS, 0u, 0u));      // (the HBM tier never packs its FIFO entries: 2560 bytes of rings per wavefront)
-#undef ELBA_LAUNCH_S
-#undef ELBA_LAUNCH_D
-#undef ELBA_DTIER
-            ELBA_HIP(hipGetLastError());
-        }
-        if (timed) c.ov_marks.mark(2, s);
-        if (phase == 2) { c.ov_pend_passes = 1; c.ov_pend_timed = timed; c.ov_phase = 2; return; }      // (queued: no read-back, no wait)
-        if (phase == 0) ov_launch_finalize(c, p.half, !c.ov_tiers_known, skipped_sorts, nullptr, 0);
-        if (timed) c.ov_marks.mark(3, s);
-        ELBA_HIP(hipMemcpyAsync(&hc, c.ov_counters.p, sizeof(OvCounters), hipMemcpyDeviceToHost, s));
-        ELBA_HIP(hipStreamSynchronize(s));
-        if (timed) { ms_sym += c.ov_marks.ms(0, 1); ms_num += c.ov_marks.ms(1, 2); ms_fin = c.ov_marks.ms(2, 3); ms_tot += c.ov_marks.ms(0, 3); }
-        was_timed = timed;
-        c.ov_passes = passes; c.ov_forwarded += hc.nforward;
-        bool missed = false;
-        for (int t = 0; t < NUM_TIERS; ++t) missed |= ((skipped_tiers >> t) & 1u) && hc.tier_count[t] > 0;
-        missed |= ((skipped_sorts & 1u) && hc.fin_count[0] > 0) || ((skipped_sorts & 2u) && hc.fin_count[1] > 0);
-        if (hc.overflow || missed) {      // staging too small, or a row reached a tier / sort that was not launched: repeat with what is known now
-            if (c.opt.trace) fprintf(stderr, "[elba] overlap call repeated: overflow=%u missed=%d cursor=%llu tmp_cap=%lld\n", hc.overflow, (int)missed, hc.cursor, (long long)c.ov_tmp_cap);
-            ELBA_REQUIRE(passes < 4, ELBA_ERR_INTERNAL, "overlap output did not settle");
-            if (hc.overflow) c.ov_tmp_cap = (int64_t)hc.cursor + slack;      // every row drew its space even when it did not fit: the cursor is the need
-            c.ov_tiers_known = false;
-            continue;
-        }
-        c.ov_low_clean = phase == 0;
-        break;
-    }
-    if (phase == 1) { c.ov_pend_passes = passes; c.ov_pend_timed = was_timed; c.ov_pend_ms[0] = ms_tot; c.ov_pend_ms[1] = ms_sym; c.ov_pend_ms[2] = ms_num; c.ov_phase = 1; return; }
-
-    ov_finish_stats(c, hc, st, passes, was_timed, ms_tot, ms_sym, ms_num, ms_fin, 0, 0);
+    enter(c.v, EV_CREATE_SEED_MATRIX);
+    ELBA_REQUIRE(has(c.v, P_A), ELBA_ERR_STATE, "create_seed_matrix: no k-mer matrix (call elba_create_kmer_matrix or elba_set_kmer_matrix)");
+    OvRun r = ov_begin(c, 0);
+    do {
+        ov_numeric_pass(r);
+        ov_finalize(c, r.plan.fin, r.plan.half, nullptr, 0);
+        ov_read_back(r);
+    } while (!ov_settle(r));
+    ov_finish(c, *r.hc, r.passes, r.was_timed, r.ms_tot, r.ms_sym, r.ms_num, r.ms_fin, 0, 0);
     done(c.v, EV_CREATE_SEED_MATRIX);
 }
-
-
 
 // ---- sharded call with mirror exchange: begin -> (counts, fill: the driver's all-to-all) -> end -----------------------------------------
 static RemoteParams remote_params(Ctx &c)
 {
     RemoteParams r{};
+    const RowWindow w = c.window();
     r.row_cnt = c.ov_rowcnt.as<uint32_t>(); r.row_off = c.ov_rowoff.as<unsigned long long>(); r.tmp = c.ov_tmp.as<StageRec>(); r.rec16 = c.ov_rec16 ? 1u : 0u; r.rec = c.ov_tmp.as<uint4>();
-    r.row_lo = (uint32_t)c.row_lo; r.row_hi = (uint32_t)(c.row_hi < 0 ? c.M : c.row_hi); r.nranks = (uint32_t)c.ov_remote_bounds.size() - 1u;
+    r.row_lo = (uint32_t)w.lo; r.row_hi = (uint32_t)w.hi; r.nranks = (uint32_t)c.ov_remote_bounds.size() - 1u;
     for (size_t k = 0; k < c.ov_remote_bounds.size(); ++k) r.bounds[k] = c.ov_remote_bounds[k];
     return r;
 }
+// workgroups of the k_remote_mirror kernels: none where there is nobody to send to
+static unsigned remote_blocks(Ctx &c)
+{
+    const int64_t nrows = c.window().rows();
+    return nrows > 0 && c.ov_remote_bounds.size() > 2 ? (unsigned)((nrows + REMOTE_ROWS_PER_BLOCK - 1) / REMOTE_ROWS_PER_BLOCK) : 0u;
+}
 
+// what seed_matrix_begin and _send ask of their arguments alike (rest_ok, rest: the entry point's own): a matrix, 1..64 ranks whose row ranges
+// cover the matrix, this context's window one of them.  The ranges are kept for the kernels that sort mirror images by destination
+static void ov_accept_ranks(Ctx &c, const char *who, int nranks, const uint64_t *bounds_host, bool rest_ok, const char *rest)
+{
+    ELBA_REQUIRE(has(c.v, P_A), ELBA_ERR_STATE, std::string(who) + ": no k-mer matrix");
+    ELBA_REQUIRE(nranks >= 1 && nranks <= REMOTE_MAX_RANKS && bounds_host && rest_ok, ELBA_ERR_INVALID_ARG, std::string(who) + ": 1..64 ranks, read bounds" + rest);
+    const RowWindow w = c.window();
+    bool found = false;
+    for (int r = 0; r < nranks; ++r) found |= (int64_t)bounds_host[r] == w.lo && (int64_t)bounds_host[r + 1] == w.hi;
+    ELBA_REQUIRE(found && (int64_t)bounds_host[nranks] == c.M, ELBA_ERR_INVALID_ARG, std::string(who) + ": this context's row window is not one of the ranks' row ranges");
+    c.ov_remote_bounds.assign(bounds_host, bounds_host + nranks + 1);
+}
+
+// the output and the mirror area hold `entries`: what was staged, mirrored locally and received (seed_matrix_end / _recv)
+static void ov_reserve_output(Ctx &c, int64_t entries)
+{
+    c.b_cap_entries = entries;
+    c.b_col.reserve((size_t)(entries + 1) * 4);
+    c.b_val.reserve((size_t)(entries + 1) * sizeof(elba_seed_t));
+    c.ov_mir.reserve((size_t)(entries + 1) * (ov_mir16(c) ? 16 : sizeof(StageRec)));
+}
+// the second half of a sharded call (phase: the first half's): the finalize over staged, mirrored and received entries — every sort, rows grow by
+// what other ranks sent —, mark 3, the counters on their way to the host.  The caller synchronises
+static OvCounters &ov_finalize_sharded(Ctx &c, const StageRec *remote, int64_t nremote, int64_t slot)
+{
+    OvInput in;      // (what plan_ov_finalize reads: the sizes, the window, "tune4")
+    const RowWindow w = c.window();
+    in.M = c.M; in.row_lo = w.lo; in.row_hi = w.hi; in.max_row_nnz = c.max_row_nnz; in.max_col_nnz = c.max_col_nnz; in.num_cus = c.num_cus; in.opt.tune4 = c.opt.tune[4];
+    ov_finalize(c, plan_ov_finalize(in, false, true, nremote > 0), 2u, remote, nremote, slot);
+    c.ov_marks.mark(3, c.stream);
+    OvCounters &hc = *static_cast<OvCounters *>(c.ov_host.p);
+    ELBA_HIP(hipMemcpyAsync(&hc, c.ov_counters.p, sizeof(OvCounters), hipMemcpyDeviceToHost, c.stream));
+    return hc;
+}
+// ... and its close: the ticket counters came back clean, the statistics and hints of the whole call, the event
+static void ov_finish_sharded(Ctx &c, OvCounters &hc, Event ev, int passes, bool timed, float ms_tot, float ms_sym, float ms_num, float ms_fin, int64_t extra_nnz, int64_t extra_upper)
+{
+    c.ov_low_clean = true;
+    ov_finish(c, hc, passes, timed, ms_tot, ms_sym, ms_num, ms_fin, extra_nnz, extra_upper);
+    done(c.v, ev);
+}
+
+// classify + numeric with GLOBAL pair ownership, repeated until the staging area held everything; stops before the finalize pass
 void stage_seed_matrix_begin(Ctx &c, int nranks, const uint64_t *bounds_host, uint64_t *send_counts_host)
 {
     enter(c.v, EV_SEED_MATRIX_BEGIN);
-    ELBA_REQUIRE(has(c.v, P_A), ELBA_ERR_STATE, "seed_matrix_begin: no k-mer matrix");
-    ELBA_REQUIRE(nranks >= 1 && nranks <= REMOTE_MAX_RANKS && bounds_host && send_counts_host, ELBA_ERR_INVALID_ARG, "seed_matrix_begin: 1..64 ranks, read bounds and a count array");
-    const int64_t row_lo = c.row_lo, row_hi = c.row_hi < 0 ? c.M : c.row_hi;
-    bool found = false;
-    for (int r = 0; r < nranks; ++r) found |= (int64_t)bounds_host[r] == row_lo && (int64_t)bounds_host[r + 1] == row_hi;
-    ELBA_REQUIRE(found && (int64_t)bounds_host[nranks] == c.M, ELBA_ERR_INVALID_ARG, "seed_matrix_begin: this context's row window is not one of the ranks' row ranges");
-    c.ov_remote_bounds.assign(bounds_host, bounds_host + nranks + 1);
-    create_seed_matrix_direct(c, 1);
+    ov_accept_ranks(c, "seed_matrix_begin", nranks, bounds_host, send_counts_host != nullptr, " and a count array");
+    OvRun r = ov_begin(c, 1);
+    do {
+        ov_numeric_pass(r);
+        ov_read_back(r);
+    } while (!ov_settle(r));
+    c.ov_pend_passes = r.passes; c.ov_pend_timed = r.was_timed; c.ov_pend_ms[0] = r.ms_tot; c.ov_pend_ms[1] = r.ms_sym; c.ov_pend_ms[2] = r.ms_num; c.ov_phase = 1;
     hipStream_t s = c.stream;
     c.ws_scan.reserve(REMOTE_MAX_RANKS * 8);
     ELBA_HIP(hipMemsetAsync(c.ws_scan.p, 0, REMOTE_MAX_RANKS * 8, s));
-    const int64_t nrows = row_hi - row_lo;
-    if (nrows > 0 && nranks > 1)
-        hipLaunchKernelGGL((k_remote_mirror<false>), dim3((unsigned)((nrows + REMOTE_ROWS_PER_BLOCK - 1) / REMOTE_ROWS_PER_BLOCK)), dim3(256), 0, s, remote_params(c), c.ws_scan.as<unsigned long long>(), (StageRec *)nullptr);
+    if (remote_blocks(c)) hipLaunchKernelGGL((k_remote_mirror<false>), dim3(remote_blocks(c)), dim3(256), 0, s, remote_params(c), c.ws_scan.as<unsigned long long>(), (StageRec *)nullptr);
     ELBA_HIP(hipMemcpyAsync(send_counts_host, c.ws_scan.p, (size_t)nranks * 8, hipMemcpyDeviceToHost, s));
     ELBA_HIP(hipStreamSynchronize(s));
 }
@@ -1276,9 +1281,7 @@ void stage_seed_matrix_fill(Ctx &c, void *d_send, const uint64_t *offsets_host)
     const int nranks = (int)c.ov_remote_bounds.size() - 1;
     c.ws_scan.reserve(REMOTE_MAX_RANKS * 8);
     ELBA_HIP(hipMemcpyAsync(c.ws_scan.p, offsets_host, (size_t)nranks * 8, hipMemcpyHostToDevice, s));
-    const int64_t row_lo = c.row_lo, row_hi = c.row_hi < 0 ? c.M : c.row_hi, nrows = row_hi - row_lo;
-    if (nrows > 0 && nranks > 1)
-        hipLaunchKernelGGL((k_remote_mirror<true>), dim3((unsigned)((nrows + REMOTE_ROWS_PER_BLOCK - 1) / REMOTE_ROWS_PER_BLOCK)), dim3(256), 0, s, remote_params(c), c.ws_scan.as<unsigned long long>(), static_cast<StageRec *>(d_send));
+    if (remote_blocks(c)) hipLaunchKernelGGL((k_remote_mirror<true>), dim3(remote_blocks(c)), dim3(256), 0, s, remote_params(c), c.ws_scan.as<unsigned long long>(), static_cast<StageRec *>(d_send));
     ELBA_HIP(hipStreamSynchronize(s));
 }
 
@@ -1289,16 +1292,10 @@ void stage_seed_matrix_end(Ctx &c, const void *d_recv, int64_t nrecv)
     ELBA_REQUIRE(nrecv >= 0 && (nrecv == 0 || d_recv), ELBA_ERR_INVALID_ARG, "seed_matrix_end: null records");
     accepted(c.v, EV_SEED_MATRIX_END);
     hipStream_t s = c.stream;
-    const int64_t row_lo = c.row_lo, row_hi = c.row_hi < 0 ? c.M : c.row_hi;
-    OvCounters &hc = *static_cast<OvCounters *>(c.ov_host.p);          // the numeric phase's counters (read back by begin)
-    int64_t staged = 0;
-    for (int sh = 0; sh < NUM_SHARDS; ++sh) staged += (int64_t)hc.shard[sh].nnz;
-    // the output holds what was staged, mirrored locally and received
-    if (c.b_cap_entries < staged + nrecv + 1) c.b_cap_entries = staged + nrecv + 1;
-    c.b_col.reserve((size_t)(c.b_cap_entries + 1) * 4);
-    c.b_val.reserve((size_t)(c.b_cap_entries + 1) * sizeof(elba_seed_t));
-    const bool mir16 = c.pos16 && !c.opt.mir32;
-    c.ov_mir.reserve((size_t)(c.b_cap_entries + 1) * (mir16 ? 16 : sizeof(StageRec)));
+    const RowWindow w = c.window();
+    int64_t staged = 0;          // from the numeric phase's counters (read back by begin)
+    for (int sh = 0; sh < NUM_SHARDS; ++sh) staged += (int64_t)static_cast<OvCounters *>(c.ov_host.p)->shard[sh].nnz;
+    ov_reserve_output(c, std::max<int64_t>(c.b_cap_entries, staged + nrecv + 1));
     c.ov_marks.mark(2, s);
     c.ov_remote.reserve((size_t)(nrecv + 1) * sizeof(StageRec));
     c.ws_scan.reserve(64);
@@ -1306,23 +1303,16 @@ void stage_seed_matrix_end(Ctx &c, const void *d_recv, int64_t nrecv)
     if (nrecv > 0) {
         ELBA_HIP(hipMemcpyAsync(c.ov_remote.p, d_recv, (size_t)nrecv * sizeof(StageRec), hipMemcpyDeviceToDevice, s));
         hipLaunchKernelGGL(k_ingest_remote, dim3((unsigned)((nrecv + 255) / 256)), dim3(256), 0, s, c.ov_remote.as<StageRec>(), (unsigned long long)nrecv, c.ov_totcnt.as<uint32_t>(),
-                           (uint32_t)row_lo, (uint32_t)row_hi, c.ws_scan.as<unsigned long long>(), c.ws_scan.as<unsigned long long>() + 1);
+                           (uint32_t)w.lo, (uint32_t)w.hi, c.ws_scan.as<unsigned long long>(), c.ws_scan.as<unsigned long long>() + 1);
     }
     unsigned long long chk[2] = {0, 0};
     ELBA_HIP(hipMemcpyAsync(chk, c.ws_scan.p, 16, hipMemcpyDeviceToHost, s));
-    uint32_t skipped_sorts = 0;
-    ov_launch_finalize(c, 2u, true, skipped_sorts, c.ov_remote.as<StageRec>(), nrecv);
-    c.ov_marks.mark(3, s);
-    ELBA_HIP(hipMemcpyAsync(&hc, c.ov_counters.p, sizeof(OvCounters), hipMemcpyDeviceToHost, s));
+    OvCounters &hc = ov_finalize_sharded(c, c.ov_remote.as<StageRec>(), nrecv, 0);
     ELBA_HIP(hipStreamSynchronize(s));
     ELBA_REQUIRE(chk[0] == 0, ELBA_ERR_INVALID_ARG, "seed_matrix_end: received records for rows outside this context's window");
-    c.ov_low_clean = true;
     c.ov_phase = 0;
-    elba_overlap_stats st{};
-    st.nrows = row_hi - row_lo;
     const float ms_fin = c.ov_marks.ms(2, 3);
-    ov_finish_stats(c, hc, st, c.ov_pend_passes, c.ov_pend_timed, c.ov_pend_ms[0] + ms_fin, c.ov_pend_ms[1], c.ov_pend_ms[2], ms_fin, nrecv, (int64_t)chk[1]);
-    done(c.v, EV_SEED_MATRIX_END);
+    ov_finish_sharded(c, hc, EV_SEED_MATRIX_END, c.ov_pend_passes, c.ov_pend_timed, c.ov_pend_ms[0] + ms_fin, c.ov_pend_ms[1], c.ov_pend_ms[2], ms_fin, nrecv, (int64_t)chk[1]);
 }
 
 // ---- the same step with ONE host synchronisation: fixed-size slots, nothing about the exchange is known on the host ------------------------
@@ -1410,25 +1400,21 @@ __global__ void k_ingest_remote_slots(StageRec *rem, unsigned long long slot, ui
     if ((threadIdx.x & 63) == 0) { if (up) atomicAdd(&chk[1], up); if (got) atomicAdd(&chk[4], got); }
 }
 
+// classify + numeric as in seed_matrix_begin, only QUEUED: every tier is launched, nothing is read back and the host does not wait (what begin
+// checks after its synchronisation, seed_matrix_recv checks at the end of the step)
 void stage_seed_matrix_send(Ctx &c, int nranks, const uint64_t *bounds_host, void *d_send, int64_t slot)
 {
     enter(c.v, EV_SEED_MATRIX_SEND);
-    ELBA_REQUIRE(has(c.v, P_A), ELBA_ERR_STATE, "seed_matrix_send: no k-mer matrix");
-    ELBA_REQUIRE(nranks >= 1 && nranks <= REMOTE_MAX_RANKS && bounds_host && d_send && slot >= 2, ELBA_ERR_INVALID_ARG, "seed_matrix_send: 1..64 ranks, read bounds, a send buffer of nranks slots of >= 2 records");
-    const int64_t row_lo = c.row_lo, row_hi = c.row_hi < 0 ? c.M : c.row_hi;
-    bool found = false;
-    for (int r = 0; r < nranks; ++r) found |= (int64_t)bounds_host[r] == row_lo && (int64_t)bounds_host[r + 1] == row_hi;
-    ELBA_REQUIRE(found && (int64_t)bounds_host[nranks] == c.M, ELBA_ERR_INVALID_ARG, "seed_matrix_send: this context's row window is not one of the ranks' row ranges");
-    c.ov_remote_bounds.assign(bounds_host, bounds_host + nranks + 1);
-    create_seed_matrix_direct(c, 2);
+    ov_accept_ranks(c, "seed_matrix_send", nranks, bounds_host, d_send && slot >= 2, ", a send buffer of nranks slots of >= 2 records");
+    OvRun r = ov_begin(c, 2);
+    ov_numeric_pass(r);
+    c.ov_pend_passes = 1; c.ov_pend_timed = r.timed; c.ov_phase = 2;
     c.ov_send_slot = slot;
     hipStream_t s = c.stream;
     c.ov_cursors.reserve(REMOTE_MAX_RANKS * 8 + 64);
     ELBA_HIP(hipMemsetAsync(c.ov_cursors.p, 0, REMOTE_MAX_RANKS * 8 + 64, s));
-    const int64_t nrows = row_hi - row_lo;
-    if (nrows > 0 && nranks > 1)
-        hipLaunchKernelGGL(k_remote_mirror_slots, dim3((unsigned)((nrows + REMOTE_ROWS_PER_BLOCK - 1) / REMOTE_ROWS_PER_BLOCK)), dim3(256), 0, s, remote_params(c), c.ov_cursors.as<unsigned long long>(),
-                           static_cast<StageRec *>(d_send), (unsigned long long)slot);
+    if (remote_blocks(c))
+        hipLaunchKernelGGL(k_remote_mirror_slots, dim3(remote_blocks(c)), dim3(256), 0, s, remote_params(c), c.ov_cursors.as<unsigned long long>(), static_cast<StageRec *>(d_send), (unsigned long long)slot);
     hipLaunchKernelGGL(k_slot_headers, dim3(1), dim3(64), 0, s, (const unsigned long long *)c.ov_cursors.as<unsigned long long>(), (const OvCounters *)c.ov_counters.as<OvCounters>(),
                        static_cast<StageRec *>(d_send), (unsigned long long)slot, (uint32_t)nranks);
     ELBA_HIP(hipGetLastError());
@@ -1443,33 +1429,24 @@ bool stage_seed_matrix_recv(Ctx &c, void *d_recv, int64_t slot, int64_t *slot_ne
     ELBA_REQUIRE(slot == c.ov_send_slot, ELBA_ERR_INVALID_ARG, "seed_matrix_recv: slot_records differs from the value given to seed_matrix_send");
     accepted(c.v, EV_SEED_MATRIX_RECV);
     hipStream_t s = c.stream;
-    const int64_t row_lo = c.row_lo, row_hi = c.row_hi < 0 ? c.M : c.row_hi;
+    const RowWindow w = c.window();
     const int nranks = (int)c.ov_remote_bounds.size() - 1;
     const int64_t nslotrec = (int64_t)nranks * slot;
-    // the output holds what was staged, mirrored locally (both bounded by the staging capacity) and received (bounded by the slots)
-    c.b_cap_entries = 2 * c.ov_tmp_cap + nslotrec + 1;
-    c.b_col.reserve((size_t)(c.b_cap_entries + 1) * 4);
-    c.b_val.reserve((size_t)(c.b_cap_entries + 1) * sizeof(elba_seed_t));
-    const bool mir16 = c.pos16 && !c.opt.mir32;
-    c.ov_mir.reserve((size_t)(c.b_cap_entries + 1) * (mir16 ? 16 : sizeof(StageRec)));
+    // staged and mirrored locally are both bounded by the staging capacity, received by the slots
+    ov_reserve_output(c, 2 * c.ov_tmp_cap + nslotrec + 1);
     c.ov_marks.mark(4, s);
     unsigned long long *chk = c.ov_cursors.as<unsigned long long>() + REMOTE_MAX_RANKS;      // (zeroed by send)
     hipLaunchKernelGGL(k_ingest_remote_slots, dim3((unsigned)((slot + 255) / 256), (unsigned)nranks), dim3(256), 0, s, static_cast<StageRec *>(d_recv), (unsigned long long)slot,
-                       c.ov_totcnt.as<uint32_t>(), (uint32_t)row_lo, (uint32_t)row_hi, chk);
-    uint32_t skipped_sorts = 0;
-    ov_launch_finalize(c, 2u, true, skipped_sorts, static_cast<const StageRec *>(d_recv), nslotrec, slot);
-    c.ov_marks.mark(3, s);
-    OvCounters &hc = *static_cast<OvCounters *>(c.ov_host.p);
+                       c.ov_totcnt.as<uint32_t>(), (uint32_t)w.lo, (uint32_t)w.hi, chk);
+    OvCounters &hc = ov_finalize_sharded(c, static_cast<const StageRec *>(d_recv), nslotrec, slot);
     unsigned long long hchk[5] = {0, 0, 0, 0, 0};
-    ELBA_HIP(hipMemcpyAsync(&hc, c.ov_counters.p, sizeof(OvCounters), hipMemcpyDeviceToHost, s));
     ELBA_HIP(hipMemcpyAsync(hchk, chk, sizeof(hchk), hipMemcpyDeviceToHost, s));
     ELBA_HIP(hipStreamSynchronize(s));      // the step's one synchronisation
     c.ov_phase = 0;
     ELBA_REQUIRE(hchk[0] == 0, ELBA_ERR_INVALID_ARG, "seed_matrix_recv: received records for rows outside this context's window, or a slot header that claims more records than a slot holds");
     if (hc.overflow || hchk[2]) {
         // some rank's staging area or slot was too small: every rank saw the flag (it travels in every header) and repeats the step
-        const int64_t slack = (int64_t)c.num_cus * 32 * STAGE_CHUNK + 64;
-        if (hc.overflow) c.ov_tmp_cap = (int64_t)hc.cursor + slack;
+        if (hc.overflow) c.ov_tmp_cap = (int64_t)hc.cursor + ov_stage_slack(c.num_cus);
         if (slot_needed) *slot_needed = std::max<int64_t>((int64_t)hchk[3] + (int64_t)hchk[3] / 8 + 16, slot);
         c.ov_low_clean = false;
         return false;
@@ -1477,20 +1454,9 @@ bool stage_seed_matrix_recv(Ctx &c, void *d_recv, int64_t slot, int64_t *slot_ne
     // (what would have sufficed — the same number on every rank: the largest count any sender put into any slot, + 1/8 — lets the caller SHRINK a
     //  first guess that was several times too generous: the all-to-all moves whole slots)
     if (slot_needed) *slot_needed = std::min<int64_t>(slot, (int64_t)hchk[3] + (int64_t)hchk[3] / 8 + 16);
-    c.ov_low_clean = true;
-    elba_overlap_stats st{};
-    st.nrows = row_hi - row_lo;
     const float ms_sym = c.ov_pend_timed ? c.ov_marks.ms(0, 1) : 0.f, ms_num = c.ov_pend_timed ? c.ov_marks.ms(1, 2) : 0.f, ms_fin = c.ov_marks.ms(4, 3);
-    ov_finish_stats(c, hc, st, 1, c.ov_pend_timed, c.ov_pend_timed ? c.ov_marks.ms(0, 3) : ms_fin, ms_sym, ms_num, ms_fin, (int64_t)hchk[4], (int64_t)hchk[1]);
-    done(c.v, EV_SEED_MATRIX_RECV);
+    ov_finish_sharded(c, hc, EV_SEED_MATRIX_RECV, 1, c.ov_pend_timed, c.ov_pend_timed ? c.ov_marks.ms(0, 3) : ms_fin, ms_sym, ms_num, ms_fin, (int64_t)hchk[4], (int64_t)hchk[1]);
     return true;
-}
-
-void stage_create_seed_matrix(Ctx &c)
-{
-    enter(c.v, EV_CREATE_SEED_MATRIX);
-    ELBA_REQUIRE(has(c.v, P_A), ELBA_ERR_STATE, "create_seed_matrix: no k-mer matrix (call elba_create_kmer_matrix or elba_set_kmer_matrix)");
-    create_seed_matrix_direct(c, 0);
 }
 
 }  // namespace elba

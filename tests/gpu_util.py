@@ -98,3 +98,20 @@ def assert_whole_B_equals_oracle(e, k, lo, up, st=None, threads=None):
     if st is not None:
         assert_stats_equal(st, o)
     return int(v["Y"])
+
+
+def escalation_triples():
+    """Rows whose distinct-partner count defeats every optimistic LDS table: `dense` columns each hold ALL reads (every row then has M partners,
+    M / 2 > 3/4 of the largest LDS table -> HBM spill), a band of medium columns makes rows that overflow the small tiers only (escalation),
+    singletons make rows that fit at once.  Returns (M, ncol, rows, cols, vals)."""
+    M, rng = 14000, np.random.default_rng(12)
+    rows, cols, vals = [], [], []
+    ncol = 0
+    for c in range(2):                                   # two dense columns over rows 0..6999 -> 7000 partners, numshared 2
+        r = np.arange(7000); rows.append(r); cols.append(np.full(len(r), ncol)); vals.append(rng.integers(0, 5000, len(r))); ncol += 1
+    for c in range(2):                                   # rows 0..13999 in two more dense columns -> 14000 partners: a row accumulates half of
+        r = np.arange(M); rows.append(r); cols.append(np.full(len(r), ncol)); vals.append(rng.integers(0, 5000, len(r))); ncol += 1      # them (the other half is mirrored), still more than 3/4 of the largest LDS table
+    for b in range(0, 3000, 500):                        # medium: groups of 500 rows sharing 2 columns
+        for c in range(2):
+            r = 7000 + np.arange(b, b + 500) % 3500; rows.append(r); cols.append(np.full(len(r), ncol)); vals.append(rng.integers(0, 5000, len(r))); ncol += 1
+    return M, ncol, np.concatenate(rows), np.concatenate(cols), np.concatenate(vals).astype(np.uint32)
