@@ -145,6 +145,15 @@ class BubbleStats(C.Structure):
                 ("ms_total", C.c_float), ("ms_compact", C.c_float)]
 
 
+class WeakCfg(C.Structure):
+    _fields_ = [("min_ratio_q16", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class WeakStats(C.Structure):
+    _fields_ = [("nreads", C.c_int64), ("nnz_before", C.c_int64), ("nnz_after", C.c_int64), ("branch_sides", C.c_int64), ("weak_entries", C.c_int64),
+                ("entries_removed", C.c_int64), ("sides_emptied", C.c_int64), ("ms_total", C.c_float), ("ms_compact", C.c_float)]
+
+
 class Overlaps(C.Structure):
     _fields_ = [("n", C.c_int64), ("rows", C.c_void_p), ("cols", C.c_void_p), ("vals", C.c_void_p)]
 
@@ -199,7 +208,7 @@ EXPORTED_SYMBOLS = [
     "elba_generate_contigs", "elba_export_contigs", "elba_free_contigs", "elba_export_read_contigs", "elba_generate_contigs_ex", "elba_export_contig_kinds",
     "elba_read_pileup", "elba_export_pileup", "elba_free_pileup", "elba_prune_reads",
     "elba_trim_reads", "elba_export_trim_map", "elba_free_trim_map", "elba_get_trimmed_reads_device", "elba_adopt_trimmed_reads",
-    "elba_clip_tips", "elba_pop_bubbles",
+    "elba_clip_tips", "elba_pop_bubbles", "elba_cut_weak_overlaps",
 ]
 
 _lib = None
@@ -251,6 +260,7 @@ def load_library():
     L.elba_export_read_flags.restype = i32; L.elba_export_read_flags.argtypes = [vp, vp, i64]
     L.elba_clip_tips.restype = i32; L.elba_clip_tips.argtypes = [vp, C.POINTER(TipCfg), C.POINTER(TipStats)]
     L.elba_pop_bubbles.restype = i32; L.elba_pop_bubbles.argtypes = [vp, C.POINTER(BubbleCfg), C.POINTER(BubbleStats)]
+    L.elba_cut_weak_overlaps.restype = i32; L.elba_cut_weak_overlaps.argtypes = [vp, C.POINTER(WeakCfg), C.POINTER(WeakStats)]
     L.elba_generate_contigs.restype = i32; L.elba_generate_contigs.argtypes = [vp, C.POINTER(ContigStats)]
     L.elba_generate_contigs_ex.restype = i32; L.elba_generate_contigs_ex.argtypes = [vp, C.POINTER(ContigCfg), C.POINTER(ContigStats)]
     L.elba_export_contig_kinds.restype = i32; L.elba_export_contig_kinds.argtypes = [vp, vp, i64]
@@ -511,15 +521,33 @@ class Engine:
         d.pop("reserved", None)
         return d
 
-    def simplify_graph(self, max_tip_reads, max_arm_reads, passes=16):
+    # --- cutting weak overlaps (between transitive_reduction and generate_contigs, before or after the two above; not in the reference) ---
+    def cut_weak_overlaps(self, min_ratio=0.7):
+        """Where an end of a read has two or more overlaps, removes those whose score is below min_ratio times the best score of that end
+        — and every overlap that is so at its other read — from the string graph, in one pass.  Entries leave, no read does; the read
+        flags stay.  min_ratio becomes min_ratio_q16 = int(round(min_ratio * 65536)), which must lie in 1 .. 65536.  Returns the stats."""
+        q16 = int(round(min_ratio * 65536))
+        if not 1 <= q16 <= 65536:
+            raise ValueError("cut_weak_overlaps: min_ratio * 65536 rounds to %d, outside 1 .. 65536" % q16)
+        cfg = WeakCfg(q16, (C.c_int32 * 3)(0, 0, 0))
+        st = WeakStats()
+        self._check(self.L.elba_cut_weak_overlaps(self.h, C.byref(cfg), C.byref(st)))
+        return _stats(st)
+
+    def simplify_graph(self, max_tip_reads, max_arm_reads, passes=16, min_overlap_ratio=None):
         """clip_tips(max_tip_reads, 64) then pop_bubbles(max_arm_reads, 64), again and again until a pass of both removes nothing or `passes`
         passes have run.  pop_bubbles alone does not reach that fixed point: a tip on an arm gives the arm a read of degree 3, so there is
         no arm until the tip is clipped.  (A pop makes no new tip on a symmetric graph — it lowers anchors to degree 2, which only lengthens
-        dead-end chains — so the second pass is the one that finds nothing.)  Returns [(tip stats, bubble stats)], one pair per pass."""
+        dead-end chains — so the second pass is the one that finds nothing.)  Returns [(tip stats, bubble stats)], one pair per pass.
+        With min_overlap_ratio every pass ends with cut_weak_overlaps(min_overlap_ratio), which can make new dead ends and new arms: a pass
+        is (tip stats, bubble stats, weak stats), and the loop ends after a pass in which none of the three removed anything."""
         out = []
         for _ in range(int(passes)):
-            out.append((self.clip_tips(max_tip_reads, 64), self.pop_bubbles(max_arm_reads, 64)))
-            if out[-1][0]["reads_removed"] == 0 and out[-1][1]["reads_removed"] == 0:
+            if min_overlap_ratio is None:
+                out.append((self.clip_tips(max_tip_reads, 64), self.pop_bubbles(max_arm_reads, 64)))
+            else:
+                out.append((self.clip_tips(max_tip_reads, 64), self.pop_bubbles(max_arm_reads, 64), self.cut_weak_overlaps(min_overlap_ratio)))
+            if out[-1][0]["reads_removed"] == 0 and out[-1][1]["reads_removed"] == 0 and (min_overlap_ratio is None or out[-1][2]["entries_removed"] == 0):
                 break
         return out
 

@@ -22,6 +22,7 @@
 //                                                                             built on the GPU from the S left there
 //   (none: the reference drops every branch read)                             elba::ClipTips(S, reads, max_tip_reads, rounds): dead-end tips leave S
 //   (none)                                                                    elba::PopBubbles(S, reads, max_arm_reads, rounds): all but one arm of a bubble leave S
+//   (none)                                                                    elba::CutWeakOverlaps(S, reads, min_ratio_q16): weak overlaps at branching read ends leave S
 //
 // Errors: the reference asserts/aborts; here every failing C-ABI status throws elba::Error (status + text).
 // There is no CPU path: constructing an engine without a GPU throws ELBA_ERR_NO_DEVICE.
@@ -417,7 +418,7 @@ inline std::unique_ptr<StringGraph> TransitiveReduction(const DnaBuffer &myreads
     return S;
 }
 
-// The host copy of S after a call that changed it on the device (ClipTips, PopBubbles): the entries of elba_export_string_graph; removed_reads,
+// The host copy of S after a call that changed it on the device (ClipTips, PopBubbles, CutWeakOverlaps): the entries of elba_export_string_graph; removed_reads,
 // if given, receives the reads that carry `flag` in elba_export_read_flags, ascending.
 inline void reload_string_graph(StringGraph &S, const DnaBuffer &myreads, uint8_t flag, std::vector<int64_t> *removed_reads)
 {
@@ -470,6 +471,21 @@ inline elba_bubble_stats PopBubbles(StringGraph &S, const DnaBuffer &myreads, in
     elba_bubble_stats st{};
     S.engine->check(elba_pop_bubbles(S.engine->ctx, &cfg, &st));
     reload_string_graph(S, myreads, 8, popped_reads);
+    return st;
+}
+
+// CutWeakOverlaps(S, myreads, min_ratio_q16) — not in the reference: elba_cut_weak_overlaps on the S that TransitiveReduction (or ClipTips, or
+// PopBubbles) left on the device, before GenerateContigs.  Where an end of a read (direction & 1 of the column's entries) has two or more
+// overlaps, those whose score * 65536 is below min_ratio_q16 times the best score of that end leave S, and so does every entry whose mirror
+// image is such a one; in one pass.  Entries leave, no read does, and the read flags stay; the host copy of S is replaced by the cut graph.
+inline elba_weak_stats CutWeakOverlaps(StringGraph &S, const DnaBuffer &myreads, int min_ratio_q16)
+{
+    if (!S.engine) throw Error(ELBA_ERR_STATE, "CutWeakOverlaps: the string graph is not on a device");
+    elba_weak_cfg cfg{};
+    cfg.min_ratio_q16 = min_ratio_q16;
+    elba_weak_stats st{};
+    S.engine->check(elba_cut_weak_overlaps(S.engine->ctx, &cfg, &st));
+    reload_string_graph(S, myreads, 0, nullptr);
     return st;
 }
 

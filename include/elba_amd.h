@@ -438,6 +438,47 @@ typedef struct { int64_t nreads, nnz_before, nnz_after;
                  float   ms_total, ms_compact; } elba_bubble_stats;
 int  elba_pop_bubbles(elba_ctx *ctx, const elba_bubble_cfg *cfg, elba_bubble_stats *stats);
 
+/* Cutting weak overlaps (not in the reference either; the third step of miniasm's cleaning, and at ratio 1 the "best overlap graph").  One
+ * kind of branch is left by the two calls above: an end of a read has its true overlap and one or more much weaker ones, from a repeat copy
+ * or a chance alignment.  Both lead into long paths (no tip) that do not rejoin within a few reads (no bubble), the read has degree 3 and
+ * elba_generate_contigs* cuts the path there.  elba_cut_weak_overlaps works on the S of elba_transitive_reduction, in place, between that call
+ * and elba_generate_contigs*, before or after the other two.  It removes ENTRIES, no reads.  The rule is stated on the columns of S as they
+ * are.  For an entry z of column c with row r and value o (o = S(r, c), query r, target c; a lower-triangle entry carries Overlap::Transpose
+ * of its mirror image):
+ *   side(z)    o.direction & 1: the end of read c the overlap lies on (h of Overlap::arrows).  Two entries of one column can be walked
+ *              through only if their sides differ (MinPlusSR::multiply refuses t2 == h1).  Every entry of S has a direction of 0 .. 3.
+ *   weight(z)  o.score: the one field Overlap::Transpose copies unchanged, so both images of a pair carry the same weight.  It grows with
+ *              overlap length and with identity; it is not the length in bases.
+ * ONE pass, on tables frozen at its start:
+ *   1. for every read c and side e: cnt(c, e) = entries of column c with that side, best(c, e) = their largest score.
+ *   2. z is weak at its column when cnt(c, side(z)) >= 2 and best(c, side(z)) > 0 and
+ *          (int64) score * 65536 < (int64) min_ratio_q16 * best(c, side(z))
+ *      in integer arithmetic, exactly as written.  An entry that ties the best of its side is never weak.
+ *   3. z is removed when it is weak at its column, or when its mirror image — the entry of column r whose row is c — is weak at column r.
+ *      Where S holds only one image of a pair (the direction -1 case of the reduction), only the first condition applies.
+ *   4. survivors keep their values and their order (columns ascending, rows ascending within a column).  No read is removed and the flags
+ *      of elba_export_read_flags are untouched.
+ * There is no sparing: a read end whose best overlap is weak at the other read loses it and becomes a dead end, which elba_clip_tips then
+ * judges (miniasm's behaviour); sides_emptied counts how often that happened.
+ * There is no `rounds`: the pass is its own fixed point.  Every survivor of a side had score * 65536 >= ratio * best_old >= ratio * best_new
+ * (a side's best and count only fall or stay, and a side whose best was <= 0 had nothing weak), so a second call with the same ratio removes
+ * nothing.  And a smaller ratio removes a subset of what a larger one removes: weak at ratio q is weak at every ratio above q.
+ * Errors and state are those of elba_clip_tips, row for row: ELBA_ERR_STATE without a valid S; ELBA_ERR_INVALID_ARG for a null cfg, a ratio
+ * outside 1 .. 65536 or a non-zero reserved word; both leave S, the flags and the contigs as they were.  An S without entries or reads:
+ * ELBA_OK, nothing removed.  After ELBA_OK the context's S is the cut one, contigs made before are invalid, and elba_clip_tips and
+ * elba_pop_bubbles go on from there.
+ * Stats: counts of the one pass; entries_removed counts both images of a pair; ms_compact spans the keep flags (which here look up every
+ * entry's mirror image), the scan and the scatter.  One host synchronisation per call; cost is linear in nnz whatever a column's length. */
+typedef struct { int32_t min_ratio_q16;   /* 1 .. 65536: 65536 keeps only entries tied with the best of their side */
+                 int32_t reserved[3]; } elba_weak_cfg;
+typedef struct { int64_t nreads, nnz_before, nnz_after;
+                 int64_t branch_sides;     /* (read, side) with cnt >= 2 before the cut */
+                 int64_t weak_entries;     /* entries weak at their own column */
+                 int64_t entries_removed;  /* both images */
+                 int64_t sides_emptied;    /* (read, side) with cnt >= 1 before and no entry after */
+                 float ms_total, ms_compact; } elba_weak_stats;
+int  elba_cut_weak_overlaps(elba_ctx *ctx, const elba_weak_cfg *cfg, elba_weak_stats *stats);
+
 /* Read pileups and chimera flags: PileupVector / GetReadPileup / GetTrimmedInterval (src/PruneChimeras.cpp:14-69,108-158,
  * include/PruneChimeras.hpp), which src/main.cpp never calls, and R->PruneFull(x, x) of the reads it flags.  Runs after elba_align_seeds,
  * before elba_transitive_reduction, on the pairs that call would read: the list of elba_set_overlaps if one is loaded, else this context's
