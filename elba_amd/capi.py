@@ -154,6 +154,16 @@ class WeakStats(C.Structure):
                 ("entries_removed", C.c_int64), ("sides_emptied", C.c_int64), ("ms_total", C.c_float), ("ms_compact", C.c_float)]
 
 
+class BridgeCfg(C.Structure):
+    _fields_ = [("max_bridge_reads", C.c_int32), ("min_flank_reads", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class BridgeStats(C.Structure):
+    _fields_ = [("nreads", C.c_int64), ("nnz_before", C.c_int64), ("nnz_after", C.c_int64), ("anchors", C.c_int64), ("chains", C.c_int64),
+                ("long_flanks", C.c_int64), ("bridges", C.c_int64), ("reads_removed", C.c_int64), ("entries_removed", C.c_int64),
+                ("ms_total", C.c_float), ("ms_compact", C.c_float)]
+
+
 class Overlaps(C.Structure):
     _fields_ = [("n", C.c_int64), ("rows", C.c_void_p), ("cols", C.c_void_p), ("vals", C.c_void_p)]
 
@@ -208,7 +218,7 @@ EXPORTED_SYMBOLS = [
     "elba_generate_contigs", "elba_export_contigs", "elba_free_contigs", "elba_export_read_contigs", "elba_generate_contigs_ex", "elba_export_contig_kinds",
     "elba_read_pileup", "elba_export_pileup", "elba_free_pileup", "elba_prune_reads",
     "elba_trim_reads", "elba_export_trim_map", "elba_free_trim_map", "elba_get_trimmed_reads_device", "elba_adopt_trimmed_reads",
-    "elba_clip_tips", "elba_pop_bubbles", "elba_cut_weak_overlaps",
+    "elba_clip_tips", "elba_pop_bubbles", "elba_cut_weak_overlaps", "elba_cut_bridges",
 ]
 
 _lib = None
@@ -261,6 +271,7 @@ def load_library():
     L.elba_clip_tips.restype = i32; L.elba_clip_tips.argtypes = [vp, C.POINTER(TipCfg), C.POINTER(TipStats)]
     L.elba_pop_bubbles.restype = i32; L.elba_pop_bubbles.argtypes = [vp, C.POINTER(BubbleCfg), C.POINTER(BubbleStats)]
     L.elba_cut_weak_overlaps.restype = i32; L.elba_cut_weak_overlaps.argtypes = [vp, C.POINTER(WeakCfg), C.POINTER(WeakStats)]
+    L.elba_cut_bridges.restype = i32; L.elba_cut_bridges.argtypes = [vp, C.POINTER(BridgeCfg), C.POINTER(BridgeStats)]
     L.elba_generate_contigs.restype = i32; L.elba_generate_contigs.argtypes = [vp, C.POINTER(ContigStats)]
     L.elba_generate_contigs_ex.restype = i32; L.elba_generate_contigs_ex.argtypes = [vp, C.POINTER(ContigCfg), C.POINTER(ContigStats)]
     L.elba_export_contig_kinds.restype = i32; L.elba_export_contig_kinds.argtypes = [vp, vp, i64]
@@ -493,7 +504,8 @@ class Engine:
             self.L.elba_free_overlaps(C.byref(o))
 
     def export_read_flags(self, nreads):
-        """One byte per read: bit 0 = bad read, bit 1 = contained read, bit 2 = removed by clip_tips, bit 3 = removed by pop_bubbles."""
+        """One byte per read: bit 0 = bad read, bit 1 = contained read, bit 2 = removed by clip_tips, bit 3 = removed by pop_bubbles,
+        bit 4 = removed by cut_bridges."""
         f = np.zeros(int(nreads), dtype=np.uint8)
         self._check(self.L.elba_export_read_flags(self.h, f.ctypes.data, int(nreads)))
         return f
@@ -534,20 +546,37 @@ class Engine:
         self._check(self.L.elba_cut_weak_overlaps(self.h, C.byref(cfg), C.byref(st)))
         return _stats(st)
 
-    def simplify_graph(self, max_tip_reads, max_arm_reads, passes=16, min_overlap_ratio=None):
+    # --- cutting bridges (between transitive_reduction and generate_contigs, before or after the three above; asmtools/bridge_removal.py) ---
+    def cut_bridges(self, max_bridge_reads, min_flank_reads):
+        """Removes every chain of at most max_bridge_reads reads of degree 2 between two reads of degree exactly 3 whose other two edges
+        each lead into at least min_flank_reads reads of degree 2 (the bar of an H), in one pass.  min_flank_reads > max_bridge_reads.
+        Removed reads get flag 16; the two end reads stay, at degree 2.  Returns the stats."""
+        cfg = BridgeCfg(int(max_bridge_reads), int(min_flank_reads), (C.c_int32 * 2)(0, 0))
+        st = BridgeStats()
+        self._check(self.L.elba_cut_bridges(self.h, C.byref(cfg), C.byref(st)))
+        return _stats(st)
+
+    def simplify_graph(self, max_tip_reads, max_arm_reads, passes=16, min_overlap_ratio=None, bridges=None):
         """clip_tips(max_tip_reads, 64) then pop_bubbles(max_arm_reads, 64), again and again until a pass of both removes nothing or `passes`
         passes have run.  pop_bubbles alone does not reach that fixed point: a tip on an arm gives the arm a read of degree 3, so there is
         no arm until the tip is clipped.  (A pop makes no new tip on a symmetric graph — it lowers anchors to degree 2, which only lengthens
         dead-end chains — so the second pass is the one that finds nothing.)  Returns [(tip stats, bubble stats)], one pair per pass.
-        With min_overlap_ratio every pass ends with cut_weak_overlaps(min_overlap_ratio), which can make new dead ends and new arms: a pass
-        is (tip stats, bubble stats, weak stats), and the loop ends after a pass in which none of the three removed anything."""
+        With min_overlap_ratio every pass goes on with cut_weak_overlaps(min_overlap_ratio), which can make new dead ends and new arms: a
+        pass is (tip stats, bubble stats, weak stats).  With bridges = (max_bridge_reads, min_flank_reads) every pass ends with
+        cut_bridges(*bridges), whose stats are the last element of the pass's tuple.  The loop ends after a pass in which no call removed
+        anything."""
         out = []
         for _ in range(int(passes)):
-            if min_overlap_ratio is None:
-                out.append((self.clip_tips(max_tip_reads, 64), self.pop_bubbles(max_arm_reads, 64)))
-            else:
-                out.append((self.clip_tips(max_tip_reads, 64), self.pop_bubbles(max_arm_reads, 64), self.cut_weak_overlaps(min_overlap_ratio)))
-            if out[-1][0]["reads_removed"] == 0 and out[-1][1]["reads_removed"] == 0 and (min_overlap_ratio is None or out[-1][2]["entries_removed"] == 0):
+            p = (self.clip_tips(max_tip_reads, 64), self.pop_bubbles(max_arm_reads, 64))
+            idle = p[0]["reads_removed"] == 0 and p[1]["reads_removed"] == 0
+            if min_overlap_ratio is not None:
+                p += (self.cut_weak_overlaps(min_overlap_ratio),)
+                idle = idle and p[-1]["entries_removed"] == 0
+            if bridges is not None:
+                p += (self.cut_bridges(*bridges),)
+                idle = idle and p[-1]["reads_removed"] == 0
+            out.append(p)
+            if idle:
                 break
         return out
 

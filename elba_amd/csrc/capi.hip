@@ -393,6 +393,14 @@ int elba_cut_weak_overlaps(elba_ctx *ctx, const elba_weak_cfg *cfg, elba_weak_st
     });
 }
 
+int elba_cut_bridges(elba_ctx *ctx, const elba_bridge_cfg *cfg, elba_bridge_stats *stats)
+{
+    return guarded(ctx, [&](Ctx &c) {
+        stage_cut_bridges(c, cfg);
+        if (stats) *stats = c.brstats;
+    });
+}
+
 int elba_generate_contigs(elba_ctx *ctx, elba_contig_stats *stats)
 {
     return guarded(ctx, [&](Ctx &c) {
@@ -755,6 +763,7 @@ int elba_release_workspace(elba_ctx *ctx)
         c.tp_rows.release(); c.tp_cols.release(); c.tp_vals.release();                                                                    // spare buffer of S (S itself stays)
         c.bb_end.release(); c.bb_len.release();                                                                                            // bubble scratch
         c.wk_best.release(); c.wk_cnt.release(); c.wk_nweak.release(); c.wk_after.release();                                                                     // weak-overlap scratch
+        c.br_flank.release();                                                                                                              // bridge scratch
         if (has(c.v, P_COUNTS)) { c.pre_ready = false; c.pre_consumed = true; }    // (the CSR sort keys / column ids of the entries are gone: create_kmer_matrix rebuilds them from the column pointers)
     });
 }

@@ -342,6 +342,11 @@ struct Ctx {
     EventTimer wk_t_total, wk_t_compact;
     elba_weak_stats wkstats{};
 
+    // cutting bridge chains (bridges.hip): scratch of its own, one word per entry of S; the compaction's buffers are the tp_ ones above
+    DevBuf br_flank;
+    EventTimer br_t_total, br_t_compact;
+    elba_bridge_stats brstats{};
+
     // workspaces
     DevBuf ws_scan, ws_sort, ws_a, ws_b, ws_c, ws_d, ws_e, ws_f;
     DevBuf ws_cursor;       // the gather-slot cursor of the k-mer stage's emit kernels (kmer_msd.hip)
@@ -442,6 +447,7 @@ void stage_adopt_trimmed_reads(Ctx &c);
 void stage_clip_tips(Ctx &c, const elba_tip_cfg *cfg);                        // tips.hip
 void stage_pop_bubbles(Ctx &c, const elba_bubble_cfg *cfg);                   // bubbles.hip
 void stage_cut_weak_overlaps(Ctx &c, const elba_weak_cfg *cfg);              // weak.hip
+void stage_cut_bridges(Ctx &c, const elba_bridge_cfg *cfg);                   // bridges.hip
 void stage_dist_count_owners(Ctx &c, int nranks, uint64_t *counts_host);                                   // kmer.hip
 void stage_dist_value_histogram(Ctx &c, uint64_t *hist_host, int64_t nbins);
 void stage_ref_hash_owner(Ctx &c, const uint64_t *kmers_host, int64_t n, int nprocs, uint64_t *hash_host, int32_t *owner_host);

@@ -2,7 +2,8 @@
 // elba_pop_bubbles): the round-batch protocol and the compaction of S.  A call brings its RULE — kernels that, for round r, read the
 // round's S and set removed[v] = 1 for every read that goes, adding the reads they removed to st[SG_LIVE + r + 1]; everything else is here.
 // weak.hip (elba_cut_weak_overlaps) removes entries, not reads, in one pass: it brings a keep kernel of its own beside k_sg_keep and uses
-// sg_col_ptrs, sg_reserve, k_sg_init and k_sg_scatter as round 0 of the protocol, without sg_run_rounds.
+// sg_col_ptrs, sg_reserve, k_sg_init and k_sg_scatter as round 0 of the protocol, without sg_run_rounds.  bridges.hip (elba_cut_bridges)
+// removes reads in one pass and runs round 0 the same way, with k_sg_keep.
 //
 //   sg_col_ptrs     (device function) column pointers of the round's S from its column ids, nnz read on the device
 //   k_sg_keep       keep[z] = neither row nor column of entry z is removed (0 behind the round's nnz)

@@ -29,7 +29,8 @@ enum Event : unsigned {
     EV_SET_READS, EV_SET_READS_FASTA, EV_SET_READS_DEVICE, EV_ADOPT_TRIMMED_READS, EV_MATRIX_OF_OLD_READS,
     EV_COUNT_KMERS, EV_CREATE_KMER_MATRIX, EV_SET_KMER_MATRIX, EV_SET_KMER_MATRIX_DEVICE, EV_DIST_COUNT_RECORDS, EV_DIST_SET_PANEL,
     EV_CREATE_SEED_MATRIX, EV_SEED_MATRIX_BEGIN, EV_SEED_MATRIX_END, EV_SEED_MATRIX_SEND, EV_SEED_MATRIX_RECV,
-    EV_ALIGN_SEEDS, EV_DIST_SET_ALL_READS, EV_SET_OVERLAPS, EV_TRANSITIVE_REDUCTION, EV_CLIP_TIPS, EV_POP_BUBBLES, EV_CUT_WEAK_OVERLAPS, EV_GENERATE_CONTIGS,
+    EV_ALIGN_SEEDS, EV_DIST_SET_ALL_READS, EV_SET_OVERLAPS, EV_TRANSITIVE_REDUCTION, EV_CLIP_TIPS, EV_POP_BUBBLES, EV_CUT_WEAK_OVERLAPS, EV_CUT_BRIDGES,
+    EV_GENERATE_CONTIGS,
     EV_READ_PILEUP, EV_PRUNE_READS, EV_TRIM_READS,
     EV_COUNT
 };
@@ -78,6 +79,7 @@ constexpr Row TABLE[] = {
     {EV_CLIP_TIPS,              "clip_tips",              0,                       mask(P_S, P_CONTIGS),                 0,                                mask(P_S),      0},
     {EV_POP_BUBBLES,            "pop_bubbles",            0,                       mask(P_S, P_CONTIGS),                 0,                                mask(P_S),      0},          // (as clip_tips, row for row)
     {EV_CUT_WEAK_OVERLAPS,      "cut_weak_overlaps",      0,                       mask(P_S, P_CONTIGS),                 0,                                mask(P_S),      0},          // (the same: it removes entries, not reads, which the table does not see)
+    {EV_CUT_BRIDGES,            "cut_bridges",            0,                       mask(P_S, P_CONTIGS),                 0,                                mask(P_S),      0},          // (as clip_tips, row for row: it removes reads)
     {EV_GENERATE_CONTIGS,       "generate_contigs",       mask(P_CONTIGS),         0,                                    0,                                mask(P_CONTIGS), 0},         // (elba_generate_contigs and _ex: a rejected call leaves no contigs)
     {EV_READ_PILEUP,            "read_pileup",            mask(P_PILEUP, P_TRIM),  0,                                    0,                                mask(P_PILEUP), 0},          // (the trimmed reads are cut from the pileup they were asked of)
     // the kept pairs become the loaded edge list; the alignments and the trimmed reads stay

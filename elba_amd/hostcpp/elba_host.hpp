@@ -23,6 +23,7 @@
 //   (none: the reference drops every branch read)                             elba::ClipTips(S, reads, max_tip_reads, rounds): dead-end tips leave S
 //   (none)                                                                    elba::PopBubbles(S, reads, max_arm_reads, rounds): all but one arm of a bubble leave S
 //   (none)                                                                    elba::CutWeakOverlaps(S, reads, min_ratio_q16): weak overlaps at branching read ends leave S
+//   asmtools/bridge_removal.py (a script run on the written-out graph)        elba::CutBridges(S, reads, max_bridge_reads, min_flank_reads): short chains between two long paths leave S
 //
 // Errors: the reference asserts/aborts; here every failing C-ABI status throws elba::Error (status + text).
 // There is no CPU path: constructing an engine without a GPU throws ELBA_ERR_NO_DEVICE.
@@ -418,7 +419,7 @@ inline std::unique_ptr<StringGraph> TransitiveReduction(const DnaBuffer &myreads
     return S;
 }
 
-// The host copy of S after a call that changed it on the device (ClipTips, PopBubbles, CutWeakOverlaps): the entries of elba_export_string_graph; removed_reads,
+// The host copy of S after a call that changed it on the device (ClipTips, PopBubbles, CutWeakOverlaps, CutBridges): the entries of elba_export_string_graph; removed_reads,
 // if given, receives the reads that carry `flag` in elba_export_read_flags, ascending.
 inline void reload_string_graph(StringGraph &S, const DnaBuffer &myreads, uint8_t flag, std::vector<int64_t> *removed_reads)
 {
@@ -486,6 +487,22 @@ inline elba_weak_stats CutWeakOverlaps(StringGraph &S, const DnaBuffer &myreads,
     elba_weak_stats st{};
     S.engine->check(elba_cut_weak_overlaps(S.engine->ctx, &cfg, &st));
     reload_string_graph(S, myreads, 0, nullptr);
+    return st;
+}
+
+// CutBridges(S, myreads, max_bridge_reads, min_flank_reads) — the rule of asmtools/bridge_removal.py for chains: elba_cut_bridges on the S that
+// TransitiveReduction (or one of the three calls above) left on the device, before GenerateContigs.  A chain of at most max_bridge_reads reads
+// of degree 2 between two reads of degree exactly 3, each of whose other two edges leads into at least min_flank_reads reads of degree 2,
+// leaves S, in one pass; the two end reads stay.  The host copy of S is replaced by the cut graph, and cut_reads, if given, receives the reads
+// removed so far (flag bit 4 of elba_export_read_flags), ascending.
+inline elba_bridge_stats CutBridges(StringGraph &S, const DnaBuffer &myreads, int max_bridge_reads, int min_flank_reads, std::vector<int64_t> *cut_reads = nullptr)
+{
+    if (!S.engine) throw Error(ELBA_ERR_STATE, "CutBridges: the string graph is not on a device");
+    elba_bridge_cfg cfg{};
+    cfg.max_bridge_reads = max_bridge_reads; cfg.min_flank_reads = min_flank_reads;
+    elba_bridge_stats st{};
+    S.engine->check(elba_cut_bridges(S.engine->ctx, &cfg, &st));
+    reload_string_graph(S, myreads, 16, cut_reads);
     return st;
 }
 

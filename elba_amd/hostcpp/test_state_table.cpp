@@ -11,14 +11,16 @@ using namespace elba;
 
 static const char *const PRODUCT_NAMES[P_COUNT] = {"reads", "counts", "A", "B", "aln", "edges", "S", "contigs", "pileup", "trim"};
 
-// the three calls that change S in place share one row: what elba_clip_tips does to a context, the other two do
+// the four calls that change S in place share one row: what elba_clip_tips does to a context, the other three do
 constexpr bool same_row(Event a, Event b)
 {
     return TABLE[a].enter == TABLE[b].enter && TABLE[a].accepted == TABLE[b].accepted && TABLE[a].done == TABLE[b].done && TABLE[a].publish == TABLE[b].publish &&
            TABLE[a].of_aln == TABLE[b].of_aln;
 }
-static_assert(same_row(EV_CLIP_TIPS, EV_POP_BUBBLES) && same_row(EV_CLIP_TIPS, EV_CUT_WEAK_OVERLAPS), "state.hpp: pop_bubbles and cut_weak_overlaps are clip_tips, row for row");
-static_assert(EV_POP_BUBBLES == EV_CLIP_TIPS + 1 && EV_CUT_WEAK_OVERLAPS == EV_POP_BUBBLES + 1, "state.hpp: the three rows follow one another");
+static_assert(same_row(EV_CLIP_TIPS, EV_POP_BUBBLES) && same_row(EV_CLIP_TIPS, EV_CUT_WEAK_OVERLAPS) && same_row(EV_CLIP_TIPS, EV_CUT_BRIDGES),
+              "state.hpp: pop_bubbles, cut_weak_overlaps and cut_bridges are clip_tips, row for row");
+static_assert(EV_POP_BUBBLES == EV_CLIP_TIPS + 1 && EV_CUT_WEAK_OVERLAPS == EV_POP_BUBBLES + 1 && EV_CUT_BRIDGES == EV_CUT_WEAK_OVERLAPS + 1,
+              "state.hpp: the four rows follow one another");
 
 int main(int argc, char **argv)
 {

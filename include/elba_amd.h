@@ -294,7 +294,7 @@ void elba_free_overlaps(elba_overlaps_t *o);
  * elba_export_string_graph returns the entries of S, both triangles, in the order parallel_write_paf walks the reference's S
  * (src/main.cpp:527-541: columns ascending, rows ascending within a column); an entry below the diagonal carries Overlap::Transpose
  * (include/Overlap.hpp:43-69) of its mirror image.  elba_export_read_flags: flags[v] bit 0 = bad read, bit 1 = contained read,
- * bit 2 = removed by elba_clip_tips since, bit 3 = removed by elba_pop_bubbles since. */
+ * bit 2 = removed by elba_clip_tips since, bit 3 = removed by elba_pop_bubbles since, bit 4 = removed by elba_cut_bridges since. */
 int  elba_set_overlaps(elba_ctx *ctx, int64_t nreads, const int64_t *rows, const int64_t *cols, const elba_overlap_t *vals, int64_t n);
 int  elba_transitive_reduction(elba_ctx *ctx, double bad_read_cutoff, int fuzz, elba_string_stats *stats);
 int  elba_export_string_graph(elba_ctx *ctx, elba_overlaps_t *out);
@@ -478,6 +478,70 @@ typedef struct { int64_t nreads, nnz_before, nnz_after;
                  int64_t sides_emptied;    /* (read, side) with cnt >= 1 before and no entry after */
                  float ms_total, ms_compact; } elba_weak_stats;
 int  elba_cut_weak_overlaps(elba_ctx *ctx, const elba_weak_cfg *cfg, elba_weak_stats *stats);
+
+/* Cutting bridges (the rule of the reference's asmtools/bridge_removal.py, which runs on a written-out graph after the program; taken here
+ * from one read to a chain of reads).  A bridge is a read, or a short chain of reads, that joins the middles of two otherwise independent
+ * long paths — a chimeric read that survived the pileup, a repeat copy two loci share — so that the graph looks like the letter H.  Each end
+ * read of the bridge has degree 3 and elba_generate_contigs* drops it: an H costs four contigs and three or more lost reads where there are
+ * two paths.  Both flanks are long (no tip), the chains do not rejoin (no bubble) and the scores can tie (no weak overlap).
+ * elba_cut_bridges works on the S of elba_transitive_reduction, in place, between that call and elba_generate_contigs*, before or after the
+ * other three cleaning calls.  The rule is stated on the columns of S alone, as the tips and bubbles rules are: deg(v) = entries of column v,
+ * the neighbours of v = their rows; no sequence, no suffix, no score, no direction, no length in bases.  ONE pass, on tables frozen at its
+ * start:
+ *   anchor     a read of degree >= 3.
+ *   chain      exactly the arm of elba_pop_bubbles: for an anchor a and an entry of column a whose row v1 has degree 2, the tips walk: "came
+ *              from" is a for v1, and from a read of degree 2 the walk goes on to the first row of its column that is not the read it came
+ *              from.  The first read b of degree >= 3 ends it: v1 .. vt, 1 <= t <= max_bridge_reads, is a chain from a to b.  There is no
+ *              chain if the walk ends at a read of degree 0 or 1, if b == a, or if it would need more than max_bridge_reads reads.  Every
+ *              chain is recorded once, at its smaller anchor (a < b).
+ *   flank      for a read u of degree exactly 3 and an entry of column u with row w: walk from w, "came from" u, and count the reads of
+ *              degree 2 passed; stop at the first read whose degree is not 2, or when min_flank_reads have been counted.  The flank is LONG
+ *              when the count reached min_flank_reads.  A flank that ends in a dead end counts its degree-2 reads only: min_flank_reads - 1
+ *              reads of degree 2 followed by a read of degree 1 is short.  (The walk does not ask where it is: round a loop of degree-2 reads
+ *              that returns to u it counts the loop's reads once, and in a component that is one cycle it would go round until the count is
+ *              reached — but such a component has no anchor to start from.)
+ *   bridge     a chain from a to b for which all three hold: deg(a) == 3 and deg(b) == 3; the two entries of column a other than v1's are
+ *              both long flanks; column b holds an entry whose row is vt, and its two other entries are both long flanks.  (On a symmetric
+ *              S column b always holds vt.)
+ *   removal    every read of a bridge gets bit 4 (value 16) in the flags of elba_export_read_flags until the next
+ *              elba_transitive_reduction rebuilds them; every entry of S whose row or column is such a read goes, in both triangles; the
+ *              other entries keep their values and their order (columns ascending, rows ascending within a column).  a and b stay: each
+ *              falls to degree 2, and its two flanks become one path.
+ * min_flank_reads > max_bridge_reads is required.  On a symmetric S this gives:
+ *   1. A chain is never a long flank: seen from either anchor as a flank it counts t <= max_bridge_reads < min_flank_reads reads and ends
+ *      at a read of degree >= 3.  A bridge at a needs the two other entries of column a to be long flanks, so of the three entries of
+ *      column a at most one starts a bridge: an anchor has at most one bridge, bridges are disjoint (their reads have degree 2 and lie on
+ *      one chain), and no read loses an entry except the bridge's reads, which lose all, and its two anchors, which lose one each.
+ *   2. No component is erased: the bridge's reads go, but each anchor keeps two long flanks, 2 * min_flank_reads reads or more.
+ *   3. The pass is its own fixed point, so there is no `rounds`.  A chain left uncut between anchors of degree 3 had a short flank: one
+ *      that ended, after fewer than min_flank_reads reads of degree 2, at a read x of degree != 2.  After the pass the degree of x is
+ *      another only if x is a cut anchor (guarantee 1), reached here through one of its own flanks.  But then the same reads walked the
+ *      other way, from x, were a flank of x of fewer than min_flank_reads reads that ended at an anchor: a short flank of x, so x was not
+ *      cut.  A chain whose anchor has degree >= 4 keeps it (such an anchor is no bridge's end), and new chains do not appear: a cut anchor
+ *      has degree 2 afterwards and only lengthens what passes through it.  A second call with the same cfg removes nothing.
+ *   4. With max_bridge_reads = 1 and min_flank_reads = walklen >= 2 the removed entries are those asmtools/bridge_removal.py removes from
+ *      the same graph: a read of degree 2 whose two neighbours both have degree 3, each with exactly two walks of at least walklen reads
+ *      of degree 2 (that script's third walk, the one through the bridge read, has length 1 and never counts).
+ * Where the reduction kept only one image of a pair (the direction -1 case) the contract is what the statements above produce on the
+ * columns as they are; the guarantees are not claimed there.
+ * Errors and state are those of elba_clip_tips, row for row: ELBA_ERR_STATE without a valid S; ELBA_ERR_INVALID_ARG for a null cfg, a value
+ * out of range, min_flank_reads <= max_bridge_reads or a non-zero reserved word; all of these leave S, the flags and the contigs as they
+ * were.  An S without entries or reads: ELBA_OK, nothing removed.  After ELBA_OK the context's S is the cut one, contigs made before are
+ * invalid, and the other cleaning calls go on from there.  Since ELBA_CONTIG_SINGLETONS emits only reads whose flags are 0, a bridge read
+ * does not come back as a contig of its own.
+ * Stats: counts of the one pass; entries_removed counts both triangles; ms_compact spans the keep flags, the scan and the scatter.  One host
+ * synchronisation per call; an entry of a degree-3 column costs at most min_flank_reads dependent steps, an entry of an anchor's column at
+ * most max_bridge_reads more. */
+typedef struct { int32_t max_bridge_reads;   /* 1 .. 65534 */
+                 int32_t min_flank_reads;    /* max_bridge_reads + 1 .. 65535 */
+                 int32_t reserved[2]; } elba_bridge_cfg;
+typedef struct { int64_t nreads, nnz_before, nnz_after;
+                 int64_t anchors;        /* reads of degree >= 3 */
+                 int64_t chains;         /* chains found, cut or not: equals elba_pop_bubbles' `arms` of one round with max_arm_reads = max_bridge_reads on the same S */
+                 int64_t long_flanks;    /* entries of degree-3 columns whose flank is long */
+                 int64_t bridges, reads_removed, entries_removed;   /* entries: both triangles */
+                 float ms_total, ms_compact; } elba_bridge_stats;
+int  elba_cut_bridges(elba_ctx *ctx, const elba_bridge_cfg *cfg, elba_bridge_stats *stats);
 
 /* Read pileups and chimera flags: PileupVector / GetReadPileup / GetTrimmedInterval (src/PruneChimeras.cpp:14-69,108-158,
  * include/PruneChimeras.hpp), which src/main.cpp never calls, and R->PruneFull(x, x) of the reads it flags.  Runs after elba_align_seeds,
