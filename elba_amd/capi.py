@@ -164,6 +164,16 @@ class BridgeStats(C.Structure):
                 ("ms_total", C.c_float), ("ms_compact", C.c_float)]
 
 
+class StarCfg(C.Structure):
+    _fields_ = [("rounds", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class StarStats(C.Structure):
+    _fields_ = [("nreads", C.c_int64), ("nnz_before", C.c_int64), ("nnz_after", C.c_int64), ("centres", C.c_int64), ("pairs0", C.c_int64),
+                ("pairs1", C.c_int64), ("pairs2", C.c_int64), ("pairs3", C.c_int64), ("reads_removed", C.c_int64), ("entries_removed", C.c_int64),
+                ("rounds_run", C.c_int32), ("reserved", C.c_int32), ("ms_total", C.c_float), ("ms_compact", C.c_float)]
+
+
 class Overlaps(C.Structure):
     _fields_ = [("n", C.c_int64), ("rows", C.c_void_p), ("cols", C.c_void_p), ("vals", C.c_void_p)]
 
@@ -218,7 +228,7 @@ EXPORTED_SYMBOLS = [
     "elba_generate_contigs", "elba_export_contigs", "elba_free_contigs", "elba_export_read_contigs", "elba_generate_contigs_ex", "elba_export_contig_kinds",
     "elba_read_pileup", "elba_export_pileup", "elba_free_pileup", "elba_prune_reads",
     "elba_trim_reads", "elba_export_trim_map", "elba_free_trim_map", "elba_get_trimmed_reads_device", "elba_adopt_trimmed_reads",
-    "elba_clip_tips", "elba_pop_bubbles", "elba_cut_weak_overlaps", "elba_cut_bridges",
+    "elba_clip_tips", "elba_pop_bubbles", "elba_cut_weak_overlaps", "elba_cut_bridges", "elba_resolve_stars",
 ]
 
 _lib = None
@@ -272,6 +282,7 @@ def load_library():
     L.elba_pop_bubbles.restype = i32; L.elba_pop_bubbles.argtypes = [vp, C.POINTER(BubbleCfg), C.POINTER(BubbleStats)]
     L.elba_cut_weak_overlaps.restype = i32; L.elba_cut_weak_overlaps.argtypes = [vp, C.POINTER(WeakCfg), C.POINTER(WeakStats)]
     L.elba_cut_bridges.restype = i32; L.elba_cut_bridges.argtypes = [vp, C.POINTER(BridgeCfg), C.POINTER(BridgeStats)]
+    L.elba_resolve_stars.restype = i32; L.elba_resolve_stars.argtypes = [vp, C.POINTER(StarCfg), C.POINTER(StarStats)]
     L.elba_generate_contigs.restype = i32; L.elba_generate_contigs.argtypes = [vp, C.POINTER(ContigStats)]
     L.elba_generate_contigs_ex.restype = i32; L.elba_generate_contigs_ex.argtypes = [vp, C.POINTER(ContigCfg), C.POINTER(ContigStats)]
     L.elba_export_contig_kinds.restype = i32; L.elba_export_contig_kinds.argtypes = [vp, vp, i64]
@@ -505,7 +516,7 @@ class Engine:
 
     def export_read_flags(self, nreads):
         """One byte per read: bit 0 = bad read, bit 1 = contained read, bit 2 = removed by clip_tips, bit 3 = removed by pop_bubbles,
-        bit 4 = removed by cut_bridges."""
+        bit 4 = removed by cut_bridges, bit 5 = removed by resolve_stars."""
         f = np.zeros(int(nreads), dtype=np.uint8)
         self._check(self.L.elba_export_read_flags(self.h, f.ctypes.data, int(nreads)))
         return f
@@ -556,15 +567,26 @@ class Engine:
         self._check(self.L.elba_cut_bridges(self.h, C.byref(cfg), C.byref(st)))
         return _stats(st)
 
-    def simplify_graph(self, max_tip_reads, max_arm_reads, passes=16, min_overlap_ratio=None, bridges=None):
+    # --- resolving three-armed stars (between transitive_reduction and generate_contigs, before or after the four above; asmtools/star_resolution.py) ---
+    def resolve_stars(self, rounds=1):
+        """A read of degree 3 whose three neighbours all have degree 2 is a centre; when exactly one pair of the three neighbours is a pair
+        of R (the overlaps the last transitive_reduction started from, after its prunes), the neighbour in no such pair leaves S with its
+        entries and gets flag 32.  Up to `rounds` rounds, each on the S the one before left.  Returns the stats (resolved = pairs1)."""
+        cfg = StarCfg(int(rounds), (C.c_int32 * 3)(0, 0, 0))
+        st = StarStats()
+        self._check(self.L.elba_resolve_stars(self.h, C.byref(cfg), C.byref(st)))
+        return _stats(st)
+
+    def simplify_graph(self, max_tip_reads, max_arm_reads, passes=16, min_overlap_ratio=None, bridges=None, stars=None):
         """clip_tips(max_tip_reads, 64) then pop_bubbles(max_arm_reads, 64), again and again until a pass of both removes nothing or `passes`
         passes have run.  pop_bubbles alone does not reach that fixed point: a tip on an arm gives the arm a read of degree 3, so there is
         no arm until the tip is clipped.  (A pop makes no new tip on a symmetric graph — it lowers anchors to degree 2, which only lengthens
         dead-end chains — so the second pass is the one that finds nothing.)  Returns [(tip stats, bubble stats)], one pair per pass.
         With min_overlap_ratio every pass goes on with cut_weak_overlaps(min_overlap_ratio), which can make new dead ends and new arms: a
         pass is (tip stats, bubble stats, weak stats).  With bridges = (max_bridge_reads, min_flank_reads) every pass ends with
-        cut_bridges(*bridges), whose stats are the last element of the pass's tuple.  The loop ends after a pass in which no call removed
-        anything."""
+        cut_bridges(*bridges), whose stats are the last element of the pass's tuple.  With stars = True (64 rounds) or a round count every
+        pass ends with resolve_stars, after cut_bridges if that is asked for, and its stats are the last element.  The loop ends after a
+        pass in which no call removed anything."""
         out = []
         for _ in range(int(passes)):
             p = (self.clip_tips(max_tip_reads, 64), self.pop_bubbles(max_arm_reads, 64))
@@ -574,6 +596,9 @@ class Engine:
                 idle = idle and p[-1]["entries_removed"] == 0
             if bridges is not None:
                 p += (self.cut_bridges(*bridges),)
+                idle = idle and p[-1]["reads_removed"] == 0
+            if stars is not None and stars is not False:
+                p += (self.resolve_stars(64 if stars is True else stars),)
                 idle = idle and p[-1]["reads_removed"] == 0
             out.append(p)
             if idle:

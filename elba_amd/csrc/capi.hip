@@ -401,6 +401,14 @@ int elba_cut_bridges(elba_ctx *ctx, const elba_bridge_cfg *cfg, elba_bridge_stat
     });
 }
 
+int elba_resolve_stars(elba_ctx *ctx, const elba_star_cfg *cfg, elba_star_stats *stats)
+{
+    return guarded(ctx, [&](Ctx &c) {
+        stage_resolve_stars(c, cfg);
+        if (stats) *stats = c.srstats;
+    });
+}
+
 int elba_generate_contigs(elba_ctx *ctx, elba_contig_stats *stats)
 {
     return guarded(ctx, [&](Ctx &c) {
@@ -764,6 +772,7 @@ int elba_release_workspace(elba_ctx *ctx)
         c.bb_end.release(); c.bb_len.release();                                                                                            // bubble scratch
         c.wk_best.release(); c.wk_cnt.release(); c.wk_nweak.release(); c.wk_after.release();                                                                     // weak-overlap scratch
         c.br_flank.release();                                                                                                              // bridge scratch
+        c.sr_word.release();                                                                                                               // star scratch (tr_ptr / tr_sym, which it reads, stay)
         if (has(c.v, P_COUNTS)) { c.pre_ready = false; c.pre_consumed = true; }    // (the CSR sort keys / column ids of the entries are gone: create_kmer_matrix rebuilds them from the column pointers)
     });
 }

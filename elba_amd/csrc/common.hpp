@@ -193,6 +193,11 @@ struct Options {
 // the rows [lo, hi) of B a context computes (Ctx::window)
 struct RowWindow { int64_t lo, hi; int64_t rows() const { return hi - lo; } };
 
+// an entry of the symmetrised R that tr.hip builds and leaves in Ctx::tr_sym (CSR over the reads, Ctx::tr_ptr; columns ascending within a row):
+// meta = direction | directionT << 3 | below-diagonal << 6.  stars.hip looks columns up in it
+struct alignas(16) SymEntry { uint32_t col; int32_t suffix, suffixT; uint32_t meta; };
+static_assert(sizeof(SymEntry) == 16, "tr.hip and stars.hip read 16-byte entries");
+
 struct Ctx {
     elba_cfg cfg{};
     Options opt;
@@ -300,6 +305,7 @@ struct Ctx {
     DevBuf tr_in_rows, tr_in_cols, tr_in_vals;
     int64_t tr_M = 0, tr_nnz = 0, tr_id_base = 0;
     DevBuf tr_deg, tr_pas, tr_flags, tr_k0, tr_v0, tr_k1, tr_v1, tr_ptr, tr_sym, tr_src, tr_mark, tr_ctr, tr_sel, tr_out_rows, tr_out_cols, tr_out_vals;
+    int64_t tr_sym_M = 0, tr_sym_n = 0;     // what tr_ptr / tr_sym describe since the last reduction that succeeded: reads, symmetrised entries (0: tr_ptr was not written)
     elba_string_stats sstats{};
 
     // contigs (contig.hip): results (cid, eread, epre, estr, eboff, soff, coff, seq, kind) survive elba_release_workspace, the rest is scratch
@@ -346,6 +352,11 @@ struct Ctx {
     DevBuf br_flank;
     EventTimer br_t_total, br_t_compact;
     elba_bridge_stats brstats{};
+
+    // resolving three-armed stars (stars.hip): scratch of its own, one word per read; the rounds' buffers are the tp_ ones above.  It reads tr_ptr / tr_sym
+    DevBuf sr_word;
+    EventTimer sr_t_total, sr_t_compact;
+    elba_star_stats srstats{};
 
     // workspaces
     DevBuf ws_scan, ws_sort, ws_a, ws_b, ws_c, ws_d, ws_e, ws_f;
@@ -448,6 +459,7 @@ void stage_clip_tips(Ctx &c, const elba_tip_cfg *cfg);                        //
 void stage_pop_bubbles(Ctx &c, const elba_bubble_cfg *cfg);                   // bubbles.hip
 void stage_cut_weak_overlaps(Ctx &c, const elba_weak_cfg *cfg);              // weak.hip
 void stage_cut_bridges(Ctx &c, const elba_bridge_cfg *cfg);                   // bridges.hip
+void stage_resolve_stars(Ctx &c, const elba_star_cfg *cfg);                   // stars.hip
 void stage_dist_count_owners(Ctx &c, int nranks, uint64_t *counts_host);                                   // kmer.hip
 void stage_dist_value_histogram(Ctx &c, uint64_t *hist_host, int64_t nbins);
 void stage_ref_hash_owner(Ctx &c, const uint64_t *kmers_host, int64_t n, int nprocs, uint64_t *hash_host, int32_t *owner_host);

@@ -1,5 +1,5 @@
 // sg_rounds.hpp — what the calls that take reads out of the string graph in rounds share (tips.hip: elba_clip_tips, bubbles.hip:
-// elba_pop_bubbles): the round-batch protocol and the compaction of S.  A call brings its RULE — kernels that, for round r, read the
+// elba_pop_bubbles, stars.hip: elba_resolve_stars): the round-batch protocol and the compaction of S.  A call brings its RULE — kernels that, for round r, read the
 // round's S and set removed[v] = 1 for every read that goes, adding the reads they removed to st[SG_LIVE + r + 1]; everything else is here.
 // weak.hip (elba_cut_weak_overlaps) removes entries, not reads, in one pass: it brings a keep kernel of its own beside k_sg_keep and uses
 // sg_col_ptrs, sg_reserve, k_sg_init and k_sg_scatter as round 0 of the protocol, without sg_run_rounds.  bridges.hip (elba_cut_bridges)

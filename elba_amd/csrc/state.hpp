@@ -29,7 +29,7 @@ enum Event : unsigned {
     EV_SET_READS, EV_SET_READS_FASTA, EV_SET_READS_DEVICE, EV_ADOPT_TRIMMED_READS, EV_MATRIX_OF_OLD_READS,
     EV_COUNT_KMERS, EV_CREATE_KMER_MATRIX, EV_SET_KMER_MATRIX, EV_SET_KMER_MATRIX_DEVICE, EV_DIST_COUNT_RECORDS, EV_DIST_SET_PANEL,
     EV_CREATE_SEED_MATRIX, EV_SEED_MATRIX_BEGIN, EV_SEED_MATRIX_END, EV_SEED_MATRIX_SEND, EV_SEED_MATRIX_RECV,
-    EV_ALIGN_SEEDS, EV_DIST_SET_ALL_READS, EV_SET_OVERLAPS, EV_TRANSITIVE_REDUCTION, EV_CLIP_TIPS, EV_POP_BUBBLES, EV_CUT_WEAK_OVERLAPS, EV_CUT_BRIDGES,
+    EV_ALIGN_SEEDS, EV_DIST_SET_ALL_READS, EV_SET_OVERLAPS, EV_TRANSITIVE_REDUCTION, EV_RESOLVE_STARS, EV_CLIP_TIPS, EV_POP_BUBBLES, EV_CUT_WEAK_OVERLAPS, EV_CUT_BRIDGES,
     EV_GENERATE_CONTIGS,
     EV_READ_PILEUP, EV_PRUNE_READS, EV_TRIM_READS,
     EV_COUNT
@@ -76,6 +76,7 @@ constexpr Row TABLE[] = {
     {EV_TRANSITIVE_REDUCTION,   "transitive_reduction",   mask(P_CONTIGS),         mask(P_S),                            0,                                mask(P_S),      0},
     // S is invalid while the rounds are queued and valid again when the counters are back; accepted only after every buffer is
     // reserved, so that a rejected cfg — or no memory — leaves S and the contigs as they are
+    {EV_RESOLVE_STARS,          "resolve_stars",          0,                       mask(P_S, P_CONTIGS),                 0,                                mask(P_S),      0},          // (as clip_tips, row for row: it removes reads; it stands here because the four rows below follow one another)
     {EV_CLIP_TIPS,              "clip_tips",              0,                       mask(P_S, P_CONTIGS),                 0,                                mask(P_S),      0},
     {EV_POP_BUBBLES,            "pop_bubbles",            0,                       mask(P_S, P_CONTIGS),                 0,                                mask(P_S),      0},          // (as clip_tips, row for row)
     {EV_CUT_WEAK_OVERLAPS,      "cut_weak_overlaps",      0,                       mask(P_S, P_CONTIGS),                 0,                                mask(P_S),      0},          // (the same: it removes entries, not reads, which the table does not see)

@@ -28,8 +28,6 @@ namespace elba {
 
 namespace {
 
-struct alignas(16) SymEntry { uint32_t col; int32_t suffix, suffixT; uint32_t meta; };
-
 struct TrParams {
     const int64_t *rows, *cols; const elba_overlap_t *vals; int64_t n;
     uint32_t M; int mb; double cutoff; int fuzz;
@@ -325,7 +323,7 @@ void stage_transitive_reduction(Ctx &c, double bad_read_cutoff, int fuzz)
     st.products = (int64_t)h[4]; st.marked = (int64_t)h[5]; st.removed = (int64_t)h[6]; st.nnz = nnz;
     st.iterations = st.removed > 0 ? 2 : 1;
     st.ms_total = c.t_total.ms(); st.ms_minplus = ms_mark;
-    c.tr_M = M; c.tr_nnz = nnz; c.sstats = st; done(c.v, EV_TRANSITIVE_REDUCTION);
+    c.tr_M = M; c.tr_nnz = nnz; c.tr_sym_M = M; c.tr_sym_n = n2; c.sstats = st; done(c.v, EV_TRANSITIVE_REDUCTION);
 }
 
 }  // namespace elba

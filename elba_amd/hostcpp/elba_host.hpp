@@ -24,6 +24,7 @@
 //   (none)                                                                    elba::PopBubbles(S, reads, max_arm_reads, rounds): all but one arm of a bubble leave S
 //   (none)                                                                    elba::CutWeakOverlaps(S, reads, min_ratio_q16): weak overlaps at branching read ends leave S
 //   asmtools/bridge_removal.py (a script run on the written-out graph)        elba::CutBridges(S, reads, max_bridge_reads, min_flank_reads): short chains between two long paths leave S
+//   asmtools/star_resolution.py (a script run on the written-out graphs)      elba::ResolveStars(S, reads, rounds): the stray arm of a three-armed star leaves S
 //
 // Errors: the reference asserts/aborts; here every failing C-ABI status throws elba::Error (status + text).
 // There is no CPU path: constructing an engine without a GPU throws ELBA_ERR_NO_DEVICE.
@@ -419,7 +420,7 @@ inline std::unique_ptr<StringGraph> TransitiveReduction(const DnaBuffer &myreads
     return S;
 }
 
-// The host copy of S after a call that changed it on the device (ClipTips, PopBubbles, CutWeakOverlaps, CutBridges): the entries of elba_export_string_graph; removed_reads,
+// The host copy of S after a call that changed it on the device (ClipTips, PopBubbles, CutWeakOverlaps, CutBridges, ResolveStars): the entries of elba_export_string_graph; removed_reads,
 // if given, receives the reads that carry `flag` in elba_export_read_flags, ascending.
 inline void reload_string_graph(StringGraph &S, const DnaBuffer &myreads, uint8_t flag, std::vector<int64_t> *removed_reads)
 {
@@ -503,6 +504,23 @@ inline elba_bridge_stats CutBridges(StringGraph &S, const DnaBuffer &myreads, in
     elba_bridge_stats st{};
     S.engine->check(elba_cut_bridges(S.engine->ctx, &cfg, &st));
     reload_string_graph(S, myreads, 16, cut_reads);
+    return st;
+}
+
+// ResolveStars(S, myreads, rounds) — the rule of asmtools/star_resolution.py: elba_resolve_stars on the S that TransitiveReduction (or one of the
+// four calls above) left on the device, before GenerateContigs.  A read of degree 3 whose three neighbours all have degree 2 is a centre; when
+// exactly one pair of the three neighbours is a pair of R — the overlaps TransitiveReduction started from, after its prunes, which the device
+// keeps — the neighbour in no such pair leaves S with its entries, in up to `rounds` rounds; the centre stays.  The script's second argument,
+// the overlap graph, is not passed: it is the R of the TransitiveReduction call that made S.  The host copy of S is replaced by the resolved
+// graph, and odd_arms, if given, receives the reads removed so far (flag bit 5 of elba_export_read_flags), ascending.
+inline elba_star_stats ResolveStars(StringGraph &S, const DnaBuffer &myreads, int rounds = 1, std::vector<int64_t> *odd_arms = nullptr)
+{
+    if (!S.engine) throw Error(ELBA_ERR_STATE, "ResolveStars: the string graph is not on a device");
+    elba_star_cfg cfg{};
+    cfg.rounds = rounds;
+    elba_star_stats st{};
+    S.engine->check(elba_resolve_stars(S.engine->ctx, &cfg, &st));
+    reload_string_graph(S, myreads, 32, odd_arms);
     return st;
 }
 

@@ -21,6 +21,9 @@ static_assert(same_row(EV_CLIP_TIPS, EV_POP_BUBBLES) && same_row(EV_CLIP_TIPS, E
               "state.hpp: pop_bubbles, cut_weak_overlaps and cut_bridges are clip_tips, row for row");
 static_assert(EV_POP_BUBBLES == EV_CLIP_TIPS + 1 && EV_CUT_WEAK_OVERLAPS == EV_POP_BUBBLES + 1 && EV_CUT_BRIDGES == EV_CUT_WEAK_OVERLAPS + 1,
               "state.hpp: the four rows follow one another");
+// the fifth, resolve_stars, is the same row again and stands in front of the four
+static_assert(same_row(EV_CLIP_TIPS, EV_RESOLVE_STARS) && EV_RESOLVE_STARS == EV_TRANSITIVE_REDUCTION + 1 && EV_CLIP_TIPS == EV_RESOLVE_STARS + 1,
+              "state.hpp: resolve_stars is clip_tips, row for row, between transitive_reduction and clip_tips");
 
 int main(int argc, char **argv)
 {

@@ -294,7 +294,8 @@ void elba_free_overlaps(elba_overlaps_t *o);
  * elba_export_string_graph returns the entries of S, both triangles, in the order parallel_write_paf walks the reference's S
  * (src/main.cpp:527-541: columns ascending, rows ascending within a column); an entry below the diagonal carries Overlap::Transpose
  * (include/Overlap.hpp:43-69) of its mirror image.  elba_export_read_flags: flags[v] bit 0 = bad read, bit 1 = contained read,
- * bit 2 = removed by elba_clip_tips since, bit 3 = removed by elba_pop_bubbles since, bit 4 = removed by elba_cut_bridges since. */
+ * bit 2 = removed by elba_clip_tips since, bit 3 = removed by elba_pop_bubbles since, bit 4 = removed by elba_cut_bridges since,
+ * bit 5 = removed by elba_resolve_stars since. */
 int  elba_set_overlaps(elba_ctx *ctx, int64_t nreads, const int64_t *rows, const int64_t *cols, const elba_overlap_t *vals, int64_t n);
 int  elba_transitive_reduction(elba_ctx *ctx, double bad_read_cutoff, int fuzz, elba_string_stats *stats);
 int  elba_export_string_graph(elba_ctx *ctx, elba_overlaps_t *out);
@@ -542,6 +543,72 @@ typedef struct { int64_t nreads, nnz_before, nnz_after;
                  int64_t bridges, reads_removed, entries_removed;   /* entries: both triangles */
                  float ms_total, ms_compact; } elba_bridge_stats;
 int  elba_cut_bridges(elba_ctx *ctx, const elba_bridge_cfg *cfg, elba_bridge_stats *stats);
+
+/* Resolving three-armed stars (the rule of the reference's asmtools/star_resolution.py, which runs on the written-out string graph and
+ * overlap graph after the program).  A star is a read u of degree 3 whose three neighbours all have degree 2.  elba_generate_contigs* drops
+ * u with its edges, so one spurious overlap at u — typically a repeat copy u shares with a read from elsewhere — costs three contigs and a
+ * lost read where there is one path and a stray read.  None of the three arms has to end within max_tip_reads (no tip), the arms need not
+ * rejoin (no bubble), u has no second anchor opposite it (no bridge), and the three scores can tie (no weak overlap).  The graph alone
+ * cannot say which arm is the stray one; the overlap matrix before the reduction can.  The two true neighbours of u on its path overlap
+ * each other: their pair was in R and was removed as transitive through u.  The stray read overlaps neither.
+ * elba_resolve_stars works on the S of elba_transitive_reduction, in place, between that call and elba_generate_contigs*, before or after
+ * the other four cleaning calls, and beside S it reads the R of that same reduction, which the context keeps on the device and never
+ * changes (elba_release_workspace does not free it).  The rule is on the columns of S and on membership in R alone: deg(v) = entries of
+ * column v, the neighbours of v = their rows; no sequence, no suffix, no score, no direction, no length.  One ROUND, on tables frozen at
+ * its start:
+ *   centre     a read u with deg(u) == 3 whose three rows x1 < x2 < x3 each have degree exactly 2.
+ *   pair in R  {x, y} is a pair in R when the symmetrised R of the elba_transitive_reduction call that made this S has an entry (row x,
+ *              column y).  R is symmetric by construction, so either row answers (the kernel searches the shorter one).  R holds every
+ *              input pair that passed and touches no bad and no contained read — the pairs the reduction marked transitive among them,
+ *              and the pairs without a direction, which never reach S.
+ *   odd arm    let e be how many of {x1,x2}, {x1,x3}, {x2,x3} are pairs in R.  When e == 1 the neighbour in no such pair is the centre's
+ *              odd arm w.  When e is 0, 2 or 3 the centre is left alone.
+ *   removal    every odd arm gets bit 5 (value 32) in the flags of elba_export_read_flags until the next elba_transitive_reduction
+ *              rebuilds them; every entry of S whose row or column is an odd arm goes, in both triangles; the other entries keep their
+ *              values and their order (columns ascending, rows ascending within a column).  u stays and falls to degree 2 (lower if
+ *              another centre names one of its other neighbours); w's other neighbour loses an entry too.  That is what the script does:
+ *              it deletes every edge from and to the star vertex.
+ * Up to `rounds` rounds run, each on the S the one before left; the call stops after a round that removed nothing, and rounds_run counts
+ * that round, as in elba_clip_tips.  Rounds are needed because one pass is not its own fixed point: a removal can lower a degree-3
+ * neighbour of some degree-3 read to degree 2, and that read is then a new centre.  R is never changed; look-ups between reads that an
+ * earlier round or an earlier cleaning call removed never occur, because such reads are in no column and no row of S any more.
+ * What follows from the statements:
+ *   1. The result does not depend on the order in which reads are looked at.  Whether u is a centre, its e and its odd arm are functions
+ *      of the round's columns and of R, both frozen; what a round writes is a SET of odd arms, and a read named by two centres is in the
+ *      set once: it is flagged once, counted once in reads_removed, and its entries leave once.
+ *   2. Only reads of degree 2 are removed: an odd arm is a row of a centre's column, and all three of those have degree exactly 2 on the
+ *      tables the round decides on.  So a centre is never removed in the round in which it is a centre.
+ *   3. reads_removed <= resolved (= pairs1), with equality unless two centres of one round name the same arm: every centre with e == 1
+ *      names exactly one arm, and every removed read was named by at least one.
+ *   4. A round that removes nothing is a fixed point of the call: the next round would find the same columns and the same R, hence the
+ *      same centres, the same e, and again no arm.  So a further call with any `rounds` removes nothing either, until another call
+ *      changes S.
+ *   5. Correspondence with the script: with rounds = 1 the removed entries are those asmtools/star_resolution.py deletes from the same S
+ *      and R, when both graphs carry both arcs of every edge.  Its stars are the vertices of in-degree 3 whose successors all have
+ *      in-degree 2: the centres.  Its `len(star_arcs) == 2` then counts ONE pair among the three neighbours, present as two arcs: e == 1;
+ *      its `assert len(tmp) == 1` holds only under that reading (with two distinct pairs the three neighbours are all arc ends and tmp is
+ *      empty).  tmp's one vertex is the neighbour in no pair, and the script deletes every edge from and to it.  igraph is not available
+ *      to the tests, so the correspondence is by reading, as for asmtools/bridge_removal.py; no fixture was recorded from the script.  (The script runs one pass; its own loop to a fixed point is commented out.  `rounds` is that loop.)
+ * Where the reduction kept only one image of a pair (the direction -1 case) the contract is what the statements above produce on the
+ * columns as they are; guarantees 2 to 5 are not claimed there (a column can hold a row whose own column does not hold it back, so "u
+ * falls to degree 2" and the script's arcs need not hold).  Guarantee 1 holds always.
+ * Errors and state are those of elba_clip_tips, row for row: ELBA_ERR_STATE without a valid S; ELBA_ERR_INVALID_ARG for a null cfg, rounds
+ * outside 1 .. 64 or a non-zero reserved word; all of these leave S, the flags and the contigs as they were.  An S without entries or
+ * reads: ELBA_OK, nothing removed, rounds_run 1.  Index ranges beyond 32 bit: ELBA_ERR_UNSUPPORTED.  After ELBA_OK the context's S is the
+ * resolved one, contigs made before are invalid, and the other cleaning calls go on from there.  Since ELBA_CONTIG_SINGLETONS emits only
+ * reads whose flags are 0, an odd arm does not come back as a contig of its own.
+ * Stats: centres, pairs0 .. pairs3 (centres by e; pairs1 is `resolved`), reads_removed and entries_removed (both triangles) are summed over
+ * the rounds — a centre left alone in three rounds counts three times; ms_compact is the compaction of the first round.  Cost of `rounds`: as
+ * for elba_clip_tips, one host synchronisation per four rounds.  A read of degree 3 costs three more pointer pairs, a centre three binary
+ * searches of at most floor(log2(len)) + 1 dependent 4-byte loads each, len the shorter of the two rows of R. */
+typedef struct { int32_t rounds;          /* 1 .. 64: at most this many */
+                 int32_t reserved[3]; } elba_star_cfg;
+typedef struct { int64_t nreads, nnz_before, nnz_after;
+                 int64_t centres, pairs0, pairs1, pairs2, pairs3;      /* summed over the rounds: centres, and centres by e; pairs1 = resolved */
+                 int64_t reads_removed, entries_removed;               /* summed over the rounds; entries: both triangles */
+                 int32_t rounds_run, reserved;
+                 float   ms_total, ms_compact; } elba_star_stats;
+int  elba_resolve_stars(elba_ctx *ctx, const elba_star_cfg *cfg, elba_star_stats *stats);
 
 /* Read pileups and chimera flags: PileupVector / GetReadPileup / GetTrimmedInterval (src/PruneChimeras.cpp:14-69,108-158,
  * include/PruneChimeras.hpp), which src/main.cpp never calls, and R->PruneFull(x, x) of the reads it flags.  Runs after elba_align_seeds,
