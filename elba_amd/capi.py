@@ -69,6 +69,18 @@ class IngestStats(C.Structure):
     _fields_ = [("nreads", C.c_int64), ("bases", C.c_int64), ("packed_bytes", C.c_int64), ("chunk_bytes", C.c_int64), ("ms_total", C.c_float), ("ms_encode", C.c_float)]
 
 
+class TextCfg(C.Structure):
+    _fields_ = [("format", C.c_int32), ("flags", C.c_int32), ("first_global_id", C.c_int64)]
+
+
+class TextStats(C.Structure):
+    _fields_ = [("nreads", C.c_int64), ("bases", C.c_int64), ("packed_bytes", C.c_int64), ("chunk_bytes", C.c_int64), ("lines", C.c_int64),
+                ("format", C.c_int32), ("reserved", C.c_int32), ("ms_total", C.c_float), ("ms_index", C.c_float), ("ms_encode", C.c_float)]
+
+
+TEXT_FORMATS = {"auto": 0, "fasta": 1, "fastq": 2}      # ELBA_TEXT_AUTO / _FASTA / _FASTQ
+
+
 class AlignStats(C.Structure):
     _fields_ = [("nalignments", C.c_int64), ("seeds_rejected", C.c_int64), ("passed", C.c_int64), ("contained", C.c_int64),
                 ("extensions_strided", C.c_int64), ("cells", C.c_int64), ("ms_total", C.c_float), ("ms_extend", C.c_float)]
@@ -229,6 +241,7 @@ EXPORTED_SYMBOLS = [
     "elba_read_pileup", "elba_export_pileup", "elba_free_pileup", "elba_prune_reads",
     "elba_trim_reads", "elba_export_trim_map", "elba_free_trim_map", "elba_get_trimmed_reads_device", "elba_adopt_trimmed_reads",
     "elba_clip_tips", "elba_pop_bubbles", "elba_cut_weak_overlaps", "elba_cut_bridges", "elba_resolve_stars",
+    "elba_set_reads_text", "elba_export_read_index",
 ]
 
 _lib = None
@@ -265,6 +278,8 @@ def load_library():
     L.elba_set_reads_device.restype = i32; L.elba_set_reads_device.argtypes = [vp, vp, i64, vp, vp, i64, i64]
     L.elba_set_reads_fasta.restype = i32; L.elba_set_reads_fasta.argtypes = [vp, vp, i64, C.c_uint64, vp, i64, i64, C.POINTER(IngestStats)]
     L.elba_export_reads.restype = i32; L.elba_export_reads.argtypes = [vp, vp, i64, vp, vp, i64]
+    L.elba_set_reads_text.restype = i32; L.elba_set_reads_text.argtypes = [vp, vp, i64, C.c_uint64, C.POINTER(TextCfg), C.POINTER(TextStats)]
+    L.elba_export_read_index.restype = i32; L.elba_export_read_index.argtypes = [vp, vp, vp, vp, i64]
     L.elba_count_kmers.restype = i32; L.elba_count_kmers.argtypes = [vp, C.POINTER(KmerStats)]
     L.elba_create_kmer_matrix.restype = i32; L.elba_create_kmer_matrix.argtypes = [vp, C.POINTER(MatrixStats)]
     L.elba_set_kmer_matrix.restype = i32; L.elba_set_kmer_matrix.argtypes = [vp, i64, i64, i64, vp, vp, vp, C.POINTER(MatrixStats)]
@@ -413,6 +428,49 @@ class Engine:
         self._check(self.L.elba_set_reads_fasta(self.h, buf.ctypes.data if buf.size else None, buf.size, chunk_file_offset, recs.ctypes.data if recs.size else None,
                                                 len(recs), first_global_id, C.byref(st)))
         return _stats(st)
+
+    def set_reads_text(self, chunk, chunk_file_offset=0, fmt="auto", first_global_id=0):
+        """Reads from raw FASTA or FASTQ text without a .fai (elba_set_reads_text): `chunk` = the file's bytes from `chunk_file_offset` on,
+        beginning at a record; the index is built and the reads are 2-bit encoded on the GPU.  fmt: "auto" (by the first byte), "fasta",
+        "fastq".  Returns the stats as a dict.  The binding keeps a reference to the chunk: export_read_index slices the names from it."""
+        buf = np.frombuffer(chunk, dtype=np.uint8) if not isinstance(chunk, np.ndarray) else np.ascontiguousarray(chunk, dtype=np.uint8)
+        cfg = TextCfg(TEXT_FORMATS[fmt], 0, first_global_id)
+        st = TextStats()
+        self._check(self.L.elba_set_reads_text(self.h, buf.ctypes.data if buf.size else None, buf.size, chunk_file_offset, C.byref(cfg), C.byref(st)))
+        self._text_chunk, self._text_chunk_offset, self._text_nreads = buf, int(chunk_file_offset), int(st.nreads)
+        return _stats(st)
+
+    def export_read_index(self):
+        """(names, recs) of the reads that came in through set_reads_text, in the shape fasta.read_fai returns: the records
+        (fasta.FAI_DTYPE, file offsets) from the library, the names sliced on the host from the chunk of that call."""
+        from .fasta import FAI_DTYPE
+        m = getattr(self, "_text_nreads", 0)      # (a stale count cannot pass: the library checks the state first)
+        recs = np.zeros(m, dtype=FAI_DTYPE); npos = np.zeros(m, dtype=np.uint64); nlen = np.zeros(m, dtype=np.uint32)
+        self._check(self.L.elba_export_read_index(self.h, recs.ctypes.data, npos.ctypes.data, nlen.ctypes.data, m))
+        raw = self._text_chunk.tobytes()
+        lo = npos.astype(np.int64) - self._text_chunk_offset
+        names = [raw[a:a + l].decode() for a, l in zip(lo.tolist(), nlen.tolist())]
+        return names, recs
+
+    def export_read_index_raw(self):
+        """(recs, name_pos, name_len) as the library keeps them (elba_export_read_index)."""
+        from .fasta import FAI_DTYPE
+        m = getattr(self, "_text_nreads", 0)      # (a stale count cannot pass: the library checks the state first)
+        recs = np.zeros(m, dtype=FAI_DTYPE); npos = np.zeros(m, dtype=np.uint64); nlen = np.zeros(m, dtype=np.uint32)
+        self._check(self.L.elba_export_read_index(self.h, recs.ctypes.data, npos.ctypes.data, nlen.ctypes.data, m))
+        return recs, npos, nlen
+
+    def set_reads_file(self, path, fmt="auto", first_global_id=0):
+        """A whole FASTA or FASTQ file through set_reads_text.  A name that ends in .gz is inflated with Python's gzip on the host:
+        there is no device inflate."""
+        if str(path).endswith(".gz"):
+            import gzip
+            with gzip.open(path, "rb") as f:
+                data = f.read()
+        else:
+            with open(path, "rb") as f:
+                data = f.read()
+        return self.set_reads_text(data, 0, fmt, first_global_id)
 
     def export_reads(self, nreads, packed_bytes):
         packed = np.zeros(packed_bytes + 16, dtype=np.uint8); off = np.zeros(nreads, dtype=np.uint64); ln = np.zeros(nreads, dtype=np.uint32)

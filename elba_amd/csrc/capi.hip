@@ -150,6 +150,16 @@ int elba_set_reads_fasta(elba_ctx *ctx, const char *chunk, int64_t chunk_bytes, 
     return guarded(ctx, [&](Ctx &c) { stage_set_reads_fasta(c, chunk, chunk_bytes, chunk_file_offset, recs, nreads, first_global_id, stats); });
 }
 
+int elba_set_reads_text(elba_ctx *ctx, const char *chunk, int64_t chunk_bytes, uint64_t chunk_file_offset, const elba_text_cfg *cfg, elba_text_stats *stats)
+{
+    return guarded(ctx, [&](Ctx &c) { stage_set_reads_text(c, chunk, chunk_bytes, chunk_file_offset, cfg, stats); });
+}
+
+int elba_export_read_index(elba_ctx *ctx, elba_fasta_record_t *recs, uint64_t *name_pos, uint32_t *name_len, int64_t nreads_capacity)
+{
+    return guarded(ctx, [&](Ctx &c) { stage_export_read_index(c, recs, name_pos, name_len, nreads_capacity); });
+}
+
 int elba_export_reads(elba_ctx *ctx, uint8_t *packed, int64_t packed_capacity, uint64_t *byte_off, uint32_t *len, int64_t nreads_capacity)
 {
     return guarded(ctx, [&](Ctx &c) {
@@ -796,6 +806,8 @@ int elba_get_stat(elba_ctx *ctx, const char *name, int64_t *value)
         else if (!strcmp(name, "spgemm_prep_us")) *value = c.prep_us;      // (option "measure_prep"; -1: not measured — the option was off, or the path taken has no emit kernels of its own)
         else if (!strcmp(name, "emit_us")) *value = c.emit_us;
         else if (!strcmp(name, "triples_path")) *value = c.triples_path;
+        else if (!strcmp(name, "text_tile_bytes")) *value = TEXT_TILE_BYTES;      // constants of elba_set_reads_text: the bytes of a tile of its two passes over the chunk,
+        else if (!strcmp(name, "text_scan_span")) *value = scan_block_span();      // and the elements beyond which its scans recurse (tests size their inputs from them)
         else if (!strcmp(name, "padded_columns")) *value = has(c.v, P_A) && c.use_ell ? 1 : 0;
         else if (!strcmp(name, "gather_slots")) *value = has(c.v, P_A) && c.use_ell ? c.ell_nslots : 0;
         else if (!strcmp(name, "contig_count")) *value = has(c.v, P_S, P_CONTIGS) ? c.cstats.contigs : 0;          // the last elba_generate_contigs (0: none valid — the condition of the contig exports)

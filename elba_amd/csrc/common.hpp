@@ -143,6 +143,7 @@ void fill_u64(hipStream_t s, uint64_t *p, uint64_t v, int64_t n);
 // ptr[k] = first index z with keys[z] >= k, for k in [0, nkeys]; keys ascending (sorted group ids -> CSR/CSC pointers)
 void group_offsets_u32(hipStream_t s, const uint64_t *sorted_keys, int key_shift, int64_t n, uint32_t *ptr, int64_t nkeys);
 uint64_t reduce_max_u64(hipStream_t s, const uint64_t *p, int64_t n, DevBuf &tmp);   // synchronises
+int64_t scan_block_span();      // elements one workgroup of the scans covers: beyond it they recurse (elba_get_stat "text_scan_span")
 
 // ---- tuning and A/B switches (elba_set_option) --------------------------------------------------------------------------
 // Every default is the production path and none of them changes a result: the alternatives are kept for measurements and for the parity
@@ -216,6 +217,11 @@ struct Ctx {
     uint32_t max_read_len = 0;             // longest read (set by stage_count_kmers)
     std::vector<uint32_t> h_len;           // host copy of lengths (instance offsets are a host-side prefix sum)
     std::vector<uint64_t> h_byte_off;
+    // the index of reads that came in as text (text_index.hip): .fai records and name extents, device and host copy.  It belongs to the read
+    // set like its lengths: tx_index is true only while the reads of that elba_set_reads_text call are the context's (reads_replaced)
+    bool tx_index = false;
+    DevBuf tx_recs, tx_name_pos, tx_name_len;      // elba_fasta_record_t[nreads], u64[nreads], u32[nreads]
+    std::vector<elba_fasta_record_t> tx_h_recs; std::vector<uint64_t> tx_h_name_pos; std::vector<uint32_t> tx_h_name_len;
 
     // k-mer stage results (device)
     int triples_path = 0; // diagnostic: how the last elba_set_kmer_matrix_device built the matrix — 0 radix sorts of the whole matrix (matrix.hip), 1 the k-mer stage's bucket kernels (kmer_msd.hip)
@@ -402,6 +408,7 @@ inline void reads_replaced(Ctx &c, Event ev)
 {
     done(c.v, ev);
     if (c.A_has_kmers) done(c.v, EV_MATRIX_OF_OLD_READS);
+    c.tx_index = false;      // (elba_set_reads_text sets it again behind this call)
 }
 
 // The pairs the string graph is built from — what elba_transitive_reduction, elba_read_pileup and elba_prune_reads read: a loaded edge
@@ -431,6 +438,11 @@ inline ReadSource read_source(Ctx &c, int64_t M, const char *who, const char *wh
 // ---- stages -----------------------------------------------------------------------------------------------------
 void stage_set_reads_fasta(Ctx &c, const char *chunk, int64_t chunk_bytes, uint64_t chunk_file_offset, const elba_fasta_record_t *recs, int64_t nreads,
                            int64_t first_global_id, elba_ingest_stats *stats);      // ingest.hip
+void launch_fasta_encode(Ctx &c, const uint8_t *d_chunk, uint64_t chunk_file_offset, uint64_t chunk_bytes, const elba_fasta_record_t *d_recs, const uint64_t *d_byte_off,
+                         int64_t nreads, uint8_t *d_packed);      // ingest.hip: k_fasta_encode on records that are on the device already (nreads > 0)
+constexpr uint32_t TEXT_TILE_BYTES = 4096;                        // text_index.hip: bytes of the chunk one workgroup takes per trip (elba_get_stat "text_tile_bytes")
+void stage_set_reads_text(Ctx &c, const char *chunk, int64_t chunk_bytes, uint64_t chunk_file_offset, const elba_text_cfg *cfg, elba_text_stats *stats);      // text_index.hip
+void stage_export_read_index(Ctx &c, elba_fasta_record_t *recs, uint64_t *name_pos, uint32_t *name_len, int64_t nreads_capacity);
 void stage_count_kmers(Ctx &c);                                   // kmer.hip
 void stage_create_kmer_matrix(Ctx &c);                            // kmer.hip
 bool msd_matrix_from_triples(Ctx &c, int64_t M, int64_t N, int64_t Z, const int64_t *d_rows, const int64_t *d_cols, const uint32_t *d_vals);   // kmer_msd.hip: false = matrix.hip sorts

@@ -90,6 +90,14 @@ __global__ __launch_bounds__(ENC_THREADS) void k_fasta_encode(const uint8_t *chu
 
 }  // namespace
 
+void launch_fasta_encode(Ctx &c, const uint8_t *d_chunk, uint64_t chunk_file_offset, uint64_t chunk_bytes, const elba_fasta_record_t *d_recs, const uint64_t *d_byte_off,
+                         int64_t nreads, uint8_t *d_packed)
+{
+    const int64_t nb = nreads < (int64_t)c.num_cus * 16 ? nreads : (int64_t)c.num_cus * 16;
+    hipLaunchKernelGGL(k_fasta_encode, dim3((unsigned)nb), dim3(ENC_THREADS), 0, c.stream, d_chunk, chunk_file_offset, chunk_bytes, d_recs, d_byte_off, (uint32_t)nreads, d_packed);
+    ELBA_HIP(hipGetLastError());
+}
+
 void stage_set_reads_fasta(Ctx &c, const char *chunk, int64_t chunk_bytes, uint64_t chunk_file_offset, const elba_fasta_record_t *recs, int64_t nreads,
                            int64_t first_global_id, elba_ingest_stats *stats)
 {
@@ -124,11 +132,8 @@ void stage_set_reads_fasta(Ctx &c, const char *chunk, int64_t chunk_bytes, uint6
         ELBA_HIP(hipMemcpyAsync(c.own_byte_off.p, off.data(), (size_t)nreads * 8, hipMemcpyHostToDevice, s));
         ELBA_HIP(hipMemcpyAsync(c.own_len.p, len.data(), (size_t)nreads * 4, hipMemcpyHostToDevice, s));
         c.t_a.start(s);
-        int64_t nb = nreads < (int64_t)c.num_cus * 16 ? nreads : (int64_t)c.num_cus * 16;
-        hipLaunchKernelGGL(k_fasta_encode, dim3((unsigned)nb), dim3(256), 0, s, d_chunk.as<uint8_t>(), chunk_file_offset, (uint64_t)chunk_bytes, d_recs.as<elba_fasta_record_t>(),
-                           c.own_byte_off.as<uint64_t>(), (uint32_t)nreads, c.own_packed.as<uint8_t>());
+        launch_fasta_encode(c, d_chunk.as<uint8_t>(), chunk_file_offset, (uint64_t)chunk_bytes, d_recs.as<elba_fasta_record_t>(), c.own_byte_off.as<uint64_t>(), nreads, c.own_packed.as<uint8_t>());
         c.t_a.stop(s);
-        ELBA_HIP(hipGetLastError());
     }
     c.t_total.stop(s);
     ELBA_HIP(hipStreamSynchronize(s));

@@ -432,6 +432,8 @@ __global__ __launch_bounds__(256) void k_rowptr_close_c(uint32_t *rowptr, int64_
 
 }  // namespace
 
+int64_t scan_block_span() { return SCAN_TILE; }
+
 void exclusive_scan_u32(hipStream_t s, const uint32_t *in, uint32_t *out, int64_t n, DevBuf &tmp)
 {
     tmp.reserve(scan_tmp_elems(n) * sizeof(uint64_t));

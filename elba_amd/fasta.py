@@ -49,6 +49,15 @@ def write_fai(fasta_path, fai_path=None):
     return fai_path
 
 
+def write_fai_from_index(names, recs, path):
+    """The .fai of reads indexed on the device (Engine.export_read_index): name, len, pos, bases and width = bases + 1 per line, which
+    read_fai gives back as the same (names, records)."""
+    with open(path, "w") as f:
+        for name, r in zip(names, recs):
+            f.write("%s\t%d\t%d\t%d\t%d\n" % (name, int(r["len"]), int(r["pos"]), int(r["bases"]), int(r["bases"]) + 1))
+    return path
+
+
 def chunk_bounds(recs, file_size):
     """[startpos, endpos) of the file bytes holding `recs` (consecutive records): src/FastaIndex.cpp:222-224."""
     first, last = recs[0], recs[-1]

@@ -13,6 +13,8 @@
 //   create_seed_matrix   include/SharedSeeds.hpp:98-99                same name -> elba::SeedMatrix
 //   FastaIndex           include/FastaIndex.hpp, src/FastaIndex.cpp          same name: .fai records, base-balanced partition, chunk bounds;
 //                                                                             the reads are 2-bit encoded on the GPU (elba_set_reads_fasta)
+//   (none: the reference reads only indexed FASTA)                            elba::set_reads_text(engine, path): FASTA or FASTQ text without a .fai,
+//                                                                             indexed and encoded on the GPU (elba_set_reads_text)
 //   PairwiseAlignment    include/PairwiseAlignment.hpp, src/PairwiseAlignment.cpp:5-106     same name -> elba::OverlapMatrix (triples of elba::Overlap)
 //   Bmat.seqptr()->getnnz() / GetDCSC()  src/PairwiseAlignment.cpp:16-19   SeedMatrix::seqptr()->getnnz() / GetDCSC()
 //   find_bad_reads / find_contained_reads / TransitiveReduction   src/main.cpp:305-312, src/TransitiveReduction.cpp:3-90
@@ -33,6 +35,7 @@
 #include <algorithm>
 #include <cstring>
 #include <fstream>
+#include <iterator>
 #include <ostream>
 #include <memory>
 #include <sstream>
@@ -306,6 +309,37 @@ inline std::unique_ptr<KmerCountMap> get_kmer_count_map_keys(const FastaIndex &i
     if (ingest) *ingest = is;
     map->engine->check(elba_count_kmers(map->engine->ctx, &map->stats));
     return map;
+}
+
+// Reads from a FASTA or FASTQ file that has no .fai: the whole file goes to the GPU as text, the index is built there (elba_set_reads_text)
+// and comes back with the reads — the names (sliced here from the file's bytes), the .fai records, and the reads in DnaBuffer layout as
+// index.getmydna() would have left them.  Mirrors Engine.set_reads_file / export_read_index of the Python binding; a .gz is not inflated here.
+struct TextReads {
+    std::vector<std::string> names;
+    std::vector<elba_fasta_record_t> records;
+    DnaBuffer reads;
+    elba_text_stats stats{};
+};
+inline TextReads set_reads_text(detail::Engine &engine, const std::string &path, int format = ELBA_TEXT_AUTO, int64_t first_global_id = 0)
+{
+    std::ifstream in(path, std::ios::binary);
+    if (!in) throw Error(ELBA_ERR_INVALID_ARG, "cannot open " + path);
+    const std::string text((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
+    elba_text_cfg cfg{};
+    cfg.format = format; cfg.first_global_id = first_global_id;
+    TextReads out;
+    engine.check(elba_set_reads_text(engine.ctx, text.data(), (int64_t)text.size(), 0, &cfg, &out.stats));
+    const size_t m = (size_t)out.stats.nreads;
+    std::vector<uint64_t> name_pos(m), off(m);
+    std::vector<uint32_t> name_len(m), len(m);
+    std::vector<uint8_t> buf((size_t)out.stats.packed_bytes);
+    out.records.resize(m);
+    engine.check(elba_export_read_index(engine.ctx, out.records.data(), name_pos.data(), name_len.data(), (int64_t)m));
+    engine.check(elba_export_reads(engine.ctx, buf.data(), out.stats.packed_bytes, off.data(), len.data(), (int64_t)m));
+    out.names.reserve(m);
+    for (size_t i = 0; i < m; ++i) out.names.emplace_back(text, (size_t)name_pos[i], (size_t)name_len[i]);
+    out.reads = DnaBuffer::from_packed(std::move(buf), std::move(off), std::move(len));
+    return out;
 }
 
 inline void get_kmer_count_map_values(const DnaBuffer &, KmerCountMap &kmermap, std::shared_ptr<Grid>)

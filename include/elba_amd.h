@@ -245,6 +245,37 @@ int  elba_set_reads_device(elba_ctx *ctx, const void *d_packed, int64_t packed_b
  * and become the context's reads, as after elba_set_reads. */
 int  elba_set_reads_fasta(elba_ctx *ctx, const char *chunk, int64_t chunk_bytes, uint64_t chunk_file_offset,
                           const elba_fasta_record_t *recs, int64_t nreads, int64_t first_global_id, elba_ingest_stats *stats);
+/* Reads from raw FASTA or FASTQ text, without a .fai: the index is built on the device (elba_amd/csrc/text_index.hip) and
+ * the call ends where elba_set_reads_fasta ends — the reads 2-bit encoded (the same kernel: N/n as A, any other character code 4 ORed in
+ * truncated to 8 bits) as the context's own, in DnaBuffer layout.  `chunk` = chunk_bytes bytes of the file from offset chunk_file_offset
+ * on, beginning at a record; cfg NULL = ELBA_TEXT_AUTO (first byte '>' FASTA, '@' FASTQ; an empty chunk: FASTA, no reads), first id 0.
+ * Lines end at '\n'.  FASTA: a line that begins with '>' starts a record; pos = the offset behind the header's newline (the chunk's end
+ * when there is none), len = the record's bytes without its newlines, bases = the length of its first sequence line (1 when len is 0);
+ * the line lengths of a record must read bases, .., bases, t, 0, .., 0 with 0 <= t <= bases (trailing empty lines are allowed, a blank
+ * line in the middle is not).  FASTQ: four lines per record — '@' header, sequence, '+' line, quality of the sequence's length; the
+ * rank of a line decides its role, quality values are not kept, bases = max(len, 1).  A name begins behind the '>' / '@' and ends at the
+ * first space, tab, VT, FF or the line's end.  ELBA_ERR_INVALID_ARG: a '\r' anywhere, a first byte that is neither '>' nor '@', a line
+ * that breaks the shape, a FASTQ line count that is no multiple of 4, a missing '@' or '+', a quality line of another length, a read of
+ * 0x7FFFFFF0 bases or more — of several violations the one with the smallest file offset is reported (the offending byte for '\r', the
+ * line's start otherwise, the record's header for a quality length), and elba_last_error names its kind, record and file offset.
+ * ELBA_ERR_UNSUPPORTED: 2^32-1 lines or reads, or more.  A rejected call leaves the previous reads and their index in place; as a
+ * rejected elba_set_reads_fasta, it still invalidates the pileup and the trimmed reads.
+ * elba_export_read_index: the .fai records and the name extents of the reads (pos and name_pos are file offsets, chunk_file_offset
+ * included; caller-allocated arrays of nreads_capacity >= nreads entries, any pointer may be NULL).  The index belongs to the read set:
+ * ELBA_ERR_STATE unless the context's reads are those of an elba_set_reads_text call (any other elba_set_reads*, or
+ * elba_adopt_trimmed_reads, has replaced them).  elba_get_stat "text_tile_bytes" / "text_scan_span": the tile of the two passes over
+ * the chunk and the span of one scan workgroup (constants; tests size inputs from them). */
+enum { ELBA_TEXT_AUTO = 0, ELBA_TEXT_FASTA = 1, ELBA_TEXT_FASTQ = 2 };
+typedef struct { int32_t format, flags /* 0 */; int64_t first_global_id; } elba_text_cfg;
+typedef struct {
+    int64_t nreads, bases, packed_bytes, chunk_bytes, lines;
+    int32_t format, reserved;     /* format: ELBA_TEXT_FASTA or ELBA_TEXT_FASTQ, as decided */
+    float   ms_total;             /* H2D copy of the chunk + index + encode + D2H of the index */
+    float   ms_index;             /* count pass .. scan of the byte offsets, the first read-back included */
+    float   ms_encode;            /* the encode kernel alone */
+} elba_text_stats;
+int  elba_set_reads_text(elba_ctx *ctx, const char *chunk, int64_t chunk_bytes, uint64_t chunk_file_offset, const elba_text_cfg *cfg, elba_text_stats *stats);
+int  elba_export_read_index(elba_ctx *ctx, elba_fasta_record_t *recs, uint64_t *name_pos, uint32_t *name_len, int64_t nreads_capacity);
 /* The resident reads back on the host in DnaBuffer layout: packed[packed_bytes], byte_off[nreads], len[nreads] (caller-allocated;
  * any pointer may be NULL to skip it).  Sizes: elba_ingest_stats, or nreads and sum((len+3)/4). */
 int  elba_export_reads(elba_ctx *ctx, uint8_t *packed, int64_t packed_capacity, uint64_t *byte_off, uint32_t *len, int64_t nreads_capacity);
@@ -765,7 +796,10 @@ int  elba_set_option(elba_ctx *ctx, const char *name, int64_t value);
  *   "emit_us"                ... and the emit kernels as built
  *   "contig_count", "contig_cycles", "contig_circular", "contig_singletons", "contig_reads", "contig_bases", "contig_branches"
  *                            the last elba_generate_contigs[_ex], under the condition of the contig exports: 0 when the string graph or its
- *                            contigs are not valid ("contig_rank_us": -1) */
+ *                            contigs are not valid ("contig_rank_us": -1)
+ *   "text_tile_bytes", "text_scan_span"
+ *                            constants of elba_set_reads_text: the bytes of the chunk one workgroup takes per trip of its two passes, and the
+ *                            elements one workgroup of its scans covers (longer arrays make the scan recurse) */
 int  elba_get_stat(elba_ctx *ctx, const char *name, int64_t *value);
 
 /* Gives the stage calls' scratch memory back to the device (the sort / partition buffers of elba_count_kmers, elba_create_kmer_matrix and
