@@ -1,6 +1,7 @@
 // capi.hip — the extern "C" surface declared in include/elba_amd.h.  Every entry point converts elba::Error into a status
 // code + elba_last_error text; nothing here computes on the CPU except index bookkeeping of exported copies.
 #include "common.hpp"
+#include "ov_plan.hpp"
 #include <new>
 
 using namespace elba;
@@ -803,7 +804,23 @@ int elba_get_stat(elba_ctx *ctx, const char *name, int64_t *value)
         else if (!strcmp(name, "overlap_passes")) *value = c.ov_passes;      // passes the last create_seed_matrix took (1: no repeat; set also when the call failed)
         else if (!strcmp(name, "overlap_spec")) *value = c.ov_spec;      // 1: the last create_seed_matrix ran the reads-path instantiation of the numeric kernel (ov_plan.hpp: ov_spec_ok), 0: the general one
         else if (!strcmp(name, "overlap_forwarded")) *value = c.ov_forwarded;      // rows the last create_seed_matrix forwarded to a larger tier on a prediction, all passes
-        else if (!strcmp(name, "spgemm_prep_us")) *value = c.prep_us;      // (option "measure_prep"; -1: not measured — the option was off, or the path taken has no emit kernels of its own)
+        // where the rows of the last create_seed_matrix went (its final pass) and on which shape of A it ran: read-only, for tests that place a row on a constant
+        else if (!strncmp(name, "overlap_tier_limit_", 19) && name[19] >= '0' && name[19] < '0' + NUM_LDS_TIERS && !name[20]) *value = c.ov_tier_limit[name[19] - '0'];
+        else if (!strncmp(name, "overlap_tier_queued_", 20) && name[20] >= '0' && name[20] < '0' + NUM_TIERS && !name[21]) *value = c.ov_tier_queued[name[20] - '0'];
+        else if (!strncmp(name, "overlap_tier_done_", 18) && name[18] >= '0' && name[18] < '0' + NUM_TIERS && !name[19]) *value = c.ov_tier_done[name[18] - '0'];
+        else if (!strcmp(name, "overlap_sort_rows_bucket")) *value = c.ov_sort_rows[0];
+        else if (!strcmp(name, "overlap_sort_rows_huge")) *value = c.ov_sort_rows[1];
+        else if (!strcmp(name, "overlap_family")) *value = c.ov_family;
+        else if (!strcmp(name, "overlap_pay16")) *value = c.ov_pay16;
+        else if (!strcmp(name, "overlap_rec16")) *value = c.ov_rec16_used;
+        else if (!strcmp(name, "matrix_col_stride")) *value = has(c.v, P_A) && c.use_ell ? (int64_t)c.s_stride : 0;
+        else if (!strcmp(name, "matrix_fbits")) *value = has(c.v, P_A) ? (int64_t)c.fbits : 0;
+        else if (!strcmp(name, "matrix_pos16")) *value = has(c.v, P_A) && c.pos16 ? 1 : 0;
+        else if (!strcmp(name, "matrix_hints")) *value = has(c.v, P_A) && c.csr_hints ? 1 : 0;
+        else if (!strcmp(name, "matrix_inline")) *value = has(c.v, P_A) && c.csr_inline ? 1 : 0;
+        else if (!strcmp(name, "matrix_suffix")) *value = has(c.v, P_A) && c.csr_suffix ? 1 : 0;
+        else if (!strcmp(name, "matrix_csr_words")) *value = has(c.v, P_A) && c.csr_one_word ? 1 : 0;
+        else if (!strcmp(name, "spgemm_prep_us")) *value = c.prep_us;     // (option "measure_prep"; -1: not measured — the option was off, or the path taken has no emit kernels of its own)
         else if (!strcmp(name, "emit_us")) *value = c.emit_us;
         else if (!strcmp(name, "triples_path")) *value = c.triples_path;
         else if (!strcmp(name, "text_tile_bytes")) *value = TEXT_TILE_BYTES;      // constants of elba_set_reads_text: the bytes of a tile of its two passes over the chunk,

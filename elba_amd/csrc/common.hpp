@@ -251,6 +251,7 @@ struct Ctx {
     // fetches no column for it (58 % of its gathers on BASELINE config 3).  Such an entry has no k-mer id: exports rebuild CSR from the columns.
     bool csr_inline = false;
     bool csr_inline_window = false;      // ... written for a matrix with a row window (option "panel_inline"): valid under the parity rule over all rows only, i.e. for calls with the mirror exchange
+    bool csr_one_word = false;  // diagnostic (elba_get_stat "matrix_csr_words"): the one-word CSR sort built the rows of the resident A, not the key/value pair sort
     bool csr_suffix = false;  // dense matrices: a_csr entries are kid << 32 | column length << 23 | own place in the column << 16 | pos, pairs owned by the smaller row (matrix.hip)
     DevBuf ov_sample;         // u32[256]: the rows a cold SpGEMM call computes first (spgemm.hip)
     int64_t A_products = 0;   // sum over the window's row entries of their column's length (what the SpGEMM reports as `products`)
@@ -386,6 +387,10 @@ struct Ctx {
     uint32_t ov_slab_q16_used = 0;  // diagnostic: the ratio the last call's slabs were sized by (margin included), 0 = none
     int64_t ov_mir_placed = 0;      // diagnostic: mirrored entries of the last call that did NOT go to a slab (placed by k_mirror)
     int64_t ov_spec = 0;            // diagnostic: the last call's numeric kernels were the reads-path instantiation (1) or the general one (0)
+    // diagnostics of the last create_seed_matrix, from its final pass (elba_get_stat "overlap_tier_*", "overlap_sort_rows_*", "overlap_family", "overlap_pay16",
+    // "overlap_rec16"): the plan's claim limits, the rows queued / completed per tier, the rows the two wide-row sorts took, the kernel family and record format
+    int64_t ov_tier_limit[5] = {0, 0, 0, 0, 0}, ov_tier_queued[6] = {0, 0, 0, 0, 0, 0}, ov_tier_done[6] = {0, 0, 0, 0, 0, 0}, ov_sort_rows[2] = {0, 0};
+    int64_t ov_family = 0, ov_pay16 = 0, ov_rec16_used = 0;
     int64_t ov_passes = 0, ov_forwarded = 0;      // diagnostic: passes the last call took (1 = no repeat); rows its numeric kernels forwarded on a prediction (spgemm_direct.hpp)
     // sharded call with mirror exchange (spgemm.hip: stage_seed_matrix_begin / _fill / _end)
     int ov_phase = 0;               // 1: begin has run (numeric done, staged records waiting), end not yet

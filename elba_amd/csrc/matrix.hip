@@ -116,7 +116,7 @@ __global__ void k_unpack_csr_words(const uint64_t *words, int64_t Z, int nb, int
     const int64_t cur = z < Z ? (int64_t)((w >> rs) & rmask) : M;
     for (int64_t k = prev + 1; k <= cur; ++k) rowptr[k] = (uint32_t)z;
     if (z < Z) {
-        if (w >> 63) {      // inline partner (Ctx::csr_inline): flag | partner >> 1 | posQ | posT << 16
+        if (pbi && (w >> 63)) {      // inline partner (Ctx::csr_inline): flag | partner >> 1 | posQ | posT << 16.  (pbi 0: no word is one, and bit 63 belongs to the read when the fields fill all 64 bits)
             const uint64_t pm = (1ull << pbi) - 1;
             csr[z] = (1ull << 63) | (((w >> (2 * pbi)) & ((1ull << (mb - 1)) - 1)) << 32) | ((w >> pbi) & pm) | ((w & pm) << 16);
         } else csr[z] = (((w >> (pb + 2)) & ((1ull << nb) - 1)) << 32) | (((w >> pb) & 3ull) << 30) | (w & ((1ull << pb) - 1));
@@ -353,7 +353,8 @@ void finish_matrix_from_sorted_csc(Ctx &c, int64_t M, int64_t N, int64_t Z, cons
         hints = false;
         c.j_shift = c.max_col_nnz <= 32 ? 5u : 6u;      // (use_ell: no column longer than 64)
     }
-    if (!c.csr_suffix && mb + nb + pb + 2 <= 64 && !c.opt.csr_pairs) {
+    c.csr_one_word = !c.csr_suffix && mb + nb + pb + 2 <= 64 && !c.opt.csr_pairs;      // (diagnostic: which of the two CSR sorts builds the rows)
+    if (c.csr_one_word) {
         const bool have_words = pre && c.pre_words && c.pre_nb == nb && c.pre_pb == pb;
         uint64_t *w0 = have_words ? c.csr_words.as<uint64_t>() : c.ws_a.as<uint64_t>(), *w1 = c.ws_c.as<uint64_t>();
         ELBA_REQUIRE(!pre || have_words, ELBA_ERR_INTERNAL, "create_kmer_matrix: the sort keys of the k-mer stage do not match the matrix");

@@ -1035,6 +1035,8 @@ static void ov_numeric(OvRun &r)
 {
     Ctx &c = r.c;
     c.ov_spec = r.plan.nrows > 0 && r.plan.spec ? 1 : 0;
+    for (int t = 0; t < NUM_LDS_TIERS; ++t) c.ov_tier_limit[t] = (int64_t)r.plan.tier_limit[t];      // (diagnostics: the plan of this pass — the last pass's stand)
+    c.ov_family = (int64_t)r.plan.family; c.ov_pay16 = r.plan.pay16 ? 1 : 0; c.ov_rec16_used = r.plan.mir16 ? 1 : 0;
     for (int t = 0; t < NUM_TIERS; ++t)
         if ((r.plan.launched >> t) & 1u) ov_launch(OvRowSeq{}, r.plan.tier[t], r.plan, r.p, c.stream, 0u);
     if (r.plan.nrows > 0) ELBA_HIP(hipGetLastError());
@@ -1147,6 +1149,8 @@ static void ov_finish(Ctx &c, OvCounters &hc, int passes, bool was_timed, float 
     c.ov_sort_used[0] = h.sort_used[0]; c.ov_sort_used[1] = h.sort_used[1];
     c.ov_slab_q16 = h.slab_q16; c.ov_prior_q16 = h.prior_q16;
     c.ov_mir_placed = (int64_t)hc.mir_placed;
+    for (int t = 0; t < NUM_TIERS; ++t) { c.ov_tier_queued[t] = (int64_t)hc.tier_count[t]; c.ov_tier_done[t] = (int64_t)hc.tier_done[t]; }
+    c.ov_sort_rows[0] = (int64_t)hc.fin_count[0]; c.ov_sort_rows[1] = (int64_t)hc.fin_count[1];
     c.ov_slab_q16_used = hc.slab_q16;
     st.products = c.ov_hints_used ? c.A_products : (int64_t)hc.products;      // (entries that skip their column do not see its length: counted when A was built)
     st.nnz_before_prune = (int64_t)hc.yraw;

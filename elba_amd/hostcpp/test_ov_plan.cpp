@@ -458,9 +458,37 @@ static void test_table()
     for (OvFamily f : {OV_DENSE, OV_PAY, OV_S32}) for (int t = 0; t < NUM_TIERS; ++t) for (int up = 0; up <= 3; ++up) CHECK(ov_row_of(f, t, up) >= 0, "family %d tier %d", (int)f, t);
 }
 
+// ---- the tier limits as literals ----------------------------------------------------------------------------------------------------------------
+// tests/spgemm_edge_cases.py (TIER_LIMITS) restates these numbers and builds rows with limit - 1, limit and limit + 1 owned partners from them
+static void test_tier_limit_literals()
+{
+    const char *redo = "the tier geometry changed: re-derive TIER_LIMITS / TIER_BLOCKS of tests/spgemm_edge_cases.py and its tier_case / guaranteed_case";
+    auto same = [&](const char *what, const OvInput &in, OvFamily family, bool pay16, std::initializer_list<uint32_t> want) {
+        const OvPlan p = plan_ov(in);
+        CHECK(p.family == family && p.pay16 == pay16, "%s: family %d pay16 %d — %s", what, (int)p.family, (int)p.pay16, redo);
+        int t = 0;
+        for (uint32_t w : want) { CHECK(p.tier_limit[t] == w, "%s: tier_limit[%d] = %u, the tests hold %u — %s", what, t, p.tier_limit[t], w, redo); ++t; }
+        CHECK(t == NUM_LDS_TIERS && LDS_TBITS0 == 9, "%s: %d LDS tiers from 2^%d slots — %s", what, NUM_LDS_TIERS, LDS_TBITS0, redo);
+    };
+    OvInput in = reads_in(); in.pos16 = false; in.csr_inline = false;
+    same("s32", in, OV_S32, false, {383u, 767u, 1535u, 3071u, 6143u});
+    in = reads_in(); in.opt.tune3 = 1;
+    same("pay", in, OV_PAY, false, {383u, 767u, 1535u, 3071u, 6143u});
+    in = reads_in();
+    same("pay16", in, OV_S32, true, {383u, 767u, 1535u, 3071u, 6143u});
+    in = dense_in(); in.opt.dense_up = 0;
+    same("dense0", in, OV_DENSE, false, {255u, 767u, 1535u, 3071u, 6143u});
+    in.opt.dense_up = 1;
+    same("dense1", in, OV_DENSE, false, {255u, 511u, 1535u, 3071u, 6143u});
+    in.opt.dense_up = 2;
+    same("dense2", in, OV_DENSE, false, {255u, 511u, 1023u, 3071u, 6143u});
+    CHECK(FIN_WAVE2_MAX == 1024u && SLAB_PAD == 16u && RP_TILE == 1024, "finalize constants — %s (widths_case, slab_case, rowptr_case)", redo);
+}
+
 int main()
 {
     test_table();
+    test_tier_limit_literals();
     test_named_shapes();
     test_random_shapes();
     test_hints();

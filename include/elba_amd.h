@@ -791,6 +791,22 @@ int  elba_set_option(elba_ctx *ctx, const char *name, int64_t value);
  *                            of buckets that took a crowded path
  *   "overlap_passes"         passes the last elba_create_seed_matrix call took (1: no repeat; also set when the call failed)
  *   "overlap_forwarded"      rows that call forwarded to a larger table tier on its in-call prediction (cold calls without a sample), all passes
+ *   "overlap_tier_limit_0" .. "_4"   of the last elba_create_seed_matrix, from its final pass: the claimed table slots at which a row abandons LDS tier t
+ *                            (512 << t slots) for the next one — min(3/4 of the slots, slots - lanes of the tier's workgroup) - 1 for the family that ran
+ *   "overlap_tier_queued_0" .. "_5"  rows queued on tier t (5: the HBM tables) in that pass: by the classification, forwarded or handed on by the tier below
+ *   "overlap_tier_done_0" .. "_5"    rows that completed on tier t (a cold call's sample rows count on tier 3); the sums over t are rows_lds + rows_global
+ *   "overlap_sort_rows_bucket", "overlap_sort_rows_huge"
+ *                            rows of B whose columns the workgroup bucket sort (1025 .. 4096 entries) and the HBM sort (more) ordered
+ *   "overlap_family"         the kernel family of that call: 0 dense path, 1 64-bit accumulators that carry both positions, 2 32-bit accumulators
+ *   "overlap_pay16"          1: its 32-bit accumulators carried the partner's position (positions and product sequence numbers fit 16 bits)
+ *   "overlap_rec16"          1: staged and mirrored entries were 16-byte records, 0: 32-byte ones
+ *   "matrix_col_stride"      of the resident k-mer matrix: entries per column of the padded column store (0: columns are read through their pointers)
+ *   "matrix_fbits"           bits of the place-in-column field of a product sequence number
+ *   "matrix_pos16"           1: every position is below 65536
+ *   "matrix_hints", "matrix_inline", "matrix_suffix"
+ *                            1: the row entries carry ownership hints above their position (positions below 2^30) | inline partners | their
+ *                            column's length and their place in it (the dense path: some column holds more than 16 entries)
+ *   "matrix_csr_words"       1: the rows were built by the sort of one 64-bit word per entry, 0: by the sort of (row, entry) pairs
  *   "spgemm_prep_us"         option "measure_prep": device microseconds the emit kernels of the last elba_count_kmers spent on hint bits, inline partners,
  *                            gather slots and padded columns (the kernels as built minus the same kernels without them; -1: not measured)
  *   "emit_us"                ... and the emit kernels as built

@@ -7,6 +7,7 @@ import pytest
 
 import elba_amd
 import gpu_util as gu
+import spgemm_edge_cases as ec
 import synth
 import util
 from oracle import pyoracle as po
@@ -99,19 +100,55 @@ def _concat(sets):
     return np.concatenate(packed + [np.zeros(16, np.uint8)]), np.concatenate(off), np.concatenate(lens)
 
 
+def _sort_rows_equal_the_oracles_widths(e, o):
+    """the rows the two wide-row sorts of the last call took: the rows of the oracle's B of 1025 .. 4096 entries and of more"""
+    w = np.diff(o.B()["rowptr"])
+    assert (e.get_stat("overlap_sort_rows_bucket"), e.get_stat("overlap_sort_rows_huge")) == (int(((w > 1024) & (w <= 4096)).sum()), int((w > 4096).sum()))
+
+
 def test_every_table_tier_including_hbm_spill():
-    """A noisy set with very uneven read lengths (row bounds from ~10^2 to ~10^3.5: every LDS tier) plus an error-free, extremely
-    deep set whose per-row partner bound exceeds the largest LDS table (HBM spill path)."""
+    """A noisy set with very uneven read lengths plus an error-free, extremely deep set: which tiers their rows end on depends on the in-call
+    prediction (the share of partners per entry among the rows that happened to finish first), so of the reads only what holds on every run is
+    asserted — measured, their rows complete on the 512- to 4096-slot tiers and none on the 8192-slot tier or the HBM tables.  That EVERY tier
+    completes a row is asserted on the matrix of spgemm_edge_cases.every_tier_case (triples, fewer than 2^18 entries: no prediction acts): five
+    rows that own 600, 1200, 2400, 4800 and 7200 partners — more than tiers 0 .. 4 take, no more than the next one takes — start below by the
+    cold estimate and are handed on until they fit: exactly one row completes on each of tiers 1 .. 4 and on the HBM tables."""
     noisy = elba_amd.synth_reads(5, 150000, 14, 2500, 1800, error_rate=0.10, min_len=60)
     deep = elba_amd.synth_reads(15, 2000, 250, 100, 10, error_rate=0.0, min_len=60)
     packed, off, lens = _concat([noisy, deep])
     assert len(lens) > 4300
     e, ks, ms, st = gu.gpu_full(packed, off, lens, 17, 2, 600)
     assert st["rows_lds"] > 3000 and st["rows_lds"] + st["rows_global"] == int((np.diff(e.export_kmer_matrix()["rowptr"]) > 0).sum())
+    queued = [e.get_stat("overlap_tier_queued_%d" % t) for t in range(6)]
+    done = [e.get_stat("overlap_tier_done_%d" % t) for t in range(6)]
+    assert sum(done[:5]) == st["rows_lds"] and done[5] == st["rows_global"] and done[0] > 3000
+    assert sum(queued) - sum(done) == st["rows_escalated"]      # (fewer than 8192 reads: no sample rows queued apart)
     o = gu.oracle_run(packed, off, lens, 17, 2, 600, threads=8)
+    _sort_rows_equal_the_oracles_widths(e, o)
     gu.assert_A_equal(e.export_kmer_matrix(), o.A())
     gu.assert_B_equal(e.export_csr(), o.B())
     gu.assert_stats_equal(st, o)
+    e.close()
+
+    case = ec.every_tier_case()
+    assert len(case.rows) < (1 << 18)
+    o = po.Oracle(17, 2, 8)
+    o.set_triples(*case.triples)
+    o.spgemm(8)
+    e = elba_amd.Engine(17, 2, 8, options={"no_sample": 1})      # (14 700 rows: without the option a cold call computes a sample of rows first, row 0 among them)
+    e.set_kmer_matrix(*case.triples)
+    nonempty = len(np.unique(case.rows))
+    for cold in (0, 1):      # the first call on the matrix, and a call that has forgotten it
+        e.set_option("overlap_cold_calls", cold)
+        st = e.create_seed_matrix()
+        limits = [e.get_stat("overlap_tier_limit_%d" % t) for t in range(5)]
+        for t, owned in enumerate(ec.EVERY_TIER_OWNED):
+            assert limits[t] < owned and (t == 4 or owned <= limits[t + 1]), (t, owned, limits)
+        done = [e.get_stat("overlap_tier_done_%d" % t) for t in range(6)]
+        assert done == [nonempty - 5, 1, 1, 1, 1, 1], done      # every LDS tier and the HBM tables completed rows
+        assert e.get_stat("overlap_forwarded") == 0 and st["rows_global"] == 1 and st["rows_lds"] == nonempty - 1
+        gu.assert_B_equal(e.export_csr(), o.B())
+        gu.assert_stats_equal(st, o)
     e.close()
 
 
@@ -120,7 +157,9 @@ def test_wide_rows_use_block_and_global_sorts():
     packed, off, lens, info = elba_amd.synth_reads(6, 200, 2200, 100, 0, error_rate=0.0, min_len=100)
     e, ks, ms, st = gu.gpu_full(packed, off, lens, 21, 2, 20000)
     o = gu.oracle_run(packed, off, lens, 21, 2, 20000, threads=8)
-    assert np.diff(o.B()["rowptr"]).max() > 4096
+    w = np.diff(o.B()["rowptr"])
+    assert w.max() > 4096 and ((w > 1024) & (w <= 4096)).sum() > 0      # (rows for both wide-row sorts; this read set has none of 65 .. 1024 entries)
+    _sort_rows_equal_the_oracles_widths(e, o)
     gu.assert_B_equal(e.export_csr(), o.B())
     gu.assert_stats_equal(st, o)
     e.close()
@@ -135,9 +174,15 @@ def test_optimistic_tables_escalate_and_spill_to_hbm():
     e.set_kmer_matrix(M, ncol, rows, cols, vals)
     st = e.create_seed_matrix()
     assert st["rows_global"] > 0 and st["rows_escalated"] > 0
+    queued = [e.get_stat("overlap_tier_queued_%d" % t) for t in range(6)]
+    done = [e.get_stat("overlap_tier_done_%d" % t) for t in range(6)]
+    assert M >= 8192      # (a cold call computes a sample of 256 rows first: they are queued apart from the tiers and counted with the attempts)
+    assert sum(queued) + 256 - sum(done) == st["rows_escalated"] and done[5] == st["rows_global"] and sum(done) == len(np.unique(rows))
+    assert any(queued[t] > done[t] for t in range(5)) and queued[5] == done[5]      # LDS tiers handed rows on, the HBM tables completed all of theirs
     o = po.Oracle(17, 2, 8)
     o.set_triples(M, ncol, rows, cols, vals)
     o.spgemm(8)
+    _sort_rows_equal_the_oracles_widths(e, o)
     gu.assert_B_equal(e.export_csr(), o.B())
     gu.assert_stats_equal(st, o)
     e.close()
