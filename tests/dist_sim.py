@@ -116,7 +116,8 @@ def _mix64(k):
 
 
 class NumpyBackend:
-    """CPU stand-in for HipBackend (same method names and tensor conventions), for the gloo tests only."""
+    """CPU stand-in for HipBackend (same method names and tensor conventions): the gloo tests' backend, and the author of the scripted worlds of
+    dist_step_cases.py that the device calls are compared with one by one."""
 
     def __init__(self, k, lower, upper):
         self.k, self.lower, self.upper = k, lower, upper
@@ -183,6 +184,8 @@ class NumpyBackend:
         if self.kw != 1 or getattr(self, "no_packed", False):
             return None
         k2 = 2 * self.k
+        if k2 < 12:                                        # a value has fewer bits than a bin index (stage_dist_packed_format: k2 < OWNER_BITS)
+            return None
         self._pb = np.asarray(bounds, dtype=np.int64)
         n = np.maximum(np.asarray(all_lens, dtype=np.int64) - self.k + 1, 0)
         self._poff = [np.concatenate([[0], np.cumsum(n[self._pb[r]:self._pb[r + 1]])]).astype(np.uint64) for r in range(W)]

@@ -116,7 +116,8 @@ def test_string_graph_from_gathered_shares_equals_one_rank_oracle():
 @pytest.mark.parametrize("k,world", [(33, 2), (63, 3), (65, 2), (95, 3)])
 def test_multi_word_kmers_sharded_overlap_equals_oracle(k, world):
     """k > 31 across ranks: records of two / three k-mer words + (read, pos), every word in the owner hash, the owner's multi-word sort
-    (index permutation, last word first), global ids by lexicographic rank in the gathered union."""
+    (index permutation, last word first), global ids = the owner's local index + the id base (the exclusive scan of the owners' counts: the
+    driver calls elba_dist_set_kmer_id_base; the gathered union of elba_dist_set_global_kmers is tested in test_gpu_dist_steps.py)."""
     reads = elba_amd.synth_reads(35, 120000, 10, 2500, 600, error_rate=0.02, min_len=200)
     o = po.Oracle(k, 2, 12)
     o.count_and_build(*reads[:3])
