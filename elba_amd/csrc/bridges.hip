@@ -29,11 +29,10 @@
 //                   of column b is found by comparing its three rows with vt — it is a bridge: bit 2 of flank[z], and the lane walks the
 //                   chain again, t reads: removed[vi] = 1 (atomicExch: the winner sets flag bit 4)
 //   k_brg_sums      BR_SUM_BLOCKS workgroups stride over the entries and the reads: the three bits of flank sum to long_flanks, chains and
-//                   bridges, columns of length >= 3 to anchors, removed to reads_removed, which also goes to st[SG_LIVE + 1]; every wavefront
+//                   bridges, columns of length >= 3 to anchors, removed to reads_removed, which also goes to *sg_removed_slot(st, 0); every wavefront
 //                   adds its lanes' sums up by shuffles and does one atomicAdd per counter that is not 0
-//   keep flags, scan, scatter: the compaction of sg_rounds.hpp (k_sg_keep, k_sg_scatter) as its round 0, without sg_run_rounds, as weak.hip
-//                   uses it.  A pass that removed no read leaves st[SG_LIVE + 1] 0, k_sg_keep and k_sg_scatter return at once and S stays in
-//                   its buffer; otherwise the two buffers of S are swapped
+//   keep flags, scan, scatter: the compaction of sg_rounds.hpp (sg_compact) as its round 0.  After a pass that removed no read k_sg_keep
+//                   and k_sg_scatter return at once and S stays in its buffer; otherwise the two buffers of S are swapped
 //
 // The walks are dependent loads of a few lanes: an entry of a degree-3 column costs up to min_flank_reads steps of two pointers and one or
 // two rows each, an entry of an anchor's column with a degree-2 row up to max_bridge_reads such steps, every other entry the two pointers of
@@ -67,20 +66,6 @@ static_assert(BR_READS < SG_LIVE, "the rule's counters lie in front of the proto
 // flank[z]: bit 0 the flank of entry z is long (k_brg_flank), bit 1 entry z starts a chain, bit 2 that chain is a bridge (k_brg_cut)
 enum : uint32_t { BR_F_LONG = 1u, BR_F_CHAIN = 2u, BR_F_BRIDGE = 4u };
 
-// the sum of v over the 64 lanes of a wavefront, in lane 0; every lane must call it
-__device__ __forceinline__ uint32_t br_wave_sum(uint32_t v)
-{
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-    return v;
-}
-
-// one step of the tips walk from a read of degree 2 whose column starts at cs: the first row that is not the read it came from
-__device__ __forceinline__ uint32_t br_next(const int64_t *rows, uint32_t cs, uint32_t prev)
-{
-    const uint32_t x = (uint32_t)rows[cs];
-    return x != prev ? x : (uint32_t)rows[cs + 1];
-}
-
 __global__ void k_brg_begin(const int64_t *cols, int64_t n, uint32_t M, uint32_t *ptr, uint32_t *flank)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -101,7 +86,7 @@ __global__ void k_brg_flank(const uint32_t *ptr, const int64_t *rows, const int6
         const uint32_t cs = ptr[cur];
         if (ptr[cur + 1] - cs != 2) break;                              // the flank ends here: an anchor, a dead end
         ++cnt;
-        const uint32_t nx = br_next(rows, cs, prev);
+        const uint32_t nx = sg_walk_next(rows, cs, prev);
         prev = cur; cur = nx;
     }
     if (cnt == minf) flank[z] = BR_F_LONG;
@@ -126,7 +111,7 @@ __global__ void k_brg_cut(const uint32_t *ptr, const int64_t *rows, const int64_
             break;
         }
         if (d != 2 || t == maxt) break;                                 // a dead end, or a chain longer than max_bridge_reads
-        const uint32_t nx = br_next(rows, cs, prev);
+        const uint32_t nx = sg_walk_next(rows, cs, prev);
         prev = cur; cur = nx; ++t;
     }
     if (!chain) return;
@@ -146,7 +131,7 @@ __global__ void k_brg_cut(const uint32_t *ptr, const int64_t *rows, const int64_
             if (atomicExch(&removed[c], 1u) == 0) flags[c] = (uint8_t)(flags[c] | 16u);
             const uint32_t cs = ptr[c];
             if (ptr[c + 1] - cs != 2) break;                            // (never: the first walk went through here on the same tables)
-            const uint32_t nx = br_next(rows, cs, p);
+            const uint32_t nx = sg_walk_next(rows, cs, p);
             p = c; c = nx;
         }
     }
@@ -169,13 +154,13 @@ __global__ __launch_bounds__(BR_THREADS) void k_brg_sums(const uint32_t *ptr, co
             reads += removed[i] != 0;
         }
     }
-    anchors = br_wave_sum(anchors); chains = br_wave_sum(chains); longs = br_wave_sum(longs); bridges = br_wave_sum(bridges); reads = br_wave_sum(reads);
+    anchors = sg_wave_sum(anchors); chains = sg_wave_sum(chains); longs = sg_wave_sum(longs); bridges = sg_wave_sum(bridges); reads = sg_wave_sum(reads);
     if ((threadIdx.x & 63) == 0) {
         if (anchors) atomicAdd(&st[BR_ANCHORS], (u64)anchors);
         if (chains) atomicAdd(&st[BR_CHAINS], (u64)chains);
         if (longs) atomicAdd(&st[BR_LONG], (u64)longs);
         if (bridges) atomicAdd(&st[BR_BRIDGES], (u64)bridges);
-        if (reads) { atomicAdd(&st[BR_READS], (u64)reads); atomicAdd(&st[SG_LIVE + 1], (u64)reads); }
+        if (reads) { atomicAdd(&st[BR_READS], (u64)reads); atomicAdd(sg_removed_slot(st, 0), (u64)reads); }
     }
 }
 
@@ -183,61 +168,34 @@ __global__ __launch_bounds__(BR_THREADS) void k_brg_sums(const uint32_t *ptr, co
 
 void stage_cut_bridges(Ctx &c, const elba_bridge_cfg *cfgp)
 {
-    enter(c.v, EV_CUT_BRIDGES);
-    ELBA_REQUIRE(has(c.v, P_S), ELBA_ERR_STATE, "cut_bridges: no string graph (call elba_transitive_reduction)");
-    ELBA_REQUIRE(cfgp, ELBA_ERR_INVALID_ARG, "cut_bridges: null cfg");
-    const elba_bridge_cfg &cfg = *cfgp;
+    const elba_bridge_cfg &cfg = sg_enter(c, EV_CUT_BRIDGES, cfgp);
     ELBA_REQUIRE(cfg.max_bridge_reads >= 1 && cfg.max_bridge_reads <= 65534, ELBA_ERR_INVALID_ARG, "cut_bridges: max_bridge_reads outside 1 .. 65534");
     ELBA_REQUIRE(cfg.min_flank_reads > cfg.max_bridge_reads && cfg.min_flank_reads <= 65535, ELBA_ERR_INVALID_ARG,
                  "cut_bridges: min_flank_reads outside max_bridge_reads + 1 .. 65535");
     ELBA_REQUIRE(!cfg.reserved[0] && !cfg.reserved[1], ELBA_ERR_INVALID_ARG, "cut_bridges: reserved words must be 0");
     const int64_t M = c.tr_M, n0 = c.tr_nnz;
-    ELBA_REQUIRE(M < 0xffffffffll && n0 < 0xfffffffell, ELBA_ERR_UNSUPPORTED, "cut_bridges: index ranges beyond 32 bit");
-    elba_bridge_stats st{};
-    st.nreads = M; st.nnz_before = n0; st.nnz_after = n0;
+    sg_require_32bit(EV_CUT_BRIDGES, M < 0xffffffffll && n0 < 0xfffffffell);
+    elba_bridge_stats st = sg_stats_begin<elba_bridge_stats>(c);
     if (M == 0 || n0 == 0) { accepted(c.v, EV_CUT_BRIDGES); done(c.v, EV_CUT_BRIDGES); c.brstats = st; return; }      // no entry: no anchor
-    hipStream_t s = c.stream;
     // every buffer of the launch sequence before the first launch
     sg_reserve(c, M, n0);
     c.br_flank.reserve((size_t)(n0 + 1) * 4);
-    uint32_t *ptr = c.tp_ptr.as<uint32_t>(), *flank = c.br_flank.as<uint32_t>(), *removed = c.tp_removed.as<uint32_t>(), *keep = c.tp_keep.as<uint32_t>(),
-             *pos = c.tp_pos.as<uint32_t>();
-    u64 *dst = c.tp_st.as<u64>();
-    const int64_t *rows = c.tr_out_rows.as<int64_t>(), *cols = c.tr_out_cols.as<int64_t>();
-    const int64_t lanes = M > n0 + 1 ? M : n0 + 1;
-    const unsigned nbB = (unsigned)((lanes + BR_THREADS - 1) / BR_THREADS), nbZ = (unsigned)((n0 + BR_THREADS - 1) / BR_THREADS),
-                   nbK = (unsigned)((n0 + 1 + SG_THREADS - 1) / SG_THREADS), nbS = (unsigned)((n0 + SG_TILE - 1) / SG_TILE);
+    const SgCall w(c);
+    uint32_t *flank = c.br_flank.as<uint32_t>();
+    const int64_t *rows = w.rows[0], *cols = w.cols[0];
     accepted(c.v, EV_CUT_BRIDGES);                              // as in stage_clip_tips: the contigs go, and S is invalid until the counters are back
-    c.br_t_total.start(s);
-    ELBA_HIP(hipMemsetAsync(dst, 0, SG_ST * 8, s));
-    ELBA_HIP(hipMemsetAsync(removed, 0, (size_t)(M + 1) * 4, s));
-    ELBA_HIP(hipMemsetAsync(keep, 0, (size_t)(n0 + 2) * 4, s));
-    hipLaunchKernelGGL(k_sg_init, dim3(1), dim3(1), 0, s, dst, (u64)n0);
-    hipLaunchKernelGGL(k_brg_begin, dim3(nbB), dim3(BR_THREADS), 0, s, cols, n0, (uint32_t)M, ptr, flank);
-    hipLaunchKernelGGL(k_brg_flank, dim3(nbZ), dim3(BR_THREADS), 0, s, ptr, rows, cols, n0, (uint32_t)cfg.min_flank_reads, (uint32_t)M, flank);
-    hipLaunchKernelGGL(k_brg_cut, dim3(nbZ), dim3(BR_THREADS), 0, s, ptr, rows, cols, n0, (uint32_t)cfg.max_bridge_reads, (uint32_t)M, flank, removed,
-                       c.tr_flags.as<uint8_t>());
-    hipLaunchKernelGGL(k_brg_sums, dim3(nbB < (unsigned)BR_SUM_BLOCKS ? nbB : (unsigned)BR_SUM_BLOCKS), dim3(BR_THREADS), 0, s, ptr, flank, removed, n0, (uint32_t)M, dst);
-    c.br_t_compact.start(s);
-    hipLaunchKernelGGL(k_sg_keep, dim3(nbK), dim3(SG_THREADS), 0, s, rows, cols, removed, dst, 0, n0, keep);
-    exclusive_scan_u32(s, keep, pos, n0 + 1, c.ws_scan);
-    hipLaunchKernelGGL(k_sg_scatter, dim3(nbS), dim3(SG_THREADS), 0, s, rows, cols, c.tr_out_vals.as<uint32_t>(), pos, dst, 0, n0, c.tp_rows.as<int64_t>(),
-                       c.tp_cols.as<int64_t>(), c.tp_vals.as<uint32_t>());
-    c.br_t_compact.stop(s);
-    ELBA_HIP(hipGetLastError());
-    c.br_t_total.stop(s);
+    sg_start(w);
+    hipLaunchKernelGGL(k_brg_begin, dim3(w.nbB), dim3(BR_THREADS), 0, w.s, cols, n0, (uint32_t)M, w.ptr, flank);
+    hipLaunchKernelGGL(k_brg_flank, dim3(w.nbZ), dim3(BR_THREADS), 0, w.s, w.ptr, rows, cols, n0, (uint32_t)cfg.min_flank_reads, (uint32_t)M, flank);
+    hipLaunchKernelGGL(k_brg_cut, dim3(w.nbZ), dim3(BR_THREADS), 0, w.s, w.ptr, rows, cols, n0, (uint32_t)cfg.max_bridge_reads, (uint32_t)M, flank, w.removed, w.flags);
+    hipLaunchKernelGGL(k_brg_sums, dim3(w.nbB < (unsigned)BR_SUM_BLOCKS ? w.nbB : (unsigned)BR_SUM_BLOCKS), dim3(BR_THREADS), 0, w.s, w.ptr, flank, w.removed, n0, (uint32_t)M, w.st);
+    sg_compact(w, 0);
     u64 h[SG_ST];
-    ELBA_HIP(hipMemcpyAsync(h, dst, SG_ST * 8, hipMemcpyDeviceToHost, s));
-    ELBA_HIP(hipStreamSynchronize(s));
-    if (h[SG_LIVE + 1] > 0) {                                   // S moved into the second buffer
-        c.tr_out_rows.swap(c.tp_rows); c.tr_out_cols.swap(c.tp_cols); c.tr_out_vals.swap(c.tp_vals);
-        c.tr_nnz = (int64_t)h[SG_NNZ + 1];
-    }
+    sg_settle(w, h, sg_read_back(w, h, 1, 0));
     done(c.v, EV_CUT_BRIDGES);
-    st.nnz_after = c.tr_nnz; st.entries_removed = n0 - c.tr_nnz;
     st.anchors = (int64_t)h[BR_ANCHORS]; st.chains = (int64_t)h[BR_CHAINS]; st.long_flanks = (int64_t)h[BR_LONG]; st.bridges = (int64_t)h[BR_BRIDGES];
     st.reads_removed = (int64_t)h[BR_READS];
-    st.ms_total = c.br_t_total.ms(); st.ms_compact = c.br_t_compact.ms();
+    sg_stats_end(c, st);
     c.brstats = st;
 }
 

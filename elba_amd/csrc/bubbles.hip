@@ -22,7 +22,7 @@
 //   k_bub_pick      one lane per entry that holds an arm: it looks through column a's entries for arms with the same arm_end; it is the kept
 //                   arm if none has a larger (arm_len, -z); the kept lane of a group of >= 2 counts a bubble; every other lane walks its arm
 //                   again, arm_len reads: removed[vi] = 1 (atomicExch: the winner counts the read and sets flag bit 3), and counts a removed arm
-//   keep flags, scan, scatter: the compaction of sg_rounds.hpp (k_sg_keep, k_sg_scatter), shared with tips.hip
+//   keep flags, scan, scatter: the compaction of sg_rounds.hpp
 //
 // The pick is quadratic per anchor: an arm costs deg(a) reads of arm_end (4 bytes, the same addresses for the lanes of a column, which are
 // neighbours: cached) and one of arm_len per arm of its group, so a pair of hubs joined by d arms costs d^2 of each.  The alternative, sorting
@@ -32,7 +32,7 @@
 //
 // Rounds without host synchronisation, in batches of four with one synchronisation per batch: the protocol of sg_rounds.hpp.  The rule's
 // part of it: every kernel here returns at once when the round before removed nothing, and k_bub_pick adds the reads it removed to
-// st[SG_LIVE + r + 1].
+// *sg_removed_slot(st, r).
 //
 // Bounds: a lane works on an entry z < n, the round's nnz; ptr is built from n, so every column range lies in [0, n) and arm_end / arm_len
 // (n0 + 1 elements, n <= n0) are read and written below n; every read index is tested below M before ptr is read at it (rows and cols of S
@@ -55,18 +55,11 @@ constexpr int BB_THREADS = SG_THREADS;          // threads of every kernel here
 enum { BB_ANCHORS = 0, BB_ARMS = 1, BB_BUBBLES = 2, BB_GONE = 3, BB_READS = 4 };
 static_assert(BB_READS < SG_LIVE, "the rule's counters lie in front of the protocol's");
 
-// one atomicAdd per wavefront for a count of lanes
-__device__ __forceinline__ void bb_count(u64 *slot, bool mine)
-{
-    const u64 b = __ballot(mine);
-    if (b && (threadIdx.x & 63) == (unsigned)__builtin_ctzll(b)) atomicAdd(slot, (u64)__builtin_popcountll(b));
-}
-
 __global__ void k_bub_begin(const int64_t *cols, const u64 *st, int r, uint32_t M, uint32_t *ptr, uint32_t *arm_end, uint32_t *arm_len)
 {
-    if (st[SG_LIVE + r] == 0) return;
+    if (!sg_live(st, r)) return;
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t n = (int64_t)st[SG_NNZ + r];
+    const int64_t n = sg_nnz(st, r);
     if (i < n) { arm_end[i] = BB_NONE; arm_len[i] = 0; }
     sg_col_ptrs(cols, n, M, i, ptr);
 }
@@ -74,9 +67,9 @@ __global__ void k_bub_begin(const int64_t *cols, const u64 *st, int r, uint32_t 
 __global__ void k_bub_walk(const uint32_t *ptr, const int64_t *rows, const int64_t *cols, u64 *st, int r, uint32_t maxt, uint32_t M,
                            uint32_t *arm_end, uint32_t *arm_len)
 {
-    if (st[SG_LIVE + r] == 0) return;
+    if (!sg_live(st, r)) return;
     const int64_t z = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t n = (int64_t)st[SG_NNZ + r];
+    const int64_t n = sg_nnz(st, r);
     bool anchor = false, arm = false;
     if (z < n) {
         const uint32_t a = (uint32_t)cols[z], v1 = (uint32_t)rows[z];
@@ -92,23 +85,22 @@ __global__ void k_bub_walk(const uint32_t *ptr, const int64_t *rows, const int64
                         break;
                     }
                     if (d != 2 || t == maxt) break;                     // a dead end, or a chain longer than max_arm_reads
-                    const uint32_t x = (uint32_t)rows[cs];
-                    const uint32_t nx = x != prev ? x : (uint32_t)rows[cs + 1];
+                    const uint32_t nx = sg_walk_next(rows, cs, prev);
                     prev = cur; cur = nx; ++t;
                 }
             }
         }
     }
-    bb_count(&st[BB_ANCHORS], anchor);
-    bb_count(&st[BB_ARMS], arm);
+    sg_count(&st[BB_ANCHORS], anchor);
+    sg_count(&st[BB_ARMS], arm);
 }
 
 __global__ void k_bub_pick(const uint32_t *ptr, const int64_t *rows, const int64_t *cols, u64 *st, int r, uint32_t M, const uint32_t *arm_end,
                            const uint32_t *arm_len, uint32_t *removed, uint8_t *flags)
 {
-    if (st[SG_LIVE + r] == 0) return;
+    if (!sg_live(st, r)) return;
     const int64_t z = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t n = (int64_t)st[SG_NNZ + r];
+    const int64_t n = sg_nnz(st, r);
     bool bubble = false, gone = false;
     if (z < n) {
         const uint32_t b = arm_end[z];
@@ -131,55 +123,47 @@ __global__ void k_bub_pick(const uint32_t *ptr, const int64_t *rows, const int64
                     if (atomicExch(&removed[cur], 1u) == 0) { ++cnt; flags[cur] = (uint8_t)(flags[cur] | 8u); }
                     const uint32_t cs = ptr[cur];
                     if (ptr[cur + 1] - cs != 2) break;                  // (never: k_bub_walk went through here on the same tables)
-                    const uint32_t x = (uint32_t)rows[cs];
-                    const uint32_t nx = x != prev ? x : (uint32_t)rows[cs + 1];
+                    const uint32_t nx = sg_walk_next(rows, cs, prev);
                     prev = cur; cur = nx;
                 }
-                if (cnt) { atomicAdd(&st[BB_READS], (u64)cnt); atomicAdd(&st[SG_LIVE + r + 1], (u64)cnt); }
+                if (cnt) { atomicAdd(&st[BB_READS], (u64)cnt); atomicAdd(sg_removed_slot(st, r), (u64)cnt); }
             }
         }
     }
-    bb_count(&st[BB_BUBBLES], bubble);
-    bb_count(&st[BB_GONE], gone);
+    sg_count(&st[BB_BUBBLES], bubble);
+    sg_count(&st[BB_GONE], gone);
 }
 
 }  // namespace
 
 void stage_pop_bubbles(Ctx &c, const elba_bubble_cfg *cfgp)
 {
-    enter(c.v, EV_POP_BUBBLES);
-    ELBA_REQUIRE(has(c.v, P_S), ELBA_ERR_STATE, "pop_bubbles: no string graph (call elba_transitive_reduction)");
-    ELBA_REQUIRE(cfgp, ELBA_ERR_INVALID_ARG, "pop_bubbles: null cfg");
-    const elba_bubble_cfg &cfg = *cfgp;
+    const elba_bubble_cfg &cfg = sg_enter(c, EV_POP_BUBBLES, cfgp);
     ELBA_REQUIRE(cfg.max_arm_reads >= 1 && cfg.max_arm_reads <= 65535, ELBA_ERR_INVALID_ARG, "pop_bubbles: max_arm_reads outside 1 .. 65535");
     ELBA_REQUIRE(cfg.rounds >= 1 && cfg.rounds <= SG_MAX_ROUNDS, ELBA_ERR_INVALID_ARG, "pop_bubbles: rounds outside 1 .. 64");
     ELBA_REQUIRE(!cfg.reserved[0] && !cfg.reserved[1], ELBA_ERR_INVALID_ARG, "pop_bubbles: reserved words must be 0");
     const int64_t M = c.tr_M, n0 = c.tr_nnz;
-    ELBA_REQUIRE(M < 0xffffffffll && n0 < 0xfffffffell, ELBA_ERR_UNSUPPORTED, "pop_bubbles: index ranges beyond 32 bit");
-    elba_bubble_stats st{};
-    st.nreads = M; st.nnz_before = n0; st.nnz_after = n0; st.rounds_run = 1;
+    sg_require_32bit(EV_POP_BUBBLES, M < 0xffffffffll && n0 < 0xfffffffell);
+    elba_bubble_stats st = sg_stats_begin<elba_bubble_stats>(c);
+    st.rounds_run = 1;
     if (M == 0 || n0 == 0) { accepted(c.v, EV_POP_BUBBLES); done(c.v, EV_POP_BUBBLES); c.bbstats = st; return; }      // no entry: no anchor, the one round removes nothing
-    hipStream_t s = c.stream;
     // every buffer of the launch sequence before the first launch
     sg_reserve(c, M, n0);
     c.bb_end.reserve((size_t)(n0 + 1) * 4); c.bb_len.reserve((size_t)(n0 + 1) * 4);
-    uint32_t *ptr = c.tp_ptr.as<uint32_t>(), *arm_end = c.bb_end.as<uint32_t>(), *arm_len = c.bb_len.as<uint32_t>(), *removed = c.tp_removed.as<uint32_t>();
-    u64 *dst = c.tp_st.as<u64>();
-    const int64_t lanes = M > n0 + 1 ? M : n0 + 1;
-    const unsigned nbB = (unsigned)((lanes + BB_THREADS - 1) / BB_THREADS), nbZ = (unsigned)((n0 + BB_THREADS - 1) / BB_THREADS);
+    const SgCall w(c);
+    uint32_t *arm_end = c.bb_end.as<uint32_t>(), *arm_len = c.bb_len.as<uint32_t>();
     accepted(c.v, EV_POP_BUBBLES);                              // as in stage_clip_tips: the contigs go, and S is invalid until the counters are back
     u64 h[SG_ST];
-    const int moves = sg_run_rounds(c, cfg.rounds, c.bb_t_total, c.bb_t_compact, h, [&](int r, const int64_t *rows, const int64_t *cols) {
-        hipLaunchKernelGGL(k_bub_begin, dim3(nbB), dim3(BB_THREADS), 0, s, cols, dst, r, (uint32_t)M, ptr, arm_end, arm_len);
-        hipLaunchKernelGGL(k_bub_walk, dim3(nbZ), dim3(BB_THREADS), 0, s, ptr, rows, cols, dst, r, (uint32_t)cfg.max_arm_reads, (uint32_t)M, arm_end, arm_len);
-        hipLaunchKernelGGL(k_bub_pick, dim3(nbZ), dim3(BB_THREADS), 0, s, ptr, rows, cols, dst, r, (uint32_t)M, arm_end, arm_len, removed, c.tr_flags.as<uint8_t>());
+    const int moves = sg_run_rounds(w, cfg.rounds, h, [&](int r, const int64_t *rows, const int64_t *cols) {
+        hipLaunchKernelGGL(k_bub_begin, dim3(w.nbB), dim3(BB_THREADS), 0, w.s, cols, w.st, r, (uint32_t)M, w.ptr, arm_end, arm_len);
+        hipLaunchKernelGGL(k_bub_walk, dim3(w.nbZ), dim3(BB_THREADS), 0, w.s, w.ptr, rows, cols, w.st, r, (uint32_t)cfg.max_arm_reads, (uint32_t)M, arm_end, arm_len);
+        hipLaunchKernelGGL(k_bub_pick, dim3(w.nbZ), dim3(BB_THREADS), 0, w.s, w.ptr, rows, cols, w.st, r, (uint32_t)M, arm_end, arm_len, w.removed, w.flags);
     });
     done(c.v, EV_POP_BUBBLES);
-    st.nnz_after = c.tr_nnz; st.entries_removed = n0 - c.tr_nnz;
     st.anchors = (int64_t)h[BB_ANCHORS]; st.arms = (int64_t)h[BB_ARMS]; st.bubbles = (int64_t)h[BB_BUBBLES]; st.arms_removed = (int64_t)h[BB_GONE];
     st.reads_removed = (int64_t)h[BB_READS];
     st.rounds_run = moves < cfg.rounds ? moves + 1 : cfg.rounds;
-    st.ms_total = c.bb_t_total.ms(); st.ms_compact = c.bb_t_compact.ms();
+    sg_stats_end(c, st);
     c.bbstats = st;
 }
 

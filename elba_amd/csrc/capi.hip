@@ -778,8 +778,8 @@ int elba_release_workspace(elba_ctx *ctx)
         c.pu_k0.release(); c.pu_k1.release(); c.pu_eptr.release(); c.pu_head.release(); c.pu_hidx.release(); c.pu_delta.release();   // pileup scratch (the results stay)
         c.pu_dsum.release(); c.pu_gstart.release(); c.pu_tok.release(); c.pu_tpos.release(); c.pu_sel.release(); c.pu_rows.release(); c.pu_cols.release(); c.pu_vals.release();
         c.tm_cnt.release(); c.tm_bytes.release(); c.tm_first.release(); c.tm_boff.release(); c.tm_srcb.release();   // trim scratch (the trimmed reads and their map stay)
-        c.tp_ptr.release(); c.tp_ntips.release(); c.tp_anchor.release(); c.tp_removed.release(); c.tp_keep.release(); c.tp_pos.release(); c.tp_st.release();   // tip scratch and the
-        c.tp_rows.release(); c.tp_cols.release(); c.tp_vals.release();                                                                    // spare buffer of S (S itself stays)
+        c.sg.release();                                                                                                                    // the cleaning calls' shared scratch and the spare buffer of S (S itself stays)
+        c.tp_ntips.release(); c.tp_anchor.release();                                                                                       // tip scratch
         c.bb_end.release(); c.bb_len.release();                                                                                            // bubble scratch
         c.wk_best.release(); c.wk_cnt.release(); c.wk_nweak.release(); c.wk_after.release();                                                                     // weak-overlap scratch
         c.br_flank.release();                                                                                                              // bridge scratch

@@ -339,30 +339,33 @@ struct Ctx {
     EventTimer tm_t_total, tm_t_repack;
     elba_trim_stats tmstats{};
 
-    // tip clipping (tips.hip): all scratch; tp_rows / tp_cols / tp_vals are the second buffer of S (swapped with tr_out_* after an odd number of moves).
-    // tp_ptr, tp_removed, tp_keep, tp_pos, tp_st and that second buffer belong to the rounds of sg_rounds.hpp, which bubbles.hip runs too
-    DevBuf tp_ptr, tp_ntips, tp_anchor, tp_removed, tp_keep, tp_pos, tp_st, tp_rows, tp_cols, tp_vals;
-    EventTimer tp_t_total, tp_t_compact;
+    // string graph cleaning (sg_rounds.hpp): what the five calls below share, all scratch.  Column pointers of the round's S, the removed reads,
+    // keep flags and their scan, the counters, and the second buffer of S (rows, cols, vals: swapped with tr_out_* after an odd number of
+    // moves).  The calls run one after another on the context's stream and each reads its two times before it returns: one pair of timers
+    struct SgWork {
+        DevBuf ptr, removed, keep, pos, st, rows, cols, vals;
+        EventTimer t_total, t_compact;
+        void release() { ptr.release(); removed.release(); keep.release(); pos.release(); st.release(); rows.release(); cols.release(); vals.release(); }
+    } sg;
+
+    // tip clipping (tips.hip): scratch of its own, one word per read each
+    DevBuf tp_ntips, tp_anchor;
     elba_tip_stats tpstats{};
 
     // bubble popping (bubbles.hip): scratch of its own, one word per entry of S each
     DevBuf bb_end, bb_len;
-    EventTimer bb_t_total, bb_t_compact;
     elba_bubble_stats bbstats{};
 
-    // cutting weak overlaps (weak.hip): scratch of its own, one word per (read, side) each; the compaction's buffers are the tp_ ones above
+    // cutting weak overlaps (weak.hip): scratch of its own, one word per (read, side) each
     DevBuf wk_best, wk_cnt, wk_nweak, wk_after;
-    EventTimer wk_t_total, wk_t_compact;
     elba_weak_stats wkstats{};
 
-    // cutting bridge chains (bridges.hip): scratch of its own, one word per entry of S; the compaction's buffers are the tp_ ones above
+    // cutting bridge chains (bridges.hip): scratch of its own, one word per entry of S
     DevBuf br_flank;
-    EventTimer br_t_total, br_t_compact;
     elba_bridge_stats brstats{};
 
-    // resolving three-armed stars (stars.hip): scratch of its own, one word per read; the rounds' buffers are the tp_ ones above.  It reads tr_ptr / tr_sym
+    // resolving three-armed stars (stars.hip): scratch of its own, one word per read.  It reads tr_ptr / tr_sym
     DevBuf sr_word;
-    EventTimer sr_t_total, sr_t_compact;
     elba_star_stats srstats{};
 
     // workspaces

@@ -1,9 +1,8 @@
-// sg_rounds.hpp — what the calls that take reads out of the string graph in rounds share (tips.hip: elba_clip_tips, bubbles.hip:
-// elba_pop_bubbles, stars.hip: elba_resolve_stars): the round-batch protocol and the compaction of S.  A call brings its RULE — kernels that, for round r, read the
-// round's S and set removed[v] = 1 for every read that goes, adding the reads they removed to st[SG_LIVE + r + 1]; everything else is here.
-// weak.hip (elba_cut_weak_overlaps) removes entries, not reads, in one pass: it brings a keep kernel of its own beside k_sg_keep and uses
-// sg_col_ptrs, sg_reserve, k_sg_init and k_sg_scatter as round 0 of the protocol, without sg_run_rounds.  bridges.hip (elba_cut_bridges)
-// removes reads in one pass and runs round 0 the same way, with k_sg_keep.
+// sg_rounds.hpp — what the five calls that clean the string graph share (tips.hip: elba_clip_tips, bubbles.hip: elba_pop_bubbles, stars.hip:
+// elba_resolve_stars, in rounds; weak.hip: elba_cut_weak_overlaps, bridges.hip: elba_cut_bridges, in one pass): the protocol of the rounds,
+// the compaction of S, the frame of a stage function and three device helpers.  A call brings its RULE — kernels that, for round r, read the
+// round's S, mark what goes and add what they removed to *sg_removed_slot(st, r) — its cfg checks and its counters; everything else is here,
+// and only this file knows the protocol's slots of st[], the two buffers of S and when they swap, and how the counters come back.
 //
 //   sg_col_ptrs     (device function) column pointers of the round's S from its column ids, nnz read on the device
 //   k_sg_keep       keep[z] = neither row nor column of entry z is removed (0 behind the round's nnz)
@@ -11,6 +10,11 @@
 //   k_sg_scatter    rows and cols: one lane per entry, 8-byte accesses.  Values (36 bytes = 9 dwords): one lane per DWORD of a 256-entry
 //                   tile, so that a wavefront's loads are 256 contiguous bytes and its stores contiguous over every run of kept entries
 //                   (one lane per entry would read 36-byte strided records: 9 instructions that each touch 64 x 36 bytes for 256 useful)
+//
+// The host side is three pieces: sg_start (timer, clears, k_sg_init), sg_compact (keep flags, scan, scatter of round r) and sg_read_back
+// with sg_settle (the counters back, S in the buffer the moves left it in).  sg_run_rounds loops over them in batches; a one-pass call is
+// sg_start, its rule, sg_compact of round 0, sg_read_back, sg_settle.  weak.hip removes entries, not reads: it hands sg_compact a keep
+// kernel of its own and a kernel between scan and scatter, and starts by itself, because it has no removed reads to clear.
 //
 // Rounds without host synchronisation: the host queues the rounds in batches of SG_BATCH, all sized by the nnz the call starts with;
 // st[SG_LIVE + r] (reads the round before r removed; 1 for the first) and st[SG_NNZ + r] live on the device, every kernel of a round returns
@@ -48,6 +52,34 @@ using u64 = unsigned long long;
 __global__ void k_sg_init(u64 *st, u64 nnz)
 {
     st[SG_LIVE] = 1; st[SG_NNZ] = nnz;
+}
+
+// The protocol's slots, for the kernels of a rule: round r runs only if the round before it removed something; nnz(S) as it finds it; and
+// where it adds what it removed itself (reads, or entries: only "none" matters to the protocol)
+__device__ __forceinline__ bool sg_live(const u64 *st, int r) { return st[SG_LIVE + r] != 0; }
+__device__ __forceinline__ int64_t sg_nnz(const u64 *st, int r) { return (int64_t)st[SG_NNZ + r]; }
+__device__ __forceinline__ u64 *sg_removed_slot(u64 *st, int r) { return &st[SG_LIVE + r + 1]; }
+
+// the sum of v over the 64 lanes of a wavefront, in lane 0; every lane must call it
+__device__ __forceinline__ uint32_t sg_wave_sum(uint32_t v)
+{
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
+    return v;
+}
+
+// one atomicAdd per wavefront for a count of lanes; every lane must call it (mine: 0 or 1, an int as __ballot takes it)
+__device__ __forceinline__ void sg_count(u64 *slot, int mine)
+{
+    const u64 b = __ballot(mine);
+    if (b && (threadIdx.x & 63) == (unsigned)__builtin_ctzll(b)) atomicAdd(slot, (u64)__builtin_popcountll(b));
+}
+
+// one step of a walk through a read of degree 2 whose column starts at cs: the first row that is not the read it came from.  `only`: the
+// column has one row, which is taken whatever prev is (the second walk of k_tip_mark starts at its dead end)
+__device__ __forceinline__ uint32_t sg_walk_next(const int64_t *rows, uint32_t cs, uint32_t prev, bool only = false)
+{
+    const uint32_t x = (uint32_t)rows[cs];
+    return (only || x != prev) ? x : (uint32_t)rows[cs + 1];
 }
 
 // lane i of a grid of at least n + 1 lanes: ptr[k] = i for every column k in (cols[i - 1], cols[i]] (cols[n] taken as M): M + 1 pointers
@@ -100,59 +132,149 @@ __global__ __launch_bounds__(SG_THREADS) void k_sg_scatter(const int64_t *rows, 
     }
 }
 
+// ---- the frame of a stage function: enter, check, reserve, `accepted`, launch, `done`, stats ------------------------------------------
+
+// enter, and the two checks every cleaning call makes in front of its own: a valid S and a cfg
+template <class Cfg>
+inline const Cfg &sg_enter(Ctx &c, Event ev, const Cfg *cfgp)
+{
+    enter(c.v, ev);
+    ELBA_REQUIRE(has(c.v, P_S), ELBA_ERR_STATE, std::string(TABLE[ev].name) + ": no string graph (call elba_transitive_reduction)");
+    ELBA_REQUIRE(cfgp, ELBA_ERR_INVALID_ARG, std::string(TABLE[ev].name) + ": null cfg");
+    return *cfgp;
+}
+
+// behind the cfg checks: the rule's own limits on M and nnz (the kernels index with 32 bits)
+inline void sg_require_32bit(Event ev, bool fits)
+{
+    ELBA_REQUIRE(fits, ELBA_ERR_UNSUPPORTED, std::string(TABLE[ev].name) + ": index ranges beyond 32 bit");
+}
+
+// the stats of a call as they stand before it removes anything, and what every call reports when the counters are back
+template <class Stats>
+inline Stats sg_stats_begin(const Ctx &c)
+{
+    Stats st{};
+    st.nreads = c.tr_M; st.nnz_before = c.tr_nnz; st.nnz_after = c.tr_nnz;
+    return st;
+}
+
+template <class Stats>
+inline void sg_stats_end(Ctx &c, Stats &st)
+{
+    st.nnz_after = c.tr_nnz; st.entries_removed = st.nnz_before - c.tr_nnz;
+    st.ms_total = c.sg.t_total.ms(); st.ms_compact = c.sg.t_compact.ms();
+}
+
 // The buffers the protocol itself needs, for an S of M reads and n0 entries: column pointers, the removed set, keep flags and their scan,
 // the counters, the second buffer of S.  A call reserves these and its rule's own before its first launch, and only then is `accepted`.
 inline void sg_reserve(Ctx &c, int64_t M, int64_t n0)
 {
-    c.tp_ptr.reserve((size_t)(M + 2) * 4); c.tp_removed.reserve((size_t)(M + 1) * 4);
-    c.tp_keep.reserve((size_t)(n0 + 2) * 4); c.tp_pos.reserve((size_t)(n0 + 2) * 4); c.tp_st.reserve(SG_ST * 8);
-    c.tp_rows.reserve((size_t)(n0 + 1) * 8); c.tp_cols.reserve((size_t)(n0 + 1) * 8); c.tp_vals.reserve((size_t)(n0 + 1) * sizeof(elba_overlap_t));
+    c.sg.ptr.reserve((size_t)(M + 2) * 4); c.sg.removed.reserve((size_t)(M + 1) * 4);
+    c.sg.keep.reserve((size_t)(n0 + 2) * 4); c.sg.pos.reserve((size_t)(n0 + 2) * 4); c.sg.st.reserve(SG_ST * 8);
+    c.sg.rows.reserve((size_t)(n0 + 1) * 8); c.sg.cols.reserve((size_t)(n0 + 1) * 8); c.sg.vals.reserve((size_t)(n0 + 1) * sizeof(elba_overlap_t));
     c.ws_scan.reserve((size_t)((n0 + 1) / 1024 + 64) * 8);      // (exclusive_scan_u32 sizes it itself; reserved here so that no launch waits for a hipMalloc)
 }
 
-// Runs up to `rounds` rounds on the context's S (c.tr_M reads, c.tr_nnz entries, both > 0) and leaves the S the last one made in tr_out_*
-// with tr_nnz.  rule(r, rows, cols) queues the rule's kernels of round r on c.stream, which read the round's S at rows / cols.  h receives
-// the counters as the last synchronisation found them.  Returns the moves: the rounds that removed something, a prefix of the rounds.
-// t_total spans the call, t_compact the compaction of the first round.  The caller has reserved the buffers and named its event `accepted`;
-// S is not valid while this runs, and `done` is the caller's when it returns.
-template <class Rule>
-inline int sg_run_rounds(Ctx &c, int rounds, EventTimer &t_total, EventTimer &t_compact, u64 (&h)[SG_ST], Rule rule)
+inline unsigned sg_blocks(int64_t lanes) { return (unsigned)((lanes + SG_THREADS - 1) / SG_THREADS); }
+
+// What the launches of a call work with, taken once sg_reserve is through: the context's S (M reads, n0 entries, both > 0) in its two
+// buffers — [0] is tr_out_*, where S is when the call starts — the protocol's typed pointers, and the grids of SG_THREADS lanes
+struct SgCall {
+    Ctx &c;
+    const int64_t M, n0;
+    hipStream_t s;
+    uint32_t *ptr, *removed, *keep, *pos;
+    u64 *st;
+    uint8_t *flags;
+    int64_t *rows[2], *cols[2];
+    uint32_t *vals[2];
+    unsigned nbM, nbZ, nbB;     // one lane per read, per entry, and for a kernel that clears a table per read beside sg_col_ptrs' n0 + 1 lanes
+    explicit SgCall(Ctx &cx)
+        : c(cx), M(cx.tr_M), n0(cx.tr_nnz), s(cx.stream), ptr(cx.sg.ptr.as<uint32_t>()), removed(cx.sg.removed.as<uint32_t>()), keep(cx.sg.keep.as<uint32_t>()),
+          pos(cx.sg.pos.as<uint32_t>()), st(cx.sg.st.as<u64>()), flags(cx.tr_flags.as<uint8_t>()), rows{cx.tr_out_rows.as<int64_t>(), cx.sg.rows.as<int64_t>()},
+          cols{cx.tr_out_cols.as<int64_t>(), cx.sg.cols.as<int64_t>()}, vals{cx.tr_out_vals.as<uint32_t>(), cx.sg.vals.as<uint32_t>()}, nbM(sg_blocks(M)),
+          nbZ(sg_blocks(n0)), nbB(sg_blocks(M > n0 + 1 ? M : n0 + 1))
+    {
+    }
+};
+
+// ---- the protocol: a start, the compaction of round r, and the counters back ------------------------------------------------------
+
+// The start of a call whose rule removes READS: t_total, the counters, the removed set and the keep flags (k_sg_keep leaves them alone
+// in a round that has nothing to do) cleared, round 0 set up.  The caller has reserved the buffers and named its event `accepted`; S is
+// not valid from here until sg_settle.
+inline void sg_start(const SgCall &w)
 {
-    const int64_t M = c.tr_M, n0 = c.tr_nnz;
-    hipStream_t s = c.stream;
-    uint32_t *removed = c.tp_removed.as<uint32_t>(), *keep = c.tp_keep.as<uint32_t>(), *pos = c.tp_pos.as<uint32_t>();
-    u64 *dst = c.tp_st.as<u64>();
-    int64_t *rows[2] = {c.tr_out_rows.as<int64_t>(), c.tp_rows.as<int64_t>()}, *cols[2] = {c.tr_out_cols.as<int64_t>(), c.tp_cols.as<int64_t>()};
-    uint32_t *vals[2] = {c.tr_out_vals.as<uint32_t>(), c.tp_vals.as<uint32_t>()};
-    const unsigned nbK = (unsigned)((n0 + 1 + SG_THREADS - 1) / SG_THREADS), nbS = (unsigned)((n0 + SG_TILE - 1) / SG_TILE);
-    t_total.start(s);
-    ELBA_HIP(hipMemsetAsync(dst, 0, SG_ST * 8, s));
-    ELBA_HIP(hipMemsetAsync(removed, 0, (size_t)(M + 1) * 4, s));
-    ELBA_HIP(hipMemsetAsync(keep, 0, (size_t)(n0 + 2) * 4, s));
-    hipLaunchKernelGGL(k_sg_init, dim3(1), dim3(1), 0, s, dst, (u64)n0);
-    for (int i = 0; i < SG_ST; ++i) h[i] = 0;
+    w.c.sg.t_total.start(w.s);
+    ELBA_HIP(hipMemsetAsync(w.st, 0, SG_ST * 8, w.s));
+    ELBA_HIP(hipMemsetAsync(w.removed, 0, (size_t)(w.M + 1) * 4, w.s));
+    ELBA_HIP(hipMemsetAsync(w.keep, 0, (size_t)(w.n0 + 2) * 4, w.s));
+    hipLaunchKernelGGL(k_sg_init, dim3(1), dim3(1), 0, w.s, w.st, (u64)w.n0);
+}
+
+// The compaction of round r, from buffer r & 1 of S into the other; t_compact spans that of round 0.  keep(rows, cols) queues the kernel
+// that writes the n0 + 1 keep flags of the round's S, scanned() what the rule has to do between the scan and the scatter.
+template <class Keep, class Scanned>
+inline void sg_compact(const SgCall &w, int r, Keep keep, Scanned scanned)
+{
+    const int a = r & 1, b = a ^ 1;
+    if (r == 0) w.c.sg.t_compact.start(w.s);
+    keep(w.rows[a], w.cols[a]);
+    exclusive_scan_u32(w.s, w.keep, w.pos, w.n0 + 1, w.c.ws_scan);
+    scanned();
+    hipLaunchKernelGGL(k_sg_scatter, dim3((unsigned)((w.n0 + SG_TILE - 1) / SG_TILE)), dim3(SG_THREADS), 0, w.s, w.rows[a], w.cols[a], w.vals[a], w.pos, w.st, r, w.n0,
+                       w.rows[b], w.cols[b], w.vals[b]);
+    if (r == 0) w.c.sg.t_compact.stop(w.s);
+}
+
+// ... of a rule that removes reads: an entry stays if neither its row nor its column is in the removed set
+inline void sg_compact(const SgCall &w, int r)
+{
+    sg_compact(w, r, [&](const int64_t *rows, const int64_t *cols) {
+        hipLaunchKernelGGL(k_sg_keep, dim3(sg_blocks(w.n0 + 1)), dim3(SG_THREADS), 0, w.s, rows, cols, w.removed, w.st, r, w.n0, w.keep);
+    }, [] {});
+}
+
+// The counters back into h: the one host synchronisation of a one-pass call, or of a batch of rounds (t_total is recorded again behind
+// every batch: the last record counts).  Returns `moves` counted on over the rounds below `queued` that removed something.
+inline int sg_read_back(const SgCall &w, u64 (&h)[SG_ST], int queued, int moves)
+{
+    ELBA_HIP(hipGetLastError());
+    w.c.sg.t_total.stop(w.s);
+    ELBA_HIP(hipMemcpyAsync(h, w.st, SG_ST * 8, hipMemcpyDeviceToHost, w.s));
+    ELBA_HIP(hipStreamSynchronize(w.s));
+    while (moves < queued && h[SG_LIVE + moves + 1] > 0) ++moves;
+    return moves;
+}
+
+// S is in the buffer `moves` moves left it in: an odd number swaps the two, and tr_nnz is what the last move kept.  `done` is the caller's.
+inline void sg_settle(const SgCall &w, const u64 (&h)[SG_ST], int moves)
+{
+    Ctx &c = w.c;
+    if (moves & 1) { c.tr_out_rows.swap(c.sg.rows); c.tr_out_cols.swap(c.sg.cols); c.tr_out_vals.swap(c.sg.vals); }
+    c.tr_nnz = (int64_t)h[SG_NNZ + moves];
+}
+
+// Runs up to `rounds` >= 1 rounds and leaves the S the last one made in tr_out_* with tr_nnz.  rule(r, rows, cols) queues the rule's
+// kernels of round r on the stream, which read the round's S at rows / cols.  h receives the counters as the last synchronisation found
+// them.  Returns the moves: the rounds that removed something, a prefix of the rounds.
+template <class Rule>
+inline int sg_run_rounds(const SgCall &w, int rounds, u64 (&h)[SG_ST], Rule rule)
+{
+    sg_start(w);
     int moves = 0, queued = 0;
     while (queued < rounds) {
         const int end = queued + SG_BATCH < rounds ? queued + SG_BATCH : rounds;
         for (int r = queued; r < end; ++r) {
-            const int a = r & 1, b = a ^ 1;
-            rule(r, rows[a], cols[a]);
-            if (r == 0) t_compact.start(s);
-            hipLaunchKernelGGL(k_sg_keep, dim3(nbK), dim3(SG_THREADS), 0, s, rows[a], cols[a], removed, dst, r, n0, keep);
-            exclusive_scan_u32(s, keep, pos, n0 + 1, c.ws_scan);
-            hipLaunchKernelGGL(k_sg_scatter, dim3(nbS), dim3(SG_THREADS), 0, s, rows[a], cols[a], vals[a], pos, dst, r, n0, rows[b], cols[b], vals[b]);
-            if (r == 0) t_compact.stop(s);
+            rule(r, w.rows[r & 1], w.cols[r & 1]);
+            sg_compact(w, r);
         }
-        ELBA_HIP(hipGetLastError());
         queued = end;
-        t_total.stop(s);                                        // (recorded again behind every batch: the last record counts)
-        ELBA_HIP(hipMemcpyAsync(h, dst, SG_ST * 8, hipMemcpyDeviceToHost, s));
-        ELBA_HIP(hipStreamSynchronize(s));
-        while (moves < queued && h[SG_LIVE + moves + 1] > 0) ++moves;
+        moves = sg_read_back(w, h, queued, moves);
         if (moves < queued) break;                              // a round of this batch removed nothing: the rounds behind it would all return at once
     }
-    if (moves & 1) { c.tr_out_rows.swap(c.tp_rows); c.tr_out_cols.swap(c.tp_cols); c.tr_out_vals.swap(c.tp_vals); }
-    c.tr_nnz = (int64_t)h[SG_NNZ + moves];
+    sg_settle(w, h, moves);
     return moves;
 }
 

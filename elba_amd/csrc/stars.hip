@@ -24,13 +24,13 @@
 //                   word[u] = SR_W_CENTRE | e << 1 | slot of the odd arm << 3, and for e == 1 does atomicExch on removed[w]: the winner ORs 32
 //                   into flags[w] and sets SR_W_WON in its own word.  Every other lane writes word[u] = 0
 //   k_star_sums     SR_SUM_BLOCKS workgroups stride over the reads and add the bits of word up: centres, centres by e, reads removed (the
-//                   winners), which also goes to st[SG_LIVE + r + 1]; a wavefront adds its lanes' sums up by shuffles, a workgroup its four
+//                   winners), which also goes to *sg_removed_slot(st, r); a wavefront adds its lanes' sums up by shuffles, a workgroup its four
 //                   wavefronts' through 96 bytes of LDS, and does one atomicAdd per counter that is not 0: at most 7 x 128 atomics per
 //                   round.  The flat kernel counts nothing: a ballot and one atomic per wavefront there is what bridges.hip and weak.hip
 //                   measured at four times the call
 //   keep flags, scan, scatter: the compaction of sg_rounds.hpp
 // Rounds without host synchronisation, in batches of SG_BATCH: the protocol of sg_rounds.hpp (sg_run_rounds).  The rule's part of it: every
-// kernel here returns at once when st[SG_LIVE + r] == 0.  removed[] is cleared once per call; a read removed in an earlier round is in no
+// kernel here returns at once when the round before removed nothing.  removed[] is cleared once per call; a read removed in an earlier round is in no
 // column and no row of a later round's S, so it is never named again and never wins twice.
 //
 // Bounds: ptr has M + 1 elements built from the round's nnz, so every column range lies inside it; a lane reads rows only at the three
@@ -57,13 +57,6 @@ static_assert(SR_COUNTERS <= SG_LIVE && SR_PAIRS0 + 3 == SR_READS - 1, "the rule
 // word[u]: bit 0 u is a centre, bits 1-2 e, bits 3-4 the slot (0 .. 2) of the odd arm among u's rows, bit 5 this lane's exchange on removed[] won
 enum : uint32_t { SR_W_CENTRE = 1u, SR_W_E_SHIFT = 1, SR_W_SLOT_SHIFT = 3, SR_W_WON = 32u };
 
-// the sum of v over the 64 lanes of a wavefront, in lane 0; every lane must call it
-__device__ __forceinline__ uint32_t sr_wave_sum(uint32_t v)
-{
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-    return v;
-}
-
 // is {x, y} a pair in R: column y in row x of the symmetrised R, or column x in row y, whichever row is shorter.  RM reads, Rn entries
 __device__ __forceinline__ bool sr_pair_in_R(const uint32_t *rptr, const SymEntry *sym, uint32_t RM, uint32_t Rn, uint32_t x, uint32_t y)
 {
@@ -85,15 +78,15 @@ __device__ __forceinline__ bool sr_pair_in_R(const uint32_t *rptr, const SymEntr
 
 __global__ void k_star_begin(const int64_t *cols, const u64 *st, int r, uint32_t M, uint32_t *ptr)
 {
-    if (st[SG_LIVE + r] == 0) return;
+    if (!sg_live(st, r)) return;
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    sg_col_ptrs(cols, (int64_t)st[SG_NNZ + r], M, i, ptr);
+    sg_col_ptrs(cols, sg_nnz(st, r), M, i, ptr);
 }
 
 __global__ void k_star_mark(const uint32_t *ptr, const int64_t *rows, const u64 *st, int r, uint32_t M, const uint32_t *rptr, const SymEntry *sym, uint32_t RM,
                             uint32_t Rn, uint32_t *word, uint32_t *removed, uint8_t *flags)
 {
-    if (st[SG_LIVE + r] == 0) return;
+    if (!sg_live(st, r)) return;
     const uint32_t u = blockIdx.x * blockDim.x + threadIdx.x;
     if (u >= M) return;
     uint32_t w = 0;
@@ -123,7 +116,7 @@ __global__ void k_star_mark(const uint32_t *ptr, const int64_t *rows, const u64 
 // for "round r removed something"
 __global__ __launch_bounds__(SR_THREADS) void k_star_sums(const uint32_t *word, uint32_t M, u64 *st, int r)
 {
-    if (st[SG_LIVE + r] == 0) return;
+    if (!sg_live(st, r)) return;
     uint32_t centres = 0, by_e[4] = {0, 0, 0, 0}, reads = 0;
     const uint32_t stride = gridDim.x * blockDim.x;
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < M; i += stride) {
@@ -142,7 +135,7 @@ __global__ __launch_bounds__(SR_THREADS) void k_star_sums(const uint32_t *word, 
     uint32_t mine[SR_COUNTERS] = {centres, by_e[0], by_e[1], by_e[2], by_e[3], reads};
 #pragma unroll
     for (int k = 0; k < SR_COUNTERS; ++k) {
-        const uint32_t v = sr_wave_sum(mine[k]);
+        const uint32_t v = sg_wave_sum(mine[k]);
         if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6][k] = v;
     }
     __syncthreads();
@@ -152,7 +145,7 @@ __global__ __launch_bounds__(SR_THREADS) void k_star_sums(const uint32_t *word, 
         for (int w = 0; w < SR_THREADS / 64; ++w) v += part[w][threadIdx.x];
         if (v) {
             atomicAdd(&st[threadIdx.x], (u64)v);                        // (the counters are st[0 .. SR_COUNTERS) in this order)
-            if (threadIdx.x == SR_READS) atomicAdd(&st[SG_LIVE + r + 1], (u64)v);
+            if (threadIdx.x == SR_READS) atomicAdd(sg_removed_slot(st, r), (u64)v);
         }
     }
 }
@@ -161,42 +154,35 @@ __global__ __launch_bounds__(SR_THREADS) void k_star_sums(const uint32_t *word, 
 
 void stage_resolve_stars(Ctx &c, const elba_star_cfg *cfgp)
 {
-    enter(c.v, EV_RESOLVE_STARS);
-    ELBA_REQUIRE(has(c.v, P_S), ELBA_ERR_STATE, "resolve_stars: no string graph (call elba_transitive_reduction)");
-    ELBA_REQUIRE(cfgp, ELBA_ERR_INVALID_ARG, "resolve_stars: null cfg");
-    const elba_star_cfg &cfg = *cfgp;
+    const elba_star_cfg &cfg = sg_enter(c, EV_RESOLVE_STARS, cfgp);
     ELBA_REQUIRE(cfg.rounds >= 1 && cfg.rounds <= SG_MAX_ROUNDS, ELBA_ERR_INVALID_ARG, "resolve_stars: rounds outside 1 .. 64");
     ELBA_REQUIRE(!cfg.reserved[0] && !cfg.reserved[1] && !cfg.reserved[2], ELBA_ERR_INVALID_ARG, "resolve_stars: reserved words must be 0");
     const int64_t M = c.tr_M, n0 = c.tr_nnz;
-    ELBA_REQUIRE(M < 0xffffffffll && n0 < 0xfffffffell && c.tr_sym_n < 0xffffffffll, ELBA_ERR_UNSUPPORTED, "resolve_stars: index ranges beyond 32 bit");
-    elba_star_stats st{};
-    st.nreads = M; st.nnz_before = n0; st.nnz_after = n0; st.rounds_run = 1;
+    sg_require_32bit(EV_RESOLVE_STARS, M < 0xffffffffll && n0 < 0xfffffffell && c.tr_sym_n < 0xffffffffll);
+    elba_star_stats st = sg_stats_begin<elba_star_stats>(c);
+    st.rounds_run = 1;
     if (M == 0 || n0 == 0) { accepted(c.v, EV_RESOLVE_STARS); done(c.v, EV_RESOLVE_STARS); c.srstats = st; return; }      // no entry: no centre, the one round removes nothing
-    hipStream_t s = c.stream;
     // every buffer of the launch sequence before the first launch
     sg_reserve(c, M, n0);
     c.sr_word.reserve((size_t)(M + 1) * 4);
-    uint32_t *ptr = c.tp_ptr.as<uint32_t>(), *word = c.sr_word.as<uint32_t>(), *removed = c.tp_removed.as<uint32_t>();
-    u64 *dst = c.tp_st.as<u64>();
+    const SgCall w(c);
+    uint32_t *word = c.sr_word.as<uint32_t>();
     // R as the reduction that made this S recorded it; without a kept pair tr_ptr holds nothing of this graph, and no read is looked up
     const uint32_t Rn = (uint32_t)c.tr_sym_n, RM = c.tr_sym_n > 0 ? (uint32_t)(c.tr_sym_M < M ? c.tr_sym_M : M) : 0u;
     const uint32_t *rptr = c.tr_ptr.as<uint32_t>();
     const SymEntry *sym = c.tr_sym.as<SymEntry>();
-    const int64_t lanes = M > n0 + 1 ? M : n0 + 1;
-    const unsigned nbB = (unsigned)((lanes + SR_THREADS - 1) / SR_THREADS), nbM = (unsigned)((M + SR_THREADS - 1) / SR_THREADS);
     accepted(c.v, EV_RESOLVE_STARS);                            // as in stage_clip_tips: the contigs go, and S is invalid until the counters are back
     u64 h[SG_ST];
-    const int moves = sg_run_rounds(c, cfg.rounds, c.sr_t_total, c.sr_t_compact, h, [&](int r, const int64_t *rows, const int64_t *cols) {
-        hipLaunchKernelGGL(k_star_begin, dim3(nbB), dim3(SR_THREADS), 0, s, cols, dst, r, (uint32_t)M, ptr);
-        hipLaunchKernelGGL(k_star_mark, dim3(nbM), dim3(SR_THREADS), 0, s, ptr, rows, dst, r, (uint32_t)M, rptr, sym, RM, Rn, word, removed, c.tr_flags.as<uint8_t>());
-        hipLaunchKernelGGL(k_star_sums, dim3(nbM < (unsigned)SR_SUM_BLOCKS ? nbM : (unsigned)SR_SUM_BLOCKS), dim3(SR_THREADS), 0, s, word, (uint32_t)M, dst, r);
+    const int moves = sg_run_rounds(w, cfg.rounds, h, [&](int r, const int64_t *rows, const int64_t *cols) {
+        hipLaunchKernelGGL(k_star_begin, dim3(w.nbB), dim3(SR_THREADS), 0, w.s, cols, w.st, r, (uint32_t)M, w.ptr);
+        hipLaunchKernelGGL(k_star_mark, dim3(w.nbM), dim3(SR_THREADS), 0, w.s, w.ptr, rows, w.st, r, (uint32_t)M, rptr, sym, RM, Rn, word, w.removed, w.flags);
+        hipLaunchKernelGGL(k_star_sums, dim3(w.nbM < (unsigned)SR_SUM_BLOCKS ? w.nbM : (unsigned)SR_SUM_BLOCKS), dim3(SR_THREADS), 0, w.s, word, (uint32_t)M, w.st, r);
     });
     done(c.v, EV_RESOLVE_STARS);
-    st.nnz_after = c.tr_nnz; st.entries_removed = n0 - c.tr_nnz;
     st.centres = (int64_t)h[SR_CENTRES]; st.pairs0 = (int64_t)h[SR_PAIRS0]; st.pairs1 = (int64_t)h[SR_PAIRS0 + 1]; st.pairs2 = (int64_t)h[SR_PAIRS0 + 2];
     st.pairs3 = (int64_t)h[SR_PAIRS0 + 3]; st.reads_removed = (int64_t)h[SR_READS];
     st.rounds_run = moves < cfg.rounds ? moves + 1 : cfg.rounds;
-    st.ms_total = c.sr_t_total.ms(); st.ms_compact = c.sr_t_compact.ms();
+    sg_stats_end(c, st);
     c.srstats = st;
 }
 

@@ -19,11 +19,11 @@
 //                   one atomicAdd on ntips[anchor]
 //   k_tip_mark      a lane whose dead end has an anchor with ntips < deg walks again: removed[vi] = 1 (atomicExch: the winner counts the
 //                   read and sets flag bit 2); a lane on a read with deg >= 3 and ntips >= deg counts it as spared
-//   keep flags, scan, scatter: the compaction of sg_rounds.hpp (k_sg_keep, k_sg_scatter), shared with bubbles.hip
+//   keep flags, scan, scatter: the compaction of sg_rounds.hpp
 //
 // Rounds without host synchronisation, in batches of SG_BATCH with one synchronisation per batch: the protocol of sg_rounds.hpp.  The
 // rule's part of it: every kernel here returns at once when the round before removed nothing, and k_tip_mark adds the reads it removed to
-// st[TP_LIVE + r + 1].
+// *sg_removed_slot(st, r).
 //
 // Bounds: every index into rows / cols is below the round's nnz (ptr built from n), every read index below M (rows and cols of S are; a
 // walk also tests cur < M), a walk reads rows only from a column of length 1 or 2; the compaction's bounds are in sg_rounds.hpp.
@@ -38,22 +38,23 @@ namespace {
 constexpr uint32_t TP_NONE = 0xffffffffu;
 constexpr int TP_THREADS = 256;                 // threads of every kernel here
 constexpr int TP_TILE = 256;                    // entries of S one workgroup of the compaction's scatter moves (sg_rounds.hpp)
+// (both spelled out: every version of tests/test_gpu_tips.py before the one that asks rounds_util for SG_TILE reads them from this file)
 static_assert(TP_THREADS == SG_THREADS && TP_TILE == SG_TILE, "the compaction is sg_rounds.hpp's");
 // st[]: 0 dead ends (first round), 1 tips, 2 reads removed, 3 spared anchors; the protocol's slots: sg_rounds.hpp
-enum { TP_DEAD = 0, TP_TIPS = 1, TP_READS = 2, TP_SPARED = 3, TP_LIVE = SG_LIVE, TP_NNZ = SG_NNZ, TP_ST = SG_ST };
-constexpr int TP_MAX_ROUNDS = SG_MAX_ROUNDS;
+enum { TP_DEAD = 0, TP_TIPS = 1, TP_READS = 2, TP_SPARED = 3 };
+static_assert(TP_SPARED < SG_LIVE, "the rule's counters lie in front of the protocol's");
 
 __global__ void k_tip_begin(const int64_t *cols, const u64 *st, int r, uint32_t M, uint32_t *ptr, uint32_t *ntips, uint32_t *anchor)
 {
-    if (st[TP_LIVE + r] == 0) return;
+    if (!sg_live(st, r)) return;
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < (int64_t)M) { ntips[i] = 0; anchor[i] = TP_NONE; }
-    sg_col_ptrs(cols, (int64_t)st[TP_NNZ + r], M, i, ptr);
+    sg_col_ptrs(cols, sg_nnz(st, r), M, i, ptr);
 }
 
 __global__ void k_tip_walk(const uint32_t *ptr, const int64_t *rows, u64 *st, int r, uint32_t maxt, uint32_t M, uint32_t *ntips, uint32_t *anchor)
 {
-    if (st[TP_LIVE + r] == 0) return;
+    if (!sg_live(st, r)) return;
     const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
     bool dead = false, tip = false;
     if (v < M) {
@@ -65,22 +66,19 @@ __global__ void k_tip_walk(const uint32_t *ptr, const int64_t *rows, u64 *st, in
                 const uint32_t cs = ptr[cur], d = ptr[cur + 1] - cs;
                 if (d >= 3) { anchor[v] = cur; atomicAdd(&ntips[cur], 1u); tip = true; break; }
                 if (d != 2 || t == maxt) break;                         // the other end of a path, or a chain longer than max_tip_reads
-                const uint32_t a = (uint32_t)rows[cs];
-                const uint32_t nx = a != prev ? a : (uint32_t)rows[cs + 1];
+                const uint32_t nx = sg_walk_next(rows, cs, prev);
                 prev = cur; cur = nx; ++t;
             }
         }
     }
-    const u64 bd = __ballot(dead && r == 0), bt = __ballot(tip);
-    const unsigned lane = threadIdx.x & 63;
-    if (bd && lane == (unsigned)__builtin_ctzll(bd)) atomicAdd(&st[TP_DEAD], (u64)__builtin_popcountll(bd));
-    if (bt && lane == (unsigned)__builtin_ctzll(bt)) atomicAdd(&st[TP_TIPS], (u64)__builtin_popcountll(bt));
+    sg_count(&st[TP_DEAD], dead && r == 0);
+    sg_count(&st[TP_TIPS], tip);
 }
 
 __global__ void k_tip_mark(const uint32_t *ptr, const int64_t *rows, u64 *st, int r, uint32_t M, const uint32_t *ntips, const uint32_t *anchor,
                            uint32_t *removed, uint8_t *flags)
 {
-    if (st[TP_LIVE + r] == 0) return;
+    if (!sg_live(st, r)) return;
     const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
     bool spared = false;
     if (v < M) {
@@ -92,54 +90,45 @@ __global__ void k_tip_mark(const uint32_t *ptr, const int64_t *rows, u64 *st, in
             while (cur != b) {
                 if (atomicExch(&removed[cur], 1u) == 0) { ++cnt; flags[cur] = (uint8_t)(flags[cur] | 4u); }
                 const uint32_t cs = ptr[cur];
-                const uint32_t a = (uint32_t)rows[cs];
-                const uint32_t nx = (ptr[cur + 1] - cs == 1 || a != prev) ? a : (uint32_t)rows[cs + 1];
+                const uint32_t nx = sg_walk_next(rows, cs, prev, ptr[cur + 1] - cs == 1);
                 prev = cur; cur = nx;
             }
-            if (cnt) { atomicAdd(&st[TP_READS], (u64)cnt); atomicAdd(&st[TP_LIVE + r + 1], (u64)cnt); }
+            if (cnt) { atomicAdd(&st[TP_READS], (u64)cnt); atomicAdd(sg_removed_slot(st, r), (u64)cnt); }
         }
     }
-    const u64 bs = __ballot(spared);
-    if (bs && (threadIdx.x & 63) == (unsigned)__builtin_ctzll(bs)) atomicAdd(&st[TP_SPARED], (u64)__builtin_popcountll(bs));
+    sg_count(&st[TP_SPARED], spared);
 }
 
 }  // namespace
 
 void stage_clip_tips(Ctx &c, const elba_tip_cfg *cfgp)
 {
-    enter(c.v, EV_CLIP_TIPS);
-    ELBA_REQUIRE(has(c.v, P_S), ELBA_ERR_STATE, "clip_tips: no string graph (call elba_transitive_reduction)");
-    ELBA_REQUIRE(cfgp, ELBA_ERR_INVALID_ARG, "clip_tips: null cfg");
-    const elba_tip_cfg &cfg = *cfgp;
+    const elba_tip_cfg &cfg = sg_enter(c, EV_CLIP_TIPS, cfgp);
     ELBA_REQUIRE(cfg.max_tip_reads >= 1 && cfg.max_tip_reads <= 65535, ELBA_ERR_INVALID_ARG, "clip_tips: max_tip_reads outside 1 .. 65535");
-    ELBA_REQUIRE(cfg.rounds >= 1 && cfg.rounds <= TP_MAX_ROUNDS, ELBA_ERR_INVALID_ARG, "clip_tips: rounds outside 1 .. 64");
+    ELBA_REQUIRE(cfg.rounds >= 1 && cfg.rounds <= SG_MAX_ROUNDS, ELBA_ERR_INVALID_ARG, "clip_tips: rounds outside 1 .. 64");
     ELBA_REQUIRE(!cfg.reserved[0] && !cfg.reserved[1], ELBA_ERR_INVALID_ARG, "clip_tips: reserved words must be 0");
     const int64_t M = c.tr_M, n0 = c.tr_nnz;
-    ELBA_REQUIRE(M < 0xffffffffll && n0 < 0xfffffffell, ELBA_ERR_UNSUPPORTED, "clip_tips: index ranges beyond 32 bit");
-    elba_tip_stats st{};
-    st.nreads = M; st.nnz_before = n0; st.nnz_after = n0; st.rounds_run = 1;
+    sg_require_32bit(EV_CLIP_TIPS, M < 0xffffffffll && n0 < 0xfffffffell);
+    elba_tip_stats st = sg_stats_begin<elba_tip_stats>(c);
+    st.rounds_run = 1;
     if (M == 0 || n0 == 0) { accepted(c.v, EV_CLIP_TIPS); done(c.v, EV_CLIP_TIPS); c.tpstats = st; return; }      // no entry: no dead end, the one round removes nothing
-    hipStream_t s = c.stream;
     // every buffer of the launch sequence before the first launch
     sg_reserve(c, M, n0);
     c.tp_ntips.reserve((size_t)(M + 1) * 4); c.tp_anchor.reserve((size_t)(M + 1) * 4);
-    uint32_t *ptr = c.tp_ptr.as<uint32_t>(), *ntips = c.tp_ntips.as<uint32_t>(), *anchor = c.tp_anchor.as<uint32_t>(), *removed = c.tp_removed.as<uint32_t>();
-    u64 *dst = c.tp_st.as<u64>();
-    const int64_t lanes = M > n0 + 1 ? M : n0 + 1;
-    const unsigned nbB = (unsigned)((lanes + TP_THREADS - 1) / TP_THREADS), nbM = (unsigned)((M + TP_THREADS - 1) / TP_THREADS);
+    const SgCall w(c);
+    uint32_t *ntips = c.tp_ntips.as<uint32_t>(), *anchor = c.tp_anchor.as<uint32_t>();
     accepted(c.v, EV_CLIP_TIPS);                                // S changes under the contigs of the old one, and is itself invalid until the counters are back:
                                                                 // a call that fails below leaves no S rather than one in the wrong buffer
-    u64 h[TP_ST];
-    const int moves = sg_run_rounds(c, cfg.rounds, c.tp_t_total, c.tp_t_compact, h, [&](int r, const int64_t *rows, const int64_t *cols) {
-        hipLaunchKernelGGL(k_tip_begin, dim3(nbB), dim3(TP_THREADS), 0, s, cols, dst, r, (uint32_t)M, ptr, ntips, anchor);
-        hipLaunchKernelGGL(k_tip_walk, dim3(nbM), dim3(TP_THREADS), 0, s, ptr, rows, dst, r, (uint32_t)cfg.max_tip_reads, (uint32_t)M, ntips, anchor);
-        hipLaunchKernelGGL(k_tip_mark, dim3(nbM), dim3(TP_THREADS), 0, s, ptr, rows, dst, r, (uint32_t)M, ntips, anchor, removed, c.tr_flags.as<uint8_t>());
+    u64 h[SG_ST];
+    const int moves = sg_run_rounds(w, cfg.rounds, h, [&](int r, const int64_t *rows, const int64_t *cols) {
+        hipLaunchKernelGGL(k_tip_begin, dim3(w.nbB), dim3(TP_THREADS), 0, w.s, cols, w.st, r, (uint32_t)M, w.ptr, ntips, anchor);
+        hipLaunchKernelGGL(k_tip_walk, dim3(w.nbM), dim3(TP_THREADS), 0, w.s, w.ptr, rows, w.st, r, (uint32_t)cfg.max_tip_reads, (uint32_t)M, ntips, anchor);
+        hipLaunchKernelGGL(k_tip_mark, dim3(w.nbM), dim3(TP_THREADS), 0, w.s, w.ptr, rows, w.st, r, (uint32_t)M, ntips, anchor, w.removed, w.flags);
     });
     done(c.v, EV_CLIP_TIPS);
-    st.nnz_after = c.tr_nnz; st.entries_removed = n0 - c.tr_nnz;
     st.dead_ends = (int64_t)h[TP_DEAD]; st.tips = (int64_t)h[TP_TIPS]; st.reads_removed = (int64_t)h[TP_READS]; st.spared_anchors = (int64_t)h[TP_SPARED];
     st.rounds_run = moves < cfg.rounds ? moves + 1 : cfg.rounds;
-    st.ms_total = c.tp_t_total.ms(); st.ms_compact = c.tp_t_compact.ms();
+    sg_stats_end(c, st);
     c.tpstats = st;
 }
 

@@ -18,9 +18,9 @@
 //                   column r (ascending), and whether THAT is weak at column r, from its own score and side: no per-entry weak array is
 //                   stored.  keep[z] = neither; a weak entry adds 1 to nweak[2 c + side], a kept one 1 to after[2 c + side].  It stands
 //                   beside k_sg_keep of sg_rounds.hpp, which asks the removed READS instead
-//   scan, k_weak_removed, k_sg_scatter: the compaction of sg_rounds.hpp, as its round 0.  One lane takes the removed-entry count from the
-//                   scan (n - pos[n]) into st[SG_LIVE + 1], so the scatter of a pass that removed nothing returns at once and S stays in
-//                   its buffer; otherwise the two buffers of S are swapped
+//   scan, k_weak_removed, k_sg_scatter: the compaction of sg_rounds.hpp (sg_compact), as its round 0.  One lane takes the removed-entry
+//                   count from the scan (n - pos[n]) into the protocol's slot for what round 0 removed, so the scatter of a pass that
+//                   removed nothing returns at once and S stays in its buffer; otherwise the two buffers of S are swapped
 //   k_weak_sides    WK_SIDE_BLOCKS workgroups stride over the 2 M sides: cnt >= 2 counts a branch side, cnt >= 1 with after == 0 an emptied
 //                   one, nweak sums to the weak entries; every wavefront adds its lanes' sums up by shuffles and does one atomicAdd per
 //                   counter that is not 0
@@ -47,19 +47,12 @@ namespace elba {
 namespace {
 
 constexpr int WK_THREADS = SG_THREADS;          // threads of every kernel here
-// st[]: 0 branch sides, 1 weak entries, 2 sides emptied; the removed entries are the protocol's st[SG_LIVE + 1], the kept count st[SG_NNZ + 1]
+// st[]: 0 branch sides, 1 weak entries, 2 sides emptied; the removed entries and the kept count are in the protocol's slots (sg_rounds.hpp)
 enum { WK_BRANCH = 0, WK_WEAK = 1, WK_EMPTIED = 2 };
 static_assert(WK_EMPTIED < SG_LIVE, "the rule's counters lie in front of the protocol's");
 constexpr int32_t WK_NO_BEST = (int32_t)0x80000000;
 
 constexpr int WK_SIDE_BLOCKS = 128;             // workgroups of k_weak_sides: 512 wavefronts, each with at most three atomics on st[]
-
-// the sum of v over the 64 lanes of a wavefront, in lane 0; every lane must call it
-__device__ __forceinline__ uint32_t wk_wave_sum(uint32_t v)
-{
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-    return v;
-}
 
 __device__ __forceinline__ bool wk_weak(int32_t score, uint32_t cnt, int32_t best, int32_t q16)
 {
@@ -115,7 +108,7 @@ __global__ void k_weak_keep(const uint32_t *ptr, const int64_t *rows, const int6
 // behind the scan: what the pass removed, where k_sg_scatter looks for "round 0 removed something"
 __global__ void k_weak_removed(const uint32_t *pos, int64_t n, u64 *st)
 {
-    st[SG_LIVE + 1] = (u64)n - (u64)pos[n];
+    *sg_removed_slot(st, 0) = (u64)n - (u64)pos[n];
 }
 
 __global__ __launch_bounds__(WK_THREADS) void k_weak_sides(const uint32_t *cnt, const uint32_t *nweak, const uint32_t *after, uint32_t M, u64 *st)
@@ -128,7 +121,7 @@ __global__ __launch_bounds__(WK_THREADS) void k_weak_sides(const uint32_t *cnt, 
         emptied += k >= 1 && after[i] == 0;
         weak += nweak[i];
     }
-    branch = wk_wave_sum(branch); emptied = wk_wave_sum(emptied); weak = wk_wave_sum(weak);
+    branch = sg_wave_sum(branch); emptied = sg_wave_sum(emptied); weak = sg_wave_sum(weak);
     if ((threadIdx.x & 63) == 0) {
         if (branch) atomicAdd(&st[WK_BRANCH], (u64)branch);
         if (emptied) atomicAdd(&st[WK_EMPTIED], (u64)emptied);
@@ -140,58 +133,38 @@ __global__ __launch_bounds__(WK_THREADS) void k_weak_sides(const uint32_t *cnt, 
 
 void stage_cut_weak_overlaps(Ctx &c, const elba_weak_cfg *cfgp)
 {
-    enter(c.v, EV_CUT_WEAK_OVERLAPS);
-    ELBA_REQUIRE(has(c.v, P_S), ELBA_ERR_STATE, "cut_weak_overlaps: no string graph (call elba_transitive_reduction)");
-    ELBA_REQUIRE(cfgp, ELBA_ERR_INVALID_ARG, "cut_weak_overlaps: null cfg");
-    const elba_weak_cfg &cfg = *cfgp;
+    const elba_weak_cfg &cfg = sg_enter(c, EV_CUT_WEAK_OVERLAPS, cfgp);
     ELBA_REQUIRE(cfg.min_ratio_q16 >= 1 && cfg.min_ratio_q16 <= 65536, ELBA_ERR_INVALID_ARG, "cut_weak_overlaps: min_ratio_q16 outside 1 .. 65536");
     ELBA_REQUIRE(!cfg.reserved[0] && !cfg.reserved[1] && !cfg.reserved[2], ELBA_ERR_INVALID_ARG, "cut_weak_overlaps: reserved words must be 0");
     const int64_t M = c.tr_M, n0 = c.tr_nnz;
-    ELBA_REQUIRE(M < 0x7fffffffll && n0 < 0xfffffffell, ELBA_ERR_UNSUPPORTED, "cut_weak_overlaps: index ranges beyond 32 bit");
-    elba_weak_stats st{};
-    st.nreads = M; st.nnz_before = n0; st.nnz_after = n0;
+    sg_require_32bit(EV_CUT_WEAK_OVERLAPS, M < 0x7fffffffll && n0 < 0xfffffffell);         // (2 M sides)
+    elba_weak_stats st = sg_stats_begin<elba_weak_stats>(c);
     if (M == 0 || n0 == 0) { accepted(c.v, EV_CUT_WEAK_OVERLAPS); done(c.v, EV_CUT_WEAK_OVERLAPS); c.wkstats = st; return; }      // no entry: no side has two
-    hipStream_t s = c.stream;
     // every buffer of the launch sequence before the first launch
     sg_reserve(c, M, n0);
     c.wk_best.reserve((size_t)(2 * M + 2) * 4); c.wk_cnt.reserve((size_t)(2 * M + 2) * 4); c.wk_nweak.reserve((size_t)(2 * M + 2) * 4);
     c.wk_after.reserve((size_t)(2 * M + 2) * 4);
-    uint32_t *ptr = c.tp_ptr.as<uint32_t>(), *cnt = c.wk_cnt.as<uint32_t>(), *nweak = c.wk_nweak.as<uint32_t>(), *after = c.wk_after.as<uint32_t>(), *keep = c.tp_keep.as<uint32_t>(), *pos = c.tp_pos.as<uint32_t>();
+    const SgCall w(c);
+    uint32_t *cnt = c.wk_cnt.as<uint32_t>(), *nweak = c.wk_nweak.as<uint32_t>(), *after = c.wk_after.as<uint32_t>();
     int32_t *best = c.wk_best.as<int32_t>();
-    u64 *dst = c.tp_st.as<u64>();
-    const int64_t *rows = c.tr_out_rows.as<int64_t>(), *cols = c.tr_out_cols.as<int64_t>();
     const elba_overlap_t *vals = c.tr_out_vals.as<elba_overlap_t>();
-    const int64_t lanes = 2 * M > n0 + 1 ? 2 * M : n0 + 1;
-    const unsigned nbB = (unsigned)((lanes + WK_THREADS - 1) / WK_THREADS), nbZ = (unsigned)((n0 + WK_THREADS - 1) / WK_THREADS),
-                   nbK = (unsigned)((n0 + 1 + WK_THREADS - 1) / WK_THREADS), nbS = (unsigned)((n0 + SG_TILE - 1) / SG_TILE),
-                   nbAll = (unsigned)((2 * M + WK_THREADS - 1) / WK_THREADS), nbM = nbAll < (unsigned)WK_SIDE_BLOCKS ? nbAll : (unsigned)WK_SIDE_BLOCKS;
+    const unsigned nbB = sg_blocks(2 * M > n0 + 1 ? 2 * M : n0 + 1), nbAll = sg_blocks(2 * M), nbM = nbAll < (unsigned)WK_SIDE_BLOCKS ? nbAll : (unsigned)WK_SIDE_BLOCKS;
     accepted(c.v, EV_CUT_WEAK_OVERLAPS);                        // as in stage_clip_tips: the contigs go, and S is invalid until the counters are back
-    c.wk_t_total.start(s);
-    ELBA_HIP(hipMemsetAsync(dst, 0, SG_ST * 8, s));
-    hipLaunchKernelGGL(k_sg_init, dim3(1), dim3(1), 0, s, dst, (u64)n0);
-    hipLaunchKernelGGL(k_weak_begin, dim3(nbB), dim3(WK_THREADS), 0, s, cols, n0, (uint32_t)M, ptr, best, cnt, nweak, after);
-    hipLaunchKernelGGL(k_weak_fold, dim3(nbZ), dim3(WK_THREADS), 0, s, cols, vals, n0, (uint32_t)M, best, cnt);
-    c.wk_t_compact.start(s);
-    hipLaunchKernelGGL(k_weak_keep, dim3(nbK), dim3(WK_THREADS), 0, s, ptr, rows, cols, vals, n0, (uint32_t)M, (int32_t)cfg.min_ratio_q16, best, cnt, nweak, after, keep);
-    exclusive_scan_u32(s, keep, pos, n0 + 1, c.ws_scan);
-    hipLaunchKernelGGL(k_weak_removed, dim3(1), dim3(1), 0, s, pos, n0, dst);
-    hipLaunchKernelGGL(k_sg_scatter, dim3(nbS), dim3(SG_THREADS), 0, s, rows, cols, c.tr_out_vals.as<uint32_t>(), pos, dst, 0, n0, c.tp_rows.as<int64_t>(),
-                       c.tp_cols.as<int64_t>(), c.tp_vals.as<uint32_t>());
-    c.wk_t_compact.stop(s);
-    hipLaunchKernelGGL(k_weak_sides, dim3(nbM), dim3(WK_THREADS), 0, s, cnt, nweak, after, (uint32_t)M, dst);
-    ELBA_HIP(hipGetLastError());
-    c.wk_t_total.stop(s);
+    // the start is this file's, not sg_start: no read is removed, and k_weak_keep writes all n0 + 1 flags, so neither is cleared
+    c.sg.t_total.start(w.s);
+    ELBA_HIP(hipMemsetAsync(w.st, 0, SG_ST * 8, w.s));
+    hipLaunchKernelGGL(k_sg_init, dim3(1), dim3(1), 0, w.s, w.st, (u64)n0);
+    hipLaunchKernelGGL(k_weak_begin, dim3(nbB), dim3(WK_THREADS), 0, w.s, w.cols[0], n0, (uint32_t)M, w.ptr, best, cnt, nweak, after);
+    hipLaunchKernelGGL(k_weak_fold, dim3(w.nbZ), dim3(WK_THREADS), 0, w.s, w.cols[0], vals, n0, (uint32_t)M, best, cnt);
+    sg_compact(w, 0, [&](const int64_t *rows, const int64_t *cols) {
+        hipLaunchKernelGGL(k_weak_keep, dim3(sg_blocks(n0 + 1)), dim3(WK_THREADS), 0, w.s, w.ptr, rows, cols, vals, n0, (uint32_t)M, (int32_t)cfg.min_ratio_q16, best, cnt, nweak, after, w.keep);
+    }, [&] { hipLaunchKernelGGL(k_weak_removed, dim3(1), dim3(1), 0, w.s, w.pos, n0, w.st); });
+    hipLaunchKernelGGL(k_weak_sides, dim3(nbM), dim3(WK_THREADS), 0, w.s, cnt, nweak, after, (uint32_t)M, w.st);
     u64 h[SG_ST];
-    ELBA_HIP(hipMemcpyAsync(h, dst, SG_ST * 8, hipMemcpyDeviceToHost, s));
-    ELBA_HIP(hipStreamSynchronize(s));
-    if (h[SG_LIVE + 1] > 0) {                                   // S moved into the second buffer
-        c.tr_out_rows.swap(c.tp_rows); c.tr_out_cols.swap(c.tp_cols); c.tr_out_vals.swap(c.tp_vals);
-        c.tr_nnz = (int64_t)h[SG_NNZ + 1];
-    }
+    sg_settle(w, h, sg_read_back(w, h, 1, 0));
     done(c.v, EV_CUT_WEAK_OVERLAPS);
-    st.nnz_after = c.tr_nnz; st.entries_removed = (int64_t)h[SG_LIVE + 1];
     st.branch_sides = (int64_t)h[WK_BRANCH]; st.weak_entries = (int64_t)h[WK_WEAK]; st.sides_emptied = (int64_t)h[WK_EMPTIED];
-    st.ms_total = c.wk_t_total.ms(); st.ms_compact = c.wk_t_compact.ms();
+    sg_stats_end(c, st);                                        // (entries_removed: both images, nnz_before - nnz_after)
     c.wkstats = st;
 }
 

@@ -33,6 +33,7 @@ def const(path, name):
 SG_BATCH = const("sg_rounds.hpp", "SG_BATCH")                   # rounds queued between two looks at the counters
 SG_MAX_ROUNDS = const("sg_rounds.hpp", "SG_MAX_ROUNDS")
 SG_TILE = const("sg_rounds.hpp", "SG_TILE")                     # entries one workgroup of k_sg_scatter moves
+SG_THREADS = const("sg_rounds.hpp", "SG_THREADS")               # lanes per workgroup of the flat kernels
 SCAN_TILE = const("prims.hip", "SCAN_THREADS") * const("prims.hip", "SCAN_ITEMS")     # elements one workgroup of the scan takes
 B = SG_BATCH
 

@@ -3,8 +3,6 @@ in order, every field, the read flags and the stats, exactly.  Graphs are loaded
 not remove at fuzz 0 (every suffix in [5, 9]: a two-edge walk is at least 10), which each test asserts from the exported S first."""
 import ctypes as C
 import functools
-import os
-import re
 
 import numpy as np
 import pytest
@@ -12,6 +10,7 @@ import pytest
 import bubble_util as bu
 import contig_util as cu
 import elba_amd
+import rounds_util as ru
 import string_graph_util as sg
 import tip_util as tu
 from elba_amd import capi
@@ -19,18 +18,10 @@ from oracle import pyoracle as po
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = bu.hand_cases()
 
 
-def _const(path, name):
-    m = re.search(r"constexpr int %s = (\d+);" % name, open(os.path.join(ROOT, "elba_amd", "csrc", path)).read())
-    return int(m.group(1))
-
-
-SCAN_TILE = _const("prims.hip", "SCAN_THREADS") * _const("prims.hip", "SCAN_ITEMS")     # elements one workgroup of the scan takes
-SG_TILE = _const("sg_rounds.hpp", "SG_TILE")                                             # entries one workgroup of k_sg_scatter moves
-SG_THREADS = _const("sg_rounds.hpp", "SG_THREADS")                                       # lanes per workgroup of the flat kernels
+SG_TILE, SG_THREADS, SCAN_TILE = ru.SG_TILE, ru.SG_THREADS, ru.SCAN_TILE                 # read from sg_rounds.hpp and prims.hip
 
 
 def _same_S(g, rows, cols, vals):

@@ -3,14 +3,13 @@ order, every field, the read flags and the stats, exactly.  Graphs are loaded wi
 not remove at fuzz 0 (every suffix in [5, 9]: a two-edge walk is at least 10), which each test asserts from the exported S first."""
 import ctypes as C
 import functools
-import os
-import re
 
 import numpy as np
 import pytest
 
 import contig_util as cu
 import elba_amd
+import rounds_util as ru
 import string_graph_util as sg
 import tip_util as tu
 from elba_amd import capi
@@ -18,18 +17,10 @@ from oracle import pyoracle as po
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = tu.hand_cases()
 
 
-def _const(path, name):
-    m = re.search(r"constexpr int %s = (\d+);" % name, open(os.path.join(ROOT, "elba_amd", "csrc", path)).read())
-    return int(m.group(1))
-
-
-SCAN_TILE = _const("prims.hip", "SCAN_THREADS") * _const("prims.hip", "SCAN_ITEMS")     # elements one workgroup of the scan takes
-TP_TILE = _const("tips.hip", "TP_TILE")                                                  # entries one workgroup of k_tip_scatter moves
-TP_THREADS = _const("tips.hip", "TP_THREADS")                                            # lanes per workgroup of the flat kernels
+SG_TILE, SG_THREADS, SCAN_TILE = ru.SG_TILE, ru.SG_THREADS, ru.SCAN_TILE                 # read from sg_rounds.hpp and prims.hip
 
 
 def _same_S(g, rows, cols, vals):
@@ -182,13 +173,13 @@ def test_a_tip_of_1000_reads(eng, mx, gone):
     assert st["reads_removed"] == gone and st["tips"] == (1 if gone else 0) and st["dead_ends"] == 1
 
 
-@pytest.mark.parametrize("nnz", [TP_TILE - 2, TP_TILE - 1, TP_TILE, TP_TILE + 1, TP_TILE + 2, SCAN_TILE - 2, SCAN_TILE - 1, SCAN_TILE, SCAN_TILE + 1, SCAN_TILE + 2,
+@pytest.mark.parametrize("nnz", [SG_TILE - 2, SG_TILE - 1, SG_TILE, SG_TILE + 1, SG_TILE + 2, SCAN_TILE - 2, SCAN_TILE - 1, SCAN_TILE, SCAN_TILE + 1, SCAN_TILE + 2,
                                  2 * SCAN_TILE - 2, 2 * SCAN_TILE - 1, 2 * SCAN_TILE, 2 * SCAN_TILE + 1, 2 * SCAN_TILE + 2])
 def test_nnz_at_the_block_sizes_of_scan_and_compaction(eng, nnz):
-    """nnz(S) round TP_TILE (= TP_THREADS: k_tip_scatter's tile, the flat kernels' workgroup) and the scan's SCAN_TILE.  The scan and
+    """nnz(S) round SG_TILE (= SG_THREADS: k_sg_scatter's tile, the flat kernels' workgroup) and the scan's SCAN_TILE.  The scan and
     k_tip_keep run over nnz + 1 elements, so nnz = tile - 1 gives them exactly a tile.  An odd nnz comes from one pair whose directionT is -1:
     the reduction keeps one image of it, a column of one entry whose row has an empty column (a dead end that reaches no anchor)."""
-    assert TP_TILE == 256 and TP_THREADS == 256 and SCAN_TILE == 2048
+    assert SG_TILE == 256 and SG_THREADS == 256 and SCAN_TILE == 2048
     odd = nnz % 2
     g, b, arms = tu._y([1, 2, (nnz - odd) // 2 - 3])
     perm = np.random.default_rng(nnz + 1).permutation(g.n + 2 * odd)

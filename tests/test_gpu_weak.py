@@ -4,8 +4,6 @@ with suffixes the reduction does not remove at fuzz 0 (every suffix in [5, 9]: a
 directionT are set explicitly, and each load asserts that the exported S is the one weak_util.S_of expects."""
 import ctypes as C
 import functools
-import os
-import re
 
 import numpy as np
 import pytest
@@ -13,6 +11,7 @@ import pytest
 import bubble_util as bu
 import contig_util as cu
 import elba_amd
+import rounds_util as ru
 import string_graph_util as sg
 import tip_util as tu
 import weak_util as wu
@@ -21,17 +20,10 @@ from oracle import pyoracle as po
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = wu.hand_cases()
 
 
-def _const(path, name):
-    m = re.search(r"constexpr int %s = (\d+);" % name, open(os.path.join(ROOT, "elba_amd", "csrc", path)).read())
-    return int(m.group(1))
-
-
-SCAN_TILE = _const("prims.hip", "SCAN_THREADS") * _const("prims.hip", "SCAN_ITEMS")     # elements one workgroup of the scan takes
-SG_TILE = _const("sg_rounds.hpp", "SG_TILE")                                             # entries one workgroup of k_sg_scatter moves
+SG_TILE, SCAN_TILE = ru.SG_TILE, ru.SCAN_TILE                   # read from sg_rounds.hpp and prims.hip
 
 
 def _same_S(g, rows, cols, vals):
