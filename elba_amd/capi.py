@@ -110,6 +110,21 @@ class Contigs(C.Structure):
                 ("chain_prefix", C.c_void_p), ("chain_strand", C.c_void_p)]
 
 
+class Links(C.Structure):
+    _fields_ = [("n", C.c_int64), ("links", C.c_void_p)]
+
+
+class GraphStats(C.Structure):
+    _fields_ = [("segments", C.c_int64), ("candidates", C.c_int64), ("links", C.c_int64), ("closures", C.c_int64), ("twisted", C.c_int64),
+                ("unplaced", C.c_int64), ("clamped", C.c_int64), ("asymmetric", C.c_int64), ("ms_total", C.c_float), ("reserved", C.c_int32)]
+
+
+# elba_link_t: 24 bytes
+LINK_DTYPE = np.dtype([("from", "<u4"), ("to", "<u4"), ("from_read", "<u4"), ("to_read", "<u4"), ("overlap", "<i4"), ("from_rev", "u1"), ("to_rev", "u1"),
+                       ("flags", "u1"), ("reserved", "u1")])
+LINK_CLOSURE = 1          # elba_link_t.flags bit 0
+
+
 class PileupCfg(C.Structure):
     _fields_ = [("mode", C.c_int32), ("margin", C.c_int32), ("min_depth", C.c_int32), ("min_run", C.c_int32), ("trim_len", C.c_int32), ("reserved", C.c_int32)]
 
@@ -242,6 +257,7 @@ EXPORTED_SYMBOLS = [
     "elba_trim_reads", "elba_export_trim_map", "elba_free_trim_map", "elba_get_trimmed_reads_device", "elba_adopt_trimmed_reads",
     "elba_clip_tips", "elba_pop_bubbles", "elba_cut_weak_overlaps", "elba_cut_bridges", "elba_resolve_stars",
     "elba_set_reads_text", "elba_export_read_index",
+    "elba_export_assembly_links", "elba_free_links",
 ]
 
 _lib = None
@@ -304,6 +320,8 @@ def load_library():
     L.elba_export_contigs.restype = i32; L.elba_export_contigs.argtypes = [vp, C.POINTER(Contigs)]
     L.elba_free_contigs.restype = None; L.elba_free_contigs.argtypes = [C.POINTER(Contigs)]
     L.elba_export_read_contigs.restype = i32; L.elba_export_read_contigs.argtypes = [vp, vp, i64]
+    L.elba_export_assembly_links.restype = i32; L.elba_export_assembly_links.argtypes = [vp, C.POINTER(Links), C.POINTER(GraphStats)]
+    L.elba_free_links.restype = None; L.elba_free_links.argtypes = [C.POINTER(Links)]
     L.elba_read_pileup.restype = i32; L.elba_read_pileup.argtypes = [vp, C.POINTER(PileupCfg), C.POINTER(PileupStats)]
     L.elba_export_pileup.restype = i32; L.elba_export_pileup.argtypes = [vp, C.POINTER(Pileup)]
     L.elba_free_pileup.restype = None; L.elba_free_pileup.argtypes = [C.POINTER(Pileup)]
@@ -702,6 +720,20 @@ class Engine:
         out = np.zeros(int(nreads), dtype=np.int64)
         self._check(self.L.elba_export_read_contigs(self.h, out.ctypes.data, int(nreads)))
         return out
+
+    def assembly_links(self):
+        """The links of the assembly graph over the contigs of the last generate_contigs (include/elba_amd.h states the rule): the edges
+        of S at branch reads as (from contig, orientation, to contig, orientation, overlap), plus one closure record per circular contig.
+        Returns (records as a LINK_DTYPE array sorted by (from_read, to_read), stats dict).  formats.write_gfa writes them."""
+        o, st = Links(), GraphStats()
+        self._check(self.L.elba_export_assembly_links(self.h, C.byref(o), C.byref(st)))
+        try:
+            links = _copy(o.links, int(o.n), LINK_DTYPE)
+        finally:
+            self.L.elba_free_links(C.byref(o))
+        out = _stats(st)
+        del out["reserved"]
+        return links, out
 
     # --- read pileups and chimera flags (src/PruneChimeras.cpp; after align_seeds, before transitive_reduction) ---
     def read_pileup(self, mode=0, margin=0, min_depth=1, min_run=1, trim_len=2500):

@@ -478,6 +478,23 @@ int elba_export_read_contigs(elba_ctx *ctx, int64_t *contig_of_read, int64_t nre
     });
 }
 
+int elba_export_assembly_links(elba_ctx *ctx, elba_links_t *out, elba_graph_stats *stats)
+{
+    return guarded(ctx, [&](Ctx &c) {
+        ELBA_REQUIRE(out, ELBA_ERR_INVALID_ARG, "export_assembly_links: null output");
+        memset(out, 0, sizeof(*out));
+        stage_export_assembly_links(c, out);
+        if (stats) *stats = c.gstats;
+    });
+}
+
+void elba_free_links(elba_links_t *l)
+{
+    if (!l) return;
+    free(l->links);
+    memset(l, 0, sizeof(*l));
+}
+
 int elba_export_contig_kinds(elba_ctx *ctx, uint8_t *kind, int64_t ncontigs)
 {
     return guarded(ctx, [&](Ctx &c) {
@@ -774,6 +791,7 @@ int elba_release_workspace(elba_ctx *ctx)
         c.csr_words.release(); c.kid_of_entry.release();
         c.cg_ptr.release(); c.cg_slot.release(); c.cg_kdeg.release(); c.cg_term.release(); c.cg_vinfo.release(); c.cg_ctr.release();   // contig scratch (the results stay)
         c.cg_flag.release(); c.cg_cidx.release(); c.cg_nel.release(); c.cg_eoff.release();
+        c.gl_ptr.release(); c.gl_bits.release(); c.gl_cnt.release(); c.gl_off.release(); c.gl_ctr.release(); c.gl_part.release(); c.gl_out.release();          // assembly-link scratch
         for (int b = 0; b < 2; ++b) { c.cg_far[b].release(); c.cg_rank[b].release(); c.cg_mn[b].release(); c.cg_cfar[b].release(); c.cg_crank[b].release(); }
         c.pu_k0.release(); c.pu_k1.release(); c.pu_eptr.release(); c.pu_head.release(); c.pu_hidx.release(); c.pu_delta.release();   // pileup scratch (the results stay)
         c.pu_dsum.release(); c.pu_gstart.release(); c.pu_tok.release(); c.pu_tpos.release(); c.pu_sel.release(); c.pu_rows.release(); c.pu_cols.release(); c.pu_vals.release();
@@ -834,6 +852,17 @@ int elba_get_stat(elba_ctx *ctx, const char *name, int64_t *value)
         else if (!strcmp(name, "contig_reads")) *value = has(c.v, P_S, P_CONTIGS) ? c.cstats.contig_reads : 0;
         else if (!strcmp(name, "contig_bases")) *value = has(c.v, P_S, P_CONTIGS) ? c.cstats.bases : 0;
         else if (!strcmp(name, "contig_branches")) *value = has(c.v, P_S, P_CONTIGS) ? c.cstats.branches : 0;
+        else if (!strncmp(name, "graph_", 6)) {                    // the last elba_export_assembly_links on the contigs that are valid now
+            const bool ok = has(c.v, P_S, P_CONTIGS) && c.gl_for == c.cg_serial;
+            const elba_graph_stats &g = c.gstats;
+            const char *f = name + 6;
+            int64_t x;
+            if (!strcmp(f, "segments")) x = g.segments; else if (!strcmp(f, "candidates")) x = g.candidates; else if (!strcmp(f, "links")) x = g.links;
+            else if (!strcmp(f, "closures")) x = g.closures; else if (!strcmp(f, "twisted")) x = g.twisted; else if (!strcmp(f, "unplaced")) x = g.unplaced;
+            else if (!strcmp(f, "clamped")) x = g.clamped; else if (!strcmp(f, "asymmetric")) x = g.asymmetric;
+            else throw Error{ELBA_ERR_INVALID_ARG, std::string("get_stat: unknown counter ") + name};
+            *value = ok ? x : 0;
+        }
         else if (!strcmp(name, "contig_rank_us")) *value = has(c.v, P_S, P_CONTIGS) ? (int64_t)(c.cstats.ms_rank * 1000.0f) : -1;
         else if (!strcmp(name, "resident_bytes_A")) {
             int64_t b = 0;

@@ -323,6 +323,13 @@ struct Ctx {
     EventTimer cg_t_total, cg_t_rank;
     elba_contig_stats cstats{};
 
+    // assembly links (graph_links.hip): all scratch — the column pointers of S, first / last / strand bits per read, link counts per read and
+    // their scan, the counters (per workgroup and summed), the records before they are copied out.  gl_for: the contig call (cg_serial) the counts in gstats belong to
+    DevBuf gl_ptr, gl_bits, gl_cnt, gl_off, gl_ctr, gl_part, gl_out;
+    EventTimer gl_t_total;
+    elba_graph_stats gstats{};
+    uint64_t cg_serial = 0, gl_for = 0;
+
     // read pileups (pileup.hip): results (seg_off, seg_start, seg_depth, trim, flags) survive elba_release_workspace, the rest is scratch
     int64_t pu_M = 0, pu_n = 0, pu_nseg = 0;
     DevBuf pu_k0, pu_k1, pu_eptr, pu_head, pu_hidx, pu_delta, pu_dsum, pu_gstart, pu_tok, pu_tpos, pu_ctr, pu_sel, pu_rows, pu_cols, pu_vals;
@@ -471,6 +478,7 @@ void stage_set_overlaps(Ctx &c, int64_t nreads, const int64_t *rows, const int64
 void stage_transitive_reduction(Ctx &c, double bad_read_cutoff, int fuzz);   // tr.hip
 void stage_generate_contigs(Ctx &c, int flags);                                          // contig.hip
 void stage_generate_contigs_ex(Ctx &c, const elba_contig_cfg *cfg);                      // contig.hip
+void stage_export_assembly_links(Ctx &c, elba_links_t *out);                             // graph_links.hip (out->links: malloc)
 void stage_read_pileup(Ctx &c, const elba_pileup_cfg *cfg);                   // pileup.hip
 void stage_prune_reads(Ctx &c, int mask, int64_t *kept);
 void stage_trim_reads(Ctx &c, const elba_trim_cfg *cfg);                      // trim.hip

@@ -385,7 +385,7 @@ void stage_generate_contigs(Ctx &c, int flags)
     st.components = st.branches + (int64_t)h[1] + st.used_components;     // CC on S without the branches' rows and columns: a branch read is a component of its own
     st.contig_reads = E; st.bases = bases; st.longest = (int64_t)h[7];
     st.ms_total = c.cg_t_total.ms(); st.ms_rank = c.cg_t_rank.ms();
-    c.cg_n = nc; c.cg_E = E; c.cg_bases = bases; c.cg_circular = ncirc; c.cg_singletons = nsingle; c.cstats = st; done(c.v, EV_GENERATE_CONTIGS);
+    c.cg_n = nc; c.cg_E = E; c.cg_bases = bases; c.cg_circular = ncirc; c.cg_singletons = nsingle; c.cstats = st; ++c.cg_serial; done(c.v, EV_GENERATE_CONTIGS);
 }
 
 void stage_generate_contigs_ex(Ctx &c, const elba_contig_cfg *cfg)

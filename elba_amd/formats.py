@@ -111,3 +111,31 @@ def write_contigs_fasta(path, seqs, first=0, kinds=None):
             f.write(b">contig%d%s\n" % (i + first, b" circular" if kinds is not None and int(kinds[i]) == 1 else b""))
             f.write(s.encode("ascii") if isinstance(s, str) else bytes(s))
             f.write(b"\n")
+
+
+def write_gfa(path, seqs, kinds, links, chains=None):
+    """The assembly graph as GFA 1: `H\tVN:Z:1.0`, one `S\tcontig<i>\t<seq>\tLN:i:<len>` per contig (the names of write_contigs_fasta;
+    with `chains`, the chain_off of Engine.export_contigs() or one chain per contig, also `\tRC:i:<reads>`), and one
+    `L\tcontig<a>\t+|-\tcontig<b>\t+|-\t<overlap>M` per record of Engine.assembly_links(), in their order, the closure records of circular
+    contigs (a link from the contig's end to its own start, 0M) included.  `kinds` is checked against the closures: one per circular contig."""
+    n = len(seqs)
+    if kinds is not None and len(kinds) != n:
+        raise ValueError("write_gfa: one kind per contig")
+    if chains is not None and len(chains) not in (n, n + 1):
+        raise ValueError("write_gfa: chains is chain_off (n + 1 offsets) or one chain per contig")
+    closed = sorted(int(r["from"]) for r in links if int(r["flags"]) & 1)
+    if kinds is not None and closed != [i for i in range(n) if int(kinds[i]) == 1]:
+        raise ValueError("write_gfa: the closure records are not those of the circular contigs")
+    with open(path, "wb") as f:
+        f.write(b"H\tVN:Z:1.0\n")
+        for i, s in enumerate(seqs):
+            b = s.encode("ascii") if isinstance(s, str) else bytes(s)
+            f.write(b"S\tcontig%d\t%s\tLN:i:%d" % (i, b, len(b)))
+            if chains is not None:
+                f.write(b"\tRC:i:%d" % (int(chains[i + 1]) - int(chains[i]) if len(chains) == n + 1 else len(chains[i])))
+            f.write(b"\n")
+        for r in links:
+            if int(r["from"]) >= n or int(r["to"]) >= n:
+                raise ValueError("write_gfa: a link names contig %d of %d" % (max(int(r["from"]), int(r["to"])), n))
+            f.write(b"L\tcontig%d\t%s\tcontig%d\t%s\t%dM\n" % (int(r["from"]), b"-" if int(r["from_rev"]) else b"+", int(r["to"]), b"-" if int(r["to_rev"]) else b"+",
+                                                                int(r["overlap"])))

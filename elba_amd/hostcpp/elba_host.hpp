@@ -27,6 +27,8 @@
 //   (none)                                                                    elba::CutWeakOverlaps(S, reads, min_ratio_q16): weak overlaps at branching read ends leave S
 //   asmtools/bridge_removal.py (a script run on the written-out graph)        elba::CutBridges(S, reads, max_bridge_reads, min_flank_reads): short chains between two long paths leave S
 //   asmtools/star_resolution.py (a script run on the written-out graphs)      elba::ResolveStars(S, reads, rounds): the stray arm of a three-armed star leaves S
+//   asmtools/create_gml.py, assemble_gml.py (scripts over the PAF files)      elba::assembly_links(S) + elba::write_gfa(...): the contigs as segments and the
+//                                                                             edges of S at branch reads as links, found on the GPU, written as GFA 1
 //
 // Errors: the reference asserts/aborts; here every failing C-ABI status throws elba::Error (status + text).
 // There is no CPU path: constructing an engine without a GPU throws ELBA_ERR_NO_DEVICE.
@@ -742,6 +744,54 @@ inline void parallel_write_contigs(const std::vector<std::string> &contigs, cons
     const std::string cfs = contig_filecontents.str();
     f.write(cfs.data(), (std::streamsize)cfs.size());
     if (!f) throw Error(ELBA_ERR_INVALID_ARG, "parallel_write_contigs: cannot write " + contigs_fname);
+}
+
+// assembly_links(S) — elba_export_assembly_links on the S and the contigs of the last GenerateContigs (the rule is stated in
+// include/elba_amd.h): the edges of S at branch reads as links between contig ends, one closure record per circular contig, sorted by
+// (from_read, to_read).  An export: S and the contigs stay as they are.
+inline std::vector<elba_link_t> assembly_links(StringGraph &S, elba_graph_stats *stats = nullptr)
+{
+    if (!S.engine) throw Error(ELBA_ERR_STATE, "assembly_links: the string graph is not on a device");
+    elba_links_t l;
+    elba_graph_stats st{};
+    S.engine->check(elba_export_assembly_links(S.engine->ctx, &l, &st));
+    std::vector<elba_link_t> links(l.links, l.links + l.n);
+    elba_free_links(&l);
+    if (stats) *stats = st;
+    return links;
+}
+
+// write_gfa — GFA 1, byte for byte what formats.write_gfa writes: `H\tVN:Z:1.0`, one `S\tcontig<i>\t<seq>\tLN:i:<len>` per contig (the names
+// of parallel_write_contigs; with chain_reads, the reads per contig, also `\tRC:i:<reads>`) and one `L\tcontig<a>\t+|-\tcontig<b>\t+|-\t<overlap>M`
+// per record, closures included.  kinds, if given, is checked against the closures: one per circular contig.
+inline void write_gfa(const std::string &gfa_fname, const std::vector<std::string> &contigs, const std::vector<uint8_t> *kinds, const std::vector<elba_link_t> &links,
+                      const std::vector<int64_t> *chain_reads = nullptr)
+{
+    const size_t n = contigs.size();
+    if (kinds && kinds->size() != n) throw Error(ELBA_ERR_INVALID_ARG, "write_gfa: one kind per contig");
+    if (chain_reads && chain_reads->size() != n) throw Error(ELBA_ERR_INVALID_ARG, "write_gfa: one read count per contig");
+    if (kinds) {
+        std::vector<uint32_t> closed, circular;
+        for (const elba_link_t &r : links) if (r.flags & 1) closed.push_back(r.from);
+        std::sort(closed.begin(), closed.end());
+        for (size_t i = 0; i < n; ++i) if ((*kinds)[i] == 1) circular.push_back((uint32_t)i);
+        if (closed != circular) throw Error(ELBA_ERR_INVALID_ARG, "write_gfa: the closure records are not those of the circular contigs");
+    }
+    std::stringstream out;
+    out << "H\tVN:Z:1.0\n";
+    for (size_t i = 0; i < n; ++i) {
+        out << "S\tcontig" << i << "\t" << contigs[i] << "\tLN:i:" << contigs[i].size();
+        if (chain_reads) out << "\tRC:i:" << (*chain_reads)[i];
+        out << "\n";
+    }
+    for (const elba_link_t &r : links) {
+        if (r.from >= n || r.to >= n) throw Error(ELBA_ERR_INVALID_ARG, "write_gfa: a link names a contig that is not there");
+        out << "L\tcontig" << r.from << "\t" << (r.from_rev ? "-" : "+") << "\tcontig" << r.to << "\t" << (r.to_rev ? "-" : "+") << "\t" << r.overlap << "M\n";
+    }
+    std::ofstream f(gfa_fname, std::ios::binary);
+    const std::string text = out.str();
+    f.write(text.data(), (std::streamsize)text.size());
+    if (!f) throw Error(ELBA_ERR_INVALID_ARG, "write_gfa: cannot write " + gfa_fname);
 }
 
 // ---- the reference's text outputs -------------------------------------------------------------------------------

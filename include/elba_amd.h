@@ -384,6 +384,55 @@ int  elba_export_contigs(elba_ctx *ctx, elba_contigs_t *out);
 void elba_free_contigs(elba_contigs_t *c);
 int  elba_export_read_contigs(elba_ctx *ctx, int64_t *contig_of_read, int64_t nreads);  /* contig index of every read, -1: in none (without the _ex flags: branch, singleton or cycle) */
 
+/* The assembly graph: the contigs as segments and the edges of S at branch reads as links between segment ends, the records of a GFA
+ * (formats.write_gfa, hostcpp write_gfa).  elba_generate_contigs* drops every read of degree > 2 with its edges; this call says which
+ * contig ends met at which branch read, in which orientation and with how many bases of overlap.  It is an export: it needs a valid S
+ * and valid contigs of it, and the reads the contig call needed (otherwise ELBA_ERR_STATE); it changes neither, invalidates nothing and
+ * keeps only scratch and the counts of its last call on the context.
+ * Segments are the contigs of the last successful elba_generate_contigs*, indexed as elba_export_contigs orders them.  A read is PLACED
+ * when elba_export_read_contigs gives it a contig; a placed read is FIRST in its chain, LAST, or both, and has the strand bit of its
+ * chain element; it is AS STORED in its contig when that bit is 0.  deg(x) = entries of column x of S.
+ *   step        for reads u < v with an entry in S, the step u -> v is the entry the contig walk reads at u (column u, row v: the
+ *               Overlap::Transpose of what is stored there): prefix p(u->v) = its suffixT, direction d = the two low bits of its
+ *               direction.  u is left reverse-complemented iff d & 2, v is entered as stored iff d & 1.  The step v -> u is the other half
+ *               of the same entry: p(v->u) = its suffix, d' = the low bits of its directionT.
+ *   candidate   every pair u < v with an entry in column u of S where deg(u) > 2 or deg(v) > 2.  (Edges between two reads of degree <= 2
+ *               lie inside a chain or close a cycle: no links.)
+ *   unplaced    a candidate one of whose reads is not placed: counted, not emitted.  After a contig call with both ELBA_CONTIG_* flags on a
+ *               graph whose reads with entries are unflagged and not empty there are none.
+ *   leaving u   the from-segment is u's contig.  from_rev = 0 when u is last and leaves in the orientation it has in the chain (reversed
+ *               iff its strand bit is 1); from_rev = 1 when u is first and leaves in the other orientation.  (A chain of one read is
+ *               therefore left reversed iff u is.)
+ *   entering v  the to-segment is v's contig.  to_rev = 0 when v is first and is entered in its chain orientation; to_rev = 1 when v is
+ *               last and is entered in the other orientation.
+ *   twisted     a candidate with both reads placed for which neither line of `leaving` or neither line of `entering` holds: the edge
+ *               hangs on the side of the read that is interior to its contig (both overlaps on one end).  Counted, not emitted.
+ *   overlap     min(len(u) - p(u->v), len(v) - p(v->u)), clamped to [0, min(bases of the two segments)]; `clamped` counts the links
+ *               whose value the clamp changed.  No prefix fails the call.
+ *   asymmetric  counts the emitted links whose d' is not d with its two bits exchanged, i.e. whose step v -> u is not the reverse
+ *               complement of u -> v.  Aligned graphs have none; loaded edge lists can.
+ *   closure     every contig of kind circular gives one record: from = to = the contig, from_rev = to_rev = 0, overlap 0 (the sequence
+ *               closes on itself without repeating a base), from_read = to_read = its start read, flags bit 0 set.
+ *   order       records ascend in (from_read, to_read); an edge link has from_read = u < to_read = v, a closure from_read = to_read, so
+ *               keys are unique and the result does not depend on the order in which reads or columns are visited.  Read ids are those
+ *               of chain_read.
+ * Stats: segments = contigs; candidates = links (edge links only) + twisted + unplaced; closures; clamped and asymmetric are over the edge
+ * links.  elba_get_stat "graph_segments", "graph_candidates", "graph_links", "graph_closures", "graph_twisted", "graph_unplaced",
+ * "graph_clamped", "graph_asymmetric": the last call's, 0 while the graph or its contigs are not valid.  Read ids beyond 32 bit:
+ * ELBA_ERR_UNSUPPORTED.  Cost: S once (8 + 36 bytes per entry), 8 bytes per read for the table and the scan, 24 bytes per record, one host
+ * synchronisation for the output size.  A column of more than 64 entries is worked on by a whole wavefront. */
+typedef struct { uint32_t from, to;            /* segment (contig) indices */
+                 uint32_t from_read, to_read;  /* the reads of the edge (closure: the start read twice) */
+                 int32_t  overlap;             /* bases, the GFA's <overlap>M */
+                 uint8_t  from_rev, to_rev;    /* 1 = '-' */
+                 uint8_t  flags;               /* bit 0: closure of a circular contig */
+                 uint8_t  reserved; } elba_link_t;
+typedef struct { int64_t n; elba_link_t *links; } elba_links_t;
+typedef struct { int64_t segments, candidates, links, closures, twisted, unplaced, clamped, asymmetric;
+                 float   ms_total; int32_t reserved; } elba_graph_stats;
+int  elba_export_assembly_links(elba_ctx *ctx, elba_links_t *out, elba_graph_stats *stats);   /* out->n = links + closures */
+void elba_free_links(elba_links_t *l);
+
 /* Tip clipping (not in the reference, whose GenerateContigs drops every read of degree > 2 with its edges: one stray read hanging off a good
  * path cuts it into three contigs and loses the branch read).  elba_clip_tips works on the S of elba_transitive_reduction, in place, between
  * that call and elba_generate_contigs*.  The rule is on degrees alone — no sequence, no suffix, no length in bases — and is stated on the
@@ -813,6 +862,8 @@ int  elba_set_option(elba_ctx *ctx, const char *name, int64_t value);
  *   "contig_count", "contig_cycles", "contig_circular", "contig_singletons", "contig_reads", "contig_bases", "contig_branches"
  *                            the last elba_generate_contigs[_ex], under the condition of the contig exports: 0 when the string graph or its
  *                            contigs are not valid ("contig_rank_us": -1)
+ *   "graph_segments", "graph_candidates", "graph_links", "graph_closures", "graph_twisted", "graph_unplaced", "graph_clamped", "graph_asymmetric"
+ *                            the last elba_export_assembly_links, under the same condition (0 also before the first call on these contigs)
  *   "text_tile_bytes", "text_scan_span"
  *                            constants of elba_set_reads_text: the bytes of the chunk one workgroup takes per trip of its two passes, and the
  *                            elements one workgroup of its scans covers (longer arrays make the scan recurse) */
