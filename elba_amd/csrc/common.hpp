@@ -160,7 +160,6 @@ struct Options {
     bool csr_pairs_late = false; // dense matrices from the two-level partition: the CSR build's sort pairs written by the CSR build, not by the bucket kernels (A/B)
     bool msd_rank = false;      // k-mer stage: column ranks whatever UPPER is (tests)
     bool msd_no_rank = false;   // k-mer stage: entries without their column's rank — the emit kernels sort by ranges of the 16 value bits (A/B; what runs when the payload leaves no room)
-    bool msd_no_emit8 = false;  // k-mer stage: buckets of up to 2048 entries through the 512-lane emit kernel too (A/B)
     int ell_slot_cap = 0;       // test hook: the padded column store pretends to hold this many gather slots only (0: its real size)
     int slab_pct = 175;         // SpGEMM: a row's slab holds this many percent of the mirrored entries the measured ratio predicts for it (+ SLAB_PAD)
     int slab_q16 = 0;           // test hook: slab entries per row entry of A in 1/65536 units, instead of the measured ratio (small matrices take no sample)
@@ -178,7 +177,7 @@ struct Options {
     bool trace = false;         // progress lines on stderr
     bool measure_prep = false;  // diagnostic (bench.py, "spgemm_prep"): elba_count_kmers runs its emit kernels a second time WITHOUT what they write for the SpGEMM's sake alone (hint bits,
                                 // inline partners, gather slots + padded columns), both runs bracketed by events: elba_get_stat("spgemm_prep_us") = the difference (kmer_msd.hip)
-    int64_t tune[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // A/B switches of the round in progress ("tune0" .. "tune7"): what each means is said where it is read
+    int64_t tune[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // A/B switches ("tune1" .. "tune5", "tune7"; entries 0 and 6 are retired and stay zero): what each means is said where it is read
     int msd_wide_bits = 0;      // tests: value bits the partition of the 19 <= k <= 31 path takes (0: chosen from the number of instances; batched: each pass's, at least 11 + its first level's extra bits)
     int64_t kmer_batch_instances = 0;      // k-mer stage (reads, k >= 9): more instances than this are counted in passes over value ranges (0: 0xE0000000 — what a 32-bit place holds; k > 31: also no more than the device memory holds); tests force passes on small sets
     int msd_small_cap = 0;      // tests: buckets with more entries than this go to the crowded-bucket kernel (0 = its real capacity)

@@ -36,8 +36,8 @@ namespace {
 
 #include "kmer_enum.hpp"
 
-// (the tile sizes, digit widths and VBITS: msd_plan.hpp, with the ELBA_MT_* / ELBA_W2_* defaults)
-constexpr int MT_THREADS = ELBA_MT_THREADS, MT_ITEMS = ELBA_MT_ITEMS, MT_MAXBINS = 1 << MT_MAXBITS;
+// (the workgroup and tile sizes, digit widths and VBITS: msd_plan.hpp)
+constexpr int MT_MAXBINS = 1 << MT_MAXBITS;
 constexpr int BK_THREADS = 1024;
 constexpr uint32_t EW = 2048;                 // entries of a bucket half staged at a time (a window of its columns)
 constexpr uint32_t KW = EW / 2 + 1;           // columns such a window can hold (a reliable column has >= 2 entries)
@@ -120,9 +120,7 @@ __device__ __forceinline__ void enum_consecutive(const EnumParams &e, const Bloc
     const int k = e.k;
     const uint64_t kmask = ~0ull << (64 - 2 * k);
     if (wbase >= e.I) return;
-#ifndef ELBA_ENUM_ROLL
     if (ITEMS + k - 1 <= 32) { enum_consecutive_one_window<ITEMS>(e, block_read, wbase, f); return; }
-#endif
     const ReadCursor rc = cursor_at(e, block_read, wbase);
     uint32_t r = rc.lo;
     uint64_t off_lo = rc.off_lo, off_hi = rc.off_hi, boff = rc.boff;
@@ -290,7 +288,9 @@ __device__ unsigned long long g_sc_phase[2][2][12];
 #else
 #define ELBA_SSTAMP(k) do { } while (0)
 #endif
-__device__ __forceinline__ void lds_sync_fwd() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }      // LDS-only workgroup barrier (lds_sync below)
+// LDS-only workgroup barrier: global stores that the workgroup never reads back (a tile's, a bucket's) stay in flight
+__device__ __forceinline__ void lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
 // ---- stable scatter of one tile by one digit --------------------------------------------------------------------------------------
 // ENUM: the tile's keys are enumerated from the reads (tile = 8192 consecutive instances) and the digit is the top b1 value bits, which the word
 // written does not hold any more.  !ENUM: the tile's keys are read from `in` (a bucket-aligned tile) and the digit is (word >> shift) & mask.
@@ -312,7 +312,7 @@ __global__ __launch_bounds__(MT_THREADS) void k_msd_scatter(EnumParams e, const 
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const unsigned long long lane_le = (2ull << lane) - 1ull;      // (a place t = it * MT_THREADS + tid of the write-out has t & 63 == lane)
     // The keys of a tile live in registers from where they are fetched — enumerated from the reads, or loaded from the first pass's output — to where they
-    // are placed in LDS.  Round 5 (ELBA_SCATTER_NO_PIPE: off): the NEXT tile is fetched in the shadow of this tile's write-out — the key registers are dead by
+    // are placed in LDS.  The NEXT tile is fetched in the shadow of this tile's write-out — the key registers are dead by
     // then — so that the loads' latency (MEM) hides behind the write-out, and, ENUM, half the wavefronts enumerate (vector ALU) while the other half
     // write out (LDS reads + global stores) instead of all sixteen doing the one and then the other: partition of config 3 26.4 -> 24.1 ms.
 #ifdef ELBA_SCATTER_CLOCK
@@ -320,7 +320,7 @@ __global__ __launch_bounds__(MT_THREADS) void k_msd_scatter(EnumParams e, const 
 #endif
     uint64_t key[MT_ITEMS];
     uint32_t dig2[MT_ITEMS / 2];    // the items' digits, two per register (0xFFFF: no key)
-    uint32_t count = 0, ncount = 0; (void)ncount;
+    uint32_t count = 0, ncount = 0;
     auto digit = [&](int it) -> uint32_t { return (dig2[it >> 1] >> ((it & 1) * 16)) & 0xFFFFu; };
     auto set_digit = [&](int it, uint32_t d) { if (it & 1) dig2[it >> 1] |= d << 16; else dig2[it >> 1] = d; };
     auto fetch = [&](uint32_t t, uint32_t &cnt) {
@@ -359,198 +359,130 @@ __global__ __launch_bounds__(MT_THREADS) void k_msd_scatter(EnumParams e, const 
             set_digit(it, q < cnt ? (uint32_t)(key[it] >> shift) & dmask : 0xFFFFu);
         }
     };
-#ifndef ELBA_SCATTER_ENUM_MODE
-#define ELBA_SCATTER_ENUM_MODE 2      // ENUM: 0 = the tile is enumerated at the top of its own turn, 1 = every wavefront enumerates the next tile before it writes this one out, 2 = half of them before, half after
-#endif
-    constexpr bool PIPE = !ENUM || ELBA_SCATTER_ENUM_MODE != 0;
     // Which tiles a workgroup takes.  A digit's runs of CONSECUTIVE tiles lie one behind the other in the output, 256 bytes each at any 8-byte alignment: the
     // 64-byte lines at their seams are written half by one tile and half by the next.  Workgroups go to the XCDs round-robin (blockIdx mod 8), each XCD
     // has its own L2: dealt round-robin, neighbouring tiles never share an L2 and every seam line leaves two L2s as a partial line.  Each XCD therefore takes a
     // BLOCK of consecutive tiles per round (its 32 workgroups walk 32 neighbouring tiles at the same time): the seams inside the block merge in its L2.
-#ifndef ELBA_SCATTER_RR
     const uint32_t first_tile = (gridDim.x & 7u) ? blockIdx.x : (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);
-#else
-    const uint32_t first_tile = blockIdx.x;
-#endif
-#ifndef ELBA_SCATTER_NO_PIPE
-    if (PIPE && first_tile < ntiles) fetch(first_tile, count);
-#endif
-#ifndef ELBA_SCATTER_ONE_TILE      // (the persistent grid costs the ENUM kernel 50 registers — 228 bytes of scratch — and is still 0.4 ms ahead of a workgroup per tile: 25.1 vs 25.5 ms for the partition)
+    if (first_tile < ntiles) fetch(first_tile, count);
+    // (the persistent grid costs the ENUM kernel 50 registers — 228 bytes of scratch — and is still 0.4 ms ahead of a workgroup per tile: 25.1 vs 25.5 ms for the partition)
     for (uint32_t tile = first_tile; tile < ntiles; tile += gridDim.x) {
-#else
-    const uint32_t tile = blockIdx.x;
-    if (tile < ntiles) {
-#endif
-    ELBA_SSTAMP(0);
-    for (int i = threadIdx.x; i < MT_MAXBINS; i += MT_THREADS) lcnt[i] = 0;
-    for (int i = threadIdx.x; i < MT_TILE / 64; i += MT_THREADS) hbits[i] = 0;
-    __syncthreads();
-    ELBA_SSTAMP(1);
-#ifdef ELBA_SCATTER_NO_PIPE
-    fetch(tile, count);
-#else
-    if (!PIPE) fetch(tile, count);
-#endif
-    digits_of_loaded(count);
-    // (the tile's row of output places: one coalesced load, in flight while the ranks are computed)
-    uint32_t gb[DPT];
-#pragma unroll
-    for (int u = 0; u < DPT; ++u) { const uint32_t d = threadIdx.x + u * MT_THREADS; gb[u] = d < nbins ? hist_scanned[(size_t)tile * nbins + d] : 0u; }
-    // rank of every key among the tile's keys with its digit: ONE returning LDS atomic per key on the workgroup's digit counters.  (Nothing
-    // downstream needs the partition to be stable — the bucket kernels sort every column — so the keys of a digit may land in any order; the
-    // ballot ranking of the radix sort, ~70 instructions per key, bought an order nobody reads.)
-    uint16_t rank[MT_ITEMS];
-#pragma unroll
-    for (int it = 0; it < MT_ITEMS; ++it) {
-        const uint32_t d = digit(it);
-        rank[it] = 0;
-        if (d != 0xFFFFu) rank[it] = (uint16_t)atomicAdd(&lcnt[d], 1u);
-    }
-    ELBA_SSTAMP(2);
-    __syncthreads();
-    ELBA_SSTAMP(3);
-    {
-        // exclusive scan of the digit counts: the digits' places in the tile
-        uint32_t tot[DPT], both = 0;
-#pragma unroll
-        for (int u = 0; u < DPT; ++u) { const uint32_t d = DPT * threadIdx.x + u; tot[u] = d < nbins ? lcnt[d] : 0u; both += tot[u]; }
-        uint32_t inc = both;
-#pragma unroll
-        for (int s2 = 1; s2 < 64; s2 <<= 1) { const uint32_t o = __shfl_up(inc, s2, 64); if (lane >= s2) inc += o; }
-        if (lane == 63) wsum[w] = inc;
+        ELBA_SSTAMP(0);
+        for (int i = threadIdx.x; i < MT_MAXBINS; i += MT_THREADS) lcnt[i] = 0;
+        for (int i = threadIdx.x; i < MT_TILE / 64; i += MT_THREADS) hbits[i] = 0;
         __syncthreads();
-        uint32_t run = inc - both;
-        for (int ww = 0; ww < w; ++ww) run += wsum[ww];
+        ELBA_SSTAMP(1);
+        digits_of_loaded(count);
+        // (the tile's row of output places: one coalesced load, in flight while the ranks are computed)
+        uint32_t gb[DPT];
 #pragma unroll
-        for (int u = 0; u < DPT; ++u) { const uint32_t d = DPT * threadIdx.x + u; if (d < nbins) lstart[d] = run; run += tot[u]; }
-        if (threadIdx.x == MT_THREADS - 1) kept_s = run;      // (the inclusive sum at the last thread: every key of the tile that has a digit)
-#pragma unroll
-        for (int u = 0; u < DPT; ++u) { const uint32_t d = threadIdx.x + u * MT_THREADS; if (d < nbins) gbase[d] = gb[u]; }
-    }
-    __syncthreads();
-    ELBA_SSTAMP(4);
-    if (ENUM && FILTER) count = kept_s;
-#pragma unroll
-    for (int it = 0; it < MT_ITEMS; ++it) {
-        const uint32_t d = digit(it);
-        if (d != 0xFFFFu) lkey[lstart[d] + rank[it]] = key[it];
-    }
-    ELBA_SSTAMP(5);
-#ifdef ELBA_SCATTER_MEM_DIRECT
-    if (!ENUM) {
-        // a word that still holds its digit finds its run by it: delta[digit] = the run's place in the output - its place in the tile; the places of
-        // the tile are walked with a compile-time trip count, so that the LDS reads of all of a lane's places are in flight together (a loop with a
-        // run-time bound exposed three dependent LDS round trips per key: ~4 us of a tile's ~28)
-#pragma unroll
-        for (int u = 0; u < DPT; ++u) { const uint32_t d = DPT * threadIdx.x + u; if (d < nbins) delta[d] = gbase[d] - lstart[d]; }
-        __syncthreads();
+        for (int u = 0; u < DPT; ++u) { const uint32_t d = threadIdx.x + u * MT_THREADS; gb[u] = d < nbins ? hist_scanned[(size_t)tile * nbins + d] : 0u; }
+        // rank of every key among the tile's keys with its digit: ONE returning LDS atomic per key on the workgroup's digit counters.  (Nothing
+        // downstream needs the partition to be stable — the bucket kernels sort every column — so the keys of a digit may land in any order; the
+        // ballot ranking of the radix sort, ~70 instructions per key, bought an order nobody reads.)
+        uint16_t rank[MT_ITEMS];
 #pragma unroll
         for (int it = 0; it < MT_ITEMS; ++it) {
-            const uint32_t t = (uint32_t)it * MT_THREADS + threadIdx.x;
-            if (t < count) { const uint64_t kv = lkey[t]; out[delta[(uint32_t)(kv >> shift) & dmask] + t] = kv; }
+            const uint32_t d = digit(it);
+            rank[it] = 0;
+            if (d != 0xFFFFu) rank[it] = (uint16_t)atomicAdd(&lcnt[d], 1u);
+        }
+        ELBA_SSTAMP(2);
+        __syncthreads();
+        ELBA_SSTAMP(3);
+        {
+            // exclusive scan of the digit counts: the digits' places in the tile
+            uint32_t tot[DPT], both = 0;
+#pragma unroll
+            for (int u = 0; u < DPT; ++u) { const uint32_t d = DPT * threadIdx.x + u; tot[u] = d < nbins ? lcnt[d] : 0u; both += tot[u]; }
+            uint32_t inc = both;
+#pragma unroll
+            for (int s2 = 1; s2 < 64; s2 <<= 1) { const uint32_t o = __shfl_up(inc, s2, 64); if (lane >= s2) inc += o; }
+            if (lane == 63) wsum[w] = inc;
+            __syncthreads();
+            uint32_t run = inc - both;
+            for (int ww = 0; ww < w; ++ww) run += wsum[ww];
+#pragma unroll
+            for (int u = 0; u < DPT; ++u) { const uint32_t d = DPT * threadIdx.x + u; if (d < nbins) lstart[d] = run; run += tot[u]; }
+            if (threadIdx.x == MT_THREADS - 1) kept_s = run;      // (the inclusive sum at the last thread: every key of the tile that has a digit)
+#pragma unroll
+            for (int u = 0; u < DPT; ++u) { const uint32_t d = threadIdx.x + u * MT_THREADS; if (d < nbins) gbase[d] = gb[u]; }
         }
         __syncthreads();
-#ifndef ELBA_SCATTER_ONE_TILE
-        continue;
-#else
-        return;
-#endif
-    }
-#endif
-    // The tile now lies ordered by digit in LDS, but an ENUM word does not hold its digit any more.  A place finds its digit's run from a
-    // bitmap of the run starts: run number = set bits at or before the place, delta[run] = the run's place in the output - its place in the tile.
-    {
+        ELBA_SSTAMP(4);
+        if (ENUM && FILTER) count = kept_s;
+#pragma unroll
+        for (int it = 0; it < MT_ITEMS; ++it) {
+            const uint32_t d = digit(it);
+            if (d != 0xFFFFu) lkey[lstart[d] + rank[it]] = key[it];
+        }
+        ELBA_SSTAMP(5);
+        // The tile now lies ordered by digit in LDS, but an ENUM word does not hold its digit any more.  A place finds its digit's run from a
+        // bitmap of the run starts: run number = set bits at or before the place, delta[run] = the run's place in the output - its place in the tile.
+        // (!ENUM words still hold their digit and could find their run by it, without the bitmap: measured, no change)
+        {
+#pragma unroll
+            for (int u = 0; u < DPT; ++u) {
+                const uint32_t d = DPT * threadIdx.x + u;
+                if (d < nbins) { const uint32_t ls = lstart[d], le = d + 1 < nbins ? lstart[d + 1] : count; if (le > ls) atomicOr(&hbits[ls >> 6], 1ull << (ls & 63u)); }
+            }
+        }
+        __syncthreads();
+        if (w == 0) {
+            constexpr int HPL = MT_TILE / 64 / 64;      // bitmap words per lane
+            uint32_t cw[HPL], tot = 0;
+#pragma unroll
+            for (int q = 0; q < HPL; ++q) { cw[q] = (uint32_t)__popcll(hbits[HPL * lane + q]); tot += cw[q]; }
+            uint32_t inc = tot;
+#pragma unroll
+            for (int s2 = 1; s2 < 64; s2 <<= 1) { const uint32_t o = __shfl_up(inc, s2, 64); if (lane >= s2) inc += o; }
+            uint32_t run = inc - tot;
+#pragma unroll
+            for (int q = 0; q < HPL; ++q) { hpre[HPL * lane + q] = run; run += cw[q]; }
+        }
+        __syncthreads();
 #pragma unroll
         for (int u = 0; u < DPT; ++u) {
             const uint32_t d = DPT * threadIdx.x + u;
-            if (d < nbins) { const uint32_t ls = lstart[d], le = d + 1 < nbins ? lstart[d + 1] : count; if (le > ls) atomicOr(&hbits[ls >> 6], 1ull << (ls & 63u)); }
+            if (d < nbins) {
+                const uint32_t ls = lstart[d], le = d + 1 < nbins ? lstart[d + 1] : count;
+                if (le > ls) delta[hpre[ls >> 6] + (uint32_t)__popcll(hbits[ls >> 6] & ((1ull << (ls & 63u)) - 1ull))] = gbase[d] - ls;
+            }
         }
-    }
-    __syncthreads();
-    if (w == 0) {
-        constexpr int HPL = MT_TILE / 64 / 64;      // bitmap words per lane
-        uint32_t cw[HPL], tot = 0;
-#pragma unroll
-        for (int q = 0; q < HPL; ++q) { cw[q] = (uint32_t)__popcll(hbits[HPL * lane + q]); tot += cw[q]; }
-        uint32_t inc = tot;
-#pragma unroll
-        for (int s2 = 1; s2 < 64; s2 <<= 1) { const uint32_t o = __shfl_up(inc, s2, 64); if (lane >= s2) inc += o; }
-        uint32_t run = inc - tot;
-#pragma unroll
-        for (int q = 0; q < HPL; ++q) { hpre[HPL * lane + q] = run; run += cw[q]; }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int u = 0; u < DPT; ++u) {
-        const uint32_t d = DPT * threadIdx.x + u;
-        if (d < nbins) {
-            const uint32_t ls = lstart[d], le = d + 1 < nbins ? lstart[d + 1] : count;
-            if (le > ls) delta[hpre[ls >> 6] + (uint32_t)__popcll(hbits[ls >> 6] & ((1ull << (ls & 63u)) - 1ull))] = gbase[d] - ls;
-        }
-    }
-    __syncthreads();
-    ELBA_SSTAMP(6);
-    auto writeout = [&]() {
-#ifdef ELBA_SCATTER_UNROLL
-#pragma unroll
-    for (int it = 0; it < MT_ITEMS; ++it) {      // (compile-time trip count: the LDS reads of a lane's places are in flight together)
-        const uint32_t t = (uint32_t)it * MT_THREADS + threadIdx.x;
-        if (t < count) {
-            const uint32_t run = hpre[t >> 6] + (uint32_t)__popcll(hbits[t >> 6] & ((2ull << (t & 63u)) - 1ull)) - 1u;
-            out[delta[run] + t] = lkey[t];
-        }
-    }
-#else
-    // (a compile-time trip count — all of a lane's LDS reads in flight together — was measured: partition 28.0 -> 30.0 ms; the 32 keys it keeps
-    //  in registers beside the tile's cost more than the round trips they hide)
-#if defined(ELBA_X_SCATTER) && ELBA_X_SCATTER == 1      // timing experiment (wrong results): the tile leaves as ONE contiguous run
-    for (uint32_t t = threadIdx.x; t < count; t += MT_THREADS) out[(size_t)tile * MT_TILE + t] = lkey[t];
-#elif defined(ELBA_X_SCATTER) && ELBA_X_SCATTER == 2    // timing experiment (wrong results): nothing leaves
-    for (uint32_t t = threadIdx.x; t < count; t += MT_THREADS) {
-        const uint32_t run = hpre[t >> 6] + (uint32_t)__popcll(hbits[t >> 6] & lane_le) - 1u;
-        if (delta[run] == 0xFFFFFFFEu) out[t] = lkey[t];
-    }
-#else
-    // (a place's run costs two dependent LDS round trips — bitmap word, then the run's delta — in a loop with a run-time trip count: two places per trip keep two chains in
-    //  flight: ENUM 10.25 -> 9.87 ms; MEM 8.54 -> 8.76: its trips stay single; four: no better)
-    if (ENUM) {
+        __syncthreads();
+        ELBA_SSTAMP(6);
+        auto writeout = [&]() {
+            // (a compile-time trip count — all of a lane's LDS reads in flight together — was measured: partition 28.0 -> 30.0 ms; the 32 keys it keeps
+            //  in registers beside the tile's cost more than the round trips they hide)
+            // (a place's run costs two dependent LDS round trips — bitmap word, then the run's delta — in a loop with a run-time trip count: two places per trip keep two chains in
+            //  flight: ENUM 10.25 -> 9.87 ms; MEM 8.54 -> 8.76: its trips stay single; four: no better)
+            if (ENUM) {
 #pragma unroll 2
-        for (uint32_t t = threadIdx.x; t < count; t += MT_THREADS) {
-            const uint32_t run = hpre[t >> 6] + (uint32_t)__popcll(hbits[t >> 6] & lane_le) - 1u;
-            out[delta[run] + t] = lkey[t];
-        }
-    } else
-    for (uint32_t t = threadIdx.x; t < count; t += MT_THREADS) {
-        const uint32_t run = hpre[t >> 6] + (uint32_t)__popcll(hbits[t >> 6] & lane_le) - 1u;
-        out[delta[run] + t] = lkey[t];
-    }
-#endif
-#endif
-    };
-#if !defined(ELBA_SCATTER_NO_PIPE) && !defined(ELBA_SCATTER_ONE_TILE)
-    {
+                for (uint32_t t = threadIdx.x; t < count; t += MT_THREADS) {
+                    const uint32_t run = hpre[t >> 6] + (uint32_t)__popcll(hbits[t >> 6] & lane_le) - 1u;
+                    out[delta[run] + t] = lkey[t];
+                }
+            } else {
+                for (uint32_t t = threadIdx.x; t < count; t += MT_THREADS) {
+                    const uint32_t run = hpre[t >> 6] + (uint32_t)__popcll(hbits[t >> 6] & lane_le) - 1u;
+                    out[delta[run] + t] = lkey[t];
+                }
+            }
+        };
         const uint32_t nxt = tile + gridDim.x;
         const bool has = nxt < ntiles;
-        if (!PIPE) writeout();
-        else if (ENUM && ELBA_SCATTER_ENUM_MODE == 2 && (w & 1)) { writeout(); ELBA_SSTAMP(7); if (has) fetch(nxt, ncount); ELBA_SSTAMP(8); }
+        // (ENUM, measured: the tile enumerated at the top of its own turn 11.0 ms; every wavefront enumerating the next tile before it writes this one out 10.2 ms;
+        //  half of them before and half after 10.0 ms)
+        if (ENUM && (w & 1)) { writeout(); ELBA_SSTAMP(7); if (has) fetch(nxt, ncount); ELBA_SSTAMP(8); }
         else { if (has) fetch(nxt, ncount); ELBA_SSTAMP(8); writeout(); ELBA_SSTAMP(7); }
-    }
-#else
-    writeout();
-#endif
-    lds_sync_fwd();      // (the tile's LDS is reused by the workgroup's next tile; its global stores stay in flight)
-    ELBA_SSTAMP(9);
-#ifndef ELBA_SCATTER_NO_PIPE
-    if (PIPE) count = ncount;
-#endif
+        lds_sync();      // (the tile's LDS is reused by the workgroup's next tile; its global stores stay in flight)
+        ELBA_SSTAMP(9);
+        count = ncount;
     }
 #ifdef ELBA_SCATTER_CLOCK
     if (lane == 0 && w < 2) for (int q = 0; q < 12; ++q) atomicAdd(&g_sc_phase[ENUM ? 1 : 0][w][q], sph[q]);
 #endif
 }
-
-// LDS-only workgroup barrier: the global stores of a bucket (never read back by the workgroup) stay in flight
-__device__ __forceinline__ void lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 struct BucketStats { unsigned long long distinct, sumsq; unsigned int maxcol, ncrowded, nmid, nbig; };      // nmid / nbig: buckets of 4097..8192 / 8193..ES_CAP_MAX entries
 struct BucketOut {
@@ -749,15 +681,11 @@ __global__ __launch_bounds__(BK_THREADS) void k_msd_count(const uint64_t *words,
 // SPEC: the instantiation for what the reads path of k <= 17 always builds — no column ranks, distinct words, gather slots, hints, inline partners, one-word CSR sort
 // keys, k-mers from the bucket number — with those switches compiled in: the general kernel keeps ~75 kernel-argument scalars alive and spilled them to vector lanes
 // (472 v_readlane of 4000 vector instructions per bucket and lane: the emit kernels are bound by instruction issue, profiles/r05_notes.md)
-template <int ES_KPT, int ES_THREADS = 256, bool SPEC = false>
-#ifndef ELBA_ES_OCC256
-#define ELBA_ES_OCC256 5      // (92 VGPRs instead of 100: five workgroups per CU instead of four)
-#endif
-#ifndef ELBA_ES_OCC512
-#define ELBA_ES_OCC512 6      // (80 VGPRs + 32 bytes of scratch instead of 99: THREE workgroups per CU — what the 49 KB of LDS allow — instead of two: bucket kernels of config 3 17.6 -> 16.1 ms)
-#endif
 // (second launch bound = wavefronts per SIMD the register allocation leaves room for; 0: whatever the kernel needs)
-__global__ __launch_bounds__(ES_THREADS, (ES_THREADS == 256 ? ELBA_ES_OCC256 : (ES_THREADS == 512 ? ELBA_ES_OCC512 : 0))) void k_msd_emit_small(const uint64_t *wrel, const uint32_t *b2start, const uint32_t *bZ, uint32_t nbuckets, MsdParams m, uint32_t cap_lo, uint32_t cap_hi,
+constexpr int ES_OCC256 = 5;      // (92 VGPRs instead of 100: five workgroups per CU instead of four)
+constexpr int ES_OCC512 = 6;      // (80 VGPRs + 32 bytes of scratch instead of 99: THREE workgroups per CU — what the 49 KB of LDS allow — instead of two: bucket kernels of config 3 17.6 -> 16.1 ms)
+template <int ES_KPT, int ES_THREADS = 256, bool SPEC = false>
+__global__ __launch_bounds__(ES_THREADS, (ES_THREADS == 256 ? ES_OCC256 : (ES_THREADS == 512 ? ES_OCC512 : 0))) void k_msd_emit_small(const uint64_t *wrel, const uint32_t *b2start, const uint32_t *bZ, uint32_t nbuckets, MsdParams m, uint32_t cap_lo, uint32_t cap_hi,
                                                               const uint32_t *kidbase, const uint32_t *entbase, BucketOut o)
 {
     constexpr uint32_t ES_CAP = ES_THREADS * ES_KPT, NW = ES_THREADS / 64, NH = ES_KPT * NW;      // entries; wavefronts; (u, wavefront) head counts
@@ -784,11 +712,6 @@ __global__ __launch_bounds__(ES_THREADS, (ES_THREADS == 256 ? ELBA_ES_OCC256 : (
     const uint64_t *const o_kmer_src = SPEC ? nullptr : o.kmer_src, *const o_kmer_dist = SPEC ? nullptr : o.kmer_dist;
     const uint32_t *const o_ncols = SPEC ? nullptr : o.ncols;
     const bool has_relk = SPEC ? true : o.rel_kmers != nullptr;
-#ifdef ELBA_X_EMIT
-    const bool xst = o.nb == 12345;      // timing experiment (wrong results): nothing leaves the kernel
-#else
-    constexpr bool xst = true;
-#endif
     for (uint32_t b = blockIdx.x; b < nbuckets; b += gridDim.x) {
         const uint32_t Z = bZ[b];
         if (Z <= cap_lo || Z > cap_hi) continue;      // (other sizes: the other instantiation, or k_msd_bucket)
@@ -935,20 +858,20 @@ __global__ __launch_bounds__(ES_THREADS, (ES_THREADS == 256 ? ELBA_ES_OCC256 : (
                     if (mult < 2 && nown == 0) hint = 3;
                 }
                 const uint32_t z = eb + p, kid = kb + kl;
-                if (xst) o.csc[z] = (read << 32) | pos;
+                o.csc[z] = (read << 32) | pos;
                 uint64_t word = (read << o.rs) | ((uint64_t)kid << (o.pb + 2)) | (hint << o.pb) | pos;
                 // Ctx::csr_inline: a row that accumulates exactly ONE pair of this column (always so for the owner of a two-read column) carries that
                 // pair in its own entry — the SpGEMM then fetches no column for it
                 const bool isinl = o.inl && mult == 1u && nown == 1u && ((pos | opos) >> o.inl) == 0;
                 if (isinl) word = (1ull << 63) | (read << o.rs) | ((oread >> 1) << (2 * o.inl)) | (pos << o.inl) | opos;
-                if (!xst) {} else if (o_pair_val) { o.pair_key[z] = (uint32_t)read; o_pair_val[z] = ((uint64_t)kid << 32) | ((uint64_t)L << 23) | ((uint64_t)(p - h0) << 16) | pos; }
+                if (o_pair_val) { o.pair_key[z] = (uint32_t)read; o_pair_val[z] = ((uint64_t)kid << 32) | ((uint64_t)L << 23) | ((uint64_t)(p - h0) << 16) | pos; }
                 else if (o_compact && !isinl && hint == 0) {      // this entry fetches its column: the column needs a gather slot, the key names it (below)
                     needmask |= 1u << u;
                     atomicOr(&H[kl], HNEED);
                 }
                 else if (has_words) o_csr_words[z] = word;
                 else o.kid_of_entry[z] = kid;
-                if (xst && ((headmask >> u) & 1u)) {
+                if ((headmask >> u) & 1u) {
                     const uint64_t value = ((uint64_t)b << VBITS) | ((uint32_t)(x >> m.PB) & 0xFFFFu);
                     if (has_relk) o.rel_kmers[kid] = o_kmer_dist ? o_kmer_dist[o.dist_base[b] + ((uint32_t)(x >> m.PB) & 0xFFFFu)] : (o_kmer_src ? o_kmer_src[s0 + kl] : value << (64 - m.k2));
                     o.rel_counts[kid] = L; o.colptr[kid] = z;
@@ -986,7 +909,7 @@ __global__ __launch_bounds__(ES_THREADS, (ES_THREADS == 256 ? ELBA_ES_OCC256 : (
                     const uint32_t p = (uint32_t)u * ES_THREADS + tid;
                     const uint64_t x = A[p];
                     const uint64_t sid = (uint64_t)gb + ((H[slot[u]] >> 14) & 0x1FFFu);
-                    if (xst) o_csr_words[eb + p] = (((x & paymask) >> m.pbits) << o.rs) | (sid << (o.pb + 2)) | (x & posmask);
+                    o_csr_words[eb + p] = (((x & paymask) >> m.pbits) << o.rs) | (sid << (o.pb + 2)) | (x & posmask);
                 }
             const uint32_t S = o.ell_stride, nq = ng * S, sl = (S & (S - 1u)) ? 0u : (uint32_t)__ffs((int)S) - 1u;
             uint64_t *dst = o.ell + (uint64_t)gb * S;
@@ -994,8 +917,8 @@ __global__ __launch_bounds__(ES_THREADS, (ES_THREADS == 256 ? ELBA_ES_OCC256 : (
                 const uint32_t ls = (S & (S - 1u)) ? q / S : q >> sl, j = q - ls * S, kl = GL[ls], h0 = H[kl] & HPOS;
                 uint64_t v = ~0ull;
                 if (h0 + j < (H[kl + 1] & HPOS)) { const uint64_t x = A[h0 + j]; v = (((x & paymask) >> m.pbits) << 32) | (x & posmask); }
-                if (xst) dst[q] = v;
-                if (xst && j == 0) o.slot_kid[gb + ls] = kb + kl;
+                dst[q] = v;
+                if (j == 0) o.slot_kid[gb + ls] = kb + kl;
             }
         } else if (o.ell_stride) {
             const uint32_t S = o.ell_stride, nq = Nb * S, sl = (S & (S - 1u)) ? 0u : (uint32_t)__ffs((int)S) - 1u;
@@ -1006,7 +929,7 @@ __global__ __launch_bounds__(ES_THREADS, (ES_THREADS == 256 ? ELBA_ES_OCC256 : (
                 //  the bucket kernels: the stores are fire-and-forget, the test is not)
                 uint64_t v = ~0ull;
                 if (h0 + j < H[kl + 1]) { const uint64_t x = A[h0 + j]; v = (((x & paymask) >> m.pbits) << 32) | (x & posmask); }
-                if (xst) dst[q] = v;
+                dst[q] = v;
             }
         }
         lds_sync();                               // A, H and the counters are reused by the next bucket
@@ -1228,7 +1151,7 @@ __global__ __launch_bounds__(BK_THREADS) void k_msd_bucket(const uint64_t *words
 // of the flattened value —, each pass partitioned on e more bits of its coarse digits ((dhi - dlo) << e <= 2^10 first digits, k31_hist1<true> /
 // k31_scatter<true, true>) and a second digit of up to 10 bits, so that its buckets are as fine as those of an input of its size (msd_run).
 // HBM traffic per instance: 16 B written + 16 read (hist2) + 16 read + 16 written + 16 read = 80 B, against 7 passes x 32 B + 3 x 16 B on the sort path.
-constexpr int W2_THREADS = ELBA_W2_THREADS, W2_ITEMS = ELBA_W2_ITEMS, W2_MAXBINS = 1 << W2_MAXBITS;      // (W2_TILE, W2_MAXBITS: msd_plan.hpp)
+constexpr int W2_MAXBINS = 1 << W2_MAXBITS;      // (W2_THREADS, W2_ITEMS, W2_TILE, W2_MAXBITS: msd_plan.hpp)
 constexpr uint32_t W2_CAP = 4096;                // records of a bucket k31_count takes (eight per lane, in registers)
 constexpr int W2C_THREADS = 512, W2C_KPT = (int)(W2_CAP / W2C_THREADS);
 static_assert(W2_ITEMS * 64 <= (1 << IB_SHIFT), "a wavefront's share of a tile lies inside one block of the instance -> read table");
@@ -1447,29 +1370,8 @@ __global__ __launch_bounds__(W2C_THREADS, 4) void k31_count(const Rec2 *recs, co
 #pragma unroll 1
         for (uint32_t ch = 0; ch < nch; ++ch) {
         if (ch) load_chunk(ch);
-#ifdef ELBA_K31_SERIAL_CAS
-#pragma unroll
-        for (int u = 0; u < W2C_KPT; ++u) {
-            slot[u] = 0;
-            if (key[u].hi != ~0ull) {
-                const unsigned long long hk = key[u].hi;
-                uint32_t sl = (((uint32_t)hk ^ (uint32_t)(hk >> 27)) * 0x9E3779B1u) >> 20;      // 12 bits
-                if (__hip_atomic_load(&misc[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == 0u) {      // (the table is filling up: the bucket is given up)
-                    for (uint32_t probes = 0; probes < W2_SLOTS; ++probes) {      // (bounded whatever happens: a full table cannot hang the wavefront; a plain read in front of the compare-and-swap — most records find their k-mer there — was measured: 44.3 against 42.7 ms for the bucket kernels)
-                        const unsigned long long old = atomicCAS(&K[sl], ~0ull, hk);
-                        if (old == hk) break;
-                        if (old == ~0ull) { if (atomicAdd(&misc[1], 1u) >= W2_DISTINCT_MAX) __hip_atomic_store(&misc[2], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); break; }
-                        sl = (sl + 1u) & (W2_SLOTS - 1u);
-                        if (probes + 1u == W2_SLOTS) __hip_atomic_store(&misc[2], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    }
-                    atomicAdd(&CNT[sl], 1u);
-                }
-                slot[u] = sl;
-            }
-        }
-#else
-        {   // (a lane's eight first attempts are in flight together — nine records in ten find their k-mer, or an empty slot, where their hash points —, then the rest probes on: the
-            //  loop below used to be eight dependent LDS round trips per lane)
+        {   // (a lane's eight first attempts are in flight together — nine records in ten find their k-mer, or an empty slot, where their hash points —, then the rest probes on: one
+            //  record after the other was eight dependent LDS round trips per lane; a plain read in front of the compare-and-swap was measured: 44.3 against 42.7 ms for the bucket kernels)
             const bool live = __hip_atomic_load(&misc[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == 0u;      // (the table is filling up: the bucket is given up)
             unsigned long long old[W2C_KPT];
 #pragma unroll
@@ -1502,7 +1404,6 @@ __global__ __launch_bounds__(W2C_THREADS, 4) void k31_count(const Rec2 *recs, co
                 }
             }
         }
-#endif
         }
         lds_sync();
         if (__hip_atomic_load(&misc[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != 0u) {      // more distinct k-mers than the table takes: a crowded bucket like one beyond W2_CAP records
@@ -1545,23 +1446,6 @@ __global__ __launch_bounds__(W2C_THREADS, 4) void k31_count(const Rec2 *recs, co
             // ... numbered in value order.  The usual bucket holds a few dozen of them (a HiFi read set: ~1900 records of ~56 genomic k-mers): every lane
             // sums, over the bucket's reliable k-mers, those below its own and their counts — broadcast reads; no ranges, no scans, five barriers less (bucket kernels of the k = 31 workload: 47.6 -> 42.7 ms).
             // (The columns' fill counters are then sbcnt[column], zero since the bucket began.)
-#ifdef ELBA_K31_FEW_ONE_LANE
-            if (tid < Nb) {
-                const uint32_t sl = RL[tid];
-                const unsigned long long mine = K[sl];
-                uint32_t rc = 0, first = 0, tot = 0;
-#pragma unroll 4
-                for (uint32_t x = 0; x < Nb; ++x) {
-                    const uint32_t sx = RL[x], cx = CNT[sx];
-                    const bool below = K[sx] < mine;
-                    rc += below ? 1u : 0u; first += below ? cx : 0u; tot += cx;
-                }
-                RC[sl] = (uint16_t)rc;
-                C[rc] = first;
-                ktmp[s0 + rc] = mine << (64 - k2);
-                if (tid == 0) misc[3] = tot;
-            }
-#else
             {   // (G lanes per reliable k-mer share the walk — as many as the workgroup has for Nb of them, 8 for the usual 56 — and add their parts up with shuffles:
                 //  one wavefront used to walk all Nb alone while the other seven waited)
                 uint32_t lg = 0;
@@ -1589,7 +1473,6 @@ __global__ __launch_bounds__(W2C_THREADS, 4) void k31_count(const Rec2 *recs, co
                     if (i == 0u) misc[3] = tot;
                 }
             }
-#endif
             lds_sync();
             Zb = Nb ? misc[3] : 0u;
         } else {
@@ -1863,13 +1746,13 @@ static EmitGrids emit_grids(const Ctx &c, uint32_t n) { const uint32_t cu = (uin
 static void launch_emit(Ctx &c, const MsdParams &m, uint32_t small_cap, const BucketTable &t, const BucketStats &hs, const BucketOut &o, const EmitGrids &g)
 {
     hipStream_t s = c.stream;
-    const uint32_t cap16 = std::min<uint32_t>(small_cap, 4096u), cap8 = std::min<uint32_t>(cap16, c.opt.msd_no_emit8 ? 0u : 2048u), nbuckets = t.nbuckets;
+    const uint32_t cap16 = std::min<uint32_t>(small_cap, 4096u), cap8 = std::min<uint32_t>(cap16, 2048u), nbuckets = t.nbuckets;
     const uint32_t *b2start = t.b2start, *bZ = t.bZ, *kidbase = t.kidbase, *entbase = t.entbase;
     // (buckets of up to 2048 entries — more than half of them on BASELINE config 3, where a bucket holds 2040 on average — through an instantiation
     //  with 8 entries per lane: half the predicated-off work of the 16-entry one, 26 KB of LDS instead of 49: six workgroups per CU)
     // (512 lanes x 4 for them was measured too: 17.6 against 17.5 ms on config 3, 48.4 against 47.6 ms on the k = 31 workload)
     // (pseudo-buckets look their k-mers up — kmer_dist, ncols —: never the specialised instantiation)
-    const bool spec = m.rk == 0 && m.dup == 0u && o.compact && o.hints && o.csr_words && !o.pair_val && !o.kmer_src && !o.kmer_dist && !o.ncols && o.rel_kmers && c.opt.tune[6] != 3;      // ("tune6" = 3: the general instantiation — A/B)
+    const bool spec = m.rk == 0 && m.dup == 0u && o.compact && o.hints && o.csr_words && !o.pair_val && !o.kmer_src && !o.kmer_dist && !o.ncols && o.rel_kmers;
     if (cap8 && spec) hipLaunchKernelGGL((k_msd_emit_small<8, 256, true>), dim3(g.g8), dim3(256), 0, s, t.wrel, b2start, bZ, nbuckets, m, 0u, cap8, kidbase, entbase, o);
     else if (cap8) hipLaunchKernelGGL((k_msd_emit_small<8>), dim3(g.g8), dim3(256), 0, s, t.wrel, b2start, bZ, nbuckets, m, 0u, cap8, kidbase, entbase, o);
     // 2049..4096 entries: 512 lanes x 8 (three workgroups of eight wavefronts per CU, not of four: 19.0 -> 17.5 ms for the bucket kernels on config 3)
@@ -1932,11 +1815,7 @@ struct MsdRun {
     // k <= 17: the first level's segments, the scatter kernels' grid, the second digit's shift
     SegTiles seg() const { return SegTiles{b1start, tile0, pl.nb1, nullptr}; }
     int shift2() const { return m.PB + pl.vb; }
-#ifndef ELBA_SCATTER_ONE_TILE
-    uint32_t sgrid() const { return c.opt.tune[0] == 1 ? 0xFFFFFFFFu : (uint32_t)c.num_cus * (MT_TILE <= 8192 ? 2u : 1u); }      // (tune0 = 1: a workgroup per tile — A/B)
-#else
-    uint32_t sgrid() const { return 0xFFFFFFFFu; }      // a workgroup per tile
-#endif
+    uint32_t sgrid() const { return (uint32_t)c.num_cus * (MT_TILE <= 8192 ? 2u : 1u); }      // the persistent grid of k_msd_scatter
 
     // Workspaces, timers, the reads' block table.  Leaves: bt and the segment arrays carved from ws_e, m, e, bi; t_total and t_a running.
     void begin()
@@ -2096,7 +1975,7 @@ struct MsdRun {
         ELBA_HIP(hipMemsetAsync(bt.gstat, 0, sizeof(BucketStats), s));
         // (the first pass's records are dead: the front half of their buffer takes the kept entries, one word each, the back half — behind the
         //  largest pass's entries — the buckets' reliable k-mers)
-        hipLaunchKernelGGL(k31_count, dim3((unsigned)std::min<uint32_t>(nbuckets, (uint32_t)c.num_cus * (c.opt.tune[6] == 1 ? 1u : 2u))), dim3(W2C_THREADS), W2C_LDS, s, (const Rec2 *)rb, (const uint32_t *)bt.b2start, nbuckets, k2, Tp, m.PB, m.rk,
+        hipLaunchKernelGGL(k31_count, dim3((unsigned)std::min<uint32_t>(nbuckets, (uint32_t)c.num_cus * 2u)), dim3(W2C_THREADS), W2C_LDS, s, (const Rec2 *)rb, (const uint32_t *)bt.b2start, nbuckets, k2, Tp, m.PB, m.rk,
                            (uint32_t)c.cfg.lower, (uint32_t)c.cfg.upper, bt.bN, bt.bZ, bt.gstat, wa(), wa() + (largest + 2), bt.crowded);
         o.kmer_src = wa() + (largest + 2);
         bt.nbuckets = nbuckets; bt.words = nullptr; bt.wrel = wa();

@@ -6,27 +6,16 @@
 #include <cstdint>
 #include <vector>
 
-// (16384-key tiles, 139 KB of LDS, one workgroup per CU: on 1024 lanes x 16 keys — sixteen wavefronts to hide the barriers — the partition of
-//  config 3 takes 26.4 ms, on 512 x 32 27.6 ms)
-#ifndef ELBA_MT_THREADS
-#define ELBA_MT_THREADS 1024
-#endif
-#ifndef ELBA_MT_ITEMS
-#define ELBA_MT_ITEMS 16
-#endif
-#ifndef ELBA_W2_THREADS
-#define ELBA_W2_THREADS 512
-#endif
-#ifndef ELBA_W2_ITEMS
-#define ELBA_W2_ITEMS 16
-#endif
-
 namespace elba {
 
-constexpr int MT_TILE = ELBA_MT_THREADS * ELBA_MT_ITEMS;      // instances per tile; a wavefront's share is at most one block of the instance -> read table
+// (16384-key tiles, 139 KB of LDS, one workgroup per CU: on 1024 lanes x 16 keys — sixteen wavefronts to hide the barriers — the partition of
+//  config 3 takes 26.4 ms, on 512 x 32 27.6 ms)
+constexpr int MT_THREADS = 1024, MT_ITEMS = 16;      // lanes of a workgroup of the partition's kernels, keys per lane
+constexpr int W2_THREADS = 512, W2_ITEMS = 16;       // the same for the 16-byte records of 19 <= k <= 31
+constexpr int MT_TILE = MT_THREADS * MT_ITEMS;      // instances per tile; a wavefront's share is at most one block of the instance -> read table
 constexpr int MT_MAXBITS = 9;
 constexpr int VBITS = 16;                     // value bits left to the bucket kernel (two halves of 2^15 values)
-constexpr int W2_TILE = ELBA_W2_THREADS * ELBA_W2_ITEMS;      // 8192 records of 16 bytes: 128 KB of LDS (runs of 8 records per digit and tile; 4096-record tiles: partition 78 -> 58 ms on 2.0 G instances)
+constexpr int W2_TILE = W2_THREADS * W2_ITEMS;      // 8192 records of 16 bytes: 128 KB of LDS (runs of 8 records per digit and tile; 4096-record tiles: partition 78 -> 58 ms on 2.0 G instances)
 constexpr int W2_MAXBITS = 10;
 constexpr uint32_t HINT_MAX_COL = 12;     // longer columns are not examined: a row owns no pair of an L-read column with probability 2^-(L-1), and the test costs L loads
 constexpr uint32_t ES_CAP_MAX = 12288;      // entries of a bucket the widest emit kernel sorts in LDS

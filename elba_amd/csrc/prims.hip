@@ -142,16 +142,12 @@ __global__ void k_reduce_max(const uint64_t *p, int64_t n, unsigned long long *o
 // the same scattered load again in the scatter — 5*10^8 extra memory requests per pass over 2*10^9 keys, as many as the keys themselves make.
 // (A one-sweep variant — one kernel per pass, decoupled look-back over per-tile status words — was measured here and was 1.7x slower per
 // pass: with ~770 tiles in flight the look-back reads dozens of predecessors' status rows, each an agent-scope 8-byte access.)
-#ifndef ELBA_RS_SCATTER_THREADS
-#define ELBA_RS_SCATTER_THREADS 512      // (round 5: 512 lanes x 16 keys held to 128 VGPRs — two workgroups of eight wavefronts per CU; 256 x 32 needs 247 VGPRs: eight wavefronts per CU.  Round 4 measured 512 x 16 without the bound — 130 VGPRs, ONE workgroup per CU — and found it slower)
-#endif
-#ifndef ELBA_RS_PAIR_ITEMS
-#define ELBA_RS_PAIR_ITEMS 32
-#endif
-#ifndef ELBA_RS_KEY_ITEMS
-#define ELBA_RS_KEY_ITEMS 32
-#endif
 constexpr int RS_THREADS = 256;
+constexpr int RS_PAIR_ITEMS = 32, RS_KEY_ITEMS = 32;      // items per lane of the histogram's workgroup (RS_THREADS): 8192-item tiles
+// the scatter's workgroup on the same tile.  Keys alone: 512 lanes x 16 keys held to 128 VGPRs — two workgroups of eight wavefronts per CU; 256 x 32 needs 247 VGPRs: eight
+// wavefronts per CU (512 x 16 without the bound — 130 VGPRs, ONE workgroup per CU — was slower).  Pairs: 1024 lanes x 8 — the CSR build of the k = 31 workload 34.1 -> 27.0 ms
+// against 4096-pair tiles on 256 x 16; keys alone on 1024 x 8: 10.6 against 10.0 ms; pairs on 512 lanes: 14.1-14.9 ms per pass against 10.8-13.7
+constexpr int RS_SCATTER_THREADS = 512, RS_PAIR_THREADS = 1024;
 constexpr int RS_MAXBITS = 9;
 constexpr int RS_MAXBINS = 1 << RS_MAXBITS;
 constexpr int CS_ROWS = 128;           // rows of the histogram one workgroup of the column scan folds
@@ -505,13 +501,8 @@ static int radix_sort_impl(hipStream_t s, K *k0, uint64_t *v0, K *k1, uint64_t *
 {
     if (!fin && (n <= 1 || bit_hi <= bit_lo)) return 0;
     ELBA_REQUIRE(n < (int64_t)0xFFFFFFFFLL, ELBA_ERR_UNSUPPORTED, "radix sort of >= 2^32 items");
-    constexpr int ITEMS = HAS_VAL ? ELBA_RS_PAIR_ITEMS : ELBA_RS_KEY_ITEMS, TILE = RS_THREADS * ITEMS;
-    // (pairs: 8192-pair tiles on 1024 lanes x 8 — the CSR build of the k = 31 workload 34.1 -> 27.0 ms against 4096-pair tiles on 256 x 16; keys alone
-    //  stay on 256 x 32: 10.0 against 10.6 ms on 1024 x 8)
-#ifndef ELBA_RS_PAIR_THREADS
-#define ELBA_RS_PAIR_THREADS 1024
-#endif
-    constexpr int STHREADS = HAS_VAL ? ELBA_RS_PAIR_THREADS : ELBA_RS_SCATTER_THREADS;      // the scatter's workgroup (512 threads on the same 8192-key tile were measured: 14.1-14.9 ms per pass against 10.8-13.7)
+    constexpr int ITEMS = HAS_VAL ? RS_PAIR_ITEMS : RS_KEY_ITEMS, TILE = RS_THREADS * ITEMS;
+    constexpr int STHREADS = HAS_VAL ? RS_PAIR_THREADS : RS_SCATTER_THREADS;
     int shifts[64], widths[64];
     const int npass = radix_digits(bit_lo, bit_hi, shifts, widths);
     const uint32_t nblocks = (uint32_t)((n + TILE - 1) / TILE);
@@ -553,7 +544,7 @@ void radix_column_scan(hipStream_t s, uint32_t *rows, int64_t nrows, uint32_t nb
 // and the sort skips its first histogram pass (radix_sort_keys(..., first_hist_done = true) with the same n, bits and workspace).
 uint32_t *radix_first_histogram(int64_t n, int bit_lo, int bit_hi, DevBuf &tmp, int *shift, int *bits, int *tile)
 {
-    constexpr int TILE = RS_THREADS * ELBA_RS_KEY_ITEMS;
+    constexpr int TILE = RS_THREADS * RS_KEY_ITEMS;
     int shifts[64], widths[64];
     radix_digits(bit_lo, bit_hi, shifts, widths);
     const uint32_t nblocks = (uint32_t)((n + TILE - 1) / TILE);

@@ -79,10 +79,7 @@ __device__ __forceinline__ bool owns_pair(uint32_t i, uint32_t j, uint32_t row_l
 //  VGPRs instead of 128 the kernel loses one of them and runs twice as long (measured) —, 8 is what the dense path's 8 workgroups of 4 wavefronts per CU need)
 // SPEC: the reads path (OvSpecParams: its switches are constants) on the LDS tiers with 32-bit accumulators
 template <int BLOCK, bool GLOBAL, bool PAY, int DK = 2, bool SUFFIX = false, int TB = 0, bool SPEC = false>
-#ifndef ELBA_DENSE_OCC
-#define ELBA_DENSE_OCC 8
-#endif
-__global__ __launch_bounds__(BLOCK, SUFFIX ? ELBA_DENSE_OCC : (DK == 4 ? 1 : 4)) void k_spgemm_direct(std::conditional_t<SPEC, OvSpecParams, OvParams> p, int tier, uint32_t lds_tbits, uint32_t sample)
+__global__ __launch_bounds__(BLOCK, SUFFIX ? 8 : (DK == 4 ? 1 : 4)) void k_spgemm_direct(std::conditional_t<SPEC, OvSpecParams, OvParams> p, int tier, uint32_t lds_tbits, uint32_t sample)
 {
     static_assert(!PAY || !GLOBAL, "payload accumulators: LDS tiers only");
     static_assert(!SPEC || (!GLOBAL && !PAY && !SUFFIX), "the reads path: LDS tiers, 32-bit accumulators carrying posT");
@@ -315,10 +312,7 @@ __global__ __launch_bounds__(BLOCK, SUFFIX ? ELBA_DENSE_OCC : (DK == 4 ? 1 : 4))
             // front of the first owned one (first piece of an entry only) and a read that holds the k-mer twice (the diagonal); no padding
             // to skip, no ownership test, no ring.
             static_assert(!SUFFIX || !PAY, "dense path: 32-bit accumulators, the seeds of the few survivors are looked up");
-#ifndef ELBA_DENSE_UN
-#define ELBA_DENSE_UN 2
-#endif
-            constexpr uint32_t UN = ELBA_DENSE_UN;      // pieces per lane in flight
+            constexpr uint32_t UN = 2;      // pieces per lane in flight
             static_assert(UN % 2 == 0, "windows of two batches");
             const uint32_t jsh = p.j_shift, Sj = 1u << jsh;
             const uint32_t il = p.row_label ? p.row_label[i] : i;      // (partners are named by label: OvParams::row_label)
@@ -443,10 +437,7 @@ __global__ __launch_bounds__(BLOCK, SUFFIX ? ELBA_DENSE_OCC : (DK == 4 ? 1 : 4))
             uint32_t fh = 0, ft = 0;                                      // FIFO positions (uniform)
             uint2 ea, eb;
             uint32_t ca, cb;                                              // the two chunks on their way (first row entry, or NONE)
-#ifndef ELBA_CHUNKS
-#define ELBA_CHUNKS 3
-#endif
-            constexpr int XC = ELBA_CHUNKS - 2;                           // further chunks requested ahead: THREE in flight in all (numeric 6.75 -> 6.65 ms against two; four and six: no better)
+            constexpr int XC = 1;                           // further chunks requested ahead: THREE in flight in all (numeric 6.75 -> 6.65 ms against two; four and six: no better)
             uint2 ex[XC > 0 ? XC : 1]; uint32_t cx[XC > 0 ? XC : 1];
             auto load_chunk = [&](uint2 &en, uint32_t &cbase) {
                 // chunks are DRAWN, not dealt: a wavefront whose chunks held few products takes more of them (sequence numbers are the entries' ranks

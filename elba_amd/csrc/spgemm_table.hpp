@@ -9,17 +9,8 @@ enum : uint32_t {
     W_ACC_YRAW = 32 /*u64*/, W_ACC_Y = 34 /*u64*/, W_ACC_DONE = 36, W_ACC_NDIAG = 37, W_FB_N = 38,
     W_FB_C = 40 /*u64*/, W_FB_U = 42 /*u64*/, W_TOT_C = 44 /*u64*/, W_TOT_U = 46 /*u64*/, W_NUP = 48 /*u64*/, W_MIR = 50 /*u64*/, W_MX = 52, W_END = 54
 };
-// (A/B hook: a pre-mix of the key in front of the multiplicative hash — consecutive labels of the dense path land 316 slots apart on a 512-slot
-//  table, i.e. on 8 of the 32 banks; profiles/r03_notes.md)
-#if defined(ELBA_HMIX_SEL) && ELBA_HMIX_SEL == 1
-#define ELBA_HMIX(j) ((j) ^ ((j) >> 5))
-#elif defined(ELBA_HMIX_SEL) && ELBA_HMIX_SEL == 2
-#define ELBA_HMIX(j) (((j) * 0x85EBCA6Bu) ^ ((j) >> 3))
-#elif defined(ELBA_HMIX_SEL) && ELBA_HMIX_SEL == 3
-#define ELBA_HMIX(j) ((j) ^ ((j) << 7))
-#else
-#define ELBA_HMIX(j) (j)
-#endif
+// (the multiplicative hash takes the key as it is.  Consecutive labels of the dense path land 316 slots apart on a 512-slot table, i.e. on 8 of the 32 banks
+//  (profiles/r03_notes.md); pre-mixes of the key were measured, config 5 at 1/25: none 9.53 ms | j ^ j >> 5 9.62 | j * 0x85EBCA6B ^ j >> 3 10.04 | j ^ j << 7 9.75)
 template <bool GLOBAL>
 struct Table {
     uint32_t *keys, *cnt, *smin, *smax, *misc;
@@ -36,7 +27,7 @@ struct Table {
         // so at most 3T/4 + BLOCK slots are ever claimed (BLOCK <= T/8): the probe loop always meets an empty slot.
         if (full) return;
         const uint32_t mask = size() - 1;
-        uint32_t slot = (ELBA_HMIX(j) * 0x9E3779B1u) >> (32 - tbits);
+        uint32_t slot = (j * 0x9E3779B1u) >> (32 - tbits);
         // (A/B measured on MI355X: probing with a plain read before the CAS and guarding min/max with reads is SLOWER —
         //  0.84 vs 0.76 ms per step — the extra dependent LDS round trips cost more than the atomics they save.)
         for (;;) {
@@ -209,75 +200,46 @@ struct Table {
         typedef __attribute__((address_space(3))) uint32_t lds_u32;
         const lds_u32 *lk = (const lds_u32 *)keys;
         const uint32_t T = TB ? (1u << TB) : size(), tb = T * 4;
-        uint32_t slot[4], k[4], m[4];
-#ifndef ELBA_DENSE_NO_CMAX
-        uint32_t mx[4];
-#endif
+        uint32_t slot[4], k[4], m[4], mx[4];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) slot[r] = TB ? (ELBA_HMIX(j[r]) * 0x9E3779B1u) >> (32 - (TB ? TB : 1)) : lds_slot(j[r]);
+        for (int r = 0; r < 4; ++r) slot[r] = TB ? (j[r] * 0x9E3779B1u) >> (32 - (TB ? TB : 1)) : lds_slot(j[r]);
         const uint32_t base = (uint32_t)(uintptr_t)keys, one = 1u;
-#ifndef ELBA_DENSE_QUADS      // two look-ups in flight at a time (four: twelve more live registers in a kernel that is held to 64 — 36 bytes of scratch against 16; config 5 at 1/25: 8.89 vs 8.70 ms)
+        // two look-ups in flight at a time (four: twelve more live registers in a kernel that is held to 64 — 36 bytes of scratch against 16; config 5 at 1/25: 8.89 vs 8.70 ms)
 #pragma unroll
         for (int r0 = 0; r0 < 4; r0 += 2) {
-#else
-        {
-        constexpr int r0 = 0;
-#endif
 #pragma unroll
-        for (int r = r0; r < (
-#ifndef ELBA_DENSE_QUADS
-                              r0 + 2
-#else
-                              4
-#endif
-                              ); ++r) {
-            k[r] = __hip_atomic_load(&lk[slot[r]], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            m[r] = __hip_atomic_load(&lk[slot[r] + 2u * T], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#ifndef ELBA_DENSE_NO_CMAX
-            mx[r] = __hip_atomic_load(&lk[slot[r] + 3u * T], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#endif
-        }
-#pragma unroll
-        for (int r = r0; r < (
-#ifndef ELBA_DENSE_QUADS
-                              r0 + 2
-#else
-                              4
-#endif
-                              ); ++r) {
-            const uint32_t s = s0 + (uint32_t)r;
-            const bool v = (uint32_t)r >= vr;
-            const bool h = v && k[r] == j[r] && s >= m[r];
-            if (h) {
-#ifndef ELBA_DENSE_NO_CMAX
-                // The largest sequence number is only raised by a product that exceeds what the slot was READ to hold: eight wavefronts share a table and walk the
-                // row's chunks in order — the one furthest ahead raises it, the others read a value above theirs (equal addresses of a read broadcast, those of
-                // an atomic serialise).  Config 5 at 1/25: numeric 9.50 -> 8.95 ms (round 4 measured 7.3 ms with no ds_max at all: profiles/r04_notes.md).
-                if (TB) {
-                    const uint32_t a = base + (slot[r] << 2);
-                    asm volatile("ds_add_u32 %[a], %[one] offset:%[o1]\n" : : [a] "v"(a), [one] "v"(one), [o1] "n"(4 << TB) : "memory");
-                    if (s > mx[r]) asm volatile("ds_max_u32 %[a], %[s] offset:%[o3]\n" : : [a] "v"(a), [s] "v"(s), [o3] "n"(12 << TB) : "memory");
-                } else
-#endif
-                if (TB) {
-                    const uint32_t a = base + (slot[r] << 2);
-                    asm volatile("ds_add_u32 %[a], %[one] offset:%[o1]\n\t"
-                                 "ds_max_u32 %[a], %[s] offset:%[o3]\n"
-                                 : : [a] "v"(a), [one] "v"(one), [s] "v"(s), [o1] "n"(4 << TB), [o3] "n"(12 << TB) : "memory");
-                } else {
-                    uint32_t a;
-                    asm volatile("v_lshl_add_u32 %[a], %[slot], 2, %[cb]\n\t"
-                                 "ds_add_u32 %[a], %[one]\n\t"
-                                 "v_add_u32_e32 %[a], %[tb2], %[a]\n\t"
-                                 "ds_max_u32 %[a], %[s]\n"
-                                 : [a] "=&v"(a) : [slot] "v"(slot[r]), [cb] "s"(base + tb), [tb2] "s"(2u * tb), [one] "v"(one), [s] "v"(s) : "memory");
-                }
+            for (int r = r0; r < r0 + 2; ++r) {
+                k[r] = __hip_atomic_load(&lk[slot[r]], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                m[r] = __hip_atomic_load(&lk[slot[r] + 2u * T], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                mx[r] = __hip_atomic_load(&lk[slot[r] + 3u * T], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             }
-            miss[r] = v && !h;
-        }
+#pragma unroll
+            for (int r = r0; r < r0 + 2; ++r) {
+                const uint32_t s = s0 + (uint32_t)r;
+                const bool v = (uint32_t)r >= vr;
+                const bool h = v && k[r] == j[r] && s >= m[r];
+                if (h) {
+                    // The largest sequence number is only raised by a product that exceeds what the slot was READ to hold: eight wavefronts share a table and walk the
+                    // row's chunks in order — the one furthest ahead raises it, the others read a value above theirs (equal addresses of a read broadcast, those of
+                    // an atomic serialise).  Config 5 at 1/25: numeric 9.50 -> 8.95 ms (round 4 measured 7.3 ms with no ds_max at all: profiles/r04_notes.md).
+                    if (TB) {
+                        const uint32_t a = base + (slot[r] << 2);
+                        asm volatile("ds_add_u32 %[a], %[one] offset:%[o1]\n" : : [a] "v"(a), [one] "v"(one), [o1] "n"(4 << TB) : "memory");
+                        if (s > mx[r]) asm volatile("ds_max_u32 %[a], %[s] offset:%[o3]\n" : : [a] "v"(a), [s] "v"(s), [o3] "n"(12 << TB) : "memory");
+                    } else {
+                        uint32_t a;
+                        asm volatile("v_lshl_add_u32 %[a], %[slot], 2, %[cb]\n\t"
+                                     "ds_add_u32 %[a], %[one]\n\t"
+                                     "v_add_u32_e32 %[a], %[tb2], %[a]\n\t"
+                                     "ds_max_u32 %[a], %[s]\n"
+                                     : [a] "=&v"(a) : [slot] "v"(slot[r]), [cb] "s"(base + tb), [tb2] "s"(2u * tb), [one] "v"(one), [s] "v"(s) : "memory");
+                    }
+                }
+                miss[r] = v && !h;
+            }
         }
     }
-    __device__ __forceinline__ uint32_t lds_slot(uint32_t j) const { return (ELBA_HMIX(j) * 0x9E3779B1u) >> (32 - tbits); }      // (a 24-bit multiply, v_mul_u32_u24, was measured: no difference)
+    __device__ __forceinline__ uint32_t lds_slot(uint32_t j) const { return (j * 0x9E3779B1u) >> (32 - tbits); }      // (a 24-bit multiply, v_mul_u32_u24, was measured: no difference)
     __device__ __forceinline__ uint32_t ldrelaxed(const uint32_t *a) const
     {
         return __hip_atomic_load(a, __ATOMIC_RELAXED, GLOBAL ? __HIP_MEMORY_SCOPE_AGENT : __HIP_MEMORY_SCOPE_WORKGROUP);

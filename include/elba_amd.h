@@ -815,7 +815,7 @@ int  elba_get_device_view(elba_ctx *ctx, elba_device_view *view);
  *       UPPER > 255, option "kmer_no_msd", and elba_set_kmer_matrix_device (triples).
  *   "measure_prep" (0 | 1): diagnostic — elba_count_kmers runs its emit kernels a second time without what they write for the SpGEMM's sake alone and
  *       brackets both runs with events (elba_get_stat "spgemm_prep_us").
- *   "tune0" .. "tune7": A/B switches of the round in progress (what each means is said where the library reads it); never a result-changing switch. */
+ *   "tune1" .. "tune5", "tune7": A/B switches of the round in progress (what each means is said where the library reads it); never a result-changing switch. */
 int  elba_set_option(elba_ctx *ctx, const char *name, int64_t value);
 /* Diagnostic counters of the last stage call by name (unknown name: ELBA_ERR_INVALID_ARG); none of them is part of a result.
  *   "overlap_mirror_placed"  mirrored entries of the last elba_create_seed_matrix call that waited in the staging area for the placement pass

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""The k-mer stage of a bench.py workload alone (elba_count_kmers twice, nothing behind it) — for rocprofv3 kernel traces of TIMING EXPERIMENTS whose
-results are wrong by construction (ELBA_X_* builds): nothing downstream ever reads what they leave.
+"""The k-mer stage of a bench.py workload alone (elba_count_kmers twice, nothing behind it) — for rocprofv3 kernel traces of a library build whose
+k-mer kernels are under experiment: nothing downstream ever reads what they leave.
 usage: [ELBA_AMD_LIB=...] [ELBA_BENCH_OPTIONS=a=1,b=2] python3 profiles/tools/kmer_only.py [workload] [--matrix]"""
 import os, sys, time
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))

@@ -112,3 +112,18 @@ def test_exports_follow_the_tightened_cases(small_err):
     for case in sorted(sc.CASES):
         if sc.CASES[case].get("gpu", True) and sc.CASES[case].get("tightening", False):
             _walk(case, small_err, counter_everywhere=True)
+
+
+def test_retired_options_are_unknown_names():
+    """elba_set_option answers the retired switches "tune0", "tune6" and "msd_no_emit8" like any unknown name; the tuneN still read are taken"""
+    e = elba_amd.Engine(17, 2, 8)
+    try:
+        for name in ("tune0", "tune6", "tune8", "msd_no_emit8", "no_such_option"):
+            with pytest.raises(elba_amd.ElbaError) as err:
+                e.set_option(name, 1)
+            assert err.value.status == 1, (name, str(err.value))                       # ELBA_ERR_INVALID_ARG
+        for name in ("tune1", "tune2", "tune3", "tune4", "tune5", "tune7"):
+            e.set_option(name, 1)
+            e.set_option(name, 0)
+    finally:
+        e.close()
