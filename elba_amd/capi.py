@@ -125,6 +125,27 @@ LINK_DTYPE = np.dtype([("from", "<u4"), ("to", "<u4"), ("from_read", "<u4"), ("t
 LINK_CLOSURE = 1          # elba_link_t.flags bit 0
 
 
+class PlaceCfg(C.Structure):
+    _fields_ = [("skip_flags", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class Placements(C.Structure):
+    _fields_ = [("nreads", C.c_int64), ("ncontigs", C.c_int64), ("reads", C.c_void_p), ("seg_off", C.c_void_p), ("seg_start", C.c_void_p), ("seg_depth", C.c_void_p),
+                ("credited_reads", C.c_void_p), ("credited_bases", C.c_void_p)]
+
+
+class PlaceStats(C.Structure):
+    _fields_ = [("nreads", C.c_int64), ("chain", C.c_int64), ("anchored", C.c_int64), ("unanchored", C.c_int64), ("skipped", C.c_int64), ("empty", C.c_int64),
+                ("candidates", C.c_int64), ("clipped", C.c_int64), ("outside", C.c_int64), ("wrapped", C.c_int64), ("segments", C.c_int64), ("max_depth", C.c_int64),
+                ("credited_bases", C.c_int64), ("ms_total", C.c_float), ("reserved", C.c_int32)]
+
+
+# elba_placement_t: 24 bytes
+PLACEMENT_DTYPE = np.dtype([("start", "<i8"), ("contig", "<i4"), ("anchor", "<u4"), ("score", "<i4"), ("strand", "u1"), ("kind", "u1"), ("flags", "u1"), ("reserved", "u1")])
+PLACE_NONE, PLACE_CHAIN, PLACE_ANCHORED = 0, 1, 2      # elba_placement_t.kind
+PLACE_CLIPPED, PLACE_OUTSIDE, PLACE_WRAPPED = 1, 2, 4  # elba_placement_t.flags
+
+
 class PileupCfg(C.Structure):
     _fields_ = [("mode", C.c_int32), ("margin", C.c_int32), ("min_depth", C.c_int32), ("min_run", C.c_int32), ("trim_len", C.c_int32), ("reserved", C.c_int32)]
 
@@ -258,6 +279,7 @@ EXPORTED_SYMBOLS = [
     "elba_clip_tips", "elba_pop_bubbles", "elba_cut_weak_overlaps", "elba_cut_bridges", "elba_resolve_stars",
     "elba_set_reads_text", "elba_export_read_index",
     "elba_export_assembly_links", "elba_free_links",
+    "elba_place_reads", "elba_free_placements",
 ]
 
 _lib = None
@@ -322,6 +344,8 @@ def load_library():
     L.elba_export_read_contigs.restype = i32; L.elba_export_read_contigs.argtypes = [vp, vp, i64]
     L.elba_export_assembly_links.restype = i32; L.elba_export_assembly_links.argtypes = [vp, C.POINTER(Links), C.POINTER(GraphStats)]
     L.elba_free_links.restype = None; L.elba_free_links.argtypes = [C.POINTER(Links)]
+    L.elba_place_reads.restype = i32; L.elba_place_reads.argtypes = [vp, C.POINTER(PlaceCfg), C.POINTER(Placements), C.POINTER(PlaceStats)]
+    L.elba_free_placements.restype = None; L.elba_free_placements.argtypes = [C.POINTER(Placements)]
     L.elba_read_pileup.restype = i32; L.elba_read_pileup.argtypes = [vp, C.POINTER(PileupCfg), C.POINTER(PileupStats)]
     L.elba_export_pileup.restype = i32; L.elba_export_pileup.argtypes = [vp, C.POINTER(Pileup)]
     L.elba_free_pileup.restype = None; L.elba_free_pileup.argtypes = [C.POINTER(Pileup)]
@@ -734,6 +758,26 @@ class Engine:
         out = _stats(st)
         del out["reserved"]
         return links, out
+
+    def place_reads(self, skip_flags=1, reserved=(0, 0, 0)):
+        """Every read on its contig and the depth of every contig base (include/elba_amd.h states the rule): chain reads where the contig
+        stage put them, every other read that has none of `skip_flags` in its read flags through its best-scoring passed pair with a
+        chain read.  Returns ({reads (PLACEMENT_DTYPE, one per read), seg_off (i64[ncontigs + 1]), seg_start, seg_depth (i32),
+        credited_reads, credited_bases (i64[ncontigs])}, stats dict).  formats.write_placements_paf and write_gfa(depth=) take them."""
+        cfg = PlaceCfg(int(skip_flags), (C.c_int32 * 3)(*[int(x) for x in reserved]))
+        o, st = Placements(), PlaceStats()
+        self._check(self.L.elba_place_reads(self.h, C.byref(cfg), C.byref(o), C.byref(st)))
+        try:
+            M, nc = int(o.nreads), int(o.ncontigs)
+            seg_off = _copy(o.seg_off, nc + 1, np.int64)
+            S = int(seg_off[-1])
+            pl = dict(reads=_copy(o.reads, M, PLACEMENT_DTYPE), seg_off=seg_off, seg_start=_copy(o.seg_start, S, np.int32), seg_depth=_copy(o.seg_depth, S, np.int32),
+                      credited_reads=_copy(o.credited_reads, nc, np.int64), credited_bases=_copy(o.credited_bases, nc, np.int64))
+        finally:
+            self.L.elba_free_placements(C.byref(o))
+        out = _stats(st)
+        del out["reserved"]
+        return pl, out
 
     # --- read pileups and chimera flags (src/PruneChimeras.cpp; after align_seeds, before transitive_reduction) ---
     def read_pileup(self, mode=0, margin=0, min_depth=1, min_run=1, trim_len=2500):

@@ -495,6 +495,25 @@ void elba_free_links(elba_links_t *l)
     memset(l, 0, sizeof(*l));
 }
 
+int elba_place_reads(elba_ctx *ctx, const elba_place_cfg *cfg, elba_placements_t *out, elba_place_stats *stats)
+{
+    if (out) memset(out, 0, sizeof(*out));                        // (before anything can fail: what is freed below is this call's)
+    const int rc = guarded(ctx, [&](Ctx &c) {
+        ELBA_REQUIRE(out, ELBA_ERR_INVALID_ARG, "place_reads: null output");
+        stage_place_reads(c, cfg, out);
+        if (stats) *stats = c.plstats;
+    });
+    if (rc != ELBA_OK && ctx && out) elba_free_placements(out);      // (a copy that failed behind the allocations)
+    return rc;
+}
+
+void elba_free_placements(elba_placements_t *p)
+{
+    if (!p) return;
+    free(p->reads); free(p->seg_off); free(p->seg_start); free(p->seg_depth); free(p->credited_reads); free(p->credited_bases);
+    memset(p, 0, sizeof(*p));
+}
+
 int elba_export_contig_kinds(elba_ctx *ctx, uint8_t *kind, int64_t ncontigs)
 {
     return guarded(ctx, [&](Ctx &c) {
@@ -792,6 +811,9 @@ int elba_release_workspace(elba_ctx *ctx)
         c.cg_ptr.release(); c.cg_slot.release(); c.cg_kdeg.release(); c.cg_term.release(); c.cg_vinfo.release(); c.cg_ctr.release();   // contig scratch (the results stay)
         c.cg_flag.release(); c.cg_cidx.release(); c.cg_nel.release(); c.cg_eoff.release();
         c.gl_ptr.release(); c.gl_bits.release(); c.gl_cnt.release(); c.gl_off.release(); c.gl_ctr.release(); c.gl_part.release(); c.gl_out.release();          // assembly-link scratch
+        c.pl_cstart.release(); c.pl_cstrand.release(); c.pl_best.release(); c.pl_rec.release(); c.pl_clen.release(); c.pl_cred.release(); c.pl_ctr.release();    // placement scratch
+        c.pl_k0.release(); c.pl_k1.release(); c.pl_eptr.release(); c.pl_head.release(); c.pl_hidx.release(); c.pl_delta.release(); c.pl_dsum.release(); c.pl_gstart.release();
+        c.pl_tok.release(); c.pl_tpos.release(); c.pl_seg_off.release(); c.pl_seg_start.release(); c.pl_seg_depth.release();
         for (int b = 0; b < 2; ++b) { c.cg_far[b].release(); c.cg_rank[b].release(); c.cg_mn[b].release(); c.cg_cfar[b].release(); c.cg_crank[b].release(); }
         c.pu_k0.release(); c.pu_k1.release(); c.pu_eptr.release(); c.pu_head.release(); c.pu_hidx.release(); c.pu_delta.release();   // pileup scratch (the results stay)
         c.pu_dsum.release(); c.pu_gstart.release(); c.pu_tok.release(); c.pu_tpos.release(); c.pu_sel.release(); c.pu_rows.release(); c.pu_cols.release(); c.pu_vals.release();
@@ -860,6 +882,18 @@ int elba_get_stat(elba_ctx *ctx, const char *name, int64_t *value)
             if (!strcmp(f, "segments")) x = g.segments; else if (!strcmp(f, "candidates")) x = g.candidates; else if (!strcmp(f, "links")) x = g.links;
             else if (!strcmp(f, "closures")) x = g.closures; else if (!strcmp(f, "twisted")) x = g.twisted; else if (!strcmp(f, "unplaced")) x = g.unplaced;
             else if (!strcmp(f, "clamped")) x = g.clamped; else if (!strcmp(f, "asymmetric")) x = g.asymmetric;
+            else throw Error{ELBA_ERR_INVALID_ARG, std::string("get_stat: unknown counter ") + name};
+            *value = ok ? x : 0;
+        }
+        else if (!strncmp(name, "place_", 6)) {                    // the last elba_place_reads on the contigs that are valid now
+            const bool ok = has(c.v, P_S, P_CONTIGS) && c.pl_for == c.cg_serial && c.pl_for != 0;
+            const elba_place_stats &g = c.plstats;
+            const char *f = name + 6;
+            int64_t x;
+            if (!strcmp(f, "chain")) x = g.chain; else if (!strcmp(f, "anchored")) x = g.anchored; else if (!strcmp(f, "unanchored")) x = g.unanchored;
+            else if (!strcmp(f, "skipped")) x = g.skipped; else if (!strcmp(f, "candidates")) x = g.candidates; else if (!strcmp(f, "clipped")) x = g.clipped;
+            else if (!strcmp(f, "outside")) x = g.outside; else if (!strcmp(f, "wrapped")) x = g.wrapped; else if (!strcmp(f, "segments")) x = g.segments;
+            else if (!strcmp(f, "max_depth")) x = g.max_depth;
             else throw Error{ELBA_ERR_INVALID_ARG, std::string("get_stat: unknown counter ") + name};
             *value = ok ? x : 0;
         }

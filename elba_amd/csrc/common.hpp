@@ -337,6 +337,15 @@ struct Ctx {
     elba_pileup_stats pustats{};
     elba_pileup_cfg pu_cfg{};                  // the cfg of the pileup that is valid now (trim.hip's long runs are its min_depth / min_run)
 
+    // read placements and contig depth (place.hip): all scratch, in buffers of its own so that a valid pileup stays untouched — chain start /
+    // strand per read, the winning candidate per read, the records, contig lengths, the endpoint keys and what the pileup's keys-to-segments
+    // sequence needs (DepthBufs), per-contig credits, the counters.  pl_for: the contig call (cg_serial) the counts in plstats belong to
+    DevBuf pl_cstart, pl_cstrand, pl_best, pl_rec, pl_clen, pl_cred, pl_ctr;
+    DevBuf pl_k0, pl_k1, pl_eptr, pl_head, pl_hidx, pl_delta, pl_dsum, pl_gstart, pl_tok, pl_tpos, pl_seg_off, pl_seg_start, pl_seg_depth;
+    EventTimer pl_t_total;
+    elba_place_stats plstats{};
+    uint64_t pl_for = 0;
+
     // trimmed reads (trim.hip): a snapshot in buffers of its own — packed / off / len in DnaBuffer layout, the map (src, beg, end); it survives
     // elba_prune_reads and elba_release_workspace, a new read set or a new pileup invalidates it, elba_adopt_trimmed_reads consumes it
     int64_t tm_n = 0, tm_packed_bytes = 0;
@@ -449,6 +458,12 @@ inline ReadSource read_source(Ctx &c, int64_t M, const char *who, const char *wh
     throw Error{ELBA_ERR_STATE, std::string(who) + ": the " + w + " are not on this context (elba_set_reads or elba_dist_set_all_reads)"};
 }
 
+// The buffer set of the pileup's keys-to-segments sequence (pileup.hip: depth_segments), so that place.hip runs the same launches on buffers
+// of its own
+struct DepthBufs { DevBuf &k0, &k1, &eptr, &head, &hidx, &delta, &dsum, &gstart, &tok, &tpos, &seg_off, &seg_start, &seg_depth; };
+void depth_reserve(const DepthBufs &b, int64_t max_keys, int64_t G);
+const uint64_t *depth_segments(Ctx &c, const DepthBufs &b, int64_t E, int64_t M, int mb, int pb, const uint32_t *len, unsigned long long *ctr);
+
 // ---- stages -----------------------------------------------------------------------------------------------------
 void stage_set_reads_fasta(Ctx &c, const char *chunk, int64_t chunk_bytes, uint64_t chunk_file_offset, const elba_fasta_record_t *recs, int64_t nreads,
                            int64_t first_global_id, elba_ingest_stats *stats);      // ingest.hip
@@ -478,6 +493,7 @@ void stage_transitive_reduction(Ctx &c, double bad_read_cutoff, int fuzz);   // 
 void stage_generate_contigs(Ctx &c, int flags);                                          // contig.hip
 void stage_generate_contigs_ex(Ctx &c, const elba_contig_cfg *cfg);                      // contig.hip
 void stage_export_assembly_links(Ctx &c, elba_links_t *out);                             // graph_links.hip (out->links: malloc)
+void stage_place_reads(Ctx &c, const elba_place_cfg *cfg, elba_placements_t *out);        // place.hip (out's arrays: malloc)
 void stage_read_pileup(Ctx &c, const elba_pileup_cfg *cfg);                   // pileup.hip
 void stage_prune_reads(Ctx &c, int mask, int64_t *kept);
 void stage_trim_reads(Ctx &c, const elba_trim_cfg *cfg);                      // trim.hip

@@ -260,7 +260,56 @@ PuInput pileup_input(Ctx &c, const char *who)
     return in;
 }
 
+DepthBufs pileup_depth_bufs(Ctx &c)
+{
+    return {c.pu_k0, c.pu_k1, c.pu_eptr, c.pu_head, c.pu_hidx, c.pu_delta, c.pu_dsum, c.pu_gstart, c.pu_tok, c.pu_tpos, c.pu_seg_off, c.pu_seg_start, c.pu_seg_depth};
+}
+
 }  // namespace
+
+// Sorted keys to segments (the sort .. k_pu_segs of the header), shared with place.hip, which runs it over contigs: E endpoint keys
+// group << (pb + 1) | pos << 1 | kind in b.k0 (groups below M < 2^mb, positions 0 .. len[group] < 2^pb) become, per group, the maximal runs
+// of equal depth from 0 to len[group] in b.seg_off / seg_start / seg_depth.  ctr[3] = the segments, ctr[4] = the largest depth (an atomicMax:
+// zeroed by the caller).  Returns the sorted keys (b.k0 or b.k1).  Everything is queued on the context's stream; nothing synchronises.
+// depth_reserve sizes the set for at most max_keys endpoints of G groups.
+void depth_reserve(const DepthBufs &b, int64_t max_keys, int64_t G)
+{
+    const int64_t ntok_max = max_keys + G;                      // token slots: groups (<= keys) + one per group of the caller
+    b.k0.reserve((size_t)(max_keys + 4) * 8); b.k1.reserve((size_t)(max_keys + 4) * 8);
+    b.eptr.reserve((size_t)(G + 2) * 4);
+    b.head.reserve((size_t)(max_keys + 2) * 4); b.hidx.reserve((size_t)(max_keys + 2) * 4); b.delta.reserve((size_t)(max_keys + 2) * 4); b.dsum.reserve((size_t)(max_keys + 2) * 4);
+    b.gstart.reserve((size_t)(max_keys + 2) * 4); b.tok.reserve((size_t)(ntok_max + 2) * 4); b.tpos.reserve((size_t)(ntok_max + 2) * 4);
+    b.seg_off.reserve((size_t)(G + 2) * 8);
+    // segments: at most one per endpoint, plus one per group
+    b.seg_start.reserve((size_t)(ntok_max + 1) * 4); b.seg_depth.reserve((size_t)(ntok_max + 1) * 4);
+}
+
+const uint64_t *depth_segments(Ctx &c, const DepthBufs &b, int64_t E, int64_t M, int mb, int pb, const uint32_t *len, unsigned long long *ctr)
+{
+    hipStream_t s = c.stream;
+    uint32_t *eptr = b.eptr.as<uint32_t>(), *head = b.head.as<uint32_t>(), *hidx = b.hidx.as<uint32_t>(), *delta = b.delta.as<uint32_t>();
+    uint32_t *dsum = b.dsum.as<uint32_t>(), *gstart = b.gstart.as<uint32_t>(), *tok = b.tok.as<uint32_t>(), *tpos = b.tpos.as<uint32_t>();
+    const uint64_t *keys = b.k0.as<uint64_t>();
+    if (E > 0) {
+        const int which = radix_sort_keys(s, b.k0.as<uint64_t>(), b.k1.as<uint64_t>(), E, 0, mb + pb + 1, c.ws_sort);
+        keys = which ? b.k1.as<uint64_t>() : b.k0.as<uint64_t>();
+    }
+    group_offsets_u32(s, keys, pb + 1, E, eptr, M);             // (E = 0: every pointer 0)
+    const int64_t ntok = E + M;                                 // token slots: groups (<= E) + one per read
+    ELBA_HIP(hipMemsetAsync(tok, 0, (size_t)(ntok + 1) * 4, s));
+    const unsigned nbE = (unsigned)((E + 1 + 255) / 256);
+    hipLaunchKernelGGL(k_pu_marks, dim3(nbE), dim3(256), 0, s, keys, eptr, (uint32_t)M, E, head, delta);
+    exclusive_scan_u32(s, head, hidx, E + 1, c.ws_scan);
+    exclusive_scan_u32(s, delta, dsum, E + 1, c.ws_scan);
+    hipLaunchKernelGGL(k_pu_groups, dim3(nbE), dim3(256), 0, s, head, hidx, eptr, (uint32_t)M, E, gstart);
+    const int64_t nt = (E > M ? E : M) + 1;
+    const unsigned nbt = (unsigned)((nt + 255) / 256);
+    hipLaunchKernelGGL(k_pu_tokens, dim3(nbt), dim3(256), 0, s, keys, eptr, hidx, gstart, dsum, len, (uint32_t)M, pb, E, tok);
+    exclusive_scan_u32(s, tok, tpos, ntok + 1, c.ws_scan);
+    hipLaunchKernelGGL(k_pu_segs, dim3(nbt), dim3(256), 0, s, keys, eptr, hidx, gstart, dsum, len, tok, tpos, (uint32_t)M, pb, ntok,
+                       b.seg_off.as<int64_t>(), b.seg_start.as<int32_t>(), b.seg_depth.as<int32_t>(), ctr);
+    return keys;
+}
 
 void stage_read_pileup(Ctx &c, const elba_pileup_cfg *cfgp)
 {
@@ -281,18 +330,11 @@ void stage_read_pileup(Ctx &c, const elba_pileup_cfg *cfgp)
     PuParams p{};
     p.rows = in.rows; p.cols = in.cols; p.vals = in.vals; p.n = n; p.len = in.len; p.M = (uint32_t)M; p.pb = pb;
     p.mode = cfg.mode; p.margin = cfg.margin; p.min_depth = cfg.min_depth; p.min_run = cfg.min_run; p.trim_len = cfg.trim_len;
-    const int64_t ntok_max = n4 + M;                            // token slots: groups (<= E <= 4n) + one per read
-    c.pu_k0.reserve((size_t)(n4 + 4) * 8); c.pu_k1.reserve((size_t)(n4 + 4) * 8);
-    c.pu_eptr.reserve((size_t)(M + 2) * 4);
-    c.pu_head.reserve((size_t)(n4 + 2) * 4); c.pu_hidx.reserve((size_t)(n4 + 2) * 4); c.pu_delta.reserve((size_t)(n4 + 2) * 4); c.pu_dsum.reserve((size_t)(n4 + 2) * 4);
-    c.pu_gstart.reserve((size_t)(n4 + 2) * 4); c.pu_tok.reserve((size_t)(ntok_max + 2) * 4); c.pu_tpos.reserve((size_t)(ntok_max + 2) * 4);
+    const DepthBufs db = pileup_depth_bufs(c);
+    depth_reserve(db, n4, M);                                   // keys, marks, scans, tokens and segments for at most 4n endpoints of M reads
     c.pu_ctr.reserve(128);
-    c.pu_seg_off.reserve((size_t)(M + 2) * 8); c.pu_trim.reserve((size_t)(M + 1) * 8); c.pu_flags.reserve((size_t)M + 4);
-    // segments: at most 2 credited intervals per pair, 2 endpoints each, plus one per read
-    c.pu_seg_start.reserve((size_t)(n4 + M + 1) * 4); c.pu_seg_depth.reserve((size_t)(n4 + M + 1) * 4);
+    c.pu_trim.reserve((size_t)(M + 1) * 8); c.pu_flags.reserve((size_t)M + 4);
     p.keys = c.pu_k0.as<uint64_t>(); p.ctr = c.pu_ctr.as<unsigned long long>();
-    uint32_t *eptr = c.pu_eptr.as<uint32_t>(), *head = c.pu_head.as<uint32_t>(), *hidx = c.pu_hidx.as<uint32_t>(), *delta = c.pu_delta.as<uint32_t>();
-    uint32_t *dsum = c.pu_dsum.as<uint32_t>(), *gstart = c.pu_gstart.as<uint32_t>(), *tok = c.pu_tok.as<uint32_t>(), *tpos = c.pu_tpos.as<uint32_t>();
     c.pu_t_total.start(s);
     ELBA_HIP(hipMemsetAsync(c.pu_ctr.p, 0, 128, s));
     ELBA_HIP(hipMemsetAsync(p.ctr + 2, 0xff, 8, s));
@@ -312,25 +354,7 @@ void stage_read_pileup(Ctx &c, const elba_pileup_cfg *cfgp)
                                               std::to_string(o.begQ) + ", " + std::to_string(o.endQ) + "), T [" + std::to_string(o.begT) + ", " + std::to_string(o.endT) + ")"};
     }
     const int64_t E = 2 * (int64_t)h[1];                        // endpoints
-    const uint64_t *keys = p.keys;
-    if (E > 0) {
-        const int which = radix_sort_keys(s, c.pu_k0.as<uint64_t>(), c.pu_k1.as<uint64_t>(), E, 0, mb + pb + 1, c.ws_sort);
-        keys = which ? c.pu_k1.as<uint64_t>() : c.pu_k0.as<uint64_t>();
-    }
-    group_offsets_u32(s, keys, pb + 1, E, eptr, M);             // (E = 0: every pointer 0)
-    const int64_t ntok = E + M;                                 // token slots: groups (<= E) + one per read
-    ELBA_HIP(hipMemsetAsync(tok, 0, (size_t)(ntok + 1) * 4, s));
-    const unsigned nbE = (unsigned)((E + 1 + 255) / 256);
-    hipLaunchKernelGGL(k_pu_marks, dim3(nbE), dim3(256), 0, s, keys, eptr, (uint32_t)M, E, head, delta);
-    exclusive_scan_u32(s, head, hidx, E + 1, c.ws_scan);
-    exclusive_scan_u32(s, delta, dsum, E + 1, c.ws_scan);
-    hipLaunchKernelGGL(k_pu_groups, dim3(nbE), dim3(256), 0, s, head, hidx, eptr, (uint32_t)M, E, gstart);
-    const int64_t nt = (E > M ? E : M) + 1;
-    const unsigned nbt = (unsigned)((nt + 255) / 256);
-    hipLaunchKernelGGL(k_pu_tokens, dim3(nbt), dim3(256), 0, s, keys, eptr, hidx, gstart, dsum, in.len, (uint32_t)M, pb, E, tok);
-    exclusive_scan_u32(s, tok, tpos, ntok + 1, c.ws_scan);
-    hipLaunchKernelGGL(k_pu_segs, dim3(nbt), dim3(256), 0, s, keys, eptr, hidx, gstart, dsum, in.len, tok, tpos, (uint32_t)M, pb, ntok,
-                       c.pu_seg_off.as<int64_t>(), c.pu_seg_start.as<int32_t>(), c.pu_seg_depth.as<int32_t>(), p.ctr);
+    depth_segments(c, db, E, M, mb, pb, in.len, p.ctr);
     if (M > 0)
         hipLaunchKernelGGL(k_pu_reads, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, c.pu_seg_off.as<int64_t>(), c.pu_seg_start.as<int32_t>(),
                            c.pu_seg_depth.as<int32_t>(), in.len, (uint32_t)M, cfg.min_depth, cfg.min_run, cfg.trim_len, c.pu_trim.as<int2>(), c.pu_flags.as<uint8_t>(), p.ctr);

@@ -113,16 +113,62 @@ def write_contigs_fasta(path, seqs, first=0, kinds=None):
             f.write(b"\n")
 
 
-def write_gfa(path, seqs, kinds, links, chains=None):
+def placement_interval(p, length, contig_len, circular):
+    """(query begin, query end, target begin, target end) of one placed record of Engine.place_reads(): the credited part of the read in
+    FORWARD read coordinates and where it lies on the contig.  On a path or single-read contig the target interval is [max(start, 0),
+    min(start + len, L)), empty (begin = end, at the nearer contig end) for a read flagged outside.  On a circular contig it is min(len, L)
+    bases from start mod L, and the end of a wrapped read runs past L by the bases that wrap."""
+    start, l, L = int(p["start"]), int(length), int(contig_len)
+    if circular:
+        cred = min(l, L)
+        tb = start % L if L > 0 else 0
+        te, ob, oe = tb + cred, 0, cred
+    else:
+        tb = min(max(start, 0), L)
+        te = max(tb, min(start + l, L))
+        ob, oe = min(max(tb - start, 0), l), min(max(te - start, 0), l)
+    return (l - oe, l - ob, tb, te) if int(p["strand"]) else (ob, oe, tb, te)
+
+
+def write_placements_paf(path, placements, names, lens, contig_lens, kinds=None):
+    """A reads-to-contigs PAF from Engine.place_reads() (its dict, or its "reads" array): one line per placed read (chain or anchored), by
+    ascending read — name, length, the credited interval in forward read coordinates, strand, `contig<i>`, its length, the target interval
+    (placement_interval), then in the style of paf_line the anchor pair's score (0 for chain reads), the block length (target end - begin)
+    and 255.  `kinds` (Engine.export_contigs()["kinds"]) says which contigs are circular.  Without it none may be: the records do not
+    carry their contig's kind, so a record with the wrapped flag raises instead of being written as if it lay on a path."""
+    reads = placements["reads"] if isinstance(placements, dict) else placements
+    if not (len(reads) == len(names) == len(lens)):
+        raise ValueError("write_placements_paf: one record, one name and one length per read")
+    if kinds is not None and len(kinds) != len(contig_lens):
+        raise ValueError("write_placements_paf: one kind per contig")
+    with open(path, "w") as f:
+        for r, p in enumerate(reads):
+            if not int(p["kind"]):
+                continue
+            k = int(p["contig"])
+            if not 0 <= k < len(contig_lens):
+                raise ValueError("write_placements_paf: read %d names contig %d of %d" % (r, k, len(contig_lens)))
+            if kinds is None and int(p["flags"]) & 4:
+                raise ValueError("write_placements_paf: read %d is wrapped, so contig %d is circular: give the contigs' kinds" % (r, k))
+            qb, qe, tb, te = placement_interval(p, lens[r], contig_lens[k], kinds is not None and int(kinds[k]) == 1)
+            f.write("%s\t%d\t%d\t%d\t%s\tcontig%d\t%d\t%d\t%d\t%d\t%d\t255\n" % (names[r], int(lens[r]), qb, qe, "-" if int(p["strand"]) else "+", k, int(contig_lens[k]),
+                                                                                    tb, te, int(p["score"]), te - tb))
+
+
+def write_gfa(path, seqs, kinds, links, chains=None, depth=None):
     """The assembly graph as GFA 1: `H\tVN:Z:1.0`, one `S\tcontig<i>\t<seq>\tLN:i:<len>` per contig (the names of write_contigs_fasta;
     with `chains`, the chain_off of Engine.export_contigs() or one chain per contig, also `\tRC:i:<reads>`), and one
     `L\tcontig<a>\t+|-\tcontig<b>\t+|-\t<overlap>M` per record of Engine.assembly_links(), in their order, the closure records of circular
-    contigs (a link from the contig's end to its own start, 0M) included.  `kinds` is checked against the closures: one per circular contig."""
+    contigs (a link from the contig's end to its own start, 0M) included.  `kinds` is checked against the closures: one per circular contig.
+    With `depth`, the credited_bases of Engine.place_reads() (one per contig), every S line also ends in `\tDP:f:<credited bases / length>`
+    with two decimals (0.00 for a contig of no bases); without it every byte is as before."""
     n = len(seqs)
     if kinds is not None and len(kinds) != n:
         raise ValueError("write_gfa: one kind per contig")
     if chains is not None and len(chains) not in (n, n + 1):
         raise ValueError("write_gfa: chains is chain_off (n + 1 offsets) or one chain per contig")
+    if depth is not None and len(depth) != n:
+        raise ValueError("write_gfa: one depth (credited bases) per contig")
     closed = sorted(int(r["from"]) for r in links if int(r["flags"]) & 1)
     if kinds is not None and closed != [i for i in range(n) if int(kinds[i]) == 1]:
         raise ValueError("write_gfa: the closure records are not those of the circular contigs")
@@ -133,6 +179,8 @@ def write_gfa(path, seqs, kinds, links, chains=None):
             f.write(b"S\tcontig%d\t%s\tLN:i:%d" % (i, b, len(b)))
             if chains is not None:
                 f.write(b"\tRC:i:%d" % (int(chains[i + 1]) - int(chains[i]) if len(chains) == n + 1 else len(chains[i])))
+            if depth is not None:
+                f.write(b"\tDP:f:%.2f" % (int(depth[i]) / len(b) if len(b) else 0.0))
             f.write(b"\n")
         for r in links:
             if int(r["from"]) >= n or int(r["to"]) >= n:

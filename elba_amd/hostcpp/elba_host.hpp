@@ -27,6 +27,7 @@
 //   (none)                                                                    elba::CutWeakOverlaps(S, reads, min_ratio_q16): weak overlaps at branching read ends leave S
 //   asmtools/bridge_removal.py (a script run on the written-out graph)        elba::CutBridges(S, reads, max_bridge_reads, min_flank_reads): short chains between two long paths leave S
 //   asmtools/star_resolution.py (a script run on the written-out graphs)      elba::ResolveStars(S, reads, rounds): the stray arm of a three-armed star leaves S
+//   (not in the reference: reads-to-contigs PAF, depth per contig)             elba::place_reads(S) + elba::write_placements_paf(...), write_gfa(..., depth)
 //   asmtools/create_gml.py, assemble_gml.py (scripts over the PAF files)      elba::assembly_links(S) + elba::write_gfa(...): the contigs as segments and the
 //                                                                             edges of S at branch reads as links, found on the GPU, written as GFA 1
 //
@@ -35,6 +36,7 @@
 #pragma once
 #include <cstdint>
 #include <algorithm>
+#include <cstdio>
 #include <cstring>
 #include <fstream>
 #include <iterator>
@@ -763,13 +765,15 @@ inline std::vector<elba_link_t> assembly_links(StringGraph &S, elba_graph_stats 
 
 // write_gfa — GFA 1, byte for byte what formats.write_gfa writes: `H\tVN:Z:1.0`, one `S\tcontig<i>\t<seq>\tLN:i:<len>` per contig (the names
 // of parallel_write_contigs; with chain_reads, the reads per contig, also `\tRC:i:<reads>`) and one `L\tcontig<a>\t+|-\tcontig<b>\t+|-\t<overlap>M`
-// per record, closures included.  kinds, if given, is checked against the closures: one per circular contig.
+// per record, closures included.  kinds, if given, is checked against the closures: one per circular contig.  With depth, the credited
+// bases per contig (Placements::credited_bases), every S line also ends in `\tDP:f:<credited bases / length>` with two decimals.
 inline void write_gfa(const std::string &gfa_fname, const std::vector<std::string> &contigs, const std::vector<uint8_t> *kinds, const std::vector<elba_link_t> &links,
-                      const std::vector<int64_t> *chain_reads = nullptr)
+                      const std::vector<int64_t> *chain_reads = nullptr, const std::vector<int64_t> *depth = nullptr)
 {
     const size_t n = contigs.size();
     if (kinds && kinds->size() != n) throw Error(ELBA_ERR_INVALID_ARG, "write_gfa: one kind per contig");
     if (chain_reads && chain_reads->size() != n) throw Error(ELBA_ERR_INVALID_ARG, "write_gfa: one read count per contig");
+    if (depth && depth->size() != n) throw Error(ELBA_ERR_INVALID_ARG, "write_gfa: one depth (credited bases) per contig");
     if (kinds) {
         std::vector<uint32_t> closed, circular;
         for (const elba_link_t &r : links) if (r.flags & 1) closed.push_back(r.from);
@@ -782,6 +786,11 @@ inline void write_gfa(const std::string &gfa_fname, const std::vector<std::strin
     for (size_t i = 0; i < n; ++i) {
         out << "S\tcontig" << i << "\t" << contigs[i] << "\tLN:i:" << contigs[i].size();
         if (chain_reads) out << "\tRC:i:" << (*chain_reads)[i];
+        if (depth) {
+            char dp[64];
+            std::snprintf(dp, sizeof(dp), "\tDP:f:%.2f", contigs[i].empty() ? 0.0 : (double)(*depth)[i] / (double)contigs[i].size());
+            out << dp;
+        }
         out << "\n";
     }
     for (const elba_link_t &r : links) {
@@ -792,6 +801,76 @@ inline void write_gfa(const std::string &gfa_fname, const std::vector<std::strin
     const std::string text = out.str();
     f.write(text.data(), (std::streamsize)text.size());
     if (!f) throw Error(ELBA_ERR_INVALID_ARG, "write_gfa: cannot write " + gfa_fname);
+}
+
+// place_reads(S) — elba_place_reads on the S, the contigs of the last GenerateContigs and the pairs S was built from (the rule is stated in
+// include/elba_amd.h): every read on its contig — chain reads where the contig stage put them, the others through their best passed pair
+// with a chain read — and per contig the runs of equal depth and the credits.  An export: nothing on the engine changes.
+struct Placements {
+    std::vector<elba_placement_t> reads;                        // one per read of the graph
+    std::vector<int64_t> seg_off;                               // [contigs + 1] into the two below
+    std::vector<int32_t> seg_start, seg_depth;
+    std::vector<int64_t> credited_reads, credited_bases;        // per contig
+};
+
+inline Placements place_reads(StringGraph &S, int skip_flags = 1, elba_place_stats *stats = nullptr)
+{
+    if (!S.engine) throw Error(ELBA_ERR_STATE, "place_reads: the string graph is not on a device");
+    elba_place_cfg cfg{};
+    cfg.skip_flags = skip_flags;
+    elba_placements_t o;
+    elba_place_stats st{};
+    S.engine->check(elba_place_reads(S.engine->ctx, &cfg, &o, &st));
+    Placements p;
+    try {
+        const int64_t nseg = o.seg_off[o.ncontigs];
+        p.reads.assign(o.reads, o.reads + o.nreads); p.seg_off.assign(o.seg_off, o.seg_off + o.ncontigs + 1);
+        p.seg_start.assign(o.seg_start, o.seg_start + nseg); p.seg_depth.assign(o.seg_depth, o.seg_depth + nseg);
+        p.credited_reads.assign(o.credited_reads, o.credited_reads + o.ncontigs); p.credited_bases.assign(o.credited_bases, o.credited_bases + o.ncontigs);
+    } catch (...) {
+        elba_free_placements(&o);
+        throw;
+    }
+    elba_free_placements(&o);
+    if (stats) *stats = st;
+    return p;
+}
+
+// write_placements_paf — byte for byte what formats.write_placements_paf writes: one line per placed read, by ascending read — name, length,
+// the credited interval in forward read coordinates, strand, `contig<i>`, its length, the target interval, the anchor pair's score, the
+// block length and 255.  On a path or single-read contig the target interval is [max(start, 0), min(start + len, L)), empty at the nearer
+// end for a read outside; on a circular contig min(len, L) bases from start mod L, the end of a wrapped read running past L (a reader that
+// wants tend <= tlen splits such a line at L).  kinds says which contigs are circular; without it none may be: a wrapped record throws.
+inline void write_placements_paf(const std::string &paf_fname, const Placements &pl, const std::vector<std::string> &names, const std::vector<int64_t> &lens,
+                                 const std::vector<int64_t> &contig_lens, const std::vector<uint8_t> *kinds = nullptr)
+{
+    if (pl.reads.size() != names.size() || names.size() != lens.size()) throw Error(ELBA_ERR_INVALID_ARG, "write_placements_paf: one record, one name and one length per read");
+    if (kinds && kinds->size() != contig_lens.size()) throw Error(ELBA_ERR_INVALID_ARG, "write_placements_paf: one kind per contig");
+    std::stringstream out;
+    for (size_t r = 0; r < pl.reads.size(); ++r) {
+        const elba_placement_t &p = pl.reads[r];
+        if (!p.kind) continue;
+        if (p.contig < 0 || (size_t)p.contig >= contig_lens.size()) throw Error(ELBA_ERR_INVALID_ARG, "write_placements_paf: a read names a contig that is not there");
+        if (!kinds && (p.flags & 4)) throw Error(ELBA_ERR_INVALID_ARG, "write_placements_paf: a wrapped read lies on a circular contig: give the contigs' kinds");
+        const int64_t start = p.start, l = lens[r], L = contig_lens[(size_t)p.contig];
+        int64_t tb, te, ob, oe;
+        if (kinds && (*kinds)[(size_t)p.contig] == 1) {
+            const int64_t cred = std::min(l, L);
+            tb = L > 0 ? ((start % L) + L) % L : 0;
+            te = tb + cred; ob = 0; oe = cred;
+        } else {
+            tb = std::min(std::max<int64_t>(start, 0), L);
+            te = std::max(tb, std::min(start + l, L));
+            ob = std::min(std::max<int64_t>(tb - start, 0), l); oe = std::min(std::max<int64_t>(te - start, 0), l);
+        }
+        const int64_t qb = p.strand ? l - oe : ob, qe = p.strand ? l - ob : oe;
+        out << names[r] << "\t" << l << "\t" << qb << "\t" << qe << "\t" << (p.strand ? "-" : "+") << "\tcontig" << p.contig << "\t" << L << "\t" << tb << "\t" << te << "\t"
+            << p.score << "\t" << te - tb << "\t255\n";
+    }
+    std::ofstream f(paf_fname, std::ios::binary);
+    const std::string text = out.str();
+    f.write(text.data(), (std::streamsize)text.size());
+    if (!f) throw Error(ELBA_ERR_INVALID_ARG, "write_placements_paf: cannot write " + paf_fname);
 }
 
 // ---- the reference's text outputs -------------------------------------------------------------------------------

@@ -433,6 +433,59 @@ typedef struct { int64_t segments, candidates, links, closures, twisted, unplace
 int  elba_export_assembly_links(elba_ctx *ctx, elba_links_t *out, elba_graph_stats *stats);   /* out->n = links + closures */
 void elba_free_links(elba_links_t *l);
 
+/* Read placements and contig depth: where every read lies on the assembly and how deep every contig base is covered — what a reads-to-contigs
+ * PAF (formats.write_placements_paf, hostcpp write_placements_paf) and a GFA depth tag (write_gfa's depth) are written from.
+ * elba_export_contigs places the chain reads only; this call also places, through ONE aligned pair each, the reads the graph lost on the way
+ * (contained reads, reads a cleaning call removed, branches, reads whose edges the reduction dropped).  It is an export: it needs a valid S
+ * and valid contigs of it, the reads the contig call needed and the pairs the graph was built from (the list of elba_set_overlaps /
+ * elba_prune_reads, else the context's own alignments), otherwise ELBA_ERR_STATE; it changes none of them, invalidates nothing — a valid
+ * pileup included — and keeps only scratch and the counts of its last call on the context.  Every value is an integer: the result is exact
+ * and does not depend on the order in which reads or pairs are visited.
+ *   oriented    a read of length l that lies on its contig with strand s has the forward interval [b, e) at the oriented interval [b, e)
+ *               when s = 0 and at [l - e, l - b) when s = 1.  ob(b, e) is the begin of that oriented interval.
+ *   chain read  element e of contig c holding read r with strand s: kind 1, contig c, start = the sum of the prefixes of the elements of c
+ *               before e, strand s, anchor r, score 0.
+ *   candidate   a pair a of the graph's input with passed != 0 between a read x that is in no contig, has none of cfg->skip_flags in its
+ *               flags of elba_export_read_flags and len(x) > 0, and a chain read y; x may be the pair's Q or its T.  Pairs between two chain
+ *               reads or between two reads off every chain are no candidates: a read is placed through a chain read, one level deep.
+ *   anchor      of the candidates of x the one with the largest max(score, 0), on a tie the one with the smallest index in the input list.
+ *   transform   through its anchor pair x gets kind 2, the contig of y, anchor y, score = the pair's score, strand(x) = strand(y) XOR rc and
+ *               start(x) = start(y) + ob_y - ob_x, ob taken of the pair's interval on that read with that read's length and strand
+ *               (begT / endT are on T's forward strand also under rc).  start is the contig position of base 0 of x in its contig
+ *               orientation: unclipped, not wrapped, it may be negative or beyond the contig.
+ *   credit      on a path or single-read contig of L bases a placed read of length l credits [max(start, 0), min(start + l, L)): flag bit 0
+ *               (clipped) when that differs from [start, start + l), bit 1 (outside) when it is empty — credited nothing, still reported.
+ *               On a circular contig it credits min(l, L) bases from start mod L (the mathematical modulo), clipped when l > L; when that
+ *               interval crosses L it is split in two at L and the read gets bit 2 (wrapped).  A circular contig of no bases: outside.
+ *   depth       per contig the maximal runs of equal depth of the credited intervals from 0 to its length, in the layout elba_pileup_t
+ *               has per read: seg_off[c] .. seg_off[c + 1], seg_start ascending from 0, seg_depth; a contig of no bases has no run.
+ *               credited_reads[c] = the reads that credited at least one base of c, credited_bases[c] = the sum of their credited lengths
+ *               = the sum over c's runs of length x depth.
+ *   the others  kind 0, contig -1, start 0, anchor = the read itself: a read off every chain with a skip bit is `skipped`; else one of
+ *               length 0 is `empty`; else one without a candidate is `unanchored`.  chain + anchored + unanchored + skipped + empty = nreads.
+ * Read ids (anchor) are those of chain_read.  Stats: candidates = the candidate pairs; clipped, outside and wrapped count placed reads;
+ * segments = seg_off[ncontigs]; max_depth; credited_bases = the sum over the contigs.  elba_get_stat "place_chain", "place_anchored",
+ * "place_unanchored", "place_skipped", "place_candidates", "place_clipped", "place_outside", "place_wrapped", "place_segments",
+ * "place_max_depth": the last call's, 0 while the graph or its contigs are not valid.
+ * Errors, after each of which nothing of this call is left valid (*out is zeroed): a null cfg, a non-zero reserved word or a skip_flags
+ * outside 0 .. 255 (the flags are one byte): ELBA_ERR_INVALID_ARG.  A candidate whose Q or T interval is outside [0, len] or has beg > end: ELBA_ERR_INVALID_ARG, the message names
+ * the smallest such pair (pairs that are no candidates are not looked at).  A contig of 2^31 bases or more, read ids or pairs beyond 32 bit,
+ * or 4 x nreads + ncontigs >= 2^32: ELBA_ERR_UNSUPPORTED.
+ * Cost: 52 bytes per pair read, one 64-bit atomicMax per candidate, 24 bytes per read written, 8 bytes per endpoint (two or four per
+ * crediting read) through the pileup's sort and segment passes, one host synchronisation for the output sizes. */
+typedef struct { int32_t skip_flags; int32_t reserved[3]; } elba_place_cfg;   /* reads with any of these bits of elba_export_read_flags are not anchored; 1 (bad reads) is Engine's default */
+typedef struct { int64_t start;            /* contig position of base 0 of the read in its contig orientation; unclipped, not wrapped, may be < 0 */
+                 int32_t contig;           /* -1: not placed */
+                 uint32_t anchor;          /* chain read it was placed through (its own id for a chain read) */
+                 int32_t score;            /* the anchor pair's score; 0 for chain reads */
+                 uint8_t strand, kind      /* 0 none, 1 chain, 2 anchored */, flags /* bit 0 clipped, 1 outside, 2 wrapped */, reserved; } elba_placement_t;
+typedef struct { int64_t nreads, ncontigs; elba_placement_t *reads;
+                 int64_t *seg_off; int32_t *seg_start, *seg_depth;   /* per contig: maximal runs of equal depth from 0 to its length, as elba_pileup_t has them per read */
+                 int64_t *credited_reads, *credited_bases; } elba_placements_t;
+typedef struct { int64_t nreads, chain, anchored, unanchored, skipped, empty, candidates, clipped, outside, wrapped, segments, max_depth, credited_bases; float ms_total; int32_t reserved; } elba_place_stats;
+int  elba_place_reads(elba_ctx *ctx, const elba_place_cfg *cfg, elba_placements_t *out, elba_place_stats *stats);
+void elba_free_placements(elba_placements_t *p);
+
 /* Tip clipping (not in the reference, whose GenerateContigs drops every read of degree > 2 with its edges: one stray read hanging off a good
  * path cuts it into three contigs and loses the branch read).  elba_clip_tips works on the S of elba_transitive_reduction, in place, between
  * that call and elba_generate_contigs*.  The rule is on degrees alone — no sequence, no suffix, no length in bases — and is stated on the
