@@ -146,6 +146,26 @@ PLACE_NONE, PLACE_CHAIN, PLACE_ANCHORED = 0, 1, 2      # elba_placement_t.kind
 PLACE_CLIPPED, PLACE_OUTSIDE, PLACE_WRAPPED = 1, 2, 4  # elba_placement_t.flags
 
 
+class PolishCfg(C.Structure):
+    _fields_ = [("skip_flags", C.c_int32), ("band", C.c_int32), ("max_diff_q16", C.c_int32), ("min_depth", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class Polished(C.Structure):
+    _fields_ = [("n", C.c_int64), ("seq_off", C.c_void_p), ("seq", C.c_void_p), ("voters", C.c_void_p), ("substituted", C.c_void_p), ("deleted", C.c_void_p),
+                ("inserted", C.c_void_p), ("nreads", C.c_int64), ("col_off", C.c_void_p), ("col", C.c_void_p), ("gap", C.c_void_p), ("reads", C.c_void_p)]
+
+
+class PolishStats(C.Structure):
+    _fields_ = [("nreads", C.c_int64), ("voted", C.c_int64), ("rejected", C.c_int64), ("outside", C.c_int64), ("low_depth_columns", C.c_int64), ("bases_before", C.c_int64),
+                ("bases_after", C.c_int64), ("sum_dist", C.c_int64), ("cells", C.c_int64), ("batches", C.c_int64), ("ms_total", C.c_float), ("ms_align", C.c_float)]
+
+
+# elba_polish_read_t: 16 bytes
+POLISH_READ_DTYPE = np.dtype([("dist", "<i4"), ("n", "<i4"), ("end_j", "<i4"), ("status", "<i4")])
+POLISH_EXPORT_VOTES = 1                                                          # elba_polish_cfg.flags
+POLISH_NOT_PLACED, POLISH_OUTSIDE, POLISH_REJECTED, POLISH_VOTED = 0, 1, 2, 3    # elba_polish_read_t.status
+
+
 class PileupCfg(C.Structure):
     _fields_ = [("mode", C.c_int32), ("margin", C.c_int32), ("min_depth", C.c_int32), ("min_run", C.c_int32), ("trim_len", C.c_int32), ("reserved", C.c_int32)]
 
@@ -280,6 +300,7 @@ EXPORTED_SYMBOLS = [
     "elba_set_reads_text", "elba_export_read_index",
     "elba_export_assembly_links", "elba_free_links",
     "elba_place_reads", "elba_free_placements",
+    "elba_polish_contigs", "elba_free_polished",
 ]
 
 _lib = None
@@ -346,6 +367,8 @@ def load_library():
     L.elba_free_links.restype = None; L.elba_free_links.argtypes = [C.POINTER(Links)]
     L.elba_place_reads.restype = i32; L.elba_place_reads.argtypes = [vp, C.POINTER(PlaceCfg), C.POINTER(Placements), C.POINTER(PlaceStats)]
     L.elba_free_placements.restype = None; L.elba_free_placements.argtypes = [C.POINTER(Placements)]
+    L.elba_polish_contigs.restype = i32; L.elba_polish_contigs.argtypes = [vp, C.POINTER(PolishCfg), C.POINTER(Polished), C.POINTER(PolishStats)]
+    L.elba_free_polished.restype = None; L.elba_free_polished.argtypes = [C.POINTER(Polished)]
     L.elba_read_pileup.restype = i32; L.elba_read_pileup.argtypes = [vp, C.POINTER(PileupCfg), C.POINTER(PileupStats)]
     L.elba_export_pileup.restype = i32; L.elba_export_pileup.argtypes = [vp, C.POINTER(Pileup)]
     L.elba_free_pileup.restype = None; L.elba_free_pileup.argtypes = [C.POINTER(Pileup)]
@@ -778,6 +801,34 @@ class Engine:
         out = _stats(st)
         del out["reserved"]
         return pl, out
+
+    def polish_contigs(self, skip_flags=1, band=64, max_diff=0.25, min_depth=3, votes=False, flags=None, reserved=(0, 0, 0), max_diff_q16=None):
+        """The contigs of the last generate_contigs with every column and gap voted on by the reads placed there (include/elba_amd.h states
+        the rule): place_reads' records under `skip_flags`, a banded edit-distance alignment of every placed read (band 64, 128 or 256
+        diagonals; a read with more than max_diff differences per base does not vote), columns with fewer than min_depth votes kept.
+        Returns ({seqs (list of str, the order of export_contigs), seq_off, voters, substituted, deleted, inserted (i64[ncontigs])}, stats
+        dict); with votes=True also col_off, col (u32[bases, 5]), gap (u32[bases + ncontigs, 4]: contig k's gap g at row col_off[k] + k + g)
+        and reads (POLISH_READ_DTYPE, one per read).  formats.write_contigs_fasta takes seqs as it takes export_contigs' ones."""
+        q16 = int(round(float(max_diff) * 65536)) if max_diff_q16 is None else int(max_diff_q16)
+        fl = (POLISH_EXPORT_VOTES if votes else 0) if flags is None else int(flags)
+        cfg = PolishCfg(int(skip_flags), int(band), q16, int(min_depth), fl, (C.c_int32 * 3)(*[int(x) for x in reserved]))
+        o, st = Polished(), PolishStats()
+        self._check(self.L.elba_polish_contigs(self.h, C.byref(cfg), C.byref(o), C.byref(st)))
+        try:
+            n = int(o.n)
+            seq_off = _copy(o.seq_off, n + 1, np.int64)
+            raw = _copy(o.seq, int(seq_off[-1]) if n else 0, np.uint8).tobytes()
+            out = dict(seqs=[raw[int(seq_off[i]):int(seq_off[i + 1])].decode("ascii") for i in range(n)], seq_off=seq_off if n else np.zeros(1, np.int64),
+                       voters=_copy(o.voters, n, np.int64), substituted=_copy(o.substituted, n, np.int64), deleted=_copy(o.deleted, n, np.int64),
+                       inserted=_copy(o.inserted, n, np.int64))
+            if fl & POLISH_EXPORT_VOTES:
+                col_off = _copy(o.col_off, n + 1, np.int64) if n else np.zeros(1, np.int64)
+                bases = int(col_off[-1])
+                out.update(col_off=col_off, col=_copy(o.col, 5 * bases, np.uint32).reshape(bases, 5), gap=_copy(o.gap, 4 * (bases + n), np.uint32).reshape(bases + n, 4),
+                           reads=_copy(o.reads, int(o.nreads), POLISH_READ_DTYPE))
+        finally:
+            self.L.elba_free_polished(C.byref(o))
+        return out, _stats(st)
 
     # --- read pileups and chimera flags (src/PruneChimeras.cpp; after align_seeds, before transitive_reduction) ---
     def read_pileup(self, mode=0, margin=0, min_depth=1, min_run=1, trim_len=2500):

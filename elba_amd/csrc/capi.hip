@@ -507,6 +507,25 @@ int elba_place_reads(elba_ctx *ctx, const elba_place_cfg *cfg, elba_placements_t
     return rc;
 }
 
+int elba_polish_contigs(elba_ctx *ctx, const elba_polish_cfg *cfg, elba_polished_t *out, elba_polish_stats *stats)
+{
+    if (out) memset(out, 0, sizeof(*out));                        // (before anything can fail: what is freed below is this call's)
+    const int rc = guarded(ctx, [&](Ctx &c) {
+        ELBA_REQUIRE(out, ELBA_ERR_INVALID_ARG, "polish_contigs: null output");
+        stage_polish_contigs(c, cfg, out);
+        if (stats) *stats = c.postats;
+    });
+    if (rc != ELBA_OK && ctx && out) elba_free_polished(out);      // (a copy that failed behind the allocations)
+    return rc;
+}
+
+void elba_free_polished(elba_polished_t *p)
+{
+    if (!p) return;
+    free(p->seq_off); free(p->seq); free(p->voters); free(p->substituted); free(p->deleted); free(p->inserted); free(p->col_off); free(p->col); free(p->gap); free(p->reads);
+    memset(p, 0, sizeof(*p));
+}
+
 void elba_free_placements(elba_placements_t *p)
 {
     if (!p) return;
@@ -797,6 +816,7 @@ int elba_set_option(elba_ctx *ctx, const char *name, int64_t value)
         else if (!strcmp(name, "aln_tiers")) { ELBA_REQUIRE(value >= 0, ELBA_ERR_INVALID_ARG, "set_option: aln_tiers is a string of the digits 1, 2, 4, 8"); c.opt.aln_tiers = value; }
         else if (!strcmp(name, "aln_wide_hint")) c.opt.aln_wide_hint = (int)value;
         else if (!strcmp(name, "aln_long_hint")) c.opt.aln_long_hint = (int)value;
+        else if (!strcmp(name, "polish_trace_bytes")) { ELBA_REQUIRE(value >= 0, ELBA_ERR_INVALID_ARG, "set_option: polish_trace_bytes is >= 0"); c.opt.polish_trace_bytes = value; }
         else throw Error{ELBA_ERR_INVALID_ARG, std::string("set_option: unknown option ") + name};
     });
 }
@@ -814,6 +834,8 @@ int elba_release_workspace(elba_ctx *ctx)
         c.pl_cstart.release(); c.pl_cstrand.release(); c.pl_best.release(); c.pl_rec.release(); c.pl_clen.release(); c.pl_cred.release(); c.pl_ctr.release();    // placement scratch
         c.pl_k0.release(); c.pl_k1.release(); c.pl_eptr.release(); c.pl_head.release(); c.pl_hidx.release(); c.pl_delta.release(); c.pl_dsum.release(); c.pl_gstart.release();
         c.pl_tok.release(); c.pl_tpos.release(); c.pl_seg_off.release(); c.pl_seg_start.release(); c.pl_seg_depth.release();
+        c.po_plan.release(); c.po_rec.release(); c.po_toff.release(); c.po_trace.release(); c.po_col.release(); c.po_gap.release(); c.po_cnt.release();         // polishing scratch
+        c.po_emit.release(); c.po_off.release(); c.po_cstat.release(); c.po_seq.release(); c.po_seqoff.release(); c.po_ctr.release();
         for (int b = 0; b < 2; ++b) { c.cg_far[b].release(); c.cg_rank[b].release(); c.cg_mn[b].release(); c.cg_cfar[b].release(); c.cg_crank[b].release(); }
         c.pu_k0.release(); c.pu_k1.release(); c.pu_eptr.release(); c.pu_head.release(); c.pu_hidx.release(); c.pu_delta.release();   // pileup scratch (the results stay)
         c.pu_dsum.release(); c.pu_gstart.release(); c.pu_tok.release(); c.pu_tpos.release(); c.pu_sel.release(); c.pu_rows.release(); c.pu_cols.release(); c.pu_vals.release();
@@ -894,6 +916,18 @@ int elba_get_stat(elba_ctx *ctx, const char *name, int64_t *value)
             else if (!strcmp(f, "skipped")) x = g.skipped; else if (!strcmp(f, "candidates")) x = g.candidates; else if (!strcmp(f, "clipped")) x = g.clipped;
             else if (!strcmp(f, "outside")) x = g.outside; else if (!strcmp(f, "wrapped")) x = g.wrapped; else if (!strcmp(f, "segments")) x = g.segments;
             else if (!strcmp(f, "max_depth")) x = g.max_depth;
+            else throw Error{ELBA_ERR_INVALID_ARG, std::string("get_stat: unknown counter ") + name};
+            *value = ok ? x : 0;
+        }
+        else if (!strncmp(name, "polish_", 7)) {                   // the last elba_polish_contigs on the contigs that are valid now
+            const bool ok = has(c.v, P_S, P_CONTIGS) && c.po_for == c.cg_serial && c.po_for != 0;
+            const elba_polish_stats &g = c.postats;
+            const char *f = name + 7;
+            int64_t x;
+            if (!strcmp(f, "voted")) x = g.voted; else if (!strcmp(f, "rejected")) x = g.rejected; else if (!strcmp(f, "outside")) x = g.outside;
+            else if (!strcmp(f, "low_depth_columns")) x = g.low_depth_columns; else if (!strcmp(f, "bases_before")) x = g.bases_before;
+            else if (!strcmp(f, "bases_after")) x = g.bases_after; else if (!strcmp(f, "sum_dist")) x = g.sum_dist; else if (!strcmp(f, "cells")) x = g.cells;
+            else if (!strcmp(f, "batches")) x = g.batches;
             else throw Error{ELBA_ERR_INVALID_ARG, std::string("get_stat: unknown counter ") + name};
             *value = ok ? x : 0;
         }

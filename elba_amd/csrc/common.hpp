@@ -187,6 +187,7 @@ struct Options {
     int dk = -1;                // SpGEMM: gather trips per iteration of the padded-column loop: 0 = one, 1 = two, 2 = four, 4 = eight; -1 = chosen per matrix (spgemm.hip)
     int64_t aln_tiers = 0;      // x-drop register tiers as decimal digits (1248 = all), 0 = default
     int aln_wide_hint = 6, aln_long_hint = 6000;
+    int64_t polish_trace_bytes = 0;      // elba_polish_contigs: the choices of one batch of voters take at most this many bytes (0: an eighth of the free device memory, at least 64 MiB); tests force batches on small sets
 };
 
 // ---- context ----------------------------------------------------------------------------------------------------
@@ -346,6 +347,14 @@ struct Ctx {
     elba_place_stats plstats{};
     uint64_t pl_for = 0;
 
+    // contig polishing (polish.hip): all scratch — per read its slice (rows, first column, first base) and record, the row offsets of the
+    // choices, the choices of one batch, the votes (5 per column, 4 per gap), what every column emits and its scan, the per-contig counts,
+    // the polished bases.  po_for: the contig call (cg_serial) the counts in postats belong to
+    DevBuf po_plan, po_rec, po_toff, po_trace, po_col, po_gap, po_cnt, po_emit, po_off, po_cstat, po_seq, po_seqoff, po_ctr;
+    EventTimer po_t_total, po_t_align;
+    elba_polish_stats postats{};
+    uint64_t po_for = 0;
+
     // trimmed reads (trim.hip): a snapshot in buffers of its own — packed / off / len in DnaBuffer layout, the map (src, beg, end); it survives
     // elba_prune_reads and elba_release_workspace, a new read set or a new pileup invalidates it, elba_adopt_trimmed_reads consumes it
     int64_t tm_n = 0, tm_packed_bytes = 0;
@@ -464,6 +473,16 @@ struct DepthBufs { DevBuf &k0, &k1, &eptr, &head, &hidx, &delta, &dsum, &gstart,
 void depth_reserve(const DepthBufs &b, int64_t max_keys, int64_t G);
 const uint64_t *depth_segments(Ctx &c, const DepthBufs &b, int64_t E, int64_t M, int mb, int pb, const uint32_t *len, unsigned long long *ctr);
 
+// elba_place_reads up to and including its records (place.hip), for the two stages that need them: the state and size checks (messages
+// begin with `who`), the reservations, chain starts, the candidates' winners and k_pl_place — queued on the context's stream, not
+// synchronised.  ctr: the PLACE_CTR_WORDS counters of place.hip; word PLACE_CTR_BAD holds the smallest candidate with a bad interval (all
+// ones: none), which the caller reads behind its own synchronisation and hands to place_throw_bad_pair.  depth_bufs: also reserve what
+// depth_segments needs.  t, when given, is started in front of the first launch.
+constexpr int PLACE_CTR_BAD = 2, PLACE_CTR_WORDS = 16;
+struct PlaceWork { GraphInput in; ReadSource src; int64_t M, base, E, nc; elba_placement_t *rec; unsigned long long *ctr; const uint32_t *clen; };
+PlaceWork place_records(Ctx &c, int skip_flags, const char *who, bool depth_bufs, EventTimer *t);
+[[noreturn]] void place_throw_bad_pair(Ctx &c, const PlaceWork &w, int64_t a, const char *who);
+
 // ---- stages -----------------------------------------------------------------------------------------------------
 void stage_set_reads_fasta(Ctx &c, const char *chunk, int64_t chunk_bytes, uint64_t chunk_file_offset, const elba_fasta_record_t *recs, int64_t nreads,
                            int64_t first_global_id, elba_ingest_stats *stats);      // ingest.hip
@@ -494,6 +513,7 @@ void stage_generate_contigs(Ctx &c, int flags);                                 
 void stage_generate_contigs_ex(Ctx &c, const elba_contig_cfg *cfg);                      // contig.hip
 void stage_export_assembly_links(Ctx &c, elba_links_t *out);                             // graph_links.hip (out->links: malloc)
 void stage_place_reads(Ctx &c, const elba_place_cfg *cfg, elba_placements_t *out);        // place.hip (out's arrays: malloc)
+void stage_polish_contigs(Ctx &c, const elba_polish_cfg *cfg, elba_polished_t *out);       // polish.hip (out's arrays: malloc)
 void stage_read_pileup(Ctx &c, const elba_pileup_cfg *cfg);                   // pileup.hip
 void stage_prune_reads(Ctx &c, int mask, int64_t *kept);
 void stage_trim_reads(Ctx &c, const elba_trim_cfg *cfg);                      // trim.hip

@@ -6,6 +6,8 @@
 // cg_coff and the kinds; the read flags of the reduction and the cleaning calls (tr_flags); the read lengths; and the pairs the graph was
 // built from (graph_input: the loaded edge list, else the context's alignments), which the reduction read and left as they were.
 //
+// The launches up to and including k_pl_place are place_records(), which elba_polish_contigs (polish.hip) calls for the same records.
+//
 //   k_pl_chain       one lane per chain element: start (its base offset minus its contig's) and strand of its read; one lane per contig:
 //                    its length as u32 (the `len` of the segment passes)
 //   k_pl_candidates  one lane per pair: passed, exactly one of its reads on a chain, the other without a skip bit and not empty -> a
@@ -224,39 +226,36 @@ T *pl_host(size_t n)
 
 }  // namespace
 
-void stage_place_reads(Ctx &c, const elba_place_cfg *cfg, elba_placements_t *out)
+static_assert(PC_BAD == PLACE_CTR_BAD && PC_N == PLACE_CTR_WORDS, "common.hpp names the counters of place_records");
+
+PlaceWork place_records(Ctx &c, int skip_flags, const char *who_, bool depth_bufs, EventTimer *t)
 {
-    c.pl_for = 0;                                               // (whatever this call ends in, the counts of the one before are gone)
-    ELBA_REQUIRE(cfg, ELBA_ERR_INVALID_ARG, "place_reads: null cfg");
-    ELBA_REQUIRE(!cfg->reserved[0] && !cfg->reserved[1] && !cfg->reserved[2], ELBA_ERR_INVALID_ARG, "place_reads: reserved words must be 0");
-    ELBA_REQUIRE(cfg->skip_flags >= 0 && cfg->skip_flags <= 255, ELBA_ERR_INVALID_ARG, "place_reads: skip_flags must fit in one byte");
-    ELBA_REQUIRE(has(c.v, P_S, P_CONTIGS), ELBA_ERR_STATE, "place_reads: no contigs of the current string graph (call elba_generate_contigs)");
-    const GraphInput in = graph_input(c, "place_reads");
+    const std::string who(who_);
+    ELBA_REQUIRE(has(c.v, P_S, P_CONTIGS), ELBA_ERR_STATE, who + ": no contigs of the current string graph (call elba_generate_contigs)");
+    const GraphInput in = graph_input(c, who_);
     const int64_t M = c.tr_M, base = c.tr_id_base, E = c.cg_E, nc = c.cg_n, n = in.n;
-    ELBA_REQUIRE(in.M == M && in.id_base == base, ELBA_ERR_STATE, "place_reads: the pairs on this context are not the ones the string graph was built from");
-    const ReadSource src = read_source(c, M, "place_reads", "lengths of the graph's # reads", base == 0);
-    ELBA_REQUIRE(M + base < 0xFFFFFFFFll && n < 0xFFFFFFFFll, ELBA_ERR_UNSUPPORTED, "place_reads: read ids or pairs beyond 32 bit");
-    ELBA_REQUIRE(c.cstats.longest < (1ll << 31), ELBA_ERR_UNSUPPORTED, "place_reads: a contig of 2^31 bases or more");
-    ELBA_REQUIRE(4 * M + nc < 0xfffffff0ll, ELBA_ERR_UNSUPPORTED, "place_reads: 4 x reads + contigs reach 2^32");
+    ELBA_REQUIRE(in.M == M && in.id_base == base, ELBA_ERR_STATE, who + ": the pairs on this context are not the ones the string graph was built from");
+    const ReadSource src = read_source(c, M, who_, "lengths of the graph's # reads", base == 0);
+    ELBA_REQUIRE(M + base < 0xFFFFFFFFll && n < 0xFFFFFFFFll, ELBA_ERR_UNSUPPORTED, who + ": read ids or pairs beyond 32 bit");
+    ELBA_REQUIRE(c.cstats.longest < (1ll << 31), ELBA_ERR_UNSUPPORTED, who + ": a contig of 2^31 bases or more");
+    ELBA_REQUIRE(4 * M + nc < 0xfffffff0ll, ELBA_ERR_UNSUPPORTED, who + ": 4 x reads + contigs reach 2^32");
     hipStream_t s = c.stream;
-    int mb = 1, pb = 1;
-    while ((1ll << mb) < nc + 1) ++mb;
-    while ((1ll << pb) < c.cstats.longest + 1) ++pb;            // positions 0 .. length
-    const DepthBufs db{c.pl_k0, c.pl_k1, c.pl_eptr, c.pl_head, c.pl_hidx, c.pl_delta, c.pl_dsum, c.pl_gstart, c.pl_tok, c.pl_tpos, c.pl_seg_off, c.pl_seg_start, c.pl_seg_depth};
-    depth_reserve(db, 4 * M, nc);                               // at most two intervals of two endpoints per read
+    if (depth_bufs) {
+        const DepthBufs db{c.pl_k0, c.pl_k1, c.pl_eptr, c.pl_head, c.pl_hidx, c.pl_delta, c.pl_dsum, c.pl_gstart, c.pl_tok, c.pl_tpos, c.pl_seg_off, c.pl_seg_start, c.pl_seg_depth};
+        depth_reserve(db, 4 * M, nc);                           // at most two intervals of two endpoints per read
+    }
     c.pl_cstart.reserve((size_t)(M + 1) * 8); c.pl_cstrand.reserve((size_t)M + 4); c.pl_best.reserve((size_t)(M + 1) * 8);
     c.pl_rec.reserve((size_t)(M + 1) * sizeof(elba_placement_t)); c.pl_clen.reserve((size_t)(nc + 1) * 4); c.pl_cred.reserve((size_t)(2 * nc + 2) * 8);
     c.pl_ctr.reserve(PC_N * 8);
     unsigned long long *ctr = c.pl_ctr.as<unsigned long long>(), *best = c.pl_best.as<unsigned long long>();
-    unsigned long long *cred_reads = c.pl_cred.as<unsigned long long>(), *cred_bases = cred_reads + nc;
     elba_placement_t *rec = c.pl_rec.as<elba_placement_t>();
     PlIn g{in.rows, in.cols, in.vals, n, c.cg_cid.as<int32_t>(), c.tr_flags.as<uint8_t>(), src.len, c.pl_cstart.as<int64_t>(), c.pl_cstrand.as<uint8_t>(),
-           c.pl_clen.as<uint32_t>(), c.cg_kind.as<uint8_t>(), (uint32_t)M, (uint32_t)base, cfg->skip_flags};
-    c.pl_t_total.start(s);
+           c.pl_clen.as<uint32_t>(), c.cg_kind.as<uint8_t>(), (uint32_t)M, (uint32_t)base, skip_flags};
+    if (t) t->start(s);
     ELBA_HIP(hipMemsetAsync(ctr, 0, PC_N * 8, s));
     ELBA_HIP(hipMemsetAsync(ctr + PC_BAD, 0xff, 8, s));
     ELBA_HIP(hipMemsetAsync(best, 0, (size_t)(M + 1) * 8, s));
-    ELBA_HIP(hipMemsetAsync(cred_reads, 0, (size_t)(2 * nc + 2) * 8, s));
+    ELBA_HIP(hipMemsetAsync(c.pl_cred.p, 0, (size_t)(2 * nc + 2) * 8, s));
     const int64_t nce = E > nc ? E : nc;
     if (nce > 0)
         hipLaunchKernelGGL(k_pl_chain, dim3((unsigned)((nce + 255) / 256)), dim3(256), 0, s, c.cg_eread.as<int64_t>(), c.cg_estr.as<uint8_t>(), c.cg_eboff.as<int64_t>(),
@@ -266,26 +265,47 @@ void stage_place_reads(Ctx &c, const elba_place_cfg *cfg, elba_placements_t *out
         if (grid > (int64_t)c.num_cus * 16) grid = (int64_t)c.num_cus * 16;
         hipLaunchKernelGGL(k_pl_candidates, dim3((unsigned)grid), dim3(256), 0, s, g, best, ctr);
     }
-    if (M > 0) {
-        const unsigned nbM = (unsigned)((M + 255) / 256);
-        hipLaunchKernelGGL(k_pl_place, dim3(nbM), dim3(256), 0, s, g, (const unsigned long long *)best, rec, ctr);
-        hipLaunchKernelGGL(k_pl_emit, dim3(nbM), dim3(256), 0, s, (const elba_placement_t *)rec, src.len, c.pl_clen.as<uint32_t>(), c.cg_kind.as<uint8_t>(), (uint32_t)M, pb,
+    if (M > 0) hipLaunchKernelGGL(k_pl_place, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, g, (const unsigned long long *)best, rec, ctr);
+    return PlaceWork{in, src, M, base, E, nc, rec, ctr, c.pl_clen.as<uint32_t>()};
+}
+
+void place_throw_bad_pair(Ctx &c, const PlaceWork &w, int64_t a, const char *who)
+{
+    hipStream_t s = c.stream;
+    int64_t r = 0, col = 0; elba_overlap_t o{};
+    ELBA_HIP(hipMemcpyAsync(&r, w.in.rows + a, 8, hipMemcpyDeviceToHost, s));
+    ELBA_HIP(hipMemcpyAsync(&col, w.in.cols + a, 8, hipMemcpyDeviceToHost, s));
+    ELBA_HIP(hipMemcpyAsync(&o, w.in.vals + a, sizeof(o), hipMemcpyDeviceToHost, s));
+    ELBA_HIP(hipStreamSynchronize(s));
+    throw Error{ELBA_ERR_INVALID_ARG, std::string(who) + ": pair " + std::to_string(a) + " (" + std::to_string(r) + ", " + std::to_string(col) + ") has an interval outside [0, len] or with beg > end: Q [" +
+                                          std::to_string(o.begQ) + ", " + std::to_string(o.endQ) + "), T [" + std::to_string(o.begT) + ", " + std::to_string(o.endT) + ")"};
+}
+
+void stage_place_reads(Ctx &c, const elba_place_cfg *cfg, elba_placements_t *out)
+{
+    c.pl_for = 0;                                               // (whatever this call ends in, the counts of the one before are gone)
+    ELBA_REQUIRE(cfg, ELBA_ERR_INVALID_ARG, "place_reads: null cfg");
+    ELBA_REQUIRE(!cfg->reserved[0] && !cfg->reserved[1] && !cfg->reserved[2], ELBA_ERR_INVALID_ARG, "place_reads: reserved words must be 0");
+    ELBA_REQUIRE(cfg->skip_flags >= 0 && cfg->skip_flags <= 255, ELBA_ERR_INVALID_ARG, "place_reads: skip_flags must fit in one byte");
+    const PlaceWork w = place_records(c, cfg->skip_flags, "place_reads", true, &c.pl_t_total);
+    const ReadSource &src = w.src;
+    const int64_t M = w.M, nc = w.nc;
+    hipStream_t s = c.stream;
+    int mb = 1, pb = 1;
+    while ((1ll << mb) < nc + 1) ++mb;
+    while ((1ll << pb) < c.cstats.longest + 1) ++pb;            // positions 0 .. length
+    const DepthBufs db{c.pl_k0, c.pl_k1, c.pl_eptr, c.pl_head, c.pl_hidx, c.pl_delta, c.pl_dsum, c.pl_gstart, c.pl_tok, c.pl_tpos, c.pl_seg_off, c.pl_seg_start, c.pl_seg_depth};
+    unsigned long long *ctr = w.ctr;
+    unsigned long long *cred_reads = c.pl_cred.as<unsigned long long>(), *cred_bases = cred_reads + nc;
+    elba_placement_t *rec = w.rec;
+    if (M > 0)
+        hipLaunchKernelGGL(k_pl_emit, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, (const elba_placement_t *)rec, src.len, c.pl_clen.as<uint32_t>(), c.cg_kind.as<uint8_t>(), (uint32_t)M, pb,
                            c.pl_k0.as<uint64_t>(), cred_reads, ctr);
-    }
     ELBA_HIP(hipGetLastError());
     unsigned long long h[PC_N] = {0};
     ELBA_HIP(hipMemcpyAsync(h, ctr, PC_N * 8, hipMemcpyDeviceToHost, s));
     ELBA_HIP(hipStreamSynchronize(s));
-    if (h[PC_BAD] != ~0ull) {
-        const int64_t a = (int64_t)h[PC_BAD];
-        int64_t r = 0, col = 0; elba_overlap_t o{};
-        ELBA_HIP(hipMemcpyAsync(&r, in.rows + a, 8, hipMemcpyDeviceToHost, s));
-        ELBA_HIP(hipMemcpyAsync(&col, in.cols + a, 8, hipMemcpyDeviceToHost, s));
-        ELBA_HIP(hipMemcpyAsync(&o, in.vals + a, sizeof(o), hipMemcpyDeviceToHost, s));
-        ELBA_HIP(hipStreamSynchronize(s));
-        throw Error{ELBA_ERR_INVALID_ARG, "place_reads: pair " + std::to_string(a) + " (" + std::to_string(r) + ", " + std::to_string(col) + ") has an interval outside [0, len] or with beg > end: Q [" +
-                                              std::to_string(o.begQ) + ", " + std::to_string(o.endQ) + "), T [" + std::to_string(o.begT) + ", " + std::to_string(o.endT) + ")"};
-    }
+    if (h[PC_BAD] != ~0ull) place_throw_bad_pair(c, w, (int64_t)h[PC_BAD], "place_reads");
     const int64_t K = 2 * (int64_t)h[PC_INT];                   // endpoints
     ELBA_REQUIRE(K <= 4 * M, ELBA_ERR_INTERNAL, "place_reads: more endpoints than four per read");
     const uint64_t *keys = depth_segments(c, db, K, nc, mb, pb, c.pl_clen.as<uint32_t>(), ctr);

@@ -836,6 +836,45 @@ inline Placements place_reads(StringGraph &S, int skip_flags = 1, elba_place_sta
     return p;
 }
 
+// polish_contigs(S) — elba_polish_contigs on the S, the contigs of the last GenerateContigs, the reads and the pairs S was built from (the
+// rule is stated in include/elba_amd.h): every placed read aligned to its stretch of its contig in a band, the alignments voting per column
+// and gap, the contigs the votes call.  An export: nothing on the engine changes.  votes: also the counts per column and gap and the
+// per-read records.  The polished contigs are written like the others (write_contigs_fasta, write_gfa).
+struct Polished {
+    std::vector<std::string> contigs;                           // the order of GenerateContigs
+    std::vector<int64_t> voters, substituted, deleted, inserted;      // per contig
+    std::vector<int64_t> col_off;                               // votes only: [contigs + 1], the offsets of the unpolished contigs
+    std::vector<uint32_t> col, gap;                             // 5 per column; 4 per gap, contig k's gap g at 4 * (col_off[k] + k + g)
+    std::vector<elba_polish_read_t> reads;                      // one per read of the graph
+};
+
+inline Polished polish_contigs(StringGraph &S, int skip_flags = 1, int band = 64, double max_diff = 0.25, int min_depth = 3, bool votes = false, elba_polish_stats *stats = nullptr)
+{
+    if (!S.engine) throw Error(ELBA_ERR_STATE, "polish_contigs: the string graph is not on a device");
+    elba_polish_cfg cfg{};
+    cfg.skip_flags = skip_flags; cfg.band = band; cfg.max_diff_q16 = (int32_t)(max_diff * 65536.0 + 0.5); cfg.min_depth = min_depth; cfg.flags = votes ? ELBA_POLISH_EXPORT_VOTES : 0;
+    elba_polished_t o;
+    elba_polish_stats st{};
+    S.engine->check(elba_polish_contigs(S.engine->ctx, &cfg, &o, &st));
+    Polished p;
+    try {
+        for (int64_t i = 0; i < o.n; ++i) p.contigs.emplace_back(o.seq + o.seq_off[i], (size_t)(o.seq_off[i + 1] - o.seq_off[i]));
+        p.voters.assign(o.voters, o.voters + o.n); p.substituted.assign(o.substituted, o.substituted + o.n);
+        p.deleted.assign(o.deleted, o.deleted + o.n); p.inserted.assign(o.inserted, o.inserted + o.n);
+        if (votes) {
+            const int64_t bases = o.col_off[o.n];
+            p.col_off.assign(o.col_off, o.col_off + o.n + 1); p.col.assign(o.col, o.col + 5 * bases); p.gap.assign(o.gap, o.gap + 4 * (bases + o.n));
+            p.reads.assign(o.reads, o.reads + o.nreads);
+        }
+    } catch (...) {
+        elba_free_polished(&o);
+        throw;
+    }
+    elba_free_polished(&o);
+    if (stats) *stats = st;
+    return p;
+}
+
 // write_placements_paf — byte for byte what formats.write_placements_paf writes: one line per placed read, by ascending read — name, length,
 // the credited interval in forward read coordinates, strand, `contig<i>`, its length, the target interval, the anchor pair's score, the
 // block length and 255.  On a path or single-read contig the target interval is [max(start, 0), min(start + len, L)), empty at the nearer

@@ -486,6 +486,73 @@ typedef struct { int64_t nreads, chain, anchored, unanchored, skipped, empty, ca
 int  elba_place_reads(elba_ctx *ctx, const elba_place_cfg *cfg, elba_placements_t *out, elba_place_stats *stats);
 void elba_free_placements(elba_placements_t *p);
 
+/* Contig polishing (not in the reference, which has no consensus step): elba_generate_contigs writes a contig as prefixes of single reads,
+ * so every error of a chain read stands in the contig at depth 1 while elba_place_reads puts many other reads on the same bases.  This call
+ * aligns every placed read to its stretch of the contig in a band around its placement, lets the alignments vote per contig column and per
+ * gap between two columns, and writes the contigs the votes call.  It is an export like elba_place_reads: it needs a valid S, valid contigs
+ * of it, the reads and the pairs the graph was built from, otherwise ELBA_ERR_STATE; it changes and invalidates nothing on the context — a
+ * valid pileup and the contigs themselves stay as they are — and keeps only scratch and the counts of its last call.  Every value is an
+ * integer and every sum is commutative: the result does not depend on the order in which reads, rows or votes are visited.
+ *   placement   the records of elba_place_reads under cfg->skip_flags.  The voters are the reads of kind 1 (chain) and kind 2 (anchored)
+ *               without flag bit 1 (outside).
+ *   slice       r = the voter in contig orientation (its reverse complement when strand = 1), l its length, start its record's start; L the
+ *               length of its contig and s the contig's bases.  On a path or single-read contig i0 = max(0, -start), i1 = min(l, L - start);
+ *               on a circular contig i0 = 0, i1 = min(l, L).  n = i1 - i0 (>= 1 for a voter), st = start + i0, q = r[i0 .. i1): q[0] is
+ *               expected at column st.  A circular contig is used in unrolled coordinates: column j means s[j mod L] with the mathematical
+ *               modulo, st may be negative, gaps and columns are reduced mod L only where votes are added.
+ *   band        W = cfg->band.  Cell (i, j) exists when 0 <= i <= n and 0 <= j - i - st + W/2 < W, and, on a contig that is not circular,
+ *               0 <= j <= L.  D of a cell that does not exist is infinite, and infinity + 1 = infinity.
+ *   distance    D[0][j] = 0 (the begin on the contig is free).  For i >= 1, D[i][j] = the minimum of
+ *                   D[i-1][j-1] + (q[i-1] != s[j-1])      diagonal
+ *                   D[i-1][j] + 1                         up: the read base q[i-1] is inserted in front of column j
+ *                   D[i][j-1] + 1                         left: the contig base s[j-1] is deleted
+ *               and the cell's choice is the first of diagonal, up, left whose term equals that minimum.  The end cell is the (n, j) with the
+ *               smallest D, of several the one with the smallest j (cell (n, st + n) of the main diagonal is finite, so one exists); dist =
+ *               its D, end_j its j.  The read is rejected when dist > (cfg->max_diff_q16 * n) >> 16; a rejected read votes nothing.
+ *   votes       from the end cell follow the choices until row 0 is reached.  A diagonal step at (i, j) adds 1 to col[j-1][q[i-1]] and goes
+ *               to (i-1, j-1); a left step adds 1 to col[j-1][4], the deletion count, and goes to (i, j-1); an up step goes to (i-1, j).  A
+ *               maximal run of up steps at one j adds 1 to gap[j][b], b = the base of the run's LAST step, the first in read order: only
+ *               one base of an insertion is restored.  Bases are 0 A, 1 C, 2 G, 3 T.  On a circular contig column j-1 and gap j are taken
+ *               mod L; a path or single-read contig has the gaps 0 .. L, gap g lying in front of column g.
+ *   calls       depth[c] = col[c][0] + .. + col[c][4].  A column with depth[c] < cfg->min_depth keeps its base (a low-depth column).  Any
+ *               other column takes the largest of its five counts; equal counts are preferred in the order the contig's own base, A, C, G,
+ *               T, deletion; a winning deletion emits nothing (deleted), a winning base other than the contig's own is substituted.  Gap g
+ *               emits one base (inserted), the b with the largest gap[g][b], of equal ones the smallest b, when 2 * (gap[g][0] + .. +
+ *               gap[g][3]) > span(g); span(g) = min(depth[g-1], depth[g]), on a circular contig with g - 1 taken mod L, on the others
+ *               span(0) = depth[0] and span(L) = depth[L-1].  The polished contig: for c = 0 .. L-1 the base of gap c, if any, then the
+ *               base of column c, if any; then, where the contig is not circular, the base of gap L.  A contig of no bases stays empty.
+ * Output: n contigs in the order of elba_export_contigs, seq_off[n + 1] and seq (ASCII, seq_off[n] bytes); per contig voters (the reads
+ * that voted), substituted, deleted, inserted.  With ELBA_POLISH_EXPORT_VOTES in cfg->flags also col_off[n + 1] (the offsets of the
+ * UNPOLISHED contigs), col (5 counts per column: contig k's column c at 5 * (col_off[k] + c)), gap (4 counts per gap, every contig having
+ * L + 1 slots: contig k's gap g at 4 * (col_off[k] + k + g); slot L of a circular contig stays 0) and one record per read, nreads of them:
+ * {dist, n, end_j, status}, status one of ELBA_POLISH_NOT_PLACED (kind 0), _OUTSIDE, _REJECTED, _VOTED; dist and end_j are 0 unless the read
+ * was aligned (rejected or voted), n is 0 unless it is a voter.  Without the flag these pointers are null.
+ * Stats: nreads; voted + rejected = the voters, outside; low_depth_columns; bases_before / bases_after = the sum of the contig lengths
+ * before and after; sum_dist over the reads that voted; cells = the sum of n * W over the voters; batches (below).  elba_get_stat
+ * "polish_voted", "polish_rejected", "polish_outside", "polish_low_depth_columns", "polish_bases_before", "polish_bases_after",
+ * "polish_sum_dist", "polish_cells", "polish_batches": the last call's, 0 while the graph or its contigs are not valid.
+ * The choices of a voter take n * W / 4 bytes until its votes are cast, so the voters are aligned in batches of consecutive reads whose
+ * choices fit elba_set_option "polish_trace_bytes" (0, the default: an eighth of the free device memory, at least 64 MiB); a read that alone
+ * exceeds it is a batch of its own.  Votes are integer sums: batches do not change the result.
+ * Errors, after each of which nothing of this call is left valid (*out is zeroed): a null cfg, a band other than 64, 128 or 256, a
+ * max_diff_q16 outside 0 .. 65536, min_depth < 1, flags other than ELBA_POLISH_EXPORT_VOTES, a non-zero reserved word or a skip_flags
+ * outside 0 .. 255: ELBA_ERR_INVALID_ARG, as is a candidate pair with a bad interval (elba_place_reads).  What elba_place_reads does not
+ * support, a contig of 2^30 bases or more, a placed read of 2^24 bases or more, or 5 x the contig bases + 4 x the contigs at 2^32 or more: ELBA_ERR_UNSUPPORTED.
+ * Cost: elba_place_reads' pair pass; per voter n rows of W cells in registers (one wavefront per read, no memory but W / 4 bytes of
+ * choices per row written and read once, and 2 bits per read base); one integer atomic per vote; 36 bytes per contig column for the calls,
+ * two host synchronisations (the batch plan and the output size). */
+enum { ELBA_POLISH_EXPORT_VOTES = 1 };                                                /* elba_polish_cfg.flags */
+enum { ELBA_POLISH_NOT_PLACED = 0, ELBA_POLISH_OUTSIDE = 1, ELBA_POLISH_REJECTED = 2, ELBA_POLISH_VOTED = 3 };   /* elba_polish_read_t.status */
+typedef struct { int32_t skip_flags, band, max_diff_q16, min_depth, flags; int32_t reserved[3]; } elba_polish_cfg;   /* Engine's defaults: 1, 64, 16384 (0.25), 3, 0 */
+typedef struct { int32_t dist, n, end_j, status; } elba_polish_read_t;
+typedef struct { int64_t n; int64_t *seq_off; char *seq;
+                 int64_t *voters, *substituted, *deleted, *inserted;
+                 int64_t nreads; int64_t *col_off; uint32_t *col, *gap; elba_polish_read_t *reads; } elba_polished_t;
+typedef struct { int64_t nreads, voted, rejected, outside, low_depth_columns, bases_before, bases_after, sum_dist, cells, batches;
+                 float ms_total, ms_align; } elba_polish_stats;
+int  elba_polish_contigs(elba_ctx *ctx, const elba_polish_cfg *cfg, elba_polished_t *out, elba_polish_stats *stats);
+void elba_free_polished(elba_polished_t *p);
+
 /* Tip clipping (not in the reference, whose GenerateContigs drops every read of degree > 2 with its edges: one stray read hanging off a good
  * path cuts it into three contigs and loses the branch read).  elba_clip_tips works on the S of elba_transitive_reduction, in place, between
  * that call and elba_generate_contigs*.  The rule is on degrees alone — no sequence, no suffix, no length in bases — and is stated on the
@@ -866,6 +933,9 @@ int  elba_get_device_view(elba_ctx *ctx, elba_device_view *view);
  *       not fit fails with ELBA_ERR_UNSUPPORTED / ELBA_ERR_OUT_OF_MEMORY, naming it.  Tests set a small value to force passes; the result does not
  *       depend on it.  What still holds 32-bit places and refuses more than 2^32 instances with ELBA_ERR_UNSUPPORTED: 19 <= k <= 31 with
  *       UPPER > 255, option "kmer_no_msd", and elba_set_kmer_matrix_device (triples).
+ *   "polish_trace_bytes" (>= 0): elba_polish_contigs aligns its voters in batches of consecutive reads whose choices (n * band / 4 bytes per
+ *       voter) fit this many bytes; a read that alone exceeds it is a batch of its own.  0, the default: an eighth of the device memory free
+ *       as the call starts, at least 64 MiB.  Tests set a small value to force batches; the result does not depend on it.
  *   "measure_prep" (0 | 1): diagnostic — elba_count_kmers runs its emit kernels a second time without what they write for the SpGEMM's sake alone and
  *       brackets both runs with events (elba_get_stat "spgemm_prep_us").
  *   "tune1" .. "tune5", "tune7": A/B switches of the round in progress (what each means is said where the library reads it); never a result-changing switch. */
