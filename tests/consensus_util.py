@@ -166,7 +166,9 @@ def _codes(s):
     return np.frombuffer(s.encode("ascii"), dtype=np.uint8).copy() if False else np.array([CODE[x] for x in s], dtype=np.int64)
 
 
-def polish_tables(cin):
+def polish_tables(cin, walks=None):
+    """walks: a dict that takes every voter's walked steps, {read: [(choice, row, column, band cell)]} from the end cell back to row 1
+    (choice 0 diagonal, 1 up, 2 left; the step enters cell (row, column) from its predecessor)."""
     W, nc = cin["band"], len(cin["contigs"])
     sc = [_codes(s) for s in cin["contigs"]]
     col = [np.zeros((len(s), 5), dtype=np.int64) for s in cin["contigs"]]
@@ -220,6 +222,8 @@ def polish_tables(cin):
             ch = int(choices[i][j - i - base0])
             steps.append((ch, i, j))
             i, j = (i - 1, j - 1) if ch == 0 else ((i - 1, j) if ch == 1 else (i, j - 1))
+        if walks is not None:
+            walks[r] = [(ch, i, j, j - i - base0) for ch, i, j in steps]
         wrap = (lambda x: x % L) if circ else (lambda x: x)
         for (ch, j), run in itertools.groupby(steps, key=lambda t: (t[0], t[2] if t[0] == 1 else None)):
             run = list(run)
@@ -258,6 +262,24 @@ def polish_tables(cin):
 
 
 KEYS = ("seqs", "voters", "substituted", "deleted", "inserted", "col_off", "col", "gap", "reads")
+
+
+def walked_steps(cin):
+    """{read: [(choice, row, column, band cell)]} of every voter, from its end cell back to row 1, by polish_tables."""
+    walks = {}
+    polish_tables(cin, walks)
+    return walks
+
+
+def runs_of(steps, choice):
+    """The maximal runs of consecutive steps of one choice in a walk, in read order: [(first row, last row, first column, last column,
+    first band cell, last band cell)]."""
+    out = []
+    for ch, run in itertools.groupby(reversed(steps), key=lambda t: t[0]):
+        run = list(run)
+        if ch == choice:
+            out.append((run[0][1], run[-1][1], run[0][2], run[-1][2], run[0][3], run[-1][3]))
+    return out
 
 
 def first_difference(a, b):
