@@ -4,6 +4,7 @@ import os
 
 import numpy as np
 import pytest
+import torch
 
 import elba_amd
 import gpu_util as gu
@@ -63,6 +64,10 @@ def test_align_wide_bands_escalate_and_reach_the_strided_kernel(tiers):
         assert a["extensions_strided"] > 0
     b = _compare(e, o, packed, off, lens, (1, -1, -1, 900))        # bands of more than 512 columns: beyond every register tier
     assert b["extensions_strided"] > 0
+    if tiers == "1":                                             # more extensions than the strided kernel has workgroups (2 per CU): each takes
+        cus = torch.cuda.get_device_properties(0).multi_processor_count      # a second extension on the three antidiagonal buffers of its first
+        print("extensions_strided %d of %d, CUs %d" % (b["extensions_strided"], 2 * b["nalignments"], cus))
+        assert b["extensions_strided"] > 2 * cus
     e.close()
 
 

@@ -4,7 +4,6 @@ packed bytes, offsets and lengths with the oracle's encoder (po.pack_reads) — 
 (both read from the library), on the FASTA encoder's grid, on FASTQ, at a file offset beyond 2^40, and through every rejection."""
 import gzip
 import os
-import re
 
 import numpy as np
 import pytest
@@ -20,7 +19,6 @@ from oracle import pyoracle as po
 
 pytestmark = pytest.mark.gpu
 G = util.GOLDEN
-FMT = {"fasta": 1, "fastq": 2}
 
 
 @pytest.fixture(scope="module")
@@ -37,51 +35,7 @@ def T(eng):
     return t
 
 
-def _exported(e, n, packed_bytes):
-    recs, npos, nlen = e.export_read_index_raw()
-    packed, off, ln = e.export_reads(n, packed_bytes)
-    return recs, npos, nlen, packed, off, ln
-
-
-def _same_export(a, b):
-    return all(x.shape == y.shape and (x == y).all() for x, y in zip(a, b))
-
-
-def _check(e, data, fmt="auto", file_off=0, gid=0, want=None, loop=False):
-    """one call against the restatement (the vectorised form; with loop also the literal one) and the oracle's encoder"""
-    data = bytes(data)
-    want = want or tx.index_numpy(data, fmt, file_off)
-    if loop:
-        assert tx.same_index(tx.index_loop(data, fmt, file_off), want)
-    st = e.set_reads_text(data, file_off, fmt, gid)
-    n = len(want["recs"])
-    assert st["nreads"] == n and st["lines"] == want["lines"] and st["format"] == FMT[want["format"]] and st["chunk_bytes"] == len(data)
-    recs, npos, nlen = e.export_read_index_raw()
-    for f in ("len", "pos", "bases"):
-        bad = np.flatnonzero(recs[f] != want["recs"][f])
-        assert bad.size == 0, (f, int(bad[0]), int(recs[f][bad[0]]), int(want["recs"][f][bad[0]]))
-    assert (npos == want["name_pos"]).all() and (nlen == want["name_len"]).all()
-    seqs = tx.sequences_of(data, want, file_off)
-    wp, woff, wlen = po.pack_reads(seqs)
-    assert st["bases"] == int(wlen.sum()) and st["packed_bytes"] == int(((wlen.astype(np.int64) + 3) // 4).sum())
-    got, goff, glen = e.export_reads(n, st["packed_bytes"])
-    assert (goff == woff).all() and (glen == wlen).all()
-    assert (got[:st["packed_bytes"]] == wp[:st["packed_bytes"]]).all() and not got[st["packed_bytes"]:].any()
-    names, recs2 = e.export_read_index()
-    assert names == tx.names_of(data, want, file_off) and (recs2 == recs).all()
-    return st, seqs
-
-
-def _rejected(e, data, fmt="auto", file_off=0):
-    """(kind, offset) the library names, checked against both forms of the restatement"""
-    with pytest.raises(elba_amd.ElbaError) as x:
-        e.set_reads_text(bytes(data), file_off, fmt)
-    assert x.value.status == 1, x.value
-    m = re.search(r"\(kind (\d+)\) in record (-?\d+) at file offset (\d+)", str(x.value))
-    assert m, str(x.value)
-    got = (int(m.group(1)), int(m.group(3)))
-    assert got == tx.error_of(tx.index_numpy, data, fmt, file_off) == tx.error_of(tx.index_loop, data, fmt, file_off)
-    return got, int(m.group(2))
+_exported, _same_export, _check, _rejected = tx.device_exported, tx.same_export, tx.device_check, tx.device_rejected      # (shared with test_gpu_second_trips.py)
 
 
 # ---- small shapes and the hand cases -----------------------------------------------------------------------------------------------------

@@ -306,3 +306,63 @@ BAD_CASES = [
     ("two violations, the earlier one named", b">a\nAC\n\nAC\n>b\nA\r\n", "auto", SHAPE, 6),
     ("a CR before a shape violation", b">a\r\nAC\n\nAC\n", "auto", CR, 2),
 ]
+
+
+# ---- the device against the restatement (the -m gpu files share these) -----------------------------------------------------------------------
+FMT = {"fasta": 1, "fastq": 2}
+
+
+def device_exported(e, n, packed_bytes):
+    recs, npos, nlen = e.export_read_index_raw()
+    packed, off, ln = e.export_reads(n, packed_bytes)
+    return recs, npos, nlen, packed, off, ln
+
+
+def same_export(a, b):
+    return all(x.shape == y.shape and (x == y).all() for x, y in zip(a, b))
+
+
+def device_check(e, data, fmt="auto", file_off=0, gid=0, want=None, loop=False):
+    """one call against the restatement (the vectorised form; with loop also the literal one) and the oracle's encoder"""
+    from oracle import pyoracle as po
+    data = bytes(data)
+    want = want or index_numpy(data, fmt, file_off)
+    if loop:
+        assert same_index(index_loop(data, fmt, file_off), want)
+    st = e.set_reads_text(data, file_off, fmt, gid)
+    n = len(want["recs"])
+    assert st["nreads"] == n and st["lines"] == want["lines"] and st["format"] == FMT[want["format"]] and st["chunk_bytes"] == len(data)
+    recs, npos, nlen = e.export_read_index_raw()
+    for f in ("len", "pos", "bases"):
+        bad = np.flatnonzero(recs[f] != want["recs"][f])
+        assert bad.size == 0, (f, int(bad[0]), int(recs[f][bad[0]]), int(want["recs"][f][bad[0]]))
+    assert (npos == want["name_pos"]).all() and (nlen == want["name_len"]).all()
+    seqs = sequences_of(data, want, file_off)
+    wp, woff, wlen = po.pack_reads(seqs)
+    assert st["bases"] == int(wlen.sum()) and st["packed_bytes"] == int(((wlen.astype(np.int64) + 3) // 4).sum())
+    got, goff, glen = e.export_reads(n, st["packed_bytes"])
+    assert (goff == woff).all() and (glen == wlen).all()
+    assert (got[:st["packed_bytes"]] == wp[:st["packed_bytes"]]).all() and not got[st["packed_bytes"]:].any()
+    names, recs2 = e.export_read_index()
+    assert names == names_of(data, want, file_off) and (recs2 == recs).all()
+    return st, seqs
+
+
+def device_rejected(e, data, fmt="auto", file_off=0, loop=True):
+    """(kind, offset) the library names, checked against both forms of the restatement (loop=False: a text too long for the literal
+    form, which the CPU tests hold against the vectorised one at a small size), and the record of the message"""
+    import re
+
+    import pytest
+
+    import elba_amd
+    with pytest.raises(elba_amd.ElbaError) as x:
+        e.set_reads_text(bytes(data), file_off, fmt)
+    assert x.value.status == 1, x.value
+    m = re.search(r"\(kind (\d+)\) in record (-?\d+) at file offset (\d+)", str(x.value))
+    assert m, str(x.value)
+    got = (int(m.group(1)), int(m.group(3)))
+    assert got == error_of(index_numpy, data, fmt, file_off)
+    if loop:
+        assert got == error_of(index_loop, data, fmt, file_off)
+    return got, int(m.group(2))
