@@ -799,10 +799,12 @@ int elba_set_option(elba_ctx *ctx, const char *name, int64_t value)
         ELBA_REQUIRE(name, ELBA_ERR_INVALID_ARG, "set_option: null name");
         struct { const char *n; bool *b; } flags[] = {
             {"overlap_cold_calls", &c.cold_calls}, {"no_symmetry", &c.opt.no_symmetry}, {"no_ell", &c.opt.no_ell}, {"no_pay", &c.opt.no_pay}, {"mir32", &c.opt.mir32},
-            {"no_hints", &c.opt.no_hints}, {"no_sample", &c.opt.no_sample}, {"no_slab", &c.opt.no_slab}, {"no_ell_compact", &c.opt.no_ell_compact}, {"msd_no_rank", &c.opt.msd_no_rank}, {"msd_rank", &c.opt.msd_rank}, {"csr_pairs_late", &c.opt.csr_pairs_late}, {"no_suffix", &c.opt.no_suffix}, {"ov_generic", &c.opt.ov_generic}, {"no_row_order", &c.opt.no_row_order}, {"no_inline", &c.opt.no_inline}, {"panel_inline", &c.opt.panel_inline}, {"kmer_pairs", &c.opt.kmer_pairs},
+            {"no_hints", &c.opt.no_hints}, {"no_sample", &c.opt.no_sample}, {"no_slab", &c.opt.no_slab}, {"no_ell_compact", &c.opt.no_ell_compact}, {"msd_no_rank", &c.opt.msd_no_rank}, {"msd_rank", &c.opt.msd_rank}, {"csr_pairs_late", &c.opt.csr_pairs_late}, {"no_suffix", &c.opt.no_suffix}, {"no_row_order", &c.opt.no_row_order}, {"no_inline", &c.opt.no_inline}, {"panel_inline", &c.opt.panel_inline}, {"kmer_pairs", &c.opt.kmer_pairs},
             {"kmer_unfused", &c.opt.kmer_unfused}, {"kmer_no_msd", &c.opt.kmer_no_msd}, {"kmer_msd", &c.opt.kmer_msd}, {"csr_pairs", &c.opt.csr_pairs}, {"emit_plain", &c.opt.emit_plain}, {"trace", &c.opt.trace}, {"measure_prep", &c.opt.measure_prep}};
         for (auto &f : flags) if (!strcmp(name, f.n)) { *f.b = value != 0; return; }
-        if (!strcmp(name, "kmer_drop")) { ELBA_REQUIRE(value >= 0 && value <= 3, ELBA_ERR_INVALID_ARG, "set_option: kmer_drop is 0..3"); c.opt.kmer_drop = (int)value; }
+        // "ov_generic" (A/B of the numeric kernel on reads-built matrices): 0 the kernel the plan picks, 1 the general kernel, 2 the reads path with run-time geometry
+        if (!strcmp(name, "ov_generic")) { ELBA_REQUIRE(value >= 0 && value <= 2, ELBA_ERR_INVALID_ARG, "set_option: ov_generic is 0, 1 or 2"); c.opt.ov_generic = value == 1; c.opt.ov_spec_rt_geom = value == 2; }
+        else if (!strcmp(name, "kmer_drop")) { ELBA_REQUIRE(value >= 0 && value <= 3, ELBA_ERR_INVALID_ARG, "set_option: kmer_drop is 0..3"); c.opt.kmer_drop = (int)value; }
         else if (!strcmp(name, "dense_up")) { ELBA_REQUIRE(value >= 0 && value <= 3, ELBA_ERR_INVALID_ARG, "set_option: dense_up is 0..3"); c.opt.dense_up = (int)value; }
         else if (!strcmp(name, "dense_wgs")) { ELBA_REQUIRE(value >= 1 && value <= 16, ELBA_ERR_INVALID_ARG, "set_option: dense_wgs is 1..16"); c.opt.dense_wgs = (int)value; }
         else if (!strncmp(name, "tune", 4) && name[4] >= '1' && name[4] <= '7' && name[4] != '6' && name[5] == 0) c.opt.tune[name[4] - '0'] = value;      // ("tune0" and "tune6" are retired: unknown names)
@@ -865,6 +867,7 @@ int elba_get_stat(elba_ctx *ctx, const char *name, int64_t *value)
         else if (!strcmp(name, "kmer_buckets")) *value = c.kmer_buckets;      // buckets of the last elba_count_kmers' value partition, all passes (0: the sort)
         else if (!strcmp(name, "overlap_passes")) *value = c.ov_passes;      // passes the last create_seed_matrix took (1: no repeat; set also when the call failed)
         else if (!strcmp(name, "overlap_spec")) *value = c.ov_spec;      // 1: the last create_seed_matrix ran the reads-path instantiation of the numeric kernel (ov_plan.hpp: ov_spec_ok), 0: the general one
+        else if (!strcmp(name, "overlap_spec_geom")) *value = c.ov_spec_geom;      // 1: ... and its compiled-geometry variant (table size, claim limit and column geometry are constants: ov_spec_geom_ok)
         else if (!strcmp(name, "overlap_forwarded")) *value = c.ov_forwarded;      // rows the last create_seed_matrix forwarded to a larger tier on a prediction, all passes
         // where the rows of the last create_seed_matrix went (its final pass) and on which shape of A it ran: read-only, for tests that place a row on a constant
         else if (!strncmp(name, "overlap_tier_limit_", 19) && name[19] >= '0' && name[19] < '0' + NUM_LDS_TIERS && !name[20]) *value = c.ov_tier_limit[name[19] - '0'];

@@ -166,7 +166,8 @@ struct Options {
     bool panel_inline = false;  // inline partners in the rows of a windowed matrix too (a shard's panel): such a matrix is multiplied with the mirror exchange only
     bool no_inline = false;     // no inline partners in the rows of A (the owner's entry of a two-read column carries the other read: no column fetch)
     bool no_suffix = false;     // dense matrices stay on the general kernel
-    bool ov_generic = false;    // SpGEMM: reads-built matrices take the general numeric kernel, not its reads-path instantiation (A/B)
+    bool ov_generic = false;    // SpGEMM: reads-built matrices take the general numeric kernel, not its reads-path instantiation (A/B; option "ov_generic" = 1)
+    bool ov_spec_rt_geom = false;      // SpGEMM: the reads path keeps its run-time geometry, not the compiled-geometry instantiation (A/B; option "ov_generic" = 2)
     bool no_row_order = false;  // dense matrices: partners are named by their row, not by a label that brings reads of one locus together
     bool kmer_pairs = false;    // (value, payload) pairs through the k-mer sort instead of one packed word
     bool kmer_unfused = false;  // per-head column emission (k_runs<true> + k_instance_entries) instead of k_runs_emit
@@ -413,6 +414,7 @@ struct Ctx {
     bool ov_slab_on = false;        // the running call has slabs (ov_launch_finalize reads them)
     uint32_t ov_slab_q16_used = 0;  // diagnostic: the ratio the last call's slabs were sized by (margin included), 0 = none
     int64_t ov_mir_placed = 0;      // diagnostic: mirrored entries of the last call that did NOT go to a slab (placed by k_mirror)
+    int64_t ov_spec_geom = 0;       // diagnostic: ... and they were its compiled-geometry variant (ov_plan.hpp: ov_spec_geom_ok)
     int64_t ov_spec = 0;            // diagnostic: the last call's numeric kernels were the reads-path instantiation (1) or the general one (0)
     // diagnostics of the last create_seed_matrix, from its final pass (elba_get_stat "overlap_tier_*", "overlap_sort_rows_*", "overlap_family", "overlap_pay16",
     // "overlap_rec16"): the plan's claim limits, the rows queued / completed per tier, the rows the two wide-row sorts took, the kernel family and record format

@@ -24,6 +24,9 @@ constexpr size_t OV_LDS_MAX = 160 * 1024;
 namespace ov_spec {
 constexpr uint32_t half = 1, inl = 1, pay16 = 1, rec16 = 1, suffix = 0, qblk_log2 = 0, j_shift = 0;
 constexpr uint32_t hint_mask = 1u << 31, pos_mask = 0x3FFFFFFFu;
+// ... and what its compiled-geometry variant fixes on top: columns padded to ONE 64-byte line (8 entries: every matrix whose longest column holds 5 .. 8
+// entries, matrix.hip: choose_column_store), four lanes x 16 bytes per row entry, 3 bits of a sequence number for the place in the column
+constexpr uint32_t geom_stride = 8, geom_lpc_log2 = 2, geom_fbits = 3;
 }
 
 // ---- the tier table: one row per (family, tier) — THE place where tier geometry is stated ------------------------------------------------
@@ -58,6 +61,10 @@ constexpr OvTierRow OV_ROWS[] = {
 };
 constexpr int OV_NROWS = (int)(sizeof(OV_ROWS) / sizeof(OV_ROWS[0]));
 
+// the claimed slots at which a row abandons an LDS tier of 2^tbits slots under `block` lanes: min(3T/4, T - block) - 1 (a lane overshoots by at most one
+// claim: Table::insert_lds).  The plan states it per tier (OvPlan::tier_limit); the numeric kernels that compile their table size in take it from here
+constexpr uint32_t ov_tier_limit(int tbits, int block) { return std::min(((1u << tbits) >> 2) * 3, (1u << tbits) - (uint32_t)block) - 1; }
+
 // staging records beyond what the rows need: one open chunk per resident workgroup
 constexpr int64_t ov_stage_slack(int num_cus) { return (int64_t)num_cus * 32 * STAGE_CHUNK + 64; }
 
@@ -84,6 +91,7 @@ inline int ov_row_of(OvFamily family, int tier, int dense_up)
 // the options the driver's decisions read (Ctx::opt's, by name)
 struct OvOptions {
     bool no_symmetry = false, no_pay = false, mir32 = false, no_slab = false, no_sample = false, ov_generic = false;
+    bool spec_rt_geom = false;      // option "ov_generic" = 2 (A/B): the reads path keeps its run-time geometry
     int dk = -1, dense_up = 1, dense_wgs = 8, slab_q16 = 0, slab_pct = 175;
     int64_t tune3 = 0, tune4 = 0, tune5 = 0, tune7 = 0;
 };
@@ -94,7 +102,7 @@ struct OvHints { uint32_t prior_q16 = 0, slab_q16 = 0; bool tiers_known = false,
 // tmp_cap: the staging capacity in records, 0 = not chosen yet (then free_bytes — the device's free memory — and workspace_hint_bytes choose it)
 struct OvInput {
     int64_t M = 0, N = 0, Z = 0, row_lo = 0, row_hi = 0, max_row_nnz = 0, max_col_nnz = 0;
-    uint32_t fbits = 1;
+    uint32_t fbits = 1, s_stride = 0, lpc_log2 = 0;      // (s_stride: padded column stride in entries, 0 = CSC columns)
     bool pos16 = false, use_ell = false, csr_hints = false, csr_inline = false, csr_suffix = false, have_row_order = false;
     int num_cus = 256;
     OvOptions opt;
@@ -108,20 +116,22 @@ struct OvLaunch { int row = -1, grid = 0, block = 0; size_t lds = 0; };      // 
 // the finalize pass (row pointers, mirror, per-row sorts): grids, and which of the two wide-row sorts are launched
 struct OvFinPlan {
     int64_t nrows = 0;
-    bool slabs = false, scan_rowptr = false, narrow = false;      // k_slab_fold runs | row pointers by k_sum_counts + scan (M + 1 > 2^17) | no row can be wider than FIN_WAVE2_MAX
+    bool slabs = false, scan_rowptr = false, narrow = false;      // the rows hold slab entries (k_row_counts folds them) | row pointers by k_row_counts + scan (M + 1 > 2^17) | no row can be wider than FIN_WAVE2_MAX
     int slab_fold_blocks = 0, rowptr_blocks = 0, row_blocks = 0, bucket_blocks = 0, huge_blocks = FIN_HUGE_BLOCKS;
     uint64_t sort_stride = 2;
     uint32_t sorts = 0;      // launched: bit 0 k_finalize_bucket, bit 1 k_finalize_huge
 };
 struct OvPlan {
     int64_t nrows = 0;
+    bool geom_off = false;      // option "ov_generic" = 2
     bool whole = false, ell = false, forced = false;      // the window is the whole matrix | padded columns | an option forces the general kernel ("ov_generic", "dk", "tune3/4/5/7")
     uint32_t half = 0, pos_mask = 0, hint_mask = 0, suffix = 0, inl = 0;
     bool row_order = false, hints_used = false;
     bool pay = false, pay16 = false;
     OvFamily family = OV_S32;
     int dk = 1;
-    bool spec = false;
+    bool spec = false, spec_geom = false;      // the reads-path instantiation runs | ... with table size and column geometry compiled in (ov_spec_geom_ok)
+    uint32_t s_stride = 0, lpc_log2 = 0, fbits = 0;      // the column geometry of A the kernels run with (OvInput's)
     uint32_t min_tier = 0, qblk_log2 = 0, prior_q16 = 16384, use_feedback = 1, max_col = 1;
     unsigned long long fb_enough = 0;
     uint32_t nsample = 0, sstep = 1;
@@ -146,6 +156,14 @@ inline bool ov_spec_ok(const OvPlan &p)
     return !p.forced && p.dk == 0 && !p.pay && (p.pay16 ? 1u : 0u) == ov_spec::pay16 && p.ell && p.half == ov_spec::half && p.hint_mask == ov_spec::hint_mask &&
            p.pos_mask == ov_spec::pos_mask && p.inl == ov_spec::inl && (p.mir16 ? 1u : 0u) == ov_spec::rec16 && p.suffix == ov_spec::suffix && !p.row_order &&
            p.qblk_log2 == ov_spec::qblk_log2 && p.whole;
+}
+
+// The compiled-geometry variant of that instantiation (table size, claim limit, column stride, lanes per row entry and fbits are constants of the kernel)
+// runs a reads-path call whose columns have the geometry it fixes; every other stride (4, 16, 24, ...) and option "ov_generic" = 2 (A/B) keep the
+// run-time-geometry instantiation.
+inline bool ov_spec_geom_ok(const OvPlan &p)
+{
+    return ov_spec_ok(p) && !p.geom_off && p.s_stride == ov_spec::geom_stride && p.lpc_log2 == ov_spec::geom_lpc_log2 && p.fbits == ov_spec::geom_fbits;
 }
 
 inline OvLaunch ov_launch_of(int row, bool pay16, int num_cus, int dense_wgs, int spill_blocks)
@@ -256,6 +274,7 @@ inline void ov_plan_switches(const OvInput &in, OvPlan &p)
     // the option "dk" (0, 1, 2, 4) overrides
     p.dk = o.dk >= 0 ? o.dk : ((in.csr_inline && in.N > 0 && Z < 3 * in.N) ? 0 : 1);
     p.spec = ov_spec_ok(p);      // (the reads path: its switches compiled into the kernel)
+    p.spec_geom = ov_spec_geom_ok(p);      // (... and its geometry)
 }
 
 // part 3: the sample of a cold call and the mirror slabs
@@ -289,10 +308,8 @@ inline void ov_plan_tiers(const OvInput &in, OvPlan &p)
     // the tiers' rows, and from the rows' own workgroup sizes the claimed slots at which a row abandons a tier: min(3T/4, T - block) - 1 (a lane
     // overshoots by at most one claim: Table::insert_lds)
     for (int t = 0; t < NUM_TIERS; ++t) p.tier[t] = ov_launch_of(ov_row_of(p.family, t, (int)o.dense_up), p.pay16, in.num_cus, o.dense_wgs, p.spill_blocks);
-    for (int t = 0; t < NUM_LDS_TIERS; ++t) {
-        const uint32_t T = 1u << OV_ROWS[p.tier[t].row].tbits;
-        p.tier_limit[t] = std::min((T >> 2) * 3, T - (uint32_t)p.tier[t].block) - 1;
-    }
+    for (int t = 0; t < NUM_LDS_TIERS; ++t)
+        p.tier_limit[t] = ov_tier_limit(OV_ROWS[p.tier[t].row].tbits, p.tier[t].block);
     if (p.nsample) p.sample = p.tier[OV_SAMPLE_TIER];
     // the highest tier ANY row of this matrix can reach: a row's distinct partners <= min(its entries x the longest column, reads), the tier that holds
     // twice that is guaranteed to fit it and k_classify_direct never starts a row above it.  A cold call on a small matrix launched five tiers
@@ -318,6 +335,7 @@ inline OvPlan plan_ov(const OvInput &in)
     p.nrows = nrows;
     p.whole = in.row_lo == 0 && in.row_hi == in.M;
     p.ell = in.use_ell;
+    p.s_stride = in.s_stride; p.lpc_log2 = in.lpc_log2; p.fbits = in.fbits; p.geom_off = o.spec_rt_geom;
     p.forced = o.ov_generic || o.dk >= 0 || o.tune3 != 0 || o.tune4 != 0 || o.tune5 != 0 || o.tune7 != 0;
     ov_plan_capacities(in, p);
     ov_plan_switches(in, p);

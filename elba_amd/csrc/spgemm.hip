@@ -121,6 +121,7 @@ struct OvParams {
 // that carry posT, 16-byte staging words, no dense path, single queue places.  Those switches are compile-time constants here (the kernel's dead
 // branches go, and so do the scalars it used to hold for them: the general kernel spills ~120 SGPRs to VGPR lanes); what still varies between
 // such calls — slabs or none, feedback, the tier, fbits, stride, lanes per entry — stays a field.  ov_spec_ok (ov_plan.hpp) is the predicate.
+// (Its compiled-geometry variant — ov_spec_geom_ok, template argument GEOM — takes the same block and does not read s_stride, lpc_log2, fbits and tier_limit.)
 struct OvSpecParams {
     static constexpr uint32_t half = ov_spec::half, inl = ov_spec::inl, pay16 = ov_spec::pay16, rec16 = ov_spec::rec16, suffix = ov_spec::suffix, qblk_log2 = ov_spec::qblk_log2, j_shift = ov_spec::j_shift;
     static constexpr uint32_t hint_mask = ov_spec::hint_mask, pos_mask = ov_spec::pos_mask;
@@ -161,7 +162,7 @@ __global__ __launch_bounds__(256) void k_zero_regions(ZeroList z)
 // on slab_pos[j] = (slab end << 32 | next free entry) — written by the classification pass, which walks every row anyway — hands an image its
 // place and tells it whether the place is still inside the slab.  An image that finds its row's slab full (or is staged while no ratio is known:
 // the sample's own rows, small matrices) draws a ticket from low_cnt[j] and takes the old way (k_mirror, the mirror area); the finalize reads a
-// row's mirrored entries from the slab first (slab_n[j] of them: k_slab_fold), then from the mirror area.  Capacity is a performance matter only,
+// row's mirrored entries from the slab first (slab_n[j] of them: k_row_counts), then from the mirror area.  Capacity is a performance matter only,
 // never a correctness limit.
 struct __attribute__((packed, aligned(4))) RowPair { uint32_t a, b; };      // a_rowptr[j], a_rowptr[j + 1]
 __device__ __forceinline__ uint32_t slab_base(uint32_t rp, uint32_t rp0, uint32_t row_rel, uint32_t q16)
@@ -197,13 +198,14 @@ struct FinParams {
     uint32_t M, row_lo, row_hi, half;
     uint32_t *fin_lists; OvCounters *ctr;
     uint64_t *sortkeys; unsigned long long sort_stride;
-    uint32_t *sum_tmp;
+    uint32_t *sum_tmp;       // the rows' final lengths where the row pointers are scanned from them (k_row_counts; else null)
+    uint32_t queue_in_rowptr;      // k_row_pointers queues the wide rows (no k_row_counts in front of it)
     long long b_cap;         // capacity of b_col / b_val in entries: rows that would not fit are left out (the host regrows and reruns)
     uint32_t mir16;          // positions fit 16 bits: a mirrored entry is ONE 16-byte word (i, q0 | t0 << 16, q1 | t1 << 16, numshared) — one store
                              // request per scattered entry instead of two, half the bytes read back
     const uint32_t *tick_rows;      // OvParams::tick_rows
     const uint32_t *a_rowptr; uint4 *slab;      // mirror slabs (above; mir16 records): null = none
-    const unsigned long long *slab_pos; uint32_t *slab_n;      // [M] the slabs' fill words as the numeric kernels left them / entries in every row's slab (k_slab_fold; null with slab)
+    const unsigned long long *slab_pos; uint32_t *slab_n;      // [M] the slabs' fill words as the numeric kernels left them / entries in every row's slab (k_row_counts; null with slab)
 };
 
 // this call's slabs: ratio (0 = none) and the first row entry of the window
@@ -220,19 +222,42 @@ __device__ __forceinline__ uint2 slab_row(const FinParams &p, const SlabCall &s,
     if (!s.q16) return make_uint2(0u, 0u);
     return make_uint2(slab_base(p.a_rowptr[i], s.rp0, i - p.row_lo, s.q16), p.slab_n[i]);
 }
-// entries in every row's slab, from the fill words (a full slab's word has run past its end: one add per image that found no room)
-__global__ void k_slab_fold(FinParams p)
+// a row of the window whose final length (known once the counts are: staged + ticketed + slab entries) is too wide for the one-wave sorts is queued for the block sorts
+__device__ __forceinline__ void fin_queue_wide(const FinParams &p, uint32_t i, uint32_t y)
 {
-    const uint32_t i = p.row_lo + blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= p.row_hi) return;
-    const SlabCall s = slab_call(p);
-    uint32_t n = 0;
-    if (s.q16) {
-        const unsigned long long w = p.slab_pos[i];
-        const uint32_t base = slab_base(p.a_rowptr[i], s.rp0, i - p.row_lo, s.q16), cur = (uint32_t)w, lim = (uint32_t)(w >> 32);
-        n = (cur < lim ? cur : lim) - base;
+    if (y <= FIN_WAVE2_MAX || i < p.row_lo || i >= p.row_hi) return;
+    const int which = y > FIN_LDS_MAX ? 1 : 0;
+    const uint32_t at = atomicAdd(&p.ctr->fin_count[which], 1u);      // (the lists' order is whatever the draws make it: nobody depends on it)
+    p.fin_lists[(size_t)which * p.M + at] = i;
+}
+
+// The rows' counts in front of the row pointers, one lane per row, ONE pass over the rows' header words: entries in the row's slab from its fill word (a
+// full slab's word has run past its end: one add per image that found no room) -> slab_n; the row's final length -> sum_tmp where the row pointers are
+// scanned from it (M + 1 > 2^17, sum_tmp != null; entry M = 0); rows wider than FIN_WAVE2_MAX -> the queues of the block sorts.
+__global__ __launch_bounds__(256) void k_row_counts(FinParams p)
+{
+    const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e > p.M) return;
+    uint32_t y = 0;
+    if (e < p.M) {
+        uint32_t n = 0;
+        if (p.slab_n) {
+            n = p.slab_n[e];      // (zero outside the window: ov_zero_counters)
+            if (e >= p.row_lo && e < p.row_hi) {
+                const SlabCall s = slab_call(p);
+                n = 0;
+                if (s.q16) {
+                    const unsigned long long w = p.slab_pos[e];
+                    const uint32_t base = slab_base(p.a_rowptr[e], s.rp0, e - p.row_lo, s.q16), cur = (uint32_t)w, lim = (uint32_t)(w >> 32);
+                    n = (cur < lim ? cur : lim) - base;
+                }
+                p.slab_n[e] = n;
+            }
+        }
+        y = p.row_cnt[e] + p.low_cnt[e] + n;
+        fin_queue_wide(p, e, y);
     }
-    p.slab_n[i] = n;
+    if (p.sum_tmp) p.sum_tmp[e] = y;
 }
 
 // entry t of a row's extent: mirrored (the first `low`) or staged by the row itself; as the two halves of a staged record
@@ -286,6 +311,7 @@ __global__ __launch_bounds__(256) void k_row_pointers(FinParams p)
         const uint32_t e = t0 + tid * 4 + u;
         v[u] = e < p.M ? p.row_cnt[e] + p.low_cnt[e] + (p.slab_n ? p.slab_n[e] : 0u) : 0u;
         mine += v[u];
+        if (p.queue_in_rowptr && e < p.M) fin_queue_wide(p, e, v[u]);      // (no slabs: no k_row_counts in front — the wide rows are queued here)
     }
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) pre += __shfl_xor(pre, d, 64);
@@ -307,32 +333,20 @@ __global__ __launch_bounds__(256) void k_row_pointers(FinParams p)
     }
 }
 
-__global__ void k_sum_counts(FinParams p)
-{
-    const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e <= p.M) p.sum_tmp[e] = e < p.M ? p.row_cnt[e] + p.low_cnt[e] + (p.slab_n ? p.slab_n[e] : 0u) : 0u;
-}
-
 // Mirror pass: every staged entry (i,j) whose partner row j is computed here as well is the transpose's entry (j,i) with the two
 // positions of each seed exchanged (see matrix.hip, above k_products).  Its slot inside row j's extent is the ticket the numeric
-// kernel drew from low_cnt[j]; the extent is known now (b_rowptr).  One wavefront per row; rows too wide for the one-wave sort
-// are queued for the block sorts here (their final length is only known after the scan).
+// kernel drew from low_cnt[j]; the extent is known now (b_rowptr).  32-byte records: one wavefront per row that staged a ticketed entry; 16-byte
+// records: the ticketed entries are a list, one lane each (the grid is sized for the list).  Launched with `half` only.
 __global__ __launch_bounds__(256) void k_mirror(FinParams p)
 {
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const uint32_t nwaves = (gridDim.x * blockDim.x) >> 6;
     uint32_t placed = 0;
+    if (p.half && !p.rec16)
     for (uint32_t i = p.row_lo + wave; i < p.row_hi; i += nwaves) {
         const uint32_t own = p.row_cnt[i];
         const unsigned long long off = p.row_off[i];
-        const uint32_t y = own + p.low_cnt[i] + (p.slab_n ? p.slab_n[i] : 0u);
-        if (lane == 0 && y > FIN_WAVE2_MAX) {
-            const int which = y > FIN_LDS_MAX ? 1 : 0;
-            const uint32_t at = atomicAdd(&p.ctr->fin_count[which], 1u);
-            p.fin_lists[(size_t)which * p.M + at] = i;
-        }
-        if (!p.half || p.rec16) continue;      // (16-byte records: the ticketed entries are a list, below)
         if (p.tick_rows && !((p.tick_rows[i >> 5] >> (i & 31u)) & 1u)) continue;      // (none of the row's images took a ticket: nothing to place)
         for (uint32_t t = lane; t < own; t += 64) {
             const uint4 a = p.tmp[off + t].a;
@@ -817,10 +831,10 @@ static OvInput ov_input(Ctx &c, int phase, int pass)
     OvInput in;
     const RowWindow w = c.window();
     in.M = c.M; in.N = c.N; in.Z = c.Z; in.row_lo = w.lo; in.row_hi = w.hi; in.max_row_nnz = c.max_row_nnz; in.max_col_nnz = c.max_col_nnz;
-    in.fbits = c.fbits; in.pos16 = c.pos16; in.use_ell = c.use_ell; in.csr_hints = c.csr_hints; in.csr_inline = c.csr_inline; in.csr_suffix = c.csr_suffix;
+    in.fbits = c.fbits; in.s_stride = c.use_ell ? c.s_stride : 0u; in.lpc_log2 = c.lpc_log2; in.pos16 = c.pos16; in.use_ell = c.use_ell; in.csr_hints = c.csr_hints; in.csr_inline = c.csr_inline; in.csr_suffix = c.csr_suffix;
     in.have_row_order = c.have_row_order; in.num_cus = c.num_cus;
     const Options &o = c.opt;
-    in.opt.no_symmetry = o.no_symmetry; in.opt.no_pay = o.no_pay; in.opt.mir32 = o.mir32; in.opt.no_slab = o.no_slab; in.opt.no_sample = o.no_sample; in.opt.ov_generic = o.ov_generic;
+    in.opt.no_symmetry = o.no_symmetry; in.opt.no_pay = o.no_pay; in.opt.mir32 = o.mir32; in.opt.no_slab = o.no_slab; in.opt.no_sample = o.no_sample; in.opt.ov_generic = o.ov_generic; in.opt.spec_rt_geom = o.ov_spec_rt_geom;
     in.opt.dk = o.dk; in.opt.dense_up = o.dense_up; in.opt.dense_wgs = o.dense_wgs; in.opt.slab_q16 = o.slab_q16; in.opt.slab_pct = o.slab_pct;
     in.opt.tune3 = o.tune[3]; in.opt.tune4 = o.tune[4]; in.opt.tune5 = o.tune[5]; in.opt.tune7 = o.tune[7];
     in.hints.prior_q16 = c.ov_prior_q16; in.hints.slab_q16 = c.ov_slab_q16; in.hints.tiers_known = c.ov_tiers_known;
@@ -840,10 +854,12 @@ static OvInput ov_input(Ctx &c, int phase, int pass)
 // A dense row has one instantiation (gather depth 2, its table bits compiled in where the row names them); every other row one per gather depth, and
 // a row the reads path can run (no HBM table, no payload) that path's instantiation too.  ov_row_kernels is THE enumeration: the launch picks from
 // it, and ov_set_attributes raises the dynamic-LDS limit of everything in it — a launched instantiation cannot be missing there.
-template <int R, int DK, bool SPEC> static constexpr auto ov_row_kernel()
+// (GEOM: the reads path with the row's table bits and the column geometry of ov_spec::geom_* compiled in)
+template <int R, int DK, bool SPEC, bool GEOM = false> static constexpr auto ov_row_kernel()
 {
     constexpr OvTierRow r = OV_ROWS[R];
     if constexpr (r.dense) return &k_spgemm_direct<r.block, false, false, 2, true, r.tbc>;
+    else if constexpr (SPEC && GEOM) return &k_spgemm_direct<r.block, false, false, 0, false, r.tbits, true, true>;
     else if constexpr (SPEC) return &k_spgemm_direct<r.block, false, false, 0, false, 0, true>;
     else return &k_spgemm_direct<r.block, r.global, r.payload, DK>;
 }
@@ -852,7 +868,7 @@ template <int R, typename F> static void ov_row_kernels(F &&f)
 {
     f(ov_row_kernel<R, 0, false>());
     if constexpr (!OV_ROWS[R].dense) { f(ov_row_kernel<R, 1, false>()); f(ov_row_kernel<R, 2, false>()); f(ov_row_kernel<R, 4, false>()); }
-    if constexpr (ov_row_has_spec<R>()) f(ov_row_kernel<R, 0, true>());
+    if constexpr (ov_row_has_spec<R>()) { f(ov_row_kernel<R, 0, true>()); f(ov_row_kernel<R, 0, true, true>()); }
 }
 template <int... R> static void ov_set_attributes(std::integer_sequence<int, R...>)
 {
@@ -878,6 +894,7 @@ template <int R> static void ov_launch_row(const OvLaunch &l, const OvPlan &plan
     const dim3 grid((unsigned)l.grid), block((unsigned)r.block);
     const uint32_t tb = (uint32_t)r.tbits;
     if constexpr (ov_row_has_spec<R>()) {
+        if (plan.spec_geom) { hipLaunchKernelGGL((ov_row_kernel<R, 0, true, true>()), grid, block, l.lds, s, ov_spec_params(p), r.tier, tb, sample); return; }
         if (plan.spec) { hipLaunchKernelGGL((ov_row_kernel<R, 0, true>()), grid, block, l.lds, s, ov_spec_params(p), r.tier, tb, sample); return; }
     }
     if (r.dense || plan.dk == 0) hipLaunchKernelGGL((ov_row_kernel<R, 0, false>()), grid, block, l.lds, s, p, r.tier, tb, sample);
@@ -986,7 +1003,7 @@ static OvRun ov_begin(Ctx &c, int phase)
     c.ov_host.reserve(sizeof(OvCounters));
     r.hc = static_cast<OvCounters *>(c.ov_host.p);
     *r.hc = OvCounters{};
-    c.ov_passes = 0; c.ov_forwarded = 0; c.ov_spec = 0;
+    c.ov_passes = 0; c.ov_forwarded = 0; c.ov_spec = 0; c.ov_spec_geom = 0;
     ov_bind(r);
     return r;
 }
@@ -1035,6 +1052,7 @@ static void ov_numeric(OvRun &r)
 {
     Ctx &c = r.c;
     c.ov_spec = r.plan.nrows > 0 && r.plan.spec ? 1 : 0;
+    c.ov_spec_geom = r.plan.nrows > 0 && r.plan.spec_geom ? 1 : 0;
     for (int t = 0; t < NUM_LDS_TIERS; ++t) c.ov_tier_limit[t] = (int64_t)r.plan.tier_limit[t];      // (diagnostics: the plan of this pass — the last pass's stand)
     c.ov_family = (int64_t)r.plan.family; c.ov_pay16 = r.plan.pay16 ? 1 : 0; c.ov_rec16_used = r.plan.mir16 ? 1 : 0;
     for (int t = 0; t < NUM_TIERS; ++t)
@@ -1064,16 +1082,18 @@ static void ov_finalize(Ctx &c, const OvFinPlan &fp, uint32_t half, const StageR
     f.a_rowptr = c.a_rowptr.as<uint32_t>(); f.slab = fp.slabs ? c.ov_slab.as<uint4>() : nullptr;
     f.slab_pos = f.slab ? c.ov_slabpos.as<unsigned long long>() : nullptr; f.slab_n = f.slab ? c.ov_slabn.as<uint32_t>() : nullptr;
     f.sortkeys = c.ov_sortkeys.as<uint64_t>(); f.sort_stride = fp.sort_stride;
-    if (fp.slab_fold_blocks > 0) hipLaunchKernelGGL(k_slab_fold, dim3((unsigned)fp.slab_fold_blocks), dim3(256), 0, s, f);
+    // ONE pass over the rows' counts in front of the row pointers (k_row_counts: slab entries, the scan's input, the wide rows' queues); a matrix of up
+    // to 2^17 rows without slabs needs none — k_row_pointers sums the counts itself and queues the wide rows on its way
+    f.sum_tmp = fp.scan_rowptr ? c.ov_sum_tmp.as<uint32_t>() : nullptr;
+    const bool counts = fp.scan_rowptr || fp.slab_fold_blocks > 0;
+    f.queue_in_rowptr = counts ? 0u : 1u;
+    if (counts) hipLaunchKernelGGL(k_row_counts, dim3((unsigned)((M + 1 + 255) / 256)), dim3(256), 0, s, f);
     if (!fp.scan_rowptr) hipLaunchKernelGGL(k_row_pointers, dim3((unsigned)fp.rowptr_blocks), dim3(256), 0, s, f);
-    else {
-        f.sum_tmp = c.ov_sum_tmp.as<uint32_t>();
-        hipLaunchKernelGGL(k_sum_counts, dim3((unsigned)fp.rowptr_blocks), dim3(256), 0, s, f);
-        exclusive_scan_u32_to_i64(s, f.sum_tmp, c.b_rowptr.as<int64_t>(), M + 1, c.ws_scan);
-    }
+    else exclusive_scan_u32_to_i64(s, f.sum_tmp, c.b_rowptr.as<int64_t>(), M + 1, c.ws_scan);
     if (fp.nrows <= 0) return;
     const dim3 rows((unsigned)fp.row_blocks);
-    hipLaunchKernelGGL(k_mirror, rows, dim3(256), 0, s, f);
+    // (16-byte records: k_mirror walks the list of ticketed entries — tens of thousands on a cold call of the 200 k-read set, none on a steady one)
+    if (half) hipLaunchKernelGGL(k_mirror, f.rec16 ? dim3((unsigned)std::min<int>(fp.row_blocks, cus)) : rows, dim3(256), 0, s, f);
     if (nremote > 0 && slot == 0) hipLaunchKernelGGL(k_place_remote, dim3((unsigned)std::min<int64_t>((nremote + 255) / 256, (int64_t)cus * 32)), dim3(256), 0, s, f, remote, (unsigned long long)nremote, 0ull);
     if (nremote > 0 && slot != 0) hipLaunchKernelGGL(k_place_remote, dim3((unsigned)std::min<int64_t>((slot + 255) / 256, (int64_t)cus * 4), (unsigned)(nremote / slot)), dim3(256), 0, s, f, remote, (unsigned long long)nremote, (unsigned long long)slot);
     hipLaunchKernelGGL(k_finalize_wave, rows, dim3(256), 0, s, f);
@@ -1184,7 +1204,7 @@ static void ov_numeric_pass(OvRun &r)
 
 // The whole call.  Launch sequence (one stream, ONE host synchronisation at the end when nothing overflows):
 //   counters = 0, row_cnt = 0 | [sample] | k_classify_direct | k_spgemm_direct on the plan's tiers, ascending (+ the HBM-table tier) |
-//   k_row_pointers (scan of the rows' counts) | k_mirror | k_finalize_wave / _mid / _bucket / _huge (per-row column sort + move to b_col / b_val) |
+//   [k_row_counts] | k_row_pointers (scan of the rows' counts) | k_mirror | k_finalize_wave / _mid / _bucket / _huge (per-row column sort + move to b_col / b_val) |
 //   counter read-back.
 void stage_create_seed_matrix(Ctx &c)
 {

@@ -78,19 +78,25 @@ __device__ __forceinline__ bool owns_pair(uint32_t i, uint32_t j, uint32_t row_l
 // (second launch bound = wavefronts per SIMD the register allocation must leave room for: 4 keeps two 512-thread workgroups on a CU — at 132
 //  VGPRs instead of 128 the kernel loses one of them and runs twice as long (measured) —, 8 is what the dense path's 8 workgroups of 4 wavefronts per CU need)
 // SPEC: the reads path (OvSpecParams: its switches are constants) on the LDS tiers with 32-bit accumulators
-template <int BLOCK, bool GLOBAL, bool PAY, int DK = 2, bool SUFFIX = false, int TB = 0, bool SPEC = false>
-__global__ __launch_bounds__(BLOCK, SUFFIX ? 8 : (DK == 4 ? 1 : 4)) void k_spgemm_direct(std::conditional_t<SPEC, OvSpecParams, OvParams> p, int tier, uint32_t lds_tbits, uint32_t sample)
+// GEOM (with SPEC and TB): the compiled-geometry reads path (ov_plan.hpp: ov_spec_geom_ok) — the table's size (TB), with it the distances between the table's
+//   arrays, the place of the misc words behind it and the tier's claim limit, and the columns' geometry (ov_spec::geom_*: stride 8, four lanes per row
+//   entry, fbits 3) are constants of the kernel; the kernel argument lds_tbits and the fields s_stride / lpc_log2 / fbits / tier_limit[tier] are not read
+template <int BLOCK, bool GLOBAL, bool PAY, int DK = 2, bool SUFFIX = false, int TB = 0, bool SPEC = false, bool GEOM = false>
+__global__ __launch_bounds__(BLOCK, SUFFIX ? 8 : (DK == 4 ? 1 : 4)) void k_spgemm_direct(std::conditional_t<SPEC, OvSpecParams, OvParams> p, int tier, uint32_t lds_tbits_arg, uint32_t sample)
 {
     static_assert(!PAY || !GLOBAL, "payload accumulators: LDS tiers only");
     static_assert(!SPEC || (!GLOBAL && !PAY && !SUFFIX), "the reads path: LDS tiers, 32-bit accumulators carrying posT");
+    static_assert(!GEOM || (SPEC && TB >= LDS_TBITS0 && TB < LDS_TBITS0 + NUM_LDS_TIERS && (1 << TB) >= 2 * BLOCK), "compiled geometry: the reads path on an LDS tier whose size is a template argument");
+    constexpr int CTB = GEOM ? TB : 0;      // the table bits where the whole kernel knows them (dense rows know TB in their fast look-up only)
+    const uint32_t lds_tbits = GEOM ? (uint32_t)TB : lds_tbits_arg;
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     uint32_t *misc = GLOBAL ? smem : smem + (size_t)(PAY ? 6 : 4) * (1u << lds_tbits) + ((size_t)1 << lds_tbits) / 2;
     const uint32_t tid = threadIdx.x, lane = tid & 63;
     const uint64_t lt = (1ull << lane) - 1;
     const uint32_t nrows = sample ? p.ctr->sample_count : p.ctr->tier_count[tier];      // complete: every lower tier has finished (same stream); sample: the rows computed before all others on a cold call
     if (nrows == 0) return;      // (a tier nobody queued on — most tiers of a small matrix: its workgroups leave before they initialise a table; rows only ever move to HIGHER tiers, which start later)
-    const uint32_t lb = p.lpc_log2, sub = tid & ((1u << lb) - 1u), grp = tid >> lb, EPT = (uint32_t)BLOCK >> lb;
-    const uint32_t fbits = p.fbits, fmask = (1u << fbits) - 1u, stride = p.s_stride;
+    const uint32_t lb = GEOM ? ov_spec::geom_lpc_log2 : p.lpc_log2, sub = tid & ((1u << lb) - 1u), grp = tid >> lb, EPT = (uint32_t)BLOCK >> lb;
+    const uint32_t fbits = GEOM ? ov_spec::geom_fbits : p.fbits, fmask = (1u << fbits) - 1u, stride = GEOM ? ov_spec::geom_stride : p.s_stride;
     const bool ell = SPEC || p.a_ell != nullptr;
     const uint32_t hmask = p.hint_mask, pmask = p.pos_mask;      // ownership hints in the row entries (Ctx::csr_hints): skip bit of this call's mode, position bits
     const uint2 *csr2 = reinterpret_cast<const uint2 *>(p.a_csr);      // .x = position in the read, .y = k-mer id
@@ -205,7 +211,7 @@ __global__ __launch_bounds__(BLOCK, SUFFIX ? 8 : (DK == 4 ? 1 : 4)) void k_spgem
             if (gu >= (1ull << 18)) {
                 const double pred = 1.25 * (double)nnz * (double)gc / (double)gu;
                 const uint32_t gbits = guaranteed_tbits(ub_i, p.Mcols);
-                if (pred > 1.2 * (double)p.tier_limit[tier] && gbits > lds_tbits) {
+                if (pred > 1.2 * (double)(GEOM ? ov_tier_limit(GEOM ? TB : 1, BLOCK) : p.tier_limit[tier]) && gbits > lds_tbits) {
                     int t2 = tier + 1;
                     while (t2 < NUM_LDS_TIERS && pred > (double)p.tier_limit[t2]) ++t2;
                     // never above the tier guaranteed to fit the row: the host launches no tier beyond the matrix's guaranteed one (spgemm.hip, tmax)
@@ -236,7 +242,7 @@ __global__ __launch_bounds__(BLOCK, SUFFIX ? 8 : (DK == 4 ? 1 : 4)) void k_spgem
         } else {
             tab.tbits = lds_tbits;
             const uint32_t T = 1u << lds_tbits;
-            tab.limit = p.tier_limit[tier];
+            tab.limit = GEOM ? ov_tier_limit(GEOM ? TB : 1, BLOCK) : p.tier_limit[tier];
             tab.keys = smem; tab.cnt = smem + T; tab.smin = smem + 2 * T; tab.smax = smem + 3 * T;
             tab.vmin = reinterpret_cast<unsigned long long *>(smem + 2 * T); tab.vmax = tab.vmin + T;
             list16 = reinterpret_cast<uint16_t *>(smem + (PAY ? 6 : 4) * T);
@@ -275,7 +281,7 @@ __global__ __launch_bounds__(BLOCK, SUFFIX ? 8 : (DK == 4 ? 1 : 4)) void k_spgem
             const uint32_t at = (head + lane) & (RING - 1u);
             const uint32_t j = qj[at];
             if (PAY) { const unsigned long long v = qv[at]; tab.insert_lds64(j, v, v, 1u, lane < n, full); }
-            else { const uint32_t sq = qs[at]; tab.insert_lds(j, sq, sq, 1u, lane < n, full); }
+            else { const uint32_t sq = qs[at]; tab.template insert_lds<CTB>(j, sq, sq, 1u, lane < n, full); }
             head += n;
         };
         // one candidate slot per lane: j == EMPTY is padding (or a lane without a row entry), j == i the diagonal; with `half` a pair of rows
@@ -284,7 +290,8 @@ __global__ __launch_bounds__(BLOCK, SUFFIX ? 8 : (DK == 4 ? 1 : 4)) void k_spgem
             const uint64_t mv = __ballot(j != EMPTY);
             if (mv == 0) return;
             const uint64_t md = __ballot(j == i);
-            pr += (uint32_t)__popcll(mv); dg += (uint32_t)__popcll(md);
+            if (!SPEC) pr += (uint32_t)__popcll(mv);      // (the reads path's entries carry hints: its product count comes from the build of A — OvPlan::hints_used, ov_finish)
+            dg += (uint32_t)__popcll(md);
             uint64_t mi = mv & ~md;
             if (p.half) mi &= __ballot(owns_pair(i, j, p.half == 2u ? 0u : p.row_lo, p.half == 2u ? 0xFFFFFFFFu : p.row_hi, !PAY && p.suffix != 0u));      // (dense matrices reach this path on the tiers without 64-bit accumulators only)      // (2: the rule holds for every partner, wherever its row lives)
             if (mi == 0) return;
@@ -561,7 +568,7 @@ __global__ __launch_bounds__(BLOCK, SUFFIX ? 8 : (DK == 4 ? 1 : 4)) void k_spgem
             }
         }
         if (!GLOBAL && tail != head) drain(tail - head);
-        if ((pr | dg) != 0 && lane == 0) { lds_add32(&misc[DG], dg); lds_add32(&misc[12], pr); }
+        if ((pr | dg) != 0 && lane == 0) { lds_add32(&misc[DG], dg); if (!SPEC) lds_add32(&misc[12], pr); }
         ELBA_DSTAMP(2);
         publish_next();
         if (GLOBAL) __syncthreads(); else lds_barrier();
@@ -588,7 +595,8 @@ __global__ __launch_bounds__(BLOCK, SUFFIX ? 8 : (DK == 4 ? 1 : 4)) void k_spgem
         // ---- one table sweep: nnz before prune + ballot-compacted survivor list ----
         uint32_t yraw = 0;
         const bool relabel = SUFFIX && p.row_label != nullptr, whole = p.row_lo == 0u && p.row_hi == p.M;
-        if (!GLOBAL && T == 4u * (uint32_t)BLOCK) {
+        // (compiled geometry: the choice is made when the kernel is compiled — tiers 0 .. 3 hold four slots per lane, the 8192-slot tier under 256 lanes walks)
+        if (CTB ? (1u << CTB) == 4u * (uint32_t)BLOCK : (!GLOBAL && T == 4u * (uint32_t)BLOCK)) {
             // (the LDS tiers up to 4096 slots: four slots per lane — all eight table words requested at once, the wavefront's survivors take their
             //  places in the list with ONE returning atomic: three LDS round trips per row where the loop below makes a dozen)
             uint32_t jj[4], cc[4], pre[4], tot = 0;
@@ -651,7 +659,7 @@ __global__ __launch_bounds__(BLOCK, SUFFIX ? 8 : (DK == 4 ? 1 : 4)) void k_spgem
             p.row_off[i] = off;
             misc[6] = (uint32_t)off; misc[7] = (uint32_t)(off >> 32); misc[8] = fits ? 1u : 0u;
             lds_add64(w64(W_ACC_YRAW), (unsigned long long)(misc[5] + (dcount >= 1 ? 1u : 0u)));
-            lds_add64(w64(W_ACC_P), (unsigned long long)misc[12]);
+            if (!SPEC) lds_add64(w64(W_ACC_P), (unsigned long long)misc[12]);
             lds_add32(&misc[W_ACC_DONE], 1u);
             lds_add32(&misc[W_ACC_NDIAG], dcount >= 2 ? 1u : 0u);
             lds_add64(w64(W_ACC_Y), (unsigned long long)ytot);

@@ -50,15 +50,78 @@ struct Table {
     // value >= limit, so each wave notices within the insert in which it claims next — at most one claim per lane beyond the limit,
     // hence limit <= T - BLOCK — and a uniform flag costs a scalar branch where a per-lane one costs ten mask instructions per insert.
     // (cnt products of the same pair at once: their count, their smallest and their largest sequence number — 1, s, s for a single product)
+    // CTB != 0: the table size is known when the kernel is compiled (T = 1 << CTB, tbits == CTB) — the probe mask is a literal and the counts, minima and
+    // maxima are reached through the `offset:` field of ONE address (T, 2T, 3T words behind the key) where the run-time size takes three v_add_u32 per
+    // product.  The field holds 16 bits: 12 T <= 49152 up to 4096 slots; the 8192-slot tier reaches its minima with one add and the maxima from there.
+    template <int CTB = 0>
     __device__ __forceinline__ void insert_lds(uint32_t j, uint32_t s, uint32_t smx, uint32_t cnt, bool valid, bool &full) const
     {
         if (full) return;
-        uint32_t slot = lds_slot(j);
+        uint32_t slot = CTB ? (j * 0x9E3779B1u) >> (32 - (CTB ? CTB : 1)) : lds_slot(j);
         uint32_t claimed = 0, old, addr = 0;
         unsigned long long save, t;
         const uint32_t base = (uint32_t)(uintptr_t)keys;        // LDS byte offset (a local address is the low half of its flat form)
         const uint32_t mask = size() - 1, empty = EMPTY;
         const uint32_t tb = size() * 4;                         // byte distance between the four arrays
+        if constexpr (CTB != 0) {
+            static_assert(CTB == 0 || (CTB >= 9 && CTB <= 13), "LDS tiers: 512 .. 8192 slots");
+            constexpr bool NEAR = (12u << CTB) <= 0xFFFFu;      // all three arrays within the offset field of the key's address
+            static_assert((4u << CTB) <= 0xFFFFu, "the count array lies within the 16-bit offset field");
+            if (valid) {
+                if constexpr (NEAR) {
+                    asm volatile(
+                        "s_mov_b64 %[save], exec\n"
+                        ".Lprobe%=:\n\t"
+                        "v_lshl_add_u32 %[addr], %[slot], 2, %[base]\n\t"
+                        "ds_cmpst_rtn_b32 %[old], %[addr], %[empty], %[j]\n\t"
+                        "s_waitcnt lgkmcnt(0)\n\t"
+                        "v_cmp_eq_u32_e64 %[t], %[old], %[empty]\n\t"
+                        "v_cndmask_b32_e64 %[cl], %[cl], 1, %[t]\n\t"
+                        "v_cmp_eq_u32_e32 vcc, %[old], %[j]\n\t"
+                        "s_or_b64 vcc, vcc, %[t]\n\t"
+                        "s_andn2_b64 exec, exec, vcc\n\t"
+                        "s_cbranch_execz .Ldone%=\n\t"
+                        "v_add_u32_e32 %[slot], 1, %[slot]\n\t"
+                        "v_and_b32_e32 %[slot], %[mask], %[slot]\n\t"
+                        "s_branch .Lprobe%=\n"
+                        ".Ldone%=:\n\t"
+                        "s_mov_b64 exec, %[save]\n\t"
+                        "ds_add_u32 %[addr], %[one] offset:%[o1]\n\t"
+                        "ds_min_u32 %[addr], %[s] offset:%[o2]\n\t"
+                        "ds_max_u32 %[addr], %[smx] offset:%[o3]\n"
+                        : [save] "=&s"(save), [addr] "+v"(addr), [old] "=&v"(old), [t] "=&s"(t), [cl] "+v"(claimed), [slot] "+v"(slot)
+                        : [base] "s"(base), [empty] "v"(empty), [j] "v"(j), [mask] "n"((1u << CTB) - 1u), [one] "v"(cnt), [s] "v"(s), [smx] "v"(smx),
+                          [o1] "n"(NEAR ? (4u << CTB) : 0u), [o2] "n"(NEAR ? (8u << CTB) : 0u), [o3] "n"(NEAR ? (12u << CTB) : 0u)
+                        : "vcc", "memory");
+                } else {
+                    asm volatile(
+                        "s_mov_b64 %[save], exec\n"
+                        ".Lprobe%=:\n\t"
+                        "v_lshl_add_u32 %[addr], %[slot], 2, %[base]\n\t"
+                        "ds_cmpst_rtn_b32 %[old], %[addr], %[empty], %[j]\n\t"
+                        "s_waitcnt lgkmcnt(0)\n\t"
+                        "v_cmp_eq_u32_e64 %[t], %[old], %[empty]\n\t"
+                        "v_cndmask_b32_e64 %[cl], %[cl], 1, %[t]\n\t"
+                        "v_cmp_eq_u32_e32 vcc, %[old], %[j]\n\t"
+                        "s_or_b64 vcc, vcc, %[t]\n\t"
+                        "s_andn2_b64 exec, exec, vcc\n\t"
+                        "s_cbranch_execz .Ldone%=\n\t"
+                        "v_add_u32_e32 %[slot], 1, %[slot]\n\t"
+                        "v_and_b32_e32 %[slot], %[mask], %[slot]\n\t"
+                        "s_branch .Lprobe%=\n"
+                        ".Ldone%=:\n\t"
+                        "s_mov_b64 exec, %[save]\n\t"
+                        "ds_add_u32 %[addr], %[one] offset:%[o1]\n\t"
+                        "v_add_u32_e32 %[old], %[tb2], %[addr]\n\t"
+                        "ds_min_u32 %[old], %[s]\n\t"
+                        "ds_max_u32 %[old], %[smx] offset:%[o1]\n"
+                        : [save] "=&s"(save), [addr] "+v"(addr), [old] "=&v"(old), [t] "=&s"(t), [cl] "+v"(claimed), [slot] "+v"(slot)
+                        : [base] "s"(base), [empty] "v"(empty), [j] "v"(j), [mask] "n"((1u << CTB) - 1u), [tb2] "s"(8u << CTB), [one] "v"(cnt), [s] "v"(s), [smx] "v"(smx),
+                          [o1] "n"(4u << CTB)
+                        : "vcc", "memory");
+                }
+            }
+        } else
         if (valid) {
             asm volatile(
                 "s_mov_b64 %[save], exec\n"
