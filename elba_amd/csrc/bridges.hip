@@ -176,12 +176,12 @@ void stage_cut_bridges(Ctx &c, const elba_bridge_cfg *cfgp)
     const int64_t M = c.tr_M, n0 = c.tr_nnz;
     sg_require_32bit(EV_CUT_BRIDGES, M < 0xffffffffll && n0 < 0xfffffffell);
     elba_bridge_stats st = sg_stats_begin<elba_bridge_stats>(c);
-    if (M == 0 || n0 == 0) { accepted(c.v, EV_CUT_BRIDGES); done(c.v, EV_CUT_BRIDGES); c.brstats = st; return; }      // no entry: no anchor
+    if (M == 0 || n0 == 0) { accepted(c.v, EV_CUT_BRIDGES); done(c.v, EV_CUT_BRIDGES); c.br.stats = st; return; }      // no entry: no anchor
     // every buffer of the launch sequence before the first launch
     sg_reserve(c, M, n0);
-    c.br_flank.reserve((size_t)(n0 + 1) * 4);
+    c.br.flank.reserve((size_t)(n0 + 1) * 4);
     const SgCall w(c);
-    uint32_t *flank = c.br_flank.as<uint32_t>();
+    uint32_t *flank = c.br.flank.as<uint32_t>();
     const int64_t *rows = w.rows[0], *cols = w.cols[0];
     accepted(c.v, EV_CUT_BRIDGES);                              // as in stage_clip_tips: the contigs go, and S is invalid until the counters are back
     sg_start(w);
@@ -196,7 +196,7 @@ void stage_cut_bridges(Ctx &c, const elba_bridge_cfg *cfgp)
     st.anchors = (int64_t)h[BR_ANCHORS]; st.chains = (int64_t)h[BR_CHAINS]; st.long_flanks = (int64_t)h[BR_LONG]; st.bridges = (int64_t)h[BR_BRIDGES];
     st.reads_removed = (int64_t)h[BR_READS];
     sg_stats_end(c, st);
-    c.brstats = st;
+    c.br.stats = st;
 }
 
 }  // namespace elba

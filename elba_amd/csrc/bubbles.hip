@@ -146,12 +146,12 @@ void stage_pop_bubbles(Ctx &c, const elba_bubble_cfg *cfgp)
     sg_require_32bit(EV_POP_BUBBLES, M < 0xffffffffll && n0 < 0xfffffffell);
     elba_bubble_stats st = sg_stats_begin<elba_bubble_stats>(c);
     st.rounds_run = 1;
-    if (M == 0 || n0 == 0) { accepted(c.v, EV_POP_BUBBLES); done(c.v, EV_POP_BUBBLES); c.bbstats = st; return; }      // no entry: no anchor, the one round removes nothing
+    if (M == 0 || n0 == 0) { accepted(c.v, EV_POP_BUBBLES); done(c.v, EV_POP_BUBBLES); c.bb.stats = st; return; }      // no entry: no anchor, the one round removes nothing
     // every buffer of the launch sequence before the first launch
     sg_reserve(c, M, n0);
-    c.bb_end.reserve((size_t)(n0 + 1) * 4); c.bb_len.reserve((size_t)(n0 + 1) * 4);
+    c.bb.end.reserve((size_t)(n0 + 1) * 4); c.bb.len.reserve((size_t)(n0 + 1) * 4);
     const SgCall w(c);
-    uint32_t *arm_end = c.bb_end.as<uint32_t>(), *arm_len = c.bb_len.as<uint32_t>();
+    uint32_t *arm_end = c.bb.end.as<uint32_t>(), *arm_len = c.bb.len.as<uint32_t>();
     accepted(c.v, EV_POP_BUBBLES);                              // as in stage_clip_tips: the contigs go, and S is invalid until the counters are back
     u64 h[SG_ST];
     const int moves = sg_run_rounds(w, cfg.rounds, h, [&](int r, const int64_t *rows, const int64_t *cols) {
@@ -164,7 +164,7 @@ void stage_pop_bubbles(Ctx &c, const elba_bubble_cfg *cfgp)
     st.reads_removed = (int64_t)h[BB_READS];
     st.rounds_run = moves < cfg.rounds ? moves + 1 : cfg.rounds;
     sg_stats_end(c, st);
-    c.bbstats = st;
+    c.bb.stats = st;
 }
 
 }  // namespace elba

@@ -32,12 +32,13 @@ int guarded(elba_ctx *ctx, F &&f)
     }
 }
 
-template <class T>
-T *host_alloc(size_t n)
+// elba_get_stat's counters of one late stage: the names behind the stage's prefix and where each stands in its stats struct
+template <class S> struct StatName { const char *name; int64_t S::*field; };
+template <class S, size_t N>
+int64_t stage_stat(const StatName<S> (&table)[N], const S &st, bool valid, const char *field, const char *name)
 {
-    T *p = static_cast<T *>(malloc((n ? n : 1) * sizeof(T)));
-    if (!p) throw std::bad_alloc();
-    return p;
+    for (const StatName<S> &e : table) if (!strcmp(field, e.name)) return valid ? st.*e.field : 0;
+    throw Error{ELBA_ERR_INVALID_ARG, std::string("get_stat: unknown counter ") + name};
 }
 
 template <class T>
@@ -320,12 +321,8 @@ int elba_export_overlaps(elba_ctx *ctx, elba_overlaps_t *out)
         ELBA_REQUIRE(has(c.v, P_ALN), ELBA_ERR_STATE, "export_overlaps: no alignments (call elba_align_seeds)");
         const int64_t n = c.naln;
         out->n = n;
-        out->rows = host_alloc<int64_t>((size_t)n); out->cols = host_alloc<int64_t>((size_t)n); out->vals = host_alloc<elba_overlap_t>((size_t)n);
-        if (n) {
-            ELBA_HIP(hipMemcpyAsync(out->rows, c.aln_rows.p, (size_t)n * 8, hipMemcpyDeviceToHost, c.stream));
-            ELBA_HIP(hipMemcpyAsync(out->cols, c.aln_cols.p, (size_t)n * 8, hipMemcpyDeviceToHost, c.stream));
-            ELBA_HIP(hipMemcpyAsync(out->vals, c.aln_out.p, (size_t)n * sizeof(elba_overlap_t), hipMemcpyDeviceToHost, c.stream));
-        }
+        out->rows = host_block<int64_t>((size_t)n); out->cols = host_block<int64_t>((size_t)n); out->vals = host_block<elba_overlap_t>((size_t)n);
+        copy_out(c, out->rows, c.aln_rows.p, (size_t)n); copy_out(c, out->cols, c.aln_cols.p, (size_t)n); copy_out(c, out->vals, c.aln_out.p, (size_t)n);
         ELBA_HIP(hipStreamSynchronize(c.stream));
         for (int64_t a = 0; a < n; ++a) { out->rows[a] += c.first_global_id_rows(); out->cols[a] += c.first_global_id_rows(); }
     });
@@ -359,12 +356,8 @@ int elba_export_string_graph(elba_ctx *ctx, elba_overlaps_t *out)
         ELBA_REQUIRE(has(c.v, P_S), ELBA_ERR_STATE, "export_string_graph: no string graph (call elba_transitive_reduction)");
         const int64_t n = c.tr_nnz;
         out->n = n;
-        out->rows = host_alloc<int64_t>((size_t)n); out->cols = host_alloc<int64_t>((size_t)n); out->vals = host_alloc<elba_overlap_t>((size_t)n);
-        if (n) {
-            ELBA_HIP(hipMemcpyAsync(out->rows, c.tr_out_rows.p, (size_t)n * 8, hipMemcpyDeviceToHost, c.stream));
-            ELBA_HIP(hipMemcpyAsync(out->cols, c.tr_out_cols.p, (size_t)n * 8, hipMemcpyDeviceToHost, c.stream));
-            ELBA_HIP(hipMemcpyAsync(out->vals, c.tr_out_vals.p, (size_t)n * sizeof(elba_overlap_t), hipMemcpyDeviceToHost, c.stream));
-        }
+        out->rows = host_block<int64_t>((size_t)n); out->cols = host_block<int64_t>((size_t)n); out->vals = host_block<elba_overlap_t>((size_t)n);
+        copy_out(c, out->rows, c.tr_out_rows.p, (size_t)n); copy_out(c, out->cols, c.tr_out_cols.p, (size_t)n); copy_out(c, out->vals, c.tr_out_vals.p, (size_t)n);
         ELBA_HIP(hipStreamSynchronize(c.stream));
         for (int64_t a = 0; a < n; ++a) { out->rows[a] += c.tr_id_base; out->cols[a] += c.tr_id_base; }
     });
@@ -384,7 +377,7 @@ int elba_clip_tips(elba_ctx *ctx, const elba_tip_cfg *cfg, elba_tip_stats *stats
 {
     return guarded(ctx, [&](Ctx &c) {
         stage_clip_tips(c, cfg);
-        if (stats) *stats = c.tpstats;
+        if (stats) *stats = c.tp.stats;
     });
 }
 
@@ -392,7 +385,7 @@ int elba_pop_bubbles(elba_ctx *ctx, const elba_bubble_cfg *cfg, elba_bubble_stat
 {
     return guarded(ctx, [&](Ctx &c) {
         stage_pop_bubbles(c, cfg);
-        if (stats) *stats = c.bbstats;
+        if (stats) *stats = c.bb.stats;
     });
 }
 
@@ -400,7 +393,7 @@ int elba_cut_weak_overlaps(elba_ctx *ctx, const elba_weak_cfg *cfg, elba_weak_st
 {
     return guarded(ctx, [&](Ctx &c) {
         stage_cut_weak_overlaps(c, cfg);
-        if (stats) *stats = c.wkstats;
+        if (stats) *stats = c.wk.stats;
     });
 }
 
@@ -408,7 +401,7 @@ int elba_cut_bridges(elba_ctx *ctx, const elba_bridge_cfg *cfg, elba_bridge_stat
 {
     return guarded(ctx, [&](Ctx &c) {
         stage_cut_bridges(c, cfg);
-        if (stats) *stats = c.brstats;
+        if (stats) *stats = c.br.stats;
     });
 }
 
@@ -416,7 +409,7 @@ int elba_resolve_stars(elba_ctx *ctx, const elba_star_cfg *cfg, elba_star_stats 
 {
     return guarded(ctx, [&](Ctx &c) {
         stage_resolve_stars(c, cfg);
-        if (stats) *stats = c.srstats;
+        if (stats) *stats = c.sr.stats;
     });
 }
 
@@ -424,7 +417,7 @@ int elba_generate_contigs(elba_ctx *ctx, elba_contig_stats *stats)
 {
     return guarded(ctx, [&](Ctx &c) {
         stage_generate_contigs(c, 0);
-        if (stats) *stats = c.cstats;
+        if (stats) *stats = c.cg.stats;
     });
 }
 
@@ -432,7 +425,7 @@ int elba_generate_contigs_ex(elba_ctx *ctx, const elba_contig_cfg *cfg, elba_con
 {
     return guarded(ctx, [&](Ctx &c) {
         stage_generate_contigs_ex(c, cfg);
-        if (stats) *stats = c.cstats;
+        if (stats) *stats = c.cg.stats;
     });
 }
 
@@ -442,22 +435,15 @@ int elba_export_contigs(elba_ctx *ctx, elba_contigs_t *out)
         ELBA_REQUIRE(out, ELBA_ERR_INVALID_ARG, "export_contigs: null output");
         memset(out, 0, sizeof(*out));
         ELBA_REQUIRE(has(c.v, P_S, P_CONTIGS), ELBA_ERR_STATE, "export_contigs: no contigs of the current string graph (call elba_generate_contigs)");
-        const int64_t n = c.cg_n, E = c.cg_E, b = c.cg_bases;
+        const int64_t n = c.cg.n, E = c.cg.E, b = c.cg.bases;
         elba_contigs_t o{};
         o.n = n;
-        o.seq_off = host_alloc<int64_t>((size_t)n + 1); o.seq = host_alloc<char>((size_t)b); o.chain_off = host_alloc<int64_t>((size_t)n + 1);
-        o.chain_read = host_alloc<int64_t>((size_t)E); o.chain_prefix = host_alloc<int32_t>((size_t)E); o.chain_strand = host_alloc<uint8_t>((size_t)E);
+        o.seq_off = host_block<int64_t>((size_t)n + 1); o.seq = host_block<char>((size_t)b); o.chain_off = host_block<int64_t>((size_t)n + 1);
+        o.chain_read = host_block<int64_t>((size_t)E); o.chain_prefix = host_block<int32_t>((size_t)E); o.chain_strand = host_block<uint8_t>((size_t)E);
         *out = o;                                                   // (allocated before any copy: elba_free_contigs releases them if a copy fails)
-        hipStream_t s = c.stream;
-        ELBA_HIP(hipMemcpyAsync(o.seq_off, c.cg_soff.p, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, s));
-        ELBA_HIP(hipMemcpyAsync(o.chain_off, c.cg_coff.p, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, s));
-        if (b) ELBA_HIP(hipMemcpyAsync(o.seq, c.cg_seq.p, (size_t)b, hipMemcpyDeviceToHost, s));
-        if (E) {
-            ELBA_HIP(hipMemcpyAsync(o.chain_read, c.cg_eread.p, (size_t)E * 8, hipMemcpyDeviceToHost, s));
-            ELBA_HIP(hipMemcpyAsync(o.chain_prefix, c.cg_epre.p, (size_t)E * 4, hipMemcpyDeviceToHost, s));
-            ELBA_HIP(hipMemcpyAsync(o.chain_strand, c.cg_estr.p, (size_t)E, hipMemcpyDeviceToHost, s));
-        }
-        ELBA_HIP(hipStreamSynchronize(s));
+        copy_out(c, o.seq_off, c.cg.soff.p, (size_t)n + 1); copy_out(c, o.chain_off, c.cg.coff.p, (size_t)n + 1); copy_out(c, o.seq, c.cg.seq.p, (size_t)b);
+        copy_out(c, o.chain_read, c.cg.eread.p, (size_t)E); copy_out(c, o.chain_prefix, c.cg.epre.p, (size_t)E); copy_out(c, o.chain_strand, c.cg.estr.p, (size_t)E);
+        ELBA_HIP(hipStreamSynchronize(c.stream));
     });
 }
 
@@ -473,7 +459,7 @@ int elba_export_read_contigs(elba_ctx *ctx, int64_t *contig_of_read, int64_t nre
     return guarded(ctx, [&](Ctx &c) {
         ELBA_REQUIRE(has(c.v, P_S, P_CONTIGS), ELBA_ERR_STATE, "export_read_contigs: no contigs of the current string graph (call elba_generate_contigs)");
         ELBA_REQUIRE(nreads == c.tr_M && (contig_of_read || nreads == 0), ELBA_ERR_INVALID_ARG, "export_read_contigs: need one entry per read of the graph");
-        const std::vector<int32_t> h = download<int32_t>(c, c.cg_cid.p, (size_t)nreads);
+        const std::vector<int32_t> h = download<int32_t>(c, c.cg.cid.p, (size_t)nreads);
         for (int64_t v = 0; v < nreads; ++v) contig_of_read[v] = h[(size_t)v];
     });
 }
@@ -484,7 +470,7 @@ int elba_export_assembly_links(elba_ctx *ctx, elba_links_t *out, elba_graph_stat
         ELBA_REQUIRE(out, ELBA_ERR_INVALID_ARG, "export_assembly_links: null output");
         memset(out, 0, sizeof(*out));
         stage_export_assembly_links(c, out);
-        if (stats) *stats = c.gstats;
+        if (stats) *stats = c.gl.stats;
     });
 }
 
@@ -501,7 +487,7 @@ int elba_place_reads(elba_ctx *ctx, const elba_place_cfg *cfg, elba_placements_t
     const int rc = guarded(ctx, [&](Ctx &c) {
         ELBA_REQUIRE(out, ELBA_ERR_INVALID_ARG, "place_reads: null output");
         stage_place_reads(c, cfg, out);
-        if (stats) *stats = c.plstats;
+        if (stats) *stats = c.pl.stats;
     });
     if (rc != ELBA_OK && ctx && out) elba_free_placements(out);      // (a copy that failed behind the allocations)
     return rc;
@@ -513,7 +499,7 @@ int elba_polish_contigs(elba_ctx *ctx, const elba_polish_cfg *cfg, elba_polished
     const int rc = guarded(ctx, [&](Ctx &c) {
         ELBA_REQUIRE(out, ELBA_ERR_INVALID_ARG, "polish_contigs: null output");
         stage_polish_contigs(c, cfg, out);
-        if (stats) *stats = c.postats;
+        if (stats) *stats = c.po.stats;
     });
     if (rc != ELBA_OK && ctx && out) elba_free_polished(out);      // (a copy that failed behind the allocations)
     return rc;
@@ -537,8 +523,8 @@ int elba_export_contig_kinds(elba_ctx *ctx, uint8_t *kind, int64_t ncontigs)
 {
     return guarded(ctx, [&](Ctx &c) {
         ELBA_REQUIRE(has(c.v, P_S, P_CONTIGS), ELBA_ERR_STATE, "export_contig_kinds: no contigs of the current string graph (call elba_generate_contigs)");
-        ELBA_REQUIRE(ncontigs == c.cg_n && (kind || ncontigs == 0), ELBA_ERR_INVALID_ARG, "export_contig_kinds: need one byte per contig");
-        if (ncontigs) ELBA_HIP(hipMemcpyAsync(kind, c.cg_kind.p, (size_t)ncontigs, hipMemcpyDeviceToHost, c.stream));
+        ELBA_REQUIRE(ncontigs == c.cg.n && (kind || ncontigs == 0), ELBA_ERR_INVALID_ARG, "export_contig_kinds: need one byte per contig");
+        if (ncontigs) ELBA_HIP(hipMemcpyAsync(kind, c.cg.kind.p, (size_t)ncontigs, hipMemcpyDeviceToHost, c.stream));
         ELBA_HIP(hipStreamSynchronize(c.stream));
     });
 }
@@ -547,7 +533,7 @@ int elba_read_pileup(elba_ctx *ctx, const elba_pileup_cfg *cfg, elba_pileup_stat
 {
     return guarded(ctx, [&](Ctx &c) {
         stage_read_pileup(c, cfg);
-        if (stats) *stats = c.pustats;
+        if (stats) *stats = c.pu.stats;
     });
 }
 
@@ -557,24 +543,16 @@ int elba_export_pileup(elba_ctx *ctx, elba_pileup_t *out)
         ELBA_REQUIRE(out, ELBA_ERR_INVALID_ARG, "export_pileup: null output");
         memset(out, 0, sizeof(*out));
         ELBA_REQUIRE(has(c.v, P_PILEUP), ELBA_ERR_STATE, "export_pileup: no pileup of the current overlaps (call elba_read_pileup)");
-        const int64_t n = c.pu_M, S = c.pu_nseg;
+        const int64_t n = c.pu.M, S = c.pu.nseg;
         elba_pileup_t o{};
         o.n = n; o.nseg = S;
-        o.seg_off = host_alloc<int64_t>((size_t)n + 1); o.seg_start = host_alloc<int32_t>((size_t)S); o.seg_depth = host_alloc<int32_t>((size_t)S);
-        o.trim_beg = host_alloc<int32_t>((size_t)n); o.trim_end = host_alloc<int32_t>((size_t)n); o.flags = host_alloc<uint8_t>((size_t)n);
+        o.seg_off = host_block<int64_t>((size_t)n + 1); o.seg_start = host_block<int32_t>((size_t)S); o.seg_depth = host_block<int32_t>((size_t)S);
+        o.trim_beg = host_block<int32_t>((size_t)n); o.trim_end = host_block<int32_t>((size_t)n); o.flags = host_block<uint8_t>((size_t)n);
         *out = o;                                                   // (allocated before any copy: elba_free_pileup releases them if a copy fails)
-        hipStream_t s = c.stream;
-        ELBA_HIP(hipMemcpyAsync(o.seg_off, c.pu_seg_off.p, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, s));
-        if (S) {
-            ELBA_HIP(hipMemcpyAsync(o.seg_start, c.pu_seg_start.p, (size_t)S * 4, hipMemcpyDeviceToHost, s));
-            ELBA_HIP(hipMemcpyAsync(o.seg_depth, c.pu_seg_depth.p, (size_t)S * 4, hipMemcpyDeviceToHost, s));
-        }
+        copy_out(c, o.seg_off, c.pu.depth.seg_off.p, (size_t)n + 1); copy_out(c, o.seg_start, c.pu.depth.seg_start.p, (size_t)S); copy_out(c, o.seg_depth, c.pu.depth.seg_depth.p, (size_t)S);
         std::vector<int32_t> trim((size_t)(2 * n));
-        if (n) {
-            ELBA_HIP(hipMemcpyAsync(trim.data(), c.pu_trim.p, (size_t)n * 8, hipMemcpyDeviceToHost, s));
-            ELBA_HIP(hipMemcpyAsync(o.flags, c.pu_flags.p, (size_t)n, hipMemcpyDeviceToHost, s));
-        }
-        ELBA_HIP(hipStreamSynchronize(s));
+        copy_out(c, trim.data(), c.pu.trim.p, (size_t)(2 * n)); copy_out(c, o.flags, c.pu.flags.p, (size_t)n);
+        ELBA_HIP(hipStreamSynchronize(c.stream));
         for (int64_t v = 0; v < n; ++v) { o.trim_beg[v] = trim[(size_t)(2 * v)]; o.trim_end[v] = trim[(size_t)(2 * v + 1)]; }
     });
 }
@@ -595,7 +573,7 @@ int elba_trim_reads(elba_ctx *ctx, const elba_trim_cfg *cfg, elba_trim_stats *st
 {
     return guarded(ctx, [&](Ctx &c) {
         stage_trim_reads(c, cfg);
-        if (stats) *stats = c.tmstats;
+        if (stats) *stats = c.tm.stats;
     });
 }
 
@@ -605,18 +583,13 @@ int elba_export_trim_map(elba_ctx *ctx, elba_trim_map_t *out)
         ELBA_REQUIRE(out, ELBA_ERR_INVALID_ARG, "export_trim_map: null output");
         memset(out, 0, sizeof(*out));
         ELBA_REQUIRE(has(c.v, P_TRIM), ELBA_ERR_STATE, "export_trim_map: no trimmed reads (call elba_trim_reads)");
-        const int64_t n = c.tm_n;
+        const int64_t n = c.tm.n;
         elba_trim_map_t o{};
         o.n = n;
-        o.src_read = host_alloc<int64_t>((size_t)n); o.src_beg = host_alloc<int32_t>((size_t)n); o.src_end = host_alloc<int32_t>((size_t)n);
+        o.src_read = host_block<int64_t>((size_t)n); o.src_beg = host_block<int32_t>((size_t)n); o.src_end = host_block<int32_t>((size_t)n);
         *out = o;                                                   // (allocated before any copy: elba_free_trim_map releases them if a copy fails)
-        hipStream_t s = c.stream;
-        if (n) {
-            ELBA_HIP(hipMemcpyAsync(o.src_read, c.tm_src.p, (size_t)n * 8, hipMemcpyDeviceToHost, s));
-            ELBA_HIP(hipMemcpyAsync(o.src_beg, c.tm_beg.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-            ELBA_HIP(hipMemcpyAsync(o.src_end, c.tm_end.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-        }
-        ELBA_HIP(hipStreamSynchronize(s));
+        copy_out(c, o.src_read, c.tm.src.p, (size_t)n); copy_out(c, o.src_beg, c.tm.beg.p, (size_t)n); copy_out(c, o.src_end, c.tm.end.p, (size_t)n);
+        ELBA_HIP(hipStreamSynchronize(c.stream));
     });
 }
 
@@ -632,7 +605,7 @@ int elba_get_trimmed_reads_device(elba_ctx *ctx, const void **d_packed, int64_t 
     return guarded(ctx, [&](Ctx &c) {
         ELBA_REQUIRE(d_packed && packed_bytes && d_byte_off && d_len && n, ELBA_ERR_INVALID_ARG, "get_trimmed_reads_device: null output");
         ELBA_REQUIRE(has(c.v, P_TRIM), ELBA_ERR_STATE, "get_trimmed_reads_device: no trimmed reads (call elba_trim_reads)");
-        *d_packed = c.tm_packed.p; *packed_bytes = c.tm_packed_bytes; *d_byte_off = c.tm_off.p; *d_len = c.tm_len.p; *n = c.tm_n;
+        *d_packed = c.tm.packed.p; *packed_bytes = c.tm.packed_bytes; *d_byte_off = c.tm.off.p; *d_len = c.tm.len.p; *n = c.tm.n;
     });
 }
 
@@ -652,12 +625,12 @@ int elba_export_csr(elba_ctx *ctx, int64_t row_lo, int64_t row_hi, elba_csr_t *o
         const int64_t e0 = rp.front(), e1 = rp.back(), n = e1 - e0;
         auto col = download<uint32_t>(c, c.b_col.as<uint32_t>() + e0, (size_t)n);
         out->nrows = row_hi - row_lo; out->ncols = c.M; out->nnz = n;
-        out->rowptr = host_alloc<int64_t>((size_t)(row_hi - row_lo + 1));
-        out->col = host_alloc<int64_t>((size_t)n);
-        out->val = host_alloc<elba_seed_t>((size_t)n);
+        out->rowptr = host_block<int64_t>((size_t)(row_hi - row_lo + 1));
+        out->col = host_block<int64_t>((size_t)n);
+        out->val = host_block<elba_seed_t>((size_t)n);
         for (size_t i = 0; i < rp.size(); ++i) out->rowptr[i] = rp[i] - e0;
         for (int64_t i = 0; i < n; ++i) out->col[i] = col[(size_t)i];
-        if (n) ELBA_HIP(hipMemcpyAsync(out->val, c.b_val.as<elba_seed_t>() + e0, (size_t)n * sizeof(elba_seed_t), hipMemcpyDeviceToHost, c.stream));
+        copy_out(c, out->val, c.b_val.as<elba_seed_t>() + e0, (size_t)n);
         ELBA_HIP(hipStreamSynchronize(c.stream));
     });
 }
@@ -688,10 +661,10 @@ int elba_export_dcsc(elba_ctx *ctx, int64_t row_lo, int64_t row_hi, int64_t col_
         int64_t nzc = 0;
         for (int64_t j = 0; j < ncols; ++j) if (cnt[(size_t)j]) ++nzc;
         out->nrows = row_hi - row_lo; out->ncols = ncols; out->nnz = total; out->nzc = nzc;
-        out->jc = host_alloc<int64_t>((size_t)nzc);
-        out->cp = host_alloc<int64_t>((size_t)nzc + 1);
-        out->ir = host_alloc<int64_t>((size_t)total);
-        out->numx = host_alloc<elba_seed_t>((size_t)total);
+        out->jc = host_block<int64_t>((size_t)nzc);
+        out->cp = host_block<int64_t>((size_t)nzc + 1);
+        out->ir = host_block<int64_t>((size_t)total);
+        out->numx = host_block<elba_seed_t>((size_t)total);
         std::vector<int64_t> start((size_t)ncols + 1, 0);
         int64_t run = 0, ci = 0;
         for (int64_t j = 0; j < ncols; ++j) {
@@ -727,9 +700,9 @@ int elba_export_kmer_matrix(elba_ctx *ctx, elba_kmer_matrix_t *out)
         auto csr = download<uint64_t>(c, c.a_csr.p, Z);
         auto csc = download<uint64_t>(c, c.a_csc.p, Z);
         out->nrows = c.M; out->ncols = c.N; out->nnz = c.Z;
-        out->colptr = host_alloc<int64_t>(N + 1); out->rowptr = host_alloc<int64_t>(M + 1);
-        out->csc_row = host_alloc<int64_t>(Z); out->csc_val = host_alloc<uint32_t>(Z);
-        out->csr_col = host_alloc<int64_t>(Z); out->csr_val = host_alloc<uint32_t>(Z);
+        out->colptr = host_block<int64_t>(N + 1); out->rowptr = host_block<int64_t>(M + 1);
+        out->csc_row = host_block<int64_t>(Z); out->csc_val = host_block<uint32_t>(Z);
+        out->csr_col = host_block<int64_t>(Z); out->csr_val = host_block<uint32_t>(Z);
         for (size_t i = 0; i <= N; ++i) out->colptr[i] = cp[i];
         for (size_t i = 0; i <= M; ++i) out->rowptr[i] = rp[i];
         for (size_t z = 0; z < Z; ++z) {
@@ -744,15 +717,15 @@ int elba_export_kmer_matrix(elba_ctx *ctx, elba_kmer_matrix_t *out)
                 for (size_t z = cp[k]; z < cp[k + 1]; ++z) { const size_t at = fill[(size_t)(csc[z] >> 32)]++; out->csr_col[at] = (int64_t)k; out->csr_val[at] = (uint32_t)csc[z]; }
         }
         if (c.A_has_kmers) {
-            out->kmers = host_alloc<uint64_t>(N);
-            if (N) ELBA_HIP(hipMemcpyAsync(out->kmers, c.rel_kmers.p, N * 8, hipMemcpyDeviceToHost, c.stream));
+            out->kmers = host_block<uint64_t>(N);
+            copy_out(c, out->kmers, c.rel_kmers.p, N);
             if (c.cfg.k > 32) {
-                out->kmers_lo = host_alloc<uint64_t>(N);
-                if (N) ELBA_HIP(hipMemcpyAsync(out->kmers_lo, c.rel_kmers_lo.p, N * 8, hipMemcpyDeviceToHost, c.stream));
+                out->kmers_lo = host_block<uint64_t>(N);
+                copy_out(c, out->kmers_lo, c.rel_kmers_lo.p, N);
             }
             if (c.cfg.k > 64) {
-                out->kmers_lo2 = host_alloc<uint64_t>(N);
-                if (N) ELBA_HIP(hipMemcpyAsync(out->kmers_lo2, c.rel_kmers_lo2.p, N * 8, hipMemcpyDeviceToHost, c.stream));
+                out->kmers_lo2 = host_block<uint64_t>(N);
+                copy_out(c, out->kmers_lo2, c.rel_kmers_lo2.p, N);
             }
             ELBA_HIP(hipStreamSynchronize(c.stream));
         }
@@ -830,24 +803,10 @@ int elba_release_workspace(elba_ctx *ctx)
         ELBA_HIP(hipStreamSynchronize(c.stream));
         c.ws_a.release(); c.ws_b.release(); c.ws_c.release(); c.ws_d.release(); c.ws_e.release(); c.ws_f.release(); c.ws_g.release(); c.ws_h.release(); c.ws_sort.release();
         c.csr_words.release(); c.kid_of_entry.release();
-        c.cg_ptr.release(); c.cg_slot.release(); c.cg_kdeg.release(); c.cg_term.release(); c.cg_vinfo.release(); c.cg_ctr.release();   // contig scratch (the results stay)
-        c.cg_flag.release(); c.cg_cidx.release(); c.cg_nel.release(); c.cg_eoff.release();
-        c.gl_ptr.release(); c.gl_bits.release(); c.gl_cnt.release(); c.gl_off.release(); c.gl_ctr.release(); c.gl_part.release(); c.gl_out.release();          // assembly-link scratch
-        c.pl_cstart.release(); c.pl_cstrand.release(); c.pl_best.release(); c.pl_rec.release(); c.pl_clen.release(); c.pl_cred.release(); c.pl_ctr.release();    // placement scratch
-        c.pl_k0.release(); c.pl_k1.release(); c.pl_eptr.release(); c.pl_head.release(); c.pl_hidx.release(); c.pl_delta.release(); c.pl_dsum.release(); c.pl_gstart.release();
-        c.pl_tok.release(); c.pl_tpos.release(); c.pl_seg_off.release(); c.pl_seg_start.release(); c.pl_seg_depth.release();
-        c.po_plan.release(); c.po_rec.release(); c.po_toff.release(); c.po_trace.release(); c.po_col.release(); c.po_gap.release(); c.po_cnt.release();         // polishing scratch
-        c.po_emit.release(); c.po_off.release(); c.po_cstat.release(); c.po_seq.release(); c.po_seqoff.release(); c.po_ctr.release();
-        for (int b = 0; b < 2; ++b) { c.cg_far[b].release(); c.cg_rank[b].release(); c.cg_mn[b].release(); c.cg_cfar[b].release(); c.cg_crank[b].release(); }
-        c.pu_k0.release(); c.pu_k1.release(); c.pu_eptr.release(); c.pu_head.release(); c.pu_hidx.release(); c.pu_delta.release();   // pileup scratch (the results stay)
-        c.pu_dsum.release(); c.pu_gstart.release(); c.pu_tok.release(); c.pu_tpos.release(); c.pu_sel.release(); c.pu_rows.release(); c.pu_cols.release(); c.pu_vals.release();
-        c.tm_cnt.release(); c.tm_bytes.release(); c.tm_first.release(); c.tm_boff.release(); c.tm_srcb.release();   // trim scratch (the trimmed reads and their map stay)
-        c.sg.release();                                                                                                                    // the cleaning calls' shared scratch and the spare buffer of S (S itself stays)
-        c.tp_ntips.release(); c.tp_anchor.release();                                                                                       // tip scratch
-        c.bb_end.release(); c.bb_len.release();                                                                                            // bubble scratch
-        c.wk_best.release(); c.wk_cnt.release(); c.wk_nweak.release(); c.wk_after.release();                                                                     // weak-overlap scratch
-        c.br_flank.release();                                                                                                              // bridge scratch
-        c.sr_word.release();                                                                                                               // star scratch (tr_ptr / tr_sym, which it reads, stay)
+        // the late stages: what each keeps is its release_scratch()'s decision (common.hpp, the stage structs of Ctx)
+        c.cg.release_scratch(); c.gl.release_scratch(); c.pu.release_scratch(); c.pl.release_scratch(); c.po.release_scratch(); c.tm.release_scratch();
+        c.sg.release();      // the cleaning calls' shared scratch and the spare buffer of S (S itself stays)
+        c.tp.release_scratch(); c.bb.release_scratch(); c.wk.release_scratch(); c.br.release_scratch(); c.sr.release_scratch();
         if (has(c.v, P_COUNTS)) { c.pre_ready = false; c.pre_consumed = true; }    // (the CSR sort keys / column ids of the entries are gone: create_kmer_matrix rebuilds them from the column pointers)
     });
 }
@@ -892,49 +851,33 @@ int elba_get_stat(elba_ctx *ctx, const char *name, int64_t *value)
         else if (!strcmp(name, "text_scan_span")) *value = scan_block_span();      // and the elements beyond which its scans recurse (tests size their inputs from them)
         else if (!strcmp(name, "padded_columns")) *value = has(c.v, P_A) && c.use_ell ? 1 : 0;
         else if (!strcmp(name, "gather_slots")) *value = has(c.v, P_A) && c.use_ell ? c.ell_nslots : 0;
-        else if (!strcmp(name, "contig_count")) *value = has(c.v, P_S, P_CONTIGS) ? c.cstats.contigs : 0;          // the last elba_generate_contigs (0: none valid — the condition of the contig exports)
-        else if (!strcmp(name, "contig_cycles")) *value = has(c.v, P_S, P_CONTIGS) ? c.cstats.cycles : 0;
-        else if (!strcmp(name, "contig_circular")) *value = has(c.v, P_S, P_CONTIGS) ? c.cg_circular : 0;
-        else if (!strcmp(name, "contig_singletons")) *value = has(c.v, P_S, P_CONTIGS) ? c.cg_singletons : 0;
-        else if (!strcmp(name, "contig_reads")) *value = has(c.v, P_S, P_CONTIGS) ? c.cstats.contig_reads : 0;
-        else if (!strcmp(name, "contig_bases")) *value = has(c.v, P_S, P_CONTIGS) ? c.cstats.bases : 0;
-        else if (!strcmp(name, "contig_branches")) *value = has(c.v, P_S, P_CONTIGS) ? c.cstats.branches : 0;
-        else if (!strncmp(name, "graph_", 6)) {                    // the last elba_export_assembly_links on the contigs that are valid now
-            const bool ok = has(c.v, P_S, P_CONTIGS) && c.gl_for == c.cg_serial;
-            const elba_graph_stats &g = c.gstats;
-            const char *f = name + 6;
-            int64_t x;
-            if (!strcmp(f, "segments")) x = g.segments; else if (!strcmp(f, "candidates")) x = g.candidates; else if (!strcmp(f, "links")) x = g.links;
-            else if (!strcmp(f, "closures")) x = g.closures; else if (!strcmp(f, "twisted")) x = g.twisted; else if (!strcmp(f, "unplaced")) x = g.unplaced;
-            else if (!strcmp(f, "clamped")) x = g.clamped; else if (!strcmp(f, "asymmetric")) x = g.asymmetric;
-            else throw Error{ELBA_ERR_INVALID_ARG, std::string("get_stat: unknown counter ") + name};
-            *value = ok ? x : 0;
+        else if (!strcmp(name, "contig_count")) *value = has(c.v, P_S, P_CONTIGS) ? c.cg.stats.contigs : 0;          // the last elba_generate_contigs (0: none valid — the condition of the contig exports)
+        else if (!strcmp(name, "contig_cycles")) *value = has(c.v, P_S, P_CONTIGS) ? c.cg.stats.cycles : 0;
+        else if (!strcmp(name, "contig_circular")) *value = has(c.v, P_S, P_CONTIGS) ? c.cg.circular : 0;
+        else if (!strcmp(name, "contig_singletons")) *value = has(c.v, P_S, P_CONTIGS) ? c.cg.singletons : 0;
+        else if (!strcmp(name, "contig_reads")) *value = has(c.v, P_S, P_CONTIGS) ? c.cg.stats.contig_reads : 0;
+        else if (!strcmp(name, "contig_bases")) *value = has(c.v, P_S, P_CONTIGS) ? c.cg.stats.bases : 0;
+        else if (!strcmp(name, "contig_branches")) *value = has(c.v, P_S, P_CONTIGS) ? c.cg.stats.branches : 0;
+        // the last elba_export_assembly_links / elba_place_reads / elba_polish_contigs on the contigs that are valid now
+        else if (!strncmp(name, "graph_", 6)) {
+            using S = elba_graph_stats;
+            static const StatName<S> table[] = {{"segments", &S::segments}, {"candidates", &S::candidates}, {"links", &S::links}, {"closures", &S::closures},
+                                                {"twisted", &S::twisted}, {"unplaced", &S::unplaced}, {"clamped", &S::clamped}, {"asymmetric", &S::asymmetric}};
+            *value = stage_stat(table, c.gl.stats, has(c.v, P_S, P_CONTIGS) && c.gl.for_cg == c.cg.serial, name + 6, name);
         }
-        else if (!strncmp(name, "place_", 6)) {                    // the last elba_place_reads on the contigs that are valid now
-            const bool ok = has(c.v, P_S, P_CONTIGS) && c.pl_for == c.cg_serial && c.pl_for != 0;
-            const elba_place_stats &g = c.plstats;
-            const char *f = name + 6;
-            int64_t x;
-            if (!strcmp(f, "chain")) x = g.chain; else if (!strcmp(f, "anchored")) x = g.anchored; else if (!strcmp(f, "unanchored")) x = g.unanchored;
-            else if (!strcmp(f, "skipped")) x = g.skipped; else if (!strcmp(f, "candidates")) x = g.candidates; else if (!strcmp(f, "clipped")) x = g.clipped;
-            else if (!strcmp(f, "outside")) x = g.outside; else if (!strcmp(f, "wrapped")) x = g.wrapped; else if (!strcmp(f, "segments")) x = g.segments;
-            else if (!strcmp(f, "max_depth")) x = g.max_depth;
-            else throw Error{ELBA_ERR_INVALID_ARG, std::string("get_stat: unknown counter ") + name};
-            *value = ok ? x : 0;
+        else if (!strncmp(name, "place_", 6)) {
+            using S = elba_place_stats;
+            static const StatName<S> table[] = {{"chain", &S::chain}, {"anchored", &S::anchored}, {"unanchored", &S::unanchored}, {"skipped", &S::skipped}, {"candidates", &S::candidates},
+                                                {"clipped", &S::clipped}, {"outside", &S::outside}, {"wrapped", &S::wrapped}, {"segments", &S::segments}, {"max_depth", &S::max_depth}};
+            *value = stage_stat(table, c.pl.stats, has(c.v, P_S, P_CONTIGS) && c.pl.for_cg == c.cg.serial && c.pl.for_cg != 0, name + 6, name);
         }
-        else if (!strncmp(name, "polish_", 7)) {                   // the last elba_polish_contigs on the contigs that are valid now
-            const bool ok = has(c.v, P_S, P_CONTIGS) && c.po_for == c.cg_serial && c.po_for != 0;
-            const elba_polish_stats &g = c.postats;
-            const char *f = name + 7;
-            int64_t x;
-            if (!strcmp(f, "voted")) x = g.voted; else if (!strcmp(f, "rejected")) x = g.rejected; else if (!strcmp(f, "outside")) x = g.outside;
-            else if (!strcmp(f, "low_depth_columns")) x = g.low_depth_columns; else if (!strcmp(f, "bases_before")) x = g.bases_before;
-            else if (!strcmp(f, "bases_after")) x = g.bases_after; else if (!strcmp(f, "sum_dist")) x = g.sum_dist; else if (!strcmp(f, "cells")) x = g.cells;
-            else if (!strcmp(f, "batches")) x = g.batches;
-            else throw Error{ELBA_ERR_INVALID_ARG, std::string("get_stat: unknown counter ") + name};
-            *value = ok ? x : 0;
+        else if (!strncmp(name, "polish_", 7)) {
+            using S = elba_polish_stats;
+            static const StatName<S> table[] = {{"voted", &S::voted}, {"rejected", &S::rejected}, {"outside", &S::outside}, {"low_depth_columns", &S::low_depth_columns},
+                                                {"bases_before", &S::bases_before}, {"bases_after", &S::bases_after}, {"sum_dist", &S::sum_dist}, {"cells", &S::cells}, {"batches", &S::batches}};
+            *value = stage_stat(table, c.po.stats, has(c.v, P_S, P_CONTIGS) && c.po.for_cg == c.cg.serial && c.po.for_cg != 0, name + 7, name);
         }
-        else if (!strcmp(name, "contig_rank_us")) *value = has(c.v, P_S, P_CONTIGS) ? (int64_t)(c.cstats.ms_rank * 1000.0f) : -1;
+        else if (!strcmp(name, "contig_rank_us")) *value = has(c.v, P_S, P_CONTIGS) ? (int64_t)(c.cg.stats.ms_rank * 1000.0f) : -1;
         else if (!strcmp(name, "resident_bytes_A")) {
             int64_t b = 0;
             if (has(c.v, P_A)) {

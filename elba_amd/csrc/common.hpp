@@ -6,6 +6,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
+#include <new>
 #include <string>
 #include <vector>
 #include "../../include/elba_amd.h"
@@ -200,6 +201,15 @@ struct RowWindow { int64_t lo, hi; int64_t rows() const { return hi - lo; } };
 struct alignas(16) SymEntry { uint32_t col; int32_t suffix, suffixT; uint32_t meta; };
 static_assert(sizeof(SymEntry) == 16, "tr.hip and stars.hip read 16-byte entries");
 
+// The buffer set of the pileup's keys-to-segments sequence (pileup.hip: depth_segments), owned by each stage that runs it (Ctx::pu, and Ctx::pl
+// so that place.hip runs the same launches on buffers of its own).  seg_off / seg_start / seg_depth are what the sequence leaves, the rest is scratch
+struct DepthBufs {
+    DevBuf k0, k1, eptr, head, hidx, delta, dsum, gstart, tok, tpos, seg_off, seg_start, seg_depth;
+    void reserve(int64_t max_keys, int64_t G);      // for at most max_keys endpoints of G groups (pileup.hip)
+    void release_scratch() { for (DevBuf *b : {&k0, &k1, &eptr, &head, &hidx, &delta, &dsum, &gstart, &tok, &tpos}) b->release(); }
+    void release() { release_scratch(); seg_off.release(); seg_start.release(); seg_depth.release(); }
+};
+
 struct Ctx {
     elba_cfg cfg{};
     Options opt;
@@ -316,53 +326,79 @@ struct Ctx {
     int64_t tr_sym_M = 0, tr_sym_n = 0;     // what tr_ptr / tr_sym describe since the last reduction that succeeded: reads, symmetrised entries (0: tr_ptr was not written)
     elba_string_stats sstats{};
 
-    // contigs (contig.hip): results (cid, eread, epre, estr, eboff, soff, coff, seq, kind) survive elba_release_workspace, the rest is scratch
-    int64_t cg_n = 0, cg_E = 0, cg_bases = 0, cg_circular = 0, cg_singletons = 0;
-    DevBuf cg_ptr, cg_slot, cg_kdeg, cg_far[2], cg_rank[2], cg_mn[2], cg_term, cg_vinfo, cg_flag, cg_cidx, cg_nel, cg_eoff, cg_ctr;
-    DevBuf cg_cid, cg_eread, cg_epre, cg_estr, cg_eboff, cg_soff, cg_coff, cg_seq, cg_kind;
-    DevBuf cg_cfar[2], cg_crank[2];          // scratch of the second ranking pass (ELBA_CONTIG_CIRCULAR)
-    EventTimer cg_t_total, cg_t_rank;
-    elba_contig_stats cstats{};
+    // contigs (contig.hip): results (cid, eread, epre, estr, eboff, soff, coff, seq, kind) survive elba_release_workspace, the rest is scratch.
+    // serial counts the contig calls: the later stages note in their for_cg which one their counts belong to
+    struct ContigStage {
+        int64_t n = 0, E = 0, bases = 0, circular = 0, singletons = 0;
+        DevBuf ptr, slot, kdeg, far[2], rank[2], mn[2], term, vinfo, flag, cidx, nel, eoff, ctr;
+        DevBuf cid, eread, epre, estr, eboff, soff, coff, seq, kind;
+        DevBuf cfar[2], crank[2];          // scratch of the second ranking pass (ELBA_CONTIG_CIRCULAR)
+        EventTimer t_total, t_rank;
+        elba_contig_stats stats{};
+        uint64_t serial = 0;
+        void release_scratch()
+        {
+            for (DevBuf *b : {&ptr, &slot, &kdeg, &term, &vinfo, &ctr, &flag, &cidx, &nel, &eoff}) b->release();
+            for (int b = 0; b < 2; ++b) { far[b].release(); rank[b].release(); mn[b].release(); cfar[b].release(); crank[b].release(); }
+        }
+    } cg;
 
     // assembly links (graph_links.hip): all scratch — the column pointers of S, first / last / strand bits per read, link counts per read and
-    // their scan, the counters (per workgroup and summed), the records before they are copied out.  gl_for: the contig call (cg_serial) the counts in gstats belong to
-    DevBuf gl_ptr, gl_bits, gl_cnt, gl_off, gl_ctr, gl_part, gl_out;
-    EventTimer gl_t_total;
-    elba_graph_stats gstats{};
-    uint64_t cg_serial = 0, gl_for = 0;
+    // their scan, the counters (per workgroup and summed), the records before they are copied out.  for_cg: the contig call (cg.serial) the counts in stats belong to
+    struct LinkStage {
+        DevBuf ptr, bits, cnt, off, ctr, part, out;
+        EventTimer t_total;
+        elba_graph_stats stats{};
+        uint64_t for_cg = 0;
+        void release_scratch() { for (DevBuf *b : {&ptr, &bits, &cnt, &off, &ctr, &part, &out}) b->release(); }
+    } gl;
 
-    // read pileups (pileup.hip): results (seg_off, seg_start, seg_depth, trim, flags) survive elba_release_workspace, the rest is scratch
-    int64_t pu_M = 0, pu_n = 0, pu_nseg = 0;
-    DevBuf pu_k0, pu_k1, pu_eptr, pu_head, pu_hidx, pu_delta, pu_dsum, pu_gstart, pu_tok, pu_tpos, pu_ctr, pu_sel, pu_rows, pu_cols, pu_vals;
-    DevBuf pu_seg_off, pu_seg_start, pu_seg_depth, pu_trim, pu_flags;
-    EventTimer pu_t_total;
-    elba_pileup_stats pustats{};
-    elba_pileup_cfg pu_cfg{};                  // the cfg of the pileup that is valid now (trim.hip's long runs are its min_depth / min_run)
+    // read pileups (pileup.hip): results (depth.seg_off, depth.seg_start, depth.seg_depth, trim, flags) and the counters survive
+    // elba_release_workspace, the rest is scratch
+    struct PileupStage {
+        int64_t M = 0, n = 0, nseg = 0;
+        DepthBufs depth;
+        DevBuf ctr, sel, rows, cols, vals;
+        DevBuf trim, flags;
+        EventTimer t_total;
+        elba_pileup_stats stats{};
+        elba_pileup_cfg cfg{};                  // the cfg of the pileup that is valid now (trim.hip's long runs are its min_depth / min_run)
+        void release_scratch() { depth.release_scratch(); for (DevBuf *b : {&sel, &rows, &cols, &vals}) b->release(); }
+    } pu;
 
     // read placements and contig depth (place.hip): all scratch, in buffers of its own so that a valid pileup stays untouched — chain start /
     // strand per read, the winning candidate per read, the records, contig lengths, the endpoint keys and what the pileup's keys-to-segments
-    // sequence needs (DepthBufs), per-contig credits, the counters.  pl_for: the contig call (cg_serial) the counts in plstats belong to
-    DevBuf pl_cstart, pl_cstrand, pl_best, pl_rec, pl_clen, pl_cred, pl_ctr;
-    DevBuf pl_k0, pl_k1, pl_eptr, pl_head, pl_hidx, pl_delta, pl_dsum, pl_gstart, pl_tok, pl_tpos, pl_seg_off, pl_seg_start, pl_seg_depth;
-    EventTimer pl_t_total;
-    elba_place_stats plstats{};
-    uint64_t pl_for = 0;
+    // sequence needs (depth), per-contig credits, the counters.  for_cg: the contig call (cg.serial) the counts in stats belong to
+    struct PlaceStage {
+        DevBuf cstart, cstrand, best, rec, clen, cred, ctr;
+        DepthBufs depth;
+        EventTimer t_total;
+        elba_place_stats stats{};
+        uint64_t for_cg = 0;
+        void release_scratch() { for (DevBuf *b : {&cstart, &cstrand, &best, &rec, &clen, &cred, &ctr}) b->release(); depth.release(); }
+    } pl;
 
     // contig polishing (polish.hip): all scratch — per read its slice (rows, first column, first base) and record, the row offsets of the
     // choices, the choices of one batch, the votes (5 per column, 4 per gap), what every column emits and its scan, the per-contig counts,
-    // the polished bases.  po_for: the contig call (cg_serial) the counts in postats belong to
-    DevBuf po_plan, po_rec, po_toff, po_trace, po_col, po_gap, po_cnt, po_emit, po_off, po_cstat, po_seq, po_seqoff, po_ctr;
-    EventTimer po_t_total, po_t_align;
-    elba_polish_stats postats{};
-    uint64_t po_for = 0;
+    // the polished bases.  for_cg: the contig call (cg.serial) the counts in stats belong to
+    struct PolishStage {
+        DevBuf plan, rec, toff, trace, col, gap, cnt, emit, off, cstat, seq, seqoff, ctr;
+        EventTimer t_total;
+        elba_polish_stats stats{};
+        uint64_t for_cg = 0;
+        void release_scratch() { for (DevBuf *b : {&plan, &rec, &toff, &trace, &col, &gap, &cnt, &emit, &off, &cstat, &seq, &seqoff, &ctr}) b->release(); }
+    } po;
 
     // trimmed reads (trim.hip): a snapshot in buffers of its own — packed / off / len in DnaBuffer layout, the map (src, beg, end); it survives
-    // elba_prune_reads and elba_release_workspace, a new read set or a new pileup invalidates it, elba_adopt_trimmed_reads consumes it
-    int64_t tm_n = 0, tm_packed_bytes = 0;
-    DevBuf tm_packed, tm_off, tm_len, tm_src, tm_beg, tm_end;
-    DevBuf tm_cnt, tm_bytes, tm_first, tm_boff, tm_srcb, tm_ctr;      // scratch
-    EventTimer tm_t_total, tm_t_repack;
-    elba_trim_stats tmstats{};
+    // elba_prune_reads and elba_release_workspace (as do the counters), a new read set or a new pileup invalidates it, elba_adopt_trimmed_reads consumes it
+    struct TrimStage {
+        int64_t n = 0, packed_bytes = 0;
+        DevBuf packed, off, len, src, beg, end, ctr;
+        DevBuf cnt, bytes, first, boff, srcb;      // scratch
+        EventTimer t_total, t_repack;
+        elba_trim_stats stats{};
+        void release_scratch() { for (DevBuf *b : {&cnt, &bytes, &first, &boff, &srcb}) b->release(); }
+    } tm;
 
     // string graph cleaning (sg_rounds.hpp): what the five calls below share, all scratch.  Column pointers of the round's S, the removed reads,
     // keep flags and their scan, the counters, and the second buffer of S (rows, cols, vals: swapped with tr_out_* after an odd number of
@@ -374,24 +410,19 @@ struct Ctx {
     } sg;
 
     // tip clipping (tips.hip): scratch of its own, one word per read each
-    DevBuf tp_ntips, tp_anchor;
-    elba_tip_stats tpstats{};
+    struct TipStage { DevBuf ntips, anchor; elba_tip_stats stats{}; void release_scratch() { ntips.release(); anchor.release(); } } tp;
 
     // bubble popping (bubbles.hip): scratch of its own, one word per entry of S each
-    DevBuf bb_end, bb_len;
-    elba_bubble_stats bbstats{};
+    struct BubbleStage { DevBuf end, len; elba_bubble_stats stats{}; void release_scratch() { end.release(); len.release(); } } bb;
 
     // cutting weak overlaps (weak.hip): scratch of its own, one word per (read, side) each
-    DevBuf wk_best, wk_cnt, wk_nweak, wk_after;
-    elba_weak_stats wkstats{};
+    struct WeakStage { DevBuf best, cnt, nweak, after; elba_weak_stats stats{}; void release_scratch() { best.release(); cnt.release(); nweak.release(); after.release(); } } wk;
 
     // cutting bridge chains (bridges.hip): scratch of its own, one word per entry of S
-    DevBuf br_flank;
-    elba_bridge_stats brstats{};
+    struct BridgeStage { DevBuf flank; elba_bridge_stats stats{}; void release_scratch() { flank.release(); } } br;
 
     // resolving three-armed stars (stars.hip): scratch of its own, one word per read.  It reads tr_ptr / tr_sym
-    DevBuf sr_word;
-    elba_star_stats srstats{};
+    struct StarStage { DevBuf word; elba_star_stats stats{}; void release_scratch() { word.release(); } } sr;
 
     // workspaces
     DevBuf ws_scan, ws_sort, ws_a, ws_b, ws_c, ws_d, ws_e, ws_f;
@@ -469,21 +500,34 @@ inline ReadSource read_source(Ctx &c, int64_t M, const char *who, const char *wh
     throw Error{ELBA_ERR_STATE, std::string(who) + ": the " + w + " are not on this context (elba_set_reads or elba_dist_set_all_reads)"};
 }
 
-// The buffer set of the pileup's keys-to-segments sequence (pileup.hip: depth_segments), so that place.hip runs the same launches on buffers
-// of its own
-struct DepthBufs { DevBuf &k0, &k1, &eptr, &head, &hidx, &delta, &dsum, &gstart, &tok, &tpos, &seg_off, &seg_start, &seg_depth; };
-void depth_reserve(const DepthBufs &b, int64_t max_keys, int64_t G);
-const uint64_t *depth_segments(Ctx &c, const DepthBufs &b, int64_t E, int64_t M, int mb, int pb, const uint32_t *len, unsigned long long *ctr);
+const uint64_t *depth_segments(Ctx &c, DepthBufs &b, int64_t E, int64_t M, int mb, int pb, const uint32_t *len, unsigned long long *ctr);      // pileup.hip
+
+// What an export hands to the caller: a malloc'ed block of at least one element (the elba_free_* functions free it), and the copy of n
+// elements from the device into it, queued on the context's stream
+template <class T>
+T *host_block(size_t n)
+{
+    T *p = static_cast<T *>(malloc((n ? n : 1) * sizeof(T)));
+    if (!p) throw std::bad_alloc();
+    return p;
+}
+template <class T>
+void copy_out(Ctx &c, T *dst, const void *src, size_t n)
+{
+    if (n) ELBA_HIP(hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyDeviceToHost, c.stream));
+}
+
+// pair a of the graph's input has a bad interval (the smallest such pair, found by a kernel of read_pileup, place_reads or polish_contigs)
+[[noreturn]] void throw_bad_pair(Ctx &c, const GraphInput &in, int64_t a, const char *who);      // pileup.hip
 
 // elba_place_reads up to and including its records (place.hip), for the two stages that need them: the state and size checks (messages
 // begin with `who`), the reservations, chain starts, the candidates' winners and k_pl_place — queued on the context's stream, not
 // synchronised.  ctr: the PLACE_CTR_WORDS counters of place.hip; word PLACE_CTR_BAD holds the smallest candidate with a bad interval (all
-// ones: none), which the caller reads behind its own synchronisation and hands to place_throw_bad_pair.  depth_bufs: also reserve what
+// ones: none), which the caller reads behind its own synchronisation and hands to throw_bad_pair.  depth_bufs: also reserve what
 // depth_segments needs.  t, when given, is started in front of the first launch.
 constexpr int PLACE_CTR_BAD = 2, PLACE_CTR_WORDS = 16;
 struct PlaceWork { GraphInput in; ReadSource src; int64_t M, base, E, nc; elba_placement_t *rec; unsigned long long *ctr; const uint32_t *clen; };
 PlaceWork place_records(Ctx &c, int skip_flags, const char *who, bool depth_bufs, EventTimer *t);
-[[noreturn]] void place_throw_bad_pair(Ctx &c, const PlaceWork &w, int64_t a, const char *who);
 
 // ---- stages -----------------------------------------------------------------------------------------------------
 void stage_set_reads_fasta(Ctx &c, const char *chunk, int64_t chunk_bytes, uint64_t chunk_file_offset, const elba_fasta_record_t *recs, int64_t nreads,

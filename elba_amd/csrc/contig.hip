@@ -302,57 +302,57 @@ void stage_generate_contigs(Ctx &c, int flags)
     int R = 0;
     while ((1ll << R) < M) ++R;                                 // arc chains are shorter than M: 2^R >= M covers every path and cycle
     // every buffer of the launch sequence before the first launch (the output is sized after the one synchronisation)
-    c.cg_ptr.reserve((size_t)(M + 2) * 4); c.cg_slot.reserve((size_t)(2 * M + 2) * sizeof(CgSlot)); c.cg_kdeg.reserve((size_t)M + 4);
-    for (int b = 0; b < 2; ++b) { c.cg_far[b].reserve((size_t)(2 * M + 2) * 4); c.cg_rank[b].reserve((size_t)(2 * M + 2) * 4); c.cg_mn[b].reserve((size_t)(2 * M + 2) * 4); }
-    c.cg_term.reserve((size_t)2 * M + 4); c.cg_vinfo.reserve((size_t)(M + 1) * sizeof(uint4));
-    c.cg_flag.reserve((size_t)(M + 2) * 4); c.cg_cidx.reserve((size_t)(M + 2) * 4); c.cg_nel.reserve((size_t)(M + 2) * 4); c.cg_eoff.reserve((size_t)(M + 2) * 4);
-    c.cg_cid.reserve((size_t)(M + 1) * 4); c.cg_eread.reserve((size_t)(M + 1) * 8); c.cg_epre.reserve((size_t)(M + 2) * 4); c.cg_estr.reserve((size_t)M + 4);
-    c.cg_eboff.reserve((size_t)(M + 2) * 8); c.cg_soff.reserve((size_t)(M + 2) * 8); c.cg_coff.reserve((size_t)(M + 2) * 8); c.cg_ctr.reserve(128);
-    c.cg_kind.reserve((size_t)M + 4);
+    c.cg.ptr.reserve((size_t)(M + 2) * 4); c.cg.slot.reserve((size_t)(2 * M + 2) * sizeof(CgSlot)); c.cg.kdeg.reserve((size_t)M + 4);
+    for (int b = 0; b < 2; ++b) { c.cg.far[b].reserve((size_t)(2 * M + 2) * 4); c.cg.rank[b].reserve((size_t)(2 * M + 2) * 4); c.cg.mn[b].reserve((size_t)(2 * M + 2) * 4); }
+    c.cg.term.reserve((size_t)2 * M + 4); c.cg.vinfo.reserve((size_t)(M + 1) * sizeof(uint4));
+    c.cg.flag.reserve((size_t)(M + 2) * 4); c.cg.cidx.reserve((size_t)(M + 2) * 4); c.cg.nel.reserve((size_t)(M + 2) * 4); c.cg.eoff.reserve((size_t)(M + 2) * 4);
+    c.cg.cid.reserve((size_t)(M + 1) * 4); c.cg.eread.reserve((size_t)(M + 1) * 8); c.cg.epre.reserve((size_t)(M + 2) * 4); c.cg.estr.reserve((size_t)M + 4);
+    c.cg.eboff.reserve((size_t)(M + 2) * 8); c.cg.soff.reserve((size_t)(M + 2) * 8); c.cg.coff.reserve((size_t)(M + 2) * 8); c.cg.ctr.reserve(128);
+    c.cg.kind.reserve((size_t)M + 4);
     const bool circular = (flags & ELBA_CONTIG_CIRCULAR) != 0;
     if (circular)                                               // the second ranking pass reads the first one's far / mn / term, which stay as they are
-        for (int b = 0; b < 2; ++b) { c.cg_cfar[b].reserve((size_t)(2 * M + 2) * 4); c.cg_crank[b].reserve((size_t)(2 * M + 2) * 4); }
-    uint32_t *ptr = c.cg_ptr.as<uint32_t>(); CgSlot *slot = c.cg_slot.as<CgSlot>(); uint8_t *kdeg = c.cg_kdeg.as<uint8_t>(), *term = c.cg_term.as<uint8_t>();
-    unsigned long long *ctr = c.cg_ctr.as<unsigned long long>();
-    c.cg_t_total.start(s);
+        for (int b = 0; b < 2; ++b) { c.cg.cfar[b].reserve((size_t)(2 * M + 2) * 4); c.cg.crank[b].reserve((size_t)(2 * M + 2) * 4); }
+    uint32_t *ptr = c.cg.ptr.as<uint32_t>(); CgSlot *slot = c.cg.slot.as<CgSlot>(); uint8_t *kdeg = c.cg.kdeg.as<uint8_t>(), *term = c.cg.term.as<uint8_t>();
+    unsigned long long *ctr = c.cg.ctr.as<unsigned long long>();
+    c.cg.t_total.start(s);
     ELBA_HIP(hipMemsetAsync(ctr, 0, 128, s));
     ELBA_HIP(hipMemsetAsync(ctr + 3, 0xff, 8, s));
-    ELBA_HIP(hipMemsetAsync(c.cg_epre.p, 0, (size_t)(M + 2) * 4, s));
+    ELBA_HIP(hipMemsetAsync(c.cg.epre.p, 0, (size_t)(M + 2) * 4, s));
     const unsigned nbM = (unsigned)((M + 1 + 255) / 256), nbA = (unsigned)((2 * M + 255) / 256);
     if (nnz > 0) group_offsets_u32(s, reinterpret_cast<const uint64_t *>(c.tr_out_cols.p), 0, nnz, ptr, M);     // column pointers of S (columns ascending)
     else ELBA_HIP(hipMemsetAsync(ptr, 0, (size_t)(M + 1) * 4, s));
     int which = 0;
     if (M > 0) {
         hipLaunchKernelGGL(k_cg_adjacency, dim3(nbM), dim3(256), 0, s, ptr, c.tr_out_rows.as<int64_t>(), c.tr_out_vals.as<elba_overlap_t>(), (uint32_t)M, slot, kdeg, ctr);
-        hipLaunchKernelGGL(k_cg_arcs, dim3(nbA), dim3(256), 0, s, slot, kdeg, (uint32_t)M, c.cg_far[0].as<uint32_t>(), c.cg_rank[0].as<uint32_t>(), c.cg_mn[0].as<uint32_t>(), term);
+        hipLaunchKernelGGL(k_cg_arcs, dim3(nbA), dim3(256), 0, s, slot, kdeg, (uint32_t)M, c.cg.far[0].as<uint32_t>(), c.cg.rank[0].as<uint32_t>(), c.cg.mn[0].as<uint32_t>(), term);
     }
-    c.cg_t_rank.start(s);
+    c.cg.t_rank.start(s);
     if (M > 0) {
         for (int r = 0; r < R; ++r, which ^= 1)
-            hipLaunchKernelGGL(k_cg_jump, dim3(nbA), dim3(256), 0, s, (uint32_t)(2 * M), c.cg_far[which].as<uint32_t>(), c.cg_rank[which].as<uint32_t>(), c.cg_mn[which].as<uint32_t>(),
-                               c.cg_far[which ^ 1].as<uint32_t>(), c.cg_rank[which ^ 1].as<uint32_t>(), c.cg_mn[which ^ 1].as<uint32_t>());
+            hipLaunchKernelGGL(k_cg_jump, dim3(nbA), dim3(256), 0, s, (uint32_t)(2 * M), c.cg.far[which].as<uint32_t>(), c.cg.rank[which].as<uint32_t>(), c.cg.mn[which].as<uint32_t>(),
+                               c.cg.far[which ^ 1].as<uint32_t>(), c.cg.rank[which ^ 1].as<uint32_t>(), c.cg.mn[which ^ 1].as<uint32_t>());
     }
     int cwhich = 0;
     if (circular && M > 0) {
-        hipLaunchKernelGGL(k_cg_cut, dim3(nbA), dim3(256), 0, s, slot, kdeg, c.cg_far[which].as<uint32_t>(), c.cg_mn[which].as<uint32_t>(), term, (uint32_t)M,
-                           c.cg_cfar[0].as<uint32_t>(), c.cg_crank[0].as<uint32_t>(), c.cg_cfar[1].as<uint32_t>(), c.cg_crank[1].as<uint32_t>(), ctr);
+        hipLaunchKernelGGL(k_cg_cut, dim3(nbA), dim3(256), 0, s, slot, kdeg, c.cg.far[which].as<uint32_t>(), c.cg.mn[which].as<uint32_t>(), term, (uint32_t)M,
+                           c.cg.cfar[0].as<uint32_t>(), c.cg.crank[0].as<uint32_t>(), c.cg.cfar[1].as<uint32_t>(), c.cg.crank[1].as<uint32_t>(), ctr);
         for (int r = 0; r < R; ++r, cwhich ^= 1)
-            hipLaunchKernelGGL(k_cg_jump2, dim3(nbA), dim3(256), 0, s, (uint32_t)(2 * M), c.cg_cfar[cwhich].as<uint32_t>(), c.cg_crank[cwhich].as<uint32_t>(),
-                               c.cg_cfar[cwhich ^ 1].as<uint32_t>(), c.cg_crank[cwhich ^ 1].as<uint32_t>(), ctr);
+            hipLaunchKernelGGL(k_cg_jump2, dim3(nbA), dim3(256), 0, s, (uint32_t)(2 * M), c.cg.cfar[cwhich].as<uint32_t>(), c.cg.crank[cwhich].as<uint32_t>(),
+                               c.cg.cfar[cwhich ^ 1].as<uint32_t>(), c.cg.crank[cwhich ^ 1].as<uint32_t>(), ctr);
     }
-    c.cg_t_rank.stop(s);
-    uint32_t *flag = c.cg_flag.as<uint32_t>(), *cidx = c.cg_cidx.as<uint32_t>(), *nel = c.cg_nel.as<uint32_t>(), *eoff = c.cg_eoff.as<uint32_t>();
-    hipLaunchKernelGGL(k_cg_vertices, dim3(nbM), dim3(256), 0, s, slot, kdeg, c.cg_far[which].as<uint32_t>(), c.cg_rank[which].as<uint32_t>(), c.cg_mn[which].as<uint32_t>(), term,
-                       (uint32_t)M, c.cg_vinfo.as<uint4>(), flag, nel, ctr, flags, circular ? c.cg_cfar[cwhich].as<uint32_t>() : nullptr,
-                       circular ? c.cg_crank[cwhich].as<uint32_t>() : nullptr, c.tr_flags.as<uint8_t>(), len);
+    c.cg.t_rank.stop(s);
+    uint32_t *flag = c.cg.flag.as<uint32_t>(), *cidx = c.cg.cidx.as<uint32_t>(), *nel = c.cg.nel.as<uint32_t>(), *eoff = c.cg.eoff.as<uint32_t>();
+    hipLaunchKernelGGL(k_cg_vertices, dim3(nbM), dim3(256), 0, s, slot, kdeg, c.cg.far[which].as<uint32_t>(), c.cg.rank[which].as<uint32_t>(), c.cg.mn[which].as<uint32_t>(), term,
+                       (uint32_t)M, c.cg.vinfo.as<uint4>(), flag, nel, ctr, flags, circular ? c.cg.cfar[cwhich].as<uint32_t>() : nullptr,
+                       circular ? c.cg.crank[cwhich].as<uint32_t>() : nullptr, c.tr_flags.as<uint8_t>(), len);
     exclusive_scan_u32(s, flag, cidx, M + 1, c.ws_scan);
     exclusive_scan_u32(s, nel, eoff, M + 1, c.ws_scan);
     if (M > 0)
-        hipLaunchKernelGGL(k_cg_elements, dim3(nbM), dim3(256), 0, s, slot, c.cg_vinfo.as<uint4>(), cidx, eoff, len, (uint32_t)M, base, c.cg_cid.as<int32_t>(),
-                           c.cg_eread.as<int64_t>(), c.cg_epre.as<int32_t>(), c.cg_estr.as<uint8_t>(), ctr);
-    exclusive_scan_u32_to_i64(s, c.cg_epre.as<uint32_t>(), c.cg_eboff.as<int64_t>(), M + 1, c.ws_scan);     // prefixes are >= 0 here (bad ones were zeroed)
-    hipLaunchKernelGGL(k_cg_contigs, dim3(nbM), dim3(256), 0, s, flag, cidx, eoff, nel, c.cg_eboff.as<int64_t>(), c.cg_vinfo.as<uint4>(), (uint32_t)M,
-                       c.cg_soff.as<int64_t>(), c.cg_coff.as<int64_t>(), c.cg_kind.as<uint8_t>(), ctr);
+        hipLaunchKernelGGL(k_cg_elements, dim3(nbM), dim3(256), 0, s, slot, c.cg.vinfo.as<uint4>(), cidx, eoff, len, (uint32_t)M, base, c.cg.cid.as<int32_t>(),
+                           c.cg.eread.as<int64_t>(), c.cg.epre.as<int32_t>(), c.cg.estr.as<uint8_t>(), ctr);
+    exclusive_scan_u32_to_i64(s, c.cg.epre.as<uint32_t>(), c.cg.eboff.as<int64_t>(), M + 1, c.ws_scan);     // prefixes are >= 0 here (bad ones were zeroed)
+    hipLaunchKernelGGL(k_cg_contigs, dim3(nbM), dim3(256), 0, s, flag, cidx, eoff, nel, c.cg.eboff.as<int64_t>(), c.cg.vinfo.as<uint4>(), (uint32_t)M,
+                       c.cg.soff.as<int64_t>(), c.cg.coff.as<int64_t>(), c.cg.kind.as<uint8_t>(), ctr);
     ELBA_HIP(hipGetLastError());
     unsigned long long h[16] = {0};
     ELBA_HIP(hipMemcpyAsync(h, ctr, 128, hipMemcpyDeviceToHost, s));
@@ -369,23 +369,23 @@ void stage_generate_contigs(Ctx &c, int flags)
                                               std::to_string((int64_t)v + base) + ", " + std::to_string((int64_t)r + base) + ") is not a valid prefix length"};
     }
     const int64_t nc = (int64_t)h[4], E = (int64_t)h[5], bases = (int64_t)h[6];
-    c.cg_seq.reserve((size_t)bases + 64);
+    c.cg.seq.reserve((size_t)bases + 64);
     if (E > 0 && bases > 0) {
         int64_t grid = (E + CG_WRITE_THREADS / 64 - 1) / (CG_WRITE_THREADS / 64);
         if (grid > (int64_t)c.num_cus * 16) grid = (int64_t)c.num_cus * 16;
-        hipLaunchKernelGGL(k_cg_write, dim3((unsigned)grid), dim3(CG_WRITE_THREADS), 0, s, c.cg_eread.as<int64_t>(), c.cg_epre.as<int32_t>(), c.cg_estr.as<uint8_t>(),
-                           c.cg_eboff.as<int64_t>(), E, base, packed, byte_off, len, c.cg_seq.as<char>());
+        hipLaunchKernelGGL(k_cg_write, dim3((unsigned)grid), dim3(CG_WRITE_THREADS), 0, s, c.cg.eread.as<int64_t>(), c.cg.epre.as<int32_t>(), c.cg.estr.as<uint8_t>(),
+                           c.cg.eboff.as<int64_t>(), E, base, packed, byte_off, len, c.cg.seq.as<char>());
         ELBA_HIP(hipGetLastError());
     }
-    c.cg_t_total.stop(s);
+    c.cg.t_total.stop(s);
     ELBA_HIP(hipStreamSynchronize(s));
     const int64_t ncirc = (int64_t)h[9], nsingle = (int64_t)h[10];
     st.branches = (int64_t)h[0]; st.cycles = (int64_t)h[2]; st.contigs = nc;
     st.used_components = nc - ncirc - nsingle + st.cycles;                  // paths + cycles, whether the cycles were emitted or not
     st.components = st.branches + (int64_t)h[1] + st.used_components;     // CC on S without the branches' rows and columns: a branch read is a component of its own
     st.contig_reads = E; st.bases = bases; st.longest = (int64_t)h[7];
-    st.ms_total = c.cg_t_total.ms(); st.ms_rank = c.cg_t_rank.ms();
-    c.cg_n = nc; c.cg_E = E; c.cg_bases = bases; c.cg_circular = ncirc; c.cg_singletons = nsingle; c.cstats = st; ++c.cg_serial; done(c.v, EV_GENERATE_CONTIGS);
+    st.ms_total = c.cg.t_total.ms(); st.ms_rank = c.cg.t_rank.ms();
+    c.cg.n = nc; c.cg.E = E; c.cg.bases = bases; c.cg.circular = ncirc; c.cg.singletons = nsingle; c.cg.stats = st; ++c.cg.serial; done(c.v, EV_GENERATE_CONTIGS);
 }
 
 void stage_generate_contigs_ex(Ctx &c, const elba_contig_cfg *cfg)

@@ -3,10 +3,10 @@
 //
 // Input, all resident: S as tr.hip leaves it (tr_out_*: both triangles, column-major, the entry at (row v, column u) is S(v, u), so the
 // step u -> v the contig walk reads at u is its transpose: prefix = the stored suffix, direction = the stored directionT, and the step
-// v -> u is the stored suffixT / direction); of the last contig call the read map cg_cid (contig of every read, -1: none — kept by the
-// contig stage and read as it is), the chain arrays cg_eread / cg_estr / cg_coff, the kinds and the sequence offsets; the read lengths.
+// v -> u is the stored suffixT / direction); of the last contig call the read map cg.cid (contig of every read, -1: none — kept by the
+// contig stage and read as it is), the chain arrays cg.eread / cg.estr / cg.coff, the kinds and the sequence offsets; the read lengths.
 //
-//   k_gl_bits       one lane per chain element: first / last / strand bits of its read (the contig of a read is cg_cid, not recomputed)
+//   k_gl_bits       one lane per chain element: first / last / strand bits of its read (the contig of a read is cg.cid, not recomputed)
 //   k_gl_links<0>   the count pass.  A wavefront takes 64 consecutive columns.  A column of up to 64 entries is walked by its lane (its
 //                   rows below the diagonal: v > u).  A longer column is worked on by the whole wavefront afterwards, 64 entries a trip,
 //                   the kept entries placed by ballot + popcount.  cnt[u] = records of column u, the closure record of a circular contig
@@ -192,28 +192,28 @@ __global__ __launch_bounds__(GL_THREADS) void k_gl_sum(const unsigned long long 
 void stage_export_assembly_links(Ctx &c, elba_links_t *out)
 {
     ELBA_REQUIRE(has(c.v, P_S, P_CONTIGS), ELBA_ERR_STATE, "export_assembly_links: no contigs of the current string graph (call elba_generate_contigs)");
-    const int64_t M = c.tr_M, nnz = c.tr_nnz, base = c.tr_id_base, E = c.cg_E, nc = c.cg_n;
+    const int64_t M = c.tr_M, nnz = c.tr_nnz, base = c.tr_id_base, E = c.cg.E, nc = c.cg.n;
     const ReadSource src = read_source(c, M, "export_assembly_links", "lengths of the graph's # reads", base == 0);
     ELBA_REQUIRE(M + base < 0xFFFFFFFFll && nc < 0xFFFFFFFFll, ELBA_ERR_UNSUPPORTED, "export_assembly_links: read ids beyond 32 bit");
     hipStream_t s = c.stream;
-    c.gl_ptr.reserve((size_t)(M + 2) * 4); c.gl_bits.reserve((size_t)M + 4); c.gl_cnt.reserve((size_t)(M + 2) * 4); c.gl_off.reserve((size_t)(M + 2) * 4);
-    c.gl_ctr.reserve(64);
+    c.gl.ptr.reserve((size_t)(M + 2) * 4); c.gl.bits.reserve((size_t)M + 4); c.gl.cnt.reserve((size_t)(M + 2) * 4); c.gl.off.reserve((size_t)(M + 2) * 4);
+    c.gl.ctr.reserve(64);
     const unsigned nb = (unsigned)((M + 1 + GL_THREADS - 1) / GL_THREADS);      // (column M: the scan's last element)
-    c.gl_part.reserve((size_t)nb * GC_PART * 8);
-    uint32_t *ptr = c.gl_ptr.as<uint32_t>(), *cnt = c.gl_cnt.as<uint32_t>(), *off = c.gl_off.as<uint32_t>();
-    unsigned long long *ctr = c.gl_ctr.as<unsigned long long>();
-    c.gl_t_total.start(s);
+    c.gl.part.reserve((size_t)nb * GC_PART * 8);
+    uint32_t *ptr = c.gl.ptr.as<uint32_t>(), *cnt = c.gl.cnt.as<uint32_t>(), *off = c.gl.off.as<uint32_t>();
+    unsigned long long *ctr = c.gl.ctr.as<unsigned long long>();
+    c.gl.t_total.start(s);
     ELBA_HIP(hipMemsetAsync(ctr, 0, 64, s));
-    ELBA_HIP(hipMemsetAsync(c.gl_bits.p, 0, (size_t)M + 4, s));
+    ELBA_HIP(hipMemsetAsync(c.gl.bits.p, 0, (size_t)M + 4, s));
     if (nnz > 0) group_offsets_u32(s, reinterpret_cast<const uint64_t *>(c.tr_out_cols.p), 0, nnz, ptr, M);     // column pointers of S (columns ascending)
     else ELBA_HIP(hipMemsetAsync(ptr, 0, (size_t)(M + 1) * 4, s));
     if (E > 0)
-        hipLaunchKernelGGL(k_gl_bits, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, s, c.cg_eread.as<int64_t>(), c.cg_estr.as<uint8_t>(), c.cg_coff.as<int64_t>(),
-                           c.cg_cid.as<int32_t>(), E, base, (uint32_t)M, c.gl_bits.as<uint8_t>());
-    GlIn g{ptr, c.tr_out_rows.as<int64_t>(), c.tr_out_vals.as<elba_overlap_t>(), c.cg_cid.as<int32_t>(), c.gl_bits.as<uint8_t>(), c.cg_kind.as<uint8_t>(),
-           c.cg_soff.as<int64_t>(), src.len, (uint32_t)M, (uint32_t)base};
-    hipLaunchKernelGGL(k_gl_links<0>, dim3(nb), dim3(GL_THREADS), 0, s, g, cnt, (const uint32_t *)nullptr, (elba_link_t *)nullptr, c.gl_part.as<unsigned long long>());
-    hipLaunchKernelGGL(k_gl_sum, dim3(1), dim3(GL_THREADS), 0, s, c.gl_part.as<unsigned long long>(), nb, ctr);
+        hipLaunchKernelGGL(k_gl_bits, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, s, c.cg.eread.as<int64_t>(), c.cg.estr.as<uint8_t>(), c.cg.coff.as<int64_t>(),
+                           c.cg.cid.as<int32_t>(), E, base, (uint32_t)M, c.gl.bits.as<uint8_t>());
+    GlIn g{ptr, c.tr_out_rows.as<int64_t>(), c.tr_out_vals.as<elba_overlap_t>(), c.cg.cid.as<int32_t>(), c.gl.bits.as<uint8_t>(), c.cg.kind.as<uint8_t>(),
+           c.cg.soff.as<int64_t>(), src.len, (uint32_t)M, (uint32_t)base};
+    hipLaunchKernelGGL(k_gl_links<0>, dim3(nb), dim3(GL_THREADS), 0, s, g, cnt, (const uint32_t *)nullptr, (elba_link_t *)nullptr, c.gl.part.as<unsigned long long>());
+    hipLaunchKernelGGL(k_gl_sum, dim3(1), dim3(GL_THREADS), 0, s, c.gl.part.as<unsigned long long>(), nb, ctr);
     exclusive_scan_u32(s, cnt, off, M + 1, c.ws_scan);
     ELBA_HIP(hipGetLastError());
     unsigned long long h[8] = {0};
@@ -223,21 +223,20 @@ void stage_export_assembly_links(Ctx &c, elba_links_t *out)
     ELBA_HIP(hipStreamSynchronize(s));
     ELBA_REQUIRE((unsigned long long)total == h[GC_LINKS] + h[GC_CLOS], ELBA_ERR_INTERNAL, "export_assembly_links: the scanned total is not the counted records");
     out->n = (int64_t)total;
-    out->links = static_cast<elba_link_t *>(malloc(((size_t)total ? (size_t)total : 1) * sizeof(elba_link_t)));
-    if (!out->links) throw std::bad_alloc();
+    out->links = host_block<elba_link_t>((size_t)total);
     if (total) {
-        c.gl_out.reserve((size_t)total * sizeof(elba_link_t));
-        hipLaunchKernelGGL(k_gl_links<1>, dim3(nb), dim3(GL_THREADS), 0, s, g, cnt, (const uint32_t *)off, c.gl_out.as<elba_link_t>(), (unsigned long long *)nullptr);
+        c.gl.out.reserve((size_t)total * sizeof(elba_link_t));
+        hipLaunchKernelGGL(k_gl_links<1>, dim3(nb), dim3(GL_THREADS), 0, s, g, cnt, (const uint32_t *)off, c.gl.out.as<elba_link_t>(), (unsigned long long *)nullptr);
         ELBA_HIP(hipGetLastError());
-        ELBA_HIP(hipMemcpyAsync(out->links, c.gl_out.p, (size_t)total * sizeof(elba_link_t), hipMemcpyDeviceToHost, s));
+        copy_out(c, out->links, c.gl.out.p, (size_t)total);
     }
-    c.gl_t_total.stop(s);
+    c.gl.t_total.stop(s);
     ELBA_HIP(hipStreamSynchronize(s));
     elba_graph_stats st{};
     st.segments = nc; st.candidates = (int64_t)h[GC_CAND]; st.links = (int64_t)h[GC_LINKS]; st.closures = (int64_t)h[GC_CLOS]; st.twisted = (int64_t)h[GC_TWIST];
     st.unplaced = (int64_t)h[GC_UNPL]; st.clamped = (int64_t)h[GC_CLAMP]; st.asymmetric = (int64_t)h[GC_ASYM];
-    st.ms_total = c.gl_t_total.ms();
-    c.gstats = st; c.gl_for = c.cg_serial;
+    st.ms_total = c.gl.t_total.ms();
+    c.gl.stats = st; c.gl.for_cg = c.cg.serial;
 }
 
 }  // namespace elba

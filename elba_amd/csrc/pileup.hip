@@ -260,31 +260,26 @@ PuInput pileup_input(Ctx &c, const char *who)
     return in;
 }
 
-DepthBufs pileup_depth_bufs(Ctx &c)
-{
-    return {c.pu_k0, c.pu_k1, c.pu_eptr, c.pu_head, c.pu_hidx, c.pu_delta, c.pu_dsum, c.pu_gstart, c.pu_tok, c.pu_tpos, c.pu_seg_off, c.pu_seg_start, c.pu_seg_depth};
-}
-
 }  // namespace
 
 // Sorted keys to segments (the sort .. k_pu_segs of the header), shared with place.hip, which runs it over contigs: E endpoint keys
 // group << (pb + 1) | pos << 1 | kind in b.k0 (groups below M < 2^mb, positions 0 .. len[group] < 2^pb) become, per group, the maximal runs
 // of equal depth from 0 to len[group] in b.seg_off / seg_start / seg_depth.  ctr[3] = the segments, ctr[4] = the largest depth (an atomicMax:
 // zeroed by the caller).  Returns the sorted keys (b.k0 or b.k1).  Everything is queued on the context's stream; nothing synchronises.
-// depth_reserve sizes the set for at most max_keys endpoints of G groups.
-void depth_reserve(const DepthBufs &b, int64_t max_keys, int64_t G)
+// DepthBufs::reserve sizes the set for at most max_keys endpoints of G groups.
+void DepthBufs::reserve(int64_t max_keys, int64_t G)
 {
     const int64_t ntok_max = max_keys + G;                      // token slots: groups (<= keys) + one per group of the caller
-    b.k0.reserve((size_t)(max_keys + 4) * 8); b.k1.reserve((size_t)(max_keys + 4) * 8);
-    b.eptr.reserve((size_t)(G + 2) * 4);
-    b.head.reserve((size_t)(max_keys + 2) * 4); b.hidx.reserve((size_t)(max_keys + 2) * 4); b.delta.reserve((size_t)(max_keys + 2) * 4); b.dsum.reserve((size_t)(max_keys + 2) * 4);
-    b.gstart.reserve((size_t)(max_keys + 2) * 4); b.tok.reserve((size_t)(ntok_max + 2) * 4); b.tpos.reserve((size_t)(ntok_max + 2) * 4);
-    b.seg_off.reserve((size_t)(G + 2) * 8);
+    k0.reserve((size_t)(max_keys + 4) * 8); k1.reserve((size_t)(max_keys + 4) * 8);
+    eptr.reserve((size_t)(G + 2) * 4);
+    head.reserve((size_t)(max_keys + 2) * 4); hidx.reserve((size_t)(max_keys + 2) * 4); delta.reserve((size_t)(max_keys + 2) * 4); dsum.reserve((size_t)(max_keys + 2) * 4);
+    gstart.reserve((size_t)(max_keys + 2) * 4); tok.reserve((size_t)(ntok_max + 2) * 4); tpos.reserve((size_t)(ntok_max + 2) * 4);
+    seg_off.reserve((size_t)(G + 2) * 8);
     // segments: at most one per endpoint, plus one per group
-    b.seg_start.reserve((size_t)(ntok_max + 1) * 4); b.seg_depth.reserve((size_t)(ntok_max + 1) * 4);
+    seg_start.reserve((size_t)(ntok_max + 1) * 4); seg_depth.reserve((size_t)(ntok_max + 1) * 4);
 }
 
-const uint64_t *depth_segments(Ctx &c, const DepthBufs &b, int64_t E, int64_t M, int mb, int pb, const uint32_t *len, unsigned long long *ctr)
+const uint64_t *depth_segments(Ctx &c, DepthBufs &b, int64_t E, int64_t M, int mb, int pb, const uint32_t *len, unsigned long long *ctr)
 {
     hipStream_t s = c.stream;
     uint32_t *eptr = b.eptr.as<uint32_t>(), *head = b.head.as<uint32_t>(), *hidx = b.hidx.as<uint32_t>(), *delta = b.delta.as<uint32_t>();
@@ -311,6 +306,18 @@ const uint64_t *depth_segments(Ctx &c, const DepthBufs &b, int64_t E, int64_t M,
     return keys;
 }
 
+void throw_bad_pair(Ctx &c, const GraphInput &in, int64_t a, const char *who)
+{
+    hipStream_t s = c.stream;
+    int64_t r = 0, col = 0; elba_overlap_t o{};
+    ELBA_HIP(hipMemcpyAsync(&r, in.rows + a, 8, hipMemcpyDeviceToHost, s));
+    ELBA_HIP(hipMemcpyAsync(&col, in.cols + a, 8, hipMemcpyDeviceToHost, s));
+    ELBA_HIP(hipMemcpyAsync(&o, in.vals + a, sizeof(o), hipMemcpyDeviceToHost, s));
+    ELBA_HIP(hipStreamSynchronize(s));
+    throw Error{ELBA_ERR_INVALID_ARG, std::string(who) + ": pair " + std::to_string(a) + " (" + std::to_string(r) + ", " + std::to_string(col) + ") has an interval outside [0, len] or with beg > end: Q [" +
+                                          std::to_string(o.begQ) + ", " + std::to_string(o.endQ) + "), T [" + std::to_string(o.begT) + ", " + std::to_string(o.endT) + ")"};
+}
+
 void stage_read_pileup(Ctx &c, const elba_pileup_cfg *cfgp)
 {
     enter(c.v, EV_READ_PILEUP);
@@ -330,43 +337,34 @@ void stage_read_pileup(Ctx &c, const elba_pileup_cfg *cfgp)
     PuParams p{};
     p.rows = in.rows; p.cols = in.cols; p.vals = in.vals; p.n = n; p.len = in.len; p.M = (uint32_t)M; p.pb = pb;
     p.mode = cfg.mode; p.margin = cfg.margin; p.min_depth = cfg.min_depth; p.min_run = cfg.min_run; p.trim_len = cfg.trim_len;
-    const DepthBufs db = pileup_depth_bufs(c);
-    depth_reserve(db, n4, M);                                   // keys, marks, scans, tokens and segments for at most 4n endpoints of M reads
-    c.pu_ctr.reserve(128);
-    c.pu_trim.reserve((size_t)(M + 1) * 8); c.pu_flags.reserve((size_t)M + 4);
-    p.keys = c.pu_k0.as<uint64_t>(); p.ctr = c.pu_ctr.as<unsigned long long>();
-    c.pu_t_total.start(s);
-    ELBA_HIP(hipMemsetAsync(c.pu_ctr.p, 0, 128, s));
+    DepthBufs &db = c.pu.depth;
+    db.reserve(n4, M);                                          // keys, marks, scans, tokens and segments for at most 4n endpoints of M reads
+    c.pu.ctr.reserve(128);
+    c.pu.trim.reserve((size_t)(M + 1) * 8); c.pu.flags.reserve((size_t)M + 4);
+    p.keys = db.k0.as<uint64_t>(); p.ctr = c.pu.ctr.as<unsigned long long>();
+    c.pu.t_total.start(s);
+    ELBA_HIP(hipMemsetAsync(c.pu.ctr.p, 0, 128, s));
     ELBA_HIP(hipMemsetAsync(p.ctr + 2, 0xff, 8, s));
     if (n > 0) hipLaunchKernelGGL(k_pu_emit, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, p);
     ELBA_HIP(hipGetLastError());
     unsigned long long h[16] = {0};
-    ELBA_HIP(hipMemcpyAsync(h, c.pu_ctr.p, 128, hipMemcpyDeviceToHost, s));
+    ELBA_HIP(hipMemcpyAsync(h, c.pu.ctr.p, 128, hipMemcpyDeviceToHost, s));
     ELBA_HIP(hipStreamSynchronize(s));
-    if (h[2] != ~0ull) {
-        const int64_t a = (int64_t)h[2];
-        int64_t r = 0, col = 0; elba_overlap_t o{};
-        ELBA_HIP(hipMemcpyAsync(&r, in.rows + a, 8, hipMemcpyDeviceToHost, s));
-        ELBA_HIP(hipMemcpyAsync(&col, in.cols + a, 8, hipMemcpyDeviceToHost, s));
-        ELBA_HIP(hipMemcpyAsync(&o, in.vals + a, sizeof(o), hipMemcpyDeviceToHost, s));
-        ELBA_HIP(hipStreamSynchronize(s));
-        throw Error{ELBA_ERR_INVALID_ARG, "read_pileup: pair " + std::to_string(a) + " (" + std::to_string(r) + ", " + std::to_string(col) + ") has an interval outside [0, len] or with beg > end: Q [" +
-                                              std::to_string(o.begQ) + ", " + std::to_string(o.endQ) + "), T [" + std::to_string(o.begT) + ", " + std::to_string(o.endT) + ")"};
-    }
+    if (h[2] != ~0ull) throw_bad_pair(c, in, (int64_t)h[2], "read_pileup");
     const int64_t E = 2 * (int64_t)h[1];                        // endpoints
     depth_segments(c, db, E, M, mb, pb, in.len, p.ctr);
     if (M > 0)
-        hipLaunchKernelGGL(k_pu_reads, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, c.pu_seg_off.as<int64_t>(), c.pu_seg_start.as<int32_t>(),
-                           c.pu_seg_depth.as<int32_t>(), in.len, (uint32_t)M, cfg.min_depth, cfg.min_run, cfg.trim_len, c.pu_trim.as<int2>(), c.pu_flags.as<uint8_t>(), p.ctr);
+        hipLaunchKernelGGL(k_pu_reads, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, db.seg_off.as<int64_t>(), db.seg_start.as<int32_t>(),
+                           db.seg_depth.as<int32_t>(), in.len, (uint32_t)M, cfg.min_depth, cfg.min_run, cfg.trim_len, c.pu.trim.as<int2>(), c.pu.flags.as<uint8_t>(), p.ctr);
     ELBA_HIP(hipGetLastError());
-    c.pu_t_total.stop(s);
-    ELBA_HIP(hipMemcpyAsync(h, c.pu_ctr.p, 128, hipMemcpyDeviceToHost, s));
+    c.pu.t_total.stop(s);
+    ELBA_HIP(hipMemcpyAsync(h, c.pu.ctr.p, 128, hipMemcpyDeviceToHost, s));
     ELBA_HIP(hipStreamSynchronize(s));
     elba_pileup_stats st{};
     st.nreads = M; st.pairs = (int64_t)h[0]; st.intervals = (int64_t)h[1]; st.segments = (int64_t)h[3]; st.max_depth = (int64_t)h[4];
     st.unsupported = (int64_t)h[5]; st.split = (int64_t)h[6]; st.trimmed = (int64_t)h[7]; st.trimmed_bases = (int64_t)h[8];
-    st.ms_total = c.pu_t_total.ms();
-    c.pu_M = M; c.pu_nseg = st.segments; c.pu_n = n; c.pustats = st; c.pu_cfg = cfg; done(c.v, EV_READ_PILEUP);
+    st.ms_total = c.pu.t_total.ms();
+    c.pu.M = M; c.pu.nseg = st.segments; c.pu.n = n; c.pu.stats = st; c.pu.cfg = cfg; done(c.v, EV_READ_PILEUP);
 }
 
 void stage_prune_reads(Ctx &c, int mask, int64_t *kept)
@@ -375,24 +373,24 @@ void stage_prune_reads(Ctx &c, int mask, int64_t *kept)
     ELBA_REQUIRE(mask >= 0 && mask <= 255, ELBA_ERR_INVALID_ARG, "prune_reads: mask must fit in one byte");
     ELBA_REQUIRE(has(c.v, P_PILEUP), ELBA_ERR_STATE, "prune_reads: no pileup of the current overlaps (call elba_read_pileup)");
     const PuInput in = pileup_input(c, "prune_reads");
-    ELBA_REQUIRE(in.M == c.pu_M && in.n == c.pu_n, ELBA_ERR_STATE, "prune_reads: the pileup was computed on other overlaps");
+    ELBA_REQUIRE(in.M == c.pu.M && in.n == c.pu.n, ELBA_ERR_STATE, "prune_reads: the pileup was computed on other overlaps");
     accepted(c.v, EV_PRUNE_READS);
     hipStream_t s = c.stream;
     const int64_t n = in.n;
-    c.pu_sel.reserve((size_t)(2 * n + 4) * 4);
-    c.pu_rows.reserve((size_t)(n + 1) * 8); c.pu_cols.reserve((size_t)(n + 1) * 8); c.pu_vals.reserve((size_t)(n + 1) * sizeof(elba_overlap_t));
-    uint32_t *sel = c.pu_sel.as<uint32_t>(), *pos = sel + (n + 2);
+    c.pu.sel.reserve((size_t)(2 * n + 4) * 4);
+    c.pu.rows.reserve((size_t)(n + 1) * 8); c.pu.cols.reserve((size_t)(n + 1) * 8); c.pu.vals.reserve((size_t)(n + 1) * sizeof(elba_overlap_t));
+    uint32_t *sel = c.pu.sel.as<uint32_t>(), *pos = sel + (n + 2);
     uint32_t total = 0;
-    hipLaunchKernelGGL(k_pu_prune_select, dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, s, in.rows, in.cols, n, c.pu_flags.as<uint8_t>(), (uint8_t)mask, sel);
+    hipLaunchKernelGGL(k_pu_prune_select, dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, s, in.rows, in.cols, n, c.pu.flags.as<uint8_t>(), (uint8_t)mask, sel);
     exclusive_scan_u32(s, sel, pos, n + 1, c.ws_scan);
     if (n > 0)
-        hipLaunchKernelGGL(k_pu_prune_scatter, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, in.rows, in.cols, in.vals, n, sel, pos, c.pu_rows.as<int64_t>(),
-                           c.pu_cols.as<int64_t>(), c.pu_vals.as<elba_overlap_t>());
+        hipLaunchKernelGGL(k_pu_prune_scatter, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, in.rows, in.cols, in.vals, n, sel, pos, c.pu.rows.as<int64_t>(),
+                           c.pu.cols.as<int64_t>(), c.pu.vals.as<elba_overlap_t>());
     ELBA_HIP(hipGetLastError());
     ELBA_HIP(hipMemcpyAsync(&total, pos + n, 4, hipMemcpyDeviceToHost, s));
     ELBA_HIP(hipStreamSynchronize(s));
     // the kept pairs become the loaded edge list (elba_set_overlaps' buffers); the context's own alignments stay as they are
-    c.tr_in_rows.swap(c.pu_rows); c.tr_in_cols.swap(c.pu_cols); c.tr_in_vals.swap(c.pu_vals);
+    c.tr_in_rows.swap(c.pu.rows); c.tr_in_cols.swap(c.pu.cols); c.tr_in_vals.swap(c.pu.vals);
     c.tr_in_M = in.M; c.tr_in_n = total;
     done(c.v, EV_PRUNE_READS);
     if (kept) *kept = total;

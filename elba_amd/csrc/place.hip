@@ -2,8 +2,8 @@
 // The contig stage places the reads of its chains; everything the graph lost on the way — contained reads, reads a cleaning call removed,
 // branches, reads whose edges the reduction dropped — is placed here through ONE aligned pair with a chain read, the best-scoring one.
 //
-// Input, all resident: of the last contig call the read map cg_cid, the chain arrays cg_eread / cg_estr / cg_eboff, the offsets cg_soff /
-// cg_coff and the kinds; the read flags of the reduction and the cleaning calls (tr_flags); the read lengths; and the pairs the graph was
+// Input, all resident: of the last contig call the read map cg.cid, the chain arrays cg.eread / cg.estr / cg.eboff, the offsets cg.soff /
+// cg.coff and the kinds; the read flags of the reduction and the cleaning calls (tr_flags); the read lengths; and the pairs the graph was
 // built from (graph_input: the loaded edge list, else the context's alignments), which the reduction read and left as they were.
 //
 // The launches up to and including k_pl_place are place_records(), which elba_polish_contigs (polish.hip) calls for the same records.
@@ -22,7 +22,7 @@
 //                    kind (1 = start), in slot pairs drawn per wavefront with one atomic; the credited bases summed per wavefront; a wrapped
 //                    read, whose two intervals would count it twice below, takes 1 off its contig's read count (an integer atomic: exact)
 //   -- the one host synchronisation: the endpoint count E (and the bounds check) --
-//   depth_segments   pileup.hip's sequence on the pl_* buffers with the contig lengths as `len`: radix sort of the E keys, group offsets,
+//   depth_segments   pileup.hip's sequence on the buffers of c.pl.depth with the contig lengths as `len`: radix sort of the E keys, group offsets,
 //                    k_pu_marks, two scans, k_pu_groups, k_pu_tokens, scan, k_pu_segs
 //   k_pl_credit      one lane per sorted key: start keys count 1 read and -pos bases, end keys +pos; a segmented scan over the wavefront by
 //                    contig (the keys are sorted, a contig's keys are consecutive), the last lane of every run adds the run's two sums to
@@ -216,14 +216,6 @@ __global__ void k_pl_credit(const uint64_t *keys, int64_t E, int pb, unsigned lo
     }
 }
 
-template <class T>
-T *pl_host(size_t n)
-{
-    T *p = static_cast<T *>(malloc((n ? n : 1) * sizeof(T)));
-    if (!p) throw std::bad_alloc();
-    return p;
-}
-
 }  // namespace
 
 static_assert(PC_BAD == PLACE_CTR_BAD && PC_N == PLACE_CTR_WORDS, "common.hpp names the counters of place_records");
@@ -233,102 +225,81 @@ PlaceWork place_records(Ctx &c, int skip_flags, const char *who_, bool depth_buf
     const std::string who(who_);
     ELBA_REQUIRE(has(c.v, P_S, P_CONTIGS), ELBA_ERR_STATE, who + ": no contigs of the current string graph (call elba_generate_contigs)");
     const GraphInput in = graph_input(c, who_);
-    const int64_t M = c.tr_M, base = c.tr_id_base, E = c.cg_E, nc = c.cg_n, n = in.n;
+    const int64_t M = c.tr_M, base = c.tr_id_base, E = c.cg.E, nc = c.cg.n, n = in.n;
     ELBA_REQUIRE(in.M == M && in.id_base == base, ELBA_ERR_STATE, who + ": the pairs on this context are not the ones the string graph was built from");
     const ReadSource src = read_source(c, M, who_, "lengths of the graph's # reads", base == 0);
     ELBA_REQUIRE(M + base < 0xFFFFFFFFll && n < 0xFFFFFFFFll, ELBA_ERR_UNSUPPORTED, who + ": read ids or pairs beyond 32 bit");
-    ELBA_REQUIRE(c.cstats.longest < (1ll << 31), ELBA_ERR_UNSUPPORTED, who + ": a contig of 2^31 bases or more");
+    ELBA_REQUIRE(c.cg.stats.longest < (1ll << 31), ELBA_ERR_UNSUPPORTED, who + ": a contig of 2^31 bases or more");
     ELBA_REQUIRE(4 * M + nc < 0xfffffff0ll, ELBA_ERR_UNSUPPORTED, who + ": 4 x reads + contigs reach 2^32");
     hipStream_t s = c.stream;
-    if (depth_bufs) {
-        const DepthBufs db{c.pl_k0, c.pl_k1, c.pl_eptr, c.pl_head, c.pl_hidx, c.pl_delta, c.pl_dsum, c.pl_gstart, c.pl_tok, c.pl_tpos, c.pl_seg_off, c.pl_seg_start, c.pl_seg_depth};
-        depth_reserve(db, 4 * M, nc);                           // at most two intervals of two endpoints per read
-    }
-    c.pl_cstart.reserve((size_t)(M + 1) * 8); c.pl_cstrand.reserve((size_t)M + 4); c.pl_best.reserve((size_t)(M + 1) * 8);
-    c.pl_rec.reserve((size_t)(M + 1) * sizeof(elba_placement_t)); c.pl_clen.reserve((size_t)(nc + 1) * 4); c.pl_cred.reserve((size_t)(2 * nc + 2) * 8);
-    c.pl_ctr.reserve(PC_N * 8);
-    unsigned long long *ctr = c.pl_ctr.as<unsigned long long>(), *best = c.pl_best.as<unsigned long long>();
-    elba_placement_t *rec = c.pl_rec.as<elba_placement_t>();
-    PlIn g{in.rows, in.cols, in.vals, n, c.cg_cid.as<int32_t>(), c.tr_flags.as<uint8_t>(), src.len, c.pl_cstart.as<int64_t>(), c.pl_cstrand.as<uint8_t>(),
-           c.pl_clen.as<uint32_t>(), c.cg_kind.as<uint8_t>(), (uint32_t)M, (uint32_t)base, skip_flags};
+    if (depth_bufs) c.pl.depth.reserve(4 * M, nc);              // at most two intervals of two endpoints per read
+    c.pl.cstart.reserve((size_t)(M + 1) * 8); c.pl.cstrand.reserve((size_t)M + 4); c.pl.best.reserve((size_t)(M + 1) * 8);
+    c.pl.rec.reserve((size_t)(M + 1) * sizeof(elba_placement_t)); c.pl.clen.reserve((size_t)(nc + 1) * 4); c.pl.cred.reserve((size_t)(2 * nc + 2) * 8);
+    c.pl.ctr.reserve(PC_N * 8);
+    unsigned long long *ctr = c.pl.ctr.as<unsigned long long>(), *best = c.pl.best.as<unsigned long long>();
+    elba_placement_t *rec = c.pl.rec.as<elba_placement_t>();
+    PlIn g{in.rows, in.cols, in.vals, n, c.cg.cid.as<int32_t>(), c.tr_flags.as<uint8_t>(), src.len, c.pl.cstart.as<int64_t>(), c.pl.cstrand.as<uint8_t>(),
+           c.pl.clen.as<uint32_t>(), c.cg.kind.as<uint8_t>(), (uint32_t)M, (uint32_t)base, skip_flags};
     if (t) t->start(s);
     ELBA_HIP(hipMemsetAsync(ctr, 0, PC_N * 8, s));
     ELBA_HIP(hipMemsetAsync(ctr + PC_BAD, 0xff, 8, s));
     ELBA_HIP(hipMemsetAsync(best, 0, (size_t)(M + 1) * 8, s));
-    ELBA_HIP(hipMemsetAsync(c.pl_cred.p, 0, (size_t)(2 * nc + 2) * 8, s));
+    ELBA_HIP(hipMemsetAsync(c.pl.cred.p, 0, (size_t)(2 * nc + 2) * 8, s));
     const int64_t nce = E > nc ? E : nc;
     if (nce > 0)
-        hipLaunchKernelGGL(k_pl_chain, dim3((unsigned)((nce + 255) / 256)), dim3(256), 0, s, c.cg_eread.as<int64_t>(), c.cg_estr.as<uint8_t>(), c.cg_eboff.as<int64_t>(),
-                           c.cg_cid.as<int32_t>(), c.cg_soff.as<int64_t>(), E, nc, base, (uint32_t)M, c.pl_cstart.as<int64_t>(), c.pl_cstrand.as<uint8_t>(), c.pl_clen.as<uint32_t>());
+        hipLaunchKernelGGL(k_pl_chain, dim3((unsigned)((nce + 255) / 256)), dim3(256), 0, s, c.cg.eread.as<int64_t>(), c.cg.estr.as<uint8_t>(), c.cg.eboff.as<int64_t>(),
+                           c.cg.cid.as<int32_t>(), c.cg.soff.as<int64_t>(), E, nc, base, (uint32_t)M, c.pl.cstart.as<int64_t>(), c.pl.cstrand.as<uint8_t>(), c.pl.clen.as<uint32_t>());
     if (n > 0) {                                                // (a grid that fills the device, every lane striding over the list: see the header)
         int64_t grid = (n + 255) / 256;
         if (grid > (int64_t)c.num_cus * 16) grid = (int64_t)c.num_cus * 16;
         hipLaunchKernelGGL(k_pl_candidates, dim3((unsigned)grid), dim3(256), 0, s, g, best, ctr);
     }
     if (M > 0) hipLaunchKernelGGL(k_pl_place, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, g, (const unsigned long long *)best, rec, ctr);
-    return PlaceWork{in, src, M, base, E, nc, rec, ctr, c.pl_clen.as<uint32_t>()};
-}
-
-void place_throw_bad_pair(Ctx &c, const PlaceWork &w, int64_t a, const char *who)
-{
-    hipStream_t s = c.stream;
-    int64_t r = 0, col = 0; elba_overlap_t o{};
-    ELBA_HIP(hipMemcpyAsync(&r, w.in.rows + a, 8, hipMemcpyDeviceToHost, s));
-    ELBA_HIP(hipMemcpyAsync(&col, w.in.cols + a, 8, hipMemcpyDeviceToHost, s));
-    ELBA_HIP(hipMemcpyAsync(&o, w.in.vals + a, sizeof(o), hipMemcpyDeviceToHost, s));
-    ELBA_HIP(hipStreamSynchronize(s));
-    throw Error{ELBA_ERR_INVALID_ARG, std::string(who) + ": pair " + std::to_string(a) + " (" + std::to_string(r) + ", " + std::to_string(col) + ") has an interval outside [0, len] or with beg > end: Q [" +
-                                          std::to_string(o.begQ) + ", " + std::to_string(o.endQ) + "), T [" + std::to_string(o.begT) + ", " + std::to_string(o.endT) + ")"};
+    return PlaceWork{in, src, M, base, E, nc, rec, ctr, c.pl.clen.as<uint32_t>()};
 }
 
 void stage_place_reads(Ctx &c, const elba_place_cfg *cfg, elba_placements_t *out)
 {
-    c.pl_for = 0;                                               // (whatever this call ends in, the counts of the one before are gone)
+    c.pl.for_cg = 0;                                               // (whatever this call ends in, the counts of the one before are gone)
     ELBA_REQUIRE(cfg, ELBA_ERR_INVALID_ARG, "place_reads: null cfg");
     ELBA_REQUIRE(!cfg->reserved[0] && !cfg->reserved[1] && !cfg->reserved[2], ELBA_ERR_INVALID_ARG, "place_reads: reserved words must be 0");
     ELBA_REQUIRE(cfg->skip_flags >= 0 && cfg->skip_flags <= 255, ELBA_ERR_INVALID_ARG, "place_reads: skip_flags must fit in one byte");
-    const PlaceWork w = place_records(c, cfg->skip_flags, "place_reads", true, &c.pl_t_total);
+    const PlaceWork w = place_records(c, cfg->skip_flags, "place_reads", true, &c.pl.t_total);
     const ReadSource &src = w.src;
     const int64_t M = w.M, nc = w.nc;
     hipStream_t s = c.stream;
     int mb = 1, pb = 1;
     while ((1ll << mb) < nc + 1) ++mb;
-    while ((1ll << pb) < c.cstats.longest + 1) ++pb;            // positions 0 .. length
-    const DepthBufs db{c.pl_k0, c.pl_k1, c.pl_eptr, c.pl_head, c.pl_hidx, c.pl_delta, c.pl_dsum, c.pl_gstart, c.pl_tok, c.pl_tpos, c.pl_seg_off, c.pl_seg_start, c.pl_seg_depth};
+    while ((1ll << pb) < c.cg.stats.longest + 1) ++pb;            // positions 0 .. length
+    DepthBufs &db = c.pl.depth;
     unsigned long long *ctr = w.ctr;
-    unsigned long long *cred_reads = c.pl_cred.as<unsigned long long>(), *cred_bases = cred_reads + nc;
+    unsigned long long *cred_reads = c.pl.cred.as<unsigned long long>(), *cred_bases = cred_reads + nc;
     elba_placement_t *rec = w.rec;
     if (M > 0)
-        hipLaunchKernelGGL(k_pl_emit, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, (const elba_placement_t *)rec, src.len, c.pl_clen.as<uint32_t>(), c.cg_kind.as<uint8_t>(), (uint32_t)M, pb,
-                           c.pl_k0.as<uint64_t>(), cred_reads, ctr);
+        hipLaunchKernelGGL(k_pl_emit, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, (const elba_placement_t *)rec, src.len, c.pl.clen.as<uint32_t>(), c.cg.kind.as<uint8_t>(), (uint32_t)M, pb,
+                           db.k0.as<uint64_t>(), cred_reads, ctr);
     ELBA_HIP(hipGetLastError());
     unsigned long long h[PC_N] = {0};
     ELBA_HIP(hipMemcpyAsync(h, ctr, PC_N * 8, hipMemcpyDeviceToHost, s));
     ELBA_HIP(hipStreamSynchronize(s));
-    if (h[PC_BAD] != ~0ull) place_throw_bad_pair(c, w, (int64_t)h[PC_BAD], "place_reads");
+    if (h[PC_BAD] != ~0ull) throw_bad_pair(c, w.in, (int64_t)h[PC_BAD], "place_reads");
     const int64_t K = 2 * (int64_t)h[PC_INT];                   // endpoints
     ELBA_REQUIRE(K <= 4 * M, ELBA_ERR_INTERNAL, "place_reads: more endpoints than four per read");
-    const uint64_t *keys = depth_segments(c, db, K, nc, mb, pb, c.pl_clen.as<uint32_t>(), ctr);
+    const uint64_t *keys = depth_segments(c, db, K, nc, mb, pb, c.pl.clen.as<uint32_t>(), ctr);
     if (K > 0) hipLaunchKernelGGL(k_pl_credit, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, s, keys, K, pb, cred_reads, cred_bases);
     ELBA_HIP(hipGetLastError());
-    c.pl_t_total.stop(s);
+    c.pl.t_total.stop(s);
     // the segments are at most one per endpoint and one per contig: the copies are queued at that size, the count comes back with them
     const int64_t segcap = K + nc;
     elba_placements_t &o = *out;                                // (zeroed by the caller; every block lands in it at once, so that elba_free_placements releases what a failed allocation or copy leaves)
     o.nreads = M; o.ncontigs = nc;
-    o.reads = pl_host<elba_placement_t>((size_t)M); o.seg_off = pl_host<int64_t>((size_t)nc + 1);
-    o.seg_start = pl_host<int32_t>((size_t)segcap); o.seg_depth = pl_host<int32_t>((size_t)segcap);
-    o.credited_reads = pl_host<int64_t>((size_t)nc); o.credited_bases = pl_host<int64_t>((size_t)nc);
-    if (M) ELBA_HIP(hipMemcpyAsync(o.reads, rec, (size_t)M * sizeof(elba_placement_t), hipMemcpyDeviceToHost, s));
-    ELBA_HIP(hipMemcpyAsync(o.seg_off, c.pl_seg_off.p, (size_t)(nc + 1) * 8, hipMemcpyDeviceToHost, s));
-    if (segcap) {
-        ELBA_HIP(hipMemcpyAsync(o.seg_start, c.pl_seg_start.p, (size_t)segcap * 4, hipMemcpyDeviceToHost, s));
-        ELBA_HIP(hipMemcpyAsync(o.seg_depth, c.pl_seg_depth.p, (size_t)segcap * 4, hipMemcpyDeviceToHost, s));
-    }
-    if (nc) {
-        ELBA_HIP(hipMemcpyAsync(o.credited_reads, cred_reads, (size_t)nc * 8, hipMemcpyDeviceToHost, s));
-        ELBA_HIP(hipMemcpyAsync(o.credited_bases, cred_bases, (size_t)nc * 8, hipMemcpyDeviceToHost, s));
-    }
+    o.reads = host_block<elba_placement_t>((size_t)M); o.seg_off = host_block<int64_t>((size_t)nc + 1);
+    o.seg_start = host_block<int32_t>((size_t)segcap); o.seg_depth = host_block<int32_t>((size_t)segcap);
+    o.credited_reads = host_block<int64_t>((size_t)nc); o.credited_bases = host_block<int64_t>((size_t)nc);
+    copy_out(c, o.reads, rec, (size_t)M);
+    copy_out(c, o.seg_off, db.seg_off.p, (size_t)nc + 1);
+    copy_out(c, o.seg_start, db.seg_start.p, (size_t)segcap); copy_out(c, o.seg_depth, db.seg_depth.p, (size_t)segcap);
+    copy_out(c, o.credited_reads, cred_reads, (size_t)nc); copy_out(c, o.credited_bases, cred_bases, (size_t)nc);
     ELBA_HIP(hipMemcpyAsync(h, ctr, PC_N * 8, hipMemcpyDeviceToHost, s));
     ELBA_HIP(hipStreamSynchronize(s));
     ELBA_REQUIRE((int64_t)h[PC_SEGS] <= segcap && o.seg_off[nc] == (int64_t)h[PC_SEGS], ELBA_ERR_INTERNAL, "place_reads: the segment offsets do not end at the segment count");
@@ -336,8 +307,8 @@ void stage_place_reads(Ctx &c, const elba_place_cfg *cfg, elba_placements_t *out
     st.nreads = M; st.chain = (int64_t)h[PC_CHAIN]; st.anchored = (int64_t)h[PC_ANCH]; st.unanchored = (int64_t)h[PC_UNANCH]; st.skipped = (int64_t)h[PC_SKIP];
     st.empty = (int64_t)h[PC_EMPTY]; st.candidates = (int64_t)h[PC_CAND]; st.clipped = (int64_t)h[PC_CLIP]; st.outside = (int64_t)h[PC_OUT]; st.wrapped = (int64_t)h[PC_WRAP];
     st.segments = (int64_t)h[PC_SEGS]; st.max_depth = (int64_t)h[PC_DEPTH]; st.credited_bases = (int64_t)h[PC_BASES];
-    st.ms_total = c.pl_t_total.ms();
-    c.plstats = st; c.pl_for = c.cg_serial;
+    st.ms_total = c.pl.t_total.ms();
+    c.pl.stats = st; c.pl.for_cg = c.cg.serial;
 }
 
 }  // namespace elba

@@ -4,7 +4,7 @@
 // the contig), the alignments vote per column and per gap, and the columns are called.
 //
 // Input, all resident: the records of place.hip's place_records (the same launches elba_place_reads runs), the packed reads, of the last
-// contig call cg_seq / cg_soff / cg_kind.
+// contig call cg.seq / cg.soff / cg.kind.
 //
 //   k_po_plan      one lane per read: voter or not, its slice (rows n, first base i0, first column st), the record's first fields; the
 //                  rows go through one exclusive scan: the row offset of every voter's choices
@@ -24,7 +24,7 @@
 //                  of 64 rows of choices (1 KiB x C, coalesced) and their 64 read bases go to LDS, lane 0 walks back through them and issues
 //                  one integer atomic per vote; a run of up steps is held until the step behind it is known, also across blocks
 //   k_po_call      one lane per column slot (every contig has L + 1: slot c holds gap c and column c, slot L the gap behind the last
-//                  column): the contig by binary search in cg_soff, the five counts of the column and of its left neighbour, 0 .. 2 bases
+//                  column): the contig by binary search in cg.soff, the five counts of the column and of its left neighbour, 0 .. 2 bases
 //   scan           exclusive_scan_u32_to_i64 (prims.hip) over the slots' counts
 //   k_po_write     one lane per slot: its bases at its offset; one lane per contig: seq_off
 //   -- host synchronisation 2: the output size --
@@ -62,7 +62,7 @@ struct PoIn {
 };
 
 __device__ __forceinline__ int po_read_base(const uint8_t *mem, uint32_t i) { return (mem[i >> 2] >> (6 - 2 * (i & 3))) & 3; }    // the layout of align.hip's base_at
-// the code of contig position pos (0 A, 1 C, 2 G, 3 T from the ASCII bytes of cg_seq), 4 where a path contig has no such column
+// the code of contig position pos (0 A, 1 C, 2 G, 3 T from the ASCII bytes of cg.seq), 4 where a path contig has no such column
 __device__ __forceinline__ int po_contig_code(const char *s, int pos, int L, bool circ)
 {
     if (circ) { pos %= L; if (pos < 0) pos += L; }
@@ -317,14 +317,6 @@ __global__ void k_po_write(const uint32_t *cnt, const uint32_t *emit, const int6
     if (n >= 2) out[o + 1] = (char)((w >> 8) & 0xff);
 }
 
-template <class T>
-T *po_host(size_t n)
-{
-    T *p = static_cast<T *>(malloc((n ? n : 1) * sizeof(T)));
-    if (!p) throw std::bad_alloc();
-    return p;
-}
-
 template <int C>
 void po_launch_batch(hipStream_t s, const PoIn &g, unsigned long long *trace, elba_polish_read_t *rec, uint32_t *col, uint32_t *gap, unsigned long long *cstat, unsigned long long *ctr,
                      hipEvent_t e0, hipEvent_t e1)
@@ -346,7 +338,7 @@ struct PoEvents {
 
 void stage_polish_contigs(Ctx &c, const elba_polish_cfg *cfg, elba_polished_t *out)
 {
-    c.po_for = 0;                                               // (whatever this call ends in, the counts of the one before are gone)
+    c.po.for_cg = 0;                                               // (whatever this call ends in, the counts of the one before are gone)
     ELBA_REQUIRE(cfg, ELBA_ERR_INVALID_ARG, "polish_contigs: null cfg");
     ELBA_REQUIRE(!cfg->reserved[0] && !cfg->reserved[1] && !cfg->reserved[2], ELBA_ERR_INVALID_ARG, "polish_contigs: reserved words must be 0");
     ELBA_REQUIRE(cfg->skip_flags >= 0 && cfg->skip_flags <= 255, ELBA_ERR_INVALID_ARG, "polish_contigs: skip_flags must fit in one byte");
@@ -354,27 +346,27 @@ void stage_polish_contigs(Ctx &c, const elba_polish_cfg *cfg, elba_polished_t *o
     ELBA_REQUIRE(cfg->max_diff_q16 >= 0 && cfg->max_diff_q16 <= 65536, ELBA_ERR_INVALID_ARG, "polish_contigs: max_diff_q16 is 0 .. 65536");
     ELBA_REQUIRE(cfg->min_depth >= 1, ELBA_ERR_INVALID_ARG, "polish_contigs: min_depth is at least 1");
     ELBA_REQUIRE((cfg->flags & ~ELBA_POLISH_EXPORT_VOTES) == 0, ELBA_ERR_INVALID_ARG, "polish_contigs: unknown flags");
-    const PlaceWork w = place_records(c, cfg->skip_flags, "polish_contigs", false, &c.po_t_total);
-    const int64_t M = w.M, nc = w.nc, bases = c.cg_bases, X = bases + nc;
+    const PlaceWork w = place_records(c, cfg->skip_flags, "polish_contigs", false, &c.po.t_total);
+    const int64_t M = w.M, nc = w.nc, bases = c.cg.bases, X = bases + nc;
     const int W = cfg->band;
-    ELBA_REQUIRE(c.cstats.longest < (1ll << 30), ELBA_ERR_UNSUPPORTED, "polish_contigs: a contig of 2^30 bases or more");
+    ELBA_REQUIRE(c.cg.stats.longest < (1ll << 30), ELBA_ERR_UNSUPPORTED, "polish_contigs: a contig of 2^30 bases or more");
     ELBA_REQUIRE(5 * bases + 4 * nc < 0xfffffff0ll, ELBA_ERR_UNSUPPORTED, "polish_contigs: 5 x contig bases + 4 x contigs reach 2^32");
     hipStream_t s = c.stream;
-    c.po_plan.reserve((size_t)(M + 1) * sizeof(PoPlan)); c.po_rec.reserve((size_t)(M + 1) * sizeof(elba_polish_read_t)); c.po_cnt.reserve((size_t)((M > X ? M : X) + 2) * 4);
-    c.po_toff.reserve((size_t)(M + 2) * 8); c.po_col.reserve((size_t)(5 * bases + 8) * 4); c.po_gap.reserve((size_t)(4 * X + 8) * 4); c.po_emit.reserve((size_t)(X + 2) * 4);
-    c.po_off.reserve((size_t)(X + 2) * 8); c.po_cstat.reserve((size_t)(4 * nc + 4) * 8); c.po_seqoff.reserve((size_t)(nc + 2) * 8); c.po_ctr.reserve(PQ_N * 8);
-    PoPlan *plan = c.po_plan.as<PoPlan>();
-    elba_polish_read_t *rec = c.po_rec.as<elba_polish_read_t>();
-    uint32_t *cnt = c.po_cnt.as<uint32_t>(), *col = c.po_col.as<uint32_t>(), *gap = c.po_gap.as<uint32_t>(), *emit = c.po_emit.as<uint32_t>();
-    int64_t *toff = c.po_toff.as<int64_t>(), *off = c.po_off.as<int64_t>(), *seqoff = c.po_seqoff.as<int64_t>();
-    unsigned long long *cstat = c.po_cstat.as<unsigned long long>(), *ctr = c.po_ctr.as<unsigned long long>();
+    c.po.plan.reserve((size_t)(M + 1) * sizeof(PoPlan)); c.po.rec.reserve((size_t)(M + 1) * sizeof(elba_polish_read_t)); c.po.cnt.reserve((size_t)((M > X ? M : X) + 2) * 4);
+    c.po.toff.reserve((size_t)(M + 2) * 8); c.po.col.reserve((size_t)(5 * bases + 8) * 4); c.po.gap.reserve((size_t)(4 * X + 8) * 4); c.po.emit.reserve((size_t)(X + 2) * 4);
+    c.po.off.reserve((size_t)(X + 2) * 8); c.po.cstat.reserve((size_t)(4 * nc + 4) * 8); c.po.seqoff.reserve((size_t)(nc + 2) * 8); c.po.ctr.reserve(PQ_N * 8);
+    PoPlan *plan = c.po.plan.as<PoPlan>();
+    elba_polish_read_t *rec = c.po.rec.as<elba_polish_read_t>();
+    uint32_t *cnt = c.po.cnt.as<uint32_t>(), *col = c.po.col.as<uint32_t>(), *gap = c.po.gap.as<uint32_t>(), *emit = c.po.emit.as<uint32_t>();
+    int64_t *toff = c.po.toff.as<int64_t>(), *off = c.po.off.as<int64_t>(), *seqoff = c.po.seqoff.as<int64_t>();
+    unsigned long long *cstat = c.po.cstat.as<unsigned long long>(), *ctr = c.po.ctr.as<unsigned long long>();
     ELBA_HIP(hipMemsetAsync(ctr, 0, PQ_N * 8, s));
     ELBA_HIP(hipMemsetAsync(cstat, 0, (size_t)(4 * nc + 4) * 8, s));
     ELBA_HIP(hipMemsetAsync(col, 0, (size_t)(5 * bases + 8) * 4, s));
     ELBA_HIP(hipMemsetAsync(gap, 0, (size_t)(4 * X + 8) * 4, s));
     ELBA_HIP(hipMemsetAsync(cnt, 0, (size_t)(M + 2) * 4, s));
     if (M > 0)
-        hipLaunchKernelGGL(k_po_plan, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, (const elba_placement_t *)w.rec, w.src.len, w.clen, c.cg_kind.as<uint8_t>(), (uint32_t)M, plan, cnt, rec, ctr);
+        hipLaunchKernelGGL(k_po_plan, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, (const elba_placement_t *)w.rec, w.src.len, w.clen, c.cg.kind.as<uint8_t>(), (uint32_t)M, plan, cnt, rec, ctr);
     exclusive_scan_u32_to_i64(s, cnt, toff, M + 1, c.ws_scan);
     ELBA_HIP(hipGetLastError());
     // synchronisation 1: the row offsets of the voters' choices, place_records' bad-pair word, the reads that are too long
@@ -384,14 +376,14 @@ void stage_polish_contigs(Ctx &c, const elba_polish_cfg *cfg, elba_polished_t *o
     ELBA_HIP(hipMemcpyAsync(hp, w.ctr, PLACE_CTR_WORDS * 8, hipMemcpyDeviceToHost, s));
     ELBA_HIP(hipMemcpyAsync(hq, ctr, PQ_N * 8, hipMemcpyDeviceToHost, s));
     ELBA_HIP(hipStreamSynchronize(s));
-    if (hp[PLACE_CTR_BAD] != ~0ull) place_throw_bad_pair(c, w, (int64_t)hp[PLACE_CTR_BAD], "polish_contigs");
+    if (hp[PLACE_CTR_BAD] != ~0ull) throw_bad_pair(c, w.in, (int64_t)hp[PLACE_CTR_BAD], "polish_contigs");
     ELBA_REQUIRE(hq[PQ_LONG] == 0, ELBA_ERR_UNSUPPORTED, "polish_contigs: a placed read of 2^24 bases or more");
     // the batches: consecutive reads whose choices fit the cap; a read that alone exceeds it is a batch of its own
     int64_t cap = c.opt.polish_trace_bytes;
     if (cap <= 0) {
         size_t free_b = 0, total_b = 0;
         ELBA_HIP(hipMemGetInfo(&free_b, &total_b));
-        cap = (int64_t)((free_b + c.po_trace.cap) / 8);
+        cap = (int64_t)((free_b + c.po.trace.cap) / 8);
         if (cap < (64ll << 20)) cap = 64ll << 20;
     }
     const int64_t row_bytes = W / 4, cap_rows = cap / row_bytes;
@@ -405,11 +397,11 @@ void stage_polish_contigs(Ctx &c, const elba_polish_cfg *cfg, elba_polished_t *o
         if (rows > 0) { batches.emplace_back((uint32_t)ra, (uint32_t)rb); if (rows > most) most = rows; }
         ra = rb;
     }
-    c.po_trace.reserve((size_t)most * row_bytes + 64);
+    c.po.trace.reserve((size_t)most * row_bytes + 64);
     PoEvents ev;
     ev.grow(2 * batches.size());
-    PoIn g{w.rec, plan, toff, w.src.packed, w.src.byte_off, w.src.len, c.cg_seq.as<char>(), c.cg_soff.as<int64_t>(), c.cg_kind.as<uint8_t>(), 0, 0, 0, cfg->max_diff_q16};
-    unsigned long long *trace = c.po_trace.as<unsigned long long>();
+    PoIn g{w.rec, plan, toff, w.src.packed, w.src.byte_off, w.src.len, c.cg.seq.as<char>(), c.cg.soff.as<int64_t>(), c.cg.kind.as<uint8_t>(), 0, 0, 0, cfg->max_diff_q16};
+    unsigned long long *trace = c.po.trace.as<unsigned long long>();
     for (size_t b = 0; b < batches.size(); ++b) {
         g.ra = batches[b].first; g.rb = batches[b].second; g.tbase = h_toff[g.ra];
         if (W == 64) po_launch_batch<1>(s, g, trace, rec, col, gap, cstat, ctr, ev.e[2 * b], ev.e[2 * b + 1]);
@@ -418,50 +410,48 @@ void stage_polish_contigs(Ctx &c, const elba_polish_cfg *cfg, elba_polished_t *o
     }
     ELBA_HIP(hipMemsetAsync(cnt, 0, (size_t)(X + 2) * 4, s));
     if (X > 0 && nc > 0)
-        hipLaunchKernelGGL(k_po_call, dim3((unsigned)((X + 255) / 256)), dim3(256), 0, s, c.cg_seq.as<char>(), c.cg_soff.as<int64_t>(), c.cg_kind.as<uint8_t>(), nc, X, (const uint32_t *)col,
+        hipLaunchKernelGGL(k_po_call, dim3((unsigned)((X + 255) / 256)), dim3(256), 0, s, c.cg.seq.as<char>(), c.cg.soff.as<int64_t>(), c.cg.kind.as<uint8_t>(), nc, X, (const uint32_t *)col,
                            (const uint32_t *)gap, cfg->min_depth, cnt, emit, cstat, ctr);
     exclusive_scan_u32_to_i64(s, cnt, off, X + 1, c.ws_scan);
-    c.po_seq.reserve((size_t)(2 * X + 64));                     // (a slot emits two bases at most)
+    c.po.seq.reserve((size_t)(2 * X + 64));                     // (a slot emits two bases at most)
     if (nc > 0)
-        hipLaunchKernelGGL(k_po_write, dim3((unsigned)((X + 1 + 255) / 256)), dim3(256), 0, s, (const uint32_t *)cnt, (const uint32_t *)emit, (const int64_t *)off, c.cg_soff.as<int64_t>(), nc, X,
-                           c.po_seq.as<char>(), seqoff);
-    else ELBA_HIP(hipMemsetAsync(seqoff, 0, 8, s));             // (no contig: cg_soff may not be there)
+        hipLaunchKernelGGL(k_po_write, dim3((unsigned)((X + 1 + 255) / 256)), dim3(256), 0, s, (const uint32_t *)cnt, (const uint32_t *)emit, (const int64_t *)off, c.cg.soff.as<int64_t>(), nc, X,
+                           c.po.seq.as<char>(), seqoff);
+    else ELBA_HIP(hipMemsetAsync(seqoff, 0, 8, s));             // (no contig: cg.soff may not be there)
     ELBA_HIP(hipGetLastError());
-    c.po_t_total.stop(s);
+    c.po.t_total.stop(s);
     // synchronisation 2: the output size (with the offsets and the counts)
     const bool votes = (cfg->flags & ELBA_POLISH_EXPORT_VOTES) != 0;
     elba_polished_t &o = *out;                                  // (zeroed by the caller; every block lands in it at once, so that elba_free_polished releases what a failed allocation or copy leaves)
     o.n = nc; o.nreads = votes ? M : 0;
-    o.seq_off = po_host<int64_t>((size_t)nc + 1);
+    o.seq_off = host_block<int64_t>((size_t)nc + 1);
     std::vector<unsigned long long> h_cstat((size_t)(4 * nc + 4));
-    ELBA_HIP(hipMemcpyAsync(o.seq_off, seqoff, (size_t)(nc + 1) * 8, hipMemcpyDeviceToHost, s));
+    copy_out(c, o.seq_off, seqoff, (size_t)nc + 1);
     ELBA_HIP(hipMemcpyAsync(h_cstat.data(), cstat, (size_t)(4 * nc + 4) * 8, hipMemcpyDeviceToHost, s));
     ELBA_HIP(hipMemcpyAsync(hq, ctr, PQ_N * 8, hipMemcpyDeviceToHost, s));
     ELBA_HIP(hipStreamSynchronize(s));
     ELBA_REQUIRE(hq[PQ_ERR] == 0, ELBA_ERR_INTERNAL, "polish_contigs: a walk through the choices left its band or its contig");
     const int64_t after = o.seq_off[nc];
     ELBA_REQUIRE(after >= 0 && after <= 2 * X, ELBA_ERR_INTERNAL, "polish_contigs: the offsets do not end inside the polished bases");
-    o.seq = po_host<char>((size_t)after);
-    o.voters = po_host<int64_t>((size_t)nc); o.substituted = po_host<int64_t>((size_t)nc); o.deleted = po_host<int64_t>((size_t)nc); o.inserted = po_host<int64_t>((size_t)nc);
+    o.seq = host_block<char>((size_t)after);
+    o.voters = host_block<int64_t>((size_t)nc); o.substituted = host_block<int64_t>((size_t)nc); o.deleted = host_block<int64_t>((size_t)nc); o.inserted = host_block<int64_t>((size_t)nc);
     for (int64_t k = 0; k < nc; ++k) {
         o.voters[k] = (int64_t)h_cstat[(size_t)(4 * k)]; o.substituted[k] = (int64_t)h_cstat[(size_t)(4 * k + 1)];
         o.deleted[k] = (int64_t)h_cstat[(size_t)(4 * k + 2)]; o.inserted[k] = (int64_t)h_cstat[(size_t)(4 * k + 3)];
     }
-    if (after) ELBA_HIP(hipMemcpyAsync(o.seq, c.po_seq.p, (size_t)after, hipMemcpyDeviceToHost, s));
+    copy_out(c, o.seq, c.po.seq.p, (size_t)after);
     if (votes) {
-        o.col_off = po_host<int64_t>((size_t)nc + 1); o.col = po_host<uint32_t>((size_t)(5 * bases)); o.gap = po_host<uint32_t>((size_t)(4 * X)); o.reads = po_host<elba_polish_read_t>((size_t)M);
-        ELBA_HIP(hipMemcpyAsync(o.col_off, c.cg_soff.p, (size_t)(nc + 1) * 8, hipMemcpyDeviceToHost, s));
-        if (bases) ELBA_HIP(hipMemcpyAsync(o.col, col, (size_t)(5 * bases) * 4, hipMemcpyDeviceToHost, s));
-        if (X) ELBA_HIP(hipMemcpyAsync(o.gap, gap, (size_t)(4 * X) * 4, hipMemcpyDeviceToHost, s));
-        if (M) ELBA_HIP(hipMemcpyAsync(o.reads, rec, (size_t)M * sizeof(elba_polish_read_t), hipMemcpyDeviceToHost, s));
+        o.col_off = host_block<int64_t>((size_t)nc + 1); o.col = host_block<uint32_t>((size_t)(5 * bases)); o.gap = host_block<uint32_t>((size_t)(4 * X)); o.reads = host_block<elba_polish_read_t>((size_t)M);
+        copy_out(c, o.col_off, c.cg.soff.p, (size_t)nc + 1);
+        copy_out(c, o.col, col, (size_t)(5 * bases)); copy_out(c, o.gap, gap, (size_t)(4 * X)); copy_out(c, o.reads, rec, (size_t)M);
     }
     ELBA_HIP(hipStreamSynchronize(s));
     elba_polish_stats st{};
     st.nreads = M; st.voted = (int64_t)hq[PQ_VOTED]; st.rejected = (int64_t)hq[PQ_REJ]; st.outside = (int64_t)hq[PQ_OUT]; st.low_depth_columns = (int64_t)hq[PQ_LOW];
     st.bases_before = bases; st.bases_after = after; st.sum_dist = (int64_t)hq[PQ_DIST]; st.cells = h_toff[(size_t)M] * W; st.batches = (int64_t)batches.size();
-    st.ms_total = c.po_t_total.ms();
+    st.ms_total = c.po.t_total.ms();
     for (size_t b = 0; b < batches.size(); ++b) { float t = 0; ELBA_HIP(hipEventElapsedTime(&t, ev.e[2 * b], ev.e[2 * b + 1])); st.ms_align += t; }
-    c.postats = st; c.po_for = c.cg_serial;
+    c.po.stats = st; c.po.for_cg = c.cg.serial;
 }
 
 }  // namespace elba

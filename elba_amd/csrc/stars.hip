@@ -161,12 +161,12 @@ void stage_resolve_stars(Ctx &c, const elba_star_cfg *cfgp)
     sg_require_32bit(EV_RESOLVE_STARS, M < 0xffffffffll && n0 < 0xfffffffell && c.tr_sym_n < 0xffffffffll);
     elba_star_stats st = sg_stats_begin<elba_star_stats>(c);
     st.rounds_run = 1;
-    if (M == 0 || n0 == 0) { accepted(c.v, EV_RESOLVE_STARS); done(c.v, EV_RESOLVE_STARS); c.srstats = st; return; }      // no entry: no centre, the one round removes nothing
+    if (M == 0 || n0 == 0) { accepted(c.v, EV_RESOLVE_STARS); done(c.v, EV_RESOLVE_STARS); c.sr.stats = st; return; }      // no entry: no centre, the one round removes nothing
     // every buffer of the launch sequence before the first launch
     sg_reserve(c, M, n0);
-    c.sr_word.reserve((size_t)(M + 1) * 4);
+    c.sr.word.reserve((size_t)(M + 1) * 4);
     const SgCall w(c);
-    uint32_t *word = c.sr_word.as<uint32_t>();
+    uint32_t *word = c.sr.word.as<uint32_t>();
     // R as the reduction that made this S recorded it; without a kept pair tr_ptr holds nothing of this graph, and no read is looked up
     const uint32_t Rn = (uint32_t)c.tr_sym_n, RM = c.tr_sym_n > 0 ? (uint32_t)(c.tr_sym_M < M ? c.tr_sym_M : M) : 0u;
     const uint32_t *rptr = c.tr_ptr.as<uint32_t>();
@@ -183,7 +183,7 @@ void stage_resolve_stars(Ctx &c, const elba_star_cfg *cfgp)
     st.pairs3 = (int64_t)h[SR_PAIRS0 + 3]; st.reads_removed = (int64_t)h[SR_READS];
     st.rounds_run = moves < cfg.rounds ? moves + 1 : cfg.rounds;
     sg_stats_end(c, st);
-    c.srstats = st;
+    c.sr.stats = st;
 }
 
 }  // namespace elba

@@ -111,12 +111,12 @@ void stage_clip_tips(Ctx &c, const elba_tip_cfg *cfgp)
     sg_require_32bit(EV_CLIP_TIPS, M < 0xffffffffll && n0 < 0xfffffffell);
     elba_tip_stats st = sg_stats_begin<elba_tip_stats>(c);
     st.rounds_run = 1;
-    if (M == 0 || n0 == 0) { accepted(c.v, EV_CLIP_TIPS); done(c.v, EV_CLIP_TIPS); c.tpstats = st; return; }      // no entry: no dead end, the one round removes nothing
+    if (M == 0 || n0 == 0) { accepted(c.v, EV_CLIP_TIPS); done(c.v, EV_CLIP_TIPS); c.tp.stats = st; return; }      // no entry: no dead end, the one round removes nothing
     // every buffer of the launch sequence before the first launch
     sg_reserve(c, M, n0);
-    c.tp_ntips.reserve((size_t)(M + 1) * 4); c.tp_anchor.reserve((size_t)(M + 1) * 4);
+    c.tp.ntips.reserve((size_t)(M + 1) * 4); c.tp.anchor.reserve((size_t)(M + 1) * 4);
     const SgCall w(c);
-    uint32_t *ntips = c.tp_ntips.as<uint32_t>(), *anchor = c.tp_anchor.as<uint32_t>();
+    uint32_t *ntips = c.tp.ntips.as<uint32_t>(), *anchor = c.tp.anchor.as<uint32_t>();
     accepted(c.v, EV_CLIP_TIPS);                                // S changes under the contigs of the old one, and is itself invalid until the counters are back:
                                                                 // a call that fails below leaves no S rather than one in the wrong buffer
     u64 h[SG_ST];
@@ -129,7 +129,7 @@ void stage_clip_tips(Ctx &c, const elba_tip_cfg *cfgp)
     st.dead_ends = (int64_t)h[TP_DEAD]; st.tips = (int64_t)h[TP_TIPS]; st.reads_removed = (int64_t)h[TP_READS]; st.spared_anchors = (int64_t)h[TP_SPARED];
     st.rounds_run = moves < cfg.rounds ? moves + 1 : cfg.rounds;
     sg_stats_end(c, st);
-    c.tpstats = st;
+    c.tp.stats = st;
 }
 
 }  // namespace elba

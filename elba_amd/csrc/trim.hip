@@ -181,21 +181,21 @@ void stage_trim_reads(Ctx &c, const elba_trim_cfg *cfgp)
     ELBA_REQUIRE(cfg.min_len >= 1, ELBA_ERR_INVALID_ARG, "trim_reads: need min_len >= 1");
     ELBA_REQUIRE(cfg.reserved[0] == 0 && cfg.reserved[1] == 0, ELBA_ERR_INVALID_ARG, "trim_reads: reserved words must be 0");
     ELBA_REQUIRE(has(c.v, P_PILEUP), ELBA_ERR_STATE, "trim_reads: no pileup of the current overlaps (call elba_read_pileup)");
-    const int64_t M = c.pu_M;
+    const int64_t M = c.pu.M;
     const ReadSource in = read_source(c, M, "trim_reads", "bases of the pileup's # reads");
     accepted(c.v, EV_TRIM_READS);
     hipStream_t s = c.stream;
     TrimParams p{};
-    p.seg_off = c.pu_seg_off.as<int64_t>(); p.seg_start = c.pu_seg_start.as<int32_t>(); p.seg_depth = c.pu_seg_depth.as<int32_t>(); p.trim = c.pu_trim.as<int2>();
+    p.seg_off = c.pu.depth.seg_off.as<int64_t>(); p.seg_start = c.pu.depth.seg_start.as<int32_t>(); p.seg_depth = c.pu.depth.seg_depth.as<int32_t>(); p.trim = c.pu.trim.as<int2>();
     p.len = in.len; p.src_off = in.byte_off; p.M = (uint32_t)M;
-    p.mode = cfg.mode; p.min_depth = c.pu_cfg.min_depth; p.min_run = c.pu_cfg.min_run; p.min_len = cfg.min_len;
-    c.tm_cnt.reserve((size_t)(M + 1) * 4); c.tm_bytes.reserve((size_t)(M + 1) * 4); c.tm_first.reserve((size_t)(M + 1) * 4); c.tm_boff.reserve((size_t)(M + 1) * 8);
-    c.tm_ctr.reserve(64);
-    uint32_t *cnt = c.tm_cnt.as<uint32_t>(), *bytes = c.tm_bytes.as<uint32_t>(), *first = c.tm_first.as<uint32_t>();
-    int64_t *boff = c.tm_boff.as<int64_t>();
-    unsigned long long *ctr = c.tm_ctr.as<unsigned long long>();
+    p.mode = cfg.mode; p.min_depth = c.pu.cfg.min_depth; p.min_run = c.pu.cfg.min_run; p.min_len = cfg.min_len;
+    c.tm.cnt.reserve((size_t)(M + 1) * 4); c.tm.bytes.reserve((size_t)(M + 1) * 4); c.tm.first.reserve((size_t)(M + 1) * 4); c.tm.boff.reserve((size_t)(M + 1) * 8);
+    c.tm.ctr.reserve(64);
+    uint32_t *cnt = c.tm.cnt.as<uint32_t>(), *bytes = c.tm.bytes.as<uint32_t>(), *first = c.tm.first.as<uint32_t>();
+    int64_t *boff = c.tm.boff.as<int64_t>();
+    unsigned long long *ctr = c.tm.ctr.as<unsigned long long>();
     const unsigned nbM = (unsigned)((M + 1 + 255) / 256);
-    c.tm_t_total.start(s);
+    c.tm.t_total.start(s);
     ELBA_HIP(hipMemsetAsync(ctr, 0, 64, s));
     hipLaunchKernelGGL(k_trim_count, dim3(nbM), dim3(256), 0, s, p, cnt, bytes, ctr);
     exclusive_scan_u32(s, cnt, first, M + 1, c.ws_scan);
@@ -205,29 +205,29 @@ void stage_trim_reads(Ctx &c, const elba_trim_cfg *cfgp)
     ELBA_HIP(hipMemcpyAsync(h, ctr, 64, hipMemcpyDeviceToHost, s));
     ELBA_HIP(hipStreamSynchronize(s));
     const int64_t n = (int64_t)h[0], pb = (int64_t)h[6];
-    c.tm_packed.reserve((size_t)pb + 16); c.tm_off.reserve((size_t)(n + 1) * 8); c.tm_len.reserve((size_t)(n + 1) * 4);
-    c.tm_src.reserve((size_t)(n + 1) * 8); c.tm_beg.reserve((size_t)(n + 1) * 4); c.tm_end.reserve((size_t)(n + 1) * 4); c.tm_srcb.reserve((size_t)(n + 1) * 8);
+    c.tm.packed.reserve((size_t)pb + 16); c.tm.off.reserve((size_t)(n + 1) * 8); c.tm.len.reserve((size_t)(n + 1) * 4);
+    c.tm.src.reserve((size_t)(n + 1) * 8); c.tm.beg.reserve((size_t)(n + 1) * 4); c.tm.end.reserve((size_t)(n + 1) * 4); c.tm.srcb.reserve((size_t)(n + 1) * 8);
     if (M > 0)
-        hipLaunchKernelGGL(k_trim_pieces, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, p, first, boff, c.tm_src.as<int64_t>(), c.tm_beg.as<int32_t>(),
-                           c.tm_end.as<int32_t>(), c.tm_off.as<uint64_t>(), c.tm_len.as<uint32_t>(), c.tm_srcb.as<uint64_t>());
+        hipLaunchKernelGGL(k_trim_pieces, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, p, first, boff, c.tm.src.as<int64_t>(), c.tm.beg.as<int32_t>(),
+                           c.tm.end.as<int32_t>(), c.tm.off.as<uint64_t>(), c.tm.len.as<uint32_t>(), c.tm.srcb.as<uint64_t>());
     // the last word's tail and the guard bytes; the words below are written whole by the kernel
-    ELBA_HIP(hipMemsetAsync(c.tm_packed.as<uint8_t>() + (pb & ~7ll), 0, (size_t)(pb - (pb & ~7ll)) + 16, s));
-    c.tm_t_repack.start(s);
+    ELBA_HIP(hipMemsetAsync(c.tm.packed.as<uint8_t>() + (pb & ~7ll), 0, (size_t)(pb - (pb & ~7ll)) + 16, s));
+    c.tm.t_repack.start(s);
     if (n > 0) {
         const int64_t nwords = (pb + 7) / 8;
         ELBA_REQUIRE((nwords + TRIM_THREADS - 1) / TRIM_THREADS < 0x7fffffffll, ELBA_ERR_UNSUPPORTED, "trim_reads: more than 2^42 packed bytes");
-        hipLaunchKernelGGL(k_trim_repack, dim3((unsigned)((nwords + TRIM_THREADS - 1) / TRIM_THREADS)), dim3(TRIM_THREADS), 0, s, in.packed, c.tm_off.as<uint64_t>(),
-                           c.tm_len.as<uint32_t>(), c.tm_srcb.as<uint64_t>(), n, (uint64_t)pb, c.tm_packed.as<uint64_t>());
+        hipLaunchKernelGGL(k_trim_repack, dim3((unsigned)((nwords + TRIM_THREADS - 1) / TRIM_THREADS)), dim3(TRIM_THREADS), 0, s, in.packed, c.tm.off.as<uint64_t>(),
+                           c.tm.len.as<uint32_t>(), c.tm.srcb.as<uint64_t>(), n, (uint64_t)pb, c.tm.packed.as<uint64_t>());
     }
-    c.tm_t_repack.stop(s);
+    c.tm.t_repack.stop(s);
     ELBA_HIP(hipGetLastError());
-    c.tm_t_total.stop(s);
+    c.tm.t_total.stop(s);
     ELBA_HIP(hipStreamSynchronize(s));
     elba_trim_stats st{};
     st.nreads_in = M; st.pieces = n; st.reads_dropped = (int64_t)h[1]; st.reads_split = (int64_t)h[2]; st.reads_unchanged = (int64_t)h[3];
     st.bases_in = (int64_t)h[4]; st.bases_out = (int64_t)h[5]; st.packed_bytes = pb; st.longest = (int64_t)h[7];
-    st.ms_total = c.tm_t_total.ms(); st.ms_repack = c.tm_t_repack.ms();
-    c.tm_n = n; c.tm_packed_bytes = pb; c.tmstats = st; done(c.v, EV_TRIM_READS);
+    st.ms_total = c.tm.t_total.ms(); st.ms_repack = c.tm.t_repack.ms();
+    c.tm.n = n; c.tm.packed_bytes = pb; c.tm.stats = st; done(c.v, EV_TRIM_READS);
 }
 
 // the pieces become the context's own reads, exactly as after elba_set_reads
@@ -235,18 +235,18 @@ void stage_adopt_trimmed_reads(Ctx &c)
 {
     ELBA_REQUIRE(has(c.v, P_TRIM), ELBA_ERR_STATE, "adopt_trimmed_reads: no trimmed reads (call elba_trim_reads)");
     hipStream_t s = c.stream;
-    const int64_t n = c.tm_n;
+    const int64_t n = c.tm.n;
     std::vector<uint32_t> hl((size_t)n);
     std::vector<uint64_t> ho((size_t)n);
     if (n) {
-        ELBA_HIP(hipMemcpyAsync(hl.data(), c.tm_len.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-        ELBA_HIP(hipMemcpyAsync(ho.data(), c.tm_off.p, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+        ELBA_HIP(hipMemcpyAsync(hl.data(), c.tm.len.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+        ELBA_HIP(hipMemcpyAsync(ho.data(), c.tm.off.p, (size_t)n * 8, hipMemcpyDeviceToHost, s));
     }
     ELBA_HIP(hipStreamSynchronize(s));
-    c.own_packed.swap(c.tm_packed); c.own_byte_off.swap(c.tm_off); c.own_len.swap(c.tm_len);
+    c.own_packed.swap(c.tm.packed); c.own_byte_off.swap(c.tm.off); c.own_len.swap(c.tm.len);
     c.d_packed = c.own_packed.as<uint8_t>(); c.d_byte_off = c.own_byte_off.as<uint64_t>(); c.d_len = c.own_len.as<uint32_t>();
     c.h_len.swap(hl); c.h_byte_off.swap(ho);
-    c.nreads = n; c.first_global_id = 0; c.packed_bytes = c.tm_packed_bytes;
+    c.nreads = n; c.first_global_id = 0; c.packed_bytes = c.tm.packed_bytes;
     reads_replaced(c, EV_ADOPT_TRIMMED_READS);
 }
 

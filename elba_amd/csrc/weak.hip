@@ -139,14 +139,14 @@ void stage_cut_weak_overlaps(Ctx &c, const elba_weak_cfg *cfgp)
     const int64_t M = c.tr_M, n0 = c.tr_nnz;
     sg_require_32bit(EV_CUT_WEAK_OVERLAPS, M < 0x7fffffffll && n0 < 0xfffffffell);         // (2 M sides)
     elba_weak_stats st = sg_stats_begin<elba_weak_stats>(c);
-    if (M == 0 || n0 == 0) { accepted(c.v, EV_CUT_WEAK_OVERLAPS); done(c.v, EV_CUT_WEAK_OVERLAPS); c.wkstats = st; return; }      // no entry: no side has two
+    if (M == 0 || n0 == 0) { accepted(c.v, EV_CUT_WEAK_OVERLAPS); done(c.v, EV_CUT_WEAK_OVERLAPS); c.wk.stats = st; return; }      // no entry: no side has two
     // every buffer of the launch sequence before the first launch
     sg_reserve(c, M, n0);
-    c.wk_best.reserve((size_t)(2 * M + 2) * 4); c.wk_cnt.reserve((size_t)(2 * M + 2) * 4); c.wk_nweak.reserve((size_t)(2 * M + 2) * 4);
-    c.wk_after.reserve((size_t)(2 * M + 2) * 4);
+    c.wk.best.reserve((size_t)(2 * M + 2) * 4); c.wk.cnt.reserve((size_t)(2 * M + 2) * 4); c.wk.nweak.reserve((size_t)(2 * M + 2) * 4);
+    c.wk.after.reserve((size_t)(2 * M + 2) * 4);
     const SgCall w(c);
-    uint32_t *cnt = c.wk_cnt.as<uint32_t>(), *nweak = c.wk_nweak.as<uint32_t>(), *after = c.wk_after.as<uint32_t>();
-    int32_t *best = c.wk_best.as<int32_t>();
+    uint32_t *cnt = c.wk.cnt.as<uint32_t>(), *nweak = c.wk.nweak.as<uint32_t>(), *after = c.wk.after.as<uint32_t>();
+    int32_t *best = c.wk.best.as<int32_t>();
     const elba_overlap_t *vals = c.tr_out_vals.as<elba_overlap_t>();
     const unsigned nbB = sg_blocks(2 * M > n0 + 1 ? 2 * M : n0 + 1), nbAll = sg_blocks(2 * M), nbM = nbAll < (unsigned)WK_SIDE_BLOCKS ? nbAll : (unsigned)WK_SIDE_BLOCKS;
     accepted(c.v, EV_CUT_WEAK_OVERLAPS);                        // as in stage_clip_tips: the contigs go, and S is invalid until the counters are back
@@ -165,7 +165,7 @@ void stage_cut_weak_overlaps(Ctx &c, const elba_weak_cfg *cfgp)
     done(c.v, EV_CUT_WEAK_OVERLAPS);
     st.branch_sides = (int64_t)h[WK_BRANCH]; st.weak_entries = (int64_t)h[WK_WEAK]; st.sides_emptied = (int64_t)h[WK_EMPTIED];
     sg_stats_end(c, st);                                        // (entries_removed: both images, nnz_before - nnz_after)
-    c.wkstats = st;
+    c.wk.stats = st;
 }
 
 }  // namespace elba
