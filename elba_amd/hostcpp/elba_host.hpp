@@ -388,6 +388,34 @@ public:
     int64_t getnnz() const { return (int64_t)vals.size(); }
 };
 
+namespace detail {
+// One exported pair as the reference's Overlap.  (Overlap::seed, a copy of seeds[0] of B(i,j), is not carried back: the caller still owns B)
+inline Overlap to_overlap(const elba_overlap_t &v, PosInRead lenQ, PosInRead lenT)
+{
+    Overlap w;
+    w.beg = std::make_tuple((PosInRead)v.begQ, (PosInRead)v.begT); w.end = std::make_tuple((PosInRead)v.endQ, (PosInRead)v.endT);
+    w.len = std::make_tuple(lenQ, lenT);
+    w.score = v.score; w.suffix = v.suffix; w.suffixT = v.suffixT; w.direction = v.direction; w.directionT = v.directionT;
+    w.rc = v.rc; w.passed = v.passed; w.containedQ = v.containedQ; w.containedT = v.containedT;
+    return w;
+}
+
+// The triples of an export (elba_export_overlaps, elba_export_string_graph) into rows, cols and vals; the export is freed, also when a copy throws.
+inline void take_triples(elba_overlaps_t &o, const DnaBuffer &myreads, std::vector<int64_t> &rows, std::vector<int64_t> &cols, std::vector<Overlap> &vals)
+{
+    try {
+        rows.assign(o.rows, o.rows + o.n); cols.assign(o.cols, o.cols + o.n);
+        vals.clear();
+        vals.reserve((size_t)o.n);
+        for (int64_t a = 0; a < o.n; ++a) vals.push_back(to_overlap(o.vals[a], (PosInRead)myreads.lengths()[o.rows[a]], (PosInRead)myreads.lengths()[o.cols[a]]));
+    } catch (...) {
+        elba_free_overlaps(&o);
+        throw;
+    }
+    elba_free_overlaps(&o);
+}
+}  // namespace detail
+
 // PairwiseAlignment(dfd, Bmat, mat, mis, gap, dropoff) — src/PairwiseAlignment.cpp:5-106 on one rank: every stored B(i,j), i < j, is
 // aligned from seeds[0] on the GPU (the reads are the ones the k-mer stage was given; DistributedFastaData's row/column buffers are
 // the same buffer on one rank).
@@ -399,18 +427,7 @@ inline std::unique_ptr<OverlapMatrix> PairwiseAlignment(const DnaBuffer &myreads
     Bmat.engine->check(elba_align_seeds(Bmat.engine->ctx, mat, mis, gap, dropoff, &R->stats));
     elba_overlaps_t o;
     Bmat.engine->check(elba_export_overlaps(Bmat.engine->ctx, &o));
-    R->rows.assign(o.rows, o.rows + o.n); R->cols.assign(o.cols, o.cols + o.n);
-    R->vals.resize((size_t)o.n);
-    // (Overlap::seed, a copy of seeds[0] of B(i,j), is not carried back: the caller still owns B)
-    for (int64_t a = 0; a < o.n; ++a) {
-        const elba_overlap_t &v = o.vals[a];
-        Overlap &w = R->vals[(size_t)a];
-        w.beg = std::make_tuple((PosInRead)v.begQ, (PosInRead)v.begT); w.end = std::make_tuple((PosInRead)v.endQ, (PosInRead)v.endT);
-        w.len = std::make_tuple((PosInRead)myreads.lengths()[o.rows[a]], (PosInRead)myreads.lengths()[o.cols[a]]);
-        w.score = v.score; w.suffix = v.suffix; w.suffixT = v.suffixT; w.direction = v.direction; w.directionT = v.directionT;
-        w.rc = v.rc; w.passed = v.passed; w.containedQ = v.containedQ; w.containedT = v.containedT;
-    }
-    elba_free_overlaps(&o);
+    detail::take_triples(o, myreads, R->rows, R->cols, R->vals);
     return R;
 }
 
@@ -438,17 +455,7 @@ inline std::unique_ptr<StringGraph> TransitiveReduction(const DnaBuffer &myreads
     R.engine->check(elba_transitive_reduction(R.engine->ctx, bad_read_cutoff, fuzz, &S->stats));
     elba_overlaps_t o;
     R.engine->check(elba_export_string_graph(R.engine->ctx, &o));
-    S->rows.assign(o.rows, o.rows + o.n); S->cols.assign(o.cols, o.cols + o.n);
-    S->vals.resize((size_t)o.n);
-    for (int64_t a = 0; a < o.n; ++a) {
-        const elba_overlap_t &v = o.vals[a];
-        Overlap &w = S->vals[(size_t)a];
-        w.beg = std::make_tuple((PosInRead)v.begQ, (PosInRead)v.begT); w.end = std::make_tuple((PosInRead)v.endQ, (PosInRead)v.endT);
-        w.len = std::make_tuple((PosInRead)myreads.lengths()[o.rows[a]], (PosInRead)myreads.lengths()[o.cols[a]]);
-        w.score = v.score; w.suffix = v.suffix; w.suffixT = v.suffixT; w.direction = v.direction; w.directionT = v.directionT;
-        w.rc = v.rc; w.passed = v.passed; w.containedQ = v.containedQ; w.containedT = v.containedT;
-    }
-    elba_free_overlaps(&o);
+    detail::take_triples(o, myreads, S->rows, S->cols, S->vals);
     std::vector<uint8_t> flags((size_t)R.numreads);
     R.engine->check(elba_export_read_flags(R.engine->ctx, flags.data(), R.numreads));
     for (int64_t v = 0; v < R.numreads; ++v) {
@@ -464,17 +471,7 @@ inline void reload_string_graph(StringGraph &S, const DnaBuffer &myreads, uint8_
 {
     elba_overlaps_t o;
     S.engine->check(elba_export_string_graph(S.engine->ctx, &o));
-    S.rows.assign(o.rows, o.rows + o.n); S.cols.assign(o.cols, o.cols + o.n);
-    S.vals.assign((size_t)o.n, Overlap());
-    for (int64_t a = 0; a < o.n; ++a) {
-        const elba_overlap_t &v = o.vals[a];
-        Overlap &w = S.vals[(size_t)a];
-        w.beg = std::make_tuple((PosInRead)v.begQ, (PosInRead)v.begT); w.end = std::make_tuple((PosInRead)v.endQ, (PosInRead)v.endT);
-        w.len = std::make_tuple((PosInRead)myreads.lengths()[o.rows[a]], (PosInRead)myreads.lengths()[o.cols[a]]);
-        w.score = v.score; w.suffix = v.suffix; w.suffixT = v.suffixT; w.direction = v.direction; w.directionT = v.directionT;
-        w.rc = v.rc; w.passed = v.passed; w.containedQ = v.containedQ; w.containedT = v.containedT;
-    }
-    elba_free_overlaps(&o);
+    detail::take_triples(o, myreads, S.rows, S.cols, S.vals);
     if (removed_reads) {
         std::vector<uint8_t> flags((size_t)S.numreads);
         S.engine->check(elba_export_read_flags(S.engine->ctx, flags.data(), S.numreads));
@@ -483,19 +480,29 @@ inline void reload_string_graph(StringGraph &S, const DnaBuffer &myreads, uint8_
     }
 }
 
+// What the five cleaning calls below share: S must be on a device; fn(ctx, &cfg, &stats) changes it there; the host copy is reloaded, with the
+// reads that carry `flag` into `removed`.
+namespace detail {
+template <class Stats, class Cfg, class Fn>
+inline Stats clean_call(StringGraph &S, const DnaBuffer &myreads, const char *who, uint8_t flag, std::vector<int64_t> *removed, Fn fn, const Cfg &cfg)
+{
+    if (!S.engine) throw Error(ELBA_ERR_STATE, std::string(who) + ": the string graph is not on a device");
+    Stats st{};
+    S.engine->check(fn(S.engine->ctx, &cfg, &st));
+    reload_string_graph(S, myreads, flag, removed);
+    return st;
+}
+}  // namespace detail
+
 // ClipTips(S, myreads, max_tip_reads, rounds) — not in the reference: elba_clip_tips on the S that TransitiveReduction left on the device, between
 // that call and GenerateContigs.  Dead-end chains of at most max_tip_reads reads that hang off a read of degree >= 3 leave S (a star of nothing
 // but such chains is spared), in up to `rounds` rounds; the host copy of S is replaced by the clipped graph, and clipped_reads, if given,
 // receives the reads removed so far (flag bit 2 of elba_export_read_flags), ascending.
 inline elba_tip_stats ClipTips(StringGraph &S, const DnaBuffer &myreads, int max_tip_reads, int rounds = 1, std::vector<int64_t> *clipped_reads = nullptr)
 {
-    if (!S.engine) throw Error(ELBA_ERR_STATE, "ClipTips: the string graph is not on a device");
     elba_tip_cfg cfg{};
     cfg.max_tip_reads = max_tip_reads; cfg.rounds = rounds;
-    elba_tip_stats st{};
-    S.engine->check(elba_clip_tips(S.engine->ctx, &cfg, &st));
-    reload_string_graph(S, myreads, 4, clipped_reads);
-    return st;
+    return detail::clean_call<elba_tip_stats>(S, myreads, "ClipTips", 4, clipped_reads, elba_clip_tips, cfg);
 }
 
 // PopBubbles(S, myreads, max_arm_reads, rounds) — not in the reference: elba_pop_bubbles on the S that TransitiveReduction (or ClipTips) left on the
@@ -505,13 +512,9 @@ inline elba_tip_stats ClipTips(StringGraph &S, const DnaBuffer &myreads, int max
 // elba_export_read_flags), ascending.
 inline elba_bubble_stats PopBubbles(StringGraph &S, const DnaBuffer &myreads, int max_arm_reads, int rounds = 1, std::vector<int64_t> *popped_reads = nullptr)
 {
-    if (!S.engine) throw Error(ELBA_ERR_STATE, "PopBubbles: the string graph is not on a device");
     elba_bubble_cfg cfg{};
     cfg.max_arm_reads = max_arm_reads; cfg.rounds = rounds;
-    elba_bubble_stats st{};
-    S.engine->check(elba_pop_bubbles(S.engine->ctx, &cfg, &st));
-    reload_string_graph(S, myreads, 8, popped_reads);
-    return st;
+    return detail::clean_call<elba_bubble_stats>(S, myreads, "PopBubbles", 8, popped_reads, elba_pop_bubbles, cfg);
 }
 
 // CutWeakOverlaps(S, myreads, min_ratio_q16) — not in the reference: elba_cut_weak_overlaps on the S that TransitiveReduction (or ClipTips, or
@@ -520,13 +523,9 @@ inline elba_bubble_stats PopBubbles(StringGraph &S, const DnaBuffer &myreads, in
 // image is such a one; in one pass.  Entries leave, no read does, and the read flags stay; the host copy of S is replaced by the cut graph.
 inline elba_weak_stats CutWeakOverlaps(StringGraph &S, const DnaBuffer &myreads, int min_ratio_q16)
 {
-    if (!S.engine) throw Error(ELBA_ERR_STATE, "CutWeakOverlaps: the string graph is not on a device");
     elba_weak_cfg cfg{};
     cfg.min_ratio_q16 = min_ratio_q16;
-    elba_weak_stats st{};
-    S.engine->check(elba_cut_weak_overlaps(S.engine->ctx, &cfg, &st));
-    reload_string_graph(S, myreads, 0, nullptr);
-    return st;
+    return detail::clean_call<elba_weak_stats>(S, myreads, "CutWeakOverlaps", 0, nullptr, elba_cut_weak_overlaps, cfg);
 }
 
 // CutBridges(S, myreads, max_bridge_reads, min_flank_reads) — the rule of asmtools/bridge_removal.py for chains: elba_cut_bridges on the S that
@@ -536,13 +535,9 @@ inline elba_weak_stats CutWeakOverlaps(StringGraph &S, const DnaBuffer &myreads,
 // removed so far (flag bit 4 of elba_export_read_flags), ascending.
 inline elba_bridge_stats CutBridges(StringGraph &S, const DnaBuffer &myreads, int max_bridge_reads, int min_flank_reads, std::vector<int64_t> *cut_reads = nullptr)
 {
-    if (!S.engine) throw Error(ELBA_ERR_STATE, "CutBridges: the string graph is not on a device");
     elba_bridge_cfg cfg{};
     cfg.max_bridge_reads = max_bridge_reads; cfg.min_flank_reads = min_flank_reads;
-    elba_bridge_stats st{};
-    S.engine->check(elba_cut_bridges(S.engine->ctx, &cfg, &st));
-    reload_string_graph(S, myreads, 16, cut_reads);
-    return st;
+    return detail::clean_call<elba_bridge_stats>(S, myreads, "CutBridges", 16, cut_reads, elba_cut_bridges, cfg);
 }
 
 // ResolveStars(S, myreads, rounds) — the rule of asmtools/star_resolution.py: elba_resolve_stars on the S that TransitiveReduction (or one of the
@@ -553,13 +548,9 @@ inline elba_bridge_stats CutBridges(StringGraph &S, const DnaBuffer &myreads, in
 // graph, and odd_arms, if given, receives the reads removed so far (flag bit 5 of elba_export_read_flags), ascending.
 inline elba_star_stats ResolveStars(StringGraph &S, const DnaBuffer &myreads, int rounds = 1, std::vector<int64_t> *odd_arms = nullptr)
 {
-    if (!S.engine) throw Error(ELBA_ERR_STATE, "ResolveStars: the string graph is not on a device");
     elba_star_cfg cfg{};
     cfg.rounds = rounds;
-    elba_star_stats st{};
-    S.engine->check(elba_resolve_stars(S.engine->ctx, &cfg, &st));
-    reload_string_graph(S, myreads, 32, odd_arms);
-    return st;
+    return detail::clean_call<elba_star_stats>(S, myreads, "ResolveStars", 32, odd_arms, elba_resolve_stars, cfg);
 }
 
 // PileupVector (include/PruneChimeras.hpp:11-26): here a read's coverage is held as the (start, depth) segments elba_export_pileup returns;

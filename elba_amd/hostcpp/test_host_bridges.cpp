@@ -3,72 +3,27 @@
 // the bridge reads, in order.
 // Prints one JSON line: the stats, checksums of the cut S and of the bridge reads, the contigs' counts, whether the host comparison held.
 // Usage: test_host_bridges reads.fa K LOWER UPPER MAX_BRIDGE_READS MIN_FLANK_READS [bad_read_cutoff]
-#include <cstdio>
-#include <cstdlib>
-#include <fstream>
-#include <iostream>
-#include "elba_host.hpp"
+#include "host_test.hpp"
+namespace ht = elba::host_test;
 
 int main(int argc, char **argv)
 {
-    if (argc < 7) { std::fprintf(stderr, "usage: %s reads.fa K LOWER UPPER MAX_BRIDGE_READS MIN_FLANK_READS [bad_read_cutoff]\n", argv[0]); return 2; }
-    elba::Params prm;
-    prm.kmer_size = std::atoi(argv[2]); prm.lower_kmer_freq = std::atoi(argv[3]); prm.upper_kmer_freq = std::atoi(argv[4]);
-    const int max_bridge_reads = std::atoi(argv[5]), min_flank_reads = std::atoi(argv[6]);
-    const double cutoff = argc > 7 ? std::atof(argv[7]) : 0.65;
-    std::ifstream in(argv[1]);
-    std::vector<std::string> seqs;
-    std::string line, cur;
-    while (std::getline(in, line)) {
-        if (!line.empty() && line[0] == '>') { if (!cur.empty()) seqs.push_back(cur); cur.clear(); }
-        else cur += line;
-    }
-    if (!cur.empty()) seqs.push_back(cur);
-    std::vector<size_t> lens;
-    for (auto &s : seqs) lens.push_back(s.size());
-    elba::DnaBuffer mydna(elba::DnaBuffer::computebufsize(lens));
-    for (auto &s : seqs) mydna.push_back(s.c_str(), s.size());
-    auto commgrid = std::make_shared<elba::Grid>();
-    try {
-        auto kmermap = elba::get_kmer_count_map_keys(mydna, commgrid, prm);
-        elba::get_kmer_count_map_values(mydna, *kmermap, commgrid);
-        auto A = elba::create_kmer_matrix(mydna, *kmermap, commgrid);
-        kmermap.reset();
-        auto AT = std::make_unique<elba::KmerMatrix>(*A);
-        AT->Transpose();
-        auto B = elba::create_seed_matrix(*A, *AT);
-        A.reset(); AT.reset();
-        auto R = elba::PairwiseAlignment(mydna, *B, 1, -1, -1, 15);
-        auto S = elba::TransitiveReduction(mydna, *R, cutoff);
-        const std::vector<int64_t> rows0 = S->rows, cols0 = S->cols;
+    return ht::run(argc, argv, 7, "reads.fa K LOWER UPPER MAX_BRIDGE_READS MIN_FLANK_READS [bad_read_cutoff]", [&] {
+        const int max_bridge_reads = std::atoi(argv[5]), min_flank_reads = std::atoi(argv[6]);
+        const ht::Reads reads = ht::read_fasta(argv[1]);
+        const ht::Front f = ht::run_to_string_graph(reads, ht::params_at(argv + 2), argc > 7 ? std::atof(argv[7]) : 0.65);
+        elba::StringGraph &S = *f.S;
+        const std::vector<int64_t> rows0 = S.rows, cols0 = S.cols;
         std::vector<int64_t> cut;
-        const elba_bridge_stats st = elba::CutBridges(*S, mydna, max_bridge_reads, min_flank_reads, &cut);
-        std::vector<uint8_t> gone(mydna.size(), 0);
-        unsigned long long read_checksum = 0, s_checksum = 0;
-        for (int64_t v : cut) { gone[(size_t)v] = 1; read_checksum += (unsigned long long)(v + 1) * 10007ull; }
-        long long host_equal = S->getnnz() == st.nnz_after && (long long)rows0.size() == st.nnz_before && (long long)cut.size() == st.reads_removed;
-        size_t at = 0;
-        for (size_t a = 0; a < rows0.size() && host_equal; ++a) {
-            if (gone[(size_t)rows0[a]] || gone[(size_t)cols0[a]]) continue;
-            if (at >= S->rows.size() || S->rows[at] != rows0[a] || S->cols[at] != cols0[a]) host_equal = 0;
-            ++at;
-        }
-        if (at != S->rows.size()) host_equal = 0;
-        for (size_t a = 0; a < S->rows.size(); ++a)
-            s_checksum += (unsigned long long)(S->rows[a] + 1) * 1000003ull + (unsigned long long)S->cols[a] * 10007ull + (unsigned long long)(unsigned)S->vals[a].suffix;
-        elba_contig_stats cs{};
-        const std::vector<std::string> contigs = elba::GenerateContigs(*S, mydna, &cs);
-        size_t bases = 0;
-        for (auto &c : contigs) bases += c.size();
-        std::printf("{\"reads\": %zu, \"nnz_before\": %lld, \"nnz_after\": %lld, \"anchors\": %lld, \"chains\": %lld, \"long_flanks\": %lld, \"bridges\": %lld, "
-                    "\"reads_removed\": %lld, \"entries_removed\": %lld, \"s_checksum\": %llu, \"read_checksum\": %llu, \"host_equal\": %lld, \"contigs\": %zu, \"bases\": %zu, "
-                    "\"branches\": %lld}\n",
-                    mydna.size(), (long long)st.nnz_before, (long long)st.nnz_after, (long long)st.anchors, (long long)st.chains, (long long)st.long_flanks,
-                    (long long)st.bridges, (long long)st.reads_removed, (long long)st.entries_removed, s_checksum, read_checksum, host_equal, contigs.size(), bases,
-                    (long long)cs.branches);
-    } catch (const elba::Error &e) {
-        std::fprintf(stderr, "%s\n", e.what());
-        return e.status == ELBA_ERR_NO_DEVICE ? 3 : 1;
-    }
-    return 0;
+        const elba_bridge_stats st = elba::CutBridges(S, reads.dna, max_bridge_reads, min_flank_reads, &cut);
+        const long long host_equal = S.getnnz() == st.nnz_after && (long long)rows0.size() == st.nnz_before && (long long)cut.size() == st.reads_removed &&
+                                     ht::kept_in_order(rows0, cols0, cut, S);
+        ht::Json j;
+        j("reads", reads.size())("nnz_before", st.nnz_before)("nnz_after", st.nnz_after)("anchors", st.anchors)("chains", st.chains)
+            ("long_flanks", st.long_flanks)("bridges", st.bridges)("reads_removed", st.reads_removed)
+            ("entries_removed", st.entries_removed)("s_checksum", ht::s_checksum(S))("read_checksum", ht::read_checksum(cut))("host_equal", host_equal);
+        ht::contig_counts(j, S, reads.dna);
+        j.print();
+        return 0;
+    });
 }

@@ -2,38 +2,28 @@
 // value-range owners -> all-to-all #1 -> exact count -> k-mer ids by exclusive scan -> all-to-all #2 (column panels) -> this rank's rows of B.
 // Usage: test_host_dist reads.fa K LOWER UPPER [RANK SIZE ID_FILE]     (one process per GPU; RANK's GPU = RANK unless ELBA_DEVICE is set)
 // Prints one JSON line per rank: rows, nnz of its rows of B and a checksum over (row, col, seeds[0], numshared) of every entry.
-#include <cstdio>
-#include <cstdlib>
-#include <fstream>
 #include "elba_host_dist.hpp"
+#include "host_test.hpp"
+namespace ht = elba::host_test;
 
 int main(int argc, char **argv)
 {
-    if (argc < 5) { std::fprintf(stderr, "usage: %s reads.fa K LOWER UPPER [RANK SIZE ID_FILE]\n", argv[0]); return 2; }
-    elba::Params prm;
-    prm.kmer_size = std::atoi(argv[2]); prm.lower_kmer_freq = std::atoi(argv[3]); prm.upper_kmer_freq = std::atoi(argv[4]);
-    const int rank = argc > 7 ? std::atoi(argv[5]) : 0, size = argc > 7 ? std::atoi(argv[6]) : 1;
-    std::ifstream in(argv[1]);
-    std::vector<std::string> seqs;
-    std::string line, cur;
-    while (std::getline(in, line)) {
-        if (!line.empty() && line[0] == '>') { if (!cur.empty()) seqs.push_back(cur); cur.clear(); }
-        else cur += line;
-    }
-    if (!cur.empty()) seqs.push_back(cur);
-    // contiguous partition balanced by bases: the greedy rule of src/FastaIndex.cpp:47-94
-    size_t totbases = 0;
-    for (auto &s : seqs) totbases += s.size();
-    const double avg = (double)totbases / size;
-    std::vector<int64_t> displs((size_t)size + 1, 0);
-    size_t at = 0;
-    for (int i = 0; i < size - 1; ++i) {
-        size_t sofar = 0;
-        while (at < seqs.size() && sofar + seqs[at].size() < avg) sofar += seqs[at++].size();
-        displs[(size_t)i + 1] = (int64_t)at;
-    }
-    displs[(size_t)size] = (int64_t)seqs.size();
-    try {
+    return ht::run(argc, argv, 5, "reads.fa K LOWER UPPER [RANK SIZE ID_FILE]", [&] {
+        const elba::Params prm = ht::params_at(argv + 2);
+        const int rank = argc > 7 ? std::atoi(argv[5]) : 0, size = argc > 7 ? std::atoi(argv[6]) : 1;
+        const std::vector<std::string> seqs = ht::read_fasta(argv[1]).seqs;
+        // contiguous partition balanced by bases: the greedy rule of src/FastaIndex.cpp:47-94
+        size_t totbases = 0;
+        for (auto &s : seqs) totbases += s.size();
+        const double avg = (double)totbases / size;
+        std::vector<int64_t> displs((size_t)size + 1, 0);
+        size_t at = 0;
+        for (int i = 0; i < size - 1; ++i) {
+            size_t sofar = 0;
+            while (at < seqs.size() && sofar + seqs[at].size() < avg) sofar += seqs[at++].size();
+            displs[(size_t)i + 1] = (int64_t)at;
+        }
+        displs[(size_t)size] = (int64_t)seqs.size();
         int ndev = 0;
         if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { std::fprintf(stderr, "no HIP device\n"); return 3; }
         const int device = std::getenv("ELBA_DEVICE") ? std::atoi(std::getenv("ELBA_DEVICE")) : rank % ndev;
@@ -63,9 +53,6 @@ int main(int argc, char **argv)
                     "\"nnzB\": %lld, \"products\": %lld, \"checksum\": %llu, \"exchange_bytes\": %llu}\n", rank, size, (long long)B.nrows, (long long)ks.instances, (long long)ks.reliable,
                     (long long)ks.entries, (long long)ms.ncols, (long long)ms.nnz, (long long)B.nnz, (long long)st.products, (unsigned long long)checksum, (unsigned long long)d.exchange_bytes());
         elba_free_csr(&B);
-    } catch (const elba::Error &e) {
-        std::fprintf(stderr, "%s\n", e.what());
-        return e.status == ELBA_ERR_NO_DEVICE ? 3 : 1;
-    }
-    return 0;
+        return 0;
+    });
 }

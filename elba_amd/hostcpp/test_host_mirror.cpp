@@ -1,36 +1,21 @@
 // test_host_mirror.cpp — the front half of the reference's main() (src/main.cpp:191-285) written against elba_host.hpp, followed by
 // the DCSC walk of PairwiseAlignment (src/PairwiseAlignment.cpp:28-56).  Prints one JSON line that tests/test_gpu_hostcpp.py
 // compares with the oracle.  Usage: test_host_mirror reads.fa K LOWER UPPER
-#include <cstdio>
-#include <cstdlib>
-#include <fstream>
-#include <iostream>
-#include "elba_host.hpp"
+#include "host_test.hpp"
+namespace ht = elba::host_test;
 
 int main(int argc, char **argv)
 {
-    if (argc < 5) { std::fprintf(stderr, "usage: %s reads.fa K LOWER UPPER [fai]   (fai: reads.fa.fai exists; ingest through FastaIndex + the GPU encoder)\n", argv[0]); return 2; }
-    const bool use_fai = argc > 5 && std::string(argv[5]) == "fai";
-    elba::Params prm;
-    prm.kmer_size = std::atoi(argv[2]); prm.lower_kmer_freq = std::atoi(argv[3]); prm.upper_kmer_freq = std::atoi(argv[4]);
-    std::ifstream in(argv[1]);
-    std::vector<std::string> seqs;
-    std::string line, cur;
-    while (std::getline(in, line)) {
-        if (!line.empty() && line[0] == '>') { if (!cur.empty()) seqs.push_back(cur); cur.clear(); }
-        else cur += line;
-    }
-    if (!cur.empty()) seqs.push_back(cur);
-    std::vector<size_t> lens;
-    for (auto &s : seqs) lens.push_back(s.size());
-    elba::DnaBuffer mydna(elba::DnaBuffer::computebufsize(lens));
-    for (auto &s : seqs) mydna.push_back(s.c_str(), s.size());
-    auto commgrid = std::make_shared<elba::Grid>();
-    try {
+    return ht::run(argc, argv, 5, "reads.fa K LOWER UPPER [fai]   (fai: reads.fa.fai exists; ingest through FastaIndex + the GPU encoder)", [&] {
+        const bool use_fai = argc > 5 && std::string(argv[5]) == "fai";
+        const elba::Params prm = ht::params_at(argv + 2);
+        const ht::Reads reads = ht::read_fasta(argv[1]);
+        const elba::DnaBuffer &mydna = reads.dna;
         int ingest_equal = -1;
         std::unique_ptr<elba::KmerCountMap> kmermap;
         if (use_fai) {
             // main.cpp:157-176: FastaIndex index(fasta_fname, commgrid); DnaBuffer mydna = index.getmydna(); — the encoding happens on the GPU here
+            auto commgrid = std::make_shared<elba::Grid>();
             elba::FastaIndex index(argv[1], commgrid);
             kmermap = elba::get_kmer_count_map_keys(index, commgrid, prm);
             std::vector<uint8_t> packed(mydna.getbufsize() + 16);
@@ -39,19 +24,13 @@ int main(int argc, char **argv)
             kmermap->engine->check(elba_export_reads(kmermap->engine->ctx, packed.data(), (int64_t)mydna.getbufsize(), offs.data(), lens2.data(), (int64_t)mydna.size()));
             ingest_equal = index.gettotrecords() == mydna.size() && std::memcmp(packed.data(), mydna.data(), mydna.getbufsize()) == 0
                            && std::memcmp(offs.data(), mydna.offsets(), offs.size() * 8) == 0 && std::memcmp(lens2.data(), mydna.lengths(), lens2.size() * 4) == 0;
-        } else
-            kmermap = elba::get_kmer_count_map_keys(mydna, commgrid, prm);                 // main.cpp:192
-        elba::get_kmer_count_map_values(mydna, *kmermap, commgrid);                         // main.cpp:225
-        auto A = elba::create_kmer_matrix(mydna, *kmermap, commgrid);                       // main.cpp:259
-        kmermap.reset();                                                                    // main.cpp:266
-        auto AT = std::make_unique<elba::KmerMatrix>(*A);                                   // main.cpp:272
-        AT->Transpose();                                                                    // main.cpp:273
-        auto B = elba::create_seed_matrix(*A, *AT);                                         // main.cpp:281
-        const int64_t nnzA = A->getnnz(), ncol = A->getncol();
-        A.reset(); AT.reset();                                                              // main.cpp:284-285
+        }
+        // main.cpp:192-285; without the .fai the k-mer map is made there from mydna
+        const ht::Front f = ht::run_to_string_graph(reads, prm, 0.65, ht::Stop::B, std::move(kmermap));
+        elba::SeedMatrix &B = *f.B;
         // PairwiseAlignment.cpp:16-56
-        size_t localnnzs = (size_t)B->seqptr()->getnnz();
-        auto dcsc = B->seqptr()->GetDCSC();
+        size_t localnnzs = (size_t)B.seqptr()->getnnz();
+        auto dcsc = B.seqptr()->GetDCSC();
         int64_t nalign = 0;
         uint64_t checksum = 0;
         if (dcsc != nullptr)
@@ -66,7 +45,7 @@ int main(int argc, char **argv)
                     }
                 }
         // main.cpp:300: R = PairwiseAlignment(dfd, *B, mat, mis, gap, xdrop_cutoff) with the defaults of main.cpp:53-56
-        auto R = elba::PairwiseAlignment(mydna, *B, 1, -1, -1, 15);
+        auto R = elba::PairwiseAlignment(mydna, B, 1, -1, -1, 15);
         uint64_t achk = 0; int64_t npassed = 0;
         for (size_t a = 0; a < R->vals.size(); ++a) {
             const elba::Overlap &o = R->vals[a];
@@ -86,17 +65,13 @@ int main(int argc, char **argv)
         if (const char *pfx = std::getenv("ELBA_OUT_PREFIX")) {
             std::vector<std::string> names;
             for (size_t r = 0; r < mydna.size(); ++r) names.push_back("read" + std::to_string(r));
-            elba::log_seed_matrix(*B, std::string(pfx) + "B.mtx");
+            elba::log_seed_matrix(B, std::string(pfx) + "B.mtx");
             elba::parallel_write_paf(*R, names, std::string(pfx) + "overlap.paf");
             elba::parallel_write_paf(*S, names, std::string(pfx) + "string.paf");
         }
-        std::printf("{\"reads\": %zu, \"nnzA\": %lld, \"kmers\": %lld, \"nnzB\": %zu, \"candidates\": %lld, \"checksum\": %llu, \"alignments\": %lld, \"passed\": %lld, \"align_checksum\": %llu, \"ingest_equal\": %d, "
-                    "\"bad_reads\": %zu, \"contained_reads\": %zu, \"string_nnz\": %lld, \"string_checksum\": %llu}\n", mydna.size(),
-                    (long long)nnzA, (long long)ncol, localnnzs, (long long)nalign, (unsigned long long)checksum, (long long)R->getnnz(), (long long)npassed, (unsigned long long)achk, ingest_equal,
-                    S->bad_reads.size(), S->contained_reads.size(), (long long)S->getnnz(), (unsigned long long)schk);
-    } catch (const elba::Error &e) {
-        std::fprintf(stderr, "%s\n", e.what());
-        return e.status == ELBA_ERR_NO_DEVICE ? 3 : 1;
-    }
-    return 0;
+        ht::Json()("reads", reads.size())("nnzA", f.nnzA)("kmers", f.ncol)("nnzB", localnnzs)("candidates", nalign)("checksum", checksum)("alignments", R->getnnz())
+            ("passed", npassed)("align_checksum", achk)("ingest_equal", ingest_equal)("bad_reads", S->bad_reads.size())("contained_reads", S->contained_reads.size())
+            ("string_nnz", S->getnnz())("string_checksum", schk).print();
+        return 0;
+    });
 }

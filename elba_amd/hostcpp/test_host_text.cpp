@@ -1,14 +1,12 @@
 // test_host_text.cpp — a FASTA or FASTQ file without a .fai -> reads on the context, written against elba_host.hpp (elba::set_reads_text).
 // Prints one JSON line: reads, bases, lines, format, packed bytes, and checksums of the .fai records, the names and the packed bytes.
 // Usage: test_host_text reads.{fa,fq}
-#include <cstdio>
-#include <cstdlib>
-#include "elba_host.hpp"
+#include "host_test.hpp"
+namespace ht = elba::host_test;
 
 int main(int argc, char **argv)
 {
-    if (argc < 2) { std::fprintf(stderr, "usage: %s reads.{fa,fq}\n", argv[0]); return 2; }
-    try {
+    return ht::run(argc, argv, 2, "reads.{fa,fq}", [&] {
         elba_cfg cfg{};
         cfg.k = 17; cfg.lower = 2; cfg.upper = 8;
         elba::detail::Engine engine(cfg);
@@ -21,13 +19,8 @@ int main(int argc, char **argv)
         for (size_t b = 0; b < t.reads.getbufsize(); ++b) packed_checksum += (unsigned long long)(b + 1) * t.reads.data()[b];
         unsigned long long bases = 0;
         for (size_t i = 0; i < t.reads.size(); ++i) bases += t.reads.lengths()[i];
-        std::printf("{\"reads\": %zu, \"bases\": %llu, \"stat_bases\": %lld, \"lines\": %lld, \"format\": %d, \"packed_bytes\": %lld, \"rec_checksum\": %llu, "
-                    "\"name_checksum\": %llu, \"packed_checksum\": %llu}\n",
-                    t.reads.size(), bases, (long long)t.stats.bases, (long long)t.stats.lines, (int)t.stats.format, (long long)t.stats.packed_bytes, rec_checksum, name_checksum,
-                    packed_checksum);
-    } catch (const elba::Error &e) {
-        std::fprintf(stderr, "%s\n", e.what());
-        return e.status == ELBA_ERR_NO_DEVICE ? 3 : 1;
-    }
-    return 0;
+        ht::Json()("reads", t.reads.size())("bases", bases)("stat_bases", t.stats.bases)("lines", t.stats.lines)("format", t.stats.format)("packed_bytes", t.stats.packed_bytes)
+            ("rec_checksum", rec_checksum)("name_checksum", name_checksum)("packed_checksum", packed_checksum).print();
+        return 0;
+    });
 }

@@ -1,8 +1,6 @@
 """-m gpu: contig generation on the GPU (elba_generate_contigs, contig.hip) against the restatement of GenerateContigs in contig_util.py,
 fed with the GPU's own exported S and, end to end, with the oracle's S.  Every byte of every contig, the chains, the read map, the counts."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -10,12 +8,12 @@ import pytest
 import contig_util as cu
 import elba_amd
 import gpu_util as gu
+import hostcpp_util as hu
 from elba_amd import formats
 from oracle import pyoracle as po
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STATS = ("nreads", "branches", "components", "used_components", "contigs", "cycles", "contig_reads", "bases", "longest")
 
 
@@ -224,17 +222,11 @@ def test_replicated_reads_serve_the_graph():
 
 
 def test_host_mirror_writes_the_same_contigs_fa(tmp_path):
-    binpath = os.path.join(ROOT, "elba_amd", "hostcpp", "test_host_contigs")
-    if not os.path.exists(binpath):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "elba_amd", "hostcpp")], stdout=subprocess.DEVNULL)
     packed, off, lens, info = elba_amd.synth_reads(44, 60000, 12, 3000, 500, error_rate=0.01, min_len=400)
     seqs = cu.seqs_of(packed, off, lens)
-    fa = tmp_path / "reads.fa"
-    with open(fa, "w") as f:
-        for i, s in enumerate(seqs):
-            f.write(">r%d\n%s\n" % (i, s))
+    fa = hu.write_fasta(tmp_path / "reads.fa", seqs)
     out = tmp_path / "cpp.contigs.fa"
-    subprocess.run([binpath, str(fa), "17", "2", "12", str(out)], check=True, capture_output=True, text=True)
+    hu.run_json(hu.binary("test_host_contigs"), [fa, 17, 2, 12, out])
     e, _, _, _ = gu.gpu_full(packed, off, lens, 17, 2, 12)
     e.align_seeds()
     e.transitive_reduction(0.65, 1000)

@@ -2,8 +2,6 @@
 fed with the GPU's own exported S and read flags: every byte of every contig, the chains, the kinds, the read map, the counts.  The graphs
 are triangle-free (or planted with weights that make no entry transitive), so S keeps every edge; each test asserts that from the export."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -11,12 +9,12 @@ import pytest
 import contig_ex_util as cx
 import contig_util as cu
 import elba_amd
+import hostcpp_util as hu
 from elba_amd import capi, formats
 from oracle import pyoracle as po
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STATS = ("nreads", "branches", "components", "used_components", "contigs", "cycles", "contig_reads", "bases", "longest")
 FLAGS = [0, cx.CIRCULAR, cx.SINGLETONS, cx.CIRCULAR | cx.SINGLETONS]
 
@@ -425,18 +423,12 @@ def test_replicated_reads_serve_the_graph():
 def test_writers_agree_with_and_without_kinds(tmp_path):
     """Tiled reads of a circular genome, of a linear one, and unrelated reads through the whole pipeline: the host mirror
     (GenerateContigs + parallel_write_contigs with kinds) and write_contigs_fasta write the same file; without kinds the headers are today's."""
-    binpath = os.path.join(ROOT, "elba_amd", "hostcpp", "test_host_contigs_ex")
-    if not os.path.exists(binpath):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "elba_amd", "hostcpp")], stdout=subprocess.DEVNULL)
     rng = np.random.default_rng(50)
     circle, line = cx.random_genome(rng, 24000), cx.random_genome(rng, 12000)
     seqs = [(circle + circle)[i:i + 3000] for i in range(0, 24000, 1000)] + [line[i:i + 3000] for i in range(0, 9001, 1000)]
     seqs = [cu.revcomp(s) if rng.random() < 0.5 else s for s in seqs] + [cx.random_genome(rng, 1500) for _ in range(3)]
     seqs = [seqs[i] for i in rng.permutation(len(seqs))]
-    fa = tmp_path / "reads.fa"
-    with open(fa, "w") as f:
-        for i, s in enumerate(seqs):
-            f.write(">r%d\n%s\n" % (i, s))
+    fa = hu.write_fasta(tmp_path / "reads.fa", seqs)
     packed, off, lens = cu.pack(seqs)
     e = elba_amd.Engine(17, 2, 12)
     e.set_reads(packed, off, lens)
@@ -450,7 +442,7 @@ def test_writers_agree_with_and_without_kinds(tmp_path):
     got = e.export_contigs()
     for with_kinds in (1, 0):
         out, ref = tmp_path / ("cpp%d.contigs.fa" % with_kinds), tmp_path / ("py%d.contigs.fa" % with_kinds)
-        subprocess.run([binpath, str(fa), "17", "2", "12", str(out), "3", str(with_kinds)], check=True, capture_output=True, text=True)
+        hu.run_json(hu.binary("test_host_contigs_ex"), [fa, 17, 2, 12, out, 3, with_kinds])
         formats.write_contigs_fasta(str(ref), got["seqs"], kinds=got["kinds"] if with_kinds else None)
         assert out.read_bytes() == ref.read_bytes()
         heads = [ln for ln in ref.read_text().split("\n") if ln.startswith(">")]

@@ -7,36 +7,24 @@ import subprocess
 import numpy as np
 import pytest
 
+import hostcpp_util as hu
 import util
 from oracle import pyoracle as po
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "elba_amd", "hostcpp", "test_host_mirror")
-
-
-def _build():
-    subprocess.check_call(["make", "-C", os.path.join(ROOT, "elba_amd", "hostcpp")], stdout=subprocess.DEVNULL)
-
 
 def test_mirror_builds_and_fails_loudly_without_gpu():
-    _build()
-    p = subprocess.run([BIN, os.path.join(util.GOLDEN, "small_err.fa"), "17", "2", "8"], capture_output=True, text=True)
-    if p.returncode == 3:
-        assert "no HIP device" in p.stderr          # no silent CPU path
-    else:
-        assert p.returncode == 0 and json.loads(p.stdout)["reads"] > 0
+    got = hu.runs_or_reports_no_device([hu.binary("test_host_mirror"), os.path.join(util.GOLDEN, "small_err.fa"), 17, 2, 8])
+    assert got is None or got["reads"] > 0
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("name,idx", [("small_err", 0), ("small_clean", 1)])
 def test_mirror_matches_oracle_on_gpu(name, idx):
-    if not os.path.exists(BIN):
-        _build()
+    BIN = hu.binary("test_host_mirror")
     m = util.golden_meta()[name][idx]
     k, lo, up = m["k"], m["lower"], m["upper"]
     fa = os.path.join(util.GOLDEN, name + ".fa")
-    p = subprocess.run([BIN, fa, str(k), str(lo), str(up)], capture_output=True, text=True, check=True)
-    got = json.loads(p.stdout)
+    got = hu.run_json(BIN, [fa, k, lo, up])
     packed, off, lens = po.pack_reads(util.read_fasta(fa))
     o = po.Oracle(k, lo, up)
     o.count_and_build(packed, off, lens)
@@ -75,9 +63,9 @@ def test_mirror_matches_oracle_on_gpu(name, idx):
         fa2 = os.path.join(td, "reads.fa")
         shutil.copy(fa, fa2)
         efa.write_fai(fa2)
-        p2 = subprocess.run([BIN, fa2, str(k), str(lo), str(up), "fai"], capture_output=True, text=True, check=True)
+        got2 = hu.run_json(BIN, [fa2, k, lo, up, "fai"])
     want["ingest_equal"] = 1
-    assert json.loads(p2.stdout) == want
+    assert got2 == want
 
 
 @pytest.mark.gpu
@@ -85,13 +73,11 @@ def test_cpp_writers_equal_the_python_ones_fed_from_the_oracle(tmp_path):
     """SURVEY.md §8f-4 on the C++ side (elba_host.hpp: log_seed_matrix, parallel_write_paf over the GPU's B, R and S) against elba_amd/formats.py
     driven by the ORACLE's matrices: B.mtx in SharedSeeds notation, overlap.paf and string.paf in the order the reference walks its DCSC."""
     from elba_amd import formats as fm
-    if not os.path.exists(BIN):
-        _build()
     m = util.golden_meta()["small_err"][0]
     k, lo, up = m["k"], m["lower"], m["upper"]
     fa = os.path.join(util.GOLDEN, "small_err.fa")
     pfx = str(tmp_path) + os.sep
-    subprocess.run([BIN, fa, str(k), str(lo), str(up)], capture_output=True, text=True, check=True, env=dict(os.environ, ELBA_OUT_PREFIX=pfx))
+    hu.run_json(hu.binary("test_host_mirror"), [fa, k, lo, up], ELBA_OUT_PREFIX=pfx)
     packed, off, lens = po.pack_reads(util.read_fasta(fa))
     o = po.Oracle(k, lo, up); o.count_and_build(packed, off, lens); o.spgemm(1)
     M = m["M"]
@@ -106,12 +92,8 @@ def test_cpp_writers_equal_the_python_ones_fed_from_the_oracle(tmp_path):
     assert open(pfx + "string.paf").read() == open(pfx + "o_string.paf").read()
 
 
-DIST_BIN = os.path.join(ROOT, "elba_amd", "hostcpp", "test_host_dist")
-
-
 def test_rccl_host_builds_and_fails_loudly_without_gpu():
-    _build()
-    p = subprocess.run([DIST_BIN, os.path.join(util.GOLDEN, "small_err.fa"), "17", "2", "8"], capture_output=True, text=True)
+    p = subprocess.run([hu.binary("test_host_dist"), os.path.join(util.GOLDEN, "small_err.fa"), "17", "2", "8"], capture_output=True, text=True)
     assert p.returncode in (0, 3) and (p.returncode == 0 or "no HIP device" in p.stderr)
 
 
@@ -119,8 +101,7 @@ def test_rccl_host_builds_and_fails_loudly_without_gpu():
 def test_rccl_host_world_of_one_matches_oracle():
     """elba_host_dist.hpp (C++ over RCCL: ncclAllReduce / ncclAllGather / grouped ncclSend + ncclRecv) end to end with one rank: the rows of
     B it computes must be the oracle's (count, and a checksum over every entry's row, column, both seeds and numshared)."""
-    if not os.path.exists(DIST_BIN):
-        _build()
+    DIST_BIN = hu.binary("test_host_dist")
     fa = os.path.join(util.GOLDEN, "small_err.fa")
     p = subprocess.run([DIST_BIN, fa, "17", "2", "8"], capture_output=True, text=True, check=True)
     got = json.loads(p.stdout.strip().splitlines()[-1])

@@ -1,24 +1,14 @@
 """The C++ host mirror of the assembly graph (assembly_links and write_gfa in elba_amd/hostcpp/elba_host.hpp) against the Python binding
 on two loaded graphs: the same records, the same counts, the same GFA bytes."""
-import json
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import contig_util as cu
 import elba_amd
 import gfa_util as gu
+import hostcpp_util as hu
 from elba_amd import formats
 from oracle import pyoracle as po
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "elba_amd", "hostcpp", "test_host_gfa")
-
-
-def _build():
-    subprocess.check_call(["make", "-C", os.path.join(ROOT, "elba_amd", "hostcpp")], stdout=subprocess.DEVNULL)
 
 
 def _hub_and_rings(rng):
@@ -42,9 +32,7 @@ def _truth(rng):
 
 def _write_inputs(tmp_path, seqs, edges):
     fa, ed = tmp_path / "reads.fa", tmp_path / "edges.txt"
-    with open(fa, "w") as f:
-        for i, s in enumerate(seqs):
-            f.write(">r%d\n%s\n" % (i, s))
+    hu.write_fasta(fa, seqs)
     rows, cols, vals = cu.upper(edges)
     with open(ed, "w") as f:
         for r, c, v in zip(rows, cols, vals):
@@ -53,25 +41,19 @@ def _write_inputs(tmp_path, seqs, edges):
 
 
 def test_gfa_mirror_builds_and_fails_loudly_without_gpu(tmp_path):
-    _build()
     seqs, edges = _truth(np.random.default_rng(1))
     fa, ed, _ = _write_inputs(tmp_path, seqs, edges)
-    p = subprocess.run([BIN, str(fa), str(ed), "3", str(tmp_path / "o.gfa"), str(tmp_path / "o.links")], capture_output=True, text=True)
-    if p.returncode == 3:
-        assert "no HIP device" in p.stderr
-    else:
-        assert p.returncode == 0 and json.loads(p.stdout)["reads"] == 40
+    got = hu.runs_or_reports_no_device([hu.binary("test_host_gfa"), fa, ed, 3, tmp_path / "o.gfa", tmp_path / "o.links"])
+    assert got is None or got["reads"] == 40
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("which", ["hub_and_rings", "ground_truth"])
 def test_gfa_mirror_equals_the_python_binding(which, tmp_path):
-    if not os.path.exists(BIN):
-        _build()
     seqs, edges = (_hub_and_rings if which == "hub_and_rings" else _truth)(np.random.default_rng(9))
     fa, ed, (rows, cols, vals) = _write_inputs(tmp_path, seqs, edges)
     out, lk = tmp_path / "cpp.gfa", tmp_path / "cpp.links"
-    got = json.loads(subprocess.run([BIN, str(fa), str(ed), "3", str(out), str(lk)], capture_output=True, text=True, check=True).stdout)
+    got = hu.run_json(hu.binary("test_host_gfa"), [fa, ed, 3, out, lk])
     e = elba_amd.Engine(17, 2, 8)
     e.set_reads(*cu.pack(seqs))
     full = np.zeros(len(rows), dtype=po.OVERLAP_DTYPE)          # what the mirror's text carries: the four fields the stages read, passed

@@ -1,47 +1,35 @@
 """The C++ host mirror of the pileup stage (GetReadPileup, PileupVector::GetTrimmedInterval, PruneFull in elba_amd/hostcpp/elba_host.hpp)
 against the Python binding on one workload: the same pileups (per-base checksum), the host trim equal to the device's on every read, the
 same prune and string graph."""
-import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import elba_amd
+import hostcpp_util as hu
 import util
 from oracle import pyoracle as po
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "elba_amd", "hostcpp", "test_host_pileup")
 FA = os.path.join(util.GOLDEN, "small_err.fa")
 CFG = dict(mode=1, margin=20, min_depth=2, min_run=300, trim_len=500)
 MASK = 3
 
 
-def _build():
-    subprocess.check_call(["make", "-C", os.path.join(ROOT, "elba_amd", "hostcpp")], stdout=subprocess.DEVNULL)
-
-
 def _args():
     m = util.golden_meta()["small_err"][0]
-    return [BIN, FA, str(m["k"]), str(m["lower"]), str(m["upper"])] + [str(CFG[k]) for k in ("mode", "margin", "min_depth", "min_run", "trim_len")] + [str(MASK)]
+    return [hu.binary("test_host_pileup"), FA, str(m["k"]), str(m["lower"]), str(m["upper"])] + [str(CFG[k]) for k in ("mode", "margin", "min_depth", "min_run", "trim_len")] + [str(MASK)]
 
 
 def test_pileup_mirror_builds_and_fails_loudly_without_gpu():
-    _build()
-    p = subprocess.run(_args(), capture_output=True, text=True)
-    if p.returncode == 3:
-        assert "no HIP device" in p.stderr
-    else:
-        assert p.returncode == 0 and json.loads(p.stdout)["reads"] == 80
+    got = hu.runs_or_reports_no_device(_args())
+    assert got is None or got["reads"] == 80
 
 
 @pytest.mark.gpu
 def test_pileup_mirror_equals_the_python_binding():
-    if not os.path.exists(BIN):
-        _build()
-    got = json.loads(subprocess.run(_args(), capture_output=True, text=True, check=True).stdout)
+    args = _args()
+    got = hu.run_json(args[0], args[1:])
     m = util.golden_meta()["small_err"][0]
     packed, off, lens = po.pack_reads(util.read_fasta(FA))
     e = elba_amd.Engine(m["k"], m["lower"], m["upper"])

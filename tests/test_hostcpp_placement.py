@@ -1,31 +1,20 @@
 """The C++ host mirror of the read placements (place_reads, write_placements_paf and write_gfa's depth in elba_amd/hostcpp/elba_host.hpp)
 against the Python binding on ground-truth layouts: the same records, segments, credits and counts, the same PAF and GFA bytes."""
-import json
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import contig_util as cu
 import elba_amd
+import hostcpp_util as hu
 import placement_util as pu
 from elba_amd import formats
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "elba_amd", "hostcpp", "test_host_place")
 FIELDS = ("begQ", "endQ", "begT", "endT", "rc", "score", "passed", "containedQ", "containedT", "direction", "directionT", "suffix", "suffixT")
-
-
-def _build():
-    subprocess.check_call(["make", "-C", os.path.join(ROOT, "elba_amd", "hostcpp")], stdout=subprocess.DEVNULL)
 
 
 def _write_inputs(tmp_path, t):
     fa, pr = tmp_path / "reads.fa", tmp_path / "pairs.txt"
-    with open(fa, "w") as f:
-        for i, s in enumerate(t["seqs"]):
-            f.write(">r%d\n%s\n" % (i, s))
+    hu.write_fasta(fa, t["seqs"])
     rows, cols, vals = t["pairs"]
     with open(pr, "w") as f:
         for r, c, v in zip(rows, cols, vals):
@@ -33,31 +22,25 @@ def _write_inputs(tmp_path, t):
     return fa, pr
 
 
-def _run(tmp_path, fa, pr, flags, skip):
+def _args(tmp_path, fa, pr, flags, skip):
     out = [tmp_path / n for n in ("cpp.paf", "cpp.gfa", "cpp.records")]
-    return subprocess.run([BIN, str(fa), str(pr), str(flags), str(skip)] + [str(o) for o in out], capture_output=True, text=True), out
+    return [hu.binary("test_host_place"), fa, pr, flags, skip] + out, out
 
 
 def test_placement_mirror_builds_and_fails_loudly_without_gpu(tmp_path):
-    _build()
     t = pu.truth_set(np.random.default_rng(1), 900, 12, False, 15, 6)
-    p, _ = _run(tmp_path, *_write_inputs(tmp_path, t), 1, 1)
-    if p.returncode == 3:
-        assert "no HIP device" in p.stderr
-    else:
-        assert p.returncode == 0 and json.loads(p.stdout)["nreads"] == 33
+    args, _ = _args(tmp_path, *_write_inputs(tmp_path, t), 1, 1)
+    got = hu.runs_or_reports_no_device(args)
+    assert got is None or got["nreads"] == 33
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("seed,glen,nchain,circular,ncont,nextra,skip", [(2, 1200, 9, True, 20, 8, 1), (5, 1500, 20, False, 30, 12, 1), (5, 1500, 20, False, 30, 12, 2)])
 def test_placement_mirror_equals_the_python_binding(seed, glen, nchain, circular, ncont, nextra, skip, tmp_path):
-    if not os.path.exists(BIN):
-        _build()
     t = pu.truth_set(np.random.default_rng(seed), glen, nchain, circular, ncont, nextra)
     fa, pr = _write_inputs(tmp_path, t)
-    p, (paf, gfa, rec) = _run(tmp_path, fa, pr, 3, skip)
-    assert p.returncode == 0, p.stderr
-    got = json.loads(p.stdout)
+    args, (paf, gfa, rec) = _args(tmp_path, fa, pr, 3, skip)
+    got = hu.run_json(args[0], args[1:])
     e = elba_amd.Engine(17, 2, 8)
     e.set_reads(*cu.pack(t["seqs"]))
     e.set_overlaps(len(t["seqs"]), *t["pairs"])

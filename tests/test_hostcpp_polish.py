@@ -1,33 +1,22 @@
 """The C++ host mirror of contig polishing (polish_contigs in elba_amd/hostcpp/elba_host.hpp) against the Python binding on ground-truth
 layouts with planted errors: the same polished bytes, per-contig counts, per-read records, votes and stats."""
-import json
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import consensus_util as cs
 import contig_util as cu
 import elba_amd
+import hostcpp_util as hu
 import placement_util as pu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "elba_amd", "hostcpp", "test_host_polish")
 FIELDS = ("begQ", "endQ", "begT", "endT", "rc", "score", "passed", "containedQ", "containedT", "direction", "directionT", "suffix", "suffixT")
-
-
-def _build():
-    subprocess.check_call(["make", "-C", os.path.join(ROOT, "elba_amd", "hostcpp")], stdout=subprocess.DEVNULL)
 
 
 def _inputs(tmp_path, seed, glen, nchain, circular, ncont, nextra, nerr):
     t = pu.truth_set(np.random.default_rng(seed), glen, nchain, circular, ncont, nextra)
     seqs, _ = cs.mutate_truth(t, np.random.default_rng(seed + 1000), nerr)
     fa, pr = tmp_path / "reads.fa", tmp_path / "pairs.txt"
-    with open(fa, "w") as f:
-        for i, s in enumerate(seqs):
-            f.write(">r%d\n%s\n" % (i, s))
+    hu.write_fasta(fa, seqs)
     rows, cols, vals = t["pairs"]
     with open(pr, "w") as f:
         for r, c, v in zip(rows, cols, vals):
@@ -35,30 +24,24 @@ def _inputs(tmp_path, seed, glen, nchain, circular, ncont, nextra, nerr):
     return t, seqs, fa, pr
 
 
-def _run(tmp_path, fa, pr, flags, skip, band, max_diff, min_depth):
+def _args(tmp_path, fa, pr, flags, skip, band, max_diff, min_depth):
     out = tmp_path / "cpp.txt"
-    return subprocess.run([BIN, str(fa), str(pr), str(flags), str(skip), str(band), repr(max_diff), str(min_depth), str(out)], capture_output=True, text=True), out
+    return [hu.binary("test_host_polish"), fa, pr, flags, skip, band, repr(max_diff), min_depth, out], out
 
 
 def test_polish_mirror_builds_and_fails_loudly_without_gpu(tmp_path):
-    _build()
     t, seqs, fa, pr = _inputs(tmp_path, 7, 600, 6, False, 45, 3, 8)
-    p, _ = _run(tmp_path, fa, pr, 1, 1, 64, 0.25, 3)
-    if p.returncode == 3:
-        assert "no HIP device" in p.stderr
-    else:
-        assert p.returncode == 0 and json.loads(p.stdout)["nreads"] == 54
+    args, _ = _args(tmp_path, fa, pr, 1, 1, 64, 0.25, 3)
+    got = hu.runs_or_reports_no_device(args)
+    assert got is None or got["nreads"] == 54
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("seed,glen,nchain,circular,ncont,nextra,nerr,band", [(2, 1200, 9, True, 80, 8, 14, 64), (7, 600, 6, False, 45, 3, 8, 128)])
 def test_polish_mirror_equals_the_python_binding(seed, glen, nchain, circular, ncont, nextra, nerr, band, tmp_path):
-    if not os.path.exists(BIN):
-        _build()
     t, seqs, fa, pr = _inputs(tmp_path, seed, glen, nchain, circular, ncont, nextra, nerr)
-    p, outf = _run(tmp_path, fa, pr, 3, 1, band, 0.25, 3)
-    assert p.returncode == 0, p.stderr
-    got = json.loads(p.stdout)
+    args, outf = _args(tmp_path, fa, pr, 3, 1, band, 0.25, 3)
+    got = hu.run_json(args[0], args[1:])
     e = elba_amd.Engine(17, 2, 8)
     e.set_reads(*cu.pack(seqs))
     e.set_overlaps(len(seqs), *t["pairs"])

@@ -1,32 +1,21 @@
 """The C++ host mirror of the text ingest (set_reads_text in elba_amd/hostcpp/elba_host.hpp) against the Python binding on a FASTA and a
 FASTQ file: the same reads, bases, lines and format, the same .fai records, names and packed bytes (checksums)."""
-import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import elba_amd
+import hostcpp_util as hu
 import text_index_util as tx
 import util
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "elba_amd", "hostcpp", "test_host_text")
 FA = os.path.join(util.GOLDEN, "small_err.fa")
 
 
-def _build():
-    subprocess.check_call(["make", "-C", os.path.join(ROOT, "elba_amd", "hostcpp")], stdout=subprocess.DEVNULL)
-
-
 def test_text_mirror_builds_and_fails_loudly_without_gpu():
-    _build()
-    p = subprocess.run([BIN, FA], capture_output=True, text=True)
-    if p.returncode == 3:
-        assert "no HIP device" in p.stderr
-    else:
-        assert p.returncode == 0 and json.loads(p.stdout)["reads"] == len(util.read_fasta(FA))
+    got = hu.runs_or_reports_no_device([hu.binary("test_host_text"), FA])
+    assert got is None or got["reads"] == len(util.read_fasta(FA))
 
 
 def _u64sum(x):
@@ -36,14 +25,12 @@ def _u64sum(x):
 @pytest.mark.gpu
 @pytest.mark.parametrize("fmt", ["fasta", "fastq"])
 def test_text_mirror_equals_the_python_binding(tmp_path, fmt):
-    if not os.path.exists(BIN):
-        _build()
     seqs = util.read_fasta(FA)
     names = [b"r%d/%d extra words" % (i, len(s)) for i, s in enumerate(seqs)]
     path = str(tmp_path / ("reads." + fmt))
     with open(path, "wb") as f:
         f.write(tx.fasta_bytes(seqs, 70, names=names) if fmt == "fasta" else tx.fastq_bytes(seqs, names=names))
-    got = json.loads(subprocess.run([BIN, path], capture_output=True, text=True, check=True).stdout)
+    got = hu.run_json(hu.binary("test_host_text"), [path])
     e = elba_amd.Engine(17, 2, 8)
     st = e.set_reads_file(path)
     rnames, recs = e.export_read_index()
