@@ -125,6 +125,30 @@ LINK_DTYPE = np.dtype([("from", "<u4"), ("to", "<u4"), ("from_read", "<u4"), ("t
 LINK_CLOSURE = 1          # elba_link_t.flags bit 0
 
 
+CC_STRING, CC_OVERLAPS = 0, 1          # elba_cc_cfg.graph
+CC_BASES = 1                           # elba_cc_cfg.flags
+_CC_GRAPHS = {"string": CC_STRING, "overlaps": CC_OVERLAPS}
+_CC_WEIGHTS = {"reads": 0, "bases": 1}
+
+
+class CcCfg(C.Structure):
+    _fields_ = [("graph", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class Components(C.Structure):
+    _fields_ = [("nreads", C.c_int64), ("n", C.c_int64), ("comp_of_read", C.c_void_p), ("first_read", C.c_void_p), ("reads", C.c_void_p), ("bases", C.c_void_p),
+                ("edges", C.c_void_p), ("branches", C.c_void_p), ("ends", C.c_void_p)]
+
+
+class CcStats(C.Structure):
+    _fields_ = [("nreads", C.c_int64), ("edges", C.c_int64), ("components", C.c_int64), ("used_components", C.c_int64), ("isolated", C.c_int64),
+                ("largest_reads", C.c_int64), ("largest_bases", C.c_int64), ("passes", C.c_int32), ("reserved", C.c_int32), ("ms_total", C.c_float), ("ms_label", C.c_float)]
+
+
+class PartCfg(C.Structure):
+    _fields_ = [("graph", C.c_int32), ("nparts", C.c_int32), ("weight", C.c_int32), ("min_reads", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
 class PlaceCfg(C.Structure):
     _fields_ = [("skip_flags", C.c_int32), ("reserved", C.c_int32 * 3)]
 
@@ -301,6 +325,7 @@ EXPORTED_SYMBOLS = [
     "elba_export_assembly_links", "elba_free_links",
     "elba_place_reads", "elba_free_placements",
     "elba_polish_contigs", "elba_free_polished",
+    "elba_graph_components", "elba_free_components", "elba_partition_components",
 ]
 
 _lib = None
@@ -369,6 +394,9 @@ def load_library():
     L.elba_free_placements.restype = None; L.elba_free_placements.argtypes = [C.POINTER(Placements)]
     L.elba_polish_contigs.restype = i32; L.elba_polish_contigs.argtypes = [vp, C.POINTER(PolishCfg), C.POINTER(Polished), C.POINTER(PolishStats)]
     L.elba_free_polished.restype = None; L.elba_free_polished.argtypes = [C.POINTER(Polished)]
+    L.elba_graph_components.restype = i32; L.elba_graph_components.argtypes = [vp, C.POINTER(CcCfg), C.POINTER(Components), C.POINTER(CcStats)]
+    L.elba_free_components.restype = None; L.elba_free_components.argtypes = [C.POINTER(Components)]
+    L.elba_partition_components.restype = i32; L.elba_partition_components.argtypes = [vp, C.POINTER(PartCfg), vp, i64, vp]
     L.elba_read_pileup.restype = i32; L.elba_read_pileup.argtypes = [vp, C.POINTER(PileupCfg), C.POINTER(PileupStats)]
     L.elba_export_pileup.restype = i32; L.elba_export_pileup.argtypes = [vp, C.POINTER(Pileup)]
     L.elba_free_pileup.restype = None; L.elba_free_pileup.argtypes = [C.POINTER(Pileup)]
@@ -781,6 +809,46 @@ class Engine:
         out = _stats(st)
         del out["reserved"]
         return links, out
+
+    def graph_components(self, graph="string", bases=False, flags=None, reserved=(0, 0)):
+        """Connected components of the string graph ("string") or of the overlap graph ("overlaps": the passed pairs of the graph's
+        input); include/elba_amd.h states the rule.  Every read gets one; components are numbered by ascending smallest read.  Returns
+        ({comp_of_read (i32[nreads]), first_read, reads, bases, edges, branches, ends (i64[n])}, stats dict); bases is all zero without
+        bases=True, which needs the reads' lengths on the context.  formats.write_gfa(component=) and write_contigs_fasta(components=)
+        take a contig's component: that of its first chain read."""
+        g = _CC_GRAPHS.get(graph, graph) if isinstance(graph, str) else graph
+        if isinstance(g, str):
+            raise ValueError("graph_components: graph is 'string' or 'overlaps'")
+        fl = (CC_BASES if bases else 0) if flags is None else int(flags)
+        cfg = CcCfg(int(g), fl, (C.c_int32 * 2)(*[int(x) for x in reserved]))
+        o, st = Components(), CcStats()
+        self._check(self.L.elba_graph_components(self.h, C.byref(cfg), C.byref(o), C.byref(st)))
+        try:
+            M, n = int(o.nreads), int(o.n)
+            cc = dict(comp_of_read=_copy(o.comp_of_read, M, np.int32))
+            for name in ("first_read", "reads", "bases", "edges", "branches", "ends"):
+                cc[name] = _copy(getattr(o, name), n, np.int64)
+        finally:
+            self.L.elba_free_components(C.byref(o))
+        out = _stats(st)
+        del out["reserved"]
+        return cc, out
+
+    def partition_components(self, nparts, graph="string", weight="reads", min_reads=2, nreads=None, reserved=(0, 0, 0, 0)):
+        """The reference's greedy assignment of components to `nparts` parts, made deterministic (include/elba_amd.h): the components of
+        at least min_reads reads, heaviest first (weight "reads" or "bases"), each to the part with the smallest sum so far.  The call
+        labels the graph itself.  Returns (part_of_read (i32[nreads], -1: a read of a smaller component), part_weight (i64[nparts]))."""
+        g = _CC_GRAPHS.get(graph, graph) if isinstance(graph, str) else graph
+        w = _CC_WEIGHTS.get(weight, weight) if isinstance(weight, str) else weight
+        if isinstance(g, str) or isinstance(w, str):
+            raise ValueError("partition_components: graph is 'string' or 'overlaps', weight is 'reads' or 'bases'")
+        cfg = PartCfg(int(g), int(nparts), int(w), int(min_reads), (C.c_int32 * 4)(*[int(x) for x in reserved]))
+        if nreads is None:
+            nreads = self.graph_components(graph=int(g))[1]["nreads"]
+        part = np.full(max(int(nreads), 1), -1, dtype=np.int32)
+        pw = np.zeros(max(int(nparts), 1), dtype=np.int64)
+        self._check(self.L.elba_partition_components(self.h, C.byref(cfg), part.ctypes.data, int(nreads), pw.ctypes.data))
+        return part[:int(nreads)], pw[:max(int(nparts), 0)]
 
     def place_reads(self, skip_flags=1, reserved=(0, 0, 0)):
         """Every read on its contig and the depth of every contig base (include/elba_amd.h states the rule): chain reads where the contig

@@ -505,6 +505,30 @@ int elba_polish_contigs(elba_ctx *ctx, const elba_polish_cfg *cfg, elba_polished
     return rc;
 }
 
+int elba_graph_components(elba_ctx *ctx, const elba_cc_cfg *cfg, elba_components_t *out, elba_cc_stats *stats)
+{
+    if (out) memset(out, 0, sizeof(*out));                        // (before anything can fail: what is freed below is this call's)
+    const int rc = guarded(ctx, [&](Ctx &c) {
+        ELBA_REQUIRE(out, ELBA_ERR_INVALID_ARG, "graph_components: null output");
+        stage_graph_components(c, cfg, out);
+        if (stats) *stats = c.cc.stats;
+    });
+    if (rc != ELBA_OK && ctx && out) elba_free_components(out);      // (a copy that failed behind the allocations)
+    return rc;
+}
+
+void elba_free_components(elba_components_t *p)
+{
+    if (!p) return;
+    free(p->comp_of_read); free(p->first_read); free(p->reads); free(p->bases); free(p->edges); free(p->branches); free(p->ends);
+    memset(p, 0, sizeof(*p));
+}
+
+int elba_partition_components(elba_ctx *ctx, const elba_part_cfg *cfg, int32_t *part_of_read, int64_t nreads, int64_t *part_weight)
+{
+    return guarded(ctx, [&](Ctx &c) { stage_partition_components(c, cfg, part_of_read, nreads, part_weight); });
+}
+
 void elba_free_polished(elba_polished_t *p)
 {
     if (!p) return;
@@ -804,7 +828,7 @@ int elba_release_workspace(elba_ctx *ctx)
         c.ws_a.release(); c.ws_b.release(); c.ws_c.release(); c.ws_d.release(); c.ws_e.release(); c.ws_f.release(); c.ws_g.release(); c.ws_h.release(); c.ws_sort.release();
         c.csr_words.release(); c.kid_of_entry.release();
         // the late stages: what each keeps is its release_scratch()'s decision (common.hpp, the stage structs of Ctx)
-        c.cg.release_scratch(); c.gl.release_scratch(); c.pu.release_scratch(); c.pl.release_scratch(); c.po.release_scratch(); c.tm.release_scratch();
+        c.cg.release_scratch(); c.gl.release_scratch(); c.pu.release_scratch(); c.pl.release_scratch(); c.po.release_scratch(); c.cc.release_scratch(); c.tm.release_scratch();
         c.sg.release();      // the cleaning calls' shared scratch and the spare buffer of S (S itself stays)
         c.tp.release_scratch(); c.bb.release_scratch(); c.wk.release_scratch(); c.br.release_scratch(); c.sr.release_scratch();
         if (has(c.v, P_COUNTS)) { c.pre_ready = false; c.pre_consumed = true; }    // (the CSR sort keys / column ids of the entries are gone: create_kmer_matrix rebuilds them from the column pointers)
@@ -876,6 +900,16 @@ int elba_get_stat(elba_ctx *ctx, const char *name, int64_t *value)
             static const StatName<S> table[] = {{"voted", &S::voted}, {"rejected", &S::rejected}, {"outside", &S::outside}, {"low_depth_columns", &S::low_depth_columns},
                                                 {"bases_before", &S::bases_before}, {"bases_after", &S::bases_after}, {"sum_dist", &S::sum_dist}, {"cells", &S::cells}, {"batches", &S::batches}};
             *value = stage_stat(table, c.po.stats, has(c.v, P_S, P_CONTIGS) && c.po.for_cg == c.cg.serial && c.po.for_cg != 0, name + 7, name);
+        }
+        // the last labelling (elba_graph_components / elba_partition_components), while the graph it labelled is valid
+        else if (!strncmp(name, "cc_", 3)) {
+            using S = elba_cc_stats;
+            const bool valid = c.cc.graph == ELBA_CC_STRING ? has(c.v, P_S) : c.cc.graph == ELBA_CC_OVERLAPS && (has(c.v, P_EDGES) || has(c.v, P_ALN));
+            if (!strcmp(name, "cc_passes")) *value = valid ? c.cc.stats.passes : 0;
+            else {
+                static const StatName<S> table[] = {{"components", &S::components}, {"used_components", &S::used_components}, {"largest_reads", &S::largest_reads}};
+                *value = stage_stat(table, c.cc.stats, valid, name + 3, name);
+            }
         }
         else if (!strcmp(name, "contig_rank_us")) *value = has(c.v, P_S, P_CONTIGS) ? (int64_t)(c.cg.stats.ms_rank * 1000.0f) : -1;
         else if (!strcmp(name, "resident_bytes_A")) {

@@ -424,6 +424,17 @@ struct Ctx {
     // resolving three-armed stars (stars.hip): scratch of its own, one word per read.  It reads tr_ptr / tr_sym
     struct StarStage { DevBuf word; elba_star_stats stats{}; void release_scratch() { word.release(); } } sr;
 
+    // connected components (components.hip): all scratch — the label of every read, degrees, the column pointers of S, root flags and their
+    // scan, the component of every read, the counters, the six tables of M slots each, and the partition's two arrays.  graph: the kind the
+    // counts in stats belong to (-1: none)
+    struct ComponentStage {
+        DevBuf par, deg, ptr, flag, rank, comp, st, tab, pcomp, pread;
+        EventTimer t_total, t_label;
+        elba_cc_stats stats{};
+        int graph = -1;
+        void release_scratch() { for (DevBuf *b : {&par, &deg, &ptr, &flag, &rank, &comp, &st, &tab, &pcomp, &pread}) b->release(); }
+    } cc;
+
     // workspaces
     DevBuf ws_scan, ws_sort, ws_a, ws_b, ws_c, ws_d, ws_e, ws_f;
     DevBuf ws_cursor;       // the gather-slot cursor of the k-mer stage's emit kernels (kmer_msd.hip)
@@ -560,6 +571,8 @@ void stage_generate_contigs_ex(Ctx &c, const elba_contig_cfg *cfg);             
 void stage_export_assembly_links(Ctx &c, elba_links_t *out);                             // graph_links.hip (out->links: malloc)
 void stage_place_reads(Ctx &c, const elba_place_cfg *cfg, elba_placements_t *out);        // place.hip (out's arrays: malloc)
 void stage_polish_contigs(Ctx &c, const elba_polish_cfg *cfg, elba_polished_t *out);       // polish.hip (out's arrays: malloc)
+void stage_graph_components(Ctx &c, const elba_cc_cfg *cfg, elba_components_t *out);      // components.hip (out's arrays: malloc)
+void stage_partition_components(Ctx &c, const elba_part_cfg *cfg, int32_t *part_of_read, int64_t nreads, int64_t *part_weight);
 void stage_read_pileup(Ctx &c, const elba_pileup_cfg *cfg);                   // pileup.hip
 void stage_prune_reads(Ctx &c, int mask, int64_t *kept);
 void stage_trim_reads(Ctx &c, const elba_trim_cfg *cfg);                      // trim.hip

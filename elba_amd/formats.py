@@ -100,15 +100,26 @@ def write_paf(path, overlaps, names, lens, dcsc_order=False):
             f.write(paf_line(overlaps["vals"][a], names[i], names[j], int(lens[i]), int(lens[j])) + "\n")
 
 
-def write_contigs_fasta(path, seqs, first=0, kinds=None):
+def contig_components(comp_of_read, chain_off, chain_read, id_base=0):
+    """One component id per contig from Engine.graph_components()["comp_of_read"] and the chains of Engine.export_contigs(): a contig's
+    component is that of its first chain read (chain_read holds the ids the graph exports show: read + id_base)."""
+    n = len(chain_off) - 1
+    return np.array([int(comp_of_read[int(chain_read[int(chain_off[i])]) - int(id_base)]) for i in range(n)], dtype=np.int64)
+
+
+def write_contigs_fasta(path, seqs, first=0, kinds=None, components=None):
     """<prefix>.contigs.fa as parallel_write_contigs writes it (src/main.cpp:496-499): `>contig<i>` then the sequence, i counted from `first`
     (the rank's offset from MPI_Exscan; 0 on one rank).  With `kinds` (one per contig, Engine.export_contigs()["kinds"]) the header of a
-    circular contig (kind 1) is `>contig<i> circular`; every other line is the same."""
+    circular contig (kind 1) is `>contig<i> circular`; every other line is the same.  With `components` (one component id per contig,
+    contig_components) the header also ends in ` component=<id>`; without it every byte is as before."""
     if kinds is not None and len(kinds) != len(seqs):
         raise ValueError("write_contigs_fasta: one kind per contig")
+    if components is not None and len(components) != len(seqs):
+        raise ValueError("write_contigs_fasta: one component per contig")
     with open(path, "wb") as f:
         for i, s in enumerate(seqs):
-            f.write(b">contig%d%s\n" % (i + first, b" circular" if kinds is not None and int(kinds[i]) == 1 else b""))
+            f.write(b">contig%d%s%s\n" % (i + first, b" circular" if kinds is not None and int(kinds[i]) == 1 else b"",
+                                         b" component=%d" % int(components[i]) if components is not None else b""))
             f.write(s.encode("ascii") if isinstance(s, str) else bytes(s))
             f.write(b"\n")
 
@@ -155,14 +166,17 @@ def write_placements_paf(path, placements, names, lens, contig_lens, kinds=None)
                                                                                     tb, te, int(p["score"]), te - tb))
 
 
-def write_gfa(path, seqs, kinds, links, chains=None, depth=None):
+def write_gfa(path, seqs, kinds, links, chains=None, depth=None, component=None):
     """The assembly graph as GFA 1: `H\tVN:Z:1.0`, one `S\tcontig<i>\t<seq>\tLN:i:<len>` per contig (the names of write_contigs_fasta;
     with `chains`, the chain_off of Engine.export_contigs() or one chain per contig, also `\tRC:i:<reads>`), and one
     `L\tcontig<a>\t+|-\tcontig<b>\t+|-\t<overlap>M` per record of Engine.assembly_links(), in their order, the closure records of circular
     contigs (a link from the contig's end to its own start, 0M) included.  `kinds` is checked against the closures: one per circular contig.
     With `depth`, the credited_bases of Engine.place_reads() (one per contig), every S line also ends in `\tDP:f:<credited bases / length>`
-    with two decimals (0.00 for a contig of no bases); without it every byte is as before."""
+    with two decimals (0.00 for a contig of no bases); without it every byte is as before.  With `component`, one component id per contig
+    (contig_components over Engine.graph_components()), every S line ends in `\tcc:i:<id>`; without it every byte is as before."""
     n = len(seqs)
+    if component is not None and len(component) != n:
+        raise ValueError("write_gfa: one component per contig")
     if kinds is not None and len(kinds) != n:
         raise ValueError("write_gfa: one kind per contig")
     if chains is not None and len(chains) not in (n, n + 1):
@@ -181,6 +195,8 @@ def write_gfa(path, seqs, kinds, links, chains=None, depth=None):
                 f.write(b"\tRC:i:%d" % (int(chains[i + 1]) - int(chains[i]) if len(chains) == n + 1 else len(chains[i])))
             if depth is not None:
                 f.write(b"\tDP:f:%.2f" % (int(depth[i]) / len(b) if len(b) else 0.0))
+            if component is not None:
+                f.write(b"\tcc:i:%d" % int(component[i]))
             f.write(b"\n")
         for r in links:
             if int(r["from"]) >= n or int(r["to"]) >= n:

@@ -794,6 +794,57 @@ inline void write_gfa(const std::string &gfa_fname, const std::vector<std::strin
     if (!f) throw Error(ELBA_ERR_INVALID_ARG, "write_gfa: cannot write " + gfa_fname);
 }
 
+// graph_components(S, graph) — elba_graph_components on the engine of S (the rule is stated in include/elba_amd.h): the connected
+// components of the string graph (ELBA_CC_STRING) or of the passed pairs it was built from (ELBA_CC_OVERLAPS), every read in one,
+// numbered by ascending smallest read, with the per-component counts.  An export: nothing on the engine changes.
+struct Components {
+    std::vector<int32_t> comp_of_read;                                       // one per read of the graph
+    std::vector<int64_t> first_read, reads, bases, edges, branches, ends;    // per component
+};
+
+inline Components graph_components(StringGraph &S, int graph = ELBA_CC_STRING, bool bases = false, elba_cc_stats *stats = nullptr)
+{
+    if (!S.engine) throw Error(ELBA_ERR_STATE, "graph_components: the string graph is not on a device");
+    elba_cc_cfg cfg{};
+    cfg.graph = graph; cfg.flags = bases ? ELBA_CC_BASES : 0;
+    elba_components_t o;
+    elba_cc_stats st{};
+    S.engine->check(elba_graph_components(S.engine->ctx, &cfg, &o, &st));
+    Components c;
+    try {
+        c.comp_of_read.assign(o.comp_of_read, o.comp_of_read + o.nreads);
+        c.first_read.assign(o.first_read, o.first_read + o.n); c.reads.assign(o.reads, o.reads + o.n); c.bases.assign(o.bases, o.bases + o.n);
+        c.edges.assign(o.edges, o.edges + o.n); c.branches.assign(o.branches, o.branches + o.n); c.ends.assign(o.ends, o.ends + o.n);
+    } catch (...) {
+        elba_free_components(&o);
+        throw;
+    }
+    elba_free_components(&o);
+    if (stats) *stats = st;
+    return c;
+}
+
+// partition_components(S, nparts) — elba_partition_components: the components of at least min_reads reads dealt to nparts parts, heaviest
+// first, each to the part with the smallest sum so far (the reference's GetLocalProcAssignments, ties closed).  part_of_read: one per
+// read, -1 for a read of a smaller component; part_weight: the sums.  A multi-GPU driver hands part p's reads to rank p.
+struct Partition {
+    std::vector<int32_t> part_of_read;
+    std::vector<int64_t> part_weight;
+};
+
+inline Partition partition_components(StringGraph &S, int nparts, int graph = ELBA_CC_STRING, int weight = 0, int min_reads = 2)
+{
+    if (!S.engine) throw Error(ELBA_ERR_STATE, "partition_components: the string graph is not on a device");
+    elba_part_cfg cfg{};
+    cfg.graph = graph; cfg.nparts = nparts; cfg.weight = weight; cfg.min_reads = min_reads;
+    Partition p;
+    p.part_of_read.assign((size_t)S.numreads, -1);
+    p.part_weight.assign((size_t)(nparts > 0 ? nparts : 1), 0);
+    S.engine->check(elba_partition_components(S.engine->ctx, &cfg, p.part_of_read.data(), S.numreads, p.part_weight.data()));
+    p.part_weight.resize((size_t)(nparts > 0 ? nparts : 0));
+    return p;
+}
+
 // place_reads(S) — elba_place_reads on the S, the contigs of the last GenerateContigs and the pairs S was built from (the rule is stated in
 // include/elba_amd.h): every read on its contig — chain reads where the contig stage put them, the others through their best passed pair
 // with a chain read — and per contig the runs of equal depth and the credits.  An export: nothing on the engine changes.

@@ -553,6 +553,64 @@ typedef struct { int64_t nreads, voted, rejected, outside, low_depth_columns, ba
 int  elba_polish_contigs(elba_ctx *ctx, const elba_polish_cfg *cfg, elba_polished_t *out, elba_polish_stats *stats);
 void elba_free_polished(elba_polished_t *p);
 
+/* Connected components: which reads belong together.  The reference labels the string graph with LACC (GetRead2Contigs,
+ * src/ContigGeneration.cpp:51) and deals the components of two or more reads out to its ranks (GetContigSizes, GetLocalProcAssignments:
+ * the largest first, each to the rank with the smallest sum so far).  elba_graph_components labels either graph of a context, every read
+ * included; elba_partition_components is that dealing made deterministic.  Both are exports: they need the graph they label (otherwise
+ * ELBA_ERR_STATE), change no product, invalidate nothing — contigs, links, placements, pileup and trimmed reads stay as they are — and keep
+ * only scratch and the counts of the last call on the context.  Every value is an integer: the result is a function of the graph alone and
+ * does not depend on the order in which reads or edges are visited or in which atomics arrive.
+ *   vertices    ELBA_CC_STRING: the reads 0 .. M-1 of the current S (M = its read count).  ELBA_CC_OVERLAPS: the reads 0 .. M-1 of the
+ *               graph's input — the list of elba_set_overlaps / elba_prune_reads while one is valid, else this context's own alignments;
+ *               a context that aligned a row shard is refused as everywhere else.
+ *   edges       ELBA_CC_STRING: the unordered pairs {u, v}, u != v, with an entry in S at (u, v), at (v, u) or both — each pair once.  (S
+ *               holds both triangles, but the reduction drops an image without a direction alone: a pair can have one entry, on
+ *               either side of the diagonal.  It is one edge like the others.)  ELBA_CC_OVERLAPS: the pairs of the input with passed != 0 (the reference's
+ *               Prune(!passed)) and nothing else: bad and contained reads keep their edges, so that a contained read lies in its
+ *               container's component.
+ *   component   a maximal set of reads that reach one another over edges.  Every read is in exactly one; a read without an edge is a
+ *               component of one read.  Components are numbered 0 .. n-1 by ascending smallest read: comp_of_read[v] = the number of
+ *               components whose smallest read is below the smallest read of v's.  first_read[c] = that smallest read + the id base
+ *               (the ids elba_export_string_graph / elba_export_overlaps show).
+ *   deg(v)      the edges with v at one end.
+ *   per component c   reads[c] = its reads; edges[c] = its edges; branches[c] = its reads with deg > 2; ends[c] = its reads with deg = 1;
+ *               bases[c] = the sum of its reads' lengths in 64 bits when ELBA_CC_BASES is set (the lengths of the M reads must be on the
+ *               context: ELBA_ERR_STATE otherwise), else 0.  branches = 0 and ends = 2: a path; branches = 0, ends = 0, reads >= 3: a
+ *               ring; reads = 1: a lone read.
+ * Stats: components = n; used_components = those of two or more reads; isolated = those of one; largest_reads / largest_bases = reads and
+ * bases of the component with the most reads (the smaller number on a tie); passes = kernel launches that walked the edge list or the
+ * label array — it grows with the logarithm of the read count, not with the graph's diameter.  elba_get_stat "cc_components",
+ * "cc_used_components", "cc_largest_reads", "cc_passes": the last labelling's, 0 once the graph it labelled is no longer valid.
+ * Errors: a null cfg or output, an unknown graph, an unknown flag, a non-zero reserved word: ELBA_ERR_INVALID_ARG.  Read ids beyond 32 bit
+ * (M + id base >= 2^32 - 1 or M >= 2^31 - 1): ELBA_ERR_UNSUPPORTED.  More passes than the hard cap: ELBA_ERR_INTERNAL.
+ * Cost: 16 bytes per entry of the edge list per pass over it (+ 1 byte of the record of an input pair; for S a binary search in one
+ * column per entry above the diagonal), three passes; 4 bytes per read per
+ * pass over the labels; one 32-bit compare-and-swap per edge that joins two trees; one host synchronisation per batch of four flattening
+ * passes (one batch on every graph seen so far) and one for the tables. */
+enum { ELBA_CC_STRING = 0, ELBA_CC_OVERLAPS = 1 };
+enum { ELBA_CC_BASES = 1 };                                   /* flags */
+typedef struct { int32_t graph, flags, reserved[2]; } elba_cc_cfg;
+typedef struct { int64_t nreads, n;
+                 int32_t *comp_of_read;                       /* [nreads] */
+                 int64_t *first_read, *reads, *bases, *edges, *branches, *ends; /* [n] each */ } elba_components_t;
+typedef struct { int64_t nreads, edges, components, used_components, isolated, largest_reads, largest_bases;
+                 int32_t passes, reserved; float ms_total, ms_label; } elba_cc_stats;
+int  elba_graph_components(elba_ctx *ctx, const elba_cc_cfg *cfg, elba_components_t *out, elba_cc_stats *stats);
+void elba_free_components(elba_components_t *c);
+
+/* The reference's greedy assignment of components to parts (src/ContigGeneration.cpp:126, :184-197), with its open ends closed.  The call
+ * labels cfg->graph itself (no labels persist between calls, so none can go stale after a cleaning call), then:
+ *   weight(c)   reads[c] when cfg->weight = 0, bases[c] when cfg->weight = 1 (which implies ELBA_CC_BASES and its condition).
+ *   order       the components with reads[c] >= min_reads, by weight descending, the smaller component number first on a tie.
+ *   deal        in that order each component goes to the part whose sum of weights so far is smallest, the lowest part index on a tie
+ *               (std::min_element).  part_weight[p] = the sum of part p at the end.
+ *   reads       part_of_read[v] = the part of v's component, -1 when that component has fewer than min_reads reads.
+ * Guarantee of the rule: max - min of part_weight is at most the largest weight dealt.  nreads must be the graph's read count.
+ * Errors: null cfg or arrays, nparts < 1, weight outside {0, 1}, min_reads < 0, a non-zero reserved word, an unknown graph, a wrong nreads:
+ * ELBA_ERR_INVALID_ARG; otherwise as elba_graph_components. */
+typedef struct { int32_t graph, nparts, weight /* 0 reads, 1 bases */, min_reads /* the reference: 2 */, reserved[4]; } elba_part_cfg;
+int  elba_partition_components(elba_ctx *ctx, const elba_part_cfg *cfg, int32_t *part_of_read, int64_t nreads, int64_t *part_weight /* [nparts] */);
+
 /* Tip clipping (not in the reference, whose GenerateContigs drops every read of degree > 2 with its edges: one stray read hanging off a good
  * path cuts it into three contigs and loses the branch read).  elba_clip_tips works on the S of elba_transitive_reduction, in place, between
  * that call and elba_generate_contigs*.  The rule is on degrees alone — no sequence, no suffix, no length in bases — and is stated on the
@@ -987,6 +1045,8 @@ int  elba_set_option(elba_ctx *ctx, const char *name, int64_t value);
  *                            contigs are not valid ("contig_rank_us": -1)
  *   "graph_segments", "graph_candidates", "graph_links", "graph_closures", "graph_twisted", "graph_unplaced", "graph_clamped", "graph_asymmetric"
  *                            the last elba_export_assembly_links, under the same condition (0 also before the first call on these contigs)
+ *   "cc_components", "cc_used_components", "cc_largest_reads", "cc_passes"
+ *                            the last elba_graph_components / elba_partition_components: 0 once the graph it labelled is no longer valid
  *   "text_tile_bytes", "text_scan_span"
  *                            constants of elba_set_reads_text: the bytes of the chunk one workgroup takes per trip of its two passes, and the
  *                            elements one workgroup of its scans covers (longer arrays make the scan recurse) */
