@@ -149,6 +149,24 @@ class PartCfg(C.Structure):
     _fields_ = [("graph", C.c_int32), ("nparts", C.c_int32), ("weight", C.c_int32), ("min_reads", C.c_int32), ("reserved", C.c_int32 * 4)]
 
 
+INDUCE_BASES, INDUCE_HOST = 1, 2       # elba_induce_cfg.flags
+
+
+class InduceCfg(C.Structure):
+    _fields_ = [("part", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class Induced(C.Structure):
+    _fields_ = [("reads", C.c_int64), ("pairs", C.c_int64), ("packed_bytes", C.c_int64)] + \
+               [(n, C.c_void_p) for n in ("d_old_of_new", "d_packed", "d_byte_off", "d_len", "d_rows", "d_cols", "d_vals", "d_outside_aligned", "d_outside_passed")] + \
+               [(n, C.c_void_p) for n in ("old_of_new", "packed", "byte_off", "len", "rows", "cols", "vals", "outside_aligned", "outside_passed")]
+
+
+class InduceStats(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("nreads_in", "pairs_in", "reads", "pairs", "bases", "packed_bytes", "split_pairs", "split_passed", "id_base")] + \
+               [("ms_total", C.c_float), ("ms_pairs", C.c_float), ("ms_gather", C.c_float)]
+
+
 class PlaceCfg(C.Structure):
     _fields_ = [("skip_flags", C.c_int32), ("reserved", C.c_int32 * 3)]
 
@@ -326,6 +344,7 @@ EXPORTED_SYMBOLS = [
     "elba_place_reads", "elba_free_placements",
     "elba_polish_contigs", "elba_free_polished",
     "elba_graph_components", "elba_free_components", "elba_partition_components",
+    "elba_induce_part", "elba_free_induced", "elba_set_overlaps_device", "elba_set_outside_counts", "elba_set_outside_counts_device",
 ]
 
 _lib = None
@@ -397,6 +416,11 @@ def load_library():
     L.elba_graph_components.restype = i32; L.elba_graph_components.argtypes = [vp, C.POINTER(CcCfg), C.POINTER(Components), C.POINTER(CcStats)]
     L.elba_free_components.restype = None; L.elba_free_components.argtypes = [C.POINTER(Components)]
     L.elba_partition_components.restype = i32; L.elba_partition_components.argtypes = [vp, C.POINTER(PartCfg), vp, i64, vp]
+    L.elba_induce_part.restype = i32; L.elba_induce_part.argtypes = [vp, C.POINTER(InduceCfg), vp, i64, C.POINTER(Induced), C.POINTER(InduceStats)]
+    L.elba_free_induced.restype = None; L.elba_free_induced.argtypes = [C.POINTER(Induced)]
+    L.elba_set_overlaps_device.restype = i32; L.elba_set_overlaps_device.argtypes = [vp, i64, vp, vp, vp, i64]
+    L.elba_set_outside_counts.restype = i32; L.elba_set_outside_counts.argtypes = [vp, i64, vp, vp]
+    L.elba_set_outside_counts_device.restype = i32; L.elba_set_outside_counts_device.argtypes = [vp, i64, vp, vp]
     L.elba_read_pileup.restype = i32; L.elba_read_pileup.argtypes = [vp, C.POINTER(PileupCfg), C.POINTER(PileupStats)]
     L.elba_export_pileup.restype = i32; L.elba_export_pileup.argtypes = [vp, C.POINTER(Pileup)]
     L.elba_free_pileup.restype = None; L.elba_free_pileup.argtypes = [C.POINTER(Pileup)]
@@ -648,6 +672,28 @@ class Engine:
             raise ValueError("set_overlaps: rows, cols, vals differ in length")
         self._check(self.L.elba_set_overlaps(self.h, int(nreads), rows.ctypes.data, cols.ctypes.data, vals.ctypes.data, len(rows)))
 
+    def set_overlaps_device(self, nreads, d_rows, d_cols, d_vals, n):
+        """set_overlaps with the three arrays in HBM (device addresses; copied device to device, checked by a kernel)."""
+        self._check(self.L.elba_set_overlaps_device(self.h, int(nreads), d_rows, d_cols, d_vals, int(n)))
+
+    def set_outside_counts(self, aligned, passed, nreads=None):
+        """Attach to the loaded edge list, per read, the pairs it does not hold (u32 arrays, passed <= aligned; induce_part's outside
+        counts): the next transitive_reduction counts them in its bad-read rule.  (None, None, nreads) detaches them."""
+        if aligned is None or passed is None:
+            self._check(self.L.elba_set_outside_counts(self.h, int(nreads or 0), None if aligned is None else np.ascontiguousarray(aligned, dtype=np.uint32).ctypes.data,
+                                                       None if passed is None else np.ascontiguousarray(passed, dtype=np.uint32).ctypes.data))
+            return
+        aligned = np.ascontiguousarray(aligned, dtype=np.uint32); passed = np.ascontiguousarray(passed, dtype=np.uint32)
+        if len(aligned) != len(passed):
+            raise ValueError("set_outside_counts: aligned and passed differ in length")
+        pad = np.zeros(1, dtype=np.uint32)       # (an array of 0 elements still needs an address: null means detach)
+        a, p = (aligned, passed) if len(aligned) else (pad, pad)
+        self._check(self.L.elba_set_outside_counts(self.h, len(aligned) if nreads is None else int(nreads), a.ctypes.data, p.ctypes.data))
+
+    def set_outside_counts_device(self, nreads, d_aligned, d_passed):
+        """set_outside_counts with the two arrays in HBM (device addresses of u32[nreads]; None, None detaches)."""
+        self._check(self.L.elba_set_outside_counts_device(self.h, int(nreads), d_aligned, d_passed))
+
     def transitive_reduction(self, bad_read_cutoff=0.65, fuzz=1000):
         """find_bad_reads / find_contained_reads + prunes (src/main.cpp:305-311) and TransitiveReduction (src/TransitiveReduction.cpp:3-90)."""
         st = StringStats()
@@ -849,6 +895,43 @@ class Engine:
         pw = np.zeros(max(int(nparts), 1), dtype=np.int64)
         self._check(self.L.elba_partition_components(self.h, C.byref(cfg), part.ctypes.data, int(nreads), pw.ctypes.data))
         return part[:int(nreads)], pw[:max(int(nparts), 0)]
+
+    def induce_part(self, part_of_read, part, bases=True, host=True, flags=None, reserved=(0, 0)):
+        """The induced sub-problem of one part (elba_induce_part; include/elba_amd.h states the rule): the reads v of the graph's input with
+        part_of_read[v] == part, renumbered in order, the pairs between them, and per new read the pairs that leave the part.  Returns
+        (dict, stats): reads, pairs, packed_bytes, the device addresses d_* (valid until the next induce_part, release_workspace or
+        close) and, with host=True, numpy copies old_of_new, rows, cols, vals, outside_aligned, outside_passed and — with bases=True —
+        packed (with its 16 guard bytes), byte_off, len.  Engine.load_part(dict) loads it into an engine."""
+        pr = np.ascontiguousarray(part_of_read, dtype=np.int32)
+        fl = ((INDUCE_BASES if bases else 0) | (INDUCE_HOST if host else 0)) if flags is None else int(flags)
+        cfg = InduceCfg(int(part), fl, (C.c_int32 * 2)(*[int(x) for x in reserved]))
+        o, st = Induced(), InduceStats()
+        pad = np.zeros(1, dtype=np.int32)
+        self._check(self.L.elba_induce_part(self.h, C.byref(cfg), pr.ctypes.data if len(pr) else pad.ctypes.data, len(pr), C.byref(o), C.byref(st)))
+        try:
+            R, P, pb = int(o.reads), int(o.pairs), int(o.packed_bytes)
+            ind = dict(reads=R, pairs=P, packed_bytes=pb)
+            for name in ("d_old_of_new", "d_packed", "d_byte_off", "d_len", "d_rows", "d_cols", "d_vals", "d_outside_aligned", "d_outside_passed"):
+                ind[name] = getattr(o, name)
+            if o.old_of_new:
+                ind.update(old_of_new=_copy(o.old_of_new, R, np.int64), rows=_copy(o.rows, P, np.int64), cols=_copy(o.cols, P, np.int64), vals=_copy(o.vals, P, OVERLAP_DTYPE),
+                           outside_aligned=_copy(o.outside_aligned, R, np.uint32), outside_passed=_copy(o.outside_passed, R, np.uint32))
+                if o.packed:
+                    ind.update(packed=_copy(o.packed, pb + 16, np.uint8), byte_off=_copy(o.byte_off, R, np.uint64), len=_copy(o.len, R, np.uint32))
+        finally:
+            self.L.elba_free_induced(C.byref(o))
+        return ind, _stats(st)
+
+    def load_part(self, ind, outside=True):
+        """Load the host copies of an induce_part result into THIS engine: set_reads (when the part carries bases) + set_overlaps +
+        set_outside_counts.  outside=False leaves the counts out (what a driver without them computes: no guarantee)."""
+        if "rows" not in ind:
+            raise ValueError("load_part: the part has no host copies (induce_part(host=True))")
+        if "packed" in ind:
+            self.set_reads(ind["packed"], ind["byte_off"], ind["len"])
+        self.set_overlaps(ind["reads"], ind["rows"], ind["cols"], ind["vals"])
+        if outside:
+            self.set_outside_counts(ind["outside_aligned"], ind["outside_passed"], nreads=ind["reads"])
 
     def place_reads(self, skip_flags=1, reserved=(0, 0, 0)):
         """Every read on its contig and the depth of every contig base (include/elba_amd.h states the rule): chain reads where the contig

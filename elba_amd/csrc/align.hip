@@ -477,6 +477,7 @@ void stage_align_seeds(Ctx &c, int mat, int mis, int gap, int dropoff)
     hipStream_t s = c.stream;
     const int64_t M = c.M;
     accepted(c.v, EV_ALIGN_SEEDS);
+    c.tr_outside = false;                          // (the loaded edge list is no longer the graph's input: its outside counts go with it)
     AlnParams p{};
     if (shard) { p.packed = c.aln_all_packed.as<uint8_t>(); p.byte_off = c.aln_all_off.as<uint64_t>(); p.len = c.aln_all_len.as<uint32_t>(); }
     else { p.packed = c.d_packed; p.byte_off = c.d_byte_off; p.len = c.d_len; }

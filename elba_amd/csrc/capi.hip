@@ -340,6 +340,21 @@ int elba_set_overlaps(elba_ctx *ctx, int64_t nreads, const int64_t *rows, const 
     return guarded(ctx, [&](Ctx &c) { stage_set_overlaps(c, nreads, rows, cols, vals, n); });
 }
 
+int elba_set_overlaps_device(elba_ctx *ctx, int64_t nreads, const void *d_rows, const void *d_cols, const void *d_vals, int64_t n)
+{
+    return guarded(ctx, [&](Ctx &c) { stage_set_overlaps_device(c, nreads, d_rows, d_cols, d_vals, n); });
+}
+
+int elba_set_outside_counts(elba_ctx *ctx, int64_t nreads, const uint32_t *aligned, const uint32_t *passed)
+{
+    return guarded(ctx, [&](Ctx &c) { stage_set_outside_counts(c, nreads, aligned, passed, false); });
+}
+
+int elba_set_outside_counts_device(elba_ctx *ctx, int64_t nreads, const void *d_aligned, const void *d_passed)
+{
+    return guarded(ctx, [&](Ctx &c) { stage_set_outside_counts(c, nreads, d_aligned, d_passed, true); });
+}
+
 int elba_transitive_reduction(elba_ctx *ctx, double bad_read_cutoff, int fuzz, elba_string_stats *stats)
 {
     return guarded(ctx, [&](Ctx &c) {
@@ -527,6 +542,24 @@ void elba_free_components(elba_components_t *p)
 int elba_partition_components(elba_ctx *ctx, const elba_part_cfg *cfg, int32_t *part_of_read, int64_t nreads, int64_t *part_weight)
 {
     return guarded(ctx, [&](Ctx &c) { stage_partition_components(c, cfg, part_of_read, nreads, part_weight); });
+}
+
+int elba_induce_part(elba_ctx *ctx, const elba_induce_cfg *cfg, const int32_t *part_of_read, int64_t nreads, elba_induced_t *out, elba_induce_stats *stats)
+{
+    if (out) memset(out, 0, sizeof(*out));                        // (before anything can fail: what is freed below is this call's)
+    const int rc = guarded(ctx, [&](Ctx &c) {
+        stage_induce_part(c, cfg, part_of_read, nreads, out);
+        if (stats) *stats = c.in.stats;
+    });
+    if (rc != ELBA_OK && ctx && out) elba_free_induced(out);      // (a copy that failed behind the allocations)
+    return rc;
+}
+
+void elba_free_induced(elba_induced_t *o)
+{
+    if (!o) return;
+    free(o->old_of_new); free(o->packed); free(o->byte_off); free(o->len); free(o->rows); free(o->cols); free(o->vals); free(o->outside_aligned); free(o->outside_passed);
+    memset(o, 0, sizeof(*o));
 }
 
 void elba_free_polished(elba_polished_t *p)
@@ -828,7 +861,7 @@ int elba_release_workspace(elba_ctx *ctx)
         c.ws_a.release(); c.ws_b.release(); c.ws_c.release(); c.ws_d.release(); c.ws_e.release(); c.ws_f.release(); c.ws_g.release(); c.ws_h.release(); c.ws_sort.release();
         c.csr_words.release(); c.kid_of_entry.release();
         // the late stages: what each keeps is its release_scratch()'s decision (common.hpp, the stage structs of Ctx)
-        c.cg.release_scratch(); c.gl.release_scratch(); c.pu.release_scratch(); c.pl.release_scratch(); c.po.release_scratch(); c.cc.release_scratch(); c.tm.release_scratch();
+        c.cg.release_scratch(); c.gl.release_scratch(); c.pu.release_scratch(); c.pl.release_scratch(); c.po.release_scratch(); c.cc.release_scratch(); c.in.release_scratch(); c.tm.release_scratch();
         c.sg.release();      // the cleaning calls' shared scratch and the spare buffer of S (S itself stays)
         c.tp.release_scratch(); c.bb.release_scratch(); c.wk.release_scratch(); c.br.release_scratch(); c.sr.release_scratch();
         if (has(c.v, P_COUNTS)) { c.pre_ready = false; c.pre_consumed = true; }    // (the CSR sort keys / column ids of the entries are gone: create_kmer_matrix rebuilds them from the column pointers)
@@ -911,6 +944,9 @@ int elba_get_stat(elba_ctx *ctx, const char *name, int64_t *value)
                 *value = stage_stat(table, c.cc.stats, valid, name + 3, name);
             }
         }
+        else if (!strcmp(name, "induce_reads")) *value = c.in.stats.reads;      // the last elba_induce_part that succeeded
+        else if (!strcmp(name, "induce_pairs")) *value = c.in.stats.pairs;
+        else if (!strcmp(name, "induce_split_pairs")) *value = c.in.stats.split_pairs;
         else if (!strcmp(name, "contig_rank_us")) *value = has(c.v, P_S, P_CONTIGS) ? (int64_t)(c.cg.stats.ms_rank * 1000.0f) : -1;
         else if (!strcmp(name, "resident_bytes_A")) {
             int64_t b = 0;

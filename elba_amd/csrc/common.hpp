@@ -321,6 +321,8 @@ struct Ctx {
     // string graph (tr.hip)
     int64_t tr_in_M = 0, tr_in_n = 0;
     DevBuf tr_in_rows, tr_in_cols, tr_in_vals;
+    bool tr_outside = false;               // outside counts are attached to the loaded edge list (elba_set_outside_counts): tr_oa / tr_op, u32[tr_in_M] each
+    DevBuf tr_oa, tr_op;
     int64_t tr_M = 0, tr_nnz = 0, tr_id_base = 0;
     DevBuf tr_deg, tr_pas, tr_flags, tr_k0, tr_v0, tr_k1, tr_v1, tr_ptr, tr_sym, tr_src, tr_mark, tr_ctr, tr_sel, tr_out_rows, tr_out_cols, tr_out_vals;
     int64_t tr_sym_M = 0, tr_sym_n = 0;     // what tr_ptr / tr_sym describe since the last reduction that succeeded: reads, symmetrised entries (0: tr_ptr was not written)
@@ -435,6 +437,21 @@ struct Ctx {
         void release_scratch() { for (DevBuf *b : {&par, &deg, &ptr, &flag, &rank, &comp, &st, &tab, &pcomp, &pread}) b->release(); }
     } cc;
 
+    // the induced sub-problem of one part (induce.hip): results — old_of_new, the part's reads in DnaBuffer layout (packed / off / len), its
+    // pairs (rows / cols / vals) and the outside counters (oa / op) — are what elba_induced_t's device views point at; they and the scratch
+    // (the selection and its scans, new_of_old, source base offsets, keep flags and their scan, part_of_read, the counters) go with
+    // elba_release_workspace: the views are valid until then
+    struct InduceStage {
+        DevBuf old_of_new, packed, off, len, rows, cols, vals, oa, op;
+        DevBuf part, sel, bytes, first, boff, new_of_old, srcb, keep, pos, ctr;      // scratch
+        EventTimer t_total, t_pairs, t_scatter, t_gather;      // (the pairs' time is t_pairs + t_scatter: the first synchronisation lies between them)
+        elba_induce_stats stats{};
+        void release_scratch()
+        {
+            for (DevBuf *b : {&old_of_new, &packed, &off, &len, &rows, &cols, &vals, &oa, &op, &part, &sel, &bytes, &first, &boff, &new_of_old, &srcb, &keep, &pos, &ctr}) b->release();
+        }
+    } in;
+
     // workspaces
     DevBuf ws_scan, ws_sort, ws_a, ws_b, ws_c, ws_d, ws_e, ws_f;
     DevBuf ws_cursor;       // the gather-slot cursor of the k-mer stage's emit kernels (kmer_msd.hip)
@@ -485,6 +502,7 @@ inline void reads_replaced(Ctx &c, Event ev)
     done(c.v, ev);
     if (c.A_has_kmers) done(c.v, EV_MATRIX_OF_OLD_READS);
     c.tx_index = false;      // (elba_set_reads_text sets it again behind this call)
+    c.tr_outside = false;    // (the loaded edge list went with the old reads, and its outside counts with it)
 }
 
 // The pairs the string graph is built from — what elba_transitive_reduction, elba_read_pileup and elba_prune_reads read: a loaded edge
@@ -565,6 +583,8 @@ bool stage_seed_matrix_recv(Ctx &c, void *d_recv, int64_t slot, int64_t *slot_ne
 void stage_align_seeds(Ctx &c, int mat, int mis, int gap, int dropoff);   // align.hip
 void stage_dist_set_all_reads(Ctx &c, const void *d_packed, int64_t packed_bytes, const void *d_byte_off, const void *d_len, int64_t nreads_total);   // align.hip
 void stage_set_overlaps(Ctx &c, int64_t nreads, const int64_t *rows, const int64_t *cols, const elba_overlap_t *vals, int64_t n);   // tr.hip
+void stage_set_overlaps_device(Ctx &c, int64_t nreads, const void *d_rows, const void *d_cols, const void *d_vals, int64_t n);
+void stage_set_outside_counts(Ctx &c, int64_t nreads, const void *aligned, const void *passed, bool on_device);
 void stage_transitive_reduction(Ctx &c, double bad_read_cutoff, int fuzz);   // tr.hip
 void stage_generate_contigs(Ctx &c, int flags);                                          // contig.hip
 void stage_generate_contigs_ex(Ctx &c, const elba_contig_cfg *cfg);                      // contig.hip
@@ -573,6 +593,7 @@ void stage_place_reads(Ctx &c, const elba_place_cfg *cfg, elba_placements_t *out
 void stage_polish_contigs(Ctx &c, const elba_polish_cfg *cfg, elba_polished_t *out);       // polish.hip (out's arrays: malloc)
 void stage_graph_components(Ctx &c, const elba_cc_cfg *cfg, elba_components_t *out);      // components.hip (out's arrays: malloc)
 void stage_partition_components(Ctx &c, const elba_part_cfg *cfg, int32_t *part_of_read, int64_t nreads, int64_t *part_weight);
+void stage_induce_part(Ctx &c, const elba_induce_cfg *cfg, const int32_t *part_of_read, int64_t nreads, elba_induced_t *out);      // induce.hip (out's host arrays: malloc)
 void stage_read_pileup(Ctx &c, const elba_pileup_cfg *cfg);                   // pileup.hip
 void stage_prune_reads(Ctx &c, int mask, int64_t *kept);
 void stage_trim_reads(Ctx &c, const elba_trim_cfg *cfg);                      // trim.hip

@@ -392,6 +392,7 @@ void stage_prune_reads(Ctx &c, int mask, int64_t *kept)
     // the kept pairs become the loaded edge list (elba_set_overlaps' buffers); the context's own alignments stay as they are
     c.tr_in_rows.swap(c.pu.rows); c.tr_in_cols.swap(c.pu.cols); c.tr_in_vals.swap(c.pu.vals);
     c.tr_in_M = in.M; c.tr_in_n = total;
+    c.tr_outside = false;                                       // (outside counts belonged to the list the kept pairs replace)
     done(c.v, EV_PRUNE_READS);
     if (kept) *kept = total;
 }

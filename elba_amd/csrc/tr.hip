@@ -221,6 +221,30 @@ __global__ void k_tr_scatter(const uint64_t *keys, const uint64_t *kv, const uin
     orow[at] = (int64_t)c; ocol[at] = (int64_t)r; oval[at] = o;
 }
 
+// elba_set_overlaps_device's two checks of the host loop, on the device: bad = the smallest (a << 1 | kind) over the offending pairs a, kind 0
+// = the range (the host loop tests it first), 1 = the order; all ones: none
+__global__ void k_tr_check_pairs(const int64_t *rows, const int64_t *cols, int64_t n, int64_t nreads, unsigned long long *bad)
+{
+    const int64_t a = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (a >= n) return;
+    const int64_t r = rows[a], c = cols[a];
+    if (!(r >= 0 && r < c && c < nreads)) { atomicMin(bad, (unsigned long long)a << 1); return; }
+    if (a) {
+        const int64_t pr = rows[a - 1], pc = cols[a - 1];
+        if (!(pr < r || (pr == r && pc < c))) atomicMin(bad, (unsigned long long)a << 1 | 1ull);
+    }
+}
+
+// elba_set_outside_counts_device: the smallest read v without passed[v] <= aligned[v] < 2^31 (all ones: none)
+__global__ void k_tr_check_counts(const uint32_t *aligned, const uint32_t *passed, int64_t M, unsigned long long *bad)
+{
+    const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= M) return;
+    if (!(passed[v] <= aligned[v] && aligned[v] < 0x80000000u)) atomicMin(bad, (unsigned long long)v);
+}
+
+constexpr const char *SET_OVERLAPS_RANGE = "set_overlaps: need 0 <= row < col < nreads", *SET_OVERLAPS_ORDER = "set_overlaps: pairs must be strictly ascending in (row, col)";
+
 }  // namespace
 
 void stage_set_overlaps(Ctx &c, int64_t nreads, const int64_t *rows, const int64_t *cols, const elba_overlap_t *vals, int64_t n)
@@ -229,11 +253,12 @@ void stage_set_overlaps(Ctx &c, int64_t nreads, const int64_t *rows, const int64
     ELBA_REQUIRE(nreads >= 0 && n >= 0 && (n == 0 || (rows && cols && vals)), ELBA_ERR_INVALID_ARG, "set_overlaps: null array");
     ELBA_REQUIRE(nreads < 0x7fffffff && n < 0x7fffffff, ELBA_ERR_UNSUPPORTED, "set_overlaps: more than 2^31 reads or pairs");
     for (int64_t a = 0; a < n; ++a) {
-        ELBA_REQUIRE(rows[a] >= 0 && rows[a] < cols[a] && cols[a] < nreads, ELBA_ERR_INVALID_ARG, "set_overlaps: need 0 <= row < col < nreads");
-        if (a) ELBA_REQUIRE(rows[a - 1] < rows[a] || (rows[a - 1] == rows[a] && cols[a - 1] < cols[a]), ELBA_ERR_INVALID_ARG, "set_overlaps: pairs must be strictly ascending in (row, col)");
+        ELBA_REQUIRE(rows[a] >= 0 && rows[a] < cols[a] && cols[a] < nreads, ELBA_ERR_INVALID_ARG, SET_OVERLAPS_RANGE);
+        if (a) ELBA_REQUIRE(rows[a - 1] < rows[a] || (rows[a - 1] == rows[a] && cols[a - 1] < cols[a]), ELBA_ERR_INVALID_ARG, SET_OVERLAPS_ORDER);
     }
     hipStream_t s = c.stream;
     accepted(c.v, EV_SET_OVERLAPS);
+    c.tr_outside = false;                                       // (the outside counts belonged to the list that goes)
     c.tr_in_rows.reserve((size_t)(n + 1) * 8); c.tr_in_cols.reserve((size_t)(n + 1) * 8); c.tr_in_vals.reserve((size_t)(n + 1) * sizeof(elba_overlap_t));
     if (n) {
         ELBA_HIP(hipMemcpyAsync(c.tr_in_rows.p, rows, (size_t)n * 8, hipMemcpyHostToDevice, s));
@@ -245,11 +270,79 @@ void stage_set_overlaps(Ctx &c, int64_t nreads, const int64_t *rows, const int64
     done(c.v, EV_SET_OVERLAPS);
 }
 
+// elba_set_overlaps with the three arrays in HBM: the same event, the same checks (by k_tr_check_pairs) with the same texts, before `accepted`
+void stage_set_overlaps_device(Ctx &c, int64_t nreads, const void *d_rows, const void *d_cols, const void *d_vals, int64_t n)
+{
+    enter(c.v, EV_SET_OVERLAPS);
+    ELBA_REQUIRE(nreads >= 0 && n >= 0 && (n == 0 || (d_rows && d_cols && d_vals)), ELBA_ERR_INVALID_ARG, "set_overlaps: null array");
+    ELBA_REQUIRE(nreads < 0x7fffffff && n < 0x7fffffff, ELBA_ERR_UNSUPPORTED, "set_overlaps: more than 2^31 reads or pairs");
+    hipStream_t s = c.stream;
+    if (n) {
+        c.tr_ctr.reserve(64);
+        unsigned long long *bad = c.tr_ctr.as<unsigned long long>(), h = 0;
+        ELBA_HIP(hipMemsetAsync(bad, 0xFF, 8, s));
+        hipLaunchKernelGGL(k_tr_check_pairs, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, static_cast<const int64_t *>(d_rows), static_cast<const int64_t *>(d_cols), n, nreads, bad);
+        ELBA_HIP(hipGetLastError());
+        ELBA_HIP(hipMemcpyAsync(&h, bad, 8, hipMemcpyDeviceToHost, s));
+        ELBA_HIP(hipStreamSynchronize(s));
+        ELBA_REQUIRE(h == ~0ull, ELBA_ERR_INVALID_ARG, (h & 1) ? SET_OVERLAPS_ORDER : SET_OVERLAPS_RANGE);
+    }
+    accepted(c.v, EV_SET_OVERLAPS);
+    c.tr_outside = false;
+    // (the source may be this context's own tr_in_* — the list loaded again from itself —: reserve() keeps a buffer that is large enough, and a
+    // copy onto itself is no copy)
+    c.tr_in_rows.reserve((size_t)(n + 1) * 8); c.tr_in_cols.reserve((size_t)(n + 1) * 8); c.tr_in_vals.reserve((size_t)(n + 1) * sizeof(elba_overlap_t));
+    if (n) {
+        if (d_rows != c.tr_in_rows.p) ELBA_HIP(hipMemcpyAsync(c.tr_in_rows.p, d_rows, (size_t)n * 8, hipMemcpyDeviceToDevice, s));
+        if (d_cols != c.tr_in_cols.p) ELBA_HIP(hipMemcpyAsync(c.tr_in_cols.p, d_cols, (size_t)n * 8, hipMemcpyDeviceToDevice, s));
+        if (d_vals != c.tr_in_vals.p) ELBA_HIP(hipMemcpyAsync(c.tr_in_vals.p, d_vals, (size_t)n * sizeof(elba_overlap_t), hipMemcpyDeviceToDevice, s));
+    }
+    ELBA_HIP(hipStreamSynchronize(s));
+    c.tr_in_M = nreads; c.tr_in_n = n;
+    done(c.v, EV_SET_OVERLAPS);
+}
+
+// Attaches (or, with both arrays null, detaches) the outside counts of the loaded edge list.  No event of state.hpp: the counts are no
+// product — they ride on P_EDGES, and every call that drops or replaces it clears c.tr_outside.
+void stage_set_outside_counts(Ctx &c, int64_t nreads, const void *aligned, const void *passed, bool on_device)
+{
+    ELBA_REQUIRE(has(c.v, P_EDGES), ELBA_ERR_STATE, "set_outside_counts: no loaded edge list (call elba_set_overlaps or elba_prune_reads)");
+    ELBA_REQUIRE(nreads == c.tr_in_M, ELBA_ERR_INVALID_ARG, "set_outside_counts: need one count per read of the loaded edge list");
+    ELBA_REQUIRE((aligned == nullptr) == (passed == nullptr), ELBA_ERR_INVALID_ARG, "set_outside_counts: one array is null");
+    if (!aligned) { c.tr_outside = false; return; }
+    const int64_t M = nreads;
+    hipStream_t s = c.stream;
+    const char *text = "set_outside_counts: need passed[v] <= aligned[v] < 2^31";
+    if (!on_device) {
+        const uint32_t *a = static_cast<const uint32_t *>(aligned), *p = static_cast<const uint32_t *>(passed);
+        for (int64_t v = 0; v < M; ++v) ELBA_REQUIRE(p[v] <= a[v] && a[v] < 0x80000000u, ELBA_ERR_INVALID_ARG, text);
+    } else if (M) {
+        c.tr_ctr.reserve(64);
+        unsigned long long *bad = c.tr_ctr.as<unsigned long long>(), h = 0;
+        ELBA_HIP(hipMemsetAsync(bad, 0xFF, 8, s));
+        hipLaunchKernelGGL(k_tr_check_counts, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, static_cast<const uint32_t *>(aligned), static_cast<const uint32_t *>(passed), M, bad);
+        ELBA_HIP(hipGetLastError());
+        ELBA_HIP(hipMemcpyAsync(&h, bad, 8, hipMemcpyDeviceToHost, s));
+        ELBA_HIP(hipStreamSynchronize(s));
+        ELBA_REQUIRE(h == ~0ull, ELBA_ERR_INVALID_ARG, text);
+    }
+    c.tr_outside = false;                                       // (until both copies are in)
+    c.tr_oa.reserve((size_t)(M + 1) * 4); c.tr_op.reserve((size_t)(M + 1) * 4);
+    if (M) {
+        const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+        ELBA_HIP(hipMemcpyAsync(c.tr_oa.p, aligned, (size_t)M * 4, kind, s));
+        ELBA_HIP(hipMemcpyAsync(c.tr_op.p, passed, (size_t)M * 4, kind, s));
+    }
+    ELBA_HIP(hipStreamSynchronize(s));
+    c.tr_outside = true;
+}
+
 void stage_transitive_reduction(Ctx &c, double bad_read_cutoff, int fuzz)
 {
     enter(c.v, EV_TRANSITIVE_REDUCTION);                        // (a new S invalidates the contigs of the old one, whatever this call ends in)
     const GraphInput in = graph_input(c, "transitive_reduction");
     const int64_t M = in.M, n = in.n;
+    const bool outside = has(c.v, P_EDGES) && c.tr_outside && c.tr_in_M == M;      // (outside counts ride on the loaded list only: elba_set_outside_counts)
     c.tr_id_base = in.id_base;
     TrParams p{};
     p.rows = in.rows; p.cols = in.cols; p.vals = in.vals;
@@ -270,6 +363,10 @@ void stage_transitive_reduction(Ctx &c, double bad_read_cutoff, int fuzz)
     c.t_total.start(s);
     ELBA_HIP(hipMemsetAsync(c.tr_deg.p, 0, (size_t)(M + 1) * 4, s));
     ELBA_HIP(hipMemsetAsync(c.tr_pas.p, 0, (size_t)(M + 1) * 4, s));
+    if (outside && M > 0) {                                     // the bad-read rule counts the pairs the list does not hold: k_tr_degrees adds to them
+        ELBA_HIP(hipMemcpyAsync(c.tr_deg.p, c.tr_oa.p, (size_t)M * 4, hipMemcpyDeviceToDevice, s));
+        ELBA_HIP(hipMemcpyAsync(c.tr_pas.p, c.tr_op.p, (size_t)M * 4, hipMemcpyDeviceToDevice, s));
+    }
     ELBA_HIP(hipMemsetAsync(c.tr_flags.p, 0, (size_t)M + 4, s));
     ELBA_HIP(hipMemsetAsync(c.tr_ctr.p, 0, 64, s));
     ELBA_HIP(hipMemsetAsync(c.tr_mark.p, 0, (size_t)(n + 1) * 4, s));

@@ -12,7 +12,7 @@
 //   -- the one host synchronisation: the piece count n and packed_bytes (they size the output) and the other counters --
 //   k_trim_pieces   the same walk: (src_read, beg, end), byte_off, len of every piece, and srcb[p] = the piece's first base counted from
 //                   the start of the source buffer (4 x the read's byte offset + beg)
-//   k_trim_repack   flat over the OUTPUT: a lane owns one aligned 8-byte word.  Pieces are byte-aligned and lie back to back (byte_off is
+//   k_trim_repack   (repack.hpp, shared with induce.hip) flat over the OUTPUT: a lane owns one aligned 8-byte word.  Pieces are byte-aligned and lie back to back (byte_off is
 //                   the running sum of (len + 3) / 4), so every byte of a word below packed_bytes belongs to exactly one piece and the lane
 //                   writes its word whole, in one store — never a neighbour's byte.  A word inside one piece (all but two words of a long
 //                   piece) takes two aligned 8-byte source loads; a word with piece boundaries in it walks its pieces (at most 8: a piece
@@ -30,6 +30,7 @@
 // Bytes moved (algorithmic): bases_out / 4 read, bases_out / 4 written, 16 B per piece (byte_off + srcb; len where a piece ends), the
 // segment walk twice (12 B per segment of mode 1, 8 B per read of mode 0) and 28 B per piece written by k_trim_pieces.
 #include "common.hpp"
+#include "repack.hpp"      // k_trim_repack, trim_find, TRIM_THREADS: shared with induce.hip
 
 namespace elba {
 
@@ -117,57 +118,6 @@ __global__ void k_trim_pieces(TrimParams p, const uint32_t *first, const int64_t
         byte_off[at] = bo; plen[at] = (uint32_t)(e - b); srcb[at] = sbase + (uint64_t)b;
         bo += (uint64_t)(e - b + 3) >> 2; ++at;
     });
-}
-
-constexpr int TRIM_THREADS = 256;
-
-// last piece p in [lo, hi] with byte_off[p] <= x (byte_off[lo] <= x)
-__device__ __forceinline__ int64_t trim_find(const uint64_t *byte_off, int64_t lo, int64_t hi, uint64_t x)
-{
-    while (lo < hi) {
-        const int64_t mid = (lo + hi + 1) >> 1;
-        if (byte_off[mid] <= x) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
-__global__ __launch_bounds__(TRIM_THREADS) void k_trim_repack(const uint8_t *__restrict__ src, const uint64_t *__restrict__ byte_off, const uint32_t *__restrict__ plen,
-                                                              const uint64_t *__restrict__ srcb, int64_t n, uint64_t packed_bytes, uint64_t *__restrict__ out)
-{
-    __shared__ int64_t span[2];
-    const uint64_t nwords = (packed_bytes + 7) >> 3;
-    const uint64_t wb = (uint64_t)blockIdx.x * TRIM_THREADS;                 // the workgroup's first word (< nwords: the grid is ceil(nwords / 256))
-    if (threadIdx.x == 0) span[0] = trim_find(byte_off, 0, n - 1, wb << 3);
-    if (threadIdx.x == 64) {
-        uint64_t last = ((wb + TRIM_THREADS) << 3) - 1;
-        if (last >= packed_bytes) last = packed_bytes - 1;
-        span[1] = trim_find(byte_off, 0, n - 1, last);
-    }
-    __syncthreads();
-    const uint64_t w = wb + threadIdx.x;
-    if (w >= nwords) return;
-    const uint64_t o0 = w << 3;                                              // first output byte of the word (< packed_bytes)
-    int64_t p = trim_find(byte_off, span[0], span[1], o0);
-    uint64_t W = 0;                                                          // the word, big-endian: output byte 0 in bits 63..56
-    uint64_t pbeg = byte_off[p];
-    for (;;) {
-        const uint64_t pend = p + 1 < n ? byte_off[p + 1] : packed_bytes;    // the piece's bytes are [pbeg, pend)
-        const uint32_t lo = pbeg > o0 ? (uint32_t)(pbeg - o0) : 0u;          // bytes [lo, hi) of the word are this piece's
-        const bool ends = pend <= o0 + 8;
-        const uint32_t hi = ends ? (uint32_t)(pend - o0) : 8u;
-        const uint64_t sb = srcb[p];
-        const uint64_t s = (sb >> 2) + (o0 + lo - pbeg);                     // source byte holding the first base of output byte o0 + lo
-        const uint64_t *a = reinterpret_cast<const uint64_t *>(src + (s & ~7ull));
-        const uint64_t x = __builtin_bswap64(a[0]), y = __builtin_bswap64(a[1]);
-        const uint32_t t = (uint32_t)(s & 7) * 8 + (uint32_t)(sb & 3) * 2;  // 0 .. 62
-        const uint64_t v = t ? (x << t) | (y >> (64 - t)) : x;
-        uint32_t cut = 64 - 8 * hi;                                          // bits below `cut` are not this piece's
-        if (ends) cut += 2 * (4 * (uint32_t)(pend - pbeg) - plen[p]);        // ... nor the unused low bits of its last byte
-        W |= (v >> (8 * lo)) & (~0ull >> (8 * lo)) & (~0ull << cut);
-        if (pend >= o0 + 8 || pend >= packed_bytes) break;                   // the word is full (a piece that ends with it included), or the buffer ends
-        ++p; pbeg = pend;
-    }
-    out[w] = __builtin_bswap64(W);
 }
 
 }  // namespace

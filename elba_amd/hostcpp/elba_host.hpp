@@ -845,6 +845,57 @@ inline Partition partition_components(StringGraph &S, int nparts, int graph = EL
     return p;
 }
 
+// induce_part(engine, part_of_read, part) — elba_induce_part (the rule and the guarantee are stated in include/elba_amd.h): the reference's
+// GetInducedReadSequences + ImposeMyReadDistribution for one part.  The reads v of the graph's input with part_of_read[v] == part,
+// renumbered in order, as a DnaBuffer; the pairs between them; and per new read the pairs that leave the part, which load_part hands to
+// the engine that assembles the part so that its bad reads are the whole run's.  An export: nothing on the engine changes.
+struct InducedPart {
+    std::vector<int64_t> old_of_new;                                          // new read -> read of the whole input, ascending
+    DnaBuffer reads;                                                          // (empty without bases)
+    bool has_reads = false;
+    std::vector<int64_t> rows, cols;
+    std::vector<elba_overlap_t> vals;
+    std::vector<uint32_t> outside_aligned, outside_passed;                    // per new read
+    elba_induce_stats stats{};
+    int64_t numreads() const { return (int64_t)old_of_new.size(); }
+};
+
+inline InducedPart induce_part(detail::Engine &engine, const std::vector<int32_t> &part_of_read, int part, bool bases = true)
+{
+    elba_induce_cfg cfg{};
+    cfg.part = part; cfg.flags = ELBA_INDUCE_HOST | (bases ? ELBA_INDUCE_BASES : 0);
+    const int32_t none = 0;
+    elba_induced_t o;
+    InducedPart p;
+    engine.check(elba_induce_part(engine.ctx, &cfg, part_of_read.empty() ? &none : part_of_read.data(), (int64_t)part_of_read.size(), &o, &p.stats));
+    try {
+        p.old_of_new.assign(o.old_of_new, o.old_of_new + o.reads);
+        p.rows.assign(o.rows, o.rows + o.pairs); p.cols.assign(o.cols, o.cols + o.pairs); p.vals.assign(o.vals, o.vals + o.pairs);
+        p.outside_aligned.assign(o.outside_aligned, o.outside_aligned + o.reads); p.outside_passed.assign(o.outside_passed, o.outside_passed + o.reads);
+        if (bases) {
+            p.reads = DnaBuffer::from_packed(std::vector<uint8_t>(o.packed, o.packed + o.packed_bytes + 16), std::vector<uint64_t>(o.byte_off, o.byte_off + o.reads),
+                                             std::vector<uint32_t>(o.len, o.len + o.reads));
+            p.has_reads = true;
+        }
+    } catch (...) {
+        elba_free_induced(&o);
+        throw;
+    }
+    elba_free_induced(&o);
+    return p;
+}
+
+// load_part(engine, p) — the part becomes the input of `engine`: elba_set_reads (when the part carries bases), elba_set_overlaps and
+// elba_set_outside_counts.  outside = false leaves the counts out: what a driver without them computes (no guarantee).
+inline void load_part(detail::Engine &engine, const InducedPart &p, bool outside = true)
+{
+    const int64_t R = p.numreads();
+    if (p.has_reads) engine.check(elba_set_reads(engine.ctx, p.reads.data(), p.reads.offsets(), p.reads.lengths(), R, 0));
+    engine.check(elba_set_overlaps(engine.ctx, R, p.rows.data(), p.cols.data(), p.vals.data(), (int64_t)p.rows.size()));
+    const uint32_t none = 0;                                                  // (null arrays would detach)
+    if (outside) engine.check(elba_set_outside_counts(engine.ctx, R, R ? p.outside_aligned.data() : &none, R ? p.outside_passed.data() : &none));
+}
+
 // place_reads(S) — elba_place_reads on the S, the contigs of the last GenerateContigs and the pairs S was built from (the rule is stated in
 // include/elba_amd.h): every read on its contig — chain reads where the contig stage put them, the others through their best passed pair
 // with a chain read — and per contig the runs of equal depth and the credits.  An export: nothing on the engine changes.

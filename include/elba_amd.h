@@ -332,6 +332,23 @@ int  elba_transitive_reduction(elba_ctx *ctx, double bad_read_cutoff, int fuzz, 
 int  elba_export_string_graph(elba_ctx *ctx, elba_overlaps_t *out);
 int  elba_export_read_flags(elba_ctx *ctx, uint8_t *flags, int64_t nreads);
 
+/* The edge list from HBM, and the pairs a part does not see.
+ * elba_set_overlaps_device is elba_set_overlaps with the three arrays on the device (int64 rows, int64 cols, elba_overlap_t vals; n of each):
+ * the same conditions, checked by a kernel that finds the smallest offending index, the same ELBA_ERR_INVALID_ARG texts for that index, the
+ * same effects on the context.  The arrays are copied device to device: the source may be freed, or be another context's view (the d_rows /
+ * d_cols / d_vals of elba_induce_part), and may die afterwards.
+ * elba_set_outside_counts[_device] attaches two u32[nreads] arrays to the LOADED edge list (host arrays / device arrays): aligned[v] and
+ * passed[v] count pairs of read v that are not in the list — for a part cut out by elba_induce_part, its pairs with a read outside the
+ * part.  It needs a valid loaded list (ELBA_ERR_STATE otherwise) of exactly nreads reads and passed[v] <= aligned[v] < 2^31 for every v
+ * (ELBA_ERR_INVALID_ARG; the device flavour checks on the device); NULL for both arrays detaches the counts, NULL for one is
+ * ELBA_ERR_INVALID_ARG.  From the next elba_transitive_reduction on, read v is bad iff
+ *   (passed entries of v in the list + passed[v] + 1) / (entries of v in the list + aligned[v] + 1) <= bad_read_cutoff
+ * (in double, as before); nothing else reads the counts, and with none attached every result is bit for bit what it was.  Every call that
+ * replaces or invalidates the loaded list detaches them: elba_set_overlaps[_device], elba_prune_reads, elba_align_seeds, a new read set. */
+int  elba_set_overlaps_device(elba_ctx *ctx, int64_t nreads, const void *d_rows, const void *d_cols, const void *d_vals, int64_t n);
+int  elba_set_outside_counts(elba_ctx *ctx, int64_t nreads, const uint32_t *aligned, const uint32_t *passed);
+int  elba_set_outside_counts_device(elba_ctx *ctx, int64_t nreads, const void *d_aligned, const void *d_passed);
+
 /* Contigs: GenerateContigs (src/ContigGeneration.cpp:18-51,110,376-457) on the S of elba_transitive_reduction, one rank.  Reads of degree > 2
  * in S are branches and are dropped; the rest falls into paths, cycles and isolated reads; every path of >= 2 reads is walked from its
  * smaller-id end, and its contig is the concatenation over the chain of the first `prefix` bases of each read (reverse-complemented when the
@@ -610,6 +627,65 @@ void elba_free_components(elba_components_t *c);
  * ELBA_ERR_INVALID_ARG; otherwise as elba_graph_components. */
 typedef struct { int32_t graph, nparts, weight /* 0 reads, 1 bases */, min_reads /* the reference: 2 */, reserved[4]; } elba_part_cfg;
 int  elba_partition_components(elba_ctx *ctx, const elba_part_cfg *cfg, int32_t *part_of_read, int64_t nreads, int64_t *part_weight /* [nparts] */);
+
+/* The induced sub-problem of one part: what the reference's GetInducedReadSequences and ImposeMyReadDistribution (src/ContigGeneration.cpp)
+ * do with local_proc_assignments, cut out on the device.  elba_induce_part is an export in the sense of elba_graph_components: it reads the
+ * graph's input (M reads; the list of elba_set_overlaps[_device] / elba_prune_reads while one is valid, else this context's own alignments; a
+ * context that aligned a row shard: ELBA_ERR_STATE) and, with ELBA_INDUCE_BASES, the bases of those M reads (ELBA_ERR_STATE when they are not
+ * on the context), changes no product and invalidates nothing.  Every value is an integer and no result depends on the order of atomics.
+ *   selection   read v (0 <= v < M) is selected iff part_of_read[v] == cfg->part.  Any int32 is allowed; part = -1 selects what
+ *               elba_partition_components left unassigned.  nreads must be M.
+ *   numbering   old_of_new[0 .. reads) = the selected reads ascending: the new numbering preserves the order.  Ids are local to the graph's
+ *               input; stats.id_base is what elba_export_overlaps / elba_export_string_graph add to them.
+ *   reads       (ELBA_INDUCE_BASES) DnaBuffer layout exactly as elba_trim_reads leaves it: len'[w] = len[old_of_new[w]]; byte_off'[w] = the
+ *               running 64-bit sum of (len' + 3) / 4; the bytes are copied; the unused low bits of a read's last byte are zero; 16 zeroed
+ *               guard bytes follow the last read (d_packed / packed hold packed_bytes + 16).  Without the flag d_packed, d_byte_off, d_len
+ *               (and their host copies) are NULL and packed_bytes is 0.
+ *   pairs       pair a of the input is kept iff both of its reads are selected.  The output keeps the input's order — the numbering is
+ *               monotone, so it is again strictly ascending in (row, col) —, rows and cols renumbered, vals bit for bit the input's 36 bytes.
+ *   outside     outside_aligned[w] = the input pairs with exactly one read selected, that read being old_of_new[w]; outside_passed[w] = those
+ *               of them with passed != 0.  stats.split_pairs and stats.split_passed are their sums over w.
+ *   empty       no read selected is no error: reads = pairs = packed_bytes = 0, and the result loads as a context of 0 reads.
+ * Device views (d_*) stay valid until the next elba_induce_part on this context, elba_release_workspace or elba_ctx_destroy.  With
+ * ELBA_INDUCE_HOST the call also returns malloc'ed host copies (elba_free_induced frees them; arrays of 0 elements are still non-NULL), else
+ * the host pointers are NULL.  A failed call leaves *out zeroed.
+ * Loading a part: elba_set_reads[_device] with the reads, elba_set_overlaps[_device](reads, rows, cols, vals, pairs),
+ * elba_set_outside_counts[_device](reads, outside_aligned, outside_passed), on any context.
+ * The guarantee.  Let part_of_read come from elba_partition_components with graph = ELBA_CC_OVERLAPS on the same input, any nparts and
+ * min_reads.  Every passed pair lies inside one component and so inside one part: split_passed == 0 for every part (and for part -1).  Load
+ * a part with its reads, pairs and outside counts and run elba_transitive_reduction with the same cutoff and fuzz.  Then flag bits 0 and 1 of
+ * new read w are those of old_of_new[w] in the whole run (deg and pas of the bad-read rule are the whole run's: inside + outside; contained
+ * marks, the symmetrised R and the products of the reduction only ever follow passed pairs, which do not leave the part), and the new S is the whole
+ * run's S restricted to the part and renumbered, in the same export order.  Every call that reads only S, the flags, the reads and the
+ * passed pairs therefore returns the whole run's result restricted to the part: the five cleaning calls, contigs under all four flag
+ * combinations, links, placements, polish, and elba_read_pileup with mode = 0.  NOT covered: elba_read_pileup with mode = 1 (score > 0) when
+ * split_pairs > 0 — a failed pair with a positive score adds depth in the whole run and is absent from the part.  A selection that splits
+ * passed pairs (split_passed > 0) is served and counted but carries no guarantee.  Without the outside counts the guarantee fails as soon
+ * as one failed pair leaves the part: a read with 1 passed pair inside and 3 failed pairs outside has (1 + 1) / (4 + 1) <= 0.65 in the
+ * whole run and (1 + 1) / (1 + 1) in its part.
+ * Errors: null cfg, out or part_of_read, nreads != M, an unknown flag, a non-zero reserved
+ * word: ELBA_ERR_INVALID_ARG.  Read ids beyond 32 bit (M + id base >= 2^32 - 1 or M >= 2^31 - 1) or 2^31 - 1 pairs or more:
+ * ELBA_ERR_UNSUPPORTED.  elba_get_stat "induce_reads", "induce_pairs", "induce_split_pairs": those of the last call that succeeded.
+ * Cost: 4 B of part_of_read per read (copied to the device), 12 B per read read for the lengths and offsets; 16 + 1 B per input pair read by
+ * the mark; 52 B read and 52 B written per kept pair; bases / 4 read and written by the gather; one atomic per straddling pair and counter
+ * on its read's outside counters; two host synchronisations (the three sizes, then the counters) and one more for the host copies. */
+enum { ELBA_INDUCE_BASES = 1, ELBA_INDUCE_HOST = 2 };           /* flags */
+typedef struct { int32_t part, flags, reserved[2]; } elba_induce_cfg;
+typedef struct {
+    int64_t reads, pairs, packed_bytes;
+    /* device views */
+    const void *d_old_of_new /* i64[reads] */, *d_packed, *d_byte_off /* u64 */, *d_len /* u32 */,
+               *d_rows, *d_cols /* i64[pairs] */, *d_vals /* elba_overlap_t[pairs] */,
+               *d_outside_aligned, *d_outside_passed /* u32[reads] */;
+    /* host copies when ELBA_INDUCE_HOST is set, else NULL */
+    int64_t *old_of_new; uint8_t *packed; uint64_t *byte_off; uint32_t *len;
+    int64_t *rows, *cols; elba_overlap_t *vals; uint32_t *outside_aligned, *outside_passed;
+} elba_induced_t;
+typedef struct { int64_t nreads_in, pairs_in, reads, pairs, bases, packed_bytes, split_pairs, split_passed, id_base;
+                 float ms_total, ms_pairs, ms_gather; } elba_induce_stats;
+int  elba_induce_part(elba_ctx *ctx, const elba_induce_cfg *cfg, const int32_t *part_of_read, int64_t nreads,
+                      elba_induced_t *out, elba_induce_stats *stats);
+void elba_free_induced(elba_induced_t *o);
 
 /* Tip clipping (not in the reference, whose GenerateContigs drops every read of degree > 2 with its edges: one stray read hanging off a good
  * path cuts it into three contigs and loses the branch read).  elba_clip_tips works on the S of elba_transitive_reduction, in place, between
@@ -1047,6 +1123,8 @@ int  elba_set_option(elba_ctx *ctx, const char *name, int64_t value);
  *                            the last elba_export_assembly_links, under the same condition (0 also before the first call on these contigs)
  *   "cc_components", "cc_used_components", "cc_largest_reads", "cc_passes"
  *                            the last elba_graph_components / elba_partition_components: 0 once the graph it labelled is no longer valid
+ *   "induce_reads", "induce_pairs", "induce_split_pairs"
+ *                            the last elba_induce_part that succeeded (0 before the first)
  *   "text_tile_bytes", "text_scan_span"
  *                            constants of elba_set_reads_text: the bytes of the chunk one workgroup takes per trip of its two passes, and the
  *                            elements one workgroup of its scans covers (longer arrays make the scan recurse) */
