@@ -764,7 +764,7 @@ int elba_export_kmer_matrix(elba_ctx *ctx, elba_kmer_matrix_t *out)
         for (size_t i = 0; i <= M; ++i) out->rowptr[i] = rp[i];
         for (size_t z = 0; z < Z; ++z) {
             out->csc_row[z] = (int64_t)(csc[z] >> 32) + c.first_global_id_rows(); out->csc_val[z] = (uint32_t)csc[z];
-            out->csr_col[z] = (int64_t)(csr[z] >> 32); out->csr_val[z] = (uint32_t)csr[z] & (c.csr_suffix ? 0xFFFFu : (c.csr_hints ? 0x3FFFFFFFu : 0xFFFFFFFFu));      // (above the position: SpGEMM hints, or column length and place of a dense matrix)
+            out->csr_col[z] = (int64_t)(csr[z] >> 32); out->csr_val[z] = (uint32_t)csr[z] & csr_pos_mask(c.csr_suffix, c.csr_hints);      // (above the position: SpGEMM hints, or column length and place of a dense matrix)
         }
         if (c.csr_inline) {
             // rows with inline partners (Ctx::csr_inline) do not name the k-mer of such an entry: the rows are rebuilt from the columns — walked in
@@ -807,6 +807,7 @@ int elba_kmer_histogram(elba_ctx *ctx, int64_t *hist, int64_t len)
     });
 }
 
+static_assert((int)CSR_FORMAT_PLAIN == ELBA_CSR_PLAIN && (int)CSR_FORMAT_HINTS == ELBA_CSR_HINTS && (int)CSR_FORMAT_DENSE == ELBA_CSR_DENSE && (int)CSR_FORMAT_INLINE == ELBA_CSR_INLINE, "csr_plan.hpp numbers the formats as the ABI does");
 int elba_get_device_view(elba_ctx *ctx, elba_device_view *v)
 {
     return guarded(ctx, [&](Ctx &c) {
@@ -814,8 +815,8 @@ int elba_get_device_view(elba_ctx *ctx, elba_device_view *v)
         memset(v, 0, sizeof(*v));
         v->stream = (void *)c.stream;
         if (has(c.v, P_A)) { v->M = c.M; v->N = c.N; v->Z = c.Z; v->a_rowptr = c.a_rowptr.p; v->a_csr = c.a_csr.p; v->a_colptr = c.a_colptr.p; v->a_csc = c.a_csc.p;
-                        v->a_csr_format = c.csr_inline ? ELBA_CSR_INLINE : (c.csr_suffix ? ELBA_CSR_DENSE : (c.csr_hints ? ELBA_CSR_HINTS : ELBA_CSR_PLAIN));
-                        v->a_csr_pos_mask = c.csr_suffix ? 0xFFFFu : (c.csr_hints ? 0x3FFFFFFFu : 0xFFFFFFFFu);
+                        v->a_csr_format = csr_format(c.csr_inline, c.csr_suffix, c.csr_hints);
+                        v->a_csr_pos_mask = csr_pos_mask(c.csr_suffix, c.csr_hints);
                         v->a_kmers = c.A_has_kmers ? c.rel_kmers.p : nullptr;
                         v->a_gather_slots = c.use_ell && c.ell_compact ? c.ell_nslots : 0;
                         v->a_slot_kid = c.use_ell && c.ell_compact ? c.ell_slot_kid.p : nullptr; }
@@ -864,7 +865,7 @@ int elba_release_workspace(elba_ctx *ctx)
         c.cg.release_scratch(); c.gl.release_scratch(); c.pu.release_scratch(); c.pl.release_scratch(); c.po.release_scratch(); c.cc.release_scratch(); c.in.release_scratch(); c.tm.release_scratch();
         c.sg.release();      // the cleaning calls' shared scratch and the spare buffer of S (S itself stays)
         c.tp.release_scratch(); c.bb.release_scratch(); c.wk.release_scratch(); c.br.release_scratch(); c.sr.release_scratch();
-        if (has(c.v, P_COUNTS)) { c.pre_ready = false; c.pre_consumed = true; }    // (the CSR sort keys / column ids of the entries are gone: create_kmer_matrix rebuilds them from the column pointers)
+        if (has(c.v, P_COUNTS)) c.pre.consume();    // (the CSR sort keys / column ids of the entries are gone: create_kmer_matrix rebuilds them from the column pointers)
     });
 }
 

@@ -247,9 +247,11 @@ struct Ctx {
     DevBuf rel_kmers_lo;  // u64[N] their second word when k > 32
     DevBuf rel_kmers_lo2; // u64[N] their third word when k > 64
     DevBuf rel_counts;    // u32[N]
-    DevBuf csr_words;     // u64[Z] read << (pre_nb + pre_pb) | k-mer id << pre_pb | pos of every entry of a_csc, when pre_words (k_runs_emit -> the CSR build's sort)
-    bool pre_pairs = false;      // dense matrix from kmer_msd.hip: the (read, kid | L | place | pos) pairs of the CSR sort are written (keys in ws_b; values where a sort of Z pairs on the read bits that ENDS in a_csr starts: a_csr or ws_d)
-    bool pre_ready = false, pre_consumed = false, pre_words = false, pre_hints = false, pre_hints_done = false, pre_ell_done = false, pre_inline = false, pre_inline_pending = false /* the sort keys leave room for inline partners: k_add_hints writes them */; int pre_rs = 0, pre_pbi = 0; int pre_nb = 0, pre_pb = 0; uint64_t pre_maxpos = 0;
+    DevBuf csr_words;     // u64[Z] the CSR build's sort key of every entry of a_csc — read << pre.rs | k-mer id << (pre.pb + 2) | hint << pre.pb | pos, or an inline partner (csr_plan.hpp) — when pre.words
+    CsrHandoff pre;       // what the k-mer stage (k_runs_emit's caller in kmer.hip, the bucket kernels of kmer_msd.hip — for reads and for device triples) leaves for the CSR build of
+                          // the same matrix: assigned whole by the producer, reset where elba_count_kmers starts, consume()d by the build that used it and by elba_release_workspace
+    // The format of the resident A — csr_hints, csr_inline, csr_inline_window, csr_one_word, csr_suffix, pos16, j_shift, have_row_order below — is decided by
+    // plan_csr_build (csr_plan.hpp) and assigned in ONE place, when the build has run (matrix.hip: CsrBuild::publish_format).
     // Ownership hints of the SpGEMM, two bits in every a_csr entry (kid << 32 | hint << 30 | pos; positions below 2^30): bit 30 = under the
     // parity rule of owns_pair (spgemm_direct.hpp) this row accumulates NO pair of the entry's column and appears in it once — the column
     // need not be fetched at all, the entry only counts one diagonal product; bit 31 = the same with every partner outside the row window
@@ -571,6 +573,13 @@ void stage_create_kmer_matrix(Ctx &c);                            // kmer.hip
 bool msd_matrix_from_triples(Ctx &c, int64_t M, int64_t N, int64_t Z, const int64_t *d_rows, const int64_t *d_cols, const uint32_t *d_vals);   // kmer_msd.hip: false = matrix.hip sorts
 bool msd_count_kmers(Ctx &c, uint64_t I, elba_kmer_stats &st);   // kmer_msd.hip: false = not applicable (the caller sorts)
 void choose_column_store(Ctx &c, int64_t N, int64_t max_col);     // matrix.hip: padded column store or plain CSC, strides, sequence-number bits
+inline CsrOptions csr_options(const Ctx &c)                       // the options csr_plan.hpp's decisions read
+{
+    CsrOptions o;
+    o.csr_pairs = c.opt.csr_pairs; o.no_hints = c.opt.no_hints; o.no_pay = c.opt.no_pay; o.no_inline = c.opt.no_inline; o.no_symmetry = c.opt.no_symmetry; o.no_ell = c.opt.no_ell;
+    o.no_suffix = c.opt.no_suffix; o.panel_inline = c.opt.panel_inline; o.no_row_order = c.opt.no_row_order; o.tune1 = c.opt.tune[1];
+    return o;
+}
 void stage_set_kmer_matrix(Ctx &c, int64_t M, int64_t N, int64_t Z, const int64_t *rows, const int64_t *cols, const uint32_t *vals);  // matrix.hip
 void stage_set_kmer_matrix_device(Ctx &c, int64_t M, int64_t N, int64_t Z, const int64_t *d_rows, const int64_t *d_cols, const uint32_t *d_vals);
 void stage_export_triples_device(Ctx &c, int64_t *d_rows, int64_t *d_cols, uint32_t *d_vals);

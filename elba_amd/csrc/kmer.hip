@@ -412,13 +412,6 @@ __global__ void k_instance_entries(const uint64_t *payload, const uint64_t *kid_
     csc[z] = ((uint64_t)lo << 32) | (uint32_t)(g - off_lo);
 }
 
-int bits_needed(uint64_t maxval)
-{
-    int b = 1;
-    while (b < 64 && (maxval >> b)) ++b;
-    return b;
-}
-
 int next_pow2_bits(uint64_t v)
 {
     int b = 0;
@@ -479,7 +472,7 @@ static void runs_to_columns(Ctx &c, const uint64_t *skeys, const uint64_t *svals
     res(c.kid_of_entry, (size_t)(Z + 8) * 8);
     // Packed words with UPPER <= 62: one fused pass writes the columns, the entries' (read, pos) and — when read, k-mer id and position fit
     // one word — the sort keys of the CSR build (k_runs_emit).  Otherwise: heads write payloads and column ids, a second kernel converts.
-    c.pre_ready = false; c.pre_consumed = false; c.pre_hints_done = false; c.pre_ell_done = false; c.pre_inline_pending = false; c.pre_pairs = false;
+    CsrHandoff handoff;      // (none, unless the fused pass below leaves the sort keys)
     const bool fused = ib && p.upper <= 62 && !c.opt.kmer_unfused;
     if (fused && Z > 0) {
         EnumParams e = make_enum(c);
@@ -490,28 +483,20 @@ static void runs_to_columns(Ctx &c, const uint64_t *skeys, const uint64_t *svals
         for (int64_t r = 0; r < c.nreads; ++r) maxlen = c.h_len[(size_t)r] > maxlen ? c.h_len[(size_t)r] : maxlen;
         const uint64_t maxpos = maxlen >= (uint32_t)c.cfg.k ? maxlen - (uint32_t)c.cfg.k : 0;      // (a bound: the largest position any entry can have)
         const int mb = bits_needed((uint64_t)(c.nreads > 0 ? c.nreads - 1 : 0)), nb = bits_needed((uint64_t)(N > 0 ? N - 1 : 0)), pb = bits_needed(maxpos);
-        const bool words = mb + nb + pb + 2 <= 64 && !c.opt.csr_pairs;
-        const bool hints = pb <= 30 && !c.opt.no_hints;
+        // inline partners (Ctx::csr_inline), as kmer_msd.hip: the keys leave room for them — read as high as it goes, pbi position bits — and
+        // the hint pass that sees every entry's column anyway (k_add_hints, matrix.hip) writes them, if the matrix turns out to qualify
+        // (padded columns, not dense: UPPER <= 16 guarantees the latter here, where no column has been seen yet)
+        const CsrKeyLayout lay = csr_key_layout(mb, nb, pb, (int64_t)N, csr_options(c), CsrProducer{!c.opt.no_ell, p.upper <= (uint32_t)CSR_SPARSE_MAX_COL, maxpos < 65536, false}, CSR_INLINE_PENDING);
         c.prod_ctr.reserve(64 * 128);
         ELBA_HIP(hipMemsetAsync(c.prod_ctr.p, 0, 64 * 128, s));
         EmitOut o{};
         o.prod_ctr = c.prod_ctr.as<unsigned long long>();
         o.rel_kmers = c.rel_kmers.as<uint64_t>(); o.rel_counts = c.rel_counts.as<uint32_t>(); o.colptr = c.a_colptr.as<uint32_t>();
         o.csc = c.a_csc.as<uint64_t>(); o.kid_of_entry = c.kid_of_entry.as<uint64_t>(); o.nb = nb; o.pb = pb;
-        // inline partners (Ctx::csr_inline), as kmer_msd.hip: the keys leave room for them — read as high as it goes, pbi position bits — and
-        // the hint pass that sees every entry's column anyway (k_add_hints, matrix.hip) writes them, if the matrix turns out to qualify
-        // (padded columns, not dense: UPPER <= 16 guarantees the latter here, where no column has been seen yet)
-        int rs = nb + pb + 2, pbi = 0;
-        bool inl = words && hints && maxpos < 65536 && p.upper <= 16 && !c.opt.no_pay && !c.opt.no_inline && !c.opt.no_symmetry && !c.opt.no_ell && N < (1ll << 31) && mb >= 2;
-        if (inl) {
-            const int rs2 = 63 - mb;
-            pbi = std::min(pb, (rs2 - (mb - 1)) / 2);
-            if (rs2 >= rs && pbi >= 10) rs = rs2; else inl = false;
-        }
-        o.rs = rs;
-        if (words) { c.csr_words.reserve((size_t)(Z + 8) * 8); o.csr_words = c.csr_words.as<uint64_t>(); }
+        o.rs = lay.rs;
+        if (lay.words) { c.csr_words.reserve((size_t)(Z + 8) * 8); o.csr_words = c.csr_words.as<uint64_t>(); }
         hipLaunchKernelGGL(k_runs_emit, dim3(nblocks), dim3(RUN_THREADS), 0, s, p, e, (const BlockInfo *)c.ws_b.as<BlockInfo>(), drop, (const uint32_t *)off_rel, (const uint32_t *)off_ent, o);
-        c.pre_ready = true; c.pre_words = words; c.pre_hints = hints; c.pre_nb = nb; c.pre_pb = pb; c.pre_maxpos = maxpos; c.pre_rs = rs; c.pre_inline = false; c.pre_inline_pending = inl; c.pre_pbi = inl ? pbi : 0;
+        handoff = csr_handoff(lay, nb, pb, maxpos);
     } else {
     // entry payloads: written straight into a_csc when they are final (pairs: read << 32 | pos), else into scratch and converted
     DevBuf &scratch = c.ws_f;
@@ -530,6 +515,7 @@ static void runs_to_columns(Ctx &c, const uint64_t *skeys, const uint64_t *svals
                            c.ws_b.as<BlockInfo>());
     }
     }
+    c.pre = handoff;
     const uint32_t Zz = base.ent + (uint32_t)Z;
     ELBA_HIP(hipMemcpyAsync(c.a_colptr.as<uint32_t>() + N, &Zz, 4, hipMemcpyHostToDevice, s));
     ELBA_HIP(hipStreamSynchronize(s));
@@ -578,6 +564,7 @@ void stage_count_kmers(Ctx &c)
     accepted(c.v, EV_COUNT_KMERS);
     c.dist_owner = false;
     c.kmer_path = 0;
+    c.pre = CsrHandoff{};
     elba_kmer_stats st{};
     st.nreads = M;
 
@@ -719,8 +706,8 @@ void stage_create_kmer_matrix(Ctx &c)
     // CSC(A) came out of the counting sort already; the CSR build needs the column id of every entry.  The fused column pass (k_runs_emit) left
     // them as ready-made sort keys (csr_words), which the build CONSUMES (hint bits are ORed in, the sort ping-pongs over them): a second call
     // after one elba_count_kmers rebuilds the column ids from the column pointers instead.
-    const bool pre = c.pre_ready;
-    if (!pre && c.pre_consumed && N > 0) {
+    const bool pre = c.pre.ready();
+    if (c.pre.state == CsrHandoff::CONSUMED && N > 0) {
         c.kid_of_entry.reserve((size_t)(Z + 8) * 8);
         hipLaunchKernelGGL(k_expand_colptr, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, (const uint32_t *)c.a_colptr.as<uint32_t>(), (uint64_t)N, c.kid_of_entry.as<uint64_t>());
     }
@@ -728,7 +715,7 @@ void stage_create_kmer_matrix(Ctx &c)
     c.t_c.stop(s);
     c.A_has_kmers = true;
     finish_matrix_from_sorted_csc(c, M, N, Z, c.kid_of_entry.as<uint64_t>(), 0, c.a_csc.as<uint64_t>(), 0, -1, pre);      // (column ids — or the CSR sort keys — were written with the columns: k_runs / k_runs_emit)
-    if (pre) { c.pre_ready = false; c.pre_consumed = true; }
+    if (pre) c.pre.consume();
     c.kstats.ms_lookup = c.t_c.ms();
     done(c.v, EV_CREATE_KMER_MATRIX);
 }

@@ -1803,6 +1803,7 @@ struct MsdRun {
     uint32_t np_max = 0;
     // the layout of A (layout_output)
     int nb = 0, pb = 0, rs = 0, pbi = 0;
+    CsrKeyLayout lay;      // (csr_plan.hpp; words, hints, rs, pbi, inl: its fields, as the emit kernels' arguments name them)
     bool words = false, hints = false, inl = false, pairs = false, compact = false, mprep = false;
     EmitGrids grids{};
     MsdRun(Ctx &c_, const MsdPlan &pl_, const MsdTriples *tri_) : c(c_), pl(pl_), tri(tri_), s(c_.stream) {}
@@ -1947,7 +1948,7 @@ struct MsdRun {
     void partition_wide(const Pass &pp, bool timed)
     {
         const uint32_t nb1 = pp.nb1, nb2 = pp.nb2, nbuckets = nb1 * nb2, ntiles1 = pl.ntiles1;
-        const int Tp = pp.T, b2 = bits_needed_u(nb2) - 1, k2 = pl.k2;
+        const int Tp = pp.T, b2 = bits_needed(nb2) - 1, k2 = pl.k2;
         const uint64_t Iv = pp.I;
         ELBA_REQUIRE(Iv + 2 <= std::min(c.ws_a.cap, c.ws_c.cap) / 16, ELBA_ERR_INTERNAL, "count_kmers: a value-range pass is larger than its partition buffers");
         uint32_t *hist = this->hist();      // (the sort of an earlier pass's crowded buckets may have grown its workspace)
@@ -2170,31 +2171,23 @@ struct MsdRun {
         c.rel_counts.reserve((size_t)(N + 2) * 4);
         c.a_colptr.reserve((size_t)(N + 2) * 4);
         c.a_csc.reserve((size_t)(Z + 8) * 8);
-        nb = bits_needed_u((uint64_t)(N > 0 ? N - 1 : 0)); pb = m.pbits;
-        words = mb + nb + pb + 2 <= 64 && !c.opt.csr_pairs;
-        hints = pb <= 30 && !c.opt.no_hints;
+        nb = bits_needed((uint64_t)(N > 0 ? N - 1 : 0)); pb = m.pbits;
         o.rel_kmers = tri ? nullptr : c.rel_kmers.as<uint64_t>(); o.rel_counts = c.rel_counts.as<uint32_t>(); o.colptr = c.a_colptr.as<uint32_t>();
         c.max_col_nnz = (int64_t)hs.maxcol;
         choose_column_store(c, (int64_t)N, c.max_col_nnz);
         // inline partners (Ctx::csr_inline): whole matrix, general (not dense) SpGEMM path with position-carrying accumulators, and a sort word wide
         // enough for flag | read | partner >> 1 | posQ | posT
-        const bool dense = c.use_ell && maxpos < 65536 && c.max_col_nnz > 16 && !c.opt.no_pay && !c.opt.no_suffix;
-        // The inline key is flag | read << rs | (partner >> 1) << 2 pbi | posQ << pbi | posT with the read as high as it goes (rs = 63 - mb): pbi position
-        // bits are what is left, and an entry is written inline only if both positions fit them (200 100 reads of up to 16.6 kb: 14 bits, all but
-        // the last bases of a handful of reads)
-        rs = nb + pb + 2; pbi = 0;
-        inl = words && hints && c.use_ell && !dense && maxpos < 65536 && !c.opt.no_pay && !c.opt.no_inline && !c.opt.no_symmetry && N < (1ull << 31) && mb >= 2;
-        if (inl) {
-            const int rs2 = 63 - mb;
-            pbi = std::min(pb, (rs2 - (mb - 1)) / 2);
-            if (rs2 >= rs && pbi >= 10) rs = rs2; else inl = false;
-        }
+        const CsrOptions copt = csr_options(c);
+        const bool dense = csr_dense(c.use_ell, maxpos < 65536, c.max_col_nnz, copt);
+        // The inline key holds the read as high as it goes and pbi position bits (csr_plan.hpp: csr_key_layout); an entry is written inline only if both
+        // positions fit them (200 100 reads of up to 16.6 kb: 14 bits, all but the last bases of a handful of reads)
+        lay = csr_key_layout(mb, nb, pb, (int64_t)N, copt, CsrProducer{c.use_ell, !dense, maxpos < 65536, false}, CSR_INLINE_NOW);
+        words = lay.words; hints = lay.hints; rs = lay.rs; pbi = lay.pbi; inl = lay.inl == CSR_INLINE_NOW;
         o.csc = c.a_csc.as<uint64_t>(); o.nb = nb; o.pb = pb; o.rs = rs; o.mb = mb; o.inl = inl ? (uint32_t)pbi : 0u; o.hints = hints && words && !dense ? 1u : 0u;
         // a dense matrix's CSR build sorts (read, entry) pairs (matrix.hip, csr_suffix: the entry carries its column's length and its place in it — known
         // here, where the column lies sorted in LDS): they are written instead of sort words, the values where a sort that ends in a_csr starts
         // (not under value-range batching: phase B enumerates the reads again through the block table in ws_b, which the pairs would take — the sort words instead, as "csr_pairs_late")
         pairs = dense && N < (1ull << 32) && c.max_col_nnz < 128 && !c.opt.csr_pairs_late && !pl.batched;
-        c.pre_pairs = pairs;
         if (pairs) {
             c.ws_b.reserve((size_t)(Z + 1) * 8); c.ws_d.reserve((size_t)(Z + 1) * 8); c.a_csr.reserve((size_t)(Z + 1) * 8);      // (ws_b: the enumeration's block table is dead)
             o.pair_key = c.ws_b.as<uint32_t>();
@@ -2304,8 +2297,9 @@ struct MsdRun {
             emit_passes();
             ELBA_HIP(hipStreamSynchronize(s));
         } else if (compact) c.ell_nslots = (int64_t)slots[0];      // (an upper bound of the slots in use: chunks are drawn whole)
-        c.pre_ready = true; c.pre_consumed = false; c.pre_words = words; c.pre_hints = hints; c.pre_hints_done = hints && words; c.pre_ell_done = true; c.pre_inline_pending = false;
-        c.pre_nb = nb; c.pre_pb = pb; c.pre_maxpos = pl.maxpos; c.pre_rs = rs; c.pre_inline = inl; c.pre_pbi = pbi;
+        CsrHandoff handoff = csr_handoff(lay, nb, pb, pl.maxpos);
+        handoff.hints_done = hints && words; handoff.ell_done = true; handoff.pairs = pairs;
+        c.pre = handoff;
         if (tri) return;
         elba_kmer_stats &st = *stp;
         st.instances = (int64_t)pl.I; st.distinct = (int64_t)hs.distinct; st.reliable = (int64_t)N; st.entries = (int64_t)Z;

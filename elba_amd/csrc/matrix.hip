@@ -70,7 +70,7 @@ __global__ void k_csc_to_csr_words(const uint64_t *kid_keys, int kid_shift, cons
             }
             const uint64_t pos = e & 0xFFFFFFFFull, opos = other & 0xFFFFFFFFull;
             if (mult == 1u && nown == 1u && ((pos | opos) >> pbi) == 0)
-                word = (1ull << 63) | ((e >> 32) << rs) | (((other >> 32) >> 1) << (2 * pbi)) | (pos << pbi) | opos;
+                word = csr_inline_word(e >> 32, rs, other >> 32, pbi, pos, opos);
         }
     }
     words[z] = word;
@@ -98,7 +98,7 @@ __global__ void k_add_hints(const uint32_t *colptr, const uint64_t *csc, int64_t
             if (((i ^ j) & 1u) ? j < i : j > i) { ++nown; other = y; }
         }
         const uint64_t pos = e & 0xFFFFFFFFull, opos = other & 0xFFFFFFFFull;
-        if (mult == 1u && nown == 1u && ((pos | opos) >> pbi) == 0) { words[z] = (1ull << 63) | ((e >> 32) << rs) | (((other >> 32) >> 1) << (2 * pbi)) | (pos << pbi) | opos; return; }
+        if (mult == 1u && nown == 1u && ((pos | opos) >> pbi) == 0) { words[z] = csr_inline_word(e >> 32, rs, other >> 32, pbi, pos, opos); return; }
         if (mult < 2u && nown == 0u) words[z] = w | (3ull << pb);      // (the whole matrix: both hint bits agree)
         return;
     }
@@ -115,12 +115,7 @@ __global__ void k_unpack_csr_words(const uint64_t *words, int64_t Z, int nb, int
     const uint64_t w = z < Z ? words[z] : 0;
     const int64_t cur = z < Z ? (int64_t)((w >> rs) & rmask) : M;
     for (int64_t k = prev + 1; k <= cur; ++k) rowptr[k] = (uint32_t)z;
-    if (z < Z) {
-        if (pbi && (w >> 63)) {      // inline partner (Ctx::csr_inline): flag | partner >> 1 | posQ | posT << 16.  (pbi 0: no word is one, and bit 63 belongs to the read when the fields fill all 64 bits)
-            const uint64_t pm = (1ull << pbi) - 1;
-            csr[z] = (1ull << 63) | (((w >> (2 * pbi)) & ((1ull << (mb - 1)) - 1)) << 32) | ((w >> pbi) & pm) | ((w & pm) << 16);
-        } else csr[z] = (((w >> (pb + 2)) & ((1ull << nb) - 1)) << 32) | (((w >> pb) & 3ull) << 30) | (w & ((1ull << pb) - 1));
-    }
+    if (z < Z) csr[z] = csr_entry_of_word(w, nb, pb, mb, pbi);      // (an inline partner, Ctx::csr_inline, or kid | hint | pos: csr_plan.hpp)
 }
 
 __global__ void k_colrow_to_csc(const uint64_t *colrow, const uint64_t *pos, int64_t Z, uint64_t *csc)
@@ -231,13 +226,6 @@ __global__ void k_order_and_labels(const uint64_t *keys, uint32_t M, uint32_t *o
     if (t < M) { const uint32_t r = (uint32_t)keys[t]; order[t] = r; label[r] = t; }
 }
 
-int bits_for(uint64_t maxval)
-{
-    int b = 1;
-    while (b < 64 && (maxval >> b)) ++b;
-    return b;
-}
-
 }  // namespace
 
 int64_t max_segment_len(Ctx &c, const uint32_t *ptr, int64_t nseg)
@@ -254,188 +242,161 @@ int64_t max_segment_len(Ctx &c, const uint32_t *ptr, int64_t nseg)
     return (int64_t)h;
 }
 
-// The column store the SpGEMM gathers from.  No column longer than 64 entries (UPPER <= 64: every configuration the reference
-// documents): columns padded to a common stride S (4 entries, or whole 64-byte lines), column kid at kid * S — its address is arithmetic, and a
-// group of S/2 lanes reads it as one aligned segment.  Longer columns (or no room for the padding): the plain CSC, reached through a_colptr.
+// The column store the SpGEMM gathers from: padded columns (no column longer than 64 entries — UPPER <= 64: every configuration the reference
+// documents — and room for the padding), column kid at kid * S, its address arithmetic, read by a group of S/2 lanes as one aligned segment; else the
+// plain CSC, reached through a_colptr (csr_plan.hpp: plan_column_store decides).
 // Sets use_ell, s_stride, lpc_log2, fbits and reserves a_ell (guard words written); the caller fills it.
 void choose_column_store(Ctx &c, int64_t N, int64_t max_col)
 {
-    hipStream_t s = c.stream;
-    const uint32_t mc = (uint32_t)(max_col > 0 ? max_col : 1);
-    // stride: 4 entries, else the longest column rounded up to whole 64-byte lines (8 entries) — a power of two is not needed: the kernel
-    // multiplies (U = 35: 40 entries = 5 lines per gather where 64 entries would fetch 8)
-    const uint32_t stride = mc <= 4 ? 4u : (mc + 7u) & ~7u;
     size_t free_b = 0, total_b = 0;
     ELBA_HIP(hipMemGetInfo(&free_b, &total_b));
-    const size_t ell_bytes = (size_t)N * stride * 8;
-    c.use_ell = mc <= 64 && N > 0 && !c.opt.no_ell && ell_bytes <= (free_b + c.a_ell.cap) / 3 && (uint64_t)N * stride < (1ull << 40);
-    if (!c.use_ell && mc <= 64 && N > 0 && !c.opt.no_ell && c.opt.trace)
-        fprintf(stderr, "[elba] the padded column store (%zu bytes) does not fit a third of the free device memory (%zu bytes): columns are gathered from CSC\n", ell_bytes, free_b + c.a_ell.cap);
+    const ColumnStore st = plan_column_store(N, max_col, c.opt.no_ell, free_b + c.a_ell.cap);
+    if (!st.padded && st.wanted && c.opt.trace)
+        fprintf(stderr, "[elba] the padded column store (%zu bytes) does not fit a third of the free device memory (%zu bytes): columns are gathered from CSC\n", st.bytes, free_b + c.a_ell.cap);
+    c.use_ell = st.padded; c.s_stride = st.stride; c.lpc_log2 = st.lpc_log2; c.fbits = st.fbits;
     c.ell_compact = false; c.ell_nslots = c.use_ell ? N : 0; c.ell_cap_cols = c.use_ell ? N : 0;      // (kmer_msd.hip may compact the store: gather slots)
     if (c.use_ell) {
-        uint32_t lb = 1, fb = 2;
-        while ((2u << lb) < stride) ++lb;              // lanes per row entry: 16 bytes (two entries) each
-        while ((1u << fb) < stride) ++fb;
-        c.s_stride = stride; c.lpc_log2 = lb; c.fbits = fb;
-        c.a_ell.reserve(ell_bytes + 64);
-        ELBA_HIP(hipMemsetAsync(c.a_ell.as<char>() + ell_bytes, 0xFF, 64, s));      // (guard words behind the last column)
-    } else {
-        // lanes per row entry: half the longest column, between 2 and 64 (a column is walked in chunks of 2 * lanes entries)
-        uint32_t lb = 1;
-        while (lb < 6 && (2u << lb) < mc) ++lb;
-        c.lpc_log2 = lb; c.s_stride = 0;
-        int fb = 1;
-        while (fb < 31 && ((uint64_t)(mc > 1 ? mc - 1 : 1) >> fb)) ++fb;
-        c.fbits = (uint32_t)fb;
+        c.a_ell.reserve(st.bytes + 64);
+        ELBA_HIP(hipMemsetAsync(c.a_ell.as<char>() + st.bytes, 0xFF, 64, c.stream));      // (guard words behind the last column)
     }
 }
 
-// Input: Z entries sorted by (kid, read, pos): kid_keys[z] >> kid_shift = kid, csc[z] = read<<32|pos (device, in c.a_csc or elsewhere).
-// Produces c.a_colptr, c.a_csc (copy if csc is not already c.a_csc), c.a_rowptr, c.a_csr, max_row_nnz, max_col_nnz.
-// [win_lo, win_hi) = the rows of B this context computes (win_hi < 0: all); the product schedule is laid out for those rows only.
-void finish_matrix_from_sorted_csc(Ctx &c, int64_t M, int64_t N, int64_t Z, const uint64_t *kid_keys, int kid_shift, const uint64_t *csc, int64_t win_lo, int64_t win_hi, bool pre)
-{
-    // pre: the k-mer stage left the column pointers, a bound on the positions and (pre_words) the CSR sort keys behind (k_runs_emit, kmer.hip)
+namespace {
+
+// ---- finish_matrix_from_sorted_csc: what its steps share, and the steps -------------------------------------------------------------------
+struct CsrBuild {
+    Ctx &c;
+    const int64_t M, N, Z;
+    const uint64_t *kid_keys; int kid_shift;
+    const bool pre;                 // the k-mer stage left the column pointers, a bound on the positions and the CSR sort's input behind (Ctx::pre)
     hipStream_t s = c.stream;
-    c.M = M; c.N = N; c.Z = Z;
-    c.a_colptr.reserve((size_t)(N + 1) * 4);
-    c.a_rowptr.reserve((size_t)(M + 1) * 4);
-    c.a_csc.reserve((size_t)(Z + 8) * 8);   // + guard entries: the SpGEMM gathers up to four consecutive entries without a bounds check
-    c.a_csr.reserve((size_t)(Z + 1) * 8);
-    if (!pre) group_offsets_u32(s, kid_keys, kid_shift, Z, c.a_colptr.as<uint32_t>(), N);
-    if (csc != c.a_csc.as<uint64_t>() && Z > 0)
-        ELBA_HIP(hipMemcpyAsync(c.a_csc.p, csc, (size_t)Z * 8, hipMemcpyDeviceToDevice, s));
-    // largest position among the entries: below 2^16 the SpGEMM's 64-bit accumulators carry both positions of a seed (spgemm_direct.hpp);
-    // it also decides whether an entry fits one word for the CSR sort
-    uint64_t maxpos = pre ? c.pre_maxpos : 0;
-    if (Z > 0 && !pre) {
-        int64_t nbz = (Z + 255) / 256;
-        if (nbz > 2048) nbz = 2048;
-        c.ws_scan.reserve(64);
-        ELBA_HIP(hipMemsetAsync(c.ws_scan.p, 0, 8, s));
-        hipLaunchKernelGGL(k_max_low32, dim3((unsigned)nbz), dim3(256), 0, s, c.a_csc.as<uint64_t>(), Z, c.ws_scan.as<unsigned long long>());
-        ELBA_HIP(hipMemcpyAsync(&maxpos, c.ws_scan.p, 8, hipMemcpyDeviceToHost, s));
-        ELBA_HIP(hipStreamSynchronize(s));
-    }
-    c.pos16 = maxpos < 65536;
-    ELBA_REQUIRE(win_lo >= 0 && (win_hi < 0 || (win_lo <= win_hi && win_hi <= M)), ELBA_ERR_INVALID_ARG, "bad row window");
-    // stable sort by read: rows come out ordered by (kid, pos)
-    c.ws_a.reserve((size_t)(Z + 1) * 8); c.ws_c.reserve((size_t)(Z + 1) * 8);
-    const int mb = bits_for((uint64_t)(M > 0 ? M - 1 : 0)), nb = bits_for((uint64_t)(N > 0 ? N - 1 : 0)), pb = bits_for(maxpos);
-    bool hints = pre ? c.pre_hints : (pb <= 30 && !c.opt.no_hints);
-    const uint32_t wlo = (uint32_t)win_lo, whi = (uint32_t)(win_hi < 0 ? M : win_hi);
-    c.prod_ctr.reserve(64 * 128);
-    unsigned long long *prod_ctr = c.prod_ctr.as<unsigned long long>();
-    if (!pre) ELBA_HIP(hipMemsetAsync(prod_ctr, 0, 64 * 128, s));      // (pre: k_runs_emit has counted)
-    // Dense matrices (columns of more than 16 reads, e.g. UPPER = 35 on 40x low-error reads: every row owns pairs of every column, hundreds of
-    // products per surviving pair): pairs are owned by their SMALLER row and an entry's owned candidates are the column's entries behind its
-    // own — the row entries then carry the column's length and their own place in it, and the SpGEMM hands out exactly those candidates to
-    // its lanes (spgemm_direct.hpp, "suffix" path).  Positions below 2^16, the padded column store.  With a row window (a shard, a row block
-    // of a shard: elba_dist_set_panel) the padded columns are stored rotated so that this stays true (k_fill_ell).
-    const bool windowed = !(win_lo == 0 && (win_hi < 0 || win_hi == M));
-    c.csr_inline = false; c.csr_inline_window = false;
+    bool windowed = false; uint32_t wlo = 0, whi = 0;
+    uint64_t maxpos = 0;
     const uint8_t *colw0 = nullptr;
-    if (!(pre && c.pre_ell_done)) {      // (the two-level partition of kmer_msd.hip writes the padded columns with the columns themselves)
-        c.max_col_nnz = max_segment_len(c, c.a_colptr.as<uint32_t>(), N);
+    CsrBuildPlan p;
+    const uint32_t *colptr() const { return c.a_colptr.as<uint32_t>(); }
+    const uint64_t *columns() const { return c.a_csc.as<uint64_t>(); }
+    unsigned long long *prod_ctr() const { return c.prod_ctr.as<unsigned long long>(); }
+    DevBuf &ws(CsrBuf b) const { return b == CSR_WS_A ? c.ws_a : b == CSR_WS_B ? c.ws_b : b == CSR_WS_C ? c.ws_c : c.ws_d; }
+    static unsigned blocks(int64_t n) { return (unsigned)((n + 255) / 256); }
+
+    // the matrix's size, its buffers, the columns in a_csc, the largest position among the entries: below 2^16 the SpGEMM's 64-bit accumulators carry both
+    // positions of a seed (spgemm_direct.hpp); it also decides whether an entry fits one word for the CSR sort
+    void size_and_maxpos(const uint64_t *csc, int64_t win_lo, int64_t win_hi)
+    {
+        c.M = M; c.N = N; c.Z = Z;
+        c.a_colptr.reserve((size_t)(N + 1) * 4);
+        c.a_rowptr.reserve((size_t)(M + 1) * 4);
+        c.a_csc.reserve((size_t)(Z + 8) * 8);   // + guard entries: the SpGEMM gathers up to four consecutive entries without a bounds check
+        c.a_csr.reserve((size_t)(Z + 1) * 8);
+        if (!pre) group_offsets_u32(s, kid_keys, kid_shift, Z, c.a_colptr.as<uint32_t>(), N);
+        if (csc != columns() && Z > 0) ELBA_HIP(hipMemcpyAsync(c.a_csc.p, csc, (size_t)Z * 8, hipMemcpyDeviceToDevice, s));
+        maxpos = pre ? c.pre.maxpos : 0;
+        if (Z > 0 && !pre) {
+            c.ws_scan.reserve(64);
+            ELBA_HIP(hipMemsetAsync(c.ws_scan.p, 0, 8, s));
+            hipLaunchKernelGGL(k_max_low32, dim3(std::min(blocks(Z), 2048u)), dim3(256), 0, s, columns(), Z, c.ws_scan.as<unsigned long long>());
+            ELBA_HIP(hipMemcpyAsync(&maxpos, c.ws_scan.p, 8, hipMemcpyDeviceToHost, s));
+            ELBA_HIP(hipStreamSynchronize(s));
+        }
+        ELBA_REQUIRE(win_lo >= 0 && (win_hi < 0 || (win_lo <= win_hi && win_hi <= M)), ELBA_ERR_INVALID_ARG, "bad row window");
+        windowed = !(win_lo == 0 && (win_hi < 0 || win_hi == M));
+        wlo = (uint32_t)win_lo; whi = (uint32_t)(win_hi < 0 ? M : win_hi);
+        c.ws_a.reserve((size_t)(Z + 1) * 8); c.ws_c.reserve((size_t)(Z + 1) * 8);      // (the CSR sort's buffers)
+        c.prod_ctr.reserve(64 * 128);
+        if (!pre) ELBA_HIP(hipMemsetAsync(prod_ctr(), 0, 64 * 128, s));      // (pre: the producer has counted)
+    }
+    // the column store, unless the producer chose and filled it (the two-level partition of kmer_msd.hip writes the padded columns with the columns themselves)
+    void column_store()
+    {
+        if (pre && c.pre.ell_done) return;
+        c.max_col_nnz = max_segment_len(c, colptr(), N);
         choose_column_store(c, N, c.max_col_nnz);
     }
-    c.csr_suffix = c.use_ell && c.pos16 && c.max_col_nnz > 16 && !c.opt.no_pay && !c.opt.no_suffix;
-    if (c.csr_suffix && windowed && N > 0) {
-        c.col_w0.reserve((size_t)N + 16);
-        hipLaunchKernelGGL(k_col_w0, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, (const uint32_t *)c.a_colptr.as<uint32_t>(), (const uint64_t *)c.a_csc.as<uint64_t>(), (uint64_t)N, wlo, c.col_w0.as<uint8_t>());
-        colw0 = c.col_w0.as<uint8_t>();
+    void plan()
+    {
+        CsrBuildInput in;
+        in.M = M; in.N = N; in.Z = Z; in.maxpos = maxpos; in.windowed = windowed; in.use_ell = c.use_ell; in.ell_compact = c.ell_compact; in.max_col = c.max_col_nnz;
+        in.pre = pre ? &c.pre : nullptr; in.opt = csr_options(c);
+        p = plan_csr_build(in);
     }
-    if (!(pre && c.pre_ell_done) && c.use_ell) {
-        const uint64_t nslots = (uint64_t)N * c.s_stride;
-        hipLaunchKernelGGL(k_fill_ell, dim3((unsigned)std::min<uint64_t>((nslots / 2 + 255) / 256, 1ull << 30)), dim3(256), 0, s, c.a_colptr.as<uint32_t>(), c.a_csc.as<uint64_t>(), nslots, c.s_stride, c.a_ell.as<uint64_t>(), colw0);
-    }
-    if (c.csr_suffix) {
-        hints = false;
-        c.j_shift = c.max_col_nnz <= 32 ? 5u : 6u;      // (use_ell: no column longer than 64)
-    }
-    c.csr_one_word = !c.csr_suffix && mb + nb + pb + 2 <= 64 && !c.opt.csr_pairs;      // (diagnostic: which of the two CSR sorts builds the rows)
-    if (c.csr_one_word) {
-        const bool have_words = pre && c.pre_words && c.pre_nb == nb && c.pre_pb == pb;
-        uint64_t *w0 = have_words ? c.csr_words.as<uint64_t>() : c.ws_a.as<uint64_t>(), *w1 = c.ws_c.as<uint64_t>();
-        ELBA_REQUIRE(!pre || have_words, ELBA_ERR_INTERNAL, "create_kmer_matrix: the sort keys of the k-mer stage do not match the matrix");
-        int rs = have_words ? c.pre_rs : nb + pb + 2, pbi = have_words ? c.pre_pbi : 0;
-        // inline partners for a matrix that did not come from the k-mer stage of this context (triples, a panel of the sharded build): the keys are
-        // written here.  The rule they follow is the parity rule over ALL rows — what a whole matrix uses, and a shard when the mirror exchange
-        // assigns every pair of the job to one of its two rows (elba_seed_matrix_send / _begin); a windowed matrix gets them only on request
-        // (option "panel_inline") and can then not be multiplied without the exchange.
-        bool inl_here = false;
-        if (!have_words && hints && c.use_ell && c.pos16 && !c.opt.no_pay && !c.opt.no_inline && !c.opt.no_symmetry && (!windowed || c.opt.panel_inline) && N < (1ll << 31) && mb >= 2) {
-            const int rs2 = 63 - mb, pbi2 = std::min(pb, (rs2 - (mb - 1)) / 2);
-            if (rs2 >= nb + pb + 2 && pbi2 >= 10) { rs = rs2; pbi = pbi2; inl_here = true; }
+    // A dense matrix with a row window (a shard, a row block of a shard: elba_dist_set_panel): the padded columns are stored rotated (k_col_w0) so that a
+    // row entry's owned candidates stay the column's entries behind its own.  Then the padded columns themselves.
+    void fill_columns()
+    {
+        if (p.suffix && windowed && N > 0) {
+            c.col_w0.reserve((size_t)N + 16);
+            hipLaunchKernelGGL(k_col_w0, dim3(blocks(N)), dim3(256), 0, s, colptr(), columns(), (uint64_t)N, wlo, c.col_w0.as<uint8_t>());
+            colw0 = c.col_w0.as<uint8_t>();
         }
-        if (Z > 0 && !have_words)
-            hipLaunchKernelGGL(k_csc_to_csr_words, dim3((unsigned)((Z + 255) / 256)), dim3(256), 0, s, kid_keys, kid_shift, (const uint32_t *)c.a_colptr.as<uint32_t>(), (const uint64_t *)c.a_csc.as<uint64_t>(), Z, nb, pb, rs, inl_here ? pbi : 0, w0,
-                               hints, wlo, whi, prod_ctr);
-        // (sort keys of the k-mer stage's sort path: they left room for inline partners — whether the matrix qualifies is known here)
-        const bool inl_late = have_words && hints && !c.pre_hints_done && c.pre_inline_pending && c.use_ell && !c.csr_suffix && c.pos16 && !windowed;
-        if (Z > 0 && have_words && hints && !c.pre_hints_done)
-            hipLaunchKernelGGL(k_add_hints, dim3((unsigned)((Z + 255) / 256)), dim3(256), 0, s, (const uint32_t *)c.a_colptr.as<uint32_t>(), (const uint64_t *)c.a_csc.as<uint64_t>(), Z, nb, pb, rs, inl_late ? pbi : 0, w0);
-        // (gather slots, kmer_msd.hip: the id field of a key may hold a slot beyond the last k-mer id — slots are drawn in chunks — and is as wide as
-        //  the key leaves room below the read)
-        const int idbits = have_words && c.ell_compact ? std::min(32, rs - pb - 2) : nb;
-        const int pbi_used = (have_words && c.pre_inline) || inl_here || inl_late ? pbi : 0;
-        if (Z > 0 && M > 0 && c.opt.tune[1] != 1) {
+        if (!(pre && c.pre.ell_done) && c.use_ell) {
+            const uint64_t nslots = (uint64_t)N * c.s_stride;
+            hipLaunchKernelGGL(k_fill_ell, dim3((unsigned)std::min<uint64_t>((nslots / 2 + 255) / 256, 1ull << 30)), dim3(256), 0, s, colptr(), columns(), nslots, c.s_stride, c.a_ell.as<uint64_t>(), colw0);
+        }
+    }
+    void require_match() const
+    {
+        ELBA_REQUIRE(p.mismatch != CSR_WORDS_DO_NOT_MATCH, ELBA_ERR_INTERNAL, "create_kmer_matrix: the sort keys of the k-mer stage do not match the matrix");
+        ELBA_REQUIRE(p.mismatch != CSR_PAIRS_NOT_DENSE, ELBA_ERR_INTERNAL, "create_kmer_matrix: the k-mer stage wrote the pairs of a dense matrix, the matrix is not one");
+    }
+    // ONE word per entry, sorted on the read bits (stable: rows come out ordered by (kid, pos)).  The keys are the hand-off's (hint bits and inline
+    // partners added where it left them out) or written here.
+    void build_one_word()
+    {
+        uint64_t *w0 = p.have_words ? c.csr_words.as<uint64_t>() : c.ws_a.as<uint64_t>(), *w1 = c.ws_c.as<uint64_t>();
+        if (p.write_words)
+            hipLaunchKernelGGL(k_csc_to_csr_words, dim3(blocks(Z)), dim3(256), 0, s, kid_keys, kid_shift, colptr(), columns(), Z, p.nb, p.pb, p.rs, p.write_pbi, w0, p.hints, wlo, whi, prod_ctr());
+        if (p.add_hints) hipLaunchKernelGGL(k_add_hints, dim3(blocks(Z)), dim3(256), 0, s, colptr(), columns(), Z, p.nb, p.pb, p.rs, p.add_pbi, w0);
+        if (p.fin_sort) {
             // the sort's last pass writes the rows themselves and their pointers (prims.hip: k_rs_scatter<FIN>): no pass over the sorted keys behind it
             // (round 4: k_unpack_csr_words read and wrote all of them once more — 1.9 ms of the 10 ms CSR build of BASELINE config 3)
-            const CsrFin fin{idbits, pb, rs, mb, pbi_used, c.a_csr.as<uint64_t>(), c.a_rowptr.as<uint32_t>(), M};
-            radix_sort_keys_to_csr(s, w0, w1, Z, fin, c.ws_sort);
+            radix_sort_keys_to_csr(s, w0, w1, Z, CsrFin{p.idbits, p.pb, p.rs, p.mb, p.pbi_used, c.a_csr.as<uint64_t>(), c.a_rowptr.as<uint32_t>(), M}, c.ws_sort);
         } else {
-        const int where = radix_sort_keys(s, w0, w1, Z, rs, rs + mb, c.ws_sort);
-        const uint64_t *sorted = where ? w1 : w0;
-        hipLaunchKernelGGL(k_unpack_csr_words, dim3((unsigned)((Z + 1 + 255) / 256)), dim3(256), 0, s, sorted, Z, idbits, pb, rs, mb, pbi_used, c.a_csr.as<uint64_t>(), c.a_rowptr.as<uint32_t>(), M);
+            const int where = radix_sort_keys(s, w0, w1, Z, p.rs, p.rs + p.mb, c.ws_sort);
+            hipLaunchKernelGGL(k_unpack_csr_words, dim3(blocks(Z + 1)), dim3(256), 0, s, (const uint64_t *)(where ? w1 : w0), Z, p.idbits, p.pb, p.rs, p.mb, p.pbi_used, c.a_csr.as<uint64_t>(), c.a_rowptr.as<uint32_t>(), M);
         }
-        c.csr_inline = (have_words && c.pre_inline) || inl_here || inl_late;
-        c.csr_inline_window = inl_here && windowed;
-    } else {
-        const bool pre_pairs = pre && c.pre_pairs;           // (kmer_msd.hip has written the pairs of a dense matrix: keys in ws_b, values where the sort must start to end in a_csr)
-        ELBA_REQUIRE(!pre || !c.pre_words || c.csr_suffix || pre_pairs, ELBA_ERR_INTERNAL, "create_kmer_matrix: the sort keys of the k-mer stage do not match the matrix");
-        ELBA_REQUIRE(!pre_pairs || c.csr_suffix, ELBA_ERR_INTERNAL, "create_kmer_matrix: the k-mer stage wrote the pairs of a dense matrix, the matrix is not one");
-        const bool kid_in_words = pre && c.pre_words && !pre_pairs;        // (k_runs_emit left sort keys, not column ids: the k-mer id is a field of the word)
-        // the sorted values are the rows of A: the sort's buffers are handed over so that it ENDS in a_csr (no copy behind it)
+    }
+    // (read, entry) pairs, row ids as 32-bit keys (12 bytes per pair and pass).  The sorted values are the rows of A: the sort's buffers are handed over so
+    // that it ENDS in a_csr (no copy behind it).  The pairs are the hand-off's (a dense matrix from kmer_msd.hip) or written here.
+    void build_pairs()
+    {
         c.ws_b.reserve((size_t)(Z + 1) * 8); c.ws_d.reserve((size_t)(Z + 1) * 8);
-        const bool ends_in_second = radix_sort_where(Z, 0, mb) != 0;
-        // (row ids as 32-bit keys: 12 bytes per pair and pass)
-        uint32_t *k0 = pre_pairs ? c.ws_b.as<uint32_t>() : c.ws_a.as<uint32_t>(), *k1 = pre_pairs ? c.ws_a.as<uint32_t>() : c.ws_c.as<uint32_t>();
-        uint64_t *spare = pre_pairs ? c.ws_d.as<uint64_t>() : c.ws_b.as<uint64_t>();
-        uint64_t *v0 = ends_in_second ? spare : c.a_csr.as<uint64_t>(), *v1 = ends_in_second ? c.a_csr.as<uint64_t>() : spare;
-        const uint64_t *kk = pre_pairs ? v0 : kid_in_words ? c.csr_words.as<uint64_t>() : kid_keys;      // (pairs that must be written again — a row window rotates the columns —: the k-mer id is the value's upper half)
-        const int ks = pre_pairs ? 32 : kid_in_words ? c.pre_pb + 2 : kid_shift;
-        const uint64_t km = pre_pairs ? 0xFFFFFFFFull : kid_in_words ? (1ull << c.pre_nb) - 1 : ~0ull;
-        if (Z > 0 && !(pre_pairs && !windowed)) {
-            int64_t nbk = (Z + 255) / 256;
-            if (pre) ELBA_HIP(hipMemsetAsync(prod_ctr, 0, 64 * 128, s));
-            hipLaunchKernelGGL(k_csc_to_csr_keys, dim3((unsigned)nbk), dim3(256), 0, s, kk, ks, km, (const uint32_t *)c.a_colptr.as<uint32_t>(), (const uint64_t *)c.a_csc.as<uint64_t>(), Z, k0, v0,
-                               hints, c.csr_suffix, wlo, whi, prod_ctr, colw0);
+        const bool ends_in_second = radix_sort_where(Z, 0, p.mb) != 0;
+        uint32_t *k0 = ws(p.k0).as<uint32_t>(), *k1 = ws(p.k1).as<uint32_t>();
+        uint64_t *spare = ws(p.spare).as<uint64_t>(), *v0 = ends_in_second ? spare : c.a_csr.as<uint64_t>(), *v1 = ends_in_second ? c.a_csr.as<uint64_t>() : spare;
+        if (p.rewrite_pairs) {
+            const uint64_t *kk = p.key_source == CSR_KEYS_VALUES ? v0 : p.key_source == CSR_KEYS_WORDS ? c.csr_words.as<uint64_t>() : kid_keys;
+            if (p.recount) ELBA_HIP(hipMemsetAsync(prod_ctr(), 0, 64 * 128, s));
+            hipLaunchKernelGGL(k_csc_to_csr_keys, dim3(blocks(Z)), dim3(256), 0, s, kk, p.key_source == CSR_KEYS_CALLER ? kid_shift : p.key_shift, p.key_mask, colptr(), columns(), Z, k0, v0,
+                               p.hints, p.suffix, wlo, whi, prod_ctr(), colw0);
         }
-        const int where = radix_sort_pairs_k32(s, k0, v0, k1, v1, Z, 0, mb, c.ws_sort);
+        const int where = radix_sort_pairs_k32(s, k0, v0, k1, v1, Z, 0, p.mb, c.ws_sort);
         ELBA_REQUIRE((where != 0) == ends_in_second, ELBA_ERR_INTERNAL, "create_kmer_matrix: the CSR sort ended in the other buffer");
         group_offsets_k32(s, where ? k1 : k0, Z, c.a_rowptr.as<uint32_t>(), M);
     }
-    c.csr_hints = hints;
+    // the window's products (what the SpGEMM reports), counted on 64 counters by the kernel that saw every entry's column
+    void read_product_count()
     {
         unsigned long long hp[64 * 16];
-        ELBA_HIP(hipMemcpyAsync(hp, prod_ctr, sizeof(hp), hipMemcpyDeviceToHost, s));
+        ELBA_HIP(hipMemcpyAsync(hp, prod_ctr(), sizeof(hp), hipMemcpyDeviceToHost, s));
         ELBA_HIP(hipStreamSynchronize(s));
         c.A_products = 0;
         for (int q = 0; q < 64; ++q) c.A_products += (int64_t)hp[q * 16];
     }
-    c.row_lo = win_lo; c.row_hi = win_hi;
-    // a new matrix: the tier queues and the tier / sort usage of the previous one are forgotten.  The OUTPUT capacity is kept as a guess (the
-    // buffers exist): the first SpGEMM call on this matrix then runs without a host round trip in its middle and checks afterwards that
-    // everything fitted (spgemm.hip repeats the call on the synchronising path otherwise)
-    c.ov_tiers_known = false; c.ov_sort_used[0] = c.ov_sort_used[1] = true;
-    c.ov_prior_q16 = 0;            // a new matrix: forget the partner/product ratio measured on the previous one
-    c.ov_slab_q16 = 0;
-    c.ov_phase = 0;                // ... and a sharded call that was begun on the previous one
-    c.max_row_nnz = max_segment_len(c, c.a_rowptr.as<uint32_t>(), M);
+    // A new matrix: the tier queues and the tier / sort usage of the previous one are forgotten.  The OUTPUT capacity is kept as a guess (the buffers
+    // exist): the first SpGEMM call on this matrix then runs without a host round trip in its middle and checks afterwards that everything fitted
+    // (spgemm.hip repeats the call on the synchronising path otherwise)
+    void forget_previous_matrix()
     {
-        ELBA_REQUIRE(c.fbits < 31 && (uint64_t)c.max_row_nnz < (1ull << (32 - c.fbits)), ELBA_ERR_UNSUPPORTED,
-                     "row nnz x column nnz exceeds the 32-bit product sequence number");
+        c.ov_tiers_known = false; c.ov_sort_used[0] = c.ov_sort_used[1] = true;
+        c.ov_prior_q16 = 0;            // forget the partner/product ratio measured on the previous one
+        c.ov_slab_q16 = 0;
+        c.ov_phase = 0;                // ... and a sharded call that was begun on the previous one
+    }
+    void longest_row()
+    {
+        c.max_row_nnz = max_segment_len(c, c.a_rowptr.as<uint32_t>(), M);
+        ELBA_REQUIRE(c.fbits < 31 && (uint64_t)c.max_row_nnz < (1ull << (32 - c.fbits)), ELBA_ERR_UNSUPPORTED, "row nnz x column nnz exceeds the 32-bit product sequence number");
     }
     // Dense matrices: a row meets the same ~100 partners tens of thousands of times, and what its accumulator pays for is every look-up that
     // does not find its partner in the slot its hash names (it queues for the general insert: profiles/r03_notes.md).  Partner ids are random
@@ -444,22 +405,54 @@ void finish_matrix_from_sorted_csc(Ctx &c, int64_t M, int64_t N, int64_t Z, cons
     // sorted by minimizer give every read a LABEL (its rank); a row's partners are then a handful of runs of consecutive labels, which the
     // multiplicative hash keeps apart (config 5 / 25: 10.1 -> 9.7 ms).  The partner store of the dense path (a_ellj) holds labels, the
     // table is keyed by them, and the kernel turns the few surviving partners back into rows when it writes them.
-    c.have_row_order = false;
-    if (c.csr_suffix && !c.opt.no_row_order && M > 1 && Z > 0) {
-        c.row_order.reserve((size_t)M * 4 + 64); c.row_label.reserve((size_t)M * 4 + 64);
-        c.row_keys.reserve((size_t)(M + 1) * 16);
-        uint64_t *k0 = c.row_keys.as<uint64_t>(), *k1 = k0 + (M + 1);
-        hipLaunchKernelGGL(k_row_minimizer, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, (const uint32_t *)c.a_rowptr.as<uint32_t>(), (const uint64_t *)c.a_csr.as<uint64_t>(), (uint32_t)M, (uint64_t)N, k0);
-        const int where = radix_sort_keys(s, k0, k1, M, 32, 32 + bits_for((uint64_t)(N > 0 ? N : 1)), c.ws_sort);
-        hipLaunchKernelGGL(k_order_and_labels, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, (const uint64_t *)(where ? k1 : k0), (uint32_t)M, c.row_order.as<uint32_t>(), c.row_label.as<uint32_t>());
-        c.have_row_order = true;
+    void row_order_and_partners()
+    {
+        if (p.row_order) {
+            c.row_order.reserve((size_t)M * 4 + 64); c.row_label.reserve((size_t)M * 4 + 64);
+            c.row_keys.reserve((size_t)(M + 1) * 16);
+            uint64_t *k0 = c.row_keys.as<uint64_t>(), *k1 = k0 + (M + 1);
+            hipLaunchKernelGGL(k_row_minimizer, dim3(blocks(M)), dim3(256), 0, s, (const uint32_t *)c.a_rowptr.as<uint32_t>(), (const uint64_t *)c.a_csr.as<uint64_t>(), (uint32_t)M, (uint64_t)N, k0);
+            const int where = radix_sort_keys(s, k0, k1, M, 32, 32 + bits_needed((uint64_t)(N > 0 ? N : 1)), c.ws_sort);
+            hipLaunchKernelGGL(k_order_and_labels, dim3(blocks(M)), dim3(256), 0, s, (const uint64_t *)(where ? k1 : k0), (uint32_t)M, c.row_order.as<uint32_t>(), c.row_label.as<uint32_t>());
+        }
+        if (p.suffix) {
+            const uint64_t nslots = (uint64_t)N << p.j_shift;
+            c.a_ellj.reserve((size_t)nslots * 4 + 64);
+            hipLaunchKernelGGL(k_ell_partners, dim3((unsigned)std::min<uint64_t>((nslots / 4 + 255) / 256, 1ull << 20)), dim3(256), 0, s, windowed ? (const uint64_t *)c.a_ell.as<uint64_t>() : (const uint64_t *)nullptr, columns(), colptr(), (uint64_t)N, c.s_stride,
+                               p.j_shift, c.a_ellj.as<uint32_t>(), p.row_order ? (const uint32_t *)c.row_label.as<uint32_t>() : (const uint32_t *)nullptr);
+        }
     }
-    if (c.csr_suffix) {
-        const uint64_t nslots = (uint64_t)N << c.j_shift;
-        c.a_ellj.reserve((size_t)nslots * 4 + 64);
-        hipLaunchKernelGGL(k_ell_partners, dim3((unsigned)std::min<uint64_t>((nslots / 4 + 255) / 256, 1ull << 20)), dim3(256), 0, s, windowed ? (const uint64_t *)c.a_ell.as<uint64_t>() : (const uint64_t *)nullptr, (const uint64_t *)c.a_csc.as<uint64_t>(), (const uint32_t *)c.a_colptr.as<uint32_t>(), (uint64_t)N, c.s_stride,
-                           c.j_shift, c.a_ellj.as<uint32_t>(), c.have_row_order ? (const uint32_t *)c.row_label.as<uint32_t>() : (const uint32_t *)nullptr);
+    // the format of the resident A, for everything that reads it
+    void publish_format(int64_t win_lo, int64_t win_hi)
+    {
+        c.pos16 = p.pos16; c.csr_hints = p.hints; c.csr_suffix = p.suffix; c.csr_one_word = p.one_word;
+        c.csr_inline = p.inl != CSR_INL_NONE; c.csr_inline_window = p.inline_window;
+        if (p.suffix) c.j_shift = p.j_shift;
+        c.have_row_order = p.row_order;
+        c.row_lo = win_lo; c.row_hi = win_hi;
     }
+};
+
+}  // namespace
+
+// Input: Z entries sorted by (kid, read, pos): kid_keys[z] >> kid_shift = kid, csc[z] = read<<32|pos (device, in c.a_csc or elsewhere).
+// Produces c.a_colptr, c.a_csc (copy if csc is not already c.a_csc), c.a_rowptr, c.a_csr, max_row_nnz, max_col_nnz.
+// [win_lo, win_hi) = the rows of B this context computes (win_hi < 0: all); the product schedule is laid out for those rows only.
+// pre: the hand-off of the k-mer stage (Ctx::pre) is this matrix's.  Every decision is plan_csr_build's (csr_plan.hpp); the steps launch what it says.
+void finish_matrix_from_sorted_csc(Ctx &c, int64_t M, int64_t N, int64_t Z, const uint64_t *kid_keys, int kid_shift, const uint64_t *csc, int64_t win_lo, int64_t win_hi, bool pre)
+{
+    CsrBuild b{c, M, N, Z, kid_keys, kid_shift, pre};
+    b.size_and_maxpos(csc, win_lo, win_hi);
+    b.column_store();
+    b.plan();
+    b.fill_columns();
+    b.require_match();
+    if (b.p.one_word) b.build_one_word(); else b.build_pairs();
+    b.read_product_count();
+    b.forget_previous_matrix();
+    b.longest_row();
+    b.row_order_and_partners();
+    b.publish_format(win_lo, win_hi);
 }
 
 namespace {
@@ -529,12 +522,12 @@ static void set_kmer_matrix_from_pairs(Ctx &c, int64_t M, int64_t N, int64_t Z, 
     hipStream_t s = c.stream;
     uint64_t *k0 = c.ws_a.as<uint64_t>(), *v0 = c.ws_b.as<uint64_t>(), *k1 = c.ws_c.as<uint64_t>(), *v1 = c.ws_d.as<uint64_t>();
     // (1) by pos, (2) by row, (3) by col — LSD, stable: final order (col, row, pos)
-    int w = radix_sort_pairs(s, k0, v0, k1, v1, Z, 0, bits_for(maxpos), c.ws_sort);
+    int w = radix_sort_pairs(s, k0, v0, k1, v1, Z, 0, bits_needed(maxpos), c.ws_sort);
     // swap roles: key := (col<<32|row), value := pos
     uint64_t *ck = w ? v1 : v0, *cv = w ? k1 : k0, *ok = w ? v0 : v1, *ov = w ? k0 : k1;
-    int w2 = radix_sort_pairs(s, ck, cv, ok, ov, Z, 0, bits_for((uint64_t)(M > 0 ? M - 1 : 0)), c.ws_sort);
+    int w2 = radix_sort_pairs(s, ck, cv, ok, ov, Z, 0, bits_needed((uint64_t)(M > 0 ? M - 1 : 0)), c.ws_sort);
     if (w2) { uint64_t *t; t = ck; ck = ok; ok = t; t = cv; cv = ov; ov = t; }
-    int w3 = radix_sort_pairs(s, ck, cv, ok, ov, Z, 32, 32 + bits_for((uint64_t)(N > 0 ? N - 1 : 0)), c.ws_sort);
+    int w3 = radix_sort_pairs(s, ck, cv, ok, ov, Z, 32, 32 + bits_needed((uint64_t)(N > 0 ? N - 1 : 0)), c.ws_sort);
     if (w3) { uint64_t *t; t = ck; ck = ok; ok = t; t = cv; cv = ov; ov = t; }
     // ck = (col<<32|row) sorted, cv = pos.  Move the keys out of the ws_a..d pool (finish_* reuses it).
     uint64_t *keys = c.ws_e.as<uint64_t>();
@@ -567,7 +560,7 @@ void stage_set_kmer_matrix_device(Ctx &c, int64_t M, int64_t N, int64_t Z, const
         c.triples_path = 1;
         c.A_has_kmers = false;
         finish_matrix_from_sorted_csc(c, M, N, Z, nullptr, 0, c.a_csc.as<uint64_t>(), 0, -1, true);
-        c.pre_ready = false; c.pre_consumed = true;
+        c.pre.consume();
         done(c.v, EV_SET_KMER_MATRIX_DEVICE);
         return;
     }
@@ -582,7 +575,7 @@ void stage_set_kmer_matrix_device(Ctx &c, int64_t M, int64_t N, int64_t Z, const
     c.ws_e.reserve((size_t)(Z + 1) * 8); c.ws_f.reserve((size_t)(Z + 1) * 8);
     // k-mer id, read and position in ONE 64-bit word when they fit (28 + 18 + 14 bits on the 200 k-read set): one sort of 8-byte keys over
     // all their bits instead of three stable sorts of 16-byte (key, value) pairs — 7 passes of ~3 ms instead of 8 of ~7 ms there
-    const int mb = bits_for((uint64_t)(M > 0 ? M - 1 : 0)), nb = bits_for((uint64_t)(N > 0 ? N - 1 : 0)), pb = bits_for(chk[1]);
+    const int mb = bits_needed((uint64_t)(M > 0 ? M - 1 : 0)), nb = bits_needed((uint64_t)(N > 0 ? N - 1 : 0)), pb = bits_needed(chk[1]);
     if (mb + nb + pb <= 64 && Z > 0 && !c.opt.csr_pairs) {
         uint64_t *w0 = c.ws_a.as<uint64_t>(), *w1 = c.ws_b.as<uint64_t>();
         hipLaunchKernelGGL(k_pack_triple_words, dim3(nbz), dim3(256), 0, s, d_rows, d_cols, d_vals, Z, mb, pb, w0);
@@ -609,7 +602,7 @@ void stage_export_triples_device(Ctx &c, int64_t *d_rows, int64_t *d_cols, uint3
     } else if (c.M > 0 && c.Z > 0) {
         int nb = (int)std::min<int64_t>((c.M + 3) / 4, (int64_t)c.num_cus * 32);
         hipLaunchKernelGGL(k_export_triples, dim3(nb), dim3(256), 0, c.stream, (const uint32_t *)c.a_rowptr.as<uint32_t>(), (const uint64_t *)c.a_csr.as<uint64_t>(), (uint32_t)c.M,
-                           c.csr_suffix ? 0xFFFFu : (c.csr_hints ? 0x3FFFFFFFu : 0xFFFFFFFFu), d_rows, d_cols, d_vals);
+                           csr_pos_mask(c.csr_suffix, c.csr_hints), d_rows, d_cols, d_vals);
     }
     ELBA_HIP(hipStreamSynchronize(c.stream));
 }

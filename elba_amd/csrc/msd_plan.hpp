@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <vector>
+#include "csr_plan.hpp"      // bits_needed_u; the layout of the CSR sort keys the stage's emit kernels write
 
 namespace elba {
 
@@ -20,13 +21,6 @@ constexpr int W2_MAXBITS = 10;
 constexpr uint32_t HINT_MAX_COL = 12;     // longer columns are not examined: a row owns no pair of an L-read column with probability 2^-(L-1), and the test costs L loads
 constexpr uint32_t ES_CAP_MAX = 12288;      // entries of a bucket the widest emit kernel sorts in LDS
 constexpr uint64_t MSD_PASS_LIMIT = 0xFFFFFFF0ull;      // a pass (or an unbatched input) holds fewer instances: 32-bit places
-
-inline int bits_needed_u(uint64_t maxval)
-{
-    int b = 1;
-    while (b < 64 && (maxval >> b)) ++b;
-    return b;
-}
 
 // the options msd_run's decisions read (Ctx::opt's, by name)
 struct MsdOptions { int kmer_msd = 0, msd_wide_bits = 0, msd_rank = 0, msd_no_rank = 0, msd_small_cap = 0; long long kmer_batch_instances = 0; };

@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <cstddef>
 #include <cstdint>
+#include "csr_plan.hpp"      // the format of a row entry of A (csr_pos_mask)
 
 namespace elba {
 
@@ -23,7 +24,7 @@ constexpr size_t OV_LDS_MAX = 160 * 1024;
 // what the reads-path instantiation of the numeric kernel fixes at compile time (OvSpecParams takes them from here)
 namespace ov_spec {
 constexpr uint32_t half = 1, inl = 1, pay16 = 1, rec16 = 1, suffix = 0, qblk_log2 = 0, j_shift = 0;
-constexpr uint32_t hint_mask = 1u << 31, pos_mask = 0x3FFFFFFFu;
+constexpr uint32_t hint_mask = 1u << 31, pos_mask = csr_pos_mask(false, true);
 // ... and what its compiled-geometry variant fixes on top: columns padded to ONE 64-byte line (8 entries: every matrix whose longest column holds 5 .. 8
 // entries, matrix.hip: choose_column_store), four lanes x 16 bytes per row entry, 3 bits of a sequence number for the place in the column
 constexpr uint32_t geom_stride = 8, geom_lpc_log2 = 2, geom_fbits = 3;
@@ -243,7 +244,7 @@ inline void ov_plan_switches(const OvInput &in, OvPlan &p)
     const int64_t Z = in.Z, nrows = p.nrows;
     p.max_col = (uint32_t)(in.max_col_nnz > 0 ? in.max_col_nnz : 1);
     p.half = in.phase >= 1 ? 2u : (ov_one_triangle(in) ? 1u : 0u);      // 2: a pair is accumulated on ONE of its two rows wherever the other row lives (its rank gets the mirrored entry by exchange)
-    p.pos_mask = in.csr_suffix ? 0xFFFFu : (in.csr_hints ? 0x3FFFFFFFu : 0xFFFFFFFFu);
+    p.pos_mask = csr_pos_mask(in.csr_suffix, in.csr_hints);
     p.hint_mask = !in.csr_hints ? 0u : (p.half == 2u ? 1u << 30 : (p.half == 1u ? 1u << 31 : 0u));
     // (the dense path: one triangle per window, partners outside the window kept — its candidate hand-out knows no other rule.  Both triangles
     //  ("no_symmetry") and the mirror exchange between ranks (half == 2: the parity rule over all ranks) take the general path, which reads the

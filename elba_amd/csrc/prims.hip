@@ -346,12 +346,7 @@ __global__ __launch_bounds__(THREADS, (THREADS == 512 ? 4 : 0)) void k_rs_scatte
             const uint32_t read = (uint32_t)((w >> fin.rs) & rmask);
             if (t == lstart[d]) atomicMin(&fin.rowptr[read], dst);
             else if ((uint32_t)(((uint64_t)lkey[t - 1] >> fin.rs) & rmask) != read) fin.rowptr[read] = dst;
-            uint64_t e;
-            if (fin.pbi && (w >> 63)) {      // inline partner (Ctx::csr_inline): flag | partner >> 1 | posQ | posT << 16.  (Without inline partners — pbi 0 — bit 63 is the read's top bit when read, k-mer id, hints and position fill all 64)
-                const uint64_t pm = (1ull << fin.pbi) - 1;
-                e = (1ull << 63) | (((w >> (2 * fin.pbi)) & ((1ull << (fin.mb - 1)) - 1)) << 32) | ((w >> fin.pbi) & pm) | ((w & pm) << 16);
-            } else e = (((w >> (fin.pb + 2)) & ((1ull << fin.idbits) - 1)) << 32) | (((w >> fin.pb) & 3ull) << 30) | (w & ((1ull << fin.pb) - 1));
-            fin.csr[dst] = e;
+            fin.csr[dst] = csr_entry_of_word(w, fin.idbits, fin.pb, fin.mb, fin.pbi);      // (an inline partner, Ctx::csr_inline, or kid | hint | pos: csr_plan.hpp)
         } else {
         keys_out[dst] = k;
         if (HAS_VAL) vals_out[dst] = lval[t];
