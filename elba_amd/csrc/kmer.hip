@@ -14,12 +14,21 @@
 //                             run writes its entry (read, pos) — that IS the CSC of A, columns already sorted — and the entry's one-word
 //                             sort key for the CSR build.  (UPPER > 62 or pairs: k_runs<true> + k_instance_entries.)
 //   Multi-word k-mers (k > 31): k_kmer_emit2/3, an index permutation sorted last word first, runs compare every word.
+// The host side of elba_count_kmers, step by step (stage_count_kmers; its decisions are plain arithmetic in sort_plan.hpp):
+//   instance_offsets          the host prefix sum over the read lengths, then the refusals, then the upload
+//   one path                  count_long_kmers_in_passes (k > 31 that one pass does not take: long_histograms, plan_long_capacity, cut_long_passes,
+//                             check_long_passes, run_long_pass for every pass, concat_staged), else sort_long_one_pass; k <= 31: msd_count_kmers
+//                             (kmer_msd.hip), else sort_one_word (plan_sort_word)
+//   runs_to_columns           the end of every sort: count_runs (k_runs<false>, three scans), then emit_columns_fused or emit_columns_per_head
+//   finish_count              the statistics and the context's counts, once
+// The multi-word sorts — one pass, every value-range pass, the owner's records (stage_dist_count_records) — share LongSortBufs and sort_long_kmers.
 //
 // Packed k-mer layout (src/Kmer.cpp:67-87): base i at bits 2*(31-i), low 64-2k bits zero; canonical = min(kmer, twin)
 // (src/Kmer.cpp:200-205); position = forward start index (include/KmerOps.hpp:91-103).
 #include <memory>
 #include "common.hpp"
 #include "matrix.hpp"
+#include "sort_plan.hpp"
 
 namespace elba {
 
@@ -429,97 +438,120 @@ EnumParams make_enum(Ctx &c)
 
 }  // namespace
 
+// the instance -> read table of the kernels that walk on from a wavefront's first instance (cursor_at): one entry per 2^IB_SHIFT instances, in ws_b
+static const BlockInfo *block_reads(Ctx &c, const EnumParams &e, uint64_t I)
+{
+    const uint64_t nib = (I >> IB_SHIFT) + 1;
+    c.ws_b.reserve((size_t)(nib + 1) * sizeof(BlockInfo));
+    hipLaunchKernelGGL(k_block_reads, dim3((unsigned)((nib + 255) / 256)), dim3(256), 0, c.stream, e.inst_off, e.byte_off, e.nreads, nib, c.ws_b.as<BlockInfo>());
+    return c.ws_b.as<BlockInfo>();
+}
+
 // Sorted words / (k-mer, value) pairs -> runs -> reliable columns: rel_kmers / rel_counts / a_colptr / a_csc / kid_of_entry of the context
-// (see the comment above k_runs).  ib: payload bits below the value in `skeys` (0: the payload is svals); drop: low bits of the instance
-// index that were cut off the payload.  scratch: at least (Z + 8) u64 (entry payloads), allocated by the caller's pool.
-// base: one value-range pass of the sort of k > 31 (count_long_kmers_in_passes): the column pointers it writes count from the entries of the passes
-// before it, its entries' column ids from their k-mers, and the arrays are allocated at exactly their size (they are staged, then concatenated).
-// The per-head path only (ib == 0).
+// (see the comment above k_runs).
+// SortedRuns: ib = payload bits below the value in `keys` (0: the payload is vals); drop: low bits of the instance index that were cut off the
+// payload; lo, lo2: the further words of multi-word k-mers.
+// ColumnBase: one value-range pass of the sort of k > 31 (count_long_kmers_in_passes): the column pointers it writes count from the entries of the
+// passes before it, its entries' column ids from their k-mers, and the arrays are allocated at exactly their size (they are staged, then
+// concatenated).  The per-head path only (ib == 0).
+struct SortedRuns { const uint64_t *keys = nullptr, *lo = nullptr, *lo2 = nullptr, *vals = nullptr; int ib = 0, drop = 0; };
 struct ColumnBase { uint64_t kid = 0; uint32_t ent = 0; bool exact = false; };
-static void runs_to_columns(Ctx &c, const uint64_t *skeys, const uint64_t *svals, uint64_t I, uint64_t &nruns_out, uint64_t &N_out, uint64_t &Z_out,
-                            const uint64_t *skeys_lo = nullptr, const uint64_t *skeys_lo2 = nullptr, int ib = 0, int drop = 0, ColumnBase base = {})
+struct Columns { uint64_t nruns = 0, N = 0, Z = 0; };
+
+// run lengths = the exact counts (k_runs<false>): per block of RUN_TILE items its reliable runs, their entries and all its runs in blk (three arrays of
+// nblocks + 2), scanned into off_rel, off_ent (the two arrays behind them) and in place; the totals
+static Columns count_runs(Ctx &c, const RunParams &p, uint32_t nblocks, uint32_t *blk_rel)
+{
+    hipStream_t s = c.stream;
+    uint32_t *blk_ent = blk_rel + (nblocks + 2), *blk_heads = blk_ent + (nblocks + 2), *off_rel = blk_heads + (nblocks + 2), *off_ent = off_rel + (nblocks + 2);
+    ELBA_HIP(hipMemsetAsync(blk_rel, 0, (size_t)(nblocks + 2) * 4 * 3, s));
+    hipLaunchKernelGGL((k_runs<false>), dim3(nblocks), dim3(RUN_THREADS), 0, s, p, blk_rel, blk_ent, blk_heads, (const uint32_t *)nullptr, (const uint32_t *)nullptr,
+                       (uint64_t *)nullptr, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, (uint64_t *)nullptr, (uint64_t *)nullptr, 0ull, 0u);
+    exclusive_scan_u32(s, blk_rel, off_rel, (int64_t)nblocks + 1, c.ws_scan);
+    exclusive_scan_u32(s, blk_ent, off_ent, (int64_t)nblocks + 1, c.ws_scan);      // Z <= I < 2^32: the 32-bit scan cannot wrap
+    exclusive_scan_u32(s, blk_heads, blk_heads, (int64_t)nblocks + 1, c.ws_scan);
+    uint32_t h3[3] = {0, 0, 0};
+    ELBA_HIP(hipMemcpyAsync(&h3[0], off_rel + nblocks, 4, hipMemcpyDeviceToHost, s));
+    ELBA_HIP(hipMemcpyAsync(&h3[1], off_ent + nblocks, 4, hipMemcpyDeviceToHost, s));
+    ELBA_HIP(hipMemcpyAsync(&h3[2], blk_heads + nblocks, 4, hipMemcpyDeviceToHost, s));
+    ELBA_HIP(hipStreamSynchronize(s));
+    Columns col;
+    col.N = h3[0]; col.Z = h3[1]; col.nruns = h3[2];
+    return col;
+}
+
+// Packed words with UPPER <= 62: one fused pass writes the columns, the entries' (read, pos) and — when read, k-mer id and position fit one word —
+// the sort keys of the CSR build (k_runs_emit), which it hands over.
+static CsrHandoff emit_columns_fused(Ctx &c, const RunParams &p, int drop, uint32_t nblocks, const uint32_t *off_rel, const uint32_t *off_ent, const Columns &col)
+{
+    hipStream_t s = c.stream;
+    EnumParams e = make_enum(c);
+    const BlockInfo *block_read = block_reads(c, e, p.I);
+    const uint64_t maxpos = reads_maxpos(c.max_read_len, c.cfg.k);      // (a bound: the largest position any entry can have)
+    const int mb = bits_needed((uint64_t)(c.nreads > 0 ? c.nreads - 1 : 0)), nb = bits_needed((uint64_t)(col.N > 0 ? col.N - 1 : 0)), pb = bits_needed(maxpos);
+    // inline partners (Ctx::csr_inline), as kmer_msd.hip: the keys leave room for them — read as high as it goes, pbi position bits — and
+    // the hint pass that sees every entry's column anyway (k_add_hints, matrix.hip) writes them, if the matrix turns out to qualify
+    // (padded columns, not dense: UPPER <= 16 guarantees the latter here, where no column has been seen yet)
+    const CsrKeyLayout lay = csr_key_layout(mb, nb, pb, (int64_t)col.N, csr_options(c), CsrProducer{!c.opt.no_ell, p.upper <= (uint32_t)CSR_SPARSE_MAX_COL, maxpos < 65536, false}, CSR_INLINE_PENDING);
+    c.prod_ctr.reserve(64 * 128);
+    ELBA_HIP(hipMemsetAsync(c.prod_ctr.p, 0, 64 * 128, s));
+    EmitOut o{};
+    o.prod_ctr = c.prod_ctr.as<unsigned long long>();
+    o.rel_kmers = c.rel_kmers.as<uint64_t>(); o.rel_counts = c.rel_counts.as<uint32_t>(); o.colptr = c.a_colptr.as<uint32_t>();
+    o.csc = c.a_csc.as<uint64_t>(); o.kid_of_entry = c.kid_of_entry.as<uint64_t>(); o.nb = nb; o.pb = pb;
+    o.rs = lay.rs;
+    if (lay.words) { c.csr_words.reserve((size_t)(col.Z + 8) * 8); o.csr_words = c.csr_words.as<uint64_t>(); }
+    hipLaunchKernelGGL(k_runs_emit, dim3(nblocks), dim3(RUN_THREADS), 0, s, p, e, block_read, drop, off_rel, off_ent, o);
+    return csr_handoff(lay, nb, pb, maxpos);
+}
+
+// UPPER > 62, multi-word k-mers, pairs: the heads of the reliable runs write k-mers, counts, pointers, the entries' payloads and column ids
+// (k_runs<true>).  Payloads go straight into a_csc when they are final (pairs: read << 32 | pos), else into scratch, and a second kernel converts.
+static void emit_columns_per_head(Ctx &c, const RunParams &p, int drop, uint32_t nblocks, const uint32_t *off_rel, const uint32_t *off_ent, const Columns &col, const ColumnBase &base)
+{
+    hipStream_t s = c.stream;
+    if (p.ib) c.ws_f.reserve((size_t)(col.Z + 8) * 8);
+    uint64_t *pay = p.ib ? c.ws_f.as<uint64_t>() : c.a_csc.as<uint64_t>();
+    if (p.I > 0)
+        hipLaunchKernelGGL((k_runs<true>), dim3(nblocks), dim3(RUN_THREADS), 0, s, p, (uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, off_rel, off_ent,
+                           c.rel_kmers.as<uint64_t>(), p.lo ? c.rel_kmers_lo.as<uint64_t>() : (uint64_t *)nullptr, p.lo2 ? c.rel_kmers_lo2.as<uint64_t>() : (uint64_t *)nullptr,
+                           c.rel_counts.as<uint32_t>(), c.a_colptr.as<uint32_t>(), pay, c.kid_of_entry.as<uint64_t>(), base.kid, base.ent);
+    if (p.ib && col.Z > 0) {
+        EnumParams e = make_enum(c);
+        const BlockInfo *block_read = block_reads(c, e, p.I);
+        hipLaunchKernelGGL(k_instance_entries, dim3((unsigned)((col.Z + 255) / 256)), dim3(256), 0, s, pay, c.kid_of_entry.as<uint64_t>(), c.rel_kmers.as<uint64_t>(), c.a_csc.as<uint64_t>(), col.Z, e, drop,
+                           block_read);
+    }
+}
+
+static Columns runs_to_columns(Ctx &c, const SortedRuns &in, uint64_t I, ColumnBase base = {})
 {
     hipStream_t s = c.stream;
     const uint32_t nblocks = (uint32_t)((I + RUN_TILE - 1) / RUN_TILE);
     c.ws_e.reserve((size_t)(nblocks + 2) * 4 * 5);
-    uint32_t *blk_rel = c.ws_e.as<uint32_t>(), *blk_ent = blk_rel + (nblocks + 2), *blk_heads = blk_ent + (nblocks + 2), *off_rel = blk_heads + (nblocks + 2), *off_ent = off_rel + (nblocks + 2);
+    const uint32_t *off_rel = c.ws_e.as<uint32_t>() + 3 * (nblocks + 2), *off_ent = off_rel + (nblocks + 2);
     RunParams p{};
-    p.keys = skeys; p.lo = skeys_lo; p.lo2 = skeys_lo2; p.vals = svals; p.I = I; p.ib = ib; p.k2 = 2 * c.cfg.k;
+    p.keys = in.keys; p.lo = in.lo; p.lo2 = in.lo2; p.vals = in.vals; p.I = I; p.ib = in.ib; p.k2 = 2 * c.cfg.k;
     p.lower = (uint32_t)c.cfg.lower; p.upper = (uint32_t)c.cfg.upper;
-    uint64_t nruns = 0, N = 0, Z = 0;
-    if (I > 0) {
-        ELBA_HIP(hipMemsetAsync(blk_rel, 0, (size_t)(nblocks + 2) * 4 * 3, s));
-        hipLaunchKernelGGL((k_runs<false>), dim3(nblocks), dim3(RUN_THREADS), 0, s, p, blk_rel, blk_ent, blk_heads, (const uint32_t *)nullptr, (const uint32_t *)nullptr,
-                           (uint64_t *)nullptr, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, (uint64_t *)nullptr, (uint64_t *)nullptr, 0ull, 0u);
-        exclusive_scan_u32(s, blk_rel, off_rel, (int64_t)nblocks + 1, c.ws_scan);
-        exclusive_scan_u32(s, blk_ent, off_ent, (int64_t)nblocks + 1, c.ws_scan);      // Z <= I < 2^32: the 32-bit scan cannot wrap
-        exclusive_scan_u32(s, blk_heads, blk_heads, (int64_t)nblocks + 1, c.ws_scan);
-        uint32_t h3[3] = {0, 0, 0};
-        ELBA_HIP(hipMemcpyAsync(&h3[0], off_rel + nblocks, 4, hipMemcpyDeviceToHost, s));
-        ELBA_HIP(hipMemcpyAsync(&h3[1], off_ent + nblocks, 4, hipMemcpyDeviceToHost, s));
-        ELBA_HIP(hipMemcpyAsync(&h3[2], blk_heads + nblocks, 4, hipMemcpyDeviceToHost, s));
-        ELBA_HIP(hipStreamSynchronize(s));
-        N = h3[0]; Z = h3[1]; nruns = h3[2];
-    }
+    const Columns col = I > 0 ? count_runs(c, p, nblocks, c.ws_e.as<uint32_t>()) : Columns{};
+    const uint64_t N = col.N, Z = col.Z;
     ELBA_REQUIRE(base.ent + Z < 0xFFFFFFF0ull, ELBA_ERR_UNSUPPORTED, "count_kmers: nnz(A) beyond 32-bit device offsets");
     auto res = [&](DevBuf &b, size_t bytes) { if (base.exact) b.reserve_exact(bytes); else b.reserve(bytes); };
     res(c.rel_kmers, (size_t)(N + 1) * 8);
-    if (skeys_lo) res(c.rel_kmers_lo, (size_t)(N + 1) * 8);
-    if (skeys_lo2) res(c.rel_kmers_lo2, (size_t)(N + 1) * 8);
+    if (in.lo) res(c.rel_kmers_lo, (size_t)(N + 1) * 8);
+    if (in.lo2) res(c.rel_kmers_lo2, (size_t)(N + 1) * 8);
     res(c.rel_counts, (size_t)(N + 2) * 4);
     res(c.a_colptr, (size_t)(N + 2) * 4);
     res(c.a_csc, (size_t)(Z + 8) * 8);   // + guard entries (matrix.hip)
     res(c.kid_of_entry, (size_t)(Z + 8) * 8);
-    // Packed words with UPPER <= 62: one fused pass writes the columns, the entries' (read, pos) and — when read, k-mer id and position fit
-    // one word — the sort keys of the CSR build (k_runs_emit).  Otherwise: heads write payloads and column ids, a second kernel converts.
-    CsrHandoff handoff;      // (none, unless the fused pass below leaves the sort keys)
-    const bool fused = ib && p.upper <= 62 && !c.opt.kmer_unfused;
-    if (fused && Z > 0) {
-        EnumParams e = make_enum(c);
-        const uint64_t nib = (I >> IB_SHIFT) + 1;
-        c.ws_b.reserve((size_t)(nib + 1) * sizeof(BlockInfo));
-        hipLaunchKernelGGL(k_block_reads, dim3((unsigned)((nib + 255) / 256)), dim3(256), 0, s, e.inst_off, e.byte_off, e.nreads, nib, c.ws_b.as<BlockInfo>());
-        uint32_t maxlen = 0;
-        for (int64_t r = 0; r < c.nreads; ++r) maxlen = c.h_len[(size_t)r] > maxlen ? c.h_len[(size_t)r] : maxlen;
-        const uint64_t maxpos = maxlen >= (uint32_t)c.cfg.k ? maxlen - (uint32_t)c.cfg.k : 0;      // (a bound: the largest position any entry can have)
-        const int mb = bits_needed((uint64_t)(c.nreads > 0 ? c.nreads - 1 : 0)), nb = bits_needed((uint64_t)(N > 0 ? N - 1 : 0)), pb = bits_needed(maxpos);
-        // inline partners (Ctx::csr_inline), as kmer_msd.hip: the keys leave room for them — read as high as it goes, pbi position bits — and
-        // the hint pass that sees every entry's column anyway (k_add_hints, matrix.hip) writes them, if the matrix turns out to qualify
-        // (padded columns, not dense: UPPER <= 16 guarantees the latter here, where no column has been seen yet)
-        const CsrKeyLayout lay = csr_key_layout(mb, nb, pb, (int64_t)N, csr_options(c), CsrProducer{!c.opt.no_ell, p.upper <= (uint32_t)CSR_SPARSE_MAX_COL, maxpos < 65536, false}, CSR_INLINE_PENDING);
-        c.prod_ctr.reserve(64 * 128);
-        ELBA_HIP(hipMemsetAsync(c.prod_ctr.p, 0, 64 * 128, s));
-        EmitOut o{};
-        o.prod_ctr = c.prod_ctr.as<unsigned long long>();
-        o.rel_kmers = c.rel_kmers.as<uint64_t>(); o.rel_counts = c.rel_counts.as<uint32_t>(); o.colptr = c.a_colptr.as<uint32_t>();
-        o.csc = c.a_csc.as<uint64_t>(); o.kid_of_entry = c.kid_of_entry.as<uint64_t>(); o.nb = nb; o.pb = pb;
-        o.rs = lay.rs;
-        if (lay.words) { c.csr_words.reserve((size_t)(Z + 8) * 8); o.csr_words = c.csr_words.as<uint64_t>(); }
-        hipLaunchKernelGGL(k_runs_emit, dim3(nblocks), dim3(RUN_THREADS), 0, s, p, e, (const BlockInfo *)c.ws_b.as<BlockInfo>(), drop, (const uint32_t *)off_rel, (const uint32_t *)off_ent, o);
-        handoff = csr_handoff(lay, nb, pb, maxpos);
-    } else {
-    // entry payloads: written straight into a_csc when they are final (pairs: read << 32 | pos), else into scratch and converted
-    DevBuf &scratch = c.ws_f;
-    if (ib) scratch.reserve((size_t)(Z + 8) * 8);
-    uint64_t *pay = ib ? scratch.as<uint64_t>() : c.a_csc.as<uint64_t>();
-    if (I > 0)
-        hipLaunchKernelGGL((k_runs<true>), dim3(nblocks), dim3(RUN_THREADS), 0, s, p, (uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, off_rel, off_ent,
-                           c.rel_kmers.as<uint64_t>(), skeys_lo ? c.rel_kmers_lo.as<uint64_t>() : (uint64_t *)nullptr, skeys_lo2 ? c.rel_kmers_lo2.as<uint64_t>() : (uint64_t *)nullptr,
-                           c.rel_counts.as<uint32_t>(), c.a_colptr.as<uint32_t>(), pay, c.kid_of_entry.as<uint64_t>(), base.kid, base.ent);
-    if (ib && Z > 0) {
-        EnumParams e = make_enum(c);
-        const uint64_t nib = (I >> IB_SHIFT) + 1;
-        c.ws_b.reserve((size_t)(nib + 1) * sizeof(BlockInfo));
-        hipLaunchKernelGGL(k_block_reads, dim3((unsigned)((nib + 255) / 256)), dim3(256), 0, s, e.inst_off, e.byte_off, e.nreads, nib, c.ws_b.as<BlockInfo>());
-        hipLaunchKernelGGL(k_instance_entries, dim3((unsigned)((Z + 255) / 256)), dim3(256), 0, s, pay, c.kid_of_entry.as<uint64_t>(), c.rel_kmers.as<uint64_t>(), c.a_csc.as<uint64_t>(), Z, e, drop,
-                           c.ws_b.as<BlockInfo>());
-    }
-    }
+    CsrHandoff handoff;      // (none, unless the fused pass leaves the sort keys)
+    if (in.ib && p.upper <= 62 && !c.opt.kmer_unfused && Z > 0) handoff = emit_columns_fused(c, p, in.drop, nblocks, off_rel, off_ent, col);
+    else emit_columns_per_head(c, p, in.drop, nblocks, off_rel, off_ent, col, base);
     c.pre = handoff;
     const uint32_t Zz = base.ent + (uint32_t)Z;
     ELBA_HIP(hipMemcpyAsync(c.a_colptr.as<uint32_t>() + N, &Zz, 4, hipMemcpyHostToDevice, s));
     ELBA_HIP(hipStreamSynchronize(s));
-    nruns_out = nruns; N_out = N; Z_out = Z;
+    return col;
 }
 
 // Stable LSD sort of n multi-word keys (src[0] most significant) through an index permutation, last word first; `perm` receives the
@@ -538,153 +570,36 @@ static const uint64_t *sort_words_permutation(Ctx &c, int words, const uint64_t 
     return ia;
 }
 
-// The sort of two- and three-word k-mers (stage_count_kmers, and every value-range pass of count_long_kmers_in_passes): the identity permutation i0
-// sorted by the words, then the k-mers' words and values gathered in sorted order into shi / slo / slo2 / sval.  n > 0; i1, t0, t1: n words each.
-static void sort_long_kmers(Ctx &c, int words, uint64_t n, const uint64_t *const wordsrc[3], const uint64_t *val, uint64_t *i0, uint64_t *i1, uint64_t *t0, uint64_t *t1,
-                            uint64_t *shi, uint64_t *slo, uint64_t *slo2, uint64_t *sval)
+// The buffers of the sort of two- and three-word k-mers: the k-mers' words and values as they were emitted (khi klo klo2 val), the index permutation,
+// its ping-pong copy and the two key buffers of the sort (i0 i1 t0 t1), and the words and values in sorted order: shi slo sval in the context's ws_a
+// ws_b ws_c, slo2 (three words) in s2buf.
+struct LongSortBufs {
+    DevBuf khi, klo, klo2, val, i0, i1, t0, t1, s2buf;
+    uint64_t *shi = nullptr, *slo = nullptr, *slo2 = nullptr, *sval = nullptr;
+    void reserve(Ctx &c, uint64_t n, int words)
+    {
+        for (DevBuf *b : {&khi, &klo, &val, &i0, &i1, &t0, &t1}) b->reserve((size_t)(n + 2) * 8);
+        if (words == 3) { klo2.reserve((size_t)(n + 2) * 8); s2buf.reserve((size_t)(n + 2) * 8); }
+        c.ws_a.reserve((size_t)(n + 2) * 8); c.ws_b.reserve((size_t)(n + 2) * 8); c.ws_c.reserve((size_t)(n + 2) * 8);
+        shi = c.ws_a.as<uint64_t>(); slo = c.ws_b.as<uint64_t>(); sval = c.ws_c.as<uint64_t>(); slo2 = words == 3 ? s2buf.as<uint64_t>() : nullptr;
+    }
+    void release(Ctx &c) { for (DevBuf *b : {&s2buf, &t1, &t0, &i1, &i0, &val, &klo2, &klo, &khi, &c.ws_a, &c.ws_b, &c.ws_c}) b->release(); }      // (last reserved, first freed; then the context's)
+    SortedRuns sorted() const { SortedRuns r; r.keys = shi; r.lo = slo; r.lo2 = slo2; r.vals = sval; return r; }
+};
+
+// The sort of two- and three-word k-mers (one pass, every value-range pass, the owner's records): the identity permutation i0 sorted by the words,
+// then the k-mers' words and values gathered in sorted order into shi / slo / slo2 / sval.  n > 0.
+// (the permutation buffers are dead once the gathers are queued)
+static void sort_long_kmers(Ctx &c, int words, uint64_t n, LongSortBufs &b)
 {
     hipStream_t s = c.stream;
     const unsigned nbI = (unsigned)((n + 255) / 256);
-    const uint64_t *fin = sort_words_permutation(c, words, wordsrc, n, c.cfg.k, i0, i1, t0, t1);
-    hipLaunchKernelGGL(k_gather_u64, dim3(nbI), dim3(256), 0, s, fin, wordsrc[0], n, shi);
-    hipLaunchKernelGGL(k_gather_u64, dim3(nbI), dim3(256), 0, s, fin, wordsrc[1], n, slo);
-    if (words == 3) hipLaunchKernelGGL(k_gather_u64, dim3(nbI), dim3(256), 0, s, fin, wordsrc[2], n, slo2);
-    hipLaunchKernelGGL(k_gather_u64, dim3(nbI), dim3(256), 0, s, fin, val, n, sval);
-}
-
-static bool count_long_kmers_in_passes(Ctx &c, uint64_t I, int words, size_t free0, elba_kmer_stats &st);      // (below, beside the enumeration kernels it shares with the distributed path)
-
-void stage_count_kmers(Ctx &c)
-{
-    enter(c.v, EV_COUNT_KMERS);
-    ELBA_REQUIRE(has(c.v, P_READS), ELBA_ERR_STATE, "count_kmers: no reads (call elba_set_reads)");
-    hipStream_t s = c.stream;
-    const int k = c.cfg.k;
-    const int64_t M = c.nreads;
-    accepted(c.v, EV_COUNT_KMERS);
-    c.dist_owner = false;
-    c.kmer_path = 0;
-    c.pre = CsrHandoff{};
-    elba_kmer_stats st{};
-    st.nreads = M;
-
-    // instance offsets: a host prefix sum over the read lengths (include/KmerOps.hpp:118-119: reads shorter than k contribute nothing)
-    std::vector<uint64_t> off((size_t)M + 1);
-    uint64_t I = 0;
-    uint32_t maxlen = 0;
-    for (int64_t r = 0; r < M; ++r) { const uint32_t l = c.h_len[(size_t)r]; off[(size_t)r] = I; if ((int64_t)l >= k) I += (uint64_t)l - k + 1; maxlen = l > maxlen ? l : maxlen; }
-    off[(size_t)M] = I;
-    c.max_read_len = maxlen;      // (the one host walk over the read lengths of this stage: kmer_msd.hip sizes its position field by it)
-    // (more than 2^32 instances: the two-level partition of kmer_msd.hip counts them in passes over value ranges — 9 <= k <= 31, on 16-byte records from
-    //  k = 18 on —, and so does the sort of k > 31 (count_long_kmers_in_passes); the wide partition's LDS sort of a bucket's entries beyond UPPER = 255
-    //  holds 32-bit places)
-    size_t free0 = 0;
-    if (k > 31) { size_t total = 0; ELBA_HIP(hipMemGetInfo(&free0, &total)); }      // (what bounds the passes of the sort: count_long_kmers_in_passes)
-    if (I >= 0xFFFFFFF0ull && k <= 31) {
-        ELBA_REQUIRE(k >= 9, ELBA_ERR_UNSUPPORTED, "count_kmers: more than 2^32 k-mer instances on one GPU need k >= 9 (the sort of short k-mers holds 32-bit places)");
-        ELBA_REQUIRE(!c.opt.kmer_no_msd, ELBA_ERR_UNSUPPORTED, "count_kmers: more than 2^32 k-mer instances on one GPU need the value partition (option kmer_no_msd is set)");
-        ELBA_REQUIRE(k <= 17 || c.cfg.upper <= 255, ELBA_ERR_UNSUPPORTED, "count_kmers: more than 2^32 k-mer instances on one GPU need UPPER <= 255 for k > 17 (the sort holds 32-bit places)");
-    }
-    c.I = (int64_t)I; c.kmer_passes = 1; c.kmer_peak_bytes = 0;
-    c.kmer_crowded = 0; c.kmer_crowded_small = 0; c.kmer_largest_pass = (int64_t)I; c.kmer_buckets = 0;
-    c.inst_off.reserve((size_t)(M + 1) * 8);
-    ELBA_HIP(hipMemcpyAsync(c.inst_off.p, off.data(), (size_t)(M + 1) * 8, hipMemcpyHostToDevice, s));
-
-    if (k > 31) {
-        // ---- two- and three-word k-mers: sort an index permutation, last word first (stable LSD over all words), then gather ----
-        const int words = k > 64 ? 3 : 2;
-        if (count_long_kmers_in_passes(c, I, words, free0, st)) { done(c.v, EV_COUNT_KMERS); return; }
-        DevBuf khi, klo, klo2, val, i0, i1, t0, t1, s2buf;
-        for (DevBuf *b : {&khi, &klo, &val, &i0, &i1, &t0, &t1}) b->reserve((size_t)(I + 2) * 8);
-        if (words == 3) { klo2.reserve((size_t)(I + 2) * 8); s2buf.reserve((size_t)(I + 2) * 8); }
-        c.ws_a.reserve((size_t)(I + 2) * 8); c.ws_b.reserve((size_t)(I + 2) * 8); c.ws_c.reserve((size_t)(I + 2) * 8);
-        c.ws_e.reserve((size_t)(I + 2) * 4); c.ws_f.reserve((size_t)(I + 2) * 8);
-        c.t_total.start(s);
-        c.t_a.start(s);
-        EnumParams e = make_enum(c);
-        const uint64_t nblocks = (I + EN_PER_BLOCK - 1) / EN_PER_BLOCK;
-        uint64_t *shi = c.ws_a.as<uint64_t>(), *slo = c.ws_b.as<uint64_t>(), *sval = c.ws_c.as<uint64_t>(), *slo2 = words == 3 ? s2buf.as<uint64_t>() : nullptr;
-        if (I > 0) {
-            if (words == 3) hipLaunchKernelGGL(k_kmer_emit3, dim3((unsigned)nblocks), dim3(EN_THREADS), 0, s, e, khi.as<uint64_t>(), klo.as<uint64_t>(), klo2.as<uint64_t>(), val.as<uint64_t>(), i0.as<uint64_t>());
-            else hipLaunchKernelGGL(k_kmer_emit2, dim3((unsigned)nblocks), dim3(EN_THREADS), 0, s, e, khi.as<uint64_t>(), klo.as<uint64_t>(), val.as<uint64_t>(), i0.as<uint64_t>());
-            const uint64_t *wordsrc[3] = {khi.as<uint64_t>(), klo.as<uint64_t>(), words == 3 ? klo2.as<uint64_t>() : nullptr};
-            sort_long_kmers(c, words, I, wordsrc, val.as<uint64_t>(), i0.as<uint64_t>(), i1.as<uint64_t>(), t0.as<uint64_t>(), t1.as<uint64_t>(), shi, slo, slo2, sval);
-        }
-        c.t_a.stop(s);
-        c.t_b.start(s);
-        uint64_t nruns = 0, N = 0, Z = 0;
-        runs_to_columns(c, shi, sval, I, nruns, N, Z, slo, slo2);
-        c.t_b.stop(s);
-        c.t_total.stop(s);
-        ELBA_HIP(hipStreamSynchronize(s));
-        st.instances = (int64_t)I; st.distinct = (int64_t)nruns; st.reliable = (int64_t)N; st.entries = (int64_t)Z;
-        st.ms_total = c.t_total.ms(); st.ms_count = c.t_a.ms(); st.ms_sort = c.t_b.ms(); st.ms_lookup = 0;
-        c.ndistinct = (int64_t)nruns;
-        c.N = (int64_t)N; c.Z = (int64_t)Z;
-        c.kstats = st;
-        done(c.v, EV_COUNT_KMERS);
-        return;
-    }
-    if (msd_count_kmers(c, I, st)) {      // k <= 17 on inputs of some size: two-level value partition + LDS count tables (kmer_msd.hip)
-        c.kstats = st;
-        done(c.v, EV_COUNT_KMERS);
-        return;
-    }
-    ELBA_REQUIRE(I < 0xFFFFFFF0ull, ELBA_ERR_UNSUPPORTED, "count_kmers: more than 2^32 k-mer instances on one GPU and the two-level partition does not take this input");
-    {
-        // ---- one-word k-mers: see the header of this file ----
-        c.t_total.start(s);
-        c.t_a.start(s);
-        EnumParams e = make_enum(c);
-        const uint64_t nblocks = (I + EN_PER_BLOCK - 1) / EN_PER_BLOCK;
-        // One 64-bit word per instance: value << pb | (instance index >> drop).  The index is the payload — (read, pos) follow from it
-        // through the instance offsets, for the entries that survive the count filter only — and when value and index are a few bits too
-        // many for one word (k = 17 beyond 2^30 instances) its `drop` lowest bits are left out: the candidates they stand for are told
-        // apart afterwards by recomputing their k-mers (k_instance_entries).  The sort then moves 8 bytes per instance, not 16.
-        int ib = 1;
-        while (ib < 63 && (I >> ib)) ++ib;
-        int drop = 2 * k + ib > 64 ? 2 * k + ib - 64 : 0;
-        if (c.opt.kmer_drop) { const int want = c.opt.kmer_drop; if (want > drop && want <= 3 && want < ib) drop = want; }      // (test hook: small inputs through the dropped-index-bit path)
-        const bool packed_words = drop <= 3 && !c.opt.kmer_pairs;
-        if (!packed_words) { ib = 0; drop = 0; }
-        const int pb = ib - drop;                  // payload bits below the value
-        // workspaces: the words and their ping-pong copy; (value, payload) pairs need two more arrays (the other buffers are sized where they are used)
-        c.ws_a.reserve((size_t)(I + 2) * 8); c.ws_c.reserve((size_t)(I + 2) * 8);
-        if (!packed_words) { c.ws_b.reserve((size_t)(I + 2) * 8); c.ws_d.reserve((size_t)(I + 2) * 8); }
-        int where = 0;
-        if (packed_words) {
-            int sh0 = 0, b0 = 0, tile = 0;
-            uint32_t *hist0 = I > 1 ? radix_first_histogram((int64_t)I, pb, pb + 2 * k, c.ws_sort, &sh0, &b0, &tile) : nullptr;
-            const bool fuse_hist = hist0 && tile == 4 * EN_PER_BLOCK && b0 <= 9 && !c.opt.emit_plain;      // (the emit writes whole tiles of the sort and counts their first digit)
-            if (fuse_hist) {
-                const uint64_t nib = (I >> IB_SHIFT) + 1;
-                c.ws_b.reserve((size_t)(nib + 1) * sizeof(BlockInfo));
-                hipLaunchKernelGGL(k_block_reads, dim3((unsigned)((nib + 255) / 256)), dim3(256), 0, s, e.inst_off, e.byte_off, e.nreads, nib, c.ws_b.as<BlockInfo>());
-                hipLaunchKernelGGL((k_kmer_emit_packed_hist<4>), dim3((unsigned)((I + tile - 1) / tile)), dim3(EN_THREADS), 0, s, e, (const BlockInfo *)c.ws_b.as<BlockInfo>(), pb, drop, c.ws_a.as<uint64_t>(), sh0, b0, hist0);
-            }
-            else if (I > 0) hipLaunchKernelGGL(k_kmer_emit_packed, dim3((unsigned)nblocks), dim3(EN_THREADS), 0, s, e, pb, drop, c.ws_a.as<uint64_t>());
-            where = radix_sort_keys(s, c.ws_a.as<uint64_t>(), c.ws_c.as<uint64_t>(), (int64_t)I, pb, pb + 2 * k, c.ws_sort, fuse_hist);
-        } else {
-            if (I > 0) hipLaunchKernelGGL(k_kmer_emit, dim3((unsigned)nblocks), dim3(EN_THREADS), 0, s, e, c.ws_a.as<uint64_t>(), c.ws_b.as<uint64_t>());
-            where = radix_sort_pairs(s, c.ws_a.as<uint64_t>(), c.ws_b.as<uint64_t>(), c.ws_c.as<uint64_t>(), c.ws_d.as<uint64_t>(), (int64_t)I, 64 - 2 * k, 64, c.ws_sort);
-        }
-        const uint64_t *skeys = where ? c.ws_c.as<uint64_t>() : c.ws_a.as<uint64_t>(), *svals = packed_words ? (const uint64_t *)nullptr : (where ? c.ws_d.as<uint64_t>() : c.ws_b.as<uint64_t>());
-        c.t_a.stop(s);
-        c.t_b.start(s);
-        uint64_t nruns = 0, N = 0, Z = 0;
-        runs_to_columns(c, skeys, svals, I, nruns, N, Z, nullptr, nullptr, pb, drop);
-        c.t_b.stop(s);
-        c.t_total.stop(s);
-        ELBA_HIP(hipStreamSynchronize(s));
-        st.instances = (int64_t)I; st.distinct = (int64_t)nruns; st.reliable = (int64_t)N; st.entries = (int64_t)Z;
-        st.ms_total = c.t_total.ms(); st.ms_count = c.t_a.ms(); st.ms_sort = c.t_b.ms(); st.ms_lookup = 0;
-        c.ndistinct = (int64_t)nruns;
-        c.N = (int64_t)N; c.Z = (int64_t)Z;
-        c.kstats = st;
-        done(c.v, EV_COUNT_KMERS);
-        return;
-    }
-
+    const uint64_t *wordsrc[3] = {b.khi.as<uint64_t>(), b.klo.as<uint64_t>(), words == 3 ? b.klo2.as<uint64_t>() : nullptr};
+    const uint64_t *fin = sort_words_permutation(c, words, wordsrc, n, c.cfg.k, b.i0.as<uint64_t>(), b.i1.as<uint64_t>(), b.t0.as<uint64_t>(), b.t1.as<uint64_t>());
+    hipLaunchKernelGGL(k_gather_u64, dim3(nbI), dim3(256), 0, s, fin, wordsrc[0], n, b.shi);
+    hipLaunchKernelGGL(k_gather_u64, dim3(nbI), dim3(256), 0, s, fin, wordsrc[1], n, b.slo);
+    if (words == 3) hipLaunchKernelGGL(k_gather_u64, dim3(nbI), dim3(256), 0, s, fin, wordsrc[2], n, b.slo2);
+    hipLaunchKernelGGL(k_gather_u64, dim3(nbI), dim3(256), 0, s, fin, b.val.as<uint64_t>(), n, b.sval);
 }
 
 // column id of every entry, from the column pointers (one lane per column: columns hold at most UPPER entries)
@@ -743,7 +658,6 @@ constexpr int MAX_RANKS = 64;
 // reference's hash (GetKmerOwner, src/KmerOps.cpp:352-359) because the owners' reliable k-mers are then disjoint ascending value
 // ranges: the global k-mer id — rank of the value, SURVEY.md §8c-2 — is the owner's local index plus an exclusive scan of the owners'
 // counts (the reference's Exscan, src/KmerOps.cpp:371-375), and no rank ever needs the other ranks' k-mers.
-constexpr int OWNER_BITS = 12;
 struct OwnerMap { uint32_t nranks; uint32_t upper[MAX_RANKS]; };
 __device__ __forceinline__ uint32_t owner_of(uint64_t first_word, const OwnerMap &om)
 {
@@ -781,7 +695,6 @@ __global__ __launch_bounds__(EN_THREADS) void k_dist_value_hist(EnumParams e, un
 // A pass is a range [lo, hi) of the leading 24 bits of the canonical first word.  Planned from k_dist_value_hist<W> (the leading 12 bits) and, for the
 // 12-bit bins that hold more than the cap, one refining histogram over the next 12 bits of all of them at once: slot_of_bin[bin] = the bin's row of
 // hist2, or -1.
-constexpr int LONG_PREFIX_BITS = 24;
 __device__ __forceinline__ bool in_long_pass(uint64_t a, uint32_t lo, uint32_t hi) { const uint32_t d = (uint32_t)(a >> (64 - LONG_PREFIX_BITS)); return d >= lo && d < hi; }
 
 template <int W>
@@ -1023,171 +936,250 @@ __global__ void k_deinterleave(const uint64_t *rec, uint64_t n, uint64_t *k0, ui
 
 }  // namespace
 
-static int kmer_words(int k) { return k > 64 ? 3 : (k > 32 ? 2 : 1); }      // (k is odd: 31 is the last one-word k, 63 the last two-word k)
+// ---- elba_count_kmers by sorting: the steps of stage_count_kmers (file header) ----
 
-// ---- two- and three-word k-mers in value-range passes ----
-// The sort of k > 31 (stage_count_kmers) holds 32-bit places and reserves its workspace for the whole input at once.  Inputs that do not fit one pass
-// — 2^32 instances and more, more than the cap (option kmer_batch_instances, else 0xE0000000), or more than the device memory holds — are counted in
-// passes over ranges [lo, hi) of the leading 24 bits of the canonical first word, in ascending order: each pass emits its instances in instance order
-// (k_long_pass_count, a scan, k_kmer_emit_range), sorts and gathers them as one pass would, and cuts its runs into columns whose k-mer ids and entries
-// follow those of the passes before it.  Every pass stages its columns in buffers of exactly their size; once the passes are done and their workspace
-// is released, the context's arrays are allocated and the staged pieces concatenated into them, one kind of array at a time (peak: the staged
-// columns plus one array of the final size).  Passes change no result.  false: one pass takes the input (the caller runs the launches it always has).
-static bool count_long_kmers_in_passes(Ctx &c, uint64_t I, int words, size_t free0, elba_kmer_stats &st)
+// instance offsets: a host prefix sum over the read lengths (include/KmerOps.hpp:118-119: reads shorter than k contribute nothing); the one host walk
+// over the read lengths of a count
+struct InstanceOffsets { std::vector<uint64_t> off; uint64_t I = 0; uint32_t max_read_len = 0; };
+static InstanceOffsets instance_offsets(Ctx &c)
+{
+    const int k = c.cfg.k;
+    const int64_t M = c.nreads;
+    InstanceOffsets io;
+    io.off.resize((size_t)M + 1);
+    for (int64_t r = 0; r < M; ++r) {
+        const uint32_t l = c.h_len[(size_t)r];
+        io.off[(size_t)r] = io.I;
+        if ((int64_t)l >= k) io.I += (uint64_t)l - k + 1;
+        io.max_read_len = l > io.max_read_len ? l : io.max_read_len;
+    }
+    io.off[(size_t)M] = io.I;
+    return io;
+}
+// (asynchronous: `io` outlives the copy, or the caller synchronizes)
+static void upload_offsets(Ctx &c, const InstanceOffsets &io)
+{
+    c.I = (int64_t)io.I;
+    c.inst_off.reserve(io.off.size() * 8);
+    ELBA_HIP(hipMemcpyAsync(c.inst_off.p, io.off.data(), io.off.size() * 8, hipMemcpyHostToDevice, c.stream));
+}
+
+// what a count leaves in the context and in its statistics: the part every counting call shares, and the times of elba_count_kmers (its stream is idle)
+static void publish_counts(Ctx &c, elba_kmer_stats &st, uint64_t I, const Columns &col)
+{
+    st.instances = (int64_t)I; st.distinct = (int64_t)col.nruns; st.reliable = (int64_t)col.N; st.entries = (int64_t)col.Z;
+    c.ndistinct = (int64_t)col.nruns;
+    c.N = (int64_t)col.N; c.Z = (int64_t)col.Z;
+    c.kstats = st;
+}
+struct Counted { Columns col; double ms_count = 0, ms_sort = 0; };      // what a path of the sort hands finish_count
+static void finish_count(Ctx &c, elba_kmer_stats &st, uint64_t I, const Counted &r)
+{
+    st.ms_total = c.t_total.ms(); st.ms_count = r.ms_count; st.ms_sort = r.ms_sort; st.ms_lookup = 0;
+    publish_counts(c, st, I, r.col);
+}
+
+// two- and three-word k-mers in one pass: sort an index permutation, last word first (stable LSD over all words), then gather
+static Counted sort_long_one_pass(Ctx &c, uint64_t I, int words)
 {
     hipStream_t s = c.stream;
-    // device bytes per instance, DevBuf's 1/8 slack included.  One pass (stage_count_kmers' reservations): khi klo val i0 i1 t0 t1, ws_a ws_b ws_c
-    // (8 each), ws_e (4), ws_f (8); three words: klo2 and s2buf (8 each).  A value-range pass: the same without ws_e / ws_f, which the sort path does
-    // not use at the instance count, plus the sort's histograms and the wavefront counts (under 1).  The columns: at most I entries (a_csc and
-    // kid_of_entry, 8 each) and I / LOWER k-mers (the words, count and pointer).
-    const double one_pass_b = (words == 2 ? 92.0 : 108.0) * 1.125, pass_b = (words == 2 ? 80.0 : 96.0) * 1.125 + 1.0;
-    const double out_b = (16.0 + (8.0 * words + 8.0) / (double)std::max(c.cfg.lower, 1)) * 1.125;
-    // what the call may use: the memory free when it started, the context's buffers that it overwrites, less 2 GiB for the runtime and small buffers
-    size_t held = 0;
-    for (DevBuf *b : {&c.ws_a, &c.ws_b, &c.ws_c, &c.ws_e, &c.ws_f, &c.rel_kmers, &c.rel_kmers_lo, &c.rel_kmers_lo2, &c.rel_counts, &c.a_colptr, &c.a_csc, &c.kid_of_entry}) held += b->cap;
-    const double avail = (double)free0 + (double)held - 2.0 * (double)(1ull << 30);
-    const uint64_t opt_cap = c.opt.kmer_batch_instances > 0 ? (uint64_t)c.opt.kmer_batch_instances : 0xE0000000ull;
-    if (I < 0xFFFFFFF0ull && I <= opt_cap && (double)I * (one_pass_b + out_b) <= avail) return false;
-    const double room = avail - out_b * (double)I;                      // for the workspace of the largest pass
-    const uint64_t mem_cap = room > 0 ? (uint64_t)(room / pass_b) : 0;
-    char why[256];
-    snprintf(why, sizeof why, "count_kmers: %llu k-mer instances at k = %d leave room for passes of %llu instances only (the columns may need %.1f GB)",
-             (unsigned long long)I, c.cfg.k, (unsigned long long)mem_cap, out_b * (double)I / 1e9);
-    ELBA_REQUIRE(mem_cap >= std::min<uint64_t>(I, 1ull << 24), ELBA_ERR_OUT_OF_MEMORY, why);
-    const uint64_t cap = std::max<uint64_t>(std::min<uint64_t>(std::min(opt_cap, mem_cap), 0xE0000000ull), 1);
-
+    LongSortBufs b;
+    b.reserve(c, I, words);
+    c.ws_e.reserve((size_t)(I + 2) * 4); c.ws_f.reserve((size_t)(I + 2) * 8);
     c.t_total.start(s);
+    c.t_a.start(s);
     EnumParams e = make_enum(c);
-    const uint64_t nblocks = (I + EN_PER_BLOCK - 1) / EN_PER_BLOCK, nwaves = nblocks * (EN_THREADS / 64);
-    constexpr uint32_t NB = 1u << OWNER_BITS;
-    // ---- plan: instances per 12-bit bin of the first word; the bins above the cap per 24-bit prefix ----
-    std::vector<unsigned long long> h1(NB);
-    std::vector<unsigned long long> h2;
-    std::vector<uint32_t> heavy;
-    {
-        DevBuf plan;
-        plan.reserve((size_t)NB * 12);
-        unsigned long long *dh = plan.as<unsigned long long>();
-        ELBA_HIP(hipMemsetAsync(dh, 0, (size_t)NB * 8, s));
-        if (words == 3) hipLaunchKernelGGL(k_dist_value_hist<3>, dim3((unsigned)nblocks), dim3(EN_THREADS), 0, s, e, dh);
-        else hipLaunchKernelGGL(k_dist_value_hist<2>, dim3((unsigned)nblocks), dim3(EN_THREADS), 0, s, e, dh);
-        ELBA_HIP(hipMemcpyAsync(h1.data(), dh, (size_t)NB * 8, hipMemcpyDeviceToHost, s));
-        ELBA_HIP(hipStreamSynchronize(s));
-        std::vector<int32_t> slot(NB, -1);
-        for (uint32_t b = 0; b < NB; ++b) if (h1[b] > cap) { slot[b] = (int32_t)heavy.size(); heavy.push_back(b); }
-        if (!heavy.empty()) {
-            DevBuf hist2;
-            hist2.reserve(heavy.size() * NB * 8);
-            int32_t *dslot = reinterpret_cast<int32_t *>(dh + NB);
-            ELBA_HIP(hipMemcpyAsync(dslot, slot.data(), (size_t)NB * 4, hipMemcpyHostToDevice, s));
-            ELBA_HIP(hipMemsetAsync(hist2.p, 0, heavy.size() * NB * 8, s));
-            if (words == 3) hipLaunchKernelGGL(k_long_refine_hist<3>, dim3((unsigned)nblocks), dim3(EN_THREADS), 0, s, e, (const int32_t *)dslot, hist2.as<unsigned long long>());
-            else hipLaunchKernelGGL(k_long_refine_hist<2>, dim3((unsigned)nblocks), dim3(EN_THREADS), 0, s, e, (const int32_t *)dslot, hist2.as<unsigned long long>());
-            h2.resize(heavy.size() * NB);
-            ELBA_HIP(hipMemcpyAsync(h2.data(), hist2.p, heavy.size() * NB * 8, hipMemcpyDeviceToHost, s));
-            ELBA_HIP(hipStreamSynchronize(s));
-        }
+    if (I > 0) {
+        const uint64_t nblocks = (I + EN_PER_BLOCK - 1) / EN_PER_BLOCK;
+        if (words == 3) hipLaunchKernelGGL(k_kmer_emit3, dim3((unsigned)nblocks), dim3(EN_THREADS), 0, s, e, b.khi.as<uint64_t>(), b.klo.as<uint64_t>(), b.klo2.as<uint64_t>(), b.val.as<uint64_t>(), b.i0.as<uint64_t>());
+        else hipLaunchKernelGGL(k_kmer_emit2, dim3((unsigned)nblocks), dim3(EN_THREADS), 0, s, e, b.khi.as<uint64_t>(), b.klo.as<uint64_t>(), b.val.as<uint64_t>(), b.i0.as<uint64_t>());
+        sort_long_kmers(c, words, I, b);
     }
-    // units in ascending order (a 12-bit bin, or one 24-bit prefix of a heavy bin); passes of whole units, balanced as the wide partition's: as many
-    // as the cap needs, each near I / passes.  A unit above the cap is a pass of its own.
-    struct LongPass { uint32_t lo, hi; uint64_t n; };
-    std::vector<LongPass> passes;
-    {
-        const uint64_t npass = (I + cap - 1) / cap, target = (I + npass - 1) / npass;
-        uint32_t lo = 0;
-        uint64_t cnt = 0;
-        size_t hv = 0;
-        auto unit = [&](uint32_t start, uint64_t x) {
-            if (cnt > 0 && (cnt + x > cap || cnt + x / 2 > target)) { passes.push_back(LongPass{lo, start, cnt}); lo = start; cnt = 0; }
-            cnt += x;
-        };
-        for (uint32_t b = 0; b < NB; ++b) {
-            if (hv < heavy.size() && heavy[hv] == b) { for (uint32_t d = 0; d < NB; ++d) unit((b << OWNER_BITS) | d, h2[hv * NB + d]); ++hv; }
-            else unit(b << OWNER_BITS, h1[b]);
-        }
-        passes.push_back(LongPass{lo, 1u << LONG_PREFIX_BITS, cnt});
-    }
-    uint64_t largest = 0;
-    for (const LongPass &p : passes) {
-        if (p.n > largest) largest = p.n;
-        snprintf(why, sizeof why, "count_kmers: the k-mers whose first word begins with the 24-bit prefix 0x%06x%s number %llu instances, more than one pass of the sort "
-                 "holds (2^32)", p.lo, p.hi - p.lo > 1 ? " (and the prefixes up to it)" : "", (unsigned long long)p.n);
-        ELBA_REQUIRE(p.n < 0xFFFFFFF0ull, ELBA_ERR_UNSUPPORTED, why);
-        snprintf(why, sizeof why, "count_kmers: the k-mers whose first word begins with the 24-bit prefix 0x%06x%s number %llu instances: the workspace of their pass "
-                 "(%.1f GB) does not fit beside the columns", p.lo, p.hi - p.lo > 1 ? " (and the prefixes up to it)" : "", (unsigned long long)p.n, pass_b * (double)p.n / 1e9);
-        ELBA_REQUIRE(pass_b * (double)p.n <= room, ELBA_ERR_OUT_OF_MEMORY, why);
-    }
-    if (c.opt.trace) fprintf(stderr, "[elba] count_kmers: %llu instances of %d-word k-mers in %zu value-range passes (cap %llu, largest %llu)\n", (unsigned long long)I, words,
-                             passes.size(), (unsigned long long)cap, (unsigned long long)largest);
-    c.kmer_passes = (int)passes.size(); c.kmer_largest_pass = (int64_t)largest;
+    c.t_a.stop(s);
+    c.t_b.start(s);
+    Counted r;
+    r.col = runs_to_columns(c, b.sorted(), I);
+    c.t_b.stop(s);
+    c.t_total.stop(s);
+    ELBA_HIP(hipStreamSynchronize(s));
+    r.ms_count = c.t_a.ms(); r.ms_sort = c.t_b.ms();
+    return r;
+}
 
-    // ---- the passes ----
-    // (the columns of an earlier call and the workspace sized for another input go first: what is freed is what the passes were planned with)
-    for (DevBuf *b : {&c.ws_a, &c.ws_b, &c.ws_c, &c.ws_e, &c.ws_f, &c.rel_kmers, &c.rel_kmers_lo, &c.rel_kmers_lo2, &c.rel_counts, &c.a_colptr, &c.a_csc, &c.kid_of_entry}) b->release();
-    size_t free_base = 0, free_now = 0, total = 0;
-    ELBA_HIP(hipMemGetInfo(&free_base, &total));
+// one-word k-mers the partition does not take: see the header of this file and plan_sort_word (sort_plan.hpp)
+static Counted sort_one_word(Ctx &c, uint64_t I)
+{
+    hipStream_t s = c.stream;
+    const int k = c.cfg.k;
+    c.t_total.start(s);
+    c.t_a.start(s);
+    EnumParams e = make_enum(c);
+    const uint64_t nblocks = (I + EN_PER_BLOCK - 1) / EN_PER_BLOCK;
+    const SortWord w = plan_sort_word(k, I, c.opt.kmer_drop, c.opt.kmer_pairs != 0);
+    // workspaces: the words and their ping-pong copy; (value, payload) pairs need two more arrays (the other buffers are sized where they are used)
+    c.ws_a.reserve((size_t)(I + 2) * 8); c.ws_c.reserve((size_t)(I + 2) * 8);
+    if (!w.packed_words) { c.ws_b.reserve((size_t)(I + 2) * 8); c.ws_d.reserve((size_t)(I + 2) * 8); }
+    int where = 0;
+    if (w.packed_words) {
+        int sh0 = 0, b0 = 0, tile = 0;
+        uint32_t *hist0 = I > 1 ? radix_first_histogram((int64_t)I, w.pb, w.pb + 2 * k, c.ws_sort, &sh0, &b0, &tile) : nullptr;
+        const bool fuse_hist = hist0 && tile == 4 * EN_PER_BLOCK && b0 <= 9 && !c.opt.emit_plain;      // (the emit writes whole tiles of the sort and counts their first digit)
+        if (fuse_hist) {
+            const BlockInfo *block_read = block_reads(c, e, I);
+            hipLaunchKernelGGL((k_kmer_emit_packed_hist<4>), dim3((unsigned)((I + tile - 1) / tile)), dim3(EN_THREADS), 0, s, e, block_read, w.pb, w.drop, c.ws_a.as<uint64_t>(), sh0, b0, hist0);
+        }
+        else if (I > 0) hipLaunchKernelGGL(k_kmer_emit_packed, dim3((unsigned)nblocks), dim3(EN_THREADS), 0, s, e, w.pb, w.drop, c.ws_a.as<uint64_t>());
+        where = radix_sort_keys(s, c.ws_a.as<uint64_t>(), c.ws_c.as<uint64_t>(), (int64_t)I, w.pb, w.pb + 2 * k, c.ws_sort, fuse_hist);
+    } else {
+        if (I > 0) hipLaunchKernelGGL(k_kmer_emit, dim3((unsigned)nblocks), dim3(EN_THREADS), 0, s, e, c.ws_a.as<uint64_t>(), c.ws_b.as<uint64_t>());
+        where = radix_sort_pairs(s, c.ws_a.as<uint64_t>(), c.ws_b.as<uint64_t>(), c.ws_c.as<uint64_t>(), c.ws_d.as<uint64_t>(), (int64_t)I, 64 - 2 * k, 64, c.ws_sort);
+    }
+    SortedRuns in;
+    in.keys = where ? c.ws_c.as<uint64_t>() : c.ws_a.as<uint64_t>();
+    in.vals = w.packed_words ? (const uint64_t *)nullptr : (where ? c.ws_d.as<uint64_t>() : c.ws_b.as<uint64_t>());
+    in.ib = w.pb; in.drop = w.drop;
+    c.t_a.stop(s);
+    c.t_b.start(s);
+    Counted r;
+    r.col = runs_to_columns(c, in, I);
+    c.t_b.stop(s);
+    c.t_total.stop(s);
+    ELBA_HIP(hipStreamSynchronize(s));
+    r.ms_count = c.t_a.ms(); r.ms_sort = c.t_b.ms();
+    return r;
+}
+
+// ---- two- and three-word k-mers in value-range passes ----
+// The sort of k > 31 (sort_long_one_pass) holds 32-bit places and reserves its workspace for the whole input at once.  Inputs that do not fit one pass
+// — 2^32 instances and more, more than the cap (option kmer_batch_instances, else 0xE0000000), or more than the device memory holds — are counted in
+// passes over ranges [lo, hi) of the leading 24 bits of the canonical first word, in ascending order (sort_plan.hpp: plan_long_capacity,
+// cut_long_passes, check_long_passes): each pass emits its instances in instance order (k_long_pass_count, a scan, k_kmer_emit_range), sorts and
+// gathers them as one pass would, and cuts its runs into columns whose k-mer ids and entries follow those of the passes before it (run_long_pass).
+// Every pass stages its columns in buffers of exactly their size; once the passes are done and their workspace is released, the context's arrays are
+// allocated and the staged pieces concatenated into them, one kind of array at a time (concat_staged; peak: the staged columns plus one array of the
+// final size).  Passes change no result.
+
+// what the passes hold at their high point, from the free device memory before their first allocation ("kmer_peak_bytes")
+struct PeakMeter {
+    size_t free_base = 0;
     uint64_t peak = 0;
-    auto checkpoint = [&]() { ELBA_HIP(hipMemGetInfo(&free_now, &total)); if (free_now < free_base && free_base - free_now > peak) peak = free_base - free_now; };
-    struct Staged { DevBuf kmers, lo, lo2, counts, colptr, csc, kid; uint64_t N = 0, Z = 0; };
-    std::unique_ptr<Staged[]> staged(new Staged[passes.size()]);
+    void start() { size_t total = 0; ELBA_HIP(hipMemGetInfo(&free_base, &total)); }
+    void checkpoint() { size_t free_now = 0, total = 0; ELBA_HIP(hipMemGetInfo(&free_now, &total)); if (free_now < free_base && free_base - free_now > peak) peak = free_base - free_now; }
+};
+
+// the plan's histograms: instances per 12-bit bin of the first word (h1); the bins above the cap per 24-bit prefix (h2, one row per heavy bin)
+struct LongHists { std::vector<unsigned long long> h1, h2; HeavyBins heavy; };
+static LongHists long_histograms(Ctx &c, const EnumParams &e, int words, uint64_t nblocks, uint64_t cap)
+{
+    hipStream_t s = c.stream;
+    constexpr uint32_t NB = 1u << OWNER_BITS;
+    LongHists h;
+    h.h1.resize(NB);
+    DevBuf plan;
+    plan.reserve((size_t)NB * 12);
+    unsigned long long *dh = plan.as<unsigned long long>();
+    ELBA_HIP(hipMemsetAsync(dh, 0, (size_t)NB * 8, s));
+    if (words == 3) hipLaunchKernelGGL(k_dist_value_hist<3>, dim3((unsigned)nblocks), dim3(EN_THREADS), 0, s, e, dh);
+    else hipLaunchKernelGGL(k_dist_value_hist<2>, dim3((unsigned)nblocks), dim3(EN_THREADS), 0, s, e, dh);
+    ELBA_HIP(hipMemcpyAsync(h.h1.data(), dh, (size_t)NB * 8, hipMemcpyDeviceToHost, s));
+    ELBA_HIP(hipStreamSynchronize(s));
+    h.heavy = heavy_bins(h.h1, cap);
+    if (h.heavy.bins.empty()) return h;
+    const size_t n2 = h.heavy.bins.size() * NB;
+    DevBuf hist2;
+    hist2.reserve(n2 * 8);
+    int32_t *dslot = reinterpret_cast<int32_t *>(dh + NB);
+    ELBA_HIP(hipMemcpyAsync(dslot, h.heavy.slot.data(), (size_t)NB * 4, hipMemcpyHostToDevice, s));
+    ELBA_HIP(hipMemsetAsync(hist2.p, 0, n2 * 8, s));
+    if (words == 3) hipLaunchKernelGGL(k_long_refine_hist<3>, dim3((unsigned)nblocks), dim3(EN_THREADS), 0, s, e, (const int32_t *)dslot, hist2.as<unsigned long long>());
+    else hipLaunchKernelGGL(k_long_refine_hist<2>, dim3((unsigned)nblocks), dim3(EN_THREADS), 0, s, e, (const int32_t *)dslot, hist2.as<unsigned long long>());
+    h.h2.resize(n2);
+    ELBA_HIP(hipMemcpyAsync(h.h2.data(), hist2.p, n2 * 8, hipMemcpyDeviceToHost, s));
+    ELBA_HIP(hipStreamSynchronize(s));
+    return h;
+}
+
+// the first pass that cannot run (check_long_passes), in words
+static void refuse_long_pass(const std::vector<LongPass> &passes, const LongCapacity &cp)
+{
+    const LongPassFault f = check_long_passes(passes, cp.room, cp.pass_bytes);
+    if (f.kind == LongPassFault::NONE) return;
+    const LongPass &p = passes[f.index];
+    const char *more = p.hi - p.lo > 1 ? " (and the prefixes up to it)" : "";
+    char why[256];
+    if (f.kind == LongPassFault::TOO_MANY) {
+        snprintf(why, sizeof why, "count_kmers: the k-mers whose first word begins with the 24-bit prefix 0x%06x%s number %llu instances, more than one pass of the sort "
+                 "holds (2^32)", p.lo, more, (unsigned long long)p.n);
+        ELBA_REQUIRE(false, ELBA_ERR_UNSUPPORTED, why);
+    }
+    snprintf(why, sizeof why, "count_kmers: the k-mers whose first word begins with the 24-bit prefix 0x%06x%s number %llu instances: the workspace of their pass "
+             "(%.1f GB) does not fit beside the columns", p.lo, more, (unsigned long long)p.n, cp.pass_bytes * (double)p.n / 1e9);
+    ELBA_REQUIRE(false, ELBA_ERR_OUT_OF_MEMORY, why);
+}
+
+// the columns of one pass, in buffers of exactly their size
+struct Staged { DevBuf kmers, lo, lo2, counts, colptr, csc, kid; uint64_t N = 0, Z = 0; };
+// what the passes share: the enumeration, the workspace of the largest pass, the k-mers and entries before the next pass, the sums of the times
+struct LongRun {
+    EnumParams e;
+    int words = 2;
+    uint64_t nblocks = 0, nwaves = 0;
+    LongSortBufs bufs;
+    DevBuf wcnt;
     uint64_t kid_base = 0, ent_base = 0, distinct = 0;
     double ms_count = 0, ms_sort = 0;
-    {
-        DevBuf khi, klo, klo2, val, i0, i1, t0, t1, s2buf, wcnt;
-        for (DevBuf *b : {&khi, &klo, &val, &i0, &i1, &t0, &t1, &c.ws_a, &c.ws_b, &c.ws_c}) b->reserve((size_t)(largest + 2) * 8);
-        if (words == 3) { klo2.reserve((size_t)(largest + 2) * 8); s2buf.reserve((size_t)(largest + 2) * 8); }
-        wcnt.reserve((size_t)(nwaves + 1) * 4);
-        uint32_t *wc = wcnt.as<uint32_t>();
-        uint64_t *shi = c.ws_a.as<uint64_t>(), *slo = c.ws_b.as<uint64_t>(), *sval = c.ws_c.as<uint64_t>(), *slo2 = words == 3 ? s2buf.as<uint64_t>() : nullptr;
-        const uint64_t *wordsrc[3] = {khi.as<uint64_t>(), klo.as<uint64_t>(), words == 3 ? klo2.as<uint64_t>() : nullptr};
-        for (size_t q = 0; q < passes.size(); ++q) {
-            const LongPass &p = passes[q];
-            c.t_a.start(s);
-            ELBA_HIP(hipMemsetAsync(wc + nwaves, 0, 4, s));
-            if (words == 3) hipLaunchKernelGGL(k_long_pass_count<3>, dim3((unsigned)nblocks), dim3(EN_THREADS), 0, s, e, p.lo, p.hi, wc);
-            else hipLaunchKernelGGL(k_long_pass_count<2>, dim3((unsigned)nblocks), dim3(EN_THREADS), 0, s, e, p.lo, p.hi, wc);
-            exclusive_scan_u32(s, wc, wc, (int64_t)nwaves + 1, c.ws_scan);      // (p.n < 2^32: the 32-bit scan cannot wrap)
-            if (words == 3)
-                hipLaunchKernelGGL(k_kmer_emit_range<3>, dim3((unsigned)nblocks), dim3(EN_THREADS), 0, s, e, p.lo, p.hi, (const uint32_t *)wc, p.n, khi.as<uint64_t>(), klo.as<uint64_t>(),
-                                   klo2.as<uint64_t>(), val.as<uint64_t>(), i0.as<uint64_t>());
-            else
-                hipLaunchKernelGGL(k_kmer_emit_range<2>, dim3((unsigned)nblocks), dim3(EN_THREADS), 0, s, e, p.lo, p.hi, (const uint32_t *)wc, p.n, khi.as<uint64_t>(), klo.as<uint64_t>(),
-                                   (uint64_t *)nullptr, val.as<uint64_t>(), i0.as<uint64_t>());
-            uint32_t got = 0;
-            ELBA_HIP(hipMemcpyAsync(&got, wc + nwaves, 4, hipMemcpyDeviceToHost, s));
-            ELBA_HIP(hipStreamSynchronize(s));
-            ELBA_REQUIRE(got == p.n, ELBA_ERR_INTERNAL, "count_kmers: a value-range pass emitted another number of instances than its plan counted");
-            if (p.n > 0) sort_long_kmers(c, words, p.n, wordsrc, val.as<uint64_t>(), i0.as<uint64_t>(), i1.as<uint64_t>(), t0.as<uint64_t>(), t1.as<uint64_t>(), shi, slo, slo2, sval);
-            c.t_a.stop(s);
-            c.t_b.start(s);
-            uint64_t nruns = 0, N = 0, Z = 0;
-            ColumnBase base;
-            base.kid = kid_base; base.ent = (uint32_t)ent_base; base.exact = true;
-            runs_to_columns(c, shi, sval, p.n, nruns, N, Z, slo, slo2, 0, 0, base);
-            c.t_b.stop(s);
-            ms_count += c.t_a.ms(); ms_sort += c.t_b.ms();
-            Staged &g = staged[q];
-            g.kmers.swap(c.rel_kmers); g.lo.swap(c.rel_kmers_lo); g.lo2.swap(c.rel_kmers_lo2); g.counts.swap(c.rel_counts); g.colptr.swap(c.a_colptr);
-            g.csc.swap(c.a_csc); g.kid.swap(c.kid_of_entry);
-            g.N = N; g.Z = Z;
-            kid_base += N; ent_base += Z; distinct += nruns;
-            checkpoint();
-        }
-    }
-    c.ws_a.release(); c.ws_b.release(); c.ws_c.release();
-    // ---- the context's arrays: the staged pieces, concatenated (a pass's pieces of one kind are freed once its copy is done) ----
-    const uint64_t N = kid_base, Z = ent_base;
+};
+
+// one pass: count, scan, emit range, check, sort, columns, stage
+static void run_long_pass(Ctx &c, LongRun &r, const LongPass &p, Staged &g)
+{
+    hipStream_t s = c.stream;
+    LongSortBufs &b = r.bufs;
+    uint32_t *wc = r.wcnt.as<uint32_t>();
+    c.t_a.start(s);
+    ELBA_HIP(hipMemsetAsync(wc + r.nwaves, 0, 4, s));
+    if (r.words == 3) hipLaunchKernelGGL(k_long_pass_count<3>, dim3((unsigned)r.nblocks), dim3(EN_THREADS), 0, s, r.e, p.lo, p.hi, wc);
+    else hipLaunchKernelGGL(k_long_pass_count<2>, dim3((unsigned)r.nblocks), dim3(EN_THREADS), 0, s, r.e, p.lo, p.hi, wc);
+    exclusive_scan_u32(s, wc, wc, (int64_t)r.nwaves + 1, c.ws_scan);      // (p.n < 2^32: the 32-bit scan cannot wrap)
+    if (r.words == 3)
+        hipLaunchKernelGGL(k_kmer_emit_range<3>, dim3((unsigned)r.nblocks), dim3(EN_THREADS), 0, s, r.e, p.lo, p.hi, (const uint32_t *)wc, p.n, b.khi.as<uint64_t>(), b.klo.as<uint64_t>(),
+                           b.klo2.as<uint64_t>(), b.val.as<uint64_t>(), b.i0.as<uint64_t>());
+    else
+        hipLaunchKernelGGL(k_kmer_emit_range<2>, dim3((unsigned)r.nblocks), dim3(EN_THREADS), 0, s, r.e, p.lo, p.hi, (const uint32_t *)wc, p.n, b.khi.as<uint64_t>(), b.klo.as<uint64_t>(),
+                           (uint64_t *)nullptr, b.val.as<uint64_t>(), b.i0.as<uint64_t>());
+    uint32_t got = 0;
+    ELBA_HIP(hipMemcpyAsync(&got, wc + r.nwaves, 4, hipMemcpyDeviceToHost, s));
+    ELBA_HIP(hipStreamSynchronize(s));
+    ELBA_REQUIRE(got == p.n, ELBA_ERR_INTERNAL, "count_kmers: a value-range pass emitted another number of instances than its plan counted");
+    if (p.n > 0) sort_long_kmers(c, r.words, p.n, b);
+    c.t_a.stop(s);
+    c.t_b.start(s);
+    ColumnBase base;
+    base.kid = r.kid_base; base.ent = (uint32_t)r.ent_base; base.exact = true;
+    const Columns col = runs_to_columns(c, b.sorted(), p.n, base);
+    c.t_b.stop(s);
+    r.ms_count += c.t_a.ms(); r.ms_sort += c.t_b.ms();
+    g.kmers.swap(c.rel_kmers); g.lo.swap(c.rel_kmers_lo); g.lo2.swap(c.rel_kmers_lo2); g.counts.swap(c.rel_counts); g.colptr.swap(c.a_colptr);
+    g.csc.swap(c.a_csc); g.kid.swap(c.kid_of_entry);
+    g.N = col.N; g.Z = col.Z;
+    r.kid_base += col.N; r.ent_base += col.Z; r.distinct += col.nruns;
+}
+
+// the context's arrays: the staged pieces, concatenated one kind at a time (a pass's pieces of one kind are freed once their copy is done)
+static void concat_staged(Ctx &c, Staged *staged, size_t npass, int words, uint64_t N, uint64_t Z, PeakMeter &meter)
+{
+    hipStream_t s = c.stream;
     auto concat = [&](DevBuf &dst, size_t bytes, DevBuf Staged::*m, size_t elem, bool per_entry) {
         dst.reserve(bytes);
-        checkpoint();
+        meter.checkpoint();
         uint64_t at = 0;
-        for (size_t q = 0; q < passes.size(); ++q) {
+        for (size_t q = 0; q < npass; ++q) {
             const uint64_t n = per_entry ? staged[q].Z : staged[q].N;
             if (n) ELBA_HIP(hipMemcpyAsync(dst.as<char>() + at * elem, (staged[q].*m).p, (size_t)n * elem, hipMemcpyDeviceToDevice, s));
             at += n;
         }
         ELBA_HIP(hipStreamSynchronize(s));
-        for (size_t q = 0; q < passes.size(); ++q) (staged[q].*m).release();
+        for (size_t q = 0; q < npass; ++q) (staged[q].*m).release();
     };
     concat(c.a_csc, (size_t)(Z + 8) * 8, &Staged::csc, 8, true);      // (+ guard entries, matrix.hip)
     concat(c.kid_of_entry, (size_t)(Z + 8) * 8, &Staged::kid, 8, true);
@@ -1198,16 +1190,112 @@ static bool count_long_kmers_in_passes(Ctx &c, uint64_t I, int words, size_t fre
     concat(c.a_colptr, (size_t)(N + 2) * 4, &Staged::colptr, 4, false);
     const uint32_t Zz = (uint32_t)Z;
     ELBA_HIP(hipMemcpyAsync(c.a_colptr.as<uint32_t>() + N, &Zz, 4, hipMemcpyHostToDevice, s));
+}
+
+// false: one pass takes the input (the caller runs sort_long_one_pass).  free0: the device memory free when the call started.
+static bool count_long_kmers_in_passes(Ctx &c, uint64_t I, int words, size_t free0, Counted &out)
+{
+    hipStream_t s = c.stream;
+    // what the call may use: the memory free when it started, the context's buffers that it overwrites, less 2 GiB for the runtime and small buffers
+    DevBuf *const old[] = {&c.ws_a, &c.ws_b, &c.ws_c, &c.ws_e, &c.ws_f, &c.rel_kmers, &c.rel_kmers_lo, &c.rel_kmers_lo2, &c.rel_counts, &c.a_colptr, &c.a_csc, &c.kid_of_entry};
+    size_t held = 0;
+    for (DevBuf *b : old) held += b->cap;
+    const double avail = (double)free0 + (double)held - 2.0 * (double)(1ull << 30);
+    const LongCapacity cp = plan_long_capacity(I, words, c.cfg.lower, avail, c.opt.kmer_batch_instances > 0 ? (uint64_t)c.opt.kmer_batch_instances : 0xE0000000ull);
+    if (cp.one_pass) return false;
+    char why[256];
+    snprintf(why, sizeof why, "count_kmers: %llu k-mer instances at k = %d leave room for passes of %llu instances only (the columns may need %.1f GB)",
+             (unsigned long long)I, c.cfg.k, (unsigned long long)cp.mem_cap, cp.out_bytes * (double)I / 1e9);
+    ELBA_REQUIRE(cp.fits, ELBA_ERR_OUT_OF_MEMORY, why);
+
+    c.t_total.start(s);
+    LongRun r;
+    r.e = make_enum(c); r.words = words;
+    r.nblocks = (I + EN_PER_BLOCK - 1) / EN_PER_BLOCK; r.nwaves = r.nblocks * (EN_THREADS / 64);
+    const LongHists h = long_histograms(c, r.e, words, r.nblocks, cp.cap);
+    const std::vector<LongPass> passes = cut_long_passes(h.h1, h.heavy.bins, h.h2, I, cp.cap);
+    refuse_long_pass(passes, cp);
+    uint64_t largest = 0;
+    for (const LongPass &p : passes) largest = std::max(largest, p.n);
+    if (c.opt.trace) fprintf(stderr, "[elba] count_kmers: %llu instances of %d-word k-mers in %zu value-range passes (cap %llu, largest %llu)\n", (unsigned long long)I, words,
+                             passes.size(), (unsigned long long)cp.cap, (unsigned long long)largest);
+    c.kmer_passes = (int)passes.size(); c.kmer_largest_pass = (int64_t)largest;
+
+    // (the columns of an earlier call and the workspace sized for another input go first: what is freed is what the passes were planned with)
+    for (DevBuf *b : old) b->release();
+    PeakMeter meter;
+    meter.start();
+    std::unique_ptr<Staged[]> staged(new Staged[passes.size()]);
+    r.bufs.reserve(c, largest, words);
+    r.wcnt.reserve((size_t)(r.nwaves + 1) * 4);
+    for (size_t q = 0; q < passes.size(); ++q) { run_long_pass(c, r, passes[q], staged[q]); meter.checkpoint(); }
+    r.wcnt.release();
+    r.bufs.release(c);      // (the passes' workspace goes before the context's arrays come)
+    concat_staged(c, staged.get(), passes.size(), words, r.kid_base, r.ent_base, meter);
     c.t_total.stop(s);
     ELBA_HIP(hipStreamSynchronize(s));
-    c.kmer_peak_bytes = (int64_t)peak;
-    st.instances = (int64_t)I; st.distinct = (int64_t)distinct; st.reliable = (int64_t)N; st.entries = (int64_t)Z;
-    st.ms_total = c.t_total.ms(); st.ms_count = ms_count; st.ms_sort = ms_sort; st.ms_lookup = 0;
-    c.ndistinct = (int64_t)distinct;
-    c.N = (int64_t)N; c.Z = (int64_t)Z;
-    c.kstats = st;
+    c.kmer_peak_bytes = (int64_t)meter.peak;
+    out.col.nruns = r.distinct; out.col.N = r.kid_base; out.col.Z = r.ent_base;
+    out.ms_count = r.ms_count; out.ms_sort = r.ms_sort;
     return true;
 }
+
+void stage_count_kmers(Ctx &c)
+{
+    enter(c.v, EV_COUNT_KMERS);
+    ELBA_REQUIRE(has(c.v, P_READS), ELBA_ERR_STATE, "count_kmers: no reads (call elba_set_reads)");
+    const int k = c.cfg.k;
+    accepted(c.v, EV_COUNT_KMERS);
+    c.dist_owner = false;
+    c.kmer_path = 0;
+    c.pre = CsrHandoff{};
+    elba_kmer_stats st{};
+    st.nreads = c.nreads;
+
+    // 1. offsets and refusals
+    const InstanceOffsets io = instance_offsets(c);      // (lives to the end of the call: its upload is asynchronous)
+    const uint64_t I = io.I;
+    c.max_read_len = io.max_read_len;      // (kmer_msd.hip and the fused column pass size their position field by it)
+    // (more than 2^32 instances: the two-level partition of kmer_msd.hip counts them in passes over value ranges — 9 <= k <= 31, on 16-byte records from
+    //  k = 18 on —, and so does the sort of k > 31 (count_long_kmers_in_passes); the wide partition's LDS sort of a bucket's entries beyond UPPER = 255
+    //  holds 32-bit places)
+    size_t free0 = 0;
+    if (k > 31) { size_t total = 0; ELBA_HIP(hipMemGetInfo(&free0, &total)); }      // (what bounds the passes of the sort: count_long_kmers_in_passes)
+    if (I >= MSD_PASS_LIMIT && k <= 31) {
+        ELBA_REQUIRE(k >= 9, ELBA_ERR_UNSUPPORTED, "count_kmers: more than 2^32 k-mer instances on one GPU need k >= 9 (the sort of short k-mers holds 32-bit places)");
+        ELBA_REQUIRE(!c.opt.kmer_no_msd, ELBA_ERR_UNSUPPORTED, "count_kmers: more than 2^32 k-mer instances on one GPU need the value partition (option kmer_no_msd is set)");
+        ELBA_REQUIRE(k <= 17 || c.cfg.upper <= 255, ELBA_ERR_UNSUPPORTED, "count_kmers: more than 2^32 k-mer instances on one GPU need UPPER <= 255 for k > 17 (the sort holds 32-bit places)");
+    }
+    c.kmer_passes = 1; c.kmer_peak_bytes = 0;
+    c.kmer_crowded = 0; c.kmer_crowded_small = 0; c.kmer_largest_pass = (int64_t)I; c.kmer_buckets = 0;
+    upload_offsets(c, io);
+
+    // 2. the path: value-range passes or one pass of the multi-word sort; the two-level partition (kmer_msd.hip: k <= 31 on inputs of some size, its
+    //    own statistics); the one-word sort
+    Counted r;
+    if (k > 31) {
+        if (!count_long_kmers_in_passes(c, I, kmer_words(k), free0, r)) r = sort_long_one_pass(c, I, kmer_words(k));
+    } else {
+        if (msd_count_kmers(c, I, st)) { c.kstats = st; done(c.v, EV_COUNT_KMERS); return; }
+        ELBA_REQUIRE(I < MSD_PASS_LIMIT, ELBA_ERR_UNSUPPORTED, "count_kmers: more than 2^32 k-mer instances on one GPU and the two-level partition does not take this input");
+        r = sort_one_word(c, I);
+    }
+
+    // 3. statistics
+    finish_count(c, st, I, r);
+    done(c.v, EV_COUNT_KMERS);
+}
+
+static uint64_t upload_instance_offsets(Ctx &c)
+{
+    const InstanceOffsets io = instance_offsets(c);
+    ELBA_REQUIRE(io.I < 0xFFFFFFF0ull, ELBA_ERR_UNSUPPORTED, "more than 2^32 k-mer instances on one GPU");
+    upload_offsets(c, io);
+    ELBA_HIP(hipStreamSynchronize(c.stream));      // `io` goes out of scope
+    return io.I;
+}
+
+// ---- the distributed build's calls ----
 
 // the owners' boundaries set by elba_dist_set_owner_ranges (one rank: everything is rank 0's; otherwise they must have been set for this world size)
 static OwnerMap owner_map(Ctx &c, int nranks)
@@ -1218,22 +1306,6 @@ static OwnerMap owner_map(Ctx &c, int nranks)
     ELBA_REQUIRE((int)c.owner_upper.size() == nranks, ELBA_ERR_STATE, "owner value ranges not set for this many ranks (call elba_dist_set_owner_ranges)");
     for (int r = 0; r < nranks; ++r) om.upper[r] = c.owner_upper[(size_t)r];
     return om;
-}
-
-static uint64_t upload_instance_offsets(Ctx &c)
-{
-    const int k = c.cfg.k;
-    const int64_t M = c.nreads;
-    std::vector<uint64_t> off((size_t)M + 1);
-    uint64_t I = 0;
-    for (int64_t r = 0; r < M; ++r) { off[(size_t)r] = I; if ((int64_t)c.h_len[(size_t)r] >= k) I += (uint64_t)c.h_len[(size_t)r] - k + 1; }
-    off[(size_t)M] = I;
-    ELBA_REQUIRE(I < 0xFFFFFFF0ull, ELBA_ERR_UNSUPPORTED, "more than 2^32 k-mer instances on one GPU");
-    c.I = (int64_t)I;
-    c.inst_off.reserve((size_t)(M + 1) * 8);
-    ELBA_HIP(hipMemcpyAsync(c.inst_off.p, off.data(), (size_t)(M + 1) * 8, hipMemcpyHostToDevice, c.stream));
-    ELBA_HIP(hipStreamSynchronize(c.stream));      // `off` goes out of scope
-    return I;
 }
 
 void stage_dist_value_histogram(Ctx &c, uint64_t *hist_host, int64_t nbins)
@@ -1463,41 +1535,33 @@ void stage_dist_count_records(Ctx &c, const void *d_rec, int64_t nrec)
     // sorted by (read, pos) afterwards.
     c.ws_a.reserve((size_t)(I + 2) * 8); c.ws_b.reserve((size_t)(I + 2) * 8); c.ws_c.reserve((size_t)(I + 2) * 8); c.ws_d.reserve((size_t)(I + 2) * 8);
     c.ws_e.reserve((size_t)(I + 2) * 4); c.ws_f.reserve((size_t)(I + 2) * 8);
-    uint64_t nruns = 0, N = 0, Z = 0;
+    Columns col;
     const int W = kmer_words(k);
     if (W > 1) {
-        // multi-word k-mers: records of W + 1 words -> word arrays, an index permutation sorted last word first, everything gathered in that order
-        DevBuf w0, w1, w2, val, i0, i1, t0, t1, s2;
-        for (DevBuf *b : {&w0, &w1, &val, &i0, &i1, &t0, &t1}) b->reserve((size_t)(I + 2) * 8);
-        if (W == 3) { w2.reserve((size_t)(I + 2) * 8); s2.reserve((size_t)(I + 2) * 8); }
-        const unsigned nbI = (unsigned)((I + 255) / 256);
-        uint64_t *shi = c.ws_a.as<uint64_t>(), *slo = c.ws_b.as<uint64_t>(), *sval = c.ws_c.as<uint64_t>(), *slo2 = W == 3 ? s2.as<uint64_t>() : nullptr;
+        // multi-word k-mers: records of W + 1 words -> word arrays, sorted as the reads' own k-mers are (sort_long_kmers)
+        LongSortBufs b;
+        b.reserve(c, I, W);
         if (I > 0) {
-            hipLaunchKernelGGL(k_split_records, dim3(nbI), dim3(256), 0, s, c.d_records, I, W + 1, w0.as<uint64_t>(), w1.as<uint64_t>(), W == 3 ? w2.as<uint64_t>() : (uint64_t *)nullptr,
-                               val.as<uint64_t>(), i0.as<uint64_t>());
-            const uint64_t *src[3] = {w0.as<uint64_t>(), w1.as<uint64_t>(), W == 3 ? w2.as<uint64_t>() : nullptr};
-            const uint64_t *perm = sort_words_permutation(c, W, src, I, k, i0.as<uint64_t>(), i1.as<uint64_t>(), t0.as<uint64_t>(), t1.as<uint64_t>());
-            hipLaunchKernelGGL(k_gather_u64, dim3(nbI), dim3(256), 0, s, perm, w0.as<uint64_t>(), I, shi);
-            hipLaunchKernelGGL(k_gather_u64, dim3(nbI), dim3(256), 0, s, perm, w1.as<uint64_t>(), I, slo);
-            if (W == 3) hipLaunchKernelGGL(k_gather_u64, dim3(nbI), dim3(256), 0, s, perm, w2.as<uint64_t>(), I, slo2);
-            hipLaunchKernelGGL(k_gather_u64, dim3(nbI), dim3(256), 0, s, perm, val.as<uint64_t>(), I, sval);
+            hipLaunchKernelGGL(k_split_records, dim3((unsigned)((I + 255) / 256)), dim3(256), 0, s, c.d_records, I, W + 1, b.khi.as<uint64_t>(), b.klo.as<uint64_t>(),
+                               W == 3 ? b.klo2.as<uint64_t>() : (uint64_t *)nullptr, b.val.as<uint64_t>(), b.i0.as<uint64_t>());
+            sort_long_kmers(c, W, I, b);
         }
-        // (the permutation buffers are dead once the gathers are queued: runs_to_columns may use two of them as scratch)
-        runs_to_columns(c, shi, sval, I, nruns, N, Z, slo, slo2);
+        col = runs_to_columns(c, b.sorted(), I);
     } else {
-    if (I > 0) hipLaunchKernelGGL(k_deinterleave, dim3((unsigned)((I + 255) / 256)), dim3(256), 0, s, c.d_records, I, c.ws_a.as<uint64_t>(), c.ws_b.as<uint64_t>());
-    const int where = radix_sort_pairs(s, c.ws_a.as<uint64_t>(), c.ws_b.as<uint64_t>(), c.ws_c.as<uint64_t>(), c.ws_d.as<uint64_t>(), (int64_t)I, 64 - 2 * k, 64, c.ws_sort);
-    const uint64_t *skeys = where ? c.ws_c.as<uint64_t>() : c.ws_a.as<uint64_t>(), *svals = where ? c.ws_d.as<uint64_t>() : c.ws_b.as<uint64_t>();
-    runs_to_columns(c, skeys, svals, I, nruns, N, Z);
+        if (I > 0) hipLaunchKernelGGL(k_deinterleave, dim3((unsigned)((I + 255) / 256)), dim3(256), 0, s, c.d_records, I, c.ws_a.as<uint64_t>(), c.ws_b.as<uint64_t>());
+        const int where = radix_sort_pairs(s, c.ws_a.as<uint64_t>(), c.ws_b.as<uint64_t>(), c.ws_c.as<uint64_t>(), c.ws_d.as<uint64_t>(), (int64_t)I, 64 - 2 * k, 64, c.ws_sort);
+        SortedRuns in;
+        in.keys = where ? c.ws_c.as<uint64_t>() : c.ws_a.as<uint64_t>(); in.vals = where ? c.ws_d.as<uint64_t>() : c.ws_b.as<uint64_t>();
+        col = runs_to_columns(c, in, I);
     }
+    const uint64_t N = col.N, Z = col.Z;
     c.ws_f.reserve((size_t)(Z + 1) * 8);
     if (N > 0)
         hipLaunchKernelGGL(k_sort_columns, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, c.a_colptr.as<uint32_t>(), c.a_csc.as<uint64_t>(), c.ws_f.as<uint64_t>(), N);
     ELBA_HIP(hipStreamSynchronize(s));
-    struct { uint64_t distinct; } hc{nruns};
-    c.I = nrec; c.ndistinct = (int64_t)hc.distinct; c.N = (int64_t)N; c.Z = (int64_t)Z;
-    c.kstats = elba_kmer_stats{};
-    c.kstats.instances = nrec; c.kstats.distinct = (int64_t)hc.distinct; c.kstats.reliable = (int64_t)N; c.kstats.entries = (int64_t)Z;
+    c.I = nrec;
+    elba_kmer_stats st{};
+    publish_counts(c, st, I, col);
     c.dist_owner = true;
     // the owner's columns leave the context's A (which every panel this rank RECEIVES overwrites) for buffers of their own
     c.a_colptr.swap(c.own_colptr); c.a_csc.swap(c.own_csc);
